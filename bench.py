@@ -16,9 +16,16 @@ synthetic spawns / action stream per SURVEY.md §8d.  ``--gpus N`` shards those 
 rank all 4096.  ``--config c2|c3|c5`` selects the other BASELINE configurations for profiling.
 Inputs (state, spawn table, action stream) are resident in HBM when the timed region starts.
 
-After the timed region a short second pass (not timed, not part of ``value``) re-runs the tick
-with a boundary event after every kernel to attribute the time per kernel (``roofline.kernels``)
-and to report obs-build ms/tick.
+A plain run times exactly ``--steps`` ticks after ``--warmup`` and prints the headline line (``value``,
+``ms_per_step``).  ``--full`` adds what takes runs or passes of its own: ``--repeats`` timed regions (median
+reported) with a HIP event pair around every TIMED_EVERY-th launch (``roofline``), the alive-agent figures, a
+short second pass after the timed regions (not timed, not part of ``value``) that re-runs the tick with a
+boundary event after every kernel to attribute the time per kernel (``roofline.kernels``) and to report
+obs-build ms/tick, the measured copy / fill peaks and the CPU baseline.
+
+``--dump-outputs DIR`` writes what the last timed tick handed its caller on rank 0 (``BatchedSim.step``'s dict)
+to ``DIR/<name>.npy`` (see ``dump_outputs``); inputs are seeded, so two builds run with the same arguments can be
+compared array for array.
 """
 import argparse
 import json
@@ -201,27 +208,93 @@ def copy_peak_gbps(device, torch):
     return copy, fill
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_ENVS = 64  # envs sampled when the whole output does not fit the budget
+DUMP_SEED = 42
+
+
+def _dump_array(name, t):
+    """One output tensor as the float array written to disk: float64 / float32 as they are, integers of up to
+    16 bits as float32 and 32-bit ones as float64 (both exact), 64-bit bit masks as float64 [..., 2] = (low
+    32 bits, high 32 bits)."""
+    import torch
+
+    if t.dtype in (torch.float64, torch.float32):
+        return t
+    if t.dtype in (torch.int8, torch.uint8, torch.int16):
+        return t.to(torch.float32)
+    if t.dtype == torch.int32:
+        return t.to(torch.float64)
+    if t.dtype == torch.int64:
+        return torch.stack([t & 0xFFFFFFFF, (t >> 32) & 0xFFFFFFFF], dim=-1).to(torch.float64)
+    raise TypeError(f"{name}: no dump form for {t.dtype}")
+
+
+def dump_outputs(out, directory, num_envs):
+    """Write the arrays of ``out`` (``BatchedSim.step``'s dict: every tensor has the env axis first, the
+    learner block [2, E, N] second) to ``directory/<name>.npy`` in float32 / float64 (``_dump_array``).  All
+    envs when the whole dump fits DUMP_BUDGET_BYTES, else the same fixed, seeded sample of DUMP_ENVS envs (fewer
+    if even those do not fit) in every array; ``env_index.npy`` lists the envs written.  Returns the bytes
+    written."""
+    import torch
+
+    E = num_envs
+    env_axis = {name: 1 if name == "learner" else 0 for name in out}
+    per_env = 0
+    for name, t in out.items():
+        assert t.shape[env_axis[name]] == E, (name, tuple(t.shape))
+        item = 8 if t.dtype in (torch.float64, torch.int32, torch.int64) else 4
+        per_env += t.numel() // E * item * (2 if t.dtype == torch.int64 else 1)
+    k = E if per_env * E <= DUMP_BUDGET_BYTES - 8 * E else min(E, DUMP_ENVS, DUMP_BUDGET_BYTES // (per_env + 8))
+    if k < 1:
+        raise SystemExit(f"--dump-outputs: one env's outputs ({per_env} B) exceed the {DUMP_BUDGET_BYTES} B budget")
+    envs = np.arange(E) if k == E else np.sort(np.random.default_rng(DUMP_SEED).choice(E, size=k, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    written = 0
+    for name, t in list(out.items()) + [("env_index", None)]:
+        if t is None:
+            a = envs.astype(np.float64)
+        else:
+            idx = torch.from_numpy(envs).to(t.device)
+            a = _dump_array(name, t.index_select(env_axis[name], idx)).cpu().numpy()
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+        written += a.nbytes
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of --steps ticks each; the median is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take runs or passes of their own: --repeats timed regions, per-launch "
+                         "events and the roofline, the per-kernel pass, the copy / fill peaks and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed tick's outputs to DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="with --full: timed regions of --steps ticks each, the median is reported (default 3)")
     ap.add_argument("--config", default="c4", choices=sorted(CONFIGS))
     ap.add_argument("--scaling", default="strong", choices=("strong", "weak"),
                     help="strong: the configuration's envs are sharded over the ranks (4096/N each); weak: every rank runs them all")
     ap.add_argument("--envs-per-gpu", type=int, default=None, help="override: this many envs on every rank (weak scaling)")
     ap.add_argument("--vehicles", type=int, default=None)
     ap.add_argument("--scenario", default=None)
-    ap.add_argument("--phase-steps", type=int, default=100)
+    ap.add_argument("--phase-steps", type=int, default=None,
+                    help="with --full: ticks of the per-kernel attribution pass (default 100)")
     ap.add_argument("--launch-strategy", default="auto", choices=("auto", "small", "large", "large_one_lane", "large_teams"),
                     help="how a tick is cut into launches (include/smx.h); auto = by vehicle count")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-worker", type=int, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help=argparse.SUPPRESS)
     ap.add_argument("--launch-check", action="store_true",
                     help="only rendezvous (gloo, no GPU), all-reduce the ranks and print {n_gpus, rank_sum}: the CPU test of the launch path")
     args = ap.parse_args()
+    if not args.full and (args.repeats is not None or args.phase_steps is not None):
+        ap.error("--repeats and --phase-steps shape the --full run: add --full")
+    full = args.full
+    repeats = max(1, 3 if args.repeats is None else args.repeats) if full else 1
+    phase_steps = (100 if args.phase_steps is None else args.phase_steps) if full else 0
     if args.cpu_worker is not None:
         return cpu_worker(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -296,19 +369,21 @@ def main():
         tick(i)
     gather.finish()
     # Timed regions: EXACTLY --steps ticks each, bracketed by barrier + synchronize on both sides, the MAX over
-    # ranks taken per region; --repeats of them back to back, the median one is the reported value (§8d).
-    # HIP events around the launch sequence of every TIMED_EVERY-th step (an event pair costs the stream ~6 us).
+    # ranks taken per region.  A plain run times one region; --full runs --repeats of them back to back and reports
+    # the median one (§8d), with HIP events around the launch sequence of every TIMED_EVERY-th step (an event pair
+    # costs the stream ~6 us) for the roofline.
     region_s = []
-    alive_samples = []  # agents with a vehicle (rows being written), sampled outside the timed regions
+    alive_samples = []  # (--full) agents with a vehicle (rows being written), sampled outside the timed regions
     done_ticks = args.warmup
-    for rep in range(max(1, args.repeats)):
+    for rep in range(repeats):
         torch.cuda.synchronize()
-        alive_samples.append(float(sim.out["active"].sum().item()))
+        if full:
+            alive_samples.append(float(sim.out["active"].sum().item()))
         if world > 1:
             sharding.barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            sampled = i % TIMED_EVERY == 0
+            sampled = full and i % TIMED_EVERY == 0
             if sampled:
                 sim.set_timing(True)
             tick(done_ticks + i)
@@ -324,30 +399,64 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
         region_s.append(el)
-        alive_samples.append(float(sim.out["active"].sum().item()))
+        if full:
+            alive_samples.append(float(sim.out["active"].sum().item()))
         done_ticks += args.steps
-    # alive agents of the whole job (every rank's shard)
-    alive_job = float(np.mean(alive_samples))
-    if world > 1:
-        t = torch.tensor([alive_job], dtype=torch.float64, device=device)
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-        alive_job = float(t.item())
     elapsed = float(np.median(region_s))
-    kernel_ms = sim.read_step_ms()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(sim.out, args.dump_outputs, E)  # the last timed tick's outputs, before anything else runs
 
-    # per-kernel attribution pass (outside the timed region)
-    phase_ms = None
-    if rank == 0 and args.phase_steps > 0:
-        sim.set_timing(2)
-        for i in range(args.phase_steps):
-            sim.step(actions[(done_ticks + i) % ACTION_CYCLE])
-        torch.cuda.synchronize()
-        phase_ms = sim.read_phase_ms().mean(axis=0)
-        sim.set_timing(0)
-
-    copy_peak, fill_peak = copy_peak_gbps(device, torch) if rank == 0 else (None, None)
+    line = None
     if rank == 0:
-        env_steps_per_s = total_envs * args.steps / elapsed
+        sensors = ("waypoints(4x20, lookahead 32)+neighbours(10, r=50 m) obs"
+                   + (", OGM 64x64 @ 50/64 m/px" if cfg.ogm else "")
+                   + (", lidar 100 rays x 20 m" if cfg.lidar is not None else ""))
+        line = {
+            "metric": "aggregate env-steps/s (all agents)",
+            "value": total_envs * args.steps / elapsed,
+            "unit": "env-steps/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak" if weak else "strong",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {
+                "workload": f"scenarios/{scenario}, {total_envs} batched envs x {N} Laner agents, {sensors}, dt=0.1, "
+                            f"auto-reset (BASELINE.json {preset['label']})",
+                "total_envs": total_envs,
+                "envs_per_gpu": E,
+                "vehicles_per_env": N,
+                "launch_form": sim.launch_form(),
+                "sharding": f"{world} rank(s), envs [g*{total_envs}/{world}, (g+1)*{total_envs}/{world}) on GPU g "
+                            f"({E} on rank 0); no data-path collective; per-tick reward/done all_gather (RCCL)",
+            },
+        }
+
+    if full:
+        # alive agents of the whole job (every rank's shard)
+        alive_job = float(np.mean(alive_samples))
+        if world > 1:
+            t = torch.tensor([alive_job], dtype=torch.float64, device=device)
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            alive_job = float(t.item())
+        kernel_ms = sim.read_step_ms()
+
+        # per-kernel attribution pass (outside the timed region)
+        phase_ms = None
+        if rank == 0 and phase_steps > 0:
+            sim.set_timing(2)
+            for i in range(phase_steps):
+                sim.step(actions[(done_ticks + i) % ACTION_CYCLE])
+            torch.cuda.synchronize()
+            phase_ms = sim.read_phase_ms().mean(axis=0)
+            sim.set_timing(0)
+
+        copy_peak, fill_peak = copy_peak_gbps(device, torch) if rank == 0 else (None, None)
+    if full and rank == 0:
         # algorithmic bytes of one launch (this rank's shard): SURVEY.md §8(d) per agent-step x E x N
         kb = sim.kernel_bytes_per_agent_step()
         read_agent, write_agent = sum(r for r, _ in kb.values()), sum(w for _, w in kb.values())
@@ -381,69 +490,44 @@ def main():
             obs_build_ms = float(sum(ms for n_, ms in zip(PHASES, phase_ms) if n_ in ("scan", "ogm", "sensors", "commit")))
             # the dominant kernel of an HBM-bound path is the one that moves the most algorithmic bytes
             dominant = max((k for k in kernels if k != "reset_pass"), key=lambda k: kernels[k]["algorithmic_bytes"])
-        sensors = ("waypoints(4x20, lookahead 32)+neighbours(10, r=50 m) obs"
-                   + (", OGM 64x64 @ 50/64 m/px" if cfg.ogm else "")
-                   + (", lidar 100 rays x 20 m" if cfg.lidar is not None else ""))
-        line = {
-            "metric": "aggregate env-steps/s (all agents)",
-            "value": env_steps_per_s,
-            "unit": "env-steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak" if weak else "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "repeats": {"n": len(region_s), "reported": "median",
-                        "env_steps_per_s": [total_envs * args.steps / t for t in region_s]},
-            "config": {
-                "workload": f"scenarios/{scenario}, {total_envs} batched envs x {N} Laner agents, {sensors}, dt=0.1, "
-                            f"auto-reset (BASELINE.json {preset['label']})",
-                "total_envs": total_envs,
-                "envs_per_gpu": E,
-                "vehicles_per_env": N,
-                # agent-steps of agents that HAVE a vehicle (rows written, controller run): slots whose agent is done
-                # until its env restarts are not counted (value x N would count them)
-                "alive_agent_steps_per_s": alive_job * args.steps / elapsed,
-                "alive_fraction": alive_job / (total_envs * N),
-                "alive_agents_per_tick": {"mean_rank0": alive_mean, "of": E * N, "mean_job": alive_job,
-                                          "note": "an env restarts when all its agents are done; until then the "
-                                                  "agents already done have no vehicle: rows and byte counts "
-                                                  "are those of the alive agents"},
-                "launch_form": sim.launch_form(),
-                "sharding": f"{world} rank(s), envs [g*{total_envs}/{world}, (g+1)*{total_envs}/{world}) on GPU g "
-                            f"({E} on rank 0); no data-path collective; per-tick reward/done all_gather (RCCL)",
-                "obs_build_ms_per_tick": obs_build_ms,
-            },
-            "roofline": {
-                "bound": "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBPS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBPS,
-                "achieved_read": read_agent * agents / avg_kernel_s / 1e9,
-                "achieved_write": write_agent * agents / avg_kernel_s / 1e9,
-                "algorithmic_bytes": {"read": read_agent * agents, "write": write_agent * agents,
-                                      "total": bytes_agent * agents, "per_agent_step": bytes_agent,
-                                      "handoff_not_counted": sim.handoff_bytes_per_agent_step() * agents},
-                "traffic": traffic["bytes_per_step"] if traffic else None,
-                "traffic_read": traffic["read_bytes_per_step"] if traffic else None,
-                "traffic_write": traffic["write_bytes_per_step"] if traffic else None,
-                "traffic_source": traffic["source"] if traffic else None,
-                "measured_copy_peak": copy_peak,
-                "measured_fill_peak": fill_peak,
-                "kernel": "smx_step of rank 0's shard: the tick's launch sequence k_control > k_scan > [k_ogm] > "
-                          "k_waypoints + k_observe [+ k_lidar] (one k_sensors launch on small batches) > k_commit > "
-                          "reset pass; duration = HIP events around the sequence on its stream, median over the "
-                          "sampled launches of the timed regions",
-                "avg_kernel_ms": avg_kernel_s * 1e3,
-                "timed_launches": int(len(kernel_ms)),
-                "dominant_kernel": dominant,
-                "kernels": kernels,
-            },
+        line["repeats"] = {"n": len(region_s), "reported": "median",
+                           "env_steps_per_s": [total_envs * args.steps / t for t in region_s]}
+        line["config"].update({
+            # agent-steps of agents that HAVE a vehicle (rows written, controller run): slots whose agent is done
+            # until its env restarts are not counted (value x N would count them)
+            "alive_agent_steps_per_s": alive_job * args.steps / elapsed,
+            "alive_fraction": alive_job / (total_envs * N),
+            "alive_agents_per_tick": {"mean_rank0": alive_mean, "of": E * N, "mean_job": alive_job,
+                                      "note": "an env restarts when all its agents are done; until then the "
+                                              "agents already done have no vehicle: rows and byte counts "
+                                              "are those of the alive agents"},
+            "obs_build_ms_per_tick": obs_build_ms,
+        })
+        line["roofline"] = {
+            "bound": "hbm",
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBPS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBPS,
+            "achieved_read": read_agent * agents / avg_kernel_s / 1e9,
+            "achieved_write": write_agent * agents / avg_kernel_s / 1e9,
+            "algorithmic_bytes": {"read": read_agent * agents, "write": write_agent * agents,
+                                  "total": bytes_agent * agents, "per_agent_step": bytes_agent,
+                                  "handoff_not_counted": sim.handoff_bytes_per_agent_step() * agents},
+            "traffic": traffic["bytes_per_step"] if traffic else None,
+            "traffic_read": traffic["read_bytes_per_step"] if traffic else None,
+            "traffic_write": traffic["write_bytes_per_step"] if traffic else None,
+            "traffic_source": traffic["source"] if traffic else None,
+            "measured_copy_peak": copy_peak,
+            "measured_fill_peak": fill_peak,
+            "kernel": "smx_step of rank 0's shard: the tick's launch sequence k_control > k_scan > [k_ogm] > "
+                      "k_waypoints + k_observe [+ k_lidar] (one k_sensors launch on small batches) > k_commit > "
+                      "reset pass; duration = HIP events around the sequence on its stream, median over the "
+                      "sampled launches of the timed regions",
+            "avg_kernel_ms": avg_kernel_s * 1e3,
+            "timed_launches": int(len(kernel_ms)),
+            "dominant_kernel": dominant,
+            "kernels": kernels,
         }
         if not args.no_cpu_baseline and world == 1:
             sim.close()
@@ -452,6 +536,7 @@ def main():
             line["cpu_baseline"] = cpu_baseline(net, cm, cfg_kw, args)
         elif world == 1:
             line["cpu_baseline"] = None
+    if rank == 0:
         print(json.dumps(line))
     if sim is not None:
         sim.close()

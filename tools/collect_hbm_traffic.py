@@ -2,9 +2,9 @@
 """Turn two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE — they do not fit one pass on gfx950,
 MI355X_MICROARCH.md "rocprofv3 PMC slots") of ``bench.py`` into profiles/<round>_hbm_traffic.json.
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py ...
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_write -- python3 bench.py ...
-    python tools/collect_hbm_traffic.py --fetch gpurun_out/pmc_fetch --write gpurun_out/pmc_write \
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d profile_out/pmc_fetch -- python3 bench.py --full ... > profile_out/fetch.json
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d profile_out/pmc_write -- python3 bench.py --full ... > profile_out/write.json
+    python tools/collect_hbm_traffic.py --fetch profile_out/pmc_fetch --write profile_out/pmc_write --bench-json profile_out/write.json \
         --workload-key c2:loop:1024x8 --out profiles/r01_hbm_traffic.json
 
 Units and corrections (MI355X_MICROARCH.md §HBM): both counters are reported in KiB; WRITE_SIZE is
