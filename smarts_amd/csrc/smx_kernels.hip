@@ -384,7 +384,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(2, 8))) __launch_bounds__(SMX
     } else {
       // :113-124: (target_speed, lane_change)
       target_speed = (double)act0;
-      lane_change = (int)act1;
+      lane_change = lane_change_of_action(act1);
       lateral_gains_for_speed(target_speed, hg, lg);
     }
     const PathSeeds seed = load_seeds(a, gid, total);  // found by k_scan at this very pose
@@ -588,7 +588,7 @@ __device__ __forceinline__ bool decode_lane_action(const KernelArgs& a, size_t g
   const float act0 = a.actions_f32[gid * 3 + 0], act1 = a.actions_f32[gid * 3 + 1];
   if (act0 != act0) return false;  // NaN = no action
   target_speed = (double)act0;
-  lane_change = (int)act1;
+  lane_change = lane_change_of_action(act1);
   lateral_gains_for_speed(target_speed, hg, lg);
   return true;
 }
@@ -1083,7 +1083,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_fast(const KernelArgs a) 
       } else if (!(act0 != act0)) {  // NaN = no action
         has_action = true;
         target_speed = (double)act0;
-        lane_change = (int)act1;
+        lane_change = lane_change_of_action(act1);
         lateral_gains_for_speed(target_speed, hg, lg);
       }
       CtrlPath path;

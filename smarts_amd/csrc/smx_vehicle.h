@@ -112,6 +112,16 @@ __device__ __forceinline__ double curvature_calculation(const Traj10& t, int off
 }
 
 
+// LaneWithContinuousSpeed's lane change, int(action[1]) (controllers/__init__.py:113-124): a Python int, so
+// np.clip(current + lane_change, 0, n - 1) picks the first / last path for any change past the path count.  A float
+// outside the int range cast straight to int is undefined in C++ (a saturated INT_MAX plus the current index wraps
+// negative), so the change is clamped in double first; +-1024 is far past any path count and leaves the clip's result
+// as it was.  (NaN -> -1024: the reference raises on a NaN or infinite lane change.)
+__device__ __forceinline__ int lane_change_of_action(float act1) {
+  const double v = (double)act1;
+  return v > 1024.0 ? 1024 : (v > -1024.0 ? (int)v : -1024);
+}
+
 // LaneFollowingController.calculate_lateral_gains (lane_following_controller.py:376-437) for an
 // arbitrary target speed (ActionSpaceType.LaneWithContinuousSpeed).  The reference places the poles
 // (-35, -15, -2, -3) of the linearised lateral dynamics with scipy.signal.place_poles; for this

@@ -209,6 +209,34 @@ def compare(dev, ora, tol64=1e-9, tol32=2e-5, where=""):
     return bad
 
 
+def host(out):
+    """Device outputs -> host arrays with the env and vehicle axes flattened into one (env_done left out)."""
+    import torch
+
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy().reshape((-1,) + tuple(v.shape[2:])) for k, v in out.items() if k != "env_done"}
+
+
+def lane_actions(rng, E, N):
+    """Lane action codes: keep_lane with probability 0.8, else uniform over the other three."""
+    return np.where(rng.random((E, N)) < 0.8, 0, rng.integers(1, 4, (E, N))).astype(np.int8)
+
+
+def make(name, E, N, nets, compiled_maps, seed, **cfg_kw):
+    """A device batch and its oracle twin on the same seeded spawns (two episodes of spawn rows); neighbours within
+    50 m unless `cfg_kw` says otherwise."""
+    from smarts_amd.engine import BatchedSim, SimConfig, make_spawns
+
+    cm = compiled_maps(name)
+    kw = dict(neighbors=True, nb_radius=50.0)
+    kw.update(cfg_kw)
+    cfg = SimConfig(num_envs=E, num_vehicles=N, **kw)
+    spawns = make_spawns(cm, E, N, episodes=2, seed=seed)
+    sim = BatchedSim(cm, cfg, spawns=spawns)
+    ob = OracleBatch(nets(name), cm, cfg, spawns[0])
+    return sim, ob, cfg
+
+
 class OracleBatch:
     """E independent oracle envs driven with the same spawns/actions as the device."""
 

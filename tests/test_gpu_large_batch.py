@@ -12,26 +12,7 @@ import parity
 pytestmark = pytest.mark.gpu
 
 
-def _host(out):
-    import torch
-
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy().reshape((-1,) + tuple(v.shape[2:])) for k, v in out.items() if k != "env_done"}
-
-
-def _actions(rng, E, N):
-    return np.where(rng.random((E, N)) < 0.8, 0, rng.integers(1, 4, (E, N))).astype(np.int8)
-
-
-def _make(name, E, N, nets, compiled_maps, seed, **cfg_kw):
-    from smarts_amd.engine import BatchedSim, SimConfig, make_spawns
-
-    cm = compiled_maps(name)
-    cfg = SimConfig(num_envs=E, num_vehicles=N, neighbors=True, nb_radius=50.0, **cfg_kw)
-    spawns = make_spawns(cm, E, N, episodes=2, seed=seed)
-    sim = BatchedSim(cm, cfg, spawns=spawns)
-    ob = parity.OracleBatch(nets(name), cm, cfg, spawns[0])
-    return sim, ob, cfg
+_host, _actions, _make = parity.host, parity.lane_actions, parity.make
 
 
 @pytest.mark.parametrize("name,E,N,T,seed,extra", [
