@@ -16,10 +16,11 @@
 //                                         collisions, neighbours, ego block, accelerometer, driven
 //                                         path, events, done
 //                                       lidar / OGM roles  1 wavefront / vehicle
-//   k_commit    1 lane / vehicle        new flags (teardown), dones["__all__"], auto-reset respawn
+//   k_tail      1 lane / vehicle        new flags (teardown), dones["__all__"], auto-reset respawn,
+//                                       the new vehicles' grid tiles, the next tick's alive list
 //
-// followed, for envs whose episode ended under auto_reset (parallel_env.py:303-309), by k_scan /
-// k_sensors / k_commit restricted to the re-created vehicles.  Above 16384 vehicles every role is
+// followed, for envs whose episode ended under auto_reset (parallel_env.py:303-309), by k_first: scan /
+// sensors / commit restricted to the re-created vehicles.  Above 16384 vehicles every role is
 // launched on its own (k_waypoints, k_observe, k_lidar, k_ogm; see enqueue()).  Envs are independent
 // (reference: one process per env, parallel_env.py:96-122): no inter-workgroup communication.
 #include <hip/hip_runtime.h>
@@ -85,6 +86,7 @@ struct KernelArgs {
   // index = vehicle).  The per-vehicle team kernels then run over full wavefronts however many agents are gone.
   const int32_t* alive_list;
   const int32_t* alive_count;
+  int alive_segmented;      // 1: the list k_tail built at the end of the last tick (eight segments, launch_vehicle)
   int32_t* status;          // library-owned device word of SMX_DEVICE_* bits, read and cleared by smx_sync
   // library-owned, kept from tick to tick: what the scan's seeded searches start from (smx_scan.h).  Null: unseeded.
   double* seeds_carry;      // [4][E*N]: pose (x, y) the seeds half last ran at, d2 of its 10th nearest and of its nearest lanepoint (< 0: none)
@@ -99,12 +101,26 @@ enum { SMX_DEVICE_BAD_LANE_ACTION = 1 };  // a Lane action code outside -1..3 wa
 
 #define SF(field) a.st.f64[(size_t)(field) * total + gid]
 
+// The alive list k_tail builds for the next tick is eight segments, one counter each (2 048 workgroups adding to one
+// counter would queue behind each other: 28 us for 2 048 atomics on one word at 131 k vehicles).  Vehicle g belongs to
+// segment (g / 64) % 8 — the workgroups of 64-vehicle env groups then add to their own XCD's counter — and list
+// position i holds entry ((i / 512) * 64 + i % 64) of segment (i / 64) % 8: a wavefront's 64 positions are 64
+// consecutive entries of one segment, and a segment has exactly as many positions below E*N as it can have entries.
+#define SMX_SEG_STRIDE 32  // ints between two segment counters (a cache line each)
+__device__ __forceinline__ size_t seg_position(const size_t seg, const size_t off) {
+  return ((off >> 6) << 9) | (seg << 6) | (off & 63);
+}
+
 // The vehicle that team (or lane) i of a per-vehicle launch works on; `total` = none (i is past the last one).
 __device__ __forceinline__ size_t launch_vehicle(const KernelArgs& a, size_t i, size_t total) {
   if (a.alive_list == nullptr) return i < total ? i : total;
   // (the entry is loaded beside the count, not behind it: one round trip; entries past the count are old vehicle
   // numbers or zeros, in range either way)
   const int32_t entry = a.alive_list[i < total ? i : total - 1];
+  if (a.alive_segmented) {
+    const size_t off = ((i >> 9) << 6) | (i & 63);
+    return (i < total && off < (size_t)a.alive_count[SMX_SEG_STRIDE * ((i >> 6) & 7)]) ? (size_t)entry : total;
+  }
   return i < (size_t)*a.alive_count ? (size_t)entry : total;
 }
 
@@ -847,14 +863,6 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_paths(const KernelArgs a,
   const size_t total = (size_t)a.cfg.num_envs * a.cfg.num_vehicles;
   control_paths_for<SPACE>(a, ho, launch_vehicle(a, ((size_t)blockIdx.x * SMX_BLOCK + threadIdx.x) / SMX_WP_LANES, total), knot_scratch + threadIdx.x);
 }
-template <int SPACE>
-__global__ void __launch_bounds__(SMX_BLOCK) k_control_paths_listed(const KernelArgs a, const CtrlHandoff ho) {
-  __shared__ int knot_scratch[SMX_MAX_KNOTS * SMX_BLOCK];
-  constexpr int VPB = SMX_BLOCK / SMX_WP_LANES;
-  const int count = *a.slow_count;
-  for (int i = (int)blockIdx.x * VPB + (int)threadIdx.x / SMX_WP_LANES; i < count; i += (int)gridDim.x * VPB)
-    control_paths_for<SPACE>(a, ho, (size_t)a.slow_list[i], knot_scratch + threadIdx.x);
-}
 
 // Control law + vehicle dynamics, one lane per vehicle (see k_control_paths).  Every action space; the
 // lane-following ones read the wanted path from the hand-off.
@@ -971,11 +979,23 @@ template <int SPACE>
 __global__ void __launch_bounds__(SMX_BLOCK) k_control_law(const KernelArgs a, const CtrlHandoff ho) {
   control_law_for<SPACE>(a, ho, (size_t)blockIdx.x * SMX_BLOCK + threadIdx.x);
 }
+// The vehicles k_control_fast left on its slow list (large batches), a fixed grid striding the list, whose length is only
+// known on the device: sixteen vehicles a round, their candidate paths by teams of four lanes, then, behind a barrier,
+// their control law + dynamics on sixteen lanes, the wanted path passed through the hand-off in device memory.  (One
+// launch: the list is under 1 % of the vehicles on a map whose lanes do not split, and a second launch over it was
+// a launch boundary on the tick's longest chain.)
 template <int SPACE>
-__global__ void __launch_bounds__(SMX_BLOCK) k_control_law_listed(const KernelArgs a, const CtrlHandoff ho) {
-  const int count = *a.slow_count;  // the vehicles k_control_fast left to k_control_paths_listed (see there)
-  for (int i = (int)blockIdx.x * SMX_BLOCK + (int)threadIdx.x; i < count; i += (int)gridDim.x * SMX_BLOCK)
-    control_law_for<SPACE>(a, ho, (size_t)a.slow_list[i]);
+__global__ void __launch_bounds__(SMX_BLOCK) k_control_listed(const KernelArgs a, const CtrlHandoff ho) {
+  __shared__ int knot_scratch[SMX_MAX_KNOTS * SMX_BLOCK];
+  constexpr int VPB = SMX_BLOCK / SMX_WP_LANES;
+  const int count = *a.slow_count;
+  for (int i0 = (int)blockIdx.x * VPB; i0 < count; i0 += (int)gridDim.x * VPB) {  // (uniform in the workgroup)
+    const int i = i0 + (int)threadIdx.x / SMX_WP_LANES;
+    if (i < count) control_paths_for<SPACE>(a, ho, (size_t)a.slow_list[i], knot_scratch + threadIdx.x);
+    __threadfence_block();
+    __syncthreads();
+    if ((int)threadIdx.x < VPB && i0 + (int)threadIdx.x < count) control_law_for<SPACE>(a, ho, (size_t)a.slow_list[i0 + threadIdx.x]);
+  }
 }
 
 // =================================================================================
@@ -3606,7 +3626,7 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
     flags &= ~SMX_F_FIRST;
     if (done) flags &= ~SMX_F_ALIVE;
     a.st.steps[gid] = steps;
-    new_flags = flags;  // applied by k_commit: the waypoints role of this launch still reads the old word
+    new_flags = flags;  // applied by k_tail's commit: the waypoints role of this launch still reads the old word
     o.active[gid] = done ? 0 : 1;
     if (!a.keep_reward_done) {
       o.done[gid] = done ? 1 : 0;
@@ -3685,13 +3705,15 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
 }
 
 // =================================================================================
-// k_commit: the end of a pass, after every sensor role has read the old flags: apply the flags the
+// commit role (k_tail, k_first): the end of a pass, after every sensor role has read the old flags: apply the flags the
 // observe role decided (teardown of done agents, smarts.py:314, 329-363), per-env done count and
 // dones["__all__"] (hiway_env.py:258-261), and the auto-reset respawn (parallel_env.py:303-309) —
 // the reset pass that follows builds the first observations of the restarted envs.
 // One thread per vehicle, whole envs per workgroup.
 // =================================================================================
-__device__ __forceinline__ void commit_role(const KernelArgs& a, const int block) {
+// (`tick`: the tick's commit — every agent's teardown, done counts, auto-reset respawn; else the reset pass's, which
+// only applies the new vehicles' flags)
+__device__ __forceinline__ void commit_role(const KernelArgs& a, const int block, const bool tick) {
   __shared__ int env_new_done[SMX_BLOCK];
   __shared__ int env_respawn[SMX_BLOCK];
   __shared__ int env_first_alive[SMX_BLOCK];
@@ -3720,7 +3742,7 @@ __device__ __forceinline__ void commit_role(const KernelArgs& a, const int block
   }
   __syncthreads();
   if (valid && slot == 0) {
-    if (!a.first_only) {
+    if (tick) {
       int dcnt = a.st.env_done_count[env] + env_new_done[env_local];
       a.st.env_done_count[env] = dcnt;
       a.st.env_ticks[env] = a.st.env_ticks[env] + 1;
@@ -3757,7 +3779,6 @@ __device__ __forceinline__ void commit_role(const KernelArgs& a, const int block
   }
 }
 
-__global__ void __launch_bounds__(SMX_BLOCK) k_commit(const KernelArgs a) { commit_role(a, (int)blockIdx.x); }
 
 // =================================================================================
 // OGM role: occupancy grid map sensor (OGMSensor, sensors.py:719-758): one wavefront per observing
@@ -4219,7 +4240,7 @@ __device__ __forceinline__ void lidar_role(const KernelArgs& a, const int block)
 // waypoint paths + trip meter (4 lanes / vehicle), the rest of Sensors.observe (1 lane / vehicle,
 // whole envs per workgroup) and, if enabled, lidar and OGM (1 wavefront / vehicle each).  The roles read the
 // same pose / flags / facts and write disjoint outputs, so they overlap in time; the flags word
-// itself only changes in k_commit.
+// itself only changes in the commit role.
 // =================================================================================
 __global__ void __launch_bounds__(SMX_BLOCK) k_sensors(const KernelArgs a) {
   const int b = (int)blockIdx.x;
@@ -4238,22 +4259,20 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_sensors(const KernelArgs a) {
 // k_first: the reset pass (first observations of re-created vehicles) as ONE launch.  A workgroup
 // owns the envs of one observe-role group and runs scan -> sensors -> commit for their new vehicles
 // itself, phase after phase; results pass between phases through global memory behind a fence and a
-// barrier.  Almost always no env of the group has restarted and the workgroup leaves at once, so an
-// auto-reset tick pays for one empty launch instead of three.  (OGM tiles need dynamic LDS and keep
-// their own launch.)
+// barrier.  It runs over the env groups k_tail listed (new vehicles in them); OGM / DAGM tiles need
+// dynamic LDS and come from k_tail.
 // =================================================================================
 // (eight wavefronts: the (vehicle, scan half) pairs of a restarted 64-vehicle env are 128 teams of eight lanes — four
 // rounds of ~55 us each in a workgroup of 256, the largest piece of C5's reset pass; the waypoint teams, four lanes a
 // vehicle, fit the first 256 threads, whose knot scratch is all the LDS the workgroup may have)
 #define SMX_FIRST_BLOCK 512
 #define SMX_FIRST_WP_THREADS 256
-__global__ void __launch_bounds__(SMX_FIRST_BLOCK) k_first(const KernelArgs a) {
+__device__ __forceinline__ void first_role(const KernelArgs& a, const int block) {
   __shared__ int knot_scratch[SMX_MAX_KNOTS * SMX_FIRST_WP_THREADS];
   const smx_config& c = a.cfg;
   const MapDev& m = a.map;
   const int n_veh = c.num_vehicles;
   const int epb = SMX_BLOCK / n_veh;  // the env groups are those of the observe / commit roles
-  const int block = (int)blockIdx.x;
   const size_t total = (size_t)c.num_envs * n_veh;
   const size_t g0 = (size_t)block * epb * n_veh;
   const size_t g1 = min(total, g0 + (size_t)epb * n_veh);
@@ -4320,7 +4339,7 @@ __global__ void __launch_bounds__(SMX_FIRST_BLOCK) k_first(const KernelArgs a) {
   __syncthreads();
   // ---- commit
   SMX_TSTAMP(tk4);
-  commit_role(a, block);
+  commit_role(a, block, false);
   SMX_TSTAMP(tk5);
   SMX_TACC_ALL(60, tk4, tk5);
   SMX_TACC_ALL(61, tk0, tk5);
@@ -4339,6 +4358,15 @@ __global__ void __launch_bounds__(SMX_FIRST_BLOCK) k_first(const KernelArgs a) {
       }
     }
   }
+}
+
+// The reset pass over the env groups k_tail found new vehicles in (`groups`, `*n_groups` of them): workgroup i takes
+// entry i, and the rest leave after one scalar load instead of a flags load and a barrier count.  (A fixed grid
+// striding the list would launch eight times fewer workgroups, but the loop around the role spilled 112 registers of
+// its 256: 436 bytes of scratch a lane.)
+__global__ void __launch_bounds__(SMX_FIRST_BLOCK) k_first(const KernelArgs a, const int32_t* groups, const int32_t* n_groups) {
+  if ((int)blockIdx.x >= *n_groups) return;
+  first_role(a, groups[blockIdx.x]);
 }
 
 // single-role launches: large batches (each role then keeps its own register / LDS footprint and
@@ -4489,24 +4517,89 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_road_waypoints(const KernelArgs a
   for (int p = min(n_paths, P); p < P; ++p) o.rw_count[lane_row * (size_t)P + p] = 0;
 }
 
-// The reset pass of the grid sensors: almost no vehicle is new in a given tick, and one workgroup
-// per vehicle that only finds that out costs ~120 us at 131 k vehicles.  Here a workgroup looks at
-// the flags of 64 vehicles with one load and a ballot, and builds tiles only for the new ones.
-template <bool DAGM>
-__global__ void __launch_bounds__(SMX_BLOCK) k_grid_first(const KernelArgs a) {
-  const size_t total = (size_t)a.cfg.num_envs * a.cfg.num_vehicles;
-  const size_t g0 = (size_t)blockIdx.x * SMX_BLOCK;
-  const size_t gid = g0 + threadIdx.x;
-  const int f = gid < total ? a.st.flags[gid] : 0;
-  unsigned long long fresh = __ballot((f & SMX_F_ALIVE) && (f & SMX_F_FIRST) && !(f & SMX_F_SOCIAL));
-  while (fresh != 0ull) {  // uniform
-    const int j = __ffsll((long long)fresh) - 1;
-    fresh &= fresh - 1ull;
-    if (DAGM)
-      dagm_role(a, (int)(g0 + j));
-    else
-      ogm_role(a, (int)(g0 + j));
-    __syncthreads();  // the tile is reused
+// =================================================================================
+// k_tail: the end of every pass, one wavefront per env group (those of the observe role), in one launch:
+//  - the tick's commit (commit_role: teardown, done counts, auto-reset respawn);
+//  - the OGM / DAGM tiles of the group's new vehicles (respawned just now, or by k_reset), one after the other — almost
+//    no group has any, and a group looks at its flags with one load and a ballot;
+//  - the env groups with new vehicles, listed for k_first (the reset pass), one atomic per such group;
+//  - large batches: the next tick's alive list (seg_position), built here instead of by a k_alive_list launch at the
+//    head of that tick.  The reset pass does not change SMX_F_ALIVE (a new vehicle is never done on its first
+//    observation), so the flags are final here; the next tick's list counter, slow-list counters and reset-group
+//    counter are zeroed by workgroup 0.
+// (k_first stays a launch of its own: its 512 threads at 256 registers run one workgroup per CU, and the commit of
+// every group would wait behind that occupancy — round 2 measured the commit inside the reset pass: no gain)
+// =================================================================================
+struct TailArgs {
+  int commit;              // the tick's commit (0: smx_reset, which has no tick)
+  int grids;               // OGM / DAGM tiles of the new vehicles
+  int32_t* groups;         // env groups with new vehicles (for k_first)
+  int32_t* n_groups;
+  int32_t* n_groups_next;  // zeroed: the next pass's counter
+  int32_t* list;           // the next tick's alive list (null: not built here)
+  int32_t* seg_count;      // its eight counters, SMX_SEG_STRIDE apart
+  int32_t* seg_next;       // zeroed: the eight counters the list after it is built with
+  int32_t* flat_next;      // zeroed: k_alive_list's counter of the next tick (should that tick build its list itself)
+  int32_t* slow_next;      // zeroed: the next tick's four slow-list counters
+};
+
+__global__ void __launch_bounds__(SMX_BLOCK) k_tail(const KernelArgs a, const TailArgs t) {
+  const smx_config& c = a.cfg;
+  const int block = (int)blockIdx.x;
+  const int n_veh = c.num_vehicles;
+  const int epb = SMX_BLOCK / n_veh;
+  const size_t total = (size_t)c.num_envs * n_veh;
+  const size_t g0 = (size_t)block * epb * n_veh;
+  const size_t g1 = min(total, g0 + (size_t)epb * n_veh);
+  const int lane = (int)threadIdx.x;
+  const size_t gid = g0 + lane;
+  if (t.commit) commit_role(a, block, true);  // (lane l commits vehicle g0 + l: its flags word is read back below)
+  if (block == 0 && lane == 0) {
+    *t.n_groups_next = 0;
+    if (t.list) {
+      for (int k = 0; k < 8; ++k) t.seg_next[SMX_SEG_STRIDE * k] = 0;
+      *t.flat_next = 0;
+      for (int k = 0; k < 4; ++k) t.slow_next[k] = 0;
+    }
+  }
+  const int f = gid < g1 ? a.st.flags[gid] : 0;
+  const bool alive = (f & SMX_F_ALIVE) != 0;
+  if (__ballot(alive && (f & SMX_F_FIRST)) != 0ull) {  // (uniform)
+    if (lane == 0) t.groups[atomicAdd(t.n_groups, 1)] = block;
+    if (t.grids) {
+      unsigned long long fresh = __ballot(alive && (f & SMX_F_FIRST) && !(f & SMX_F_SOCIAL));
+      while (fresh != 0ull) {
+        const int j = __ffsll((long long)fresh) - 1;
+        fresh &= fresh - 1ull;
+        if (c.sensors & SMX_SENSOR_OGM) {
+          ogm_role(a, (int)(g0 + j));
+          __syncthreads();  // the tile is reused
+        }
+        if (c.sensors & SMX_SENSOR_DAGM) {
+          dagm_role(a, (int)(g0 + j));
+          __syncthreads();
+        }
+      }
+    }
+  }
+  if (t.list) {
+    // the group's vehicles lie in at most two segments (of 64 vehicles: one)
+    const size_t s0 = (g0 >> 6) & 7;
+    const size_t seg = (gid >> 6) & 7;
+    const unsigned long long m0 = __ballot(alive && seg == s0), m1 = __ballot(alive && seg != s0);
+    int b0 = 0, b1 = 0;
+    if (lane == 0) {
+      if (m0) b0 = atomicAdd(t.seg_count + SMX_SEG_STRIDE * s0, __popcll(m0));
+      if (m1) b1 = atomicAdd(t.seg_count + SMX_SEG_STRIDE * (((g1 - 1) >> 6) & 7), __popcll(m1));
+    }
+    b0 = __shfl(b0, 0);
+    b1 = __shfl(b1, 0);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (alive) {
+      const bool first_seg = seg == s0;
+      const size_t off = (size_t)(first_seg ? b0 : b1) + __popcll((first_seg ? m0 : m1) & below);
+      t.list[seg_position(seg, off)] = (int32_t)gid;
+    }
   }
 }
 __global__ void __launch_bounds__(SMX_BLOCK) k_waypoints(const KernelArgs a) { waypoints_role(a, (int)blockIdx.x); }
@@ -4672,6 +4765,12 @@ struct smx_handle_s {
   double heading_gain_pos, lateral_gain_pos;
   double nb_d2_max;
   int slow_blocks;  // grid of the slow lists' kernels (smx_load_map)
+  // the alive list k_tail built for the next tick: counters of parity `seg_parity` (the other parity's are zero), built
+  // from the flags of `list_state`; the next large-form tick takes it instead of launching k_alive_list
+  bool list_ready;
+  int seg_parity;
+  smx_state list_state;
+  int group_parity;  // k_tail's counter of env groups with new vehicles (the other one is zero)
   bool map_junctions;  // lanes of the map split (some lanepoint has several successors)
   double dagm_reach;  // half the widest lane width of the loaded map
   int debug_skip;
@@ -4741,6 +4840,22 @@ extern "C" uint64_t smx_struct_size(int which) {
   }
 }
 
+// alive_blob: [E*N] alive list, k_alive_list's two counters, k_tail's [2][8] segment counters and [2] counters of env
+// groups with new vehicles (SMX_SEG_STRIDE apart), the list of those groups
+struct AliveLayout {
+  size_t flat, seg, group_count, groups, size;
+};
+static AliveLayout alive_layout(const smx_config& c) {
+  AliveLayout l;
+  const size_t total = (size_t)c.num_envs * c.num_vehicles;
+  l.flat = total;
+  l.seg = (total + 2 + SMX_SEG_STRIDE - 1) / SMX_SEG_STRIDE * SMX_SEG_STRIDE;
+  l.group_count = l.seg + 2 * 8 * SMX_SEG_STRIDE;
+  l.groups = l.group_count + 2 * SMX_SEG_STRIDE;
+  l.size = l.groups + (size_t)c.num_envs;  // (at least one env a group)
+  return l;
+}
+
 static int create_impl(const smx_config* cfg, int device, smx_handle* out) {
   smx_handle h = new (std::nothrow) smx_handle_s();
   if (!h) return SMX_ERR_NOMEM;
@@ -4757,6 +4872,10 @@ static int create_impl(const smx_config* cfg, int device, smx_handle* out) {
   h->slow_blob = nullptr;
   h->pending_blob = nullptr;
   h->alive_parity = 0;
+  h->list_ready = false;
+  h->seg_parity = 0;
+  h->list_state = smx_state{};
+  h->group_parity = 0;
   h->knots = KnotLists{};
   h->ctrl_blob = nullptr;
   h->ctrl = CtrlHandoff{nullptr, nullptr};
@@ -5022,8 +5141,8 @@ extern "C" int smx_load_map(smx_handle h, const smx_map_tables* t) {
   PTR(sg_off, int32_t);
   PTR(sg_rec, smx_seg_rec);
 #undef PTR
-  if (!h->alive_blob) {  // the tick's alive list (large batches) + its two counters
-    const size_t n = (size_t)h->cfg.num_envs * h->cfg.num_vehicles + 2;
+  if (!h->alive_blob) {  // the tick's alive list (large batches) + its counters, the env groups with new vehicles (alive_layout)
+    const size_t n = alive_layout(h->cfg).size;
     SMX_HIP(hipMalloc((void**)&h->alive_blob, n * sizeof(int32_t)));
     SMX_HIP(hipMemset(h->alive_blob, 0, n * sizeof(int32_t)));
   }
@@ -5415,6 +5534,7 @@ static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const floa
   a.status = h->status_dev;
   a.alive_list = nullptr;
   a.alive_count = nullptr;
+  a.alive_segmented = 0;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
   a.slow_list = nullptr;
   a.slow_count = nullptr;
@@ -5495,7 +5615,7 @@ static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const floa
     // Large batches, no per-kernel timing asked: the grid maps and the lidar (which read poses only) leave on
     // side stream 0 at once and overlap the scan — kernels bound by their own write stream beside one bound by
     // arithmetic and load latency; observe goes to side stream 1 after the scan, the waypoint kernels stay on
-    // the caller's stream; all are joined before k_commit.
+    // the caller's stream; all are joined before k_tail.
     const bool fork = !small_batch && !phased && h->side_ready;
     hipStream_t s_grid = stream, s_obs = stream;
     KernelArgs kf = k, ks = k, kwp = k;  // (kwp: the waypoint kernels, which pass over the slow chain's vehicles)
@@ -5582,7 +5702,8 @@ static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const floa
         hipLaunchKernelGGL((k_scan_half<0, false, SMX_TEAM>), dim3(wide_blocks), dim3(SMX_BLOCK), 0, s_obs, k);
       else
         hipLaunchKernelGGL(k_scan_half<0>, dim3(half_blocks), dim3(SMX_BLOCK), 0, s_obs, k);  // (the facts half seeds no path)
-      // (holding the grid kernels back as well was slower: 0.81 -> 0.85 ms; they overlap the seeds half)
+      // (holding the grid kernels back as well was slower: 0.81 -> 0.85 ms; they overlap the seeds half.  So was one fork
+      // event after the seeds half for the grid kernels too, one record less on the caller's stream: C4 0.556 -> 0.605 ms)
     } else if (scan_split) {
       if (routed)
         hipLaunchKernelGGL((k_scan<true, true>), dim3(scan_blocks), dim3(SMX_BLOCK), 0, stream, k);
@@ -5644,21 +5765,29 @@ static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const floa
       hipLaunchKernelGGL(k_road_waypoints, dim3((unsigned)((total * SMX_RW_LANE_CAP + SMX_BLOCK - 1) / SMX_BLOCK)), dim3(SMX_BLOCK), 0,
                          stream, k);
     if (phases && phased) (void)hipEventRecord(ph[SMX_PHASE_SENSORS + 1], stream);
-    hipLaunchKernelGGL(k_commit, dim3(obs_blocks), dim3(SMX_BLOCK), 0, stream, k);
-    if (phases && phased) (void)hipEventRecord(ph[SMX_PHASE_COMMIT + 1], stream);
   };
   // the LDS-path form of k_control fits one wavefront per SIMD: only while the batch needs no more
   const bool lds_path = small_batch && total * SMX_WP_LANES <= (size_t)1024 * 64;
   if (is_step && c.num_social > 0 && c.social_model == SMX_SOCIAL_IDM)
     hipLaunchKernelGGL(k_social, dim3(veh_blocks), dim3(SMX_BLOCK), 0, stream, a);
   const bool two_launch_control = is_step && !small_batch && h->ctrl_blob;
+  const AliveLayout al = alive_layout(c);
+  // k_tail builds the next tick's alive list unless k_social moves vehicles (and can end them) ahead of the list
+  const bool build_list = !small_batch && h->alive_blob && h->slow_blob && !(c.num_social > 0 && c.social_model == SMX_SOCIAL_IDM);
   if (is_step && !small_batch && h->alive_blob) {
-    int32_t* counters = h->alive_blob + total;
+    int32_t* counters = h->alive_blob + al.flat;
     int32_t* slow_counters = h->slow_blob + 4 * total;  // [parity][4]: facts, seeds, control, waypoint rows
-    hipLaunchKernelGGL(k_alive_list, dim3((unsigned)((total + SMX_ALIVE_BLOCK - 1) / SMX_ALIVE_BLOCK)), dim3(SMX_ALIVE_BLOCK), 0, stream, a, h->alive_blob, counters + h->alive_parity,
-                       counters + (h->alive_parity ^ 1), slow_counters + 4 * (h->alive_parity ^ 1));
-    a.alive_list = h->alive_blob;
-    a.alive_count = counters + h->alive_parity;
+    if (h->list_ready && std::memcmp(&h->list_state, st, sizeof(smx_state)) == 0) {
+      // the list the last pass's k_tail built from these flags; it zeroed this tick's slow-list counters too
+      a.alive_list = h->alive_blob;
+      a.alive_count = h->alive_blob + al.seg + (size_t)8 * SMX_SEG_STRIDE * (h->seg_parity ^ 1);
+      a.alive_segmented = 1;
+    } else {
+      hipLaunchKernelGGL(k_alive_list, dim3((unsigned)((total + SMX_ALIVE_BLOCK - 1) / SMX_ALIVE_BLOCK)), dim3(SMX_ALIVE_BLOCK), 0, stream, a, h->alive_blob, counters + h->alive_parity,
+                         counters + (h->alive_parity ^ 1), slow_counters + 4 * (h->alive_parity ^ 1));
+      a.alive_list = h->alive_blob;
+      a.alive_count = counters + h->alive_parity;
+    }
     // One lane per vehicle + slow lists where the slow lists stay short: a map whose lanes never split (loop: under 1 %
     // of the vehicles).  Where lanes branch and cross, a third of the vehicles would take the lists' serial forms
     // (minicity, 262 144 vehicles: 1.40 ms a tick against 0.9x with round 2's team kernels for everybody), so those
@@ -5679,8 +5808,7 @@ static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const floa
       case SMX_ACTION_SPACE_LANE:
         if (fast_scan && h->slow_blob) {  // one lane per vehicle; the rest through the slow list (k_control_fast)
           hipLaunchKernelGGL(k_control_fast<SMX_ACTION_SPACE_LANE>, dim3(veh_blocks), dim3(SMX_BLOCK), 0, stream, ac);
-          hipLaunchKernelGGL(k_control_paths_listed<SMX_ACTION_SPACE_LANE>, dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, stream, ac, ho);
-          hipLaunchKernelGGL(k_control_law_listed<SMX_ACTION_SPACE_LANE>, dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, stream, ac, ho);
+          hipLaunchKernelGGL(k_control_listed<SMX_ACTION_SPACE_LANE>, dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, stream, ac, ho);
         } else {
           hipLaunchKernelGGL(k_control_paths<SMX_ACTION_SPACE_LANE>, dim3(wp_blocks), dim3(SMX_BLOCK), 0, stream, a, ho);
           hipLaunchKernelGGL(k_control_law<SMX_ACTION_SPACE_LANE>, dim3(veh_blocks), dim3(SMX_BLOCK), 0, stream, a, ho);
@@ -5689,8 +5817,7 @@ static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const floa
       case SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED:
         if (fast_scan && h->slow_blob) {
           hipLaunchKernelGGL(k_control_fast<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED>, dim3(veh_blocks), dim3(SMX_BLOCK), 0, stream, ac);
-          hipLaunchKernelGGL(k_control_paths_listed<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED>, dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, stream, ac, ho);
-          hipLaunchKernelGGL(k_control_law_listed<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED>, dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, stream, ac, ho);
+          hipLaunchKernelGGL(k_control_listed<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED>, dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, stream, ac, ho);
         } else {
           hipLaunchKernelGGL(k_control_paths<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED>, dim3(wp_blocks), dim3(SMX_BLOCK), 0, stream, a, ho);
           hipLaunchKernelGGL(k_control_law<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED>, dim3(veh_blocks), dim3(SMX_BLOCK), 0, stream, a, ho);
@@ -5736,36 +5863,60 @@ static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const floa
     SMX_PHASE_END(SMX_PHASE_CONTROL);
     observation_pass(a, true);
   }
-  if (!is_step || c.auto_reset) {
+  {
+    // the end of the pass: k_tail (the tick's commit, the new vehicles' grid tiles, the env groups with new vehicles,
+    // the next tick's alive list), then the reset pass over those groups (first observations of the new vehicles)
+    const bool reset_pass = !is_step || c.auto_reset;  // (in a step, k_tail's commit respawns the envs that ended)
     KernelArgs r = a;
     r.alive_list = nullptr;
     r.alive_count = nullptr;
+    r.alive_segmented = 0;
     r.first_only = 1;
     r.keep_reward_done = is_step ? 1 : 0;
     r.reset_all = (!is_step && mask == nullptr) ? 1 : 0;
     r.env_mask = is_step ? nullptr : mask;
-    if (!is_step) {  // in a step, k_commit has already respawned the envs that ended
+    if (!is_step) {
       hipLaunchKernelGGL(k_reset, dim3(veh_blocks), dim3(SMX_BLOCK), 0, stream, r);
       hipLaunchKernelGGL(k_reset_env, dim3(env_blocks), dim3(SMX_BLOCK), 0, stream, r);
     }
-    const unsigned sweep_blocks = (unsigned)((total + SMX_BLOCK - 1) / SMX_BLOCK);
-    if (ogm_bytes) hipLaunchKernelGGL(k_grid_first<false>, dim3(sweep_blocks), dim3(SMX_BLOCK), ogm_bytes, stream, r);
-    if (dagm_bytes) hipLaunchKernelGGL(k_grid_first<true>, dim3(sweep_blocks), dim3(SMX_BLOCK), dagm_bytes, stream, r);
-    if (c.sensors & SMX_SENSOR_ROAD_WAYPOINTS)  // before k_first clears SMX_F_FIRST
-      hipLaunchKernelGGL(k_road_waypoints, dim3((unsigned)((total * SMX_RW_LANE_CAP + SMX_BLOCK - 1) / SMX_BLOCK)), dim3(SMX_BLOCK), 0,
-                         stream, r);
-    if (lidar_blocks && !small_batch) {
-      // large batches: the new vehicles' lidar as a launch of its own instead of one after the other inside
-      // k_first — at C5 an env restart brings 64 new vehicles, whose serial lidar roles made the reset pass 0.58 ms
-      // of a 1.5 ms tick late in a run (many restarts per tick)
-      hipLaunchKernelGGL(k_lidar_first, dim3((unsigned)std::min<size_t>(SMX_LIDAR_FIRST_BLOCKS, total)), dim3(SMX_BLOCK), 0, stream, r);
-      r.lidar_blocks = 0;
+    TailArgs t{};
+    t.commit = is_step ? 1 : 0;
+    t.grids = (reset_pass && (ogm_bytes || dagm_bytes)) ? 1 : 0;
+    t.groups = h->alive_blob + al.groups;
+    t.n_groups = h->alive_blob + al.group_count + SMX_SEG_STRIDE * h->group_parity;
+    t.n_groups_next = h->alive_blob + al.group_count + SMX_SEG_STRIDE * (h->group_parity ^ 1);
+    if (build_list) {  // (the next tick's parity is h->alive_parity now)
+      t.list = h->alive_blob;
+      t.seg_count = h->alive_blob + al.seg + (size_t)8 * SMX_SEG_STRIDE * h->seg_parity;
+      t.seg_next = h->alive_blob + al.seg + (size_t)8 * SMX_SEG_STRIDE * (h->seg_parity ^ 1);
+      t.flat_next = h->alive_blob + al.flat + h->alive_parity;
+      t.slow_next = h->slow_blob + 4 * total + 4 * h->alive_parity;
     }
-    // large batches: k_first also walks the new vehicles' knot lists, for the next tick's k_control_fast
-    // (only k_control_fast reads them: not on the maps that keep the team kernels)
-    r.walk_new = (!small_batch && one_lane_cut(h) && h->knots_blob && (c.sensors & SMX_SENSOR_WAYPOINTS) &&
-                  c.wp_paths <= SMX_WPT_MAX_PATHS) ? 1 : 0;
-    hipLaunchKernelGGL(k_first, dim3(obs_blocks), dim3(SMX_FIRST_BLOCK), 0, stream, r);
+    hipLaunchKernelGGL(k_tail, dim3(obs_blocks), dim3(SMX_BLOCK), t.grids ? std::max(ogm_bytes, dagm_bytes) : 0, stream, r, t);
+    SMX_PHASE_END(SMX_PHASE_COMMIT);
+    h->group_parity ^= 1;
+    h->list_ready = build_list;
+    if (build_list) {
+      h->seg_parity ^= 1;
+      h->list_state = *st;
+    }
+    if (reset_pass) {
+      if (c.sensors & SMX_SENSOR_ROAD_WAYPOINTS)  // before k_first clears SMX_F_FIRST
+        hipLaunchKernelGGL(k_road_waypoints, dim3((unsigned)((total * SMX_RW_LANE_CAP + SMX_BLOCK - 1) / SMX_BLOCK)), dim3(SMX_BLOCK), 0,
+                           stream, r);
+      if (lidar_blocks && !small_batch) {
+        // large batches: the new vehicles' lidar as a launch of its own instead of one after the other inside
+        // k_first — at C5 an env restart brings 64 new vehicles, whose serial lidar roles made the reset pass 0.58 ms
+        // of a 1.5 ms tick late in a run (many restarts per tick)
+        hipLaunchKernelGGL(k_lidar_first, dim3((unsigned)std::min<size_t>(SMX_LIDAR_FIRST_BLOCKS, total)), dim3(SMX_BLOCK), 0, stream, r);
+        r.lidar_blocks = 0;
+      }
+      // large batches: k_first also walks the new vehicles' knot lists, for the next tick's k_control_fast
+      // (only k_control_fast reads them: not on the maps that keep the team kernels)
+      r.walk_new = (!small_batch && one_lane_cut(h) && h->knots_blob && (c.sensors & SMX_SENSOR_WAYPOINTS) &&
+                    c.wp_paths <= SMX_WPT_MAX_PATHS) ? 1 : 0;
+      hipLaunchKernelGGL(k_first, dim3(obs_blocks), dim3(SMX_FIRST_BLOCK), 0, stream, r, t.groups, t.n_groups);
+    }
   }
   SMX_HIP(hipGetLastError());
   if (phased) {

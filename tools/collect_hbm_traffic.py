@@ -57,11 +57,11 @@ def main():
     fetch, fd = read_counters(args.fetch, "FETCH_SIZE")
     write, wd = read_counters(args.write, "WRITE_SIZE")
     ours = [k for k in set(fetch) | set(write) if k.startswith("k_")]
-    # one k_commit dispatch per smx_step (the reset pass commits inside k_first)
-    steps_f = fd.get("k_commit", 0)
-    steps_w = wd.get("k_commit", 0)
+    # one k_tail dispatch per smx_step (and one per smx_reset: the run's one reset is within the noise)
+    steps_f = fd.get("k_tail", 0)
+    steps_w = wd.get("k_tail", 0)
     if not steps_f or not steps_w:
-        raise SystemExit("k_commit not found in the counter files")
+        raise SystemExit("k_tail not found in the counter files")
     kernels = {}
     tot_r = tot_w = 0.0
     for k in sorted(ours):
