@@ -5611,7 +5611,10 @@ static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const floa
   const bool routed = h->missions.route_last != nullptr;  // some slot has a fixed route: the scan instance that knows them
   bool fast_scan = false;  // the tick of a large batch (not its reset pass): one-lane scan kernels + teams over their slow lists
   int slow_parity = 0;
-  auto observation_pass = [&](const KernelArgs& k, bool phases) {
+  // the large form's rows: k_wp_walk -> k_waypoints_emit while they fit the staged form, else k_waypoints, which reads
+  // every vehicle's seeds (no seed_pending) and so cannot run beside or ahead of the slow seeds chain
+  const bool staged_rows = (c.sensors & SMX_SENSOR_WAYPOINTS) && c.wp_paths <= SMX_WPT_MAX_PATHS && h->knots_blob;
+  auto observation_pass = [&](const KernelArgs& k, bool phases) -> int {
     // Large batches, no per-kernel timing asked: the grid maps and the lidar (which read poses only) leave on
     // side stream 0 at once and overlap the scan — kernels bound by their own write stream beside one bound by
     // arithmetic and load latency; observe goes to side stream 1 after the scan, the waypoint kernels stay on
@@ -5648,8 +5651,9 @@ static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const floa
         ks.slow_list = h->slow_blob + total;
         ks.slow_count = slow_counters + 1;
       }
-      // path seeds without the ten-nearest list: agents with a route object and no fixed route, waypoints sensor on
-      const bool fast_seeds = !SMX_WP_STAGED && fast && !routed && (c.sensors & SMX_SENSOR_WAYPOINTS) && h->pending_blob && one_lane_seeds(h);
+      // path seeds without the ten-nearest list: agents with a route object and no fixed route, staged rows (past
+      // SMX_WPT_MAX_PATHS rows the team seeds kernel serves everybody, as in the teams cut)
+      const bool fast_seeds = !SMX_WP_STAGED && fast && !routed && staged_rows && h->pending_blob && one_lane_seeds(h);
       if (fast_seeds) {
         ks.seed_pending = h->pending_blob;
         kwp.seed_pending = h->pending_blob;
@@ -5725,7 +5729,7 @@ static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const floa
       hipLaunchKernelGGL(k_sensors, dim3(sensor_blocks), dim3(SMX_BLOCK), sensor_lds, stream, k);
     } else {
       // staged rows whenever the waypoints sensor is on and the rows fit that form
-      if ((c.sensors & SMX_SENSOR_WAYPOINTS) && c.wp_paths <= SMX_WPT_MAX_PATHS && h->knots_blob) {
+      if (staged_rows) {
         hipLaunchKernelGGL(k_wp_walk, dim3((unsigned)((total * SMX_WP_LANES + SMX_BLOCK - 1) / SMX_BLOCK)), dim3(SMX_BLOCK), 0, stream, kwp);
 #if SMX_WP_STAGED  // developer variant: round 2's staged rows
         const size_t stage_bytes = std::max((size_t)c.wp_len * SMX_BLOCK * 16, (size_t)SMX_MAX_KNOTS * SMX_BLOCK * sizeof(int));
@@ -5765,6 +5769,9 @@ static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const floa
       hipLaunchKernelGGL(k_road_waypoints, dim3((unsigned)((total * SMX_RW_LANE_CAP + SMX_BLOCK - 1) / SMX_BLOCK)), dim3(SMX_BLOCK), 0,
                          stream, k);
     if (phases && phased) (void)hipEventRecord(ph[SMX_PHASE_SENSORS + 1], stream);
+    // (the pending vehicles' seeds, rows and trip meters would stay last tick's)
+    if (slow_chain_pending) return fail(h, SMX_ERR_STATE, "internal: the slow seeds chain was not launched");
+    return SMX_OK;
   };
   // the LDS-path form of k_control fits one wavefront per SIMD: only while the batch needs no more
   const bool lds_path = small_batch && total * SMX_WP_LANES <= (size_t)1024 * 64;
@@ -5861,7 +5868,8 @@ static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const floa
         break;
     }
     SMX_PHASE_END(SMX_PHASE_CONTROL);
-    observation_pass(a, true);
+    rc = observation_pass(a, true);
+    if (rc != SMX_OK) return rc;
   }
   {
     // the end of the pass: k_tail (the tick's commit, the new vehicles' grid tiles, the env groups with new vehicles,
