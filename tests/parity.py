@@ -279,15 +279,20 @@ class OracleBatch:
         return self._stack(parts)
 
 
-def sync_oracle_from_device(ob: "OracleBatch", sim):
+def sync_oracle_from_device(ob: "OracleBatch", sim, envs=None):
     """Teacher forcing: overwrite every oracle vehicle's continuous state with the device's, so
     that each tick is compared as a single step from identical state (closed-loop lane following
-    is bang-bang and amplifies last-ulp libm differences across ticks)."""
+    is bang-bang and amplifies last-ulp libm differences across ticks).  Oracle env ``i`` follows
+    device env ``i``, or ``envs[i]`` when ``envs`` is given (a sample of a larger batch)."""
     import torch
 
     torch.cuda.synchronize()
-    st = sim.state.cpu().numpy().reshape(nat.S_COUNT, -1)
-    flags = sim.flags.cpu().numpy().reshape(-1)
+    st, flags = sim.state, sim.flags
+    if envs is not None:
+        idx = torch.as_tensor(list(envs), device=st.device)
+        st, flags = st.index_select(1, idx), flags.index_select(0, idx)
+    st = st.cpu().numpy().reshape(nat.S_COUNT, -1)
+    flags = flags.cpu().numpy().reshape(-1)
     S = nat.S
     lane_ids = sim.cm.lane_ids
     for e, env in enumerate(ob.envs):

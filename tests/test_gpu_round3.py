@@ -3,8 +3,8 @@
 * SMALL and LARGE launch forms bit for bit on more than 4 096 vehicles over a long auto-reset run, so that the alive
   list spans several 1 024-thread workgroups and thins out (k_alive_list, the one-lane kernels and their slow
   lists, k_waypoints_emit's pool);
-* BASELINE configs[3] and configs[4] at FULL size through size-independent properties and first / last slice
-  equality with a small-form batch;
+* BASELINE configs[3] and configs[4] at FULL size through size-independent properties and tile by tile equality with
+  a small-form batch (tests/test_gpu_bench_workloads.py holds the bench's own, distinct envs to their shards);
 * the lane-following envelope of smarts/core/tests/test_controller_lane.py:99-147 and the +-2 px occupancy check of
   smarts/core/tests/test_observations.py:132-152 (every OTHER vehicle's projected centre), both on the device outputs.
 """
@@ -71,8 +71,8 @@ def test_strategies_agree_bit_for_bit_on_a_long_sparse_run(name, E, N, ticks, ex
     ("configs[4]", "minicity", 4096, 64, 4, 8, dict(lidar="planar100")),
 ])
 def test_baseline_configurations_at_full_size(config, name, E, N, sub, ticks, extra, compiled_maps):
-    """The whole batch of BASELINE configs[3] / configs[4]: `sub` distinct envs tiled E / sub times.  First and last
-    slice must equal a `sub`-env small-form batch bit for bit; rows obey the dense layout's invariants."""
+    """The whole batch of BASELINE configs[3] / configs[4]: `sub` distinct envs tiled E / sub times.  Every tile must
+    equal a `sub`-env small-form batch bit for bit (compared on the device); rows obey the dense layout's invariants."""
     import torch
 
     from smarts_amd.engine import BatchedSim, SimConfig, make_spawns
@@ -90,18 +90,17 @@ def test_baseline_configurations_at_full_size(config, name, E, N, sub, ticks, ex
         a_small = _actions(rng, sub, N)
         o1 = sim.step(torch.from_numpy(np.tile(a_small, (E // sub, 1))).cuda())
         o2 = sim2.step(torch.from_numpy(a_small).cuda())
-    torch.cuda.synchronize()
+    assert sorted(o1) == sorted(o2)
     for k in o2:
-        if k in ("ogm", "lidar_point", "wp_pos"):  # the big rows: first and last slice only (host memory)
-            a_first, a_last = (o1[k][:sub].cpu().numpy(), o1[k][E - sub:].cpu().numpy())
-        elif k == "learner":
-            a = o1[k].cpu().numpy()
-            a_first, a_last = a[:, :sub], a[:, E - sub:]
-        else:
-            a = o1[k].cpu().numpy()
-            a_first, a_last = a[:sub], a[E - sub:]
-        b = o2[k].cpu().numpy()
-        assert np.array_equal(a_first, b, equal_nan=True) and np.array_equal(a_last, b, equal_nan=True), (config, k)
+        a, b = o1[k], o2[k]
+        if k == "learner":  # [2, E, N]: the env axis is 1
+            a, b = a.transpose(0, 1), b.transpose(0, 1)
+        tiles = a.reshape((E // sub, sub) + tuple(a.shape[1:]))  # tile i = envs [i * sub, (i + 1) * sub)
+        ne = tiles != b.unsqueeze(0)
+        if a.is_floating_point():
+            ne &= ~(tiles.isnan() & b.isnan().unsqueeze(0))  # np.array_equal(..., equal_nan=True)
+        bad = ne.reshape(E // sub, -1).any(1).nonzero().flatten().cpu().numpy()
+        assert bad.size == 0, (config, k, f"{bad.size} tiles differ, the first {bad[:8].tolist()}")
     act = o1["active"].cpu().numpy().astype(bool)
     assert act.mean() > 0.5
     wpc = o1["wp_count"].cpu().numpy()

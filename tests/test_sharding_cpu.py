@@ -26,16 +26,22 @@ def test_shard_plan_partitions_every_env_once():
 
 
 def test_spawns_are_shard_invariant(compiled_maps):
-    """A rank's spawn table equals the slice of the single-process table: sharding changes where an
-    env runs, not what it computes."""
+    """A rank's spawn table and bench.py's action stream equal the slices of the single-process ones, on even and
+    uneven worlds: sharding changes where an env runs, not what it computes."""
+    import bench
     from smarts_amd.engine import make_spawns
 
     cm = compiled_maps("loop")
     whole = make_spawns(cm, 8, 4, episodes=2, seed=42)
-    for r in range(2):
-        p = ShardPlan(8, 2, r)
-        part = make_spawns(cm, p.num_envs, 4, episodes=2, seed=42, first_env=p.first_env)
-        assert np.array_equal(part, whole[:, p.first_env * 4:(p.first_env + p.num_envs) * 4])
+    acts = bench.action_stream(8, 4, 42, 0)
+    assert acts.shape == (bench.ACTION_CYCLE, 8, 4) and len(np.unique(acts)) == 4
+    for world in (2, 3):
+        for r in range(world):
+            p = ShardPlan(8, world, r)
+            envs = slice(p.first_env, p.first_env + p.num_envs)
+            part = make_spawns(cm, p.num_envs, 4, episodes=2, seed=42, first_env=p.first_env)
+            assert np.array_equal(part, whole[:, p.first_env * 4:(p.first_env + p.num_envs) * 4]), (world, r)
+            assert np.array_equal(bench.action_stream(p.num_envs, 4, 42, p.first_env), acts[:, envs]), (world, r)
 
 
 def _worker(rank, world, port, q):
