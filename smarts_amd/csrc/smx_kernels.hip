@@ -34,26 +34,14 @@
 #include <string>
 #include <vector>
 
+#include "smx_plan.h"
 #include "smx_scan.h"
 #include "smx_vehicle.h"
 
-#define SMX_BLOCK 64
 #define SMX_COLLISION_LEEWAY 0.05  // chassis.py:75-78
-#define SMX_WP_LANES 4             // lanes of a wavefront that share one vehicle (k_control, waypoints role)
 #define SMX_POSE_SCAN_RADIUS 10.0
-// SMX_LAUNCH_AUTO: the LARGE launch form above this many vehicles.  Measured crossover (round 2, C4's shape:
-// 8 192 vehicles 0.165 / 0.216 ms small / large, 32 768: 0.461 / 0.303, 65 536: 0.886 / 0.505; C3 at 32 768:
-// 0.514 / 0.504; C2 at 8 192: 0.133 / 0.187).  At 16 384 the two cross: every agent alive 0.258 / 0.226, over
-// ticks 50-550 of a run (fewer alive) 0.223 / 0.250 — the longer run decides, 16 384 stays small.
-#define SMX_LARGE_BATCH_VEHICLES 16384
 #define SMX_WPT_PRELOAD 8           // knots of a path held in registers while it is interpolated
-#ifndef SMX_WP_STAGED
-#define SMX_WP_STAGED 0             // developer variant (-DSMX_WP_STAGED=1): k_waypoints_tables instead of k_waypoints_emit
-#endif
 #define SMX_SLOW_BLOCKS 512          // workgroups of the slow lists' kernels on a map without junctions (smx_load_map: slow_blocks)
-#ifndef SMX_SCAN_UNSEEDED
-#define SMX_SCAN_UNSEEDED 0         // developer variant (-DSMX_SCAN_UNSEEDED=1): the scan never starts from last tick's answers
-#endif
 
 struct KernelArgs {
   smx_config cfg;
@@ -1377,7 +1365,7 @@ __device__ __forceinline__ void scan_role(const KernelArgs& a, const MapDev& m, 
     const bool social = (flags & SMX_F_SOCIAL) != 0;  // only its nearest lane is ever asked for (neighbour rows)
     FactsCarry fc;
     fc.valid = false;
-    if (a.facts_carry != nullptr && !(flags & SMX_F_FIRST) && !SMX_SCAN_UNSEEDED) {
+    if (a.facts_carry != nullptr && !(flags & SMX_F_FIRST)) {
       fc.qx = a.facts_carry[gid];
       fc.qy = a.facts_carry[total + gid];
       fc.prev_dist = a.st.facts_f64[(size_t)SMX_FF_LANE_DIST * total + gid];
@@ -1414,7 +1402,7 @@ __device__ __forceinline__ void scan_role(const KernelArgs& a, const MapDev& m, 
   LaneGuess guess;
   SeedsCarry scy;
   scy.valid = false;
-  if (a.seeds_carry != nullptr && !(flags & SMX_F_FIRST) && !SMX_SCAN_UNSEEDED) {
+  if (a.seeds_carry != nullptr && !(flags & SMX_F_FIRST)) {
     const int32_t* sc_ = a.st.seed_cache;
     scy.qx = a.seeds_carry[gid];
     scy.qy = a.seeds_carry[total + gid];
@@ -1564,7 +1552,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_scan_fast(const KernelArgs a) {
   }
   if (in_range && (flags & SMX_F_ALIVE) && (!a.first_only || (flags & SMX_F_FIRST))) {
     int* cand = cand_lds + threadIdx.x;
-    const bool seeded = !(flags & SMX_F_FIRST) && !SMX_SCAN_UNSEEDED;
+    const bool seeded = !(flags & SMX_F_FIRST);
     if (ROLE == 0) {
       const double cxs[4] = {-0.5, 0.5, 0.5, -0.5};
       const double cys[4] = {0.5, 0.5, -0.5, -0.5};
@@ -1977,7 +1965,6 @@ __device__ __forceinline__ void waypoints_role(const KernelArgs& a, const int bl
 // cut at SMX_WPK_CAP — write their rows afterwards with the serial emitter, exactly as waypoints_for does;
 // their rows are skipped in step 3.
 // =================================================================================
-#define SMX_WPT_MAX_PATHS 8  // dense rows per vehicle (wp_paths) the staged form handles
 // floor(e / d) for 0 <= e < 4096, 1 <= d <= 64, rcp = 1.0f / d: (e + 0.5) / d is at least 0.5 / d away from an integer,
 // the float32 product is off by less than 4096 / d * 2^-22
 __device__ __forceinline__ int small_quotient(int e, float rcp) { return (int)(((float)e + 0.5f) * rcp); }
@@ -3883,24 +3870,8 @@ struct OgmPose {
   double x, y, ch, sh;  // centre, cos / sin of the wrapped heading
   int alive, observes;
 };
-#define SMX_OGM_WAVES 4
-#ifndef SMX_SCAN_WIDE_MAX_VEHICLES  // the team scan halves take eight lanes a vehicle up to this many vehicles, four above
-#define SMX_SCAN_WIDE_MAX_VEHICLES 65536
-#endif
-#ifndef SMX_ONE_LANE_ON_SPLIT_MAPS  // developer: the one-lane cut on maps whose lanes split too
-#define SMX_ONE_LANE_ON_SPLIT_MAPS 0
-#endif
-#ifndef SMX_ONE_LANE_MIN_VEHICLES  // the one-lane cut's seeds half is the one-lane kernel + slow chain from this many vehicles on
-#define SMX_ONE_LANE_MIN_VEHICLES 114688
-#endif
-#ifndef SMX_OGM_ENV_MIN_VEHICLES  // small form: OGM tiles by k_ogm_env from this many vehicles on (smarts_amd/engine.py mirrors it)
-#define SMX_OGM_ENV_MIN_VEHICLES 8192
-#endif
 #ifndef SMX_SIDE_PRIO  // developer: side streams that get the default priority instead of the lowest (bit i = side i)
 #define SMX_SIDE_PRIO 0
-#endif
-#ifndef SMX_FACTS_EARLY_MAX  // the facts half leaves with the grid kernels up to this many vehicles, else after the seeds half
-#define SMX_FACTS_EARLY_MAX 32768
 #endif
 // orders a wavefront's own LDS traffic for the compiler (the hardware keeps a wavefront's LDS operations in order)
 #define SMX_WAVE_SYNC()                                   \
@@ -4969,35 +4940,34 @@ extern "C" int smx_set_launch_strategy(smx_handle h, int strategy) {
   return SMX_OK;
 }
 
-// Which cut of the LARGE form a batch takes (smx.h, smx_launch_form): one lane per vehicle + slow lists where the lists
-// stay short (a map whose lanes never split), teams of lanes for everybody elsewhere; the strategies LARGE_ONE_LANE /
-// LARGE_TEAMS force a cut.
-static bool one_lane_cut(const smx_handle_s* h) {
-  if (h->launch_strategy == SMX_LAUNCH_LARGE_ONE_LANE) return true;
-  if (h->launch_strategy == SMX_LAUNCH_LARGE_TEAMS) return false;
-  return !h->map_junctions || SMX_ONE_LANE_ON_SPLIT_MAPS;
-}
-// ... and, inside the one-lane cut, whether the seeds half is the one-lane kernel + the slow seeds chain, or the team
-// kernel for everybody: the chain — from-scratch searches and the serial emitter for the few vehicles the one-lane
-// kernel cannot serve — is 110 us of latency behind the seeds kernel whatever the batch, and below
-// SMX_ONE_LANE_MIN_VEHICLES it ends the tick; the team seeds kernel then costs less than it saves (C4's shards, default
-// run / ticks 5-65, ms per tick, team seeds against one-lane seeds: 1024 envs 0.195 / 0.265 against 0.266 / 0.284; 2048:
-// 0.251 / 0.378 against 0.288 / 0.383; 3072: 0.286 / 0.455 against 0.325 / 0.477; 4096: 0.367 / 0.603 against 0.380 / 0.579;
-// the team kernels throughout: 0.227 / 0.287, 0.273 / 0.435, 0.371 / 0.593, 0.440 / 0.768).
-static bool one_lane_seeds(const smx_handle_s* h) {
-  if (h->launch_strategy == SMX_LAUNCH_LARGE_ONE_LANE) return true;
-  const size_t total = (size_t)h->cfg.num_envs * h->cfg.num_vehicles;
-  return total >= SMX_ONE_LANE_MIN_VEHICLES;
+// What a call's plan (smx_plan.h) may depend on, read off the handle.  `st`: the caller's state block, for the carried
+// alive list (null: no tick is planned, only the form is asked for).
+static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_state* st) {
+  PlanInputs in{};
+  in.cfg = &h->cfg;
+  in.launch_strategy = h->launch_strategy;
+  in.map_junctions = h->map_junctions;
+  in.slow_blocks = h->slow_blocks;
+  in.routed = h->missions.route_last != nullptr;
+  in.is_step = is_step;
+  in.phase_timing = h->phase_timing && h->ph_used < 16384;
+  in.side_ready = h->side_ready;
+  in.list_carried = st && h->list_ready && std::memcmp(&h->list_state, st, sizeof(smx_state)) == 0;
+  in.debug_skip = (SMX_SKIP(*h, SMX_SKIP_FORCE_SMALL) ? SMX_SKIP_FORCE_SMALL : 0) |
+                  (SMX_SKIP(*h, SMX_SKIP_FORCE_SCAN_SPLIT) ? SMX_SKIP_FORCE_SCAN_SPLIT : 0);
+  in.alive_blob = h->alive_blob != nullptr;
+  in.knots_blob = h->knots_blob != nullptr;
+  in.ctrl_blob = h->ctrl_blob != nullptr;
+  in.pending_blob = h->pending_blob;
+  in.slow = SlowLists{h->slow_blob, (size_t)h->cfg.num_envs * h->cfg.num_vehicles};
+  in.slow_parity = h->alive_parity;
+  return in;
 }
 
 extern "C" int smx_launch_form(smx_handle h) {
   if (!h) return SMX_ERR_INVALID;
   if (!h->map_loaded) return fail(h, SMX_ERR_STATE, "smx_launch_form needs the map (the form depends on it)");
-  const size_t total = (size_t)h->cfg.num_envs * h->cfg.num_vehicles;
-  const bool small_batch = h->launch_strategy == SMX_LAUNCH_SMALL ||
-                           (h->launch_strategy == SMX_LAUNCH_AUTO && total <= SMX_LARGE_BATCH_VEHICLES);
-  if (small_batch) return SMX_FORM_SMALL;
-  return (h->alive_blob && h->slow_blob && one_lane_cut(h)) ? SMX_FORM_LARGE_ONE_LANE : SMX_FORM_LARGE_TEAMS;
+  return tick_plan(plan_inputs(h, false, nullptr)).form;
 }
 
 extern "C" int smx_set_controller_gains(smx_handle h, double heading_gain, double lateral_gain) {
@@ -5147,7 +5117,7 @@ extern "C" int smx_load_map(smx_handle h, const smx_map_tables* t) {
     SMX_HIP(hipMemset(h->alive_blob, 0, n * sizeof(int32_t)));
   }
   if (!h->slow_blob) {
-    const size_t n = 4 * (size_t)h->cfg.num_envs * h->cfg.num_vehicles + 8;
+    const size_t n = SlowLists::size((size_t)h->cfg.num_envs * h->cfg.num_vehicles);
     SMX_HIP(hipMalloc((void**)&h->slow_blob, n * sizeof(int32_t)));
     SMX_HIP(hipMemset(h->slow_blob, 0, n * sizeof(int32_t)));
   }
@@ -5486,27 +5456,259 @@ static int check_buffers(smx_handle h, const smx_state* st, const smx_spawns* sp
   return SMX_OK;
 }
 
-static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const float* actions_f32, const double* traj,
-                   const int32_t* traj_n, const uint8_t* mask, const smx_state* st,
-                   const smx_spawns* sp, const smx_outputs* out, void* stream_) {
-  if (!h) return SMX_ERR_INVALID;
-  if (!h->map_loaded) return fail(h, SMX_ERR_STATE, "smx_load_map has not been called");
-  int rc = check_buffers(h, st, sp, out);
-  if (rc != SMX_OK) return rc;
-  if (is_step) {
-    const int sp_ = h->cfg.action_space;
-    const bool ok = sp_ == SMX_ACTION_SPACE_LANE ? actions != nullptr
-                    : sp_ == SMX_ACTION_SPACE_TRAJECTORY ? (traj != nullptr && traj_n != nullptr)
-                                                         : actions_f32 != nullptr;
-    if (!ok)
-      return fail(h, SMX_ERR_INVALID,
-                  "actions do not match cfg.action_space (smx_step: Lane, smx_step_trajectory: Trajectory, "
-                  "smx_step_continuous: the float spaces)");
+// enqueue() issues a call's TickPlan (smx_plan.h) step by step; the steps launch what the plan names and decide nothing.
+using Kernel = void (*)(KernelArgs);
+using HandoffKernel = void (*)(KernelArgs, CtrlHandoff);
+static void launch(Kernel k, unsigned blocks, size_t lds, hipStream_t s, const KernelArgs& a) {
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(SMX_BLOCK), lds, s, a);
+}
+static void launch(HandoffKernel k, unsigned blocks, hipStream_t s, const KernelArgs& a, const CtrlHandoff& ho) {
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(SMX_BLOCK), 0, s, a, ho);
+}
+static KernelArgs with_slow(KernelArgs a, const SlowRef& slow) {
+  a.slow_list = slow.list;
+  a.slow_count = slow.count;
+  return a;
+}
+
+// the controller kernels of one action space (the lane-following forms exist for the two lane spaces only)
+struct ControlKernels {
+  Kernel one, one_lds, fast;
+  HandoffKernel listed, paths, law;
+};
+template <int SPACE>
+static ControlKernels control_kernels_of() {
+  ControlKernels k{k_control<SPACE>, nullptr, nullptr, nullptr, nullptr, k_control_law<SPACE>};
+  if constexpr (SPACE == SMX_ACTION_SPACE_LANE || SPACE == SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED) {
+    k.one_lds = k_control<SPACE, true>;
+    k.fast = k_control_fast<SPACE>;
+    k.listed = k_control_listed<SPACE>;
+    k.paths = k_control_paths<SPACE>;
   }
-  hipStream_t stream = (hipStream_t)stream_;
-  const smx_config& c = h->cfg;
+  return k;
+}
+static ControlKernels control_kernels(int action_space) {
+  switch (action_space) {
+    case SMX_ACTION_SPACE_LANE: return control_kernels_of<SMX_ACTION_SPACE_LANE>();
+    case SMX_ACTION_SPACE_CONTINUOUS: return control_kernels_of<SMX_ACTION_SPACE_CONTINUOUS>();
+    case SMX_ACTION_SPACE_ACTUATOR_DYNAMIC: return control_kernels_of<SMX_ACTION_SPACE_ACTUATOR_DYNAMIC>();
+    case SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED: return control_kernels_of<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED>();
+    default: return control_kernels_of<SMX_ACTION_SPACE_TRAJECTORY>();
+  }
+}
+
+static void launch_control(smx_handle h, const TickPlan& p, const KernelArgs& a, hipStream_t stream) {
+  const ControlKernels k = control_kernels(h->cfg.action_space);
+  switch (p.control) {
+    case Control::NONE: break;
+    case Control::ONE: launch(k.one, p.wp_blocks, 0, stream, a); break;
+    case Control::ONE_LDS: launch(k.one_lds, p.wp_blocks, 0, stream, a); break;
+    case Control::LAW: launch(k.law, p.veh_blocks, stream, a, h->ctrl); break;
+    case Control::PATHS_LAW:
+      launch(k.paths, p.wp_blocks, stream, a, h->ctrl);
+      launch(k.law, p.veh_blocks, stream, a, h->ctrl);
+      break;
+    case Control::FAST_LISTED: {
+      const KernelArgs ac = with_slow(a, p.control_slow);  // the controller's slow list
+      launch(k.fast, p.veh_blocks, 0, stream, ac);
+      launch(k.listed, p.slow_blocks, stream, ac, h->ctrl);
+      break;
+    }
+  }
+}
+
+// the tick's alive list: the one the last pass's k_tail built from these flags (it zeroed this tick's slow-list
+// counters too), or k_alive_list now
+static void alive_list(smx_handle h, const TickPlan& p, KernelArgs& a, hipStream_t stream) {
+  if (p.alive == AliveList::NONE) return;
+  const AliveLayout al = alive_layout(h->cfg);
+  int32_t* counters = h->alive_blob + al.flat;
+  a.alive_list = h->alive_blob;
+  if (p.alive == AliveList::CARRIED) {
+    a.alive_count = h->alive_blob + al.seg + (size_t)8 * SMX_SEG_STRIDE * (h->seg_parity ^ 1);
+    a.alive_segmented = 1;
+  } else {
+    const size_t total = (size_t)h->cfg.num_envs * h->cfg.num_vehicles;
+    a.alive_count = counters + h->alive_parity;
+    hipLaunchKernelGGL(k_alive_list, dim3(smx_blocks(total, SMX_ALIVE_BLOCK)), dim3(SMX_ALIVE_BLOCK), 0, stream, a, h->alive_blob,
+                       counters + h->alive_parity, counters + (h->alive_parity ^ 1), p.alive_zero);
+  }
+  h->alive_parity ^= 1;
+}
+
+static void launch_grids(smx_handle h, const TickPlan& p, const KernelArgs& k, hipStream_t s) {
+  const unsigned total = (unsigned)(h->cfg.num_envs * h->cfg.num_vehicles);
+  switch (p.ogm) {
+    case Ogm::NONE:
+    case Ogm::IN_SENSORS: break;
+    case Ogm::ENV2: hipLaunchKernelGGL(k_ogm_env<2>, dim3((unsigned)h->cfg.num_envs), dim3(SMX_OGM_WAVES * 64), p.ogm_lds, s, k); break;
+    case Ogm::ENV1: hipLaunchKernelGGL(k_ogm_env<1>, dim3((unsigned)h->cfg.num_envs), dim3(SMX_OGM_WAVES * 64), p.ogm_lds, s, k); break;
+    case Ogm::PER_OBSERVER: launch(k_ogm, total, p.ogm_lds, s, k); break;
+  }
+  if (p.dagm) launch(k_dagm, total, p.dagm_bytes, s, k);
+}
+
+// the slow seeds chain over the vehicles the one-lane seeds kernel left seed_pending: searches from scratch, then their
+// walks and rows by the serial emitter
+static void launch_slow_chain(const TickPlan& p, const KernelArgs& ks, hipStream_t s) {
+  if (p.chain_fused) {
+    launch(k_scan_listed<1, false, SMX_TEAM>, p.slow_blocks, 0, s, ks);
+    launch(k_waypoints_walk_listed, p.slow_blocks, 0, s, ks);
+  } else {
+    launch(k_scan_listed<1>, p.slow_blocks, 0, s, ks);
+    launch(k_waypoints_listed, p.slow_blocks, 0, s, ks);
+    launch(k_wp_walk_listed, p.slow_blocks, 0, s, ks);
+  }
+}
+
+// one tick's observations: grid kernels, the scan's halves, the slow seeds chain, rows, observe, lidar, joins, road
+// waypoints (`ph`: the call's phase events, null unless the plan is phased)
+static void observation_pass(smx_handle h, const TickPlan& p, const KernelArgs& k, hipStream_t stream, hipEvent_t* ph) {
+  const size_t total = (size_t)h->cfg.num_envs * h->cfg.num_vehicles;
+  const hipStream_t s_grid = p.fork ? h->side[0] : stream, s_obs = p.fork ? h->side[1] : stream;
+  if (p.fork) {
+    (void)hipEventRecord(h->ev_fork_grid, stream);
+    (void)hipStreamWaitEvent(s_grid, h->ev_fork_grid, 0);
+    launch_grids(h, p, k, s_grid);
+    if (p.lidar == Lidar::SIDE) launch(k_lidar, p.lidar_blocks, 0, s_grid, k);
+  }
+  // the scan's halves as two launches in the large form, on two streams when forked: path seeds (-> waypoint kernels) on
+  // the caller's, road facts (-> observe) on side 1; each half appends to its own slow list
+  KernelArgs ks = with_slow(k, p.seeds_slow);
+  ks.seed_pending = p.seed_pending();
+  switch (p.seeds()) {
+    case Seeds::SCAN: {
+      const Kernel scan = p.scan_split ? (p.routed ? k_scan<true, true> : k_scan<true>) : (p.routed ? k_scan<false, true> : k_scan<false>);
+      launch(scan, p.seeds_blocks, 0, stream, k);
+      break;
+    }
+    case Seeds::ONE_LANE: launch(k_scan_fast<1>, p.seeds_blocks, 0, stream, ks); break;
+    case Seeds::ROUTED: launch(k_scan_half<1, true>, p.seeds_blocks, 0, stream, k); break;
+    case Seeds::WIDE: launch(k_scan_half<1, false, SMX_TEAM>, p.seeds_blocks, 0, stream, k); break;
+    case Seeds::FOUR: launch(k_scan_half<1>, p.seeds_blocks, 0, stream, k); break;
+  }
+  if (p.chain() == SlowChain::SIDE) {
+    // the slow chain runs beside the main chain (k_wp_walk -> k_waypoints_emit pass over its vehicles)
+    // (one event after the seeds half serves this fork and the facts half's below: every record on the caller's
+    // stream is a packet its next kernel waits behind, ten microseconds of the tick's longest chain)
+    (void)hipEventRecord(h->ev_fork, stream);
+    (void)hipStreamWaitEvent(h->side[2], h->ev_fork, 0);
+    launch_slow_chain(p, ks, h->side[2]);
+  }
+  if (p.facts_start == FactsStart::WITH_GRIDS) {
+    (void)hipStreamWaitEvent(s_obs, h->ev_fork_grid, 0);
+  } else if (p.facts_start == FactsStart::AFTER_SEEDS) {
+    if (p.chain() != SlowChain::SIDE) (void)hipEventRecord(h->ev_fork, stream);
+    (void)hipStreamWaitEvent(s_obs, h->ev_fork, 0);
+  }
+  const KernelArgs kf = with_slow(k, p.facts_slow);
+  switch (p.facts) {
+    case Facts::SCAN: break;
+    case Facts::ONE_LANE:
+      launch(k_scan_fast<0>, p.facts_blocks, 0, s_obs, kf);
+      launch(k_scan_listed<0>, p.slow_blocks, 0, s_obs, kf);
+      break;
+    case Facts::WIDE: launch(k_scan_half<0, false, SMX_TEAM>, p.facts_blocks, 0, s_obs, kf); break;
+    case Facts::FOUR: launch(k_scan_half<0>, p.facts_blocks, 0, s_obs, kf); break;  // (the facts half seeds no path)
+  }
+  if (ph) (void)hipEventRecord(ph[SMX_PHASE_SCAN + 1], stream);
+  if (!p.fork) launch_grids(h, p, k, stream);
+  if (ph) (void)hipEventRecord(ph[SMX_PHASE_OGM + 1], stream);
+  KernelArgs kw = k;  // the waypoint kernels, which pass over the slow chain's vehicles
+  kw.seed_pending = p.seed_pending();
+  const unsigned walk_blocks = smx_blocks(total * SMX_WP_LANES);
+  switch (p.rows) {
+    case Rows::SENSORS: launch(k_sensors, p.sensor_blocks, p.sensor_lds, stream, k); break;
+    case Rows::UNSTAGED: launch(k_waypoints, p.wp_blocks, 0, stream, k); break;
+    case Rows::TABLES:
+      launch(k_wp_walk, walk_blocks, 0, stream, kw);
+      launch(k_waypoints_tables, p.wp_blocks, std::max((size_t)h->cfg.wp_len * SMX_BLOCK * 16, (size_t)SMX_MAX_KNOTS * SMX_BLOCK * sizeof(int)),
+             stream, k);
+      break;
+    case Rows::EMIT:
+    case Rows::EMIT_CHAIN_SIDE:
+    case Rows::EMIT_CHAIN_AFTER:
+      launch(k_wp_walk, walk_blocks, 0, stream, kw);
+      kw = with_slow(kw, p.rows_slow);
+      launch(k_waypoints_emit, p.wp_blocks, 0, stream, kw);
+      launch(k_waypoints_listed, p.slow_blocks, 0, stream, kw);
+      if (p.rows == Rows::EMIT_CHAIN_AFTER) launch_slow_chain(p, ks, stream);  // (one stream: after the main waypoint kernels)
+      break;
+  }
+  if (!p.small()) launch(k_observe, p.obs_blocks, 0, s_obs, k);
+  if (p.lidar == Lidar::CALLER) launch(k_lidar, p.lidar_blocks, 0, stream, k);
+  if (p.fork) {
+    // (each side stream joins the caller's directly: chaining side 0 through side 1 puts one more hop behind the
+    // last kernel when k_observe ends the tick — 1 % late in a run)
+    for (int i = 0; i < (p.chain() == SlowChain::SIDE ? 3 : 2); ++i) {
+      (void)hipEventRecord(h->ev_join[i], h->side[i]);
+      (void)hipStreamWaitEvent(stream, h->ev_join[i], 0);
+    }
+  }
+  if (p.road_waypoints)  // (poses are the tick's new ones; flags still those of its start)
+    launch(k_road_waypoints, smx_blocks(total * SMX_RW_LANE_CAP), 0, stream, k);
+  if (ph) (void)hipEventRecord(ph[SMX_PHASE_SENSORS + 1], stream);
+}
+
+// the end of the pass: k_tail (the tick's commit, the new vehicles' grid tiles, the env groups with new vehicles,
+// the next tick's alive list), then the reset pass over those groups (first observations of the new vehicles)
+static int tail_and_reset_pass(smx_handle h, const TickPlan& p, const KernelArgs& a, const uint8_t* mask, const smx_state* st,
+                               hipStream_t stream, hipEvent_t* ph) {
+  const size_t total = (size_t)h->cfg.num_envs * h->cfg.num_vehicles;
+  const AliveLayout al = alive_layout(h->cfg);
+  KernelArgs r = a;
+  r.alive_list = nullptr;
+  r.alive_count = nullptr;
+  r.alive_segmented = 0;
+  r.first_only = 1;
+  r.keep_reward_done = p.is_step ? 1 : 0;
+  r.reset_all = (!p.is_step && mask == nullptr) ? 1 : 0;
+  r.env_mask = p.is_step ? nullptr : mask;
+  if (!p.is_step) {
+    launch(k_reset, p.veh_blocks, 0, stream, r);
+    launch(k_reset_env, p.env_blocks, 0, stream, r);
+  }
+  TailArgs t{};
+  t.commit = p.is_step ? 1 : 0;
+  t.grids = p.tail_grids ? 1 : 0;
+  t.groups = h->alive_blob + al.groups;
+  t.n_groups = h->alive_blob + al.group_count + SMX_SEG_STRIDE * h->group_parity;
+  t.n_groups_next = h->alive_blob + al.group_count + SMX_SEG_STRIDE * (h->group_parity ^ 1);
+  if (p.tail_builds_list) {  // (the next tick's parity is h->alive_parity now)
+    t.list = h->alive_blob;
+    t.seg_count = h->alive_blob + al.seg + (size_t)8 * SMX_SEG_STRIDE * h->seg_parity;
+    t.seg_next = h->alive_blob + al.seg + (size_t)8 * SMX_SEG_STRIDE * (h->seg_parity ^ 1);
+    t.flat_next = h->alive_blob + al.flat + h->alive_parity;
+    t.slow_next = SlowLists{h->slow_blob, total}.counters(h->alive_parity);
+  }
+  hipLaunchKernelGGL(k_tail, dim3(p.obs_blocks), dim3(SMX_BLOCK), p.tail_grids ? std::max(p.ogm_bytes, p.dagm_bytes) : 0, stream, r, t);
+  if (ph) SMX_HIP(hipEventRecord(ph[SMX_PHASE_COMMIT + 1], stream));
+  h->group_parity ^= 1;
+  h->list_ready = p.tail_builds_list;
+  if (p.tail_builds_list) {
+    h->seg_parity ^= 1;
+    h->list_state = *st;
+  }
+  if (p.reset_pass) {
+    if (p.road_waypoints)  // before k_first clears SMX_F_FIRST
+      launch(k_road_waypoints, smx_blocks(total * SMX_RW_LANE_CAP), 0, stream, r);
+    if (p.lidar_first) {
+      launch(k_lidar_first, (unsigned)std::min<size_t>(SMX_LIDAR_FIRST_BLOCKS, total), 0, stream, r);
+      r.lidar_blocks = 0;
+    }
+    r.walk_new = p.first_walks_new ? 1 : 0;
+    hipLaunchKernelGGL(k_first, dim3(p.obs_blocks), dim3(SMX_FIRST_BLOCK), 0, stream, r, t.groups, t.n_groups);
+  }
+  return SMX_OK;
+}
+
+// the argument block every kernel of the call starts from
+static KernelArgs kernel_args(smx_handle h, const TickPlan& p, const int8_t* actions, const float* actions_f32, const double* traj,
+                              const int32_t* traj_n, const uint8_t* mask, const smx_state* st, const smx_spawns* sp,
+                              const smx_outputs* out) {
+  const size_t total = (size_t)h->cfg.num_envs * h->cfg.num_vehicles;
   KernelArgs a;
-  a.cfg = c;
+  a.cfg = h->cfg;
   a.map = h->map;
   a.st = *st;
   a.sp = *sp;
@@ -5535,26 +5737,38 @@ static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const floa
   a.alive_list = nullptr;
   a.alive_count = nullptr;
   a.alive_segmented = 0;
-  const size_t total = (size_t)c.num_envs * c.num_vehicles;
   a.slow_list = nullptr;
   a.slow_count = nullptr;
   a.seed_pending = nullptr;
   a.seeds_carry = h->scan_carry;
   a.facts_carry = h->scan_carry ? h->scan_carry + 4 * total : nullptr;
-  const int veh_blocks = (int)((total + SMX_BLOCK - 1) / SMX_BLOCK);
-  // Small batches are bound by one wavefront's latency, so independent work is spread over more
-  // workgroups (k_scan halves as separate roles: 54 vs 70 us at 8 k vehicles; the OGM role inside
-  // k_sensors); large batches are bound by throughput, where the same tricks cost occupancy
-  // (131 k vehicles: k_scan 0.69 vs 0.52 ms split vs back-to-back, OGM inside k_sensors +6 %).
-  const bool small_batch = h->launch_strategy == SMX_LAUNCH_SMALL ||
-                           (h->launch_strategy == SMX_LAUNCH_AUTO && total <= SMX_LARGE_BATCH_VEHICLES) || SMX_SKIP(*h, 131072);
-  const int scan_split = (small_batch || SMX_SKIP(*h, 65536)) ? 1 : 0;
-  const int scan_blocks = (scan_split ? 2 : 1) * (int)((total * SMX_TEAM + SMX_BLOCK - 1) / SMX_BLOCK);
-  const int vpb = SMX_BLOCK / SMX_WP_LANES;
-  const int wp_blocks = (int)((total + vpb - 1) / vpb);
-  const int epb = SMX_BLOCK / c.num_vehicles;
-  const int obs_blocks = (c.num_envs + epb - 1) / epb;
-  const int env_blocks = (c.num_envs + SMX_BLOCK - 1) / SMX_BLOCK;
+  a.dagm_reach = h->dagm_reach;
+  a.wp_blocks = (int)p.wp_blocks;
+  a.obs_blocks = (int)p.obs_blocks;
+  a.lidar_blocks = (int)p.lidar_blocks;
+  return a;
+}
+
+static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const float* actions_f32, const double* traj,
+                   const int32_t* traj_n, const uint8_t* mask, const smx_state* st,
+                   const smx_spawns* sp, const smx_outputs* out, void* stream_) {
+  if (!h) return SMX_ERR_INVALID;
+  if (!h->map_loaded) return fail(h, SMX_ERR_STATE, "smx_load_map has not been called");
+  int rc = check_buffers(h, st, sp, out);
+  if (rc != SMX_OK) return rc;
+  if (is_step) {
+    const int sp_ = h->cfg.action_space;
+    const bool ok = sp_ == SMX_ACTION_SPACE_LANE ? actions != nullptr
+                    : sp_ == SMX_ACTION_SPACE_TRAJECTORY ? (traj != nullptr && traj_n != nullptr)
+                                                         : actions_f32 != nullptr;
+    if (!ok)
+      return fail(h, SMX_ERR_INVALID,
+                  "actions do not match cfg.action_space (smx_step: Lane, smx_step_trajectory: Trajectory, "
+                  "smx_step_continuous: the float spaces)");
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  const TickPlan p = tick_plan(plan_inputs(h, is_step, st));
+  KernelArgs a = kernel_args(h, p, actions, actions_f32, traj, traj_n, mask, st, sp, out);
   const bool timed = h->timing && is_step && h->ev_used < 65536;
   if (timed) {
     if (h->ev_pool.size() < 2 * (h->ev_used + 1)) {
@@ -5567,9 +5781,8 @@ static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const floa
     SMX_HIP(hipEventRecord(h->ev_pool[2 * h->ev_used], stream));
   }
   // phase timing (smx_set_timing level 2): one boundary event after every kernel of the tick
-  const bool phased = h->phase_timing && is_step && h->ph_used < 16384;
   hipEvent_t* ph = nullptr;
-  if (phased) {
+  if (p.phased) {
     const size_t need = (h->ph_used + 1) * (SMX_PHASE_COUNT + 1);
     while (h->ph_pool.size() < need) {
       hipEvent_t e;
@@ -5579,359 +5792,20 @@ static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const floa
     ph = &h->ph_pool[h->ph_used * (SMX_PHASE_COUNT + 1)];
     SMX_HIP(hipEventRecord(ph[0], stream));
   }
-#define SMX_PHASE_END(p) \
-  if (phased) SMX_HIP(hipEventRecord(ph[(p) + 1], stream))
-  const int lidar_blocks = (c.sensors & SMX_SENSOR_LIDAR) ? (int)total : 0;
-  // the OGM tile is dynamic LDS: on small batches, up to 16 KiB, it rides along in k_sensors; otherwise
-  // the OGM role gets its own launch
-  const size_t ogm_bytes = (c.sensors & SMX_SENSOR_OGM) ? (size_t)c.ogm_width * c.ogm_height : 0;
-  // (from SMX_OGM_ENV_MIN_VEHICLES on, the per-env kernel of the large form beats the per-observer role inside
-  // k_sensors even as a launch of its own on the same stream: a third of the instructions per tile)
-  const bool ogm_env_small = small_batch && total >= SMX_OGM_ENV_MIN_VEHICLES && c.num_vehicles <= 32 && ogm_bytes * SMX_OGM_WAVES * 2 <= 64 * 1024;
-  const bool ogm_inline = small_batch && ogm_bytes > 0 && ogm_bytes <= 16 * 1024 && !ogm_env_small;
-  const bool ogm_alone = ogm_bytes > 0 && !ogm_inline;
-  const size_t dagm_bytes = (c.sensors & SMX_SENSOR_DAGM) ? (size_t)c.dagm_width * c.dagm_height : 0;
-  a.dagm_reach = h->dagm_reach;
-  a.wp_blocks = wp_blocks;
-  a.obs_blocks = obs_blocks;
-  a.lidar_blocks = lidar_blocks;
-  const unsigned sensor_blocks = (unsigned)(wp_blocks + obs_blocks + lidar_blocks + (ogm_inline ? (int)total : 0));
-  const size_t sensor_lds = ogm_inline ? ogm_bytes : 0;
-  // one pass of scan + sensors + commit (the tick's, then the reset pass restricted to new vehicles)
-  // OGM tiles on their own: per env (four wavefronts share the env's poses) on large batches while four
-  // tiles fit a workgroup's LDS, else per observer
-  auto launch_ogm = [&](hipStream_t st_, const KernelArgs& k) {
-    if ((!small_batch || ogm_env_small) && c.num_vehicles <= 32 && ogm_bytes * SMX_OGM_WAVES * 2 <= 64 * 1024)
-      hipLaunchKernelGGL(k_ogm_env<2>, dim3((unsigned)c.num_envs), dim3(SMX_OGM_WAVES * 64), ogm_bytes * SMX_OGM_WAVES * 2, st_, k);
-    else if (!small_batch && ogm_bytes * SMX_OGM_WAVES <= 64 * 1024)
-      hipLaunchKernelGGL(k_ogm_env<1>, dim3((unsigned)c.num_envs), dim3(SMX_OGM_WAVES * 64), ogm_bytes * SMX_OGM_WAVES, st_, k);
-    else
-      hipLaunchKernelGGL(k_ogm, dim3((unsigned)total), dim3(SMX_BLOCK), ogm_bytes, st_, k);
-  };
-  const bool routed = h->missions.route_last != nullptr;  // some slot has a fixed route: the scan instance that knows them
-  bool fast_scan = false;  // the tick of a large batch (not its reset pass): one-lane scan kernels + teams over their slow lists
-  int slow_parity = 0;
-  // the large form's rows: k_wp_walk -> k_waypoints_emit while they fit the staged form, else k_waypoints, which reads
-  // every vehicle's seeds (no seed_pending) and so cannot run beside or ahead of the slow seeds chain
-  const bool staged_rows = (c.sensors & SMX_SENSOR_WAYPOINTS) && c.wp_paths <= SMX_WPT_MAX_PATHS && h->knots_blob;
-  auto observation_pass = [&](const KernelArgs& k, bool phases) -> int {
-    // Large batches, no per-kernel timing asked: the grid maps and the lidar (which read poses only) leave on
-    // side stream 0 at once and overlap the scan — kernels bound by their own write stream beside one bound by
-    // arithmetic and load latency; observe goes to side stream 1 after the scan, the waypoint kernels stay on
-    // the caller's stream; all are joined before k_tail.
-    const bool fork = !small_batch && !phased && h->side_ready;
-    hipStream_t s_grid = stream, s_obs = stream;
-    KernelArgs kf = k, ks = k, kwp = k;  // (kwp: the waypoint kernels, which pass over the slow chain's vehicles)
-    bool slow_chain_forked = false, slow_chain_pending = false, seeds_fork_recorded = false;
-    if (fork) {
-      (void)hipEventRecord(h->ev_fork_grid, stream);
-      (void)hipStreamWaitEvent(h->side[0], h->ev_fork_grid, 0);
-      s_grid = h->side[0];
-      s_obs = h->side[1];
-      if (ogm_alone) launch_ogm(s_grid, k);
-      if (dagm_bytes) hipLaunchKernelGGL(k_dagm, dim3((unsigned)total), dim3(SMX_BLOCK), dagm_bytes, s_grid, k);
-      if (lidar_blocks) hipLaunchKernelGGL(k_lidar, dim3((unsigned)lidar_blocks), dim3(SMX_BLOCK), 0, s_grid, k);
-    }
-    if (!small_batch) {
-      // the scan's halves as two launches, on two streams when forked: path seeds (-> waypoint kernels) on the
-      // caller's, road facts (-> observe) on side 1
-      const unsigned half_blocks = (unsigned)((total * SMX_TEAM_LARGE + SMX_BLOCK - 1) / SMX_BLOCK);
-      // (where the searches are long — lanes that split and cross: 4lane 2048 x 16 0.430 -> 0.393 ms; on loop the four-lane
-      // teams stay: 32 768 vehicles 0.260 either way, 65 536 0.371 against 0.378)
-      const bool wide_teams = h->map_junctions && total <= SMX_SCAN_WIDE_MAX_VEHICLES;
-      const unsigned wide_blocks = (unsigned)((total * SMX_TEAM + SMX_BLOCK - 1) / SMX_BLOCK);
-      const bool fast = fast_scan && k.alive_list != nullptr && !k.first_only && h->slow_blob && !SMX_SCAN_UNSEEDED;
-      const unsigned fast_blocks = (unsigned)((total + SMX_BLOCK - 1) / SMX_BLOCK);
-      kf = k;
-      ks = k;  // facts / seeds: each half appends to its own slow list
-      if (fast) {
-        int32_t* slow_counters = h->slow_blob + 4 * total + 4 * slow_parity;
-        kf.slow_list = h->slow_blob;
-        kf.slow_count = slow_counters;
-        ks.slow_list = h->slow_blob + total;
-        ks.slow_count = slow_counters + 1;
-      }
-      // path seeds without the ten-nearest list: agents with a route object and no fixed route, staged rows (past
-      // SMX_WPT_MAX_PATHS rows the team seeds kernel serves everybody, as in the teams cut)
-      const bool fast_seeds = !SMX_WP_STAGED && fast && !routed && staged_rows && h->pending_blob && one_lane_seeds(h);
-      if (fast_seeds) {
-        ks.seed_pending = h->pending_blob;
-        kwp.seed_pending = h->pending_blob;
-        hipLaunchKernelGGL(k_scan_fast<1>, dim3(fast_blocks), dim3(SMX_BLOCK), 0, stream, ks);
-        if (fork) {
-          // the slow chain — the few vehicles whose seeds take the searches from scratch, then their walks and rows by the
-          // serial emitter — runs beside the main chain (k_wp_walk -> k_waypoints_emit pass over those vehicles)
-          // (one event after the seeds half serves this fork and the facts half's below: every record on the caller's
-          // stream is a packet its next kernel waits behind, ten microseconds of the tick's longest chain)
-          (void)hipEventRecord(h->ev_fork, stream);
-          seeds_fork_recorded = true;
-          (void)hipStreamWaitEvent(h->side[2], h->ev_fork, 0);
-          if (h->map_junctions)
-            hipLaunchKernelGGL(k_scan_listed<1>, dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, h->side[2], ks);
-          else
-            hipLaunchKernelGGL((k_scan_listed<1, false, SMX_TEAM>), dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, h->side[2], ks);
-          if (!h->map_junctions && h->knots_blob) {
-            hipLaunchKernelGGL(k_waypoints_walk_listed, dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, h->side[2], ks);
-          } else {
-            hipLaunchKernelGGL(k_waypoints_listed, dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, h->side[2], ks);
-            if (h->knots_blob) hipLaunchKernelGGL(k_wp_walk_listed, dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, h->side[2], ks);
-          }
-          slow_chain_forked = true;
-        } else {
-          slow_chain_pending = true;  // (one stream: after the main waypoint kernels, below)
-        }
-      } else if (routed)
-        hipLaunchKernelGGL((k_scan_half<1, true>), dim3(half_blocks), dim3(SMX_BLOCK), 0, stream, k);
-      else if (wide_teams)
-        hipLaunchKernelGGL((k_scan_half<1, false, SMX_TEAM>), dim3(wide_blocks), dim3(SMX_BLOCK), 0, stream, k);
-      else
-        hipLaunchKernelGGL(k_scan_half<1>, dim3(half_blocks), dim3(SMX_BLOCK), 0, stream, k);
-      // the facts half (-> observe) has slack, the seeds half heads the tick's longest chain (-> walk -> rows): the
-      // facts half starts when the seeds half is done and then fills the chip beside the waypoint kernels, whose two
-      // wavefronts per SIMD leave it half empty (C4, ticks 20-220: 0.815 -> 0.792 ms)
-      // (late in a run, with 40 % of the agents alive, starting both halves together is 1.5 % faster; with 80 % alive
-      // it is 4 % slower)
-      // (at 32 768 vehicles — a quarter of the headline batch, one rank's shard at four GPUs — the chains are short and
-      // both halves start together: 0.241 against 0.249 ms; at 65 536 the order above wins, 0.294 against 0.300)
-      if (fork && total <= SMX_FACTS_EARLY_MAX) {
-        (void)hipStreamWaitEvent(h->side[1], h->ev_fork_grid, 0);
-      } else if (fork) {
-        if (!seeds_fork_recorded) (void)hipEventRecord(h->ev_fork, stream);
-        (void)hipStreamWaitEvent(h->side[1], h->ev_fork, 0);
-      }
-      if (fast) {
-        hipLaunchKernelGGL(k_scan_fast<0>, dim3(fast_blocks), dim3(SMX_BLOCK), 0, s_obs, kf);
-        hipLaunchKernelGGL(k_scan_listed<0>, dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, s_obs, kf);
-      } else if (wide_teams)
-        hipLaunchKernelGGL((k_scan_half<0, false, SMX_TEAM>), dim3(wide_blocks), dim3(SMX_BLOCK), 0, s_obs, k);
-      else
-        hipLaunchKernelGGL(k_scan_half<0>, dim3(half_blocks), dim3(SMX_BLOCK), 0, s_obs, k);  // (the facts half seeds no path)
-      // (holding the grid kernels back as well was slower: 0.81 -> 0.85 ms; they overlap the seeds half.  So was one fork
-      // event after the seeds half for the grid kernels too, one record less on the caller's stream: C4 0.556 -> 0.605 ms)
-    } else if (scan_split) {
-      if (routed)
-        hipLaunchKernelGGL((k_scan<true, true>), dim3(scan_blocks), dim3(SMX_BLOCK), 0, stream, k);
-      else
-        hipLaunchKernelGGL(k_scan<true>, dim3(scan_blocks), dim3(SMX_BLOCK), 0, stream, k);
-    } else {
-      if (routed)
-        hipLaunchKernelGGL((k_scan<false, true>), dim3(scan_blocks), dim3(SMX_BLOCK), 0, stream, k);
-      else
-        hipLaunchKernelGGL(k_scan<false>, dim3(scan_blocks), dim3(SMX_BLOCK), 0, stream, k);
-    }
-    if (phases && phased) (void)hipEventRecord(ph[SMX_PHASE_SCAN + 1], stream);
-    if (!fork) {
-      if (ogm_alone) launch_ogm(stream, k);
-      if (dagm_bytes) hipLaunchKernelGGL(k_dagm, dim3((unsigned)total), dim3(SMX_BLOCK), dagm_bytes, stream, k);
-    }
-    if (phases && phased) (void)hipEventRecord(ph[SMX_PHASE_OGM + 1], stream);
-    if (small_batch) {
-      hipLaunchKernelGGL(k_sensors, dim3(sensor_blocks), dim3(SMX_BLOCK), sensor_lds, stream, k);
-    } else {
-      // staged rows whenever the waypoints sensor is on and the rows fit that form
-      if (staged_rows) {
-        hipLaunchKernelGGL(k_wp_walk, dim3((unsigned)((total * SMX_WP_LANES + SMX_BLOCK - 1) / SMX_BLOCK)), dim3(SMX_BLOCK), 0, stream, kwp);
-#if SMX_WP_STAGED  // developer variant: round 2's staged rows
-        const size_t stage_bytes = std::max((size_t)c.wp_len * SMX_BLOCK * 16, (size_t)SMX_MAX_KNOTS * SMX_BLOCK * sizeof(int));
-        hipLaunchKernelGGL(k_waypoints_tables, dim3(wp_blocks), dim3(SMX_BLOCK), stage_bytes, stream, k);
-#else
-        if (fast_scan && k.alive_list != nullptr && h->slow_blob) {
-          KernelArgs kw = kwp;
-          kw.slow_list = h->slow_blob + 3 * total;
-          kw.slow_count = h->slow_blob + 4 * total + 4 * slow_parity + 3;
-          hipLaunchKernelGGL(k_waypoints_emit, dim3(wp_blocks), dim3(SMX_BLOCK), 0, stream, kw);
-          hipLaunchKernelGGL(k_waypoints_listed, dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, stream, kw);
-          if (slow_chain_pending) {
-            hipLaunchKernelGGL(k_scan_listed<1>, dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, stream, ks);
-            hipLaunchKernelGGL(k_waypoints_listed, dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, stream, ks);
-            if (h->knots_blob) hipLaunchKernelGGL(k_wp_walk_listed, dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, stream, ks);
-            slow_chain_pending = false;
-          }
-        } else {
-          const size_t stage_bytes = std::max((size_t)c.wp_len * SMX_BLOCK * 16, (size_t)SMX_MAX_KNOTS * SMX_BLOCK * sizeof(int));
-          hipLaunchKernelGGL(k_waypoints_tables, dim3(wp_blocks), dim3(SMX_BLOCK), stage_bytes, stream, k);
-        }
-#endif
-      } else
-        hipLaunchKernelGGL(k_waypoints, dim3(wp_blocks), dim3(SMX_BLOCK), 0, stream, k);
-      hipLaunchKernelGGL(k_observe, dim3(obs_blocks), dim3(SMX_BLOCK), 0, s_obs, k);
-      if (lidar_blocks && !fork) hipLaunchKernelGGL(k_lidar, dim3((unsigned)lidar_blocks), dim3(SMX_BLOCK), 0, stream, k);
-    }
-    if (fork) {
-      // (each side stream joins the caller's directly: chaining side 0 through side 1 puts one more hop behind the
-      // last kernel when k_observe ends the tick — 1 % late in a run)
-      for (int i = 0; i < (slow_chain_forked ? 3 : 2); ++i) {
-        (void)hipEventRecord(h->ev_join[i], h->side[i]);
-        (void)hipStreamWaitEvent(stream, h->ev_join[i], 0);
-      }
-    }
-    if (c.sensors & SMX_SENSOR_ROAD_WAYPOINTS)  // (poses are the tick's new ones; flags still those of its start)
-      hipLaunchKernelGGL(k_road_waypoints, dim3((unsigned)((total * SMX_RW_LANE_CAP + SMX_BLOCK - 1) / SMX_BLOCK)), dim3(SMX_BLOCK), 0,
-                         stream, k);
-    if (phases && phased) (void)hipEventRecord(ph[SMX_PHASE_SENSORS + 1], stream);
-    // (the pending vehicles' seeds, rows and trip meters would stay last tick's)
-    if (slow_chain_pending) return fail(h, SMX_ERR_STATE, "internal: the slow seeds chain was not launched");
-    return SMX_OK;
-  };
-  // the LDS-path form of k_control fits one wavefront per SIMD: only while the batch needs no more
-  const bool lds_path = small_batch && total * SMX_WP_LANES <= (size_t)1024 * 64;
-  if (is_step && c.num_social > 0 && c.social_model == SMX_SOCIAL_IDM)
-    hipLaunchKernelGGL(k_social, dim3(veh_blocks), dim3(SMX_BLOCK), 0, stream, a);
-  const bool two_launch_control = is_step && !small_batch && h->ctrl_blob;
-  const AliveLayout al = alive_layout(c);
-  // k_tail builds the next tick's alive list unless k_social moves vehicles (and can end them) ahead of the list
-  const bool build_list = !small_batch && h->alive_blob && h->slow_blob && !(c.num_social > 0 && c.social_model == SMX_SOCIAL_IDM);
-  if (is_step && !small_batch && h->alive_blob) {
-    int32_t* counters = h->alive_blob + al.flat;
-    int32_t* slow_counters = h->slow_blob + 4 * total;  // [parity][4]: facts, seeds, control, waypoint rows
-    if (h->list_ready && std::memcmp(&h->list_state, st, sizeof(smx_state)) == 0) {
-      // the list the last pass's k_tail built from these flags; it zeroed this tick's slow-list counters too
-      a.alive_list = h->alive_blob;
-      a.alive_count = h->alive_blob + al.seg + (size_t)8 * SMX_SEG_STRIDE * (h->seg_parity ^ 1);
-      a.alive_segmented = 1;
-    } else {
-      hipLaunchKernelGGL(k_alive_list, dim3((unsigned)((total + SMX_ALIVE_BLOCK - 1) / SMX_ALIVE_BLOCK)), dim3(SMX_ALIVE_BLOCK), 0, stream, a, h->alive_blob, counters + h->alive_parity,
-                         counters + (h->alive_parity ^ 1), slow_counters + 4 * (h->alive_parity ^ 1));
-      a.alive_list = h->alive_blob;
-      a.alive_count = counters + h->alive_parity;
-    }
-    // One lane per vehicle + slow lists where the slow lists stay short: a map whose lanes never split (loop: under 1 %
-    // of the vehicles).  Where lanes branch and cross, a third of the vehicles would take the lists' serial forms
-    // (minicity, 262 144 vehicles: 1.40 ms a tick against 0.9x with round 2's team kernels for everybody), so those
-    // maps keep the team kernels.
-    fast_scan = one_lane_cut(h);
-    slow_parity = h->alive_parity;
-    h->alive_parity ^= 1;
-  }
-  if (two_launch_control) {
-    // large batches: candidate paths by teams of four, then law + physics with one lane per vehicle
-    const CtrlHandoff ho = h->ctrl;
-    KernelArgs ac = a;  // the controller's slow list
-    if (fast_scan && h->slow_blob) {
-      ac.slow_list = h->slow_blob + 2 * total;
-      ac.slow_count = h->slow_blob + 4 * total + 4 * slow_parity + 2;
-    }
-    switch (c.action_space) {
-      case SMX_ACTION_SPACE_LANE:
-        if (fast_scan && h->slow_blob) {  // one lane per vehicle; the rest through the slow list (k_control_fast)
-          hipLaunchKernelGGL(k_control_fast<SMX_ACTION_SPACE_LANE>, dim3(veh_blocks), dim3(SMX_BLOCK), 0, stream, ac);
-          hipLaunchKernelGGL(k_control_listed<SMX_ACTION_SPACE_LANE>, dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, stream, ac, ho);
-        } else {
-          hipLaunchKernelGGL(k_control_paths<SMX_ACTION_SPACE_LANE>, dim3(wp_blocks), dim3(SMX_BLOCK), 0, stream, a, ho);
-          hipLaunchKernelGGL(k_control_law<SMX_ACTION_SPACE_LANE>, dim3(veh_blocks), dim3(SMX_BLOCK), 0, stream, a, ho);
-        }
-        break;
-      case SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED:
-        if (fast_scan && h->slow_blob) {
-          hipLaunchKernelGGL(k_control_fast<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED>, dim3(veh_blocks), dim3(SMX_BLOCK), 0, stream, ac);
-          hipLaunchKernelGGL(k_control_listed<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED>, dim3((unsigned)h->slow_blocks), dim3(SMX_BLOCK), 0, stream, ac, ho);
-        } else {
-          hipLaunchKernelGGL(k_control_paths<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED>, dim3(wp_blocks), dim3(SMX_BLOCK), 0, stream, a, ho);
-          hipLaunchKernelGGL(k_control_law<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED>, dim3(veh_blocks), dim3(SMX_BLOCK), 0, stream, a, ho);
-        }
-        break;
-      case SMX_ACTION_SPACE_CONTINUOUS:
-        hipLaunchKernelGGL(k_control_law<SMX_ACTION_SPACE_CONTINUOUS>, dim3(veh_blocks), dim3(SMX_BLOCK), 0, stream, a, ho);
-        break;
-      case SMX_ACTION_SPACE_ACTUATOR_DYNAMIC:
-        hipLaunchKernelGGL(k_control_law<SMX_ACTION_SPACE_ACTUATOR_DYNAMIC>, dim3(veh_blocks), dim3(SMX_BLOCK), 0, stream, a, ho);
-        break;
-      default:
-        hipLaunchKernelGGL(k_control_law<SMX_ACTION_SPACE_TRAJECTORY>, dim3(veh_blocks), dim3(SMX_BLOCK), 0, stream, a, ho);
-        break;
-    }
-  }
+  if (p.social) launch(k_social, p.veh_blocks, 0, stream, a);
+  alive_list(h, p, a, stream);
   if (is_step) {
-    if (!two_launch_control) switch (c.action_space) {
-      case SMX_ACTION_SPACE_LANE:
-        if (lds_path)
-          hipLaunchKernelGGL((k_control<SMX_ACTION_SPACE_LANE, true>), dim3(wp_blocks), dim3(SMX_BLOCK), 0, stream, a);
-        else
-          hipLaunchKernelGGL(k_control<SMX_ACTION_SPACE_LANE>, dim3(wp_blocks), dim3(SMX_BLOCK), 0, stream, a);
-        break;
-      case SMX_ACTION_SPACE_CONTINUOUS:
-        hipLaunchKernelGGL(k_control<SMX_ACTION_SPACE_CONTINUOUS>, dim3(wp_blocks), dim3(SMX_BLOCK), 0, stream, a);
-        break;
-      case SMX_ACTION_SPACE_ACTUATOR_DYNAMIC:
-        hipLaunchKernelGGL(k_control<SMX_ACTION_SPACE_ACTUATOR_DYNAMIC>, dim3(wp_blocks), dim3(SMX_BLOCK), 0, stream, a);
-        break;
-      case SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED:
-        if (lds_path)
-          hipLaunchKernelGGL((k_control<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED, true>), dim3(wp_blocks),
-                             dim3(SMX_BLOCK), 0, stream, a);
-        else
-          hipLaunchKernelGGL(k_control<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED>, dim3(wp_blocks), dim3(SMX_BLOCK), 0,
-                             stream, a);
-        break;
-      default:
-        hipLaunchKernelGGL(k_control<SMX_ACTION_SPACE_TRAJECTORY>, dim3(wp_blocks), dim3(SMX_BLOCK), 0, stream, a);
-        break;
-    }
-    SMX_PHASE_END(SMX_PHASE_CONTROL);
-    rc = observation_pass(a, true);
-    if (rc != SMX_OK) return rc;
+    launch_control(h, p, a, stream);
+    if (ph) SMX_HIP(hipEventRecord(ph[SMX_PHASE_CONTROL + 1], stream));
+    observation_pass(h, p, a, stream, ph);
   }
-  {
-    // the end of the pass: k_tail (the tick's commit, the new vehicles' grid tiles, the env groups with new vehicles,
-    // the next tick's alive list), then the reset pass over those groups (first observations of the new vehicles)
-    const bool reset_pass = !is_step || c.auto_reset;  // (in a step, k_tail's commit respawns the envs that ended)
-    KernelArgs r = a;
-    r.alive_list = nullptr;
-    r.alive_count = nullptr;
-    r.alive_segmented = 0;
-    r.first_only = 1;
-    r.keep_reward_done = is_step ? 1 : 0;
-    r.reset_all = (!is_step && mask == nullptr) ? 1 : 0;
-    r.env_mask = is_step ? nullptr : mask;
-    if (!is_step) {
-      hipLaunchKernelGGL(k_reset, dim3(veh_blocks), dim3(SMX_BLOCK), 0, stream, r);
-      hipLaunchKernelGGL(k_reset_env, dim3(env_blocks), dim3(SMX_BLOCK), 0, stream, r);
-    }
-    TailArgs t{};
-    t.commit = is_step ? 1 : 0;
-    t.grids = (reset_pass && (ogm_bytes || dagm_bytes)) ? 1 : 0;
-    t.groups = h->alive_blob + al.groups;
-    t.n_groups = h->alive_blob + al.group_count + SMX_SEG_STRIDE * h->group_parity;
-    t.n_groups_next = h->alive_blob + al.group_count + SMX_SEG_STRIDE * (h->group_parity ^ 1);
-    if (build_list) {  // (the next tick's parity is h->alive_parity now)
-      t.list = h->alive_blob;
-      t.seg_count = h->alive_blob + al.seg + (size_t)8 * SMX_SEG_STRIDE * h->seg_parity;
-      t.seg_next = h->alive_blob + al.seg + (size_t)8 * SMX_SEG_STRIDE * (h->seg_parity ^ 1);
-      t.flat_next = h->alive_blob + al.flat + h->alive_parity;
-      t.slow_next = h->slow_blob + 4 * total + 4 * h->alive_parity;
-    }
-    hipLaunchKernelGGL(k_tail, dim3(obs_blocks), dim3(SMX_BLOCK), t.grids ? std::max(ogm_bytes, dagm_bytes) : 0, stream, r, t);
-    SMX_PHASE_END(SMX_PHASE_COMMIT);
-    h->group_parity ^= 1;
-    h->list_ready = build_list;
-    if (build_list) {
-      h->seg_parity ^= 1;
-      h->list_state = *st;
-    }
-    if (reset_pass) {
-      if (c.sensors & SMX_SENSOR_ROAD_WAYPOINTS)  // before k_first clears SMX_F_FIRST
-        hipLaunchKernelGGL(k_road_waypoints, dim3((unsigned)((total * SMX_RW_LANE_CAP + SMX_BLOCK - 1) / SMX_BLOCK)), dim3(SMX_BLOCK), 0,
-                           stream, r);
-      if (lidar_blocks && !small_batch) {
-        // large batches: the new vehicles' lidar as a launch of its own instead of one after the other inside
-        // k_first — at C5 an env restart brings 64 new vehicles, whose serial lidar roles made the reset pass 0.58 ms
-        // of a 1.5 ms tick late in a run (many restarts per tick)
-        hipLaunchKernelGGL(k_lidar_first, dim3((unsigned)std::min<size_t>(SMX_LIDAR_FIRST_BLOCKS, total)), dim3(SMX_BLOCK), 0, stream, r);
-        r.lidar_blocks = 0;
-      }
-      // large batches: k_first also walks the new vehicles' knot lists, for the next tick's k_control_fast
-      // (only k_control_fast reads them: not on the maps that keep the team kernels)
-      r.walk_new = (!small_batch && one_lane_cut(h) && h->knots_blob && (c.sensors & SMX_SENSOR_WAYPOINTS) &&
-                    c.wp_paths <= SMX_WPT_MAX_PATHS) ? 1 : 0;
-      hipLaunchKernelGGL(k_first, dim3(obs_blocks), dim3(SMX_FIRST_BLOCK), 0, stream, r, t.groups, t.n_groups);
-    }
-  }
+  rc = tail_and_reset_pass(h, p, a, mask, st, stream, ph);
+  if (rc != SMX_OK) return rc;
   SMX_HIP(hipGetLastError());
-  if (phased) {
-    SMX_PHASE_END(SMX_PHASE_RESET);
+  if (ph) {
+    SMX_HIP(hipEventRecord(ph[SMX_PHASE_RESET + 1], stream));
     h->ph_used += 1;
   }
-#undef SMX_PHASE_END
   if (timed) {
     SMX_HIP(hipEventRecord(h->ev_pool[2 * h->ev_used + 1], stream));
     h->ev_used += 1;
@@ -5983,7 +5857,7 @@ extern "C" int smx_debug_slow_counts(smx_handle h, int32_t* out4) {
   if (!h->slow_blob) return fail(h, SMX_ERR_STATE, "no slow lists (the map is not loaded)");
   SMX_HIP(hipDeviceSynchronize());
   const size_t total = (size_t)h->cfg.num_envs * h->cfg.num_vehicles;
-  SMX_HIP(hipMemcpy(out4, h->slow_blob + 4 * total + 4 * (h->alive_parity ^ 1), 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  SMX_HIP(hipMemcpy(out4, SlowLists{h->slow_blob, total}.counters(h->alive_parity ^ 1), 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
   return SMX_OK;
 }
 

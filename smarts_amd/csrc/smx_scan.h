@@ -5,14 +5,8 @@
 // (wave64 cross-lane ops, no LDS).  Results are identical to the one-thread forms in
 // smx_roadmap.h: all reductions are exact minima with the same (value, table index) tie order.
 #pragma once
+#include "smx_plan.h"  // SMX_TEAM, SMX_TEAM_LARGE
 #include "smx_roadmap.h"
-
-#ifndef SMX_TEAM
-#define SMX_TEAM 8  // lanes per vehicle on small batches (one wavefront's latency); large batches: SMX_TEAM_LARGE
-#endif
-#ifndef SMX_TEAM_LARGE
-#define SMX_TEAM_LARGE 4  // fewer lanes repeat the per-vehicle uniform work (cell ranges, merges) at 131 k vehicles
-#endif
 
 template <int TEAM>
 __device__ __forceinline__ int team_rank() { return threadIdx.x & (TEAM - 1); }

@@ -1,4 +1,4 @@
-"""The LARGE launch form (smx_kernels.hip enqueue(); AUTO picks it above 16 384 vehicles) with every action space,
+"""The LARGE launch form (smx_plan.h tick_plan(); AUTO picks it above 16 384 vehicles) with every action space,
 social traffic, the grid maps, vias and the config variants, and the OGM kernel forms that only large batches reach.
 
 The large form has kernels and template instantiations of its own (k_control_fast / k_control_paths / k_control_law
@@ -316,7 +316,7 @@ def test_config_variants(variant, strategy, nets, compiled_maps):
     ("loop", 1, 8, 4, 185, (256, 256, 50 / 256), "large_one_lane"),        # the default grid: k_ogm per observer
 ])
 def test_ogm_kernel_forms(name, E, N, T, seed, grid, strategy, nets, compiled_maps):
-    """The large form's OGM tiles (launch_ogm in enqueue()) bit-exact against the oracle; every alive agent's own
+    """The large form's OGM tiles (TickPlan::ogm in smx_plan.h) bit-exact against the oracle; every alive agent's own
     footprint fills the 2 x 2 centre of its grid."""
     import torch
 

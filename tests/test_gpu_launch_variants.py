@@ -1,6 +1,6 @@
 """Launch variants of one tick that must not change a bit of it.
 
-The large form (smx_kernels.hip enqueue()) picks its launches at run time: the cut (one lane per vehicle or teams),
+The large form (smx_plan.h tick_plan(), issued by smx_kernels.hip enqueue()) picks its launches at run time: the cut (one lane per vehicle or teams),
 whether the one-lane path-seeds kernel and its slow seeds chain run, which row kernels run (k_wp_walk ->
 k_waypoints_emit up to SMX_WPT_MAX_PATHS = 8 rows, k_waypoints past them) and whether the grid maps, the lidar and the
 slow seeds chain leave on side streams or run on the caller's stream, as they do at per-kernel timing
