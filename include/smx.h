@@ -96,7 +96,13 @@ enum {
   SMX_ACTION_SPACE_CONTINUOUS = 1,
   SMX_ACTION_SPACE_ACTUATOR_DYNAMIC = 2,
   SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED = 3,
-  SMX_ACTION_SPACE_TRAJECTORY = 4 /* smx_step_trajectory: PD tracking (trajectory_tracking_controller.py:176-331) */
+  SMX_ACTION_SPACE_TRAJECTORY = 4, /* smx_step_trajectory: PD tracking (trajectory_tracking_controller.py:176-331) */
+  /* The kinematic spaces: the agent's vehicle is a box that a provider places (BoxChassis, chassis.py:187-320); no
+   * controller, no dynamics model. */
+  SMX_ACTION_SPACE_TARGET_POSE = 5,         /* smx_step_target_pose: MotionPlannerProvider + BezierMotionPlanner
+                                               (motion_planner_provider.py:65-129, bezier_motion_planner.py:38-121) */
+  SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME = 6 /* smx_step_trajectory_with_time: TrajectoryInterpolationProvider
+                                               (trajectory_interpolation_provider.py:96-193) */
 };
 
 #define SMX_MAX_ALIVE_LISTS 4
@@ -249,6 +255,14 @@ enum {
   SMX_S_PREV_X, SMX_S_PREV_Y,            /* position at the previous observation (driven-path segment) */
   SMX_S_COUNT
 };
+/* Agents of the kinematic action spaces have no dynamics model and no controller; their slots keep the provider's and
+ * BoxChassis' state in rows that only those read (as the social slots reuse SMX_S_MCL_X / _Y / SMX_S_SPD_INT):
+ *   SMX_S_U       = the provider's speed (VehicleState.speed; SMX_S_V and SMX_S_R stay 0)
+ *   SMX_S_DELTA   = TargetPose: the provider's own heading (MotionPlannerProvider._poses[:, 2], never re-normalised,
+ *                   motion_planner_provider.py:99), while SMX_S_HEADING holds Heading() of it (:109)
+ *   SMX_S_LAT_INT = BoxChassis._last_heading (chassis.py:211-217)
+ *   SMX_S_SPD_INT = BoxChassis._last_dt; 0 for a freshly created vehicle (the constructor's control(pose, speed)) */
+enum { SMX_S_KIN_RAW_HEADING = SMX_S_DELTA, SMX_S_KIN_LAST_HEADING = SMX_S_LAT_INT, SMX_S_KIN_LAST_DT = SMX_S_SPD_INT };
 enum {
   SMX_F_ALIVE = 1 << 0,
   SMX_F_MCL_SET = 1 << 1,
@@ -465,8 +479,21 @@ int smx_step_continuous(smx_handle h, const float* actions_dev, const smx_state*
 #define SMX_TRAJ_COLS 11
 int smx_step_trajectory(smx_handle h, const double* trajectories_dev, const int32_t* counts_dev, const smx_state* st,
                         const smx_spawns* sp, const smx_outputs* out, void* hip_stream);
-/* Waits for the stream, then reports what only the kernels could see: SMX_ERR_INVALID if a Lane action code
- * outside -1..3 was met since the last smx_sync (such an agent is stepped as if it had sent no action). */
+/* The same tick for ActionSpaceType.TargetPose.  targets[E*N][4] (float64, device): x, y, heading, seconds into the
+ * future at which the pose is wanted; a NaN x = no action this tick (the provider then aims at the pose it holds). */
+int smx_step_target_pose(smx_handle h, const double* targets_dev, const smx_state* st, const smx_spawns* sp,
+                         const smx_outputs* out, void* hip_stream);
+/* The same tick for ActionSpaceType.TrajectoryWithTime.  trajectories[E*N][5][max_points] (float64, device): rows time,
+ * x, y, heading, speed; counts[E*N] (int32, device) = points given, 0 = no action this tick (the vehicle is not
+ * updated at all). */
+int smx_step_trajectory_with_time(smx_handle h, const double* trajectories_dev, const int32_t* counts_dev,
+                                  int32_t max_points, const smx_state* st, const smx_spawns* sp, const smx_outputs* out,
+                                  void* hip_stream);
+/* Waits for the stream, then reports what only the kernels could see since the last smx_sync, as SMX_ERR_INVALID: a
+ * Lane action code outside -1..3; a TrajectoryWithTime action the reference raises on (fewer than two points or more
+ * than max_points, a value that is not finite, times not strictly increasing, no point later than dt or the first one
+ * already later); a TargetPose action that yields a pose that is not finite.  Such an agent is stepped as if it had
+ * sent no action. */
 int smx_sync(smx_handle h, void* hip_stream);
 /* Device-side timing: while enabled, every smx_step is bracketed by a hipEvent pair recorded on
  * the stream it is launched on (no synchronisation).  smx_read_step_ms waits for the recorded

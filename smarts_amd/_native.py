@@ -22,7 +22,8 @@ DONE_ON_SHOULDER, DONE_WRONG_WAY, DONE_NOT_MOVING = 8, 16, 32
 EVENT_NAMES = ["collisions", "off_road", "off_route", "on_shoulder", "wrong_way", "not_moving", "reached_goal",
                "reached_max_episode_steps", "agents_alive_done"]
 EV = {name.upper(): i for i, name in enumerate(EVENT_NAMES)}
-ACTION_SPACES = {"Lane": 0, "Continuous": 1, "ActuatorDynamic": 2, "LaneWithContinuousSpeed": 3, "Trajectory": 4}
+ACTION_SPACES = {"Lane": 0, "Continuous": 1, "ActuatorDynamic": 2, "LaneWithContinuousSpeed": 3, "Trajectory": 4,
+                 "TargetPose": 5, "TrajectoryWithTime": 6}
 TRAJ_COLS = 11
 SOCIAL_MODELS = {"constant": 0, "idm": 1}
 PHASES = ["control", "scan", "ogm", "sensors", "commit", "reset"]
@@ -138,7 +139,7 @@ def bind_buffer(struct, names, name, tensor):
 EXPORTS = [
     "smx_create", "smx_load_map", "smx_set_vias", "smx_set_missions", "smx_step_continuous", "smx_step_trajectory", "smx_read_phase_ms", "smx_set_lidar_rays", "smx_reset", "smx_step", "smx_sync", "smx_last_step_ms",
     "smx_set_timing", "smx_last_error", "smx_version", "smx_destroy", "smx_set_controller_gains", "smx_struct_size", "smx_read_step_ms",
-    "smx_check_buffers", "smx_set_launch_strategy", "smx_launch_form",
+    "smx_check_buffers", "smx_set_launch_strategy", "smx_launch_form", "smx_step_target_pose", "smx_step_trajectory_with_time",
 ]
 LAUNCH_FORMS = {0: "small", 1: "large_teams", 2: "large_one_lane"}
 LAUNCH_STRATEGIES = {"auto": 0, "small": 1, "large": 2, "large_one_lane": 3, "large_teams": 4}
@@ -198,6 +199,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.smx_set_missions.restype = C.c_int
     lib.smx_step_trajectory.argtypes = [h, _p, _p, C.POINTER(SmxState), C.POINTER(SmxSpawns), C.POINTER(SmxOutputs), _p]
     lib.smx_step_trajectory.restype = C.c_int
+    lib.smx_step_target_pose.argtypes = [h, _p, C.POINTER(SmxState), C.POINTER(SmxSpawns), C.POINTER(SmxOutputs), _p]
+    lib.smx_step_target_pose.restype = C.c_int
+    lib.smx_step_trajectory_with_time.argtypes = [h, _p, _p, _i32, C.POINTER(SmxState), C.POINTER(SmxSpawns),
+                                                  C.POINTER(SmxOutputs), _p]
+    lib.smx_step_trajectory_with_time.restype = C.c_int
     lib.smx_read_phase_ms.argtypes = [h, C.POINTER(C.c_float), _i32, C.POINTER(_i32)]
     lib.smx_read_phase_ms.restype = C.c_int
     lib.smx_set_timing.argtypes = [h, C.c_int]

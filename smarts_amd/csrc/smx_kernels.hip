@@ -53,6 +53,9 @@ struct KernelArgs {
   const float* actions_f32;  // float action spaces: [E*N][3]
   const double* traj;        // Trajectory space: [E*N][4][SMX_TRAJ_COLS]
   const int32_t* traj_n;     // ... true lengths, 0 = no action
+  // the kinematic spaces use the same two: TargetPose traj = [E*N][4] targets (traj_n null); TrajectoryWithTime
+  // traj = [E*N][5][traj_max], traj_n = points given
+  int traj_max;
   const uint8_t* env_mask;  // k_reset: explicit mask (NULL = use env_reset_pending / all)
   const double* lidar_rays;
   const smx_via* vias;          // device copy of smx_set_vias
@@ -85,7 +88,11 @@ struct KernelArgs {
   // [E*N], 1: the vehicle's path seeds, walks and rows are the slow chain's this tick (k_scan_fast<1> decides; null: none)
   uint8_t* seed_pending;
 };
-enum { SMX_DEVICE_BAD_LANE_ACTION = 1 };  // a Lane action code outside -1..3 was met (and treated as "no action")
+enum {
+  SMX_DEVICE_BAD_LANE_ACTION = 1,  // a Lane action code outside -1..3 was met (and treated as "no action")
+  SMX_DEVICE_BAD_TRAJECTORY = 2,   // a TrajectoryWithTime action the reference raises on (it moved nothing)
+  SMX_DEVICE_BAD_TARGET_POSE = 4   // a TargetPose action whose pose came out not finite (it moved nothing)
+};
 
 #define SF(field) a.st.f64[(size_t)(field) * total + gid]
 
@@ -967,6 +974,147 @@ template <int SPACE>
 __global__ void __launch_bounds__(SMX_BLOCK) k_control_law(const KernelArgs a, const CtrlHandoff ho) {
   control_law_for<SPACE>(a, ho, (size_t)blockIdx.x * SMX_BLOCK + threadIdx.x);
 }
+// =================================================================================
+// k_control_kinematic: the kinematic action spaces, one lane per vehicle, in the place of controller + vehicle_step.
+// The agent's vehicle is a box that a provider places (BoxChassis.control, chassis.py:211-217): the new pose and
+// speed go to the state rows, with the heading held before and the dt of the move for the ego read-back
+// (include/smx.h lists the rows).  All float64, in the reference's order of operations.
+// =================================================================================
+struct KinPose {
+  double x, y, heading, speed;
+};
+
+// MotionPlannerProvider.step -> BezierMotionPlanner.trajectory_batched(pose, target, n = 1, dt)
+// (motion_planner_provider.py:92-99, bezier_motion_planner.py:53-121); `heading` in and out is the provider's own
+// (_poses[:, 2]: never re-normalised).
+__device__ __forceinline__ KinPose bezier_first_point(double x, double y, double heading, double tx, double ty, double th,
+                                                      double seconds, double dt) {
+  const double extend = 0.9, bias = 0.5;
+  const double target_heading = th + SMX_PI * 0.5, current_heading = heading + SMX_PI * 0.5;
+  double tsn, tcs, csn, ccs;
+  sincos(target_heading, &tsn, &tcs);
+  sincos(current_heading, &csn, &ccs);
+  const double ex = tx - x, ey = ty - y;
+  const double extension = sqrt(ex * ex + ey * ey) * extend;
+  const double p0[2] = {x, y};
+  const double p1[2] = {x + ccs * extension * bias, y + csn * extension * bias};
+  const double p2[2] = {tx - tcs * extension * (1.0 - bias), ty - tsn * extension * (1.0 - bias)};
+  const double p3[2] = {tx, ty};
+  const double t = (1.0 * dt) / (seconds < dt ? dt : seconds);  // .clip(dt, None): a NaN stays one
+  auto linear = [t](double a, double b) { return (1.0 - t) * a + t * b; };
+  auto quadratic = [&](double a, double b, double c) { return linear(linear(a, b), linear(b, c)); };
+  double pos[2], tan[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    pos[q] = linear(quadratic(p0[q], p1[q], p2[q]), quadratic(p1[q], p2[q], p3[q]));
+    const double u = 1.0 - t;
+    tan[q] = 3.0 * (u * u) * (p1[q] - p0[q]) + 6.0 * u * t * (p2[q] - p1[q]) + 3.0 * (t * t) * (p3[q] - p2[q]);
+  }
+  const double correction = py_mod((target_heading - current_heading) + SMX_PI, SMX_TWO_PI) - SMX_PI;
+  KinPose o;
+  o.x = pos[0];
+  o.y = pos[1];
+  o.heading = current_heading + (py_mod(t * correction + SMX_PI, SMX_TWO_PI) - SMX_PI) - SMX_PI * 0.5;
+  o.speed = sqrt(tan[0] * tan[0] + tan[1] * tan[1]);
+  return o;
+}
+
+// TrajectoryInterpolationProvider.perform_trajectory_interpolation(dt, trajectory) (trajectory_interpolation_provider.py:
+// 96-193) on rows time, x, y, heading, speed of `stride` columns, n of them given.  False: the reference raises
+// (is_legal_trajectory :97-109, locate_motion_state :143-145).  (Its "stop here" branch for an infinite time,
+// :175-183, lies behind is_legal_trajectory's isfinite and cannot be reached.)
+__device__ __forceinline__ bool interpolate_trajectory(const double* tr, int n, int stride, double dt, KinPose& o) {
+  if (n < 2 || n > stride) return false;
+  bool legal = true;
+  int end = -1;  // the first column later than dt
+  double prev = 0.0;
+  for (int i = 0; i < n; ++i) {
+    const double ti = tr[i];
+#pragma unroll
+    for (int r = 0; r < 5; ++r) legal = legal && isfinite(tr[(size_t)r * stride + i]);
+    if (i > 0 && !(ti - prev > 0.0)) legal = false;
+    if (end < 0 && ti > dt) end = i;
+    prev = ti;
+  }
+  if (!legal || end < 1) return false;  // (none, or the first one already: no pair to blend)
+  const double* m0 = tr + (end - 1);
+  const double* m1 = tr + end;
+  const double ratio = fabs((dt - m0[0]) / (m1[0] - m0[0]));
+  const double u = 1.0 - ratio;
+  double s0, c0, s1, c1;
+  sincos(m0[(size_t)3 * stride], &s0, &c0);
+  sincos(m1[(size_t)3 * stride], &s1, &c1);
+  o.x = u * m0[(size_t)1 * stride] + ratio * m1[(size_t)1 * stride];
+  o.y = u * m0[(size_t)2 * stride] + ratio * m1[(size_t)2 * stride];
+  o.heading = atan2(u * s0 + ratio * s1, u * c0 + ratio * c1);
+  o.speed = u * m0[(size_t)4 * stride] + ratio * m1[(size_t)4 * stride];
+  return true;
+}
+
+template <int SPACE>
+__global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic(const KernelArgs a) {
+  const smx_config& c = a.cfg;
+  const size_t total = (size_t)c.num_envs * c.num_vehicles;
+  const size_t gid = (size_t)blockIdx.x * SMX_BLOCK + threadIdx.x;
+  if (gid >= total) return;
+  const int flags = a.st.flags[gid];
+  if (!(flags & SMX_F_ALIVE)) return;
+  if (flags & SMX_F_SOCIAL) {  // scripted lane follower, as in k_control
+    int lane = (int)SF(SMX_S_MCL_X), crossed = (int)SF(SMX_S_SPD_INT);
+    double offset = SF(SMX_S_MCL_Y), speed, x, y, heading;
+    SF(SMX_S_PREV_X) = SF(SMX_S_X);
+    SF(SMX_S_PREV_Y) = SF(SMX_S_Y);
+    const double cmd = c.social_model == SMX_SOCIAL_IDM ? SF(SMX_S_THROTTLE) : -1.0;
+    social_step(a.map, (int)(gid % c.num_vehicles), c.social_speed_factor, c.dt, lane, offset, crossed, speed, cmd);
+    social_pose(a.map, lane, offset, x, y, heading);
+    SF(SMX_S_X) = x;
+    SF(SMX_S_Y) = y;
+    SF(SMX_S_HEADING) = heading;
+    SF(SMX_S_U) = speed;
+    SF(SMX_S_MCL_X) = (double)lane;
+    SF(SMX_S_MCL_Y) = offset;
+    SF(SMX_S_SPD_INT) = (double)crossed;
+    return;
+  }
+  const double x = SF(SMX_S_X), y = SF(SMX_S_Y);
+  SF(SMX_S_PREV_X) = x;  // the position recorded by the previous observation
+  SF(SMX_S_PREV_Y) = y;
+  KinPose o;
+  if (SPACE == SMX_ACTION_SPACE_TARGET_POSE) {
+    const double raw = SF(SMX_S_KIN_RAW_HEADING);
+    const double* tp = a.traj + gid * 4;
+    double tx = tp[0], ty = tp[1], th = tp[2], seconds = tp[3];
+    bool given = !(tx != tx);
+    if (given) {
+      o = bezier_first_point(x, y, raw, tx, ty, th, seconds, c.dt);
+      if (!(isfinite(o.x) && isfinite(o.y) && isfinite(o.heading) && isfinite(o.speed))) {
+        // (the reference would carry the pose on and fail later; here it is reported at the next smx_sync and the
+        // agent is stepped as if it had sent nothing)
+        atomicOr(a.status, SMX_DEVICE_BAD_TARGET_POSE);
+        given = false;
+      }
+    }
+    // no target pose from the agent: the pose the provider holds, dt ahead (_normalize_target_pose, :119-129) — the
+    // vehicle stays, its speed is 0, and control() is still called
+    if (!given) o = bezier_first_point(x, y, raw, x, y, raw, c.dt, c.dt);
+    SF(SMX_S_KIN_RAW_HEADING) = o.heading;
+  } else {
+    const int n = a.traj_n[gid];
+    if (n == 0) return;  // no action: the vehicle is not updated (no control() call: _last_heading, _last_dt stay)
+    if (!interpolate_trajectory(a.traj + gid * (size_t)5 * a.traj_max, n, a.traj_max, c.dt, o)) {
+      atomicOr(a.status, SMX_DEVICE_BAD_TRAJECTORY);  // the reference raises; reported at the next smx_sync
+      return;
+    }
+  }
+  // Vehicle.control(pose, speed, dt) -> BoxChassis.control (vehicle.py:578, chassis.py:211-217)
+  SF(SMX_S_KIN_LAST_HEADING) = SF(SMX_S_HEADING);
+  SF(SMX_S_KIN_LAST_DT) = c.dt;
+  SF(SMX_S_X) = o.x;
+  SF(SMX_S_Y) = o.y;
+  SF(SMX_S_HEADING) = wrap_heading(o.heading);  // Heading(...) (coordinates.py:175-184)
+  SF(SMX_S_U) = o.speed;
+}
+
 // The vehicles k_control_fast left on its slow list (large batches), a fixed grid striding the list, whose length is only
 // known on the device: sixteen vehicles a round, their candidate paths by teams of four lanes, then, behind a barrier,
 // their control law + dynamics on sixteen lanes, the wanted path passed through the hand-off in device memory.  (One
@@ -3141,6 +3289,8 @@ __device__ __forceinline__ void respawn_vehicle(const KernelArgs& a, size_t gid,
   SF(SMX_S_Y) = sp[1];
   SF(SMX_S_HEADING) = wrap_heading(sp[2]);
   SF(SMX_S_U) = sp[3];
+  // kinematic spaces: MotionPlannerProvider.create_vehicle takes pose.heading (:164-168); _last_dt is 0
+  if (smx_kinematic_space(a.cfg.action_space)) SF(SMX_S_KIN_RAW_HEADING) = SF(SMX_S_HEADING);
   SF(SMX_S_PREV_X) = sp[0];
   SF(SMX_S_PREV_Y) = sp[1];
   int fl = SMX_F_ALIVE | SMX_F_FIRST;
@@ -3287,7 +3437,9 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
     }
   }
   const HeadingTrig trig = heading_trig(s.heading);
-  const double speed = vehicle_speed(s, trig);
+  // an agent of the kinematic spaces (uniform over the launch) reports the provider's speed (BoxChassis.speed)
+  const bool kinematic = smx_kinematic_space(c.action_space) && !(flags & SMX_F_SOCIAL);
+  const double speed = kinematic ? s.u : vehicle_speed(s, trig);
   if (local < SMX_BLOCK) {  // k_first runs this role in a wider workgroup: the extra threads hold nothing
     SharedPose& p = pose[local];
     p.x = s.x;
@@ -3374,19 +3526,40 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
 
     double lng, lat;
     long_lat_speed(s, trig, lng, lat);
+    double kin_av[2] = {0.0, 0.0}, kin_yaw_rate = 0.0;
+    if (kinematic) {
+      // BoxChassis.velocity_vectors / .yaw_rate (chassis.py:275-308): the linear velocity is the heading vector x speed;
+      // the "angular velocity" is the difference of the heading vectors over dt, as the reference has it; no yaw rate
+      // (None -> NaN) until control() has been called with a dt
+      double vhx, vhy;
+      radians_to_vec(s.heading, vhx, vhy);
+      lng = vhx * speed;
+      lat = vhy * speed;
+      const double last_dt = SF(SMX_S_KIN_LAST_DT), last_heading = SF(SMX_S_KIN_LAST_HEADING);
+      if (last_dt > 0.0) {
+        double lhx, lhy;
+        radians_to_vec(last_heading, lhx, lhy);
+        kin_av[0] = (vhx - lhx) / last_dt;
+        kin_av[1] = (vhy - lhy) / last_dt;
+        kin_yaw_rate = min_angles_difference_signed(s.heading, last_heading) / last_dt;
+      } else {
+        kin_yaw_rate = __builtin_nan("");
+      }
+    }
     // ---- ego lane (sensors.py:277-285): nearest lane within max(10, 2 * default lane width)
     const int ego_lane = (my_lane >= 0 && my_lane_dist < fmax(10.0, 2.0 * m.default_lane_width)) ? my_lane : -1;
     // ---- ego vehicle state (sensors.py:314-329; read-back of chassis.py:493-566)
     float* ef = stage.ego_f32[local];  // (ego_pos comes from the pose block)
     ef[SMX_EGO_HEADING] = (float)wrap_heading(s.heading);
     ef[SMX_EGO_SPEED] = (float)speed;
-    ef[SMX_EGO_STEERING] = (float)(-s.delta);
-    ef[SMX_EGO_YAW_RATE] = (float)vec_to_radians(0.0, 0.0);  // chassis.py:552-556 on a planar body
+    // (BoxChassis.steering is None: np.float32(None) = NaN, format_obs.py:432)
+    ef[SMX_EGO_STEERING] = kinematic ? __builtin_nanf("") : (float)(-s.delta);
+    ef[SMX_EGO_YAW_RATE] = kinematic ? (float)kin_yaw_rate : (float)vec_to_radians(0.0, 0.0);  // chassis.py:552-556 on a planar body
     ef[SMX_EGO_LIN_VEL + 0] = (float)lng;
     ef[SMX_EGO_LIN_VEL + 1] = (float)lat;
     ef[SMX_EGO_LIN_VEL + 2] = 0.0f;
-    ef[SMX_EGO_ANG_VEL + 0] = 0.0f;
-    ef[SMX_EGO_ANG_VEL + 1] = 0.0f;
+    ef[SMX_EGO_ANG_VEL + 0] = (float)kin_av[0];
+    ef[SMX_EGO_ANG_VEL + 1] = (float)kin_av[1];
     ef[SMX_EGO_ANG_VEL + 2] = (float)s.r;
     ef[SMX_EGO_BOX + 0] = (float)SMX_CHASSIS_LENGTH;
     ef[SMX_EGO_BOX + 1] = (float)SMX_CHASSIS_WIDTH;
@@ -4897,7 +5070,7 @@ static int create_impl(const smx_config* cfg, int device, smx_handle* out) {
     return fail(h, SMX_ERR_INVALID, "social_speed_factor must be >= 0");
   if (c.social_model != SMX_SOCIAL_CONSTANT && c.social_model != SMX_SOCIAL_IDM)
     return fail(h, SMX_ERR_INVALID, "unknown social_model");
-  if (c.action_space < SMX_ACTION_SPACE_LANE || c.action_space > SMX_ACTION_SPACE_TRAJECTORY)
+  if (c.action_space < SMX_ACTION_SPACE_LANE || c.action_space > SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME)
     return fail(h, SMX_ERR_INVALID, "unknown action_space");
   if ((c.sensors & SMX_SENSOR_OGM) &&
       (c.ogm_width < 1 || c.ogm_height < 1 || (c.ogm_width * c.ogm_height) % 16 != 0 ||
@@ -5475,10 +5648,11 @@ static KernelArgs with_slow(KernelArgs a, const SlowRef& slow) {
 struct ControlKernels {
   Kernel one, one_lds, fast;
   HandoffKernel listed, paths, law;
+  Kernel kinematic;  // (the kinematic spaces have this one alone)
 };
 template <int SPACE>
 static ControlKernels control_kernels_of() {
-  ControlKernels k{k_control<SPACE>, nullptr, nullptr, nullptr, nullptr, k_control_law<SPACE>};
+  ControlKernels k{k_control<SPACE>, nullptr, nullptr, nullptr, nullptr, k_control_law<SPACE>, nullptr};
   if constexpr (SPACE == SMX_ACTION_SPACE_LANE || SPACE == SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED) {
     k.one_lds = k_control<SPACE, true>;
     k.fast = k_control_fast<SPACE>;
@@ -5493,7 +5667,9 @@ static ControlKernels control_kernels(int action_space) {
     case SMX_ACTION_SPACE_CONTINUOUS: return control_kernels_of<SMX_ACTION_SPACE_CONTINUOUS>();
     case SMX_ACTION_SPACE_ACTUATOR_DYNAMIC: return control_kernels_of<SMX_ACTION_SPACE_ACTUATOR_DYNAMIC>();
     case SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED: return control_kernels_of<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED>();
-    default: return control_kernels_of<SMX_ACTION_SPACE_TRAJECTORY>();
+    case SMX_ACTION_SPACE_TRAJECTORY: return control_kernels_of<SMX_ACTION_SPACE_TRAJECTORY>();
+    case SMX_ACTION_SPACE_TARGET_POSE: return ControlKernels{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_control_kinematic<SMX_ACTION_SPACE_TARGET_POSE>};
+    default: return ControlKernels{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_control_kinematic<SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME>};
   }
 }
 
@@ -5514,6 +5690,7 @@ static void launch_control(smx_handle h, const TickPlan& p, const KernelArgs& a,
       launch(k.listed, p.slow_blocks, stream, ac, h->ctrl);
       break;
     }
+    case Control::KINEMATIC: launch(k.kinematic, p.veh_blocks, 0, stream, a); break;
   }
 }
 
@@ -5704,7 +5881,7 @@ static int tail_and_reset_pass(smx_handle h, const TickPlan& p, const KernelArgs
 
 // the argument block every kernel of the call starts from
 static KernelArgs kernel_args(smx_handle h, const TickPlan& p, const int8_t* actions, const float* actions_f32, const double* traj,
-                              const int32_t* traj_n, const uint8_t* mask, const smx_state* st, const smx_spawns* sp,
+                              const int32_t* traj_n, int32_t traj_max, const uint8_t* mask, const smx_state* st, const smx_spawns* sp,
                               const smx_outputs* out) {
   const size_t total = (size_t)h->cfg.num_envs * h->cfg.num_vehicles;
   KernelArgs a;
@@ -5717,6 +5894,7 @@ static KernelArgs kernel_args(smx_handle h, const TickPlan& p, const int8_t* act
   a.actions_f32 = actions_f32;
   a.traj = traj;
   a.traj_n = traj_n;
+  a.traj_max = traj_max;
   a.env_mask = mask;
   a.lidar_rays = h->lidar_rays;
   a.vias = h->n_vias > 0 ? h->vias_dev : nullptr;
@@ -5749,26 +5927,34 @@ static KernelArgs kernel_args(smx_handle h, const TickPlan& p, const int8_t* act
   return a;
 }
 
-static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const float* actions_f32, const double* traj,
-                   const int32_t* traj_n, const uint8_t* mask, const smx_state* st,
+// which entry point a call came through (each hands over its own pointers and leaves the others null)
+enum class Entry { RESET, LANE, FLOATS, TRAJECTORY, TARGET_POSE, TRAJECTORY_WITH_TIME };
+// (traj_max: columns per row of a TrajectoryWithTime action)
+static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const float* actions_f32, const double* traj,
+                   const int32_t* traj_n, int32_t traj_max, const uint8_t* mask, const smx_state* st,
                    const smx_spawns* sp, const smx_outputs* out, void* stream_) {
   if (!h) return SMX_ERR_INVALID;
   if (!h->map_loaded) return fail(h, SMX_ERR_STATE, "smx_load_map has not been called");
   int rc = check_buffers(h, st, sp, out);
   if (rc != SMX_OK) return rc;
+  const bool is_step = entry != Entry::RESET;
   if (is_step) {
     const int sp_ = h->cfg.action_space;
-    const bool ok = sp_ == SMX_ACTION_SPACE_LANE ? actions != nullptr
-                    : sp_ == SMX_ACTION_SPACE_TRAJECTORY ? (traj != nullptr && traj_n != nullptr)
-                                                         : actions_f32 != nullptr;
+    const bool ok = sp_ == SMX_ACTION_SPACE_LANE ? (entry == Entry::LANE && actions != nullptr)
+                    : sp_ == SMX_ACTION_SPACE_TRAJECTORY ? (entry == Entry::TRAJECTORY && traj != nullptr && traj_n != nullptr)
+                    : sp_ == SMX_ACTION_SPACE_TARGET_POSE ? (entry == Entry::TARGET_POSE && traj != nullptr)
+                    : sp_ == SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME
+                        ? (entry == Entry::TRAJECTORY_WITH_TIME && traj != nullptr && traj_n != nullptr)
+                        : (entry == Entry::FLOATS && actions_f32 != nullptr);
     if (!ok)
       return fail(h, SMX_ERR_INVALID,
                   "actions do not match cfg.action_space (smx_step: Lane, smx_step_trajectory: Trajectory, "
-                  "smx_step_continuous: the float spaces)");
+                  "smx_step_continuous: the float spaces, smx_step_target_pose: TargetPose, "
+                  "smx_step_trajectory_with_time: TrajectoryWithTime)");
   }
   hipStream_t stream = (hipStream_t)stream_;
   const TickPlan p = tick_plan(plan_inputs(h, is_step, st));
-  KernelArgs a = kernel_args(h, p, actions, actions_f32, traj, traj_n, mask, st, sp, out);
+  KernelArgs a = kernel_args(h, p, actions, actions_f32, traj, traj_n, traj_max, mask, st, sp, out);
   const bool timed = h->timing && is_step && h->ev_used < 65536;
   if (timed) {
     if (h->ev_pool.size() < 2 * (h->ev_used + 1)) {
@@ -5815,22 +6001,34 @@ static int enqueue(smx_handle h, bool is_step, const int8_t* actions, const floa
 
 extern "C" int smx_reset(smx_handle h, const uint8_t* env_mask_dev, const smx_state* st, const smx_spawns* sp,
                          const smx_outputs* out, void* hip_stream) {
-  return enqueue(h, false, nullptr, nullptr, nullptr, nullptr, env_mask_dev, st, sp, out, hip_stream);
+  return enqueue(h, Entry::RESET, nullptr, nullptr, nullptr, nullptr, 0, env_mask_dev, st, sp, out, hip_stream);
 }
 
 extern "C" int smx_step(smx_handle h, const int8_t* actions_dev, const smx_state* st, const smx_spawns* sp,
                         const smx_outputs* out, void* hip_stream) {
-  return enqueue(h, true, actions_dev, nullptr, nullptr, nullptr, nullptr, st, sp, out, hip_stream);
+  return enqueue(h, Entry::LANE, actions_dev, nullptr, nullptr, nullptr, 0, nullptr, st, sp, out, hip_stream);
 }
 
 extern "C" int smx_step_continuous(smx_handle h, const float* actions_dev, const smx_state* st, const smx_spawns* sp,
                                    const smx_outputs* out, void* hip_stream) {
-  return enqueue(h, true, nullptr, actions_dev, nullptr, nullptr, nullptr, st, sp, out, hip_stream);
+  return enqueue(h, Entry::FLOATS, nullptr, actions_dev, nullptr, nullptr, 0, nullptr, st, sp, out, hip_stream);
 }
 
 extern "C" int smx_step_trajectory(smx_handle h, const double* trajectories_dev, const int32_t* counts_dev,
                                    const smx_state* st, const smx_spawns* sp, const smx_outputs* out, void* hip_stream) {
-  return enqueue(h, true, nullptr, nullptr, trajectories_dev, counts_dev, nullptr, st, sp, out, hip_stream);
+  return enqueue(h, Entry::TRAJECTORY, nullptr, nullptr, trajectories_dev, counts_dev, 0, nullptr, st, sp, out, hip_stream);
+}
+
+extern "C" int smx_step_target_pose(smx_handle h, const double* targets_dev, const smx_state* st, const smx_spawns* sp,
+                                    const smx_outputs* out, void* hip_stream) {
+  return enqueue(h, Entry::TARGET_POSE, nullptr, nullptr, targets_dev, nullptr, 0, nullptr, st, sp, out, hip_stream);
+}
+
+extern "C" int smx_step_trajectory_with_time(smx_handle h, const double* trajectories_dev, const int32_t* counts_dev,
+                                             int32_t max_points, const smx_state* st, const smx_spawns* sp,
+                                             const smx_outputs* out, void* hip_stream) {
+  if (h && max_points < 2) return fail(h, SMX_ERR_INVALID, "smx_step_trajectory_with_time: max_points < 2");
+  return enqueue(h, Entry::TRAJECTORY_WITH_TIME, nullptr, nullptr, trajectories_dev, counts_dev, max_points, nullptr, st, sp, out, hip_stream);
 }
 
 extern "C" int smx_sync(smx_handle h, void* hip_stream) {
@@ -5845,6 +6043,15 @@ extern "C" int smx_sync(smx_handle h, void* hip_stream) {
         return fail(h, SMX_ERR_INVALID,
                     "a Lane action code outside -1..3 reached smx_step since the last smx_sync; the agents that sent one "
                     "were stepped as if they had sent no action");
+      if (bits & SMX_DEVICE_BAD_TRAJECTORY)
+        return fail(h, SMX_ERR_INVALID,
+                    "an illegal TrajectoryWithTime action reached smx_step_trajectory_with_time since the last smx_sync (fewer "
+                    "than two points or more than max_points, a value that is not finite, times not strictly increasing, no "
+                    "point later than dt or the first one already later); the agents that sent one were not moved");
+      if (bits & SMX_DEVICE_BAD_TARGET_POSE)
+        return fail(h, SMX_ERR_INVALID,
+                    "a TargetPose action whose pose is not finite reached smx_step_target_pose since the last smx_sync; the "
+                    "agents that sent one were stepped as if they had sent no action");
     }
   }
   return SMX_OK;

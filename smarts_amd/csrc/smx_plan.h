@@ -77,8 +77,13 @@ struct PlanInputs {
 enum class AliveList : uint8_t { NONE, CARRIED, BUILD };  // BUILD: k_alive_list ahead of the tick
 // ONE / ONE_LDS: k_control (the LDS-path form fits one wavefront per SIMD: only while the batch needs no more);
 // large batches: candidate paths by teams of four, then law + physics with one lane per vehicle (PATHS_LAW), the float
-// spaces and Trajectory the law alone (LAW); FAST_LISTED: one lane per vehicle, the rest through the slow list
-enum class Control : uint8_t { NONE, ONE, ONE_LDS, PATHS_LAW, LAW, FAST_LISTED };
+// spaces and Trajectory the law alone (LAW); FAST_LISTED: one lane per vehicle, the rest through the slow list;
+// KINEMATIC: the kinematic spaces' k_control_kinematic, one lane per vehicle in either form (no candidate paths, no
+// control slow list)
+enum class Control : uint8_t { NONE, ONE, ONE_LDS, PATHS_LAW, LAW, FAST_LISTED, KINEMATIC };
+static constexpr bool smx_kinematic_space(int action_space) {
+  return action_space == SMX_ACTION_SPACE_TARGET_POSE || action_space == SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME;
+}
 // SCAN: the small form's k_scan (both halves); large form: the one-lane kernel (+ slow list / chain), k_scan_half with the
 // routed instance, with eight lanes a vehicle, with four
 enum class Seeds : uint8_t { SCAN, ONE_LANE, ROUTED, WIDE, FOUR };
@@ -172,12 +177,14 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
     int32_t* const counters = in.slow.counters(in.slow_parity);
     p.facts_slow = {in.slow.list(SlowLists::FACTS), counters + SlowLists::FACTS};
     p.seeds_slow = {in.slow.list(SlowLists::SEEDS), counters + SlowLists::SEEDS};
-    p.control_slow = {in.slow.list(SlowLists::CONTROL), counters + SlowLists::CONTROL};
+    if (!smx_kinematic_space(c.action_space)) p.control_slow = {in.slow.list(SlowLists::CONTROL), counters + SlowLists::CONTROL};
     p.rows_slow = {in.slow.list(SlowLists::ROWS), counters + SlowLists::ROWS};
   }
   const bool lane_space = c.action_space == SMX_ACTION_SPACE_LANE || c.action_space == SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED;
   if (!in.is_step)
     p.control = Control::NONE;
+  else if (smx_kinematic_space(c.action_space))
+    p.control = Control::KINEMATIC;
   else if (!small && in.ctrl_blob)
     p.control = !lane_space ? Control::LAW : one_lane ? Control::FAST_LISTED : Control::PATHS_LAW;
   else

@@ -64,7 +64,9 @@ class SimConfig:
     num_social: int = 0  # scripted social vehicles: the last num_social slots of every env (include/smx.h)
     social_speed_factor: float = 0.8
     social_model: str = "constant"  # "constant" | "idm" (include/smx.h SMX_SOCIAL_*)
-    action_space: str = "Lane"  # ActionSpaceType name: Lane | Continuous | ActuatorDynamic | LaneWithContinuousSpeed
+    # ActionSpaceType name: Lane | Continuous | ActuatorDynamic | LaneWithContinuousSpeed | Trajectory | TargetPose |
+    # TrajectoryWithTime (the last two: kinematic agents, placed by a provider instead of driven through a controller)
+    action_space: str = "Lane"
     launch_strategy: str = "auto"  # "auto" | "small" | "large": how a tick is cut into launches (include/smx.h)
     # RoadWaypoints (agent_interface.py RoadWaypoints.horizon = 32; sensors.py:991-1040): dense rows keep the first
     # rw_lanes lanes and the first rw_paths paths of each, 2 x horizon + 1 waypoints per path
@@ -495,6 +497,10 @@ class BatchedSim:
             raise RuntimeError("step() before reset()")  # SMARTSNotSetupError (smarts.py:207-208)
         if self.cfg.action_space == "Trajectory":
             raise ValueError("ActionSpaceType.Trajectory steps through step_trajectory(trajectories, counts)")
+        if self.cfg.action_space == "TargetPose":
+            raise ValueError("ActionSpaceType.TargetPose steps through step_target_pose(targets)")
+        if self.cfg.action_space == "TrajectoryWithTime":
+            raise ValueError("ActionSpaceType.TrajectoryWithTime steps through step_trajectory_with_time(trajectories, counts)")
         lane = self.cfg.action_space == "Lane"
         want_dtype, want_shape = (torch.int8, (self.E, self.N)) if lane else (torch.float32, (self.E, self.N, 3))
         if actions.dtype != want_dtype or actions.device != self.device or not actions.is_contiguous():
@@ -539,6 +545,47 @@ class BatchedSim:
         rc = self.lib.smx_step_trajectory(self.handle, trajectories.data_ptr(), counts.data_ptr(), C.byref(self._st),
                                           C.byref(self._sp), C.byref(self._out), self._stream_ptr())
         nat.check(self.lib, self.handle, rc, "smx_step_trajectory")
+        return self.out
+
+    def step_target_pose(self, targets: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """One tick in ActionSpaceType.TargetPose: ``targets`` float64 [E, N, 4] = x, y, heading, seconds into the
+        future at which the pose is wanted; NaN in x = no action this tick (include/smx.h)."""
+        if not self._was_reset:
+            raise RuntimeError("step() before reset()")
+        if self.cfg.action_space != "TargetPose":
+            raise ValueError("step_target_pose needs SimConfig(action_space='TargetPose')")
+        targets = targets.to(device=self.device, dtype=torch.float64).contiguous()
+        if tuple(targets.shape) != (self.E, self.N, 4):
+            raise ValueError(f"TargetPose actions must have shape {(self.E, self.N, 4)}, got {tuple(targets.shape)}")
+        self._learner_k ^= 1
+        self.out["learner"] = self._learner[self._learner_k]
+        self._out.learner = self.out["learner"].data_ptr()
+        rc = self.lib.smx_step_target_pose(self.handle, targets.data_ptr(), C.byref(self._st), C.byref(self._sp),
+                                           C.byref(self._out), self._stream_ptr())
+        nat.check(self.lib, self.handle, rc, "smx_step_target_pose")
+        return self.out
+
+    def step_trajectory_with_time(self, trajectories: torch.Tensor, counts: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """One tick in ActionSpaceType.TrajectoryWithTime: ``trajectories`` float64 [E, N, 5, T] with rows time, x,
+        y, heading, speed, ``counts`` int32 [E, N] = points given (0 = no action).  A trajectory the reference
+        raises on moves nothing and is reported by the next ``sync()``."""
+        if not self._was_reset:
+            raise RuntimeError("step() before reset()")
+        if self.cfg.action_space != "TrajectoryWithTime":
+            raise ValueError("step_trajectory_with_time needs SimConfig(action_space='TrajectoryWithTime')")
+        trajectories = trajectories.to(device=self.device, dtype=torch.float64).contiguous()
+        counts = counts.to(device=self.device, dtype=torch.int32).contiguous()
+        if (trajectories.ndim != 4 or tuple(trajectories.shape[:3]) != (self.E, self.N, 5) or trajectories.shape[3] < 2
+                or tuple(counts.shape) != (self.E, self.N)):
+            raise ValueError(f"TrajectoryWithTime actions must have shapes {(self.E, self.N, 5, 'T >= 2')} and "
+                             f"{(self.E, self.N)}, got {tuple(trajectories.shape)} and {tuple(counts.shape)}")
+        self._learner_k ^= 1
+        self.out["learner"] = self._learner[self._learner_k]
+        self._out.learner = self.out["learner"].data_ptr()
+        rc = self.lib.smx_step_trajectory_with_time(self.handle, trajectories.data_ptr(), counts.data_ptr(),
+                                                    int(trajectories.shape[3]), C.byref(self._st), C.byref(self._sp),
+                                                    C.byref(self._out), self._stream_ptr())
+        nat.check(self.lib, self.handle, rc, "smx_step_trajectory_with_time")
         return self.out
 
     def set_timing(self, level):

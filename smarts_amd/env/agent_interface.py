@@ -28,9 +28,11 @@ class ActionSpaceType(Enum):
     Imitation = 9
 
 
-# action spaces with a device controller (include/smx.h SMX_ACTION_SPACE_*)
+# action spaces on the device (include/smx.h SMX_ACTION_SPACE_*): a controller in front of the dynamics model, or —
+# TargetPose, TrajectoryWithTime — a kinematic vehicle placed by a provider
 DEVICE_ACTION_SPACES = (ActionSpaceType.Lane, ActionSpaceType.Continuous, ActionSpaceType.ActuatorDynamic,
-                        ActionSpaceType.LaneWithContinuousSpeed, ActionSpaceType.Trajectory)
+                        ActionSpaceType.LaneWithContinuousSpeed, ActionSpaceType.Trajectory,
+                        ActionSpaceType.TargetPose, ActionSpaceType.TrajectoryWithTime)
 
 
 @dataclass
@@ -224,7 +226,8 @@ class AgentInterface:
     # ------------------------------------------------------------------ device support
     def validate_for_device(self):
         """Raise for anything the MI355X path does not implement (the Lane,
-        Continuous, ActuatorDynamic, LaneWithContinuousSpeed and Trajectory action spaces and the waypoints /
+        Continuous, ActuatorDynamic, LaneWithContinuousSpeed, Trajectory, TargetPose and TrajectoryWithTime action spaces
+        and the waypoints /
         neighbourhood / accelerometer / OGM / drivable-area grid map / lidar / road-waypoints sensors)."""
         # action=None (AgentType.Buddha) needs no controller: the vehicle is never given a command
         if self.action is not None and self.action not in DEVICE_ACTION_SPACES:

@@ -236,7 +236,10 @@ class BatchCore:
 
         from ..engine import pack_trajectory
 
-        if self.interface.action is not ActionSpaceType.Trajectory:
+        space = self.interface.action
+        if space is ActionSpaceType.TargetPose or space is ActionSpaceType.TrajectoryWithTime:
+            return self._step_kinematic(per_env_actions)
+        if space is not ActionSpaceType.Trajectory:
             acts = self.encode_actions(per_env_actions)
             return self.step_dense(torch.from_numpy(acts).to(self.sim.device))
         # ActionSpaceType.Trajectory: (xs, ys, headings, speeds) per agent (controllers/__init__.py:104-110)
@@ -256,6 +259,42 @@ class BatchCore:
         if not self._was_reset:
             raise SMARTSNotSetupError("Must call reset() or setup() before stepping.")
         return self.sim.step_trajectory(torch.from_numpy(packed), torch.from_numpy(counts))
+
+    def _step_kinematic(self, per_env_actions: Sequence[Dict[str, Any]]):
+        """TargetPose: ``[x, y, heading, seconds into the future]`` per agent (motion_planner_provider.py:65-78);
+        TrajectoryWithTime: a ``5 x T`` array of rows time, x, y, heading, speed
+        (trajectory_interpolation_provider.py:31-38).  ``None`` = no action this tick."""
+        import torch
+
+        slots = self.N + self.num_social
+        adapted: Dict[Tuple[int, int], np.ndarray] = {}
+        for e, agent_actions in enumerate(per_env_actions):
+            assert isinstance(agent_actions, dict) and all(isinstance(k, str) for k in agent_actions), \
+                "Expected Dict[str, any]"  # hiway_env.py:232-234
+            for agent_id, action in agent_actions.items():
+                a = self.agent_specs[agent_id].action_adapter(action)
+                if a is not None:
+                    adapted[e, self.agent_ids.index(agent_id)] = np.asarray(a, dtype=np.float64)
+        self._check_alive()
+        if not self._was_reset:
+            raise SMARTSNotSetupError("Must call reset() or setup() before stepping.")
+        if self.interface.action is ActionSpaceType.TargetPose:
+            targets = np.full((self.E, slots, 4), np.nan, dtype=np.float64)  # NaN x = no action
+            for (e, i), a in adapted.items():
+                if a.shape != (4,):
+                    raise ValueError(f"TargetPose expects [x, y, heading, seconds_into_future], got shape {a.shape}")
+                targets[e, i] = a
+            return self.sim.step_target_pose(torch.from_numpy(targets))
+        for a in adapted.values():
+            if a.ndim != 2 or a.shape[0] != 5:
+                raise ValueError(f"TrajectoryWithTime expects a 5 x T array (time, x, y, heading, speed), got shape {a.shape}")
+        # (a trajectory of one point is handed on as it is: the device refuses it as the reference does, at the next sync)
+        width = max([2] + [a.shape[1] for a in adapted.values()])
+        trajs = np.zeros((self.E, slots, 5, width), dtype=np.float64)
+        counts = np.zeros((self.E, slots), dtype=np.int32)  # 0 = no action
+        for (e, i), a in adapted.items():
+            trajs[e, i, :, :a.shape[1]], counts[e, i] = a, a.shape[1]
+        return self.sim.step_trajectory_with_time(torch.from_numpy(trajs), torch.from_numpy(counts))
 
     def encode_actions(self, per_env_actions: Sequence[Dict[str, Any]]) -> np.ndarray:
         space = self.interface.action

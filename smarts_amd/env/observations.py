@@ -128,8 +128,8 @@ class EgoVehicleObservation(NamedTuple):
     bounding_box: Dimensions
     heading: Heading
     speed: float
-    steering: float
-    yaw_rate: float
+    steering: Optional[float]  # None for a kinematic vehicle (BoxChassis.steering, chassis.py:298-300)
+    yaw_rate: Optional[float]  # None until a kinematic vehicle has been moved with a dt (chassis.py:302-308)
     road_id: Optional[str]
     lane_id: Optional[str]
     lane_index: Optional[int]
@@ -298,8 +298,9 @@ class ObservationBuilder:
             bounding_box=Dimensions(*[float(x) for x in f[E["BOX"]:E["BOX"] + 3]]),
             heading=Heading(float(f[E["HEADING"]])),
             speed=float(f[E["SPEED"]]),
-            steering=float(f[E["STEERING"]]),
-            yaw_rate=float(f[E["YAW_RATE"]]),
+            # (the dense row holds NaN where the reference has None: np.float32(None), format_obs.py:432)
+            steering=None if np.isnan(f[E["STEERING"]]) else float(f[E["STEERING"]]),
+            yaw_rate=None if np.isnan(f[E["YAW_RATE"]]) else float(f[E["YAW_RATE"]]),
             road_id=road_id, lane_id=lane_id, lane_index=lane_index,
             mission=(self.missions[slot] if slot < len(self.missions) and self.missions[slot] is not None else EndlessMission()),
             linear_velocity=v3("LIN_VEL"), angular_velocity=v3("ANG_VEL"),
