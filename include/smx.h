@@ -460,6 +460,32 @@ typedef struct smx_mission {
 } smx_mission;
 int smx_set_missions(smx_handle h, const smx_mission* missions_host, int32_t n_slots, const int32_t* route_roads_host,
                      int32_t n_route_roads);
+/* Goal kinds of the agent slots beyond the PositionalGoal of smx_set_missions.  A call of its own, after
+ * smx_set_missions (which leaves every slot SMX_GOAL_POSITIONAL): n_slots = 0 clears, else n_slots = cfg.num_vehicles.
+ *  - SMX_GOAL_POSITIONAL: what smx_set_missions set (num_laps and route_length are not read).
+ *  - SMX_GOAL_LAP (plan.py:252-277, LapMission.is_complete): the slot has a fixed route and a PositionalGoal from
+ *    smx_set_missions; reached_goal = inside the goal radius AND distance_travelled > route_length * num_laps, the
+ *    trip meter's total after this tick's waypoint (sensors.py:491-496).  num_laps >= 1, route_length finite, >= 0.
+ *  - SMX_GOAL_TRAVERSE (plan.py:127-166, TraverseGoal._drove_off_map): the slot has an empty route
+ *    (smx_mission.route_len = 0); reached_goal = the vehicle has left the map beyond the end of a dead-end lane,
+ *    heading within pi/6 of the lane's end heading.  Needs the two per-lane facts below.
+ * lane_end_heading[n_lanes] (vec_to_radians of the lane's vector_at_offset(length - 0.1), from the host's libm) and
+ * lane_dead_end[n_lanes] (1: no outgoing lanes, via lanes counted as outgoing; sumo_road_network.py:351-358) are
+ * read only when some slot is SMX_GOAL_TRAVERSE (else they may be NULL, n_lanes 0); n_lanes = the map's.  Host
+ * pointers; the handle keeps a device copy (12 bytes a lane), dropped by smx_set_missions and smx_load_map.
+ * smx_check_mission_goals is the validation alone, callable without a device or a handle (map_lanes: the lane
+ * count of the map the table is for): SMX_OK, or SMX_ERR_INVALID with the reason in err[err_len]. */
+enum { SMX_GOAL_POSITIONAL = 0, SMX_GOAL_LAP = 1, SMX_GOAL_TRAVERSE = 2 };
+typedef struct smx_mission_goal {
+  int32_t kind;         /* SMX_GOAL_* */
+  int32_t num_laps;     /* SMX_GOAL_LAP */
+  double route_length;  /* SMX_GOAL_LAP: Route.road_length of the lap (scenario.py:715-746) */
+} smx_mission_goal;
+int smx_check_mission_goals(const smx_mission_goal* goals_host, int32_t n_slots, int32_t num_vehicles,
+                            const double* lane_end_heading_host, const int32_t* lane_dead_end_host, int32_t n_lanes,
+                            int32_t map_lanes, char* err, uint64_t err_len);
+int smx_set_mission_goals(smx_handle h, const smx_mission_goal* goals_host, int32_t n_slots,
+                          const double* lane_end_heading_host, const int32_t* lane_dead_end_host, int32_t n_lanes);
 /* Base ray directions (device, [lidar_rays][3]); reference lidar.py:89-113 */
 int smx_set_lidar_rays(smx_handle h, const double* rays_dev, int32_t n_rays);
 /* Re-initialise the envs whose mask byte is non-zero (NULL = all) from the spawn

@@ -97,6 +97,13 @@ class SmxMission(C.Structure):
     _fields_ = [("goal_x", _f64), ("goal_y", _f64), ("goal_radius", _f64), ("route_off", _i32), ("route_len", _i32)]
 
 
+GOAL_POSITIONAL, GOAL_LAP, GOAL_TRAVERSE = 0, 1, 2  # SMX_GOAL_*
+
+
+class SmxMissionGoal(C.Structure):
+    _fields_ = [("kind", _i32), ("num_laps", _i32), ("route_length", _f64)]
+
+
 class SmxSpawns(C.Structure):
     _fields_ = [("episodes", _i32), ("pose", _p), ("social", _p), ("pose_count", C.c_uint64), ("social_count", C.c_uint64)]
 
@@ -140,6 +147,7 @@ EXPORTS = [
     "smx_create", "smx_load_map", "smx_set_vias", "smx_set_missions", "smx_step_continuous", "smx_step_trajectory", "smx_read_phase_ms", "smx_set_lidar_rays", "smx_reset", "smx_step", "smx_sync", "smx_last_step_ms",
     "smx_set_timing", "smx_last_error", "smx_version", "smx_destroy", "smx_set_controller_gains", "smx_struct_size", "smx_read_step_ms",
     "smx_check_buffers", "smx_set_launch_strategy", "smx_launch_form", "smx_step_target_pose", "smx_step_trajectory_with_time",
+    "smx_set_mission_goals", "smx_check_mission_goals",
 ]
 LAUNCH_FORMS = {0: "small", 1: "large_teams", 2: "large_one_lane"}
 LAUNCH_STRATEGIES = {"auto": 0, "small": 1, "large": 2, "large_one_lane": 3, "large_teams": 4}
@@ -197,6 +205,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.smx_set_vias.restype = C.c_int
     lib.smx_set_missions.argtypes = [h, C.POINTER(SmxMission), _i32, C.POINTER(_i32), _i32]
     lib.smx_set_missions.restype = C.c_int
+    lib.smx_set_mission_goals.argtypes = [h, C.POINTER(SmxMissionGoal), _i32, C.POINTER(_f64), C.POINTER(_i32), _i32]
+    lib.smx_set_mission_goals.restype = C.c_int
+    lib.smx_check_mission_goals.argtypes = [C.POINTER(SmxMissionGoal), _i32, _i32, C.POINTER(_f64), C.POINTER(_i32), _i32,
+                                            _i32, C.c_char_p, C.c_uint64]
+    lib.smx_check_mission_goals.restype = C.c_int
     lib.smx_step_trajectory.argtypes = [h, _p, _p, C.POINTER(SmxState), C.POINTER(SmxSpawns), C.POINTER(SmxOutputs), _p]
     lib.smx_step_trajectory.restype = C.c_int
     lib.smx_step_target_pose.argtypes = [h, _p, C.POINTER(SmxState), C.POINTER(SmxSpawns), C.POINTER(SmxOutputs), _p]

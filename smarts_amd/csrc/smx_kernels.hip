@@ -3400,6 +3400,54 @@ struct ObsStage {
   unsigned char mode[SMX_BLOCK];                 // 1: this vehicle's rows are written this pass
 };
 
+// TraverseGoal._drove_off_map (plan.py:147-166): the vehicle has left the map beyond the end of a dead-end lane,
+// going roughly the lane's way.  `lane`, `dist`: the scan's nearest lane — the same query as nearest_lanes(pos)[0]
+// (radius max(10, 2 x default lane width), junction lanes included, dist < radius, ties to the lower lane id).
+__device__ inline bool drove_off_map(const MissionsDev& ms, const MapDev& m, int n_slots, int lane, double dist, double px,
+                                     double py, double heading) {
+  if (lane < 0) return false;  // "we can't tell anything here"
+  const double offset = lane_offset_along(m, lane, px, py);
+  const double width = m.lane_width[lane];  // width_at_offset (sumo_road_network.py:493-494)
+  if (!ms.lane_dead_end(n_slots, m.n_lanes)[lane] || dist < 0.5 * width + 1e-1) return false;
+  if (offset < m.lane_length[lane] - 2 * width) return false;
+  const double heading_err = min_angles_difference_signed(ms.lane_end_heading(n_slots)[lane], heading);
+  return fabs(heading_err) < SMX_PI / 6;
+}
+
+// LapMission.is_complete (plan.py:272-277), second half: reached_goal also needs distance_travelled >
+// route_length * num_laps, where distance_travelled is the trip meter's total with this tick's waypoint counted
+// (sensors.py:349-351, 491-496).  The observe role runs beside the waypoints role that writes that total, so it
+// decides a lap slot as a positional one and the commit role — after both, in every launch form and in the reset
+// pass — takes the event back while the distance is short: reached_goal off, done from the other events of the
+// row (sensors.py:465-476), and the flags / active / done / learner words the observe role derived from done.
+// (`tick`: the tick's commit, whose observe role saw every agent and wrote reward / done; k_tail's argument block is
+// the reset pass's, so first_only / keep_reward_done are read only for the reset pass's own commit)
+__device__ inline void lap_goal_gate(const KernelArgs& a, size_t gid, size_t total, int slot, bool tick) {
+  const smx_mission_goal g = a.missions.goal_kind[slot];
+  if (g.kind != SMX_GOAL_LAP) return;
+  const smx_config& c = a.cfg;
+  const smx_outputs& o = a.out;
+  const int flags = a.st.flags[gid];
+  const bool observed = (flags & SMX_F_ALIVE) && !(flags & SMX_F_SOCIAL) && (tick || !a.first_only || (flags & SMX_F_FIRST));
+  uint8_t* ev = o.events + gid * SMX_EV_COUNT;
+  if (!observed || !ev[SMX_EV_REACHED_GOAL]) return;
+  if (o.dist[gid] > g.route_length * g.num_laps) return;
+  ev[SMX_EV_REACHED_GOAL] = 0;
+  const uint32_t dc = c.done_criteria;
+  bool done = (ev[SMX_EV_OFF_ROAD] && (dc & SMX_DONE_OFF_ROAD)) || ev[SMX_EV_REACHED_MAX_EPISODE_STEPS] ||
+              (ev[SMX_EV_ON_SHOULDER] && (dc & SMX_DONE_ON_SHOULDER)) || (ev[SMX_EV_COLLISIONS] && (dc & SMX_DONE_COLLISION)) ||
+              (ev[SMX_EV_NOT_MOVING] && (dc & SMX_DONE_NOT_MOVING)) || (ev[SMX_EV_OFF_ROUTE] && (dc & SMX_DONE_OFF_ROUTE)) ||
+              (ev[SMX_EV_WRONG_WAY] && (dc & SMX_DONE_WRONG_WAY)) || ev[SMX_EV_AGENTS_ALIVE_DONE];
+  if (flags & SMX_F_FIRST) done = false;
+  if (done) return;  // ended by another event: every derived word stands
+  a.st.facts_i32[(size_t)SMX_FI_FLAGS_NEXT * total + gid] |= SMX_F_ALIVE;
+  o.active[gid] = 1;
+  if (tick || !a.keep_reward_done) {
+    o.done[gid] = 0;
+    if (o.learner) o.learner[total + gid] = 0.0f;
+  }
+}
+
 __device__ __forceinline__ void observe_role(const KernelArgs& a, const int block) {
   __shared__ SharedPose pose[SMX_BLOCK];
   __shared__ ObsStage stage;
@@ -3727,6 +3775,10 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
       const double sqr_dist = (s.x - gx) * (s.x - gx) + (s.y - gy) * (s.y - gy);
       reached_goal = sqr_dist <= gr * gr;
     }
+    // (a lap goal's distance condition waits for this tick's trip meter, which the waypoints role is still writing:
+    // the commit role applies it, lap_goal_gate)
+    if (__builtin_expect(a.missions.goal_kind != nullptr, 0) && a.missions.goal_kind[slot].kind == SMX_GOAL_TRAVERSE)
+      reached_goal = drove_off_map(a.missions, m, n_veh, my_lane, my_lane_dist, s.x, s.y, wrap_heading(s.heading));
     const bool is_off_road = !(my_facts & SMX_FACT_ON_ROAD);           // sensors.py:498-500
     const bool is_on_shoulder = ((my_facts >> SMX_FACT_CORNER_SHIFT) & 15) != 15;  // sensors.py:502-509
     const bool reached_max = c.max_episode_steps > 0 && steps >= c.max_episode_steps;
@@ -3894,6 +3946,7 @@ __device__ __forceinline__ void commit_role(const KernelArgs& a, const int block
   }
   __syncthreads();
   if (valid) {
+    if (__builtin_expect(a.missions.goal_kind != nullptr, 0)) lap_goal_gate(a, gid, total, slot, tick);
     const int old_flags = a.st.flags[gid];
     const int new_flags = a.st.facts_i32[(size_t)SMX_FI_FLAGS_NEXT * total + gid];
     a.st.flags[gid] = new_flags;
@@ -4905,6 +4958,8 @@ struct smx_handle_s {
   int32_t n_vias;
   void* missions_blob;      // device copy of smx_set_missions: goals | last roads | route positions | lane table
   std::vector<int32_t> host_lane_road, host_lane_out_off, host_lane_out_idx;  // kept for smx_set_missions
+  void* goals_blob;         // device copy of smx_set_mission_goals: goal kinds | lane end headings | dead-end lanes
+  std::vector<int32_t> host_route_last;  // smx_set_missions' last roads (-1: empty route), kept for smx_set_mission_goals
   MissionsDev missions;
   double heading_gain_pos, lateral_gain_pos;
   double nb_d2_max;
@@ -5041,6 +5096,7 @@ static int create_impl(const smx_config* cfg, int device, smx_handle* out) {
   h->via_off_dev = nullptr;
   h->n_vias = 0;
   h->missions_blob = nullptr;
+  h->goals_blob = nullptr;
   h->missions = MissionsDev{nullptr, nullptr};
   h->map.route_pos = nullptr;
   h->map.route_lane_ok = nullptr;
@@ -5255,6 +5311,9 @@ extern "C" int smx_load_map(smx_handle h, const smx_map_tables* t) {
   // missions name roads of the map they were set for: a new map starts without any
   if (h->missions_blob) (void)hipFree(h->missions_blob);
   h->missions_blob = nullptr;
+  if (h->goals_blob) (void)hipFree(h->goals_blob);  // goal kinds go with the missions they refine
+  h->goals_blob = nullptr;
+  h->host_route_last.clear();
   h->missions = MissionsDev{nullptr, nullptr};
 #define PTR(field, type) m.field = (const type*)(base + off_##field)
   PTR(lane_road, int32_t);
@@ -5443,12 +5502,16 @@ extern "C" int smx_set_missions(smx_handle h, const smx_mission* missions_host, 
   SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
   if (h->missions_blob) (void)hipFree(h->missions_blob);
   h->missions_blob = nullptr;
+  if (h->goals_blob) (void)hipFree(h->goals_blob);  // goal kinds go with the missions they refine
+  h->goals_blob = nullptr;
+  h->host_route_last.clear();
   h->missions = MissionsDev{nullptr, nullptr};
   h->map.route_pos = nullptr;
   h->map.route_lane_ok = nullptr;
   // the knot lists of the previous tick were walked under the old routes
   if (h->knots_blob && h->knots.key)
     SMX_HIP(hipMemset(h->knots.key, 0xff, 3 * (size_t)h->cfg.num_envs * nv * SMX_WP_LANES * sizeof(int32_t)));
+  h->host_route_last = last;
   if (!any) return SMX_OK;
   const size_t goal_bytes = goal.size() * sizeof(double), last_bytes = last.size() * sizeof(int32_t),
                pos_bytes = pos.size() * sizeof(int16_t);
@@ -5464,6 +5527,75 @@ extern "C" int smx_set_missions(smx_handle h, const smx_mission* missions_host, 
   SMX_HIP(hipMemcpy(base + off_lane, lane_ok.data(), lane_ok.size(), hipMemcpyHostToDevice));
   h->map.route_pos = (const int16_t*)(base + off_pos);
   h->map.route_lane_ok = (const uint8_t*)(base + off_lane);
+  return SMX_OK;
+}
+
+extern "C" int smx_check_mission_goals(const smx_mission_goal* goals, int32_t n_slots, int32_t num_vehicles,
+                                       const double* lane_end_heading, const int32_t* lane_dead_end, int32_t n_lanes,
+                                       int32_t map_lanes, char* err, uint64_t err_len) {
+  auto bad = [&](const std::string& msg) {
+    if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", msg.c_str());
+    return (int)SMX_ERR_INVALID;
+  };
+  if (err && err_len > 0) err[0] = 0;
+  if (n_slots < 0 || (n_slots > 0 && !goals)) return bad("smx_set_mission_goals: null table");
+  if (n_slots != 0 && n_slots != num_vehicles) return bad("smx_set_mission_goals: one goal per vehicle slot (cfg.num_vehicles)");
+  bool traverse = false;
+  for (int s = 0; s < n_slots; ++s) {
+    const smx_mission_goal& g = goals[s];
+    const std::string at = "smx_set_mission_goals: slot " + std::to_string(s);
+    if (g.kind == SMX_GOAL_LAP) {
+      if (g.num_laps < 1) return bad(at + ": num_laps must be >= 1");
+      if (!std::isfinite(g.route_length) || g.route_length < 0.0) return bad(at + ": route_length must be finite and >= 0");
+    } else if (g.kind == SMX_GOAL_TRAVERSE) {
+      traverse = true;
+    } else if (g.kind != SMX_GOAL_POSITIONAL) {
+      return bad(at + ": unknown goal kind " + std::to_string(g.kind));
+    }
+  }
+  if (traverse) {
+    if (!lane_end_heading || !lane_dead_end) return bad("smx_set_mission_goals: a traverse goal needs the lane tables (lane_end_heading, lane_dead_end)");
+    if (n_lanes != map_lanes) return bad("smx_set_mission_goals: n_lanes is not the map's lane count");
+    for (int l = 0; l < n_lanes; ++l)
+      if (!std::isfinite(lane_end_heading[l])) return bad("smx_set_mission_goals: lane_end_heading not finite");
+  }
+  return SMX_OK;
+}
+
+extern "C" int smx_set_mission_goals(smx_handle h, const smx_mission_goal* goals_host, int32_t n_slots,
+                                     const double* lane_end_heading_host, const int32_t* lane_dead_end_host, int32_t n_lanes) {
+  if (!h) return SMX_ERR_INVALID;
+  if (!h->map_loaded) return fail(h, SMX_ERR_STATE, "smx_set_mission_goals needs the map (the lane tables are checked against it)");
+  char why[192];
+  const int nv = h->cfg.num_vehicles, nl = h->map.n_lanes;
+  if (smx_check_mission_goals(goals_host, n_slots, nv, lane_end_heading_host, lane_dead_end_host, n_lanes, nl, why, sizeof(why)) != SMX_OK)
+    return fail(h, SMX_ERR_INVALID, why);
+  bool any = false, traverse = false;
+  for (int s = 0; s < n_slots; ++s) {
+    const bool routed = s < (int)h->host_route_last.size() && h->host_route_last[s] >= 0;
+    if (goals_host[s].kind == SMX_GOAL_LAP && !routed)
+      return fail(h, SMX_ERR_INVALID, "smx_set_mission_goals: a lap goal needs the slot's fixed route and PositionalGoal (smx_set_missions)");
+    if (goals_host[s].kind == SMX_GOAL_TRAVERSE && routed)
+      return fail(h, SMX_ERR_INVALID, "smx_set_mission_goals: a traverse goal has an empty route (smx_mission.route_len = 0)");
+    any = any || goals_host[s].kind != SMX_GOAL_POSITIONAL;
+    traverse = traverse || goals_host[s].kind == SMX_GOAL_TRAVERSE;
+  }
+  SMX_HIP(hipSetDevice(h->device));
+  SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
+  if (h->goals_blob) (void)hipFree(h->goals_blob);
+  h->goals_blob = nullptr;
+  h->missions.goal_kind = nullptr;
+  if (!any) return SMX_OK;
+  const size_t kind_bytes = (size_t)nv * sizeof(smx_mission_goal);
+  const size_t head_bytes = traverse ? (size_t)nl * sizeof(double) : 0, dead_bytes = traverse ? (size_t)nl * sizeof(int32_t) : 0;
+  SMX_HIP(hipMalloc(&h->goals_blob, kind_bytes + head_bytes + dead_bytes));
+  char* base = (char*)h->goals_blob;
+  SMX_HIP(hipMemcpy(base, goals_host, kind_bytes, hipMemcpyHostToDevice));
+  if (traverse) {
+    SMX_HIP(hipMemcpy(base + kind_bytes, lane_end_heading_host, head_bytes, hipMemcpyHostToDevice));
+    SMX_HIP(hipMemcpy(base + kind_bytes + head_bytes, lane_dead_end_host, dead_bytes, hipMemcpyHostToDevice));
+  }
+  h->missions.goal_kind = (const smx_mission_goal*)base;
   return SMX_OK;
 }
 
@@ -6151,6 +6283,7 @@ extern "C" void smx_destroy(smx_handle h) {
   if (h->vias_dev) (void)hipFree(h->vias_dev);
   if (h->via_off_dev) (void)hipFree(h->via_off_dev);
   if (h->missions_blob) (void)hipFree(h->missions_blob);
+  if (h->goals_blob) (void)hipFree(h->goals_blob);
   for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ph_pool) (void)hipEventDestroy(e);
   delete h;

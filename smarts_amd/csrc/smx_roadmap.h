@@ -287,6 +287,13 @@ __device__ inline void closest_filtered4(const MapDev& m, double px, double py, 
 struct MissionsDev {
   const int32_t* route_last;  // [slots]: last road of the route (lanepoints.py:674), -1 = endless mission (empty route)
   const double* goal;         // [slots][3]: PositionalGoal x, y, radius
+  // smx_set_mission_goals, null: every goal positional.  One blob: [slots] kind / num_laps / route_length, then — the
+  // lane facts of TraverseGoal — [n_lanes] end heading (double) and [n_lanes] dead end (int32)
+  const smx_mission_goal* goal_kind;
+  __device__ __forceinline__ const double* lane_end_heading(int n_slots) const { return (const double*)(goal_kind + n_slots); }
+  __device__ __forceinline__ const int32_t* lane_dead_end(int n_slots, int n_lanes) const {
+    return (const int32_t*)(lane_end_heading(n_slots) + n_lanes);
+  }
 };
 
 // Route filter: the road ids of _resolve_in_junction (at most the junction road and the

@@ -190,7 +190,8 @@ class BatchedSim:
                  vias: Optional[Sequence[Sequence]] = None, missions: Optional[Sequence] = None):
         """``vias``: per agent slot, a list of ``vias.ResolvedVia`` (the missions' via points).
         ``missions``: per vehicle slot ``None`` (endless mission, empty route) or a
-        ``missions.PlannedMission`` (fixed route + PositionalGoal); see ``set_missions``."""
+        ``missions.PlannedMission`` (fixed route + PositionalGoal, a lap goal, or an empty route with an endless or
+        a traverse goal); see ``set_missions``."""
         self.lib = nat.load_library()
         if not torch.cuda.is_available():
             raise nat.NativeLibraryError("no ROCm device visible: the smarts_amd hot path runs on the GPU only")
@@ -441,8 +442,9 @@ class BatchedSim:
         return kb
 
     def set_missions(self, missions: Optional[Sequence]):
-        """Fixed-route missions per vehicle slot, shared by every env (``smx_set_missions``): ``None`` entries
-        (or ``missions=None``) are endless missions with an empty route."""
+        """Missions per vehicle slot, shared by every env (``smx_set_missions``, and ``smx_set_mission_goals`` when
+        a slot has a lap or a traverse goal): ``None`` entries (or ``missions=None``) are endless missions with an
+        empty route."""
         N = self.N
         if missions is None or all(m is None for m in missions):
             nat.check(self.lib, self.handle, self.lib.smx_set_missions(self.handle, None, 0, None, 0), "smx_set_missions")
@@ -462,6 +464,25 @@ class BatchedSim:
         arr = (C.c_int32 * max(len(roads), 1))(*roads)
         nat.check(self.lib, self.handle, self.lib.smx_set_missions(self.handle, recs, N, arr, len(roads)), "smx_set_missions")
         self.missions = list(missions)
+        # goal kinds beyond the positional one (smx_set_mission_goals; smx_set_missions left every slot positional)
+        kinds = [getattr(m, "goal_kind", nat.GOAL_POSITIONAL) if m is not None else nat.GOAL_POSITIONAL for m in missions]
+        if any(k != nat.GOAL_POSITIONAL for k in kinds):
+            goals = (nat.SmxMissionGoal * N)()
+            for s, m in enumerate(missions):
+                if m is not None:
+                    goals[s].kind, goals[s].num_laps, goals[s].route_length = kinds[s], int(m.num_laps), float(m.route_length)
+            heading = dead_end = None
+            n_lanes = 0
+            if nat.GOAL_TRAVERSE in kinds:
+                from .missions import lane_end_tables
+
+                h, d = lane_end_tables(self.cm)  # the two lane facts of TraverseGoal: host libm, owned by the handle
+                n_lanes = len(h)
+                heading = np.ascontiguousarray(h, dtype=np.float64).ctypes.data_as(C.POINTER(C.c_double))
+                dead_end = np.ascontiguousarray(d, dtype=np.int32).ctypes.data_as(C.POINTER(C.c_int32))
+                keep = (h, d)  # noqa: F841 (alive across the call)
+            nat.check(self.lib, self.handle, self.lib.smx_set_mission_goals(self.handle, goals, N, heading, dead_end, n_lanes),
+                      "smx_set_mission_goals")
 
     def small_form(self) -> bool:
         """Whether a tick runs in the SMALL launch form (smx_plan.h: SMX_LARGE_BATCH_VEHICLES)."""

@@ -178,8 +178,9 @@ class BatchCore:
                 raise ValueError(f"vias for unknown agents: {sorted(unknown)}")
             self.vias = [resolve_vias(self.cm, vias.get(a, ())) for a in self.agent_ids] + [[] for _ in range(num_social)]
             self.cfg.via_max = 8
-        # fixed-route missions (sstudio Mission per agent id): planned once (Scenario._extract_mission +
-        # Plan.create_route), the agent's spawn rows become the mission's start in every env and episode
+        # missions (sstudio Mission / EndlessMission / LapMission, or TraverseMission, per agent id): planned once
+        # (Scenario._extract_mission + Plan.create_route), the agent's spawn rows become the mission's start in every
+        # env and episode — for every kind, the ones with an empty route included
         self.missions = None
         if missions:
             from ..missions import plan_mission

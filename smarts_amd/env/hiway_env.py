@@ -76,9 +76,11 @@ class HiWayEnv:
         # mission via points per agent id (smarts_amd.vias.Via = sstudio's Via); the reference reads them
         # from the scenario's missions, which this path does not parse
         self._vias = dict(vias) if vias else None
-        # fixed-route missions per agent id (smarts_amd.missions.Mission = sstudio's Mission / Route, or the path
-        # of a missions JSON): the agent starts at the route's begin, is held to the route (waypoints, off_route,
-        # trip meter) and ends at its goal (reached_goal); agents without one drive endless missions
+        # missions per agent id (smarts_amd.missions.Mission = sstudio's Mission / Route, or the path of a missions
+        # JSON): the agent starts at the route's begin, is held to the route (waypoints, off_route, trip meter) and
+        # ends at its goal (reached_goal); EndlessMission (a chosen start), LapMission (the goal counts after
+        # num_laps x the route's length) and TraverseMission (the goal is to drive off the map through a dead-end
+        # lane) are taken too; agents without one drive endless missions from a drawn start
         if isinstance(missions, str):
             from ..missions import load_missions
 

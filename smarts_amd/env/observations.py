@@ -258,7 +258,7 @@ class ObservationBuilder:
         # per vehicle slot: smarts_amd.missions.PlannedMission | None
         self.missions = [
             FixedRouteMission(tuple(m.start_position), float(m.start_heading), PositionalGoal(tuple(m.goal[:2]), float(m.goal[2])),
-                              tuple(m.route_roads)) if m is not None else None for m in (missions or [])]
+                              tuple(m.route_roads)) if m is not None and m.route_roads else None for m in (missions or [])]
         self.vias = vias  # per vehicle slot: resolved mission vias (smarts_amd.vias.ResolvedVia)
 
     def vehicle_id(self, slot: int) -> str:

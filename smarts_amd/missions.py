@@ -1,5 +1,5 @@
-"""Missions with fixed routes (host side): what a scenario author writes, the route the planner finds, and the
-records the device reads (``include/smx.h`` ``smx_mission``).
+"""Missions (host side): what a scenario author writes, the route the planner finds, and the records the device
+reads (``include/smx.h`` ``smx_mission``, ``smx_mission_goal``).
 
 Mirrors ``smarts/sstudio/types.py`` ``Route`` / ``Mission`` (begin / end as (road id, lane index, offset)),
 ``Scenario._extract_mission`` (``smarts/core/scenario.py:625-700``: start pose on the lane's centre line with
@@ -7,6 +7,10 @@ the lane's direction, ``PositionalGoal`` of radius 2 at the end), ``Plan.create_
 (``smarts/core/plan.py:316-349``) and ``SumoRoadNetwork.generate_routes`` / ``_internal_routes_between``
 (``smarts/core/sumo_road_network.py:711-800``).  The edge search underneath is ``sumolib``'s
 ``getShortestPath``, restated in :mod:`smarts_amd.sumo_map`.
+
+Besides ``Mission(Route)``: ``EndlessMission`` (sstudio/types.py:487-505; scenario.py:701-714), ``LapMission``
+(types.py:508-523; scenario.py:715-746, plan.py:252-277) and ``TraverseMission`` — this project's name for what the
+reference builds as ``Mission(start, goal=TraverseGoal(road_map))`` (scenario.py:566-575, plan.py:127-166).
 """
 from __future__ import annotations
 
@@ -41,6 +45,34 @@ class Mission:
 
 
 @dataclass(frozen=True)
+class EndlessMission:
+    """sstudio/types.py:487-505: a chosen start, no goal, no route."""
+
+    begin: Tuple[str, int, Offset]
+    via: Tuple[str, ...] = ()
+
+
+@dataclass(frozen=True)
+class LapMission:
+    """sstudio/types.py:508-523: ``num_laps`` times round ``route``, then the goal at its end."""
+
+    route: Route
+    num_laps: int
+    via: Tuple[str, ...] = ()
+
+
+@dataclass(frozen=True)
+class TraverseMission:
+    """``Mission(start, goal=TraverseGoal(road_map))`` (scenario.py:566-575): done by driving off the map through
+    a dead-end lane, heading the lane's way (plan.py:147-166)."""
+
+    begin: Tuple[str, int, Offset]
+
+
+GOAL_POSITIONAL, GOAL_LAP, GOAL_TRAVERSE = 0, 1, 2  # SMX_GOAL_* (include/smx.h)
+
+
+@dataclass(frozen=True)
 class PlannedMission:
     """plan.py ``Mission`` + ``Plan.route`` after ``create_route``."""
 
@@ -48,6 +80,9 @@ class PlannedMission:
     start_heading: float
     goal: Tuple[float, float, float]     # PositionalGoal x, y, radius
     route_roads: Tuple[str, ...]         # RoadMap.Route.roads, junction-internal roads included
+    goal_kind: int = GOAL_POSITIONAL     # GOAL_*; with an empty route GOAL_POSITIONAL reads as EndlessGoal
+    route_length: float = 0.0            # GOAL_LAP: LapMission.route_length (scenario.py:726, 742)
+    num_laps: int = 0                    # GOAL_LAP
 
     def spawn_pose(self, length: float = CHASSIS_LENGTH) -> Tuple[float, float, float]:
         """Pose.from_front_bumper (coordinates.py:302-321): vehicle centre and heading."""
@@ -163,20 +198,103 @@ def generate_route(net: SumoNet, start_road: str, end_road: str, via: Sequence[s
     return out
 
 
-def plan_mission(net: SumoNet, mission: Mission) -> PlannedMission:
-    """``Scenario._extract_mission`` + ``Plan.create_route``."""
-    r = mission.route
-    start_pos, start_heading = _position_and_heading(net, *r.begin)
-    goal_pos, _ = _position_and_heading(net, *r.end)
+def _create_route(net: SumoNet, start_pos, goal_pos, via: Sequence[str]) -> Tuple[str, ...]:
+    """``Plan.create_route`` for a mission with a fixed route (plan.py:324-354)."""
     start_road = nearest_road_outside_junctions(net, start_pos)
     end_road = nearest_road_outside_junctions(net, goal_pos)
     if start_road is None or end_road is None:
         raise ValueError("route must start and end in a lane")  # plan.py:330, 337
-    roads = generate_route(net, start_road.getID(), end_road.getID(), r.via)
+    roads = generate_route(net, start_road.getID(), end_road.getID(), via)
     if not roads:
         # plan.py:345-351 (PlanningError)
         raise ValueError(f"Unable to find a route between start={start_road.getID()} and end={end_road.getID()}.")
-    return PlannedMission(start_pos, start_heading, (goal_pos[0], goal_pos[1], 2.0), tuple(roads))
+    return tuple(roads)
+
+
+def route_road_length(net: SumoNet, roads: Sequence[str]) -> float:
+    """``Route.road_length`` (sumo_road_network.py:896-903): the roads' lengths added in route order, from int 0."""
+    length = 0
+    for rid in roads:
+        length += net.getEdge(rid).getLength()
+    return float(length)
+
+
+def plan_lap_mission(net: SumoNet, mission: LapMission) -> PlannedMission:
+    """``Scenario._extract_mission`` for a LapMission (scenario.py:715-746) + ``Plan.create_route``
+    (``LapMission.has_fixed_route`` is always true, plan.py:267-270).  The lap whose length counts starts at the begin
+    road's first outgoing road when begin and end share a road; the route the plan follows is create_route's own."""
+    if isinstance(mission.num_laps, bool) or not isinstance(mission.num_laps, int) or mission.num_laps < 1:
+        # (the reference multiplies route_length by num_laps on the first goal test: None raises there)
+        raise ValueError(f"LapMission.num_laps must be an int >= 1, not {mission.num_laps!r}")
+    r = mission.route
+    travel = net.getEdge(r.begin[0])
+    end = net.getEdge(r.end[0])
+    if travel is None or end is None:
+        raise ValueError("unknown road in route")
+    if r.begin[0] == r.end[0]:
+        outgoing = list(travel.getOutgoing().keys())  # Road.outgoing_roads (sumo_road_network.py:578-583)
+        if not outgoing:
+            raise ValueError(f"road {r.begin[0]!r} has no outgoing road to lap through")
+        travel = outgoing[0]
+    # (LapMission carries its own `via` beside the route's: scenario.py:724 reads the route's)
+    via = tuple(r.via)
+    lap = generate_route(net, travel.getID(), end.getID(), via)
+    route_length = route_road_length(net, lap)
+    start_pos, start_heading = _position_and_heading(net, *r.begin)
+    goal_pos, _ = _position_and_heading(net, *r.end)
+    roads = _create_route(net, start_pos, goal_pos, via)
+    return PlannedMission(start_pos, start_heading, (goal_pos[0], goal_pos[1], 2.0), roads, GOAL_LAP, route_length,
+                          mission.num_laps)
+
+
+def plan_mission(net: SumoNet, mission) -> PlannedMission:
+    """``Scenario._extract_mission`` + ``Plan.create_route``, by the mission's type."""
+    if isinstance(mission, LapMission):
+        return plan_lap_mission(net, mission)
+    if isinstance(mission, (EndlessMission, TraverseMission)):
+        # scenario.py:701-714 / :566-575: a start, a goal that is_endless(), so an empty route (plan.py:321-323)
+        start_pos, start_heading = _position_and_heading(net, *mission.begin)
+        kind = GOAL_TRAVERSE if isinstance(mission, TraverseMission) else GOAL_POSITIONAL
+        return PlannedMission(start_pos, start_heading, (0.0, 0.0, 0.0), (), kind)
+    if not isinstance(mission, Mission):
+        raise TypeError(f"mission={mission!r} is an invalid type={type(mission)}")  # scenario.py:748-750
+    r = mission.route
+    start_pos, start_heading = _position_and_heading(net, *r.begin)
+    goal_pos, _ = _position_and_heading(net, *r.end)
+    roads = _create_route(net, start_pos, goal_pos, r.via)
+    return PlannedMission(start_pos, start_heading, (goal_pos[0], goal_pos[1], 2.0), roads)
+
+
+def _vec_to_radians_unwrapped(x: float, y: float) -> float:
+    """utils/math.py:256-277 as it returns: in [0, 2 pi)."""
+    r = math.atan2(abs(y), abs(x))
+    if x < 0:
+        return (r + 0.5 * math.pi) % (2 * math.pi) if y < 0 else (0.5 * math.pi - r) % (2 * math.pi)
+    if y < 0:
+        return (1.5 * math.pi - r) % (2 * math.pi)
+    return (r - 0.5 * math.pi) % (2 * math.pi)
+
+
+def lane_end_tables(cm) -> Tuple[np.ndarray, np.ndarray]:
+    """The two facts per lane that ``TraverseGoal._drove_off_map`` (plan.py:147-166) asks of the map, in the lane
+    order of the compiled map ``cm``: the end heading ``vec_to_radians(lane.vector_at_offset(length - 0.1)[:2])``
+    (road_map.py:377-388) as float64 and "has no outgoing lanes" (sumo_road_network.py:351-358, via lanes count as
+    outgoing: the compiled map's ``lane_out`` lists) as int32.  Uploaded with the goal kinds
+    (``smx_set_mission_goals``); the compiled-map cache does not hold them."""
+    n = len(cm.lane_ids)
+    heading = np.zeros(n, dtype=np.float64)
+    dead_end = np.zeros(n, dtype=np.int32)
+    for lane in range(n):
+        shape = cm.lane_shape(lane)
+        length = float(cm.lane_length[lane])
+        off = length - 0.1
+        s_off, e_off = (length - 1, length) if off >= length else (off, off + 1)
+        s_off = max(s_off, 0)
+        x1, y1 = _position_at_shape_offset(shape, s_off)
+        x2, y2 = _position_at_shape_offset(shape, e_off)
+        heading[lane] = _vec_to_radians_unwrapped(x2 - x1, y2 - y1)
+        dead_end[lane] = 1 if cm.lane_out_off[lane + 1] == cm.lane_out_off[lane] else 0
+    return heading, dead_end
 
 
 def _polygon_offset_with_minimum_distance(point: Sequence[float], shape: np.ndarray) -> float:
@@ -310,13 +428,27 @@ def _draw_endless_missions(net: SumoNet, count: int, rng, scenario_rolls: int) -
     return out
 
 
-def load_missions(source: Union[str, dict]) -> Dict[str, Mission]:
+def load_missions(source: Union[str, dict]) -> Dict[str, object]:
     """Missions of a scenario as JSON (the ``missions.pkl`` of the reference's ``scenario build`` holds pickled
-    sstudio objects): ``{agent id: {"begin": [road, lane index, offset], "end": [...], "via": [road, ...]}}``."""
+    sstudio objects): ``{agent id: {"begin": [road, lane index, offset], "end": [...], "via": [road, ...]}}``.
+    An optional ``"type"`` names the kind: ``"mission"`` (the default: the format above), ``"lap"`` (the same keys
+    plus ``"num_laps"``), ``"endless"`` (``"begin"``, ``"via"``) or ``"traverse"`` (``"begin"``)."""
     if isinstance(source, str):
         with open(source) as f:
             source = json.load(f)
     out = {}
     for agent_id, spec in source.items():
-        out[agent_id] = Mission(Route(begin=tuple(spec["begin"]), end=tuple(spec["end"]), via=tuple(spec.get("via", ()))))
+        kind = spec.get("type", "mission")
+        via = tuple(spec.get("via", ()))
+        if kind == "mission":
+            out[agent_id] = Mission(Route(begin=tuple(spec["begin"]), end=tuple(spec["end"]), via=via))
+        elif kind == "lap":
+            out[agent_id] = LapMission(Route(begin=tuple(spec["begin"]), end=tuple(spec["end"]), via=via),
+                                       num_laps=spec.get("num_laps"))
+        elif kind == "endless":
+            out[agent_id] = EndlessMission(begin=tuple(spec["begin"]), via=via)
+        elif kind == "traverse":
+            out[agent_id] = TraverseMission(begin=tuple(spec["begin"]))
+        else:
+            raise ValueError(f"mission of {agent_id!r}: unknown type {kind!r}")
     return out

@@ -1,0 +1,50 @@
+"""CPU restatement of the two goal tests beyond PositionalGoal, in plain Python floats: what ``lap_goal_gate`` and
+``drove_off_map`` compute (smarts_amd/csrc/smx_kernels.hip), operation by operation.  Test infrastructure; held to the
+reference's own outputs (tests/golden/mission_goals_*.npz) by tests/test_mission_goals.py."""
+import math
+
+TWO_PI = 2 * math.pi
+
+
+def lap_is_complete(x, y, distance_travelled, num_laps, route_length, goal):
+    """LapMission.is_complete (plan.py:272-277) over PositionalGoal.is_reached (:120-124).  ``distance_travelled``:
+    the trip meter's total with this tick's waypoint counted (sensors.py:349-351, 491-496)."""
+    gx, gy, radius = goal
+    sqr_dist = (x - gx) ** 2 + (y - gy) ** 2
+    return sqr_dist <= radius ** 2 and distance_travelled > route_length * num_laps
+
+
+def min_angles_difference_signed(first, second):
+    """utils/math.py:447-449."""
+    return ((first - second) + math.pi) % TWO_PI - math.pi
+
+
+def nearest_lane(net, x, y, default_lane_width=3.2):
+    """``nearest_lanes(pos)[0]`` (sumo_road_network.py:676-701): default radius, junction lanes included, the stable
+    sort keeps the first of equals — in lane-table order, the order the device's tie rule (lower lane id) restates."""
+    radius = max(10, 2 * default_lane_width)
+    order = {lane.getID(): i for i, lane in enumerate(net.all_lanes())}
+    best = None
+    for lane, d in net.neighboring_lanes(x, y, radius, False):
+        key = (d, order[lane.getID()])
+        if best is None or key < best[0]:
+            best = (key, lane, d)
+    return (best[1], best[2]) if best else (None, None)
+
+
+def drove_off_map(net, cm, tables, x, y, heading):
+    """TraverseGoal._drove_off_map (plan.py:147-166).  ``tables``: missions.lane_end_tables(cm)."""
+    from smarts_amd.missions import _offset_along_lane
+
+    lane, dist = nearest_lane(net, x, y, cm.default_lane_width)
+    if lane is None:
+        return False
+    k = cm.lane_ids.index(lane.getID())
+    offset = _offset_along_lane(cm.lane_shape(k), (x, y))
+    width = float(cm.lane_width[k])
+    end_heading, dead_end = tables
+    if not dead_end[k] or dist < 0.5 * width + 1e-1:
+        return False
+    if offset < float(cm.lane_length[k]) - 2 * width:
+        return False
+    return abs(min_angles_difference_signed(float(end_heading[k]), heading)) < math.pi / 6
