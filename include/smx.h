@@ -80,8 +80,14 @@ enum {
   SMX_SENSOR_OGM = 1 << 3,
   SMX_SENSOR_LIDAR = 1 << 4,
   SMX_SENSOR_DAGM = 1 << 5,  /* drivable-area grid map (sensors.py:675-716) */
-  SMX_SENSOR_ROAD_WAYPOINTS = 1 << 6 /* RoadWaypointsSensor (sensors.py:991-1040) */
+  SMX_SENSOR_ROAD_WAYPOINTS = 1 << 6, /* RoadWaypointsSensor (sensors.py:991-1040) */
+  /* lane_ttc (smarts/env/custom_observations.py:148-280), the observation adapter behind StdObs.ttc
+   * (format_obs.py:551-562), computed on the device from this pass's wp_*, nb_* and ego_* rows
+   * (smx_outputs.lane_ttc).  Valid only together with SMX_SENSOR_WAYPOINTS and SMX_SENSOR_NEIGHBORS, and while
+   * wp_paths * wp_len <= SMX_TTC_MAX_WAYPOINTS (an agent's waypoints are staged in LDS). */
+  SMX_SENSOR_LANE_TTC = 1 << 7
 };
+#define SMX_TTC_MAX_WAYPOINTS 512
 
 enum { SMX_SOCIAL_CONSTANT = 0, SMX_SOCIAL_IDM = 1 };
 
@@ -337,6 +343,27 @@ enum { /* columns of smx_outputs.ego_f32 */
   SMX_EGO_F32_COUNT = 25
 };
 
+/* ---- columns of smx_outputs.lane_ttc and bits of smx_outputs.lane_ttc_flags: what
+ *      lane_ttc(observation) returns (custom_observations.py:148-184); its "speed" and "steering" entries are
+ *      ego_f32[SMX_EGO_SPEED] / [SMX_EGO_STEERING] and are not repeated ---- */
+enum {
+  SMX_TTC_DIST_FROM_CENTER = 0, /* signed lateral error to the closest first waypoint / half its lane width */
+  SMX_TTC_ANGLE_ERROR = 1,      /* that waypoint's heading relative to the ego's                             */
+  SMX_TTC_TTC = 2,              /* 3: "ego_ttc" of the right, current and left lane                          */
+  SMX_TTC_DTC = 5,              /* 3: "ego_lane_dist" of the same lanes                                      */
+  SMX_TTC_COUNT = 8
+};
+enum {
+  SMX_TTC_VALID = 1 << 0,       /* the agent has an observation with at least one path: the row was written */
+  SMX_TTC_STD = 1 << 1,         /* ... and at least one neighbour: FormatObs' _std_ttc would not be None     */
+  /* the dense rows did not hold the sensors' full output (wp_count[0] > wp_paths, nb_count > nb_max or
+   * wp_len < wp_lookahead + 1): the row is lane_ttc of the rows that were kept */
+  SMX_TTC_TRUNCATED = 1 << 2,
+  /* the closest first waypoint's lane_index is not an index into the per-path list (the reference indexes that
+   * list by lane index and raises IndexError, custom_observations.py:263): the six lane columns are written as 0 */
+  SMX_TTC_INDEX_ERROR = 1 << 3
+};
+
 enum { /* indices into smx_outputs.count / .dtype: the pointers in declaration order */
   SMX_OUT_EGO_POS = 0, SMX_OUT_EGO_F32, SMX_OUT_EGO_LANE, SMX_OUT_EVENTS, SMX_OUT_REWARD, SMX_OUT_DIST, SMX_OUT_DONE,
   SMX_OUT_ACTIVE, SMX_OUT_ENV_DONE, SMX_OUT_VIA_NEAR, SMX_OUT_VIA_NEAR_COUNT, SMX_OUT_VIA_HIT, SMX_OUT_LEARNER,
@@ -347,6 +374,7 @@ enum { /* indices into smx_outputs.count / .dtype: the pointers in declaration o
   SMX_OUT_RW_LANE_COUNT, SMX_OUT_RW_LANE, SMX_OUT_RW_PATH_COUNT, SMX_OUT_RW_COUNT, SMX_OUT_RW_POS, SMX_OUT_RW_HEADING,
   SMX_OUT_RW_LANE_WIDTH, SMX_OUT_RW_SPEED_LIMIT, SMX_OUT_RW_LANE_INDEX, SMX_OUT_RW_LANE_ID,
   SMX_OUT_FINAL_EGO_POS, SMX_OUT_FINAL_EGO_F32, SMX_OUT_FINAL_EGO_LANE, SMX_OUT_FINAL_EVENTS, SMX_OUT_FINAL_DIST,
+  SMX_OUT_LANE_TTC, SMX_OUT_LANE_TTC_FLAGS,
   SMX_OUT_BUFFERS
 };
 typedef struct smx_outputs {
@@ -418,6 +446,13 @@ typedef struct smx_outputs {
   int16_t* final_ego_lane;
   uint8_t* final_events;
   double* final_dist;
+  /* SMX_SENSOR_LANE_TTC, NULL if unused: lane_ttc of every agent with an observation in this pass, written after
+   * the waypoint, neighbour and ego rows it is a function of — speeds and headings are the float32 values of those
+   * rows, positions float64, lane identity wp_lane_id / nb_lane_id (-1 never matches).  Rows of agents without an
+   * observation keep their values and read flags 0.  Under auto_reset the row of a restarted env describes its
+   * first observation; there is no final_* twin (the finishing tick's env_obs is low-dimensional). */
+  double* lane_ttc;        /* [E*N][SMX_TTC_COUNT]                             */
+  uint8_t* lane_ttc_flags; /* [E*N] SMX_TTC_* bits                             */
   /* what the caller allocated: element count and SMX_DT_* of each buffer above, in declaration order
    * (SMX_OUT_*); 0 / SMX_DT_NONE for a NULL pointer */
   uint64_t count[SMX_OUT_BUFFERS];

@@ -29,6 +29,13 @@ SOCIAL_MODELS = {"constant": 0, "idm": 1}
 PHASES = ["control", "scan", "ogm", "sensors", "commit", "reset"]
 SENSOR_WAYPOINTS, SENSOR_NEIGHBORS, SENSOR_ACCELEROMETER, SENSOR_OGM, SENSOR_LIDAR, SENSOR_DAGM = 1, 2, 4, 8, 16, 32
 SENSOR_ROAD_WAYPOINTS = 64
+SENSOR_LANE_TTC = 128
+# columns of smx_outputs.lane_ttc (SMX_TTC_*; "TTC" and "DTC" head three columns: right, current, left lane) and the
+# bits of smx_outputs.lane_ttc_flags
+TTC = dict(DIST_FROM_CENTER=0, ANGLE_ERROR=1, TTC=2, DTC=5)
+TTC_COUNT = 8
+TTC_VALID, TTC_STD, TTC_TRUNCATED, TTC_INDEX_ERROR = 1, 2, 4, 8
+TTC_MAX_WAYPOINTS = 512
 STATE_FIELDS = ["X", "Y", "HEADING", "U", "V", "R", "DELTA", "LAT_INT", "SPD_INT", "STEER", "THROTTLE", "SPD_ERR",
                 "MCL_X", "MCL_Y", "TRIP_X", "TRIP_Y", "TRIP_H", "DIST", "LV0_LONG", "LV0_LAT", "AV0_Z", "LV1_LONG",
                 "LV1_LAT", "AV1_Z", "PATH_SUM", "PREV_X", "PREV_Y"]
@@ -116,6 +123,7 @@ OUTPUT_FIELDS = [
     "rw_lane_count", "rw_lane", "rw_path_count", "rw_count", "rw_pos", "rw_heading", "rw_lane_width", "rw_speed_limit",
     "rw_lane_index", "rw_lane_id",
     "final_ego_pos", "final_ego_f32", "final_ego_lane", "final_events", "final_dist",
+    "lane_ttc", "lane_ttc_flags",
 ]
 OUTPUT_FIELDS.insert(OUTPUT_FIELDS.index("learner"), "via_hit")
 OUTPUT_FIELDS.insert(OUTPUT_FIELDS.index("via_hit"), "via_near_count")

@@ -3362,6 +3362,7 @@ __device__ __forceinline__ void zero_dense_rows(const KernelArgs& a, size_t gid,
     }
     if (t == 0) o.nb_count[gid] = 0;
   }
+  if ((c.sensors & SMX_SENSOR_LANE_TTC) && t == 0) o.lane_ttc_flags[gid] = 0;  // (the row itself stays: flags 0 say so)
   if (c.via_max > 0 && o.via_near) {
     for (int k = t; k < c.via_max; k += nth) o.via_near[gid * (size_t)c.via_max + k] = -1;
     if (t == 0) {
@@ -4715,6 +4716,185 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_road_waypoints(const KernelArgs a
 }
 
 // =================================================================================
+// k_lane_ttc: lane_ttc (custom_observations.py:148-280) of every agent with an observation, from the dense rows this
+// pass has just written (wp_*, nb_*, ego_*) — the function smarts_amd/env/lane_ttc_rows.py restates on the host.
+// SMX_TTC_TEAM lanes of a wavefront share an agent:
+//  - the team stages the agent's waypoints (x, y, lane id, per-path counts) in LDS, one coalesced sweep of the rows;
+//  - segment lengths in parallel, then lane p sums path p's in waypoint order: the reference's arclength is a
+//    sequential float64 sum (:206-211) and is not re-associated;
+//  - lane k takes neighbour k and walks the flat (path, waypoint) order itself, so min()'s "first of equal distances"
+//    (:230-232) is the loop's own strict `<` (every lane of the team reads the same LDS word: a broadcast, no bank
+//    conflict); the distances compared are the square roots, as in the reference — two different squares can round
+//    to one root — but a root is only taken of a square smaller than the best one so far;
+//  - the per-path minima (:251-254) are LDS atomic minima over the bit patterns: every value is positive (ttc <= 0 is
+//    discarded, the defaults are 1000 and 1), so the unsigned order is the numeric one and the result exact whatever
+//    the order of arrival;
+//  - lane 0 picks the closest first waypoint, indexes the per-path lists by its lane index (_ego_ttc_calc, :259-280,
+//    the quirk included) and writes the row.
+// In a tick the grid covers every vehicle and flags are still those of the tick's start (k_tail commits later): an
+// agent alive then has an observation.  In the reset pass (`groups` set) it covers the env groups k_tail listed, after
+// k_first has written the new vehicles' first observations and committed their flags: an alive agent's rows are its
+// first observation (a restarted env) or this tick's (the env beside it in the group: the same row again).
+// Its cost per tick and what bounds it have not been measured; it re-reads up to 3.4 KB of rows per agent
+// at 4 x 33 waypoints and ten neighbours.
+// =================================================================================
+__global__ void __launch_bounds__(SMX_BLOCK) k_lane_ttc(const KernelArgs a, const int32_t* groups, const int32_t* n_groups) {
+  extern __shared__ __align__(16) unsigned char ttc_lds[];
+  constexpr int T = SMX_TTC_TEAM, APB = SMX_BLOCK / T;
+  const smx_config& c = a.cfg;
+  const smx_outputs& o = a.out;
+  const size_t total = (size_t)c.num_envs * c.num_vehicles;
+  const int team = (int)threadIdx.x / T, r = (int)threadIdx.x % T;
+  size_t gid;
+  bool in_range;
+  if (groups) {
+    constexpr int BPG = SMX_BLOCK / APB;  // workgroups per env group (up to SMX_BLOCK vehicles)
+    const int entry = (int)blockIdx.x / BPG;
+    if (entry >= *n_groups) return;  // (uniform in the workgroup)
+    const int n_veh = c.num_vehicles, epb = SMX_BLOCK / n_veh;
+    const size_t g0 = (size_t)groups[entry] * epb * n_veh;
+    gid = g0 + (size_t)((int)blockIdx.x % BPG) * APB + team;
+    in_range = gid < min(total, g0 + (size_t)epb * n_veh);
+  } else {
+    gid = (size_t)blockIdx.x * APB + team;
+    in_range = gid < total;
+  }
+  const int P = c.wp_paths, W = c.wp_len, K = c.nb_max, PW = P * W;
+  unsigned char* base = ttc_lds + (size_t)team * smx_ttc_lds_per_agent(P, W);
+  double* wx = reinterpret_cast<double*>(base);
+  double* wy = wx + PW;
+  double* cum = wy + PW;
+  unsigned long long* ttc_min = reinterpret_cast<unsigned long long*>(cum + PW);
+  unsigned long long* dtc_min = ttc_min + P;
+  int* cnt = reinterpret_cast<int*>(dtc_min + P);
+  short* lid = reinterpret_cast<short*>(cnt + P);
+
+  const int flags = in_range ? a.st.flags[gid] : 0;
+  const bool agent = in_range && (flags & SMX_F_ALIVE) && !(flags & SMX_F_SOCIAL);
+  const int n_total = agent ? (int)o.wp_count[gid * (P + 1)] : 0;  // paths the sensor found
+  const int n_paths = min(n_total, P);                             // ... and the rows kept
+  for (int p = r; p < n_paths; p += T) {
+    cnt[p] = min((int)o.wp_count[gid * (P + 1) + 1 + p], W);
+    ttc_min[p] = (unsigned long long)__double_as_longlong(1000.0);
+    dtc_min[p] = (unsigned long long)__double_as_longlong(1.0);
+  }
+  __syncthreads();
+  bool ok = n_paths > 0;  // an observation with at least one path, none of them empty (path[0], :164)
+  for (int p = 0; p < n_paths; ++p) ok = ok && cnt[p] > 0;
+  const int np = ok ? n_paths : 0;
+  // ---- stage the waypoints
+  for (int p = 0; p < np; ++p) {
+    const int n = cnt[p];
+    const size_t row = (gid * P + p) * W;
+    for (int w = r; w < n; w += T) {
+      wx[p * W + w] = o.wp_pos[(row + w) * 3];
+      wy[p * W + w] = o.wp_pos[(row + w) * 3 + 1];
+      lid[p * W + w] = o.wp_lane_id[row + w];
+    }
+  }
+  __syncthreads();
+  // ---- arclength (:206-211): the segment lengths side by side, then one lane per path adds them in order
+  for (int p = 0; p < np; ++p) {
+    const int n = cnt[p];
+    for (int w = r; w + 1 < n; w += T) {
+      const int i = p * W + w;
+      const double dx = wx[i + 1] - wx[i], dy = wy[i + 1] - wy[i];
+      cum[i + 1] = sqrt(dx * dx + dy * dy);
+    }
+  }
+  __syncthreads();
+  for (int p = r; p < np; p += T) {
+    const int n = cnt[p];
+    double acc = 0.0;
+    cum[p * W] = 0.0;
+    for (int w = 1; w < n; ++w) {
+      acc += cum[p * W + w];
+      cum[p * W + w] = acc;
+    }
+  }
+  __syncthreads();
+  // ---- neighbours (:217-254): lane k takes neighbour k
+  const int nb_total = ok ? (int)o.nb_count[gid] : 0;
+  const int nb_kept = min(nb_total, K);
+  const double ego_speed = ok ? (double)o.ego_f32[gid * SMX_EGO_F32_COUNT + SMX_EGO_SPEED] : 0.0;
+  for (int k = r; k < nb_kept; k += T) {
+    const size_t q = gid * K + k;
+    const int v_lane = o.nb_lane_id[q];
+    if (v_lane < 0) continue;  // no lane: never the lane of a waypoint
+    const double vx = o.nb_pos[q * 3], vy = o.nb_pos[q * 3 + 1];
+    double best_gap = SMX_INF, best_sq = SMX_INF;
+    int best_i = -1, best_p = 0;
+    for (int p = 0; p < np; ++p) {
+      const int n = cnt[p];
+      for (int w = 0; w < n; ++w) {
+        const int i = p * W + w;
+        if (lid[i] != v_lane) continue;
+        const double dx = wx[i] - vx, dy = wy[i] - vy;
+        const double sq = dx * dx + dy * dy;
+        if (sq < best_sq) {
+          const double gap = sqrt(sq);
+          if (gap < best_gap) {  // (an equal root keeps the earlier waypoint)
+            best_gap = gap;
+            best_sq = sq;
+            best_i = i;
+            best_p = p;
+          }
+        }
+      }
+    }
+    if (best_i < 0 || best_gap > 2.0) continue;
+    const double lane_dist = cum[best_i];
+    double rel = (ego_speed - (double)o.nb_speed[q]) * 1000.0 / 3600.0;
+    if (fabs(rel) < 1e-5) rel = 1e-5;
+    const double ttc = lane_dist / rel / 10.0;
+    if (ttc <= 0.0) continue;
+    atomicMin(&ttc_min[best_p], (unsigned long long)__double_as_longlong(ttc));
+    atomicMin(&dtc_min[best_p], (unsigned long long)__double_as_longlong(lane_dist / 100.0));
+  }
+  __syncthreads();
+  if (r != 0 || !in_range) return;
+  if (!ok) {
+    // no observation, or one without paths: flags 0, the row untouched (reset pass: a vehicle that ended in this
+    // tick keeps the tick's row)
+    if (!groups || (flags & SMX_F_ALIVE)) o.lane_ttc_flags[gid] = 0;
+    return;
+  }
+  // ---- the closest first waypoint (:164-170), first of equals
+  const double ex = o.ego_pos[gid * 3], ey = o.ego_pos[gid * 3 + 1];
+  int first = 0;
+  double first_d = SMX_INF;
+  for (int p = 0; p < np; ++p) {
+    const double dx = wx[p * W] - ex, dy = wy[p * W] - ey;
+    const double d = sqrt(dx * dx + dy * dy);
+    if (d < first_d) {
+      first_d = d;
+      first = p;
+    }
+  }
+  const size_t fq = (gid * P + first) * W;
+  const double wp_heading = wrap_heading((double)o.wp_heading[fq]);
+  const double ego_heading = wrap_heading((double)o.ego_f32[gid * SMX_EGO_F32_COUNT + SMX_EGO_HEADING]);
+  double dvx, dvy;
+  radians_to_vec(wp_heading, dvx, dvy);  // Heading.direction_vector (coordinates.py:241-243)
+  const double lateral = signed_dist_to_line(ex, ey, wx[first * W], wy[first * W], dvx, dvy);  // road_map.py:608-614
+  double* row = o.lane_ttc + gid * SMX_TTC_COUNT;
+  row[SMX_TTC_DIST_FROM_CENTER] = lateral / ((double)o.wp_lane_width[fq] * 0.5);
+  row[SMX_TTC_ANGLE_ERROR] = heading_relative_to(wp_heading, ego_heading);
+  // ---- _ego_ttc_calc (:259-280): the per-path lists indexed by LANE index
+  const int li = (int)o.wp_lane_index[fq];
+  const bool index_error = li < 0 || li >= np;
+  for (int j = 0; j < 3; ++j) {
+    const int p = li - 1 + j;  // right, current, left
+    const bool have = !index_error && p >= 0 && p < np;
+    row[SMX_TTC_TTC + j] = have ? __longlong_as_double((long long)ttc_min[p]) : 0.0;
+    row[SMX_TTC_DTC + j] = have ? __longlong_as_double((long long)dtc_min[p]) : 0.0;
+  }
+  const bool truncated = n_total > P || nb_total > K || W < c.wp_lookahead + 1;
+  o.lane_ttc_flags[gid] = (uint8_t)(SMX_TTC_VALID | (nb_total > 0 ? SMX_TTC_STD : 0) | (truncated ? SMX_TTC_TRUNCATED : 0) |
+                                    (index_error ? SMX_TTC_INDEX_ERROR : 0));
+}
+
+// =================================================================================
 // k_tail: the end of every pass, one wavefront per env group (those of the observe role), in one launch:
 //  - the tick's commit (commit_role: teardown, done counts, auto-reset respawn);
 //  - the OGM / DAGM tiles of the group's new vehicles (respawned just now, or by k_reset), one after the other — almost
@@ -5055,6 +5235,18 @@ static AliveLayout alive_layout(const smx_config& c) {
   return l;
 }
 
+// SMX_SENSOR_LANE_TTC reads the waypoint and neighbour rows (smx_create and smx_check_buffers both ask)
+#define SMX_STR_(x) #x
+#define SMX_STR(x) SMX_STR_(x)
+static const char* lane_ttc_config_error(const smx_config& c) {
+  if (!(c.sensors & SMX_SENSOR_LANE_TTC)) return nullptr;
+  if (!(c.sensors & SMX_SENSOR_WAYPOINTS) || !(c.sensors & SMX_SENSOR_NEIGHBORS))
+    return "lane_ttc: SMX_SENSOR_LANE_TTC needs SMX_SENSOR_WAYPOINTS and SMX_SENSOR_NEIGHBORS (it is a function of their rows)";
+  if ((int64_t)c.wp_paths * c.wp_len > SMX_TTC_MAX_WAYPOINTS)
+    return "lane_ttc: need wp_paths * wp_len <= " SMX_STR(SMX_TTC_MAX_WAYPOINTS) " (an agent's waypoints are staged in LDS)";
+  return nullptr;
+}
+
 static int create_impl(const smx_config* cfg, int device, smx_handle* out) {
   smx_handle h = new (std::nothrow) smx_handle_s();
   if (!h) return SMX_ERR_NOMEM;
@@ -5140,6 +5332,7 @@ static int create_impl(const smx_config* cfg, int device, smx_handle* out) {
     return fail(h, SMX_ERR_INVALID, "lidar: need 1 <= lidar_rays <= 65536");
   if ((c.sensors & SMX_SENSOR_NEIGHBORS) && (c.nb_max < 1 || c.nb_max > 127))
     return fail(h, SMX_ERR_INVALID, "neighbours: need 1 <= nb_max <= 127");
+  if (const char* why = lane_ttc_config_error(c)) return fail(h, SMX_ERR_INVALID, why);
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return fail(h, SMX_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
   return SMX_OK;
@@ -5652,6 +5845,11 @@ static int check_buffers_impl(const smx_config& c, bool has_vias, bool need_lida
   const bool ogm = (c.sensors & SMX_SENSOR_OGM) != 0, dagm = (c.sensors & SMX_SENSOR_DAGM) != 0;
   const bool lidar = (c.sensors & SMX_SENSOR_LIDAR) != 0, vias = c.via_max > 0 && has_vias;
   const bool rw = (c.sensors & SMX_SENSOR_ROAD_WAYPOINTS) != 0;
+  const bool ttc = (c.sensors & SMX_SENSOR_LANE_TTC) != 0;
+  if (const char* why = lane_ttc_config_error(c)) {
+    err = why;
+    return SMX_ERR_INVALID;
+  }
   const uint64_t RWL = rw ? (uint64_t)c.rw_lanes : 0, RWP = rw ? (uint64_t)c.rw_paths : 0, RWR = rw ? 2 * (uint64_t)c.rw_horizon + 1 : 0;
   const uint64_t PW = (uint64_t)c.wp_paths * c.wp_len, K = (uint64_t)c.nb_max, R = (uint64_t)c.lidar_rays;
 #define ST(field, idx, need, want, req) \
@@ -5721,6 +5919,8 @@ static int check_buffers_impl(const smx_config& c, bool has_vias, bool need_lida
       OUT(final_ego_lane, SMX_OUT_FINAL_EGO_LANE, 2 * T, SMX_DT_I16, false),
       OUT(final_events, SMX_OUT_FINAL_EVENTS, SMX_EV_COUNT * T, SMX_DT_U8, false),
       OUT(final_dist, SMX_OUT_FINAL_DIST, T, SMX_DT_F64, false),
+      OUT(lane_ttc, SMX_OUT_LANE_TTC, SMX_TTC_COUNT * T, SMX_DT_F64, ttc),
+      OUT(lane_ttc_flags, SMX_OUT_LANE_TTC_FLAGS, T, SMX_DT_U8, ttc),
   };
 #undef ST
 #undef OUT
@@ -5956,6 +6156,8 @@ static void observation_pass(smx_handle h, const TickPlan& p, const KernelArgs& 
   }
   if (p.road_waypoints)  // (poses are the tick's new ones; flags still those of its start)
     launch(k_road_waypoints, smx_blocks(total * SMX_RW_LANE_CAP), 0, stream, k);
+  if (p.lane_ttc)  // (the waypoint, neighbour and ego rows are complete here in every form: the side streams have joined)
+    hipLaunchKernelGGL(k_lane_ttc, dim3(p.ttc_blocks), dim3(SMX_BLOCK), p.ttc_lds, stream, k, (const int32_t*)nullptr, (const int32_t*)nullptr);
   if (ph) (void)hipEventRecord(ph[SMX_PHASE_SENSORS + 1], stream);
 }
 
@@ -6007,6 +6209,8 @@ static int tail_and_reset_pass(smx_handle h, const TickPlan& p, const KernelArgs
     }
     r.walk_new = p.first_walks_new ? 1 : 0;
     hipLaunchKernelGGL(k_first, dim3(p.obs_blocks), dim3(SMX_FIRST_BLOCK), 0, stream, r, t.groups, t.n_groups);
+    if (p.lane_ttc)  // after k_first: it reads the first observations' rows, not SMX_F_FIRST
+      hipLaunchKernelGGL(k_lane_ttc, dim3(p.ttc_first_blocks), dim3(SMX_BLOCK), p.ttc_lds, stream, r, (const int32_t*)t.groups, (const int32_t*)t.n_groups);
   }
   return SMX_OK;
 }

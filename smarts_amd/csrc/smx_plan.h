@@ -17,6 +17,7 @@
 #endif
 #define SMX_WPT_MAX_PATHS 8  // dense rows per vehicle (wp_paths) the staged form handles
 #define SMX_OGM_WAVES 4
+#define SMX_TTC_TEAM 16  // lanes of a wavefront that share one agent in k_lane_ttc
 // SMX_LAUNCH_AUTO: the LARGE launch form above this many vehicles.  Measured crossover (round 2, C4's shape:
 // 8 192 vehicles 0.165 / 0.216 ms small / large, 32 768: 0.461 / 0.303, 65 536: 0.886 / 0.505; C3 at 32 768:
 // 0.514 / 0.504; C2 at 8 192: 0.133 / 0.187).  At 16 384 the two cross: every agent alive 0.258 / 0.226, over
@@ -126,6 +127,11 @@ struct TickPlan {
   Ogm ogm;
   Lidar lidar;
   bool dagm, road_waypoints;
+  // k_lane_ttc (SMX_SENSOR_LANE_TTC): in a tick over every agent, on the caller's stream once the waypoint, neighbour
+  // and ego rows are complete (after the joins); in the reset pass over the env groups k_tail listed, after k_first
+  bool lane_ttc;
+  unsigned ttc_blocks, ttc_first_blocks;
+  size_t ttc_lds;  // per workgroup: SMX_BLOCK / SMX_TTC_TEAM agents' waypoints (x, y, arclength, lane id) and per-path minima
   bool tail_builds_list;  // k_tail builds the next tick's alive list
   bool tail_grids;        // ... and the new vehicles' grid tiles
   bool reset_pass, lidar_first, first_walks_new;
@@ -142,6 +148,13 @@ struct TickPlan {
 };
 
 static inline unsigned smx_blocks(size_t threads, size_t block = SMX_BLOCK) { return (unsigned)((threads + block - 1) / block); }
+
+// k_lane_ttc's LDS per agent: x, y, arclength (float64) of wp_paths x wp_len waypoints, per-path ttc / dtc minima
+// (float64), waypoint counts (int32), lane ids (int16), rounded up to 8 bytes.  (constexpr: the kernel carves with it too)
+static constexpr size_t smx_ttc_lds_per_agent(int wp_paths, int wp_len) {
+  return 3 * 8 * ((size_t)wp_paths * wp_len) + 2 * 8 * (size_t)wp_paths +
+         ((4 * (size_t)wp_paths + 2 * ((size_t)wp_paths * wp_len) + 7) & ~(size_t)7);
+}
 
 static inline TickPlan tick_plan(const PlanInputs& in) {
   const smx_config& c = *in.cfg;
@@ -242,6 +255,7 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
   p.dagm = p.dagm_bytes != 0;
   p.lidar = !lidar ? Lidar::NONE : small ? Lidar::IN_SENSORS : p.fork ? Lidar::SIDE : Lidar::CALLER;
   p.road_waypoints = (c.sensors & SMX_SENSOR_ROAD_WAYPOINTS) != 0;
+  p.lane_ttc = (c.sensors & SMX_SENSOR_LANE_TTC) != 0;
 
   // k_tail builds the next tick's alive list unless k_social moves vehicles (and can end them) ahead of the list
   p.tail_builds_list = !small && in.alive_blob && in.slow.base && !idm;
@@ -268,5 +282,11 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
   p.facts_blocks = one_lane ? p.veh_blocks : wide ? smx_blocks(total * SMX_TEAM) : smx_blocks(total * SMX_TEAM_LARGE);
   p.sensor_blocks = p.wp_blocks + p.obs_blocks + p.lidar_blocks + (p.ogm == Ogm::IN_SENSORS ? (unsigned)total : 0);
   p.sensor_lds = p.ogm == Ogm::IN_SENSORS ? p.ogm_bytes : 0;
+  if (p.lane_ttc) {
+    const size_t apb = SMX_BLOCK / SMX_TTC_TEAM;  // agents per workgroup
+    p.ttc_blocks = smx_blocks(total, apb);
+    p.ttc_first_blocks = p.reset_pass ? p.obs_blocks * (unsigned)(SMX_BLOCK / apb) : 0;  // an env group holds up to SMX_BLOCK vehicles
+    p.ttc_lds = apb * smx_ttc_lds_per_agent(c.wp_paths, c.wp_len);
+  }
   return p;
 }

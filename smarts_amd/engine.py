@@ -74,6 +74,9 @@ class SimConfig:
     rw_horizon: int = 32
     rw_lanes: int = 8
     rw_paths: int = 4
+    # lane_ttc (custom_observations.py:148-280) of every agent on the device: out["lane_ttc"], out["lane_ttc_flags"]
+    # (include/smx.h SMX_SENSOR_LANE_TTC); needs waypoints and neighbors
+    lane_ttc: bool = False
 
     def sensors_mask(self) -> int:
         m = 0
@@ -91,6 +94,8 @@ class SimConfig:
             m |= nat.SENSOR_DAGM
         if self.road_waypoints:
             m |= nat.SENSOR_ROAD_WAYPOINTS
+        if self.lane_ttc:
+            m |= nat.SENSOR_LANE_TTC
         return m
 
     def done_mask(self) -> int:
@@ -365,6 +370,9 @@ class BatchedSim:
             o["rw_speed_limit"] = z((E, N, L, Q, R), torch.float32)
             o["rw_lane_index"] = z((E, N, L, Q, R), torch.int8)
             o["rw_lane_id"] = z((E, N, L, Q, R), torch.int16)
+        if cfg.lane_ttc:
+            o["lane_ttc"] = z((E, N, nat.TTC_COUNT), torch.float64)
+            o["lane_ttc_flags"] = z((E, N), torch.uint8)
         if cfg.lidar is not None:
             R = ray_count(cfg.lidar)
             o["lidar_hit"] = z((E, N, R), torch.uint8)

@@ -176,7 +176,10 @@ class FormatObs:
     @staticmethod
     def from_rows(rows: Dict[str, np.ndarray], env: int, slot: int) -> StdObs:
         """Slice ``StdObs`` of agent (env, slot) straight out of host copies of the dense device
-        rows (the ttc block needs lane ids per neighbour and is only built by ``observation``)."""
+        rows.  The ttc block comes from ``rows["lane_ttc"]`` / ``rows["lane_ttc_flags"]`` where the rows hold them
+        (``SimConfig(lane_ttc=True)``, or ``lane_ttc_rows`` on the host) and the agent's flags say the reference's
+        ``_std_ttc`` would not be ``None``; without those keys it stays ``None`` (``observation`` builds it from
+        objects)."""
         E = nat.EGO
         f = rows["ego_f32"][env, slot]
         v3 = lambda k: np.array(f[E[k]:E[k] + 3], dtype=np.float32)  # noqa: E731
@@ -190,7 +193,14 @@ class FormatObs:
         }
         ev = rows["events"][env, slot]
         events = {name: np.int8(ev[i]) for i, name in enumerate(nat.EVENT_NAMES)}
-        neighbors = waypoints = ogm = lidar = None
+        neighbors = waypoints = ogm = lidar = ttc = None
+        if "lane_ttc" in rows and int(rows["lane_ttc_flags"][env, slot]) & nat.TTC_STD:
+            v, T = rows["lane_ttc"][env, slot], nat.TTC  # format_obs.py:551-562
+            ttc = {
+                "angle_error": np.float32(v[T["ANGLE_ERROR"]]), "distance_from_center": np.float32(v[T["DIST_FROM_CENTER"]]),
+                "dtc": np.array(v[T["DTC"]:T["DTC"] + 3], dtype=np.float32),
+                "ttc": np.array(v[T["TTC"]:T["TTC"] + 3], dtype=np.float32),
+            }
         if "nb_pos" in rows and rows["nb_count"][env, slot] > 0:
             neighbors = {
                 "box": np.array(rows["nb_box"][env, slot]), "heading": np.array(rows["nb_heading"][env, slot]),
@@ -215,4 +225,4 @@ class FormatObs:
             cloud = np.nan_to_num(np.array(rows["lidar_point"][env, slot]), nan=0.0, posinf=0.0, neginf=0.0)
             lidar = {"hit": hit, "point_cloud": cloud}
         return StdObs(dist=np.float32(rows["dist"][env, slot]), ego=ego, events=events, lidar=lidar, neighbors=neighbors,
-                      ogm=ogm, waypoints=waypoints, dagm=dagm)
+                      ogm=ogm, waypoints=waypoints, dagm=dagm, ttc=ttc)
