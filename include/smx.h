@@ -85,7 +85,12 @@ enum {
    * (format_obs.py:551-562), computed on the device from this pass's wp_*, nb_* and ego_* rows
    * (smx_outputs.lane_ttc).  Valid only together with SMX_SENSOR_WAYPOINTS and SMX_SENSOR_NEIGHBORS, and while
    * wp_paths * wp_len <= SMX_TTC_MAX_WAYPOINTS (an agent's waypoints are staged in LDS). */
-  SMX_SENSOR_LANE_TTC = 1 << 7
+  SMX_SENSOR_LANE_TTC = 1 << 7,
+  /* The ego-centric observation adapter (smarts/core/utils/adapters/ego_centric_adapters.py:60-176 over
+   * smarts/core/utils/math.py:452-505) on the device: every position and heading of this pass's ego, waypoint,
+   * neighbour, lidar and road-waypoint rows (those whose sensors are on) in the frame of the agent's own vehicle,
+   * written beside the world rows (smx_outputs.ego_frame, ec_*), and the frame kept for smx_actions_to_world. */
+  SMX_SENSOR_EGO_CENTRIC = 1 << 8
 };
 #define SMX_TTC_MAX_WAYPOINTS 512
 
@@ -375,6 +380,8 @@ enum { /* indices into smx_outputs.count / .dtype: the pointers in declaration o
   SMX_OUT_RW_LANE_WIDTH, SMX_OUT_RW_SPEED_LIMIT, SMX_OUT_RW_LANE_INDEX, SMX_OUT_RW_LANE_ID,
   SMX_OUT_FINAL_EGO_POS, SMX_OUT_FINAL_EGO_F32, SMX_OUT_FINAL_EGO_LANE, SMX_OUT_FINAL_EVENTS, SMX_OUT_FINAL_DIST,
   SMX_OUT_LANE_TTC, SMX_OUT_LANE_TTC_FLAGS,
+  SMX_OUT_EGO_FRAME, SMX_OUT_EC_FLAGS, SMX_OUT_EC_EGO_F32, SMX_OUT_EC_WP_POS, SMX_OUT_EC_WP_HEADING, SMX_OUT_EC_NB_POS,
+  SMX_OUT_EC_NB_HEADING, SMX_OUT_EC_LIDAR_POINT, SMX_OUT_EC_RW_POS, SMX_OUT_EC_RW_HEADING,
   SMX_OUT_BUFFERS
 };
 typedef struct smx_outputs {
@@ -453,6 +460,27 @@ typedef struct smx_outputs {
    * first observation; there is no final_* twin (the finishing tick's env_obs is low-dimensional). */
   double* lane_ttc;        /* [E*N][SMX_TTC_COUNT]                             */
   uint8_t* lane_ttc_flags; /* [E*N] SMX_TTC_* bits                             */
+  /* SMX_SENSOR_EGO_CENTRIC, all NULL if unused, and a row NULL where its sensor is off: the pass's rows in the frame
+   * F = (px, py, pz, H) of the agent's own vehicle — (px, py, pz) its ego_pos row, H the float64 heading that
+   * ego_f32[SMX_EGO_HEADING] is the rounding of.  With c = cos(-H), s = sin(-H) (_gen_ego_frame_matrix, math.py:464-470):
+   *   to_ego(p) = (c dx - s dy, s dx + c dy, dz), d = p - (px, py, pz)        (position_to_ego_frame, math.py:473-487)
+   *   rel(h)    = Heading(wrap_value(h - H, -pi, pi))                          (math.py:452-461, coordinates.py:175-184)
+   *   dyn(v)    = (|v[:2]|, 0, v[2])                                           (ego_frame_dynamics, adapter :66-67)
+   * float32 inputs are widened to float64, transformed and rounded back; positions stay float64.  Entries beyond
+   * wp_count / nb_count / the rw_* counts are neither read nor written.  Rows of agents without an observation in the
+   * pass keep their contents and read ec_flags 0.  Under auto_reset the rows of a restarted env describe its first
+   * observation; there is no final_* twin.  Everything frame-independent (widths, speed limits, lane ids, counts,
+   * grids) is read from the world rows. */
+  double* ego_frame;      /* [E*N][4] px, py, pz, H: the frame itself (the adapters' last_obs)              */
+  uint8_t* ec_flags;      /* [E*N] bit 0: the agent had an observation in this pass, its rows were written  */
+  float* ec_ego_f32;      /* [E*N][SMX_EGO_F32_COUNT] heading 0, dyn() on linear velocity / acceleration / jerk, the rest copied */
+  double* ec_wp_pos;      /* [E*N][wp_paths][wp_len][3] to_ego(), z = 0                                     */
+  float* ec_wp_heading;   /* [E*N][wp_paths][wp_len] rel()                                                  */
+  double* ec_nb_pos;      /* [E*N][nb_max][3]                                                               */
+  float* ec_nb_heading;   /* [E*N][nb_max]                                                                  */
+  double* ec_lidar_point; /* [E*N][lidar_rays][3]; a ray with lidar_hit 0 reads three NaNs (the reference's 0 * inf) */
+  double* ec_rw_pos;      /* layout of rw_pos                                                               */
+  float* ec_rw_heading;   /* layout of rw_heading                                                           */
   /* what the caller allocated: element count and SMX_DT_* of each buffer above, in declaration order
    * (SMX_OUT_*); 0 / SMX_DT_NONE for a NULL pointer */
   uint64_t count[SMX_OUT_BUFFERS];
@@ -550,6 +578,23 @@ int smx_step_target_pose(smx_handle h, const double* targets_dev, const smx_stat
 int smx_step_trajectory_with_time(smx_handle h, const double* trajectories_dev, const int32_t* counts_dev,
                                   int32_t max_points, const smx_state* st, const smx_spawns* sp, const smx_outputs* out,
                                   void* hip_stream);
+/* The action half of the ego-centric adapters (ego_centric_adapters.py:195-266): rewrites an action buffer given in the
+ * frame of each agent's last observation (out->ego_frame, out->ec_flags: the last smx_reset / smx_step* pass) into
+ * out_dev, a second caller-owned device buffer of the same layout, which the matching smx_step_* then takes.  One
+ * kernel on hip_stream, no synchronisation.  With (px, py, pz, H) the frame, to_world(q) = inv(M) q + (px, py, pz)
+ * (world_position_from_ego_frame, math.py:490-505; inv(M) is M's transpose) and headings become
+ * wrap_value(h + H, -pi, pi) (no Heading()):
+ *   SMX_ACTION_SPACE_TRAJECTORY            [E*N][4][SMX_TRAJ_COLS]: columns < min(count, 10) and column 10; speed copied
+ *   SMX_ACTION_SPACE_TARGET_POSE           [E*N][4]: x, y, heading; seconds copied (counts_dev is not read)
+ *   SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME  [E*N][5][max_points]: rows 1, 2, 3 (x, y, heading) of the first
+ *                                          min(count, max_points) points; time and speed copied
+ * (the rows smx_step_trajectory_with_time calls x, y and heading; the reference's adapter would rotate rows 0 and 1,
+ * DESIGN.md).  Every other element is copied.  An agent is copied through whole when its ec_flags is 0 (last_obs is
+ * None), when it sent no action (NaN x, count 0) or when it is a social slot.  action_space must be one of the three
+ * and equal cfg.action_space (else SMX_ERR_INVALID); a configuration without SMX_SENSOR_EGO_CENTRIC gives
+ * SMX_ERR_STATE. */
+int smx_actions_to_world(smx_handle h, int32_t action_space, const double* in_dev, const int32_t* counts_dev,
+                         int32_t max_points, double* out_dev, const smx_outputs* out, void* hip_stream);
 /* Waits for the stream, then reports what only the kernels could see since the last smx_sync, as SMX_ERR_INVALID: a
  * Lane action code outside -1..3; a TrajectoryWithTime action the reference raises on (fewer than two points or more
  * than max_points, a value that is not finite, times not strictly increasing, no point later than dt or the first one

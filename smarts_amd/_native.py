@@ -30,6 +30,8 @@ PHASES = ["control", "scan", "ogm", "sensors", "commit", "reset"]
 SENSOR_WAYPOINTS, SENSOR_NEIGHBORS, SENSOR_ACCELEROMETER, SENSOR_OGM, SENSOR_LIDAR, SENSOR_DAGM = 1, 2, 4, 8, 16, 32
 SENSOR_ROAD_WAYPOINTS = 64
 SENSOR_LANE_TTC = 128
+SENSOR_EGO_CENTRIC = 256  # smx_outputs.ego_frame / ec_* (the ego-centric adapters on the device)
+EC_VALID = 1  # smx_outputs.ec_flags bit 0
 # columns of smx_outputs.lane_ttc (SMX_TTC_*; "TTC" and "DTC" head three columns: right, current, left lane) and the
 # bits of smx_outputs.lane_ttc_flags
 TTC = dict(DIST_FROM_CENTER=0, ANGLE_ERROR=1, TTC=2, DTC=5)
@@ -128,11 +130,16 @@ OUTPUT_FIELDS = [
 OUTPUT_FIELDS.insert(OUTPUT_FIELDS.index("learner"), "via_hit")
 OUTPUT_FIELDS.insert(OUTPUT_FIELDS.index("via_hit"), "via_near_count")
 OUTPUT_FIELDS.insert(OUTPUT_FIELDS.index("via_near_count"), "via_near")
+# SMX_SENSOR_EGO_CENTRIC: the frame and the ego-frame twins of the position / heading rows above, appended to
+# smx_outputs after them (OUTPUT_FIELDS keeps the world rows; OUTPUT_BUFFERS is the struct's whole pointer list)
+EC_OUTPUT_FIELDS = ["ego_frame", "ec_flags", "ec_ego_f32", "ec_wp_pos", "ec_wp_heading", "ec_nb_pos", "ec_nb_heading",
+                    "ec_lidar_point", "ec_rw_pos", "ec_rw_heading"]
+OUTPUT_BUFFERS = OUTPUT_FIELDS + EC_OUTPUT_FIELDS
 
 
 class SmxOutputs(C.Structure):
-    _fields_ = [(name, _p) for name in OUTPUT_FIELDS] + [
-        ("count", C.c_uint64 * len(OUTPUT_FIELDS)), ("dtype", C.c_uint8 * ((len(OUTPUT_FIELDS) + 7) & ~7))]
+    _fields_ = [(name, _p) for name in OUTPUT_BUFFERS] + [
+        ("count", C.c_uint64 * len(OUTPUT_BUFFERS)), ("dtype", C.c_uint8 * ((len(OUTPUT_BUFFERS) + 7) & ~7))]
 
 
 def torch_dtype_code(t) -> int:
@@ -155,7 +162,7 @@ EXPORTS = [
     "smx_create", "smx_load_map", "smx_set_vias", "smx_set_missions", "smx_step_continuous", "smx_step_trajectory", "smx_read_phase_ms", "smx_set_lidar_rays", "smx_reset", "smx_step", "smx_sync", "smx_last_step_ms",
     "smx_set_timing", "smx_last_error", "smx_version", "smx_destroy", "smx_set_controller_gains", "smx_struct_size", "smx_read_step_ms",
     "smx_check_buffers", "smx_set_launch_strategy", "smx_launch_form", "smx_step_target_pose", "smx_step_trajectory_with_time",
-    "smx_set_mission_goals", "smx_check_mission_goals",
+    "smx_set_mission_goals", "smx_check_mission_goals", "smx_actions_to_world",
 ]
 LAUNCH_FORMS = {0: "small", 1: "large_teams", 2: "large_one_lane"}
 LAUNCH_STRATEGIES = {"auto": 0, "small": 1, "large": 2, "large_one_lane": 3, "large_teams": 4}
@@ -225,6 +232,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.smx_step_trajectory_with_time.argtypes = [h, _p, _p, _i32, C.POINTER(SmxState), C.POINTER(SmxSpawns),
                                                   C.POINTER(SmxOutputs), _p]
     lib.smx_step_trajectory_with_time.restype = C.c_int
+    lib.smx_actions_to_world.argtypes = [h, _i32, _p, _p, _i32, _p, C.POINTER(SmxOutputs), _p]
+    lib.smx_actions_to_world.restype = C.c_int
     lib.smx_read_phase_ms.argtypes = [h, C.POINTER(C.c_float), _i32, C.POINTER(_i32)]
     lib.smx_read_phase_ms.restype = C.c_int
     lib.smx_set_timing.argtypes = [h, C.c_int]

@@ -4895,6 +4895,200 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_lane_ttc(const KernelArgs a, cons
 }
 
 // =================================================================================
+// k_ego_frame (SMX_SENSOR_EGO_CENTRIC): the reference's ego_centric_observation_adapter
+// (smarts/core/utils/adapters/ego_centric_adapters.py:60-176) over the dense rows this pass has just written — the
+// function smarts_amd/env/ego_centric_rows.py restates on the host.  A pure streaming transform: every position and
+// heading of the waypoint, neighbour, lidar and road-waypoint rows is read once and written once into its ec_* twin.
+// SMX_EC_TEAM lanes of a wavefront share an agent:
+//  - lane 0 of the team reads the float64 heading H the observe role rounded into ego_f32 (wrap_heading of the state's)
+//    and takes cos(-H), sin(-H) once (_gen_ego_frame_matrix, math.py:464-470: a float64 sincos is some hundred
+//    instructions on this chip, a point's transform four); the team gets them by a cross-lane read;
+//  - the team walks each [..][3] float64 row element by element in memory order, lane r element r, r + 16, ...: a store
+//    instruction of the team writes one 128-byte line, and the x and y an element needs are in the lines its
+//    neighbours read;
+//  - the per-path counts bound the loops (a path is skipped or walked whole; no lane-dependent branch inside a row
+//    beyond the select of the component).
+// The launch sites and the meaning of `groups` are k_lane_ttc's: in a tick every vehicle (flags are those of the tick's
+// start: an agent alive then has an observation), in the reset pass the env groups k_tail listed, after k_first.
+// =================================================================================
+// wrap_value(value, -pi, pi) (math.py:452-461): (-pi, pi], both branches tested on the value that came in
+__device__ __forceinline__ double wrap_value_pi(double value) {
+  double v = value;
+  if (value <= -SMX_PI) v = SMX_PI - py_mod(-SMX_PI - value, SMX_TWO_PI);
+  if (value > SMX_PI) v = -SMX_PI + py_mod(value - SMX_PI, SMX_TWO_PI);
+  return v;
+}
+
+struct EgoFrame {
+  double px, py, pz, H, cs, sn;  // cs = cos(-H), sn = sin(-H)
+};
+
+// position_to_ego_frame (math.py:473-487) over `n` points of a [..][3] row; `flat`: the row's z is written as 0 (a
+// waypoint: transform(np.append(wp.pos, [0]))[:2], adapter :93); `hit`: per point, 0 = write three NaNs (a lidar miss)
+__device__ __forceinline__ void ec_points(const EgoFrame& f, const double* __restrict__ src, double* __restrict__ dst, int n, int r,
+                                          bool flat, const uint8_t* hit) {
+  for (int i = r; i < 3 * n; i += SMX_EC_TEAM) {
+    const int q = i / 3, comp = i - 3 * q;
+    const double dx = src[3 * q] - f.px, dy = src[3 * q + 1] - f.py;
+    double v = comp == 0 ? f.cs * dx - f.sn * dy : comp == 1 ? f.sn * dx + f.cs * dy : (flat ? 0.0 : src[i] - f.pz);
+    if (hit && !hit[q]) v = __builtin_nan("");
+    dst[i] = v;
+  }
+}
+// Heading(wrap_value(h - H, -pi, pi)) (adapter :72-73, :94) over `n` float32 headings
+__device__ __forceinline__ void ec_headings(const EgoFrame& f, const float* __restrict__ src, float* __restrict__ dst, int n, int r) {
+  for (int i = r; i < n; i += SMX_EC_TEAM) dst[i] = (float)wrap_heading(wrap_value_pi((double)src[i] - f.H));
+}
+
+__global__ void __launch_bounds__(SMX_BLOCK) k_ego_frame(const KernelArgs a, const int32_t* groups, const int32_t* n_groups) {
+  constexpr int T = SMX_EC_TEAM, APB = SMX_BLOCK / T;
+  const smx_config& c = a.cfg;
+  const smx_outputs& o = a.out;
+  const size_t total = (size_t)c.num_envs * c.num_vehicles;
+  const int team = (int)threadIdx.x / T, r = (int)threadIdx.x % T;
+  size_t gid;
+  bool in_range;
+  if (groups) {
+    constexpr int BPG = SMX_BLOCK / APB;  // workgroups per env group (up to SMX_BLOCK vehicles)
+    const int entry = (int)blockIdx.x / BPG;
+    if (entry >= *n_groups) return;  // (uniform in the workgroup)
+    const int n_veh = c.num_vehicles, epb = SMX_BLOCK / n_veh;
+    const size_t g0 = (size_t)groups[entry] * epb * n_veh;
+    gid = g0 + (size_t)((int)blockIdx.x % BPG) * APB + team;
+    in_range = gid < min(total, g0 + (size_t)epb * n_veh);
+  } else {
+    gid = (size_t)blockIdx.x * APB + team;
+    in_range = gid < total;
+  }
+  const int flags = in_range ? a.st.flags[gid] : 0;
+  const bool agent = in_range && (flags & SMX_F_ALIVE) && !(flags & SMX_F_SOCIAL);
+  EgoFrame f{0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+  if (agent && r == 0) {
+    f.H = wrap_heading(SF(SMX_S_HEADING));  // what k_observe rounds into ego_f32[SMX_EGO_HEADING]
+    sincos(-f.H, &f.sn, &f.cs);
+  }
+  f.H = __shfl(f.H, 0, T);  // (every lane of the wavefront is still here)
+  f.cs = __shfl(f.cs, 0, T);
+  f.sn = __shfl(f.sn, 0, T);
+  if (!agent) {
+    // no observation in this pass: flags 0, the rows untouched (reset pass: a vehicle that ended in this tick keeps
+    // the tick's rows)
+    if (r == 0 && in_range && (!groups || (flags & SMX_F_ALIVE))) o.ec_flags[gid] = 0;
+    return;
+  }
+  f.px = o.ego_pos[gid * 3];
+  f.py = o.ego_pos[gid * 3 + 1];
+  f.pz = o.ego_pos[gid * 3 + 2];
+  if (r < 4) o.ego_frame[gid * 4 + r] = r == 0 ? f.px : r == 1 ? f.py : r == 2 ? f.pz : f.H;
+  // ---- the ego block (adapter :134-144): position and heading are the origin, the linear triples point along x
+  const float* ef = o.ego_f32 + gid * SMX_EGO_F32_COUNT;
+  for (int k = r; k < SMX_EGO_F32_COUNT; k += T) {
+    float v = ef[k];
+    if (k == SMX_EGO_HEADING) v = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int base = j == 0 ? SMX_EGO_LIN_VEL : j == 1 ? SMX_EGO_LIN_ACC : SMX_EGO_LIN_JERK;
+      if (k == base) {
+        const double x = (double)ef[base], y = (double)ef[base + 1];
+        v = (float)sqrt(x * x + y * y);  // np.linalg.norm(v[:2])
+      } else if (k == base + 1) {
+        v = 0.0f;
+      }
+    }
+    o.ec_ego_f32[gid * SMX_EGO_F32_COUNT + k] = v;
+  }
+  if (c.sensors & SMX_SENSOR_WAYPOINTS) {
+    const int P = c.wp_paths, W = c.wp_len;
+    const int n_paths = min((int)o.wp_count[gid * (P + 1)], P);
+    for (int p = 0; p < n_paths; ++p) {
+      const int n = min((int)o.wp_count[gid * (P + 1) + 1 + p], W);
+      const size_t row = (gid * P + p) * W;
+      ec_points(f, o.wp_pos + row * 3, o.ec_wp_pos + row * 3, n, r, true, nullptr);
+      ec_headings(f, o.wp_heading + row, o.ec_wp_heading + row, n, r);
+    }
+  }
+  if (c.sensors & SMX_SENSOR_NEIGHBORS) {
+    const int K = c.nb_max, n = min((int)o.nb_count[gid], K);
+    ec_points(f, o.nb_pos + gid * K * 3, o.ec_nb_pos + gid * K * 3, n, r, false, nullptr);
+    ec_headings(f, o.nb_heading + gid * K, o.ec_nb_heading + gid * K, n, r);
+  }
+  if (c.sensors & SMX_SENSOR_LIDAR) {
+    const size_t row = gid * (size_t)c.lidar_rays;
+    ec_points(f, o.lidar_point + row * 3, o.ec_lidar_point + row * 3, c.lidar_rays, r, false, o.lidar_hit + row);
+  }
+  if (c.sensors & SMX_SENSOR_ROAD_WAYPOINTS) {
+    const int L = c.rw_lanes, P = c.rw_paths, R = 2 * c.rw_horizon + 1;
+    for (int l = 0; l < L; ++l) {
+      const size_t lane_row = gid * (size_t)L + l;
+      if (o.rw_lane[lane_row] < 0) continue;  // (uniform in the team)
+      const int n_paths = min((int)o.rw_path_count[lane_row], P);
+      for (int p = 0; p < n_paths; ++p) {
+        const int n = min((int)o.rw_count[lane_row * P + p], R);
+        const size_t row = (lane_row * P + p) * (size_t)R;
+        ec_points(f, o.rw_pos + row * 3, o.ec_rw_pos + row * 3, n, r, true, nullptr);
+        ec_headings(f, o.rw_heading + row, o.ec_rw_heading + row, n, r);
+      }
+    }
+  }
+  if (r == 0) o.ec_flags[gid] = 1;
+}
+
+// =================================================================================
+// k_actions_to_world: the action half of the ego-centric adapters (ego_centric_adapters.py:195-266) — an action buffer
+// given in the frame of each agent's last observation (ego_frame / ec_flags of the last pass) rewritten into a second
+// buffer of the same layout in world coordinates.  One lane per (agent, point); the lanes of an agent are adjacent in
+// the wavefront, the first of them takes cos(-H), sin(-H) and the others read them across lanes.  A lane writes every
+// row of its column, converted or copied, so the output is complete whatever the agents sent.
+//   to_world(q) = inv(M) q + (px, py, pz) (world_position_from_ego_frame, math.py:490-505; inv(M) = M transposed)
+//   heading     = wrap_value(h + H, -pi, pi) (adapter :206-211, :260-262)
+// =================================================================================
+template <int SPACE>
+__global__ void __launch_bounds__(SMX_BLOCK) k_actions_to_world(const double* __restrict__ in, const int32_t* __restrict__ counts,
+                                                                double* __restrict__ out, const double* __restrict__ frame,
+                                                                const uint8_t* __restrict__ ec_flags, const size_t total,
+                                                                const int n_veh, const int n_social, const int cols) {
+  constexpr bool POSE = SPACE == SMX_ACTION_SPACE_TARGET_POSE, TIMED = SPACE == SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME;
+  constexpr int ROWS = POSE ? 4 : TIMED ? 5 : 4;
+  constexpr int RX = TIMED ? 1 : 0;  // rows x, y, heading are RX, RX + 1, RX + 2
+  const int t = (int)threadIdx.x;
+  const size_t tid = (size_t)blockIdx.x * SMX_BLOCK + t;
+  const size_t gid = tid / (size_t)cols;
+  const int col = (int)(tid - gid * (size_t)cols);
+  const bool valid = gid < total;
+  const int leader = max(0, t - col);  // the agent's first lane in this wavefront
+  const bool framed = valid && (ec_flags[gid] & 1) && (int)(gid % (size_t)n_veh) < n_veh - n_social;
+  double H = 0.0, cs = 1.0, sn = 0.0;
+  if (framed && t == leader) {
+    H = frame[gid * 4 + 3];
+    sincos(-H, &sn, &cs);
+  }
+  H = __shfl(H, leader);
+  cs = __shfl(cs, leader);
+  sn = __shfl(sn, leader);
+  if (!valid) return;
+  // POSE: [E*N][4], one column; else [E*N][ROWS][cols]
+  const size_t base = POSE ? gid * 4 : gid * (size_t)ROWS * cols + col, stride = POSE ? 1 : (size_t)cols;
+  double v[ROWS];
+#pragma unroll
+  for (int k = 0; k < ROWS; ++k) v[k] = in[base + k * stride];
+  bool convert = framed;
+  if (POSE) {
+    convert = convert && !(v[0] != v[0]);  // a NaN x: no action this tick
+  } else {
+    const int n = counts[gid];  // 0: no action this tick
+    convert = convert && n > 0 && (TIMED ? col < min(n, cols) : (col < min(n, SMX_TRAJ_COLS - 1) || col == SMX_TRAJ_COLS - 1));
+  }
+  if (convert) {
+    const double qx = v[RX], qy = v[RX + 1];
+    v[RX] = (cs * qx + sn * qy) + frame[gid * 4];
+    v[RX + 1] = (cs * qy - sn * qx) + frame[gid * 4 + 1];
+    v[RX + 2] = wrap_value_pi(v[RX + 2] + H);
+  }
+#pragma unroll
+  for (int k = 0; k < ROWS; ++k) out[base + k * stride] = v[k];
+}
+
+// =================================================================================
 // k_tail: the end of every pass, one wavefront per env group (those of the observe role), in one launch:
 //  - the tick's commit (commit_role: teardown, done counts, auto-reset respawn);
 //  - the OGM / DAGM tiles of the group's new vehicles (respawned just now, or by k_reset), one after the other — almost
@@ -5846,6 +6040,7 @@ static int check_buffers_impl(const smx_config& c, bool has_vias, bool need_lida
   const bool lidar = (c.sensors & SMX_SENSOR_LIDAR) != 0, vias = c.via_max > 0 && has_vias;
   const bool rw = (c.sensors & SMX_SENSOR_ROAD_WAYPOINTS) != 0;
   const bool ttc = (c.sensors & SMX_SENSOR_LANE_TTC) != 0;
+  const bool ec = (c.sensors & SMX_SENSOR_EGO_CENTRIC) != 0;
   if (const char* why = lane_ttc_config_error(c)) {
     err = why;
     return SMX_ERR_INVALID;
@@ -5921,6 +6116,16 @@ static int check_buffers_impl(const smx_config& c, bool has_vias, bool need_lida
       OUT(final_dist, SMX_OUT_FINAL_DIST, T, SMX_DT_F64, false),
       OUT(lane_ttc, SMX_OUT_LANE_TTC, SMX_TTC_COUNT * T, SMX_DT_F64, ttc),
       OUT(lane_ttc_flags, SMX_OUT_LANE_TTC_FLAGS, T, SMX_DT_U8, ttc),
+      OUT(ego_frame, SMX_OUT_EGO_FRAME, 4 * T, SMX_DT_F64, ec),
+      OUT(ec_flags, SMX_OUT_EC_FLAGS, T, SMX_DT_U8, ec),
+      OUT(ec_ego_f32, SMX_OUT_EC_EGO_F32, SMX_EGO_F32_COUNT * T, SMX_DT_F32, ec),
+      OUT(ec_wp_pos, SMX_OUT_EC_WP_POS, T * PW * 3, SMX_DT_F64, ec && wp),
+      OUT(ec_wp_heading, SMX_OUT_EC_WP_HEADING, T * PW, SMX_DT_F32, ec && wp),
+      OUT(ec_nb_pos, SMX_OUT_EC_NB_POS, T * K * 3, SMX_DT_F64, ec && nb),
+      OUT(ec_nb_heading, SMX_OUT_EC_NB_HEADING, T * K, SMX_DT_F32, ec && nb),
+      OUT(ec_lidar_point, SMX_OUT_EC_LIDAR_POINT, T * R * 3, SMX_DT_F64, ec && lidar),
+      OUT(ec_rw_pos, SMX_OUT_EC_RW_POS, T * RWL * RWP * RWR * 3, SMX_DT_F64, ec && rw),
+      OUT(ec_rw_heading, SMX_OUT_EC_RW_HEADING, T * RWL * RWP * RWR, SMX_DT_F32, ec && rw),
   };
 #undef ST
 #undef OUT
@@ -6158,6 +6363,8 @@ static void observation_pass(smx_handle h, const TickPlan& p, const KernelArgs& 
     launch(k_road_waypoints, smx_blocks(total * SMX_RW_LANE_CAP), 0, stream, k);
   if (p.lane_ttc)  // (the waypoint, neighbour and ego rows are complete here in every form: the side streams have joined)
     hipLaunchKernelGGL(k_lane_ttc, dim3(p.ttc_blocks), dim3(SMX_BLOCK), p.ttc_lds, stream, k, (const int32_t*)nullptr, (const int32_t*)nullptr);
+  if (p.ego_centric)  // (the same site: every world row it reads, the lidar's and the road waypoints' included, is complete)
+    hipLaunchKernelGGL(k_ego_frame, dim3(p.ec_blocks), dim3(SMX_BLOCK), 0, stream, k, (const int32_t*)nullptr, (const int32_t*)nullptr);
   if (ph) (void)hipEventRecord(ph[SMX_PHASE_SENSORS + 1], stream);
 }
 
@@ -6211,6 +6418,8 @@ static int tail_and_reset_pass(smx_handle h, const TickPlan& p, const KernelArgs
     hipLaunchKernelGGL(k_first, dim3(p.obs_blocks), dim3(SMX_FIRST_BLOCK), 0, stream, r, t.groups, t.n_groups);
     if (p.lane_ttc)  // after k_first: it reads the first observations' rows, not SMX_F_FIRST
       hipLaunchKernelGGL(k_lane_ttc, dim3(p.ttc_first_blocks), dim3(SMX_BLOCK), p.ttc_lds, stream, r, (const int32_t*)t.groups, (const int32_t*)t.n_groups);
+    if (p.ego_centric)
+      hipLaunchKernelGGL(k_ego_frame, dim3(p.ec_first_blocks), dim3(SMX_BLOCK), 0, stream, r, (const int32_t*)t.groups, (const int32_t*)t.n_groups);
   }
   return SMX_OK;
 }
@@ -6365,6 +6574,39 @@ extern "C" int smx_step_trajectory_with_time(smx_handle h, const double* traject
                                              const smx_outputs* out, void* hip_stream) {
   if (h && max_points < 2) return fail(h, SMX_ERR_INVALID, "smx_step_trajectory_with_time: max_points < 2");
   return enqueue(h, Entry::TRAJECTORY_WITH_TIME, nullptr, nullptr, trajectories_dev, counts_dev, max_points, nullptr, st, sp, out, hip_stream);
+}
+
+extern "C" int smx_actions_to_world(smx_handle h, int32_t action_space, const double* in_dev, const int32_t* counts_dev,
+                                    int32_t max_points, double* out_dev, const smx_outputs* out, void* hip_stream) {
+  if (!h) return SMX_ERR_INVALID;
+  const smx_config& c = h->cfg;
+  if (!(c.sensors & SMX_SENSOR_EGO_CENTRIC))
+    return fail(h, SMX_ERR_STATE, "smx_actions_to_world: the configuration has no SMX_SENSOR_EGO_CENTRIC (no frame is kept)");
+  const bool traj = action_space == SMX_ACTION_SPACE_TRAJECTORY, pose = action_space == SMX_ACTION_SPACE_TARGET_POSE;
+  const bool timed = action_space == SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME;
+  if (!traj && !pose && !timed)
+    return fail(h, SMX_ERR_INVALID, "smx_actions_to_world: only Trajectory, TargetPose and TrajectoryWithTime actions have a frame");
+  if (action_space != c.action_space) return fail(h, SMX_ERR_INVALID, "smx_actions_to_world: action_space is not cfg.action_space");
+  if (!in_dev || !out_dev || in_dev == out_dev || (!pose && !counts_dev))
+    return fail(h, SMX_ERR_INVALID, "smx_actions_to_world: null action buffer or counts, or the output is the input");
+  if (timed && max_points < 2) return fail(h, SMX_ERR_INVALID, "smx_actions_to_world: max_points < 2");
+  const uint64_t total = (uint64_t)c.num_envs * c.num_vehicles;
+  if (!out || !out->ego_frame || !out->ec_flags || out->dtype[SMX_OUT_EGO_FRAME] != SMX_DT_F64 ||
+      out->dtype[SMX_OUT_EC_FLAGS] != SMX_DT_U8 || out->count[SMX_OUT_EGO_FRAME] < 4 * total || out->count[SMX_OUT_EC_FLAGS] < total)
+    return fail(h, SMX_ERR_INVALID, "smx_actions_to_world: out.ego_frame / out.ec_flags missing, short or mistyped");
+  const int cols = traj ? SMX_TRAJ_COLS : pose ? 1 : max_points;
+  const unsigned blocks = smx_blocks((size_t)total * cols);
+  hipStream_t s = (hipStream_t)hip_stream;
+#define SMX_A2W(SPACE)                                                                                                  \
+  hipLaunchKernelGGL(k_actions_to_world<SPACE>, dim3(blocks), dim3(SMX_BLOCK), 0, s, in_dev, counts_dev, out_dev,        \
+                     (const double*)out->ego_frame, (const uint8_t*)out->ec_flags, (size_t)total, (int)c.num_vehicles, \
+                     (int)c.num_social, cols)
+  if (traj) SMX_A2W(SMX_ACTION_SPACE_TRAJECTORY);
+  else if (pose) SMX_A2W(SMX_ACTION_SPACE_TARGET_POSE);
+  else SMX_A2W(SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME);
+#undef SMX_A2W
+  SMX_HIP(hipGetLastError());
+  return SMX_OK;
 }
 
 extern "C" int smx_sync(smx_handle h, void* hip_stream) {

@@ -18,6 +18,9 @@
 #define SMX_WPT_MAX_PATHS 8  // dense rows per vehicle (wp_paths) the staged form handles
 #define SMX_OGM_WAVES 4
 #define SMX_TTC_TEAM 16  // lanes of a wavefront that share one agent in k_lane_ttc
+// ... and in k_ego_frame: a team's access to a float64 row is one 128-byte line; the shortest rows (ten neighbours: 30
+// float64, one path of 20 waypoints: 60) still fill it, and four agents' rows share a wavefront
+#define SMX_EC_TEAM 16
 // SMX_LAUNCH_AUTO: the LARGE launch form above this many vehicles.  Measured crossover (round 2, C4's shape:
 // 8 192 vehicles 0.165 / 0.216 ms small / large, 32 768: 0.461 / 0.303, 65 536: 0.886 / 0.505; C3 at 32 768:
 // 0.514 / 0.504; C2 at 8 192: 0.133 / 0.187).  At 16 384 the two cross: every agent alive 0.258 / 0.226, over
@@ -132,6 +135,9 @@ struct TickPlan {
   bool lane_ttc;
   unsigned ttc_blocks, ttc_first_blocks;
   size_t ttc_lds;  // per workgroup: SMX_BLOCK / SMX_TTC_TEAM agents' waypoints (x, y, arclength, lane id) and per-path minima
+  // k_ego_frame (SMX_SENSOR_EGO_CENTRIC): the same two sites, after k_lane_ttc (both only read the world rows)
+  bool ego_centric;
+  unsigned ec_blocks, ec_first_blocks;
   bool tail_builds_list;  // k_tail builds the next tick's alive list
   bool tail_grids;        // ... and the new vehicles' grid tiles
   bool reset_pass, lidar_first, first_walks_new;
@@ -287,6 +293,12 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
     p.ttc_blocks = smx_blocks(total, apb);
     p.ttc_first_blocks = p.reset_pass ? p.obs_blocks * (unsigned)(SMX_BLOCK / apb) : 0;  // an env group holds up to SMX_BLOCK vehicles
     p.ttc_lds = apb * smx_ttc_lds_per_agent(c.wp_paths, c.wp_len);
+  }
+  p.ego_centric = (c.sensors & SMX_SENSOR_EGO_CENTRIC) != 0;
+  if (p.ego_centric) {
+    const size_t apb = SMX_BLOCK / SMX_EC_TEAM;
+    p.ec_blocks = smx_blocks(total, apb);
+    p.ec_first_blocks = p.reset_pass ? p.obs_blocks * (unsigned)(SMX_BLOCK / apb) : 0;
   }
   return p;
 }

@@ -77,6 +77,10 @@ class SimConfig:
     # lane_ttc (custom_observations.py:148-280) of every agent on the device: out["lane_ttc"], out["lane_ttc_flags"]
     # (include/smx.h SMX_SENSOR_LANE_TTC); needs waypoints and neighbors
     lane_ttc: bool = False
+    # the ego-centric adapters (smarts/core/utils/adapters/ego_centric_adapters.py) on the device: out["ego_frame"],
+    # out["ec_flags"], out["ec_ego_f32"] and an out["ec_*"] twin of every position / heading row whose sensor is on
+    # (include/smx.h SMX_SENSOR_EGO_CENTRIC); actions_to_world turns ego-frame actions back
+    ego_centric: bool = False
 
     def sensors_mask(self) -> int:
         m = 0
@@ -96,6 +100,8 @@ class SimConfig:
             m |= nat.SENSOR_ROAD_WAYPOINTS
         if self.lane_ttc:
             m |= nat.SENSOR_LANE_TTC
+        if self.ego_centric:
+            m |= nat.SENSOR_EGO_CENTRIC
         return m
 
     def done_mask(self) -> int:
@@ -377,6 +383,13 @@ class BatchedSim:
             R = ray_count(cfg.lidar)
             o["lidar_hit"] = z((E, N, R), torch.uint8)
             o["lidar_point"] = z((E, N, R, 3), torch.float64)
+        if cfg.ego_centric:
+            o["ego_frame"] = z((E, N, 4), torch.float64)
+            o["ec_flags"] = z((E, N), torch.uint8)
+            o["ec_ego_f32"] = z((E, N, nat.EGO_F32_COUNT), torch.float32)
+            for name in ("wp_pos", "wp_heading", "nb_pos", "nb_heading", "lidar_point", "rw_pos", "rw_heading"):
+                if name in o:  # a twin of every position / heading row whose sensor is on
+                    o["ec_" + name] = torch.zeros_like(o[name])
         # learner-facing block (reward, done) as float32, two buffers used on alternate ticks so that
         # one can be in flight in a collective while the next tick writes the other
         self._learner = [z((2, E, N), torch.float32), z((2, E, N), torch.float32)]
@@ -392,8 +405,8 @@ class BatchedSim:
             o["final_events"] = z((E, N, nat.EV_COUNT), torch.uint8)
             o["final_dist"] = z((E, N), torch.float64)
         so = nat.SmxOutputs()
-        for name in nat.OUTPUT_FIELDS:
-            nat.bind_buffer(so, nat.OUTPUT_FIELDS, name, o.get(name))
+        for name in nat.OUTPUT_BUFFERS:
+            nat.bind_buffer(so, nat.OUTPUT_BUFFERS, name, o.get(name))
         self._out = so
         self._stream = None
         self._was_reset = False
@@ -558,13 +571,49 @@ class BatchedSim:
         """The learner block the NEXT ``step`` will write (see ``RewardDoneGather.release``)."""
         return self._learner[self._learner_k ^ 1]
 
-    def step_trajectory(self, trajectories: torch.Tensor, counts: torch.Tensor) -> Dict[str, torch.Tensor]:
+    def actions_to_world(self, space: str, actions: torch.Tensor, counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Ego-frame actions -> world-frame actions on the device (``smx_actions_to_world``; the action half of the
+        reference's ``get_egocentric_adapters``): ``actions`` in the layout ``step_trajectory`` / ``step_target_pose``
+        / ``step_trajectory_with_time`` take, given in the frame of each agent's last observation
+        (``out["ego_frame"]``).  Returns a new tensor of the same layout; agents without an observation yet
+        (``out["ec_flags"] == 0``), without an action and social slots are copied through."""
+        if not self.cfg.ego_centric:
+            raise ValueError("actions_to_world needs SimConfig(ego_centric=True)")
+        if space not in ("Trajectory", "TargetPose", "TrajectoryWithTime"):
+            raise ValueError(f"{space} actions hold no position or heading: they are the same in either frame")
+        if space != self.cfg.action_space:
+            raise ValueError(f"actions_to_world({space!r}) on a {self.cfg.action_space} batch")
+        actions = actions.to(device=self.device, dtype=torch.float64).contiguous()
+        want = {"Trajectory": (self.E, self.N, 4, nat.TRAJ_COLS), "TargetPose": (self.E, self.N, 4),
+                "TrajectoryWithTime": (self.E, self.N, 5) + tuple(actions.shape[3:4])}[space]
+        if tuple(actions.shape) != want or (space == "TrajectoryWithTime" and (actions.ndim != 4 or actions.shape[3] < 2)):
+            raise ValueError(f"{space} actions must have shape {want}, got {tuple(actions.shape)}")
+        counts_ptr = None
+        if space != "TargetPose":
+            if counts is None:
+                raise ValueError(f"{space} actions come with counts")
+            counts = counts.to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(counts.shape) != (self.E, self.N):
+                raise ValueError(f"counts must have shape {(self.E, self.N)}, got {tuple(counts.shape)}")
+            counts_ptr = counts.data_ptr()
+        world = torch.empty_like(actions)
+        rc = self.lib.smx_actions_to_world(self.handle, nat.ACTION_SPACES[space], actions.data_ptr(), counts_ptr,
+                                           int(actions.shape[3]) if space == "TrajectoryWithTime" else 0, world.data_ptr(),
+                                           C.byref(self._out), self._stream_ptr())
+        nat.check(self.lib, self.handle, rc, "smx_actions_to_world")
+        return world
+
+    def step_trajectory(self, trajectories: torch.Tensor, counts: torch.Tensor,
+                        ego_centric: bool = False) -> Dict[str, torch.Tensor]:
         """One tick in ActionSpaceType.Trajectory: ``trajectories`` float64 [E, N, 4, 11] in the packed
-        form of include/smx.h (``pack_trajectory``), ``counts`` int32 [E, N] (0 = no action)."""
+        form of include/smx.h (``pack_trajectory``), ``counts`` int32 [E, N] (0 = no action).  ``ego_centric``: the
+        trajectories are in the frame of each agent's last observation (``actions_to_world`` first)."""
         if not self._was_reset:
             raise RuntimeError("step() before reset()")
         if self.cfg.action_space != "Trajectory":
             raise ValueError("step_trajectory needs SimConfig(action_space='Trajectory')")
+        if ego_centric:
+            trajectories = self.actions_to_world("Trajectory", trajectories, counts)
         trajectories = trajectories.to(device=self.device, dtype=torch.float64).contiguous()
         counts = counts.to(device=self.device, dtype=torch.int32).contiguous()
         assert trajectories.shape == (self.E, self.N, 4, nat.TRAJ_COLS) and counts.shape == (self.E, self.N)
@@ -576,13 +625,16 @@ class BatchedSim:
         nat.check(self.lib, self.handle, rc, "smx_step_trajectory")
         return self.out
 
-    def step_target_pose(self, targets: torch.Tensor) -> Dict[str, torch.Tensor]:
+    def step_target_pose(self, targets: torch.Tensor, ego_centric: bool = False) -> Dict[str, torch.Tensor]:
         """One tick in ActionSpaceType.TargetPose: ``targets`` float64 [E, N, 4] = x, y, heading, seconds into the
-        future at which the pose is wanted; NaN in x = no action this tick (include/smx.h)."""
+        future at which the pose is wanted; NaN in x = no action this tick (include/smx.h).  ``ego_centric``: the
+        poses are in the frame of each agent's last observation (``actions_to_world`` first)."""
         if not self._was_reset:
             raise RuntimeError("step() before reset()")
         if self.cfg.action_space != "TargetPose":
             raise ValueError("step_target_pose needs SimConfig(action_space='TargetPose')")
+        if ego_centric:
+            targets = self.actions_to_world("TargetPose", targets)
         targets = targets.to(device=self.device, dtype=torch.float64).contiguous()
         if tuple(targets.shape) != (self.E, self.N, 4):
             raise ValueError(f"TargetPose actions must have shape {(self.E, self.N, 4)}, got {tuple(targets.shape)}")
@@ -594,14 +646,18 @@ class BatchedSim:
         nat.check(self.lib, self.handle, rc, "smx_step_target_pose")
         return self.out
 
-    def step_trajectory_with_time(self, trajectories: torch.Tensor, counts: torch.Tensor) -> Dict[str, torch.Tensor]:
+    def step_trajectory_with_time(self, trajectories: torch.Tensor, counts: torch.Tensor,
+                                  ego_centric: bool = False) -> Dict[str, torch.Tensor]:
         """One tick in ActionSpaceType.TrajectoryWithTime: ``trajectories`` float64 [E, N, 5, T] with rows time, x,
         y, heading, speed, ``counts`` int32 [E, N] = points given (0 = no action).  A trajectory the reference
-        raises on moves nothing and is reported by the next ``sync()``."""
+        raises on moves nothing and is reported by the next ``sync()``.  ``ego_centric``: rows x, y and heading are
+        in the frame of each agent's last observation (``actions_to_world`` first)."""
         if not self._was_reset:
             raise RuntimeError("step() before reset()")
         if self.cfg.action_space != "TrajectoryWithTime":
             raise ValueError("step_trajectory_with_time needs SimConfig(action_space='TrajectoryWithTime')")
+        if ego_centric:
+            trajectories = self.actions_to_world("TrajectoryWithTime", trajectories, counts)
         trajectories = trajectories.to(device=self.device, dtype=torch.float64).contiguous()
         counts = counts.to(device=self.device, dtype=torch.int32).contiguous()
         if (trajectories.ndim != 4 or tuple(trajectories.shape[:3]) != (self.E, self.N, 5) or trajectories.shape[3] < 2

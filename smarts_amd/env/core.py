@@ -132,7 +132,11 @@ class BatchCore:
     def __init__(self, scenario_dir: str, agent_specs: Dict[str, AgentSpec], num_envs: int, dt: float, seed: int,
                  auto_reset: bool, device: str = "cuda:0", waypoint_window: Optional[Tuple[int, int]] = (4, 20),
                  num_social: int = 0, vias: Optional[Dict[str, Sequence]] = None, social_model: str = "constant",
-                 missions: Optional[Dict[str, Any]] = None, spawns: str = "reference", shuffle_scenarios: bool = True):
+                 missions: Optional[Dict[str, Any]] = None, spawns: str = "reference", shuffle_scenarios: bool = True,
+                 ego_centric: bool = False):
+        """``ego_centric``: the dense rows carry their ego-frame twins (``SimConfig(ego_centric=True)``) and the
+        agents' Trajectory / TargetPose / TrajectoryWithTime actions are given in the frame of their last
+        observation: ``step_actions`` converts them on the device (the reference's ``get_egocentric_adapters``)."""
         from ..engine import BatchedSim, make_spawns
         from ..scenario_build import load_compiled_map
 
@@ -152,6 +156,7 @@ class BatchCore:
                                              self.agent_ids)
         self.num_social = num_social
         self.cfg.social_model = social_model
+        self.ego_centric = self.cfg.ego_centric = bool(ego_centric)
         # Start poses.  "reference": what hiway-v0 gives agents of a scenario without missions.pkl — a random endless
         # mission each, from CPython's random stream (missions.reference_spawn_table); "synthetic": the benchmark's
         # spawn table (PCG64(seed + env), 8 m apart on a lane, at the speed limit).  Scripted social
@@ -259,7 +264,7 @@ class BatchCore:
         self._check_alive()
         if not self._was_reset:
             raise SMARTSNotSetupError("Must call reset() or setup() before stepping.")
-        return self.sim.step_trajectory(torch.from_numpy(packed), torch.from_numpy(counts))
+        return self.sim.step_trajectory(torch.from_numpy(packed), torch.from_numpy(counts), ego_centric=self.ego_centric)
 
     def _step_kinematic(self, per_env_actions: Sequence[Dict[str, Any]]):
         """TargetPose: ``[x, y, heading, seconds into the future]`` per agent (motion_planner_provider.py:65-78);
@@ -285,7 +290,7 @@ class BatchCore:
                 if a.shape != (4,):
                     raise ValueError(f"TargetPose expects [x, y, heading, seconds_into_future], got shape {a.shape}")
                 targets[e, i] = a
-            return self.sim.step_target_pose(torch.from_numpy(targets))
+            return self.sim.step_target_pose(torch.from_numpy(targets), ego_centric=self.ego_centric)
         for a in adapted.values():
             if a.ndim != 2 or a.shape[0] != 5:
                 raise ValueError(f"TrajectoryWithTime expects a 5 x T array (time, x, y, heading, speed), got shape {a.shape}")
@@ -295,7 +300,7 @@ class BatchCore:
         counts = np.zeros((self.E, slots), dtype=np.int32)  # 0 = no action
         for (e, i), a in adapted.items():
             trajs[e, i, :, :a.shape[1]], counts[e, i] = a, a.shape[1]
-        return self.sim.step_trajectory_with_time(torch.from_numpy(trajs), torch.from_numpy(counts))
+        return self.sim.step_trajectory_with_time(torch.from_numpy(trajs), torch.from_numpy(counts), ego_centric=self.ego_centric)
 
     def encode_actions(self, per_env_actions: Sequence[Dict[str, Any]]) -> np.ndarray:
         space = self.interface.action

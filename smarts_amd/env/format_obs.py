@@ -174,13 +174,40 @@ class FormatObs:
 
     # -------------------------------------------------------------- dense rows -> StdObs, no objects
     @staticmethod
-    def from_rows(rows: Dict[str, np.ndarray], env: int, slot: int) -> StdObs:
+    def from_rows(rows: Dict[str, np.ndarray], env: int, slot: int, ego_centric: bool = False) -> StdObs:
         """Slice ``StdObs`` of agent (env, slot) straight out of host copies of the dense device
         rows.  The ttc block comes from ``rows["lane_ttc"]`` / ``rows["lane_ttc_flags"]`` where the rows hold them
         (``SimConfig(lane_ttc=True)``, or ``lane_ttc_rows`` on the host) and the agent's flags say the reference's
         ``_std_ttc`` would not be ``None``; without those keys it stays ``None`` (``observation`` builds it from
-        objects)."""
+        objects).  ``ego_centric``: the position, heading and linear velocity / acceleration / jerk fields come from the
+        ``ec_*`` rows (``SimConfig(ego_centric=True)``, or ``ego_centric_rows`` on the host) — ``StdObs`` of the
+        observation ``ego_centric_observation_adapter`` returns; everything else is frame-independent and read from
+        the world rows (the ttc block included: ``lane_ttc`` of the world rows)."""
         E = nat.EGO
+        if ego_centric:
+            if "ec_flags" not in rows or not int(rows["ec_flags"][env, slot]) & nat.EC_VALID:
+                raise ValueError(f"agent ({env}, {slot}) has no ego-centric rows (ec_flags)")
+            # (this agent's slices only: the masked copies below are then of one agent's size)
+            rows = {k: v[env:env + 1, slot:slot + 1] for k, v in rows.items() if getattr(v, "ndim", 0) >= 2}
+            env = slot = 0
+            rows["ego_f32"], rows["ego_pos"] = rows["ec_ego_f32"], np.zeros_like(rows["ego_pos"])
+            # (entries beyond the counts of an ec_* row are not written: they read as the zero padding of StdObs)
+            if "ec_nb_pos" in rows:
+                keep = np.arange(rows["nb_heading"].shape[2]) < int(rows["nb_count"][env, slot])
+                for k in ("nb_pos", "nb_heading"):
+                    a = np.zeros_like(rows[k])
+                    a[env, slot] = np.where(keep.reshape(keep.shape + (1,) * (rows[k].ndim - 3)), rows["ec_" + k][env, slot], 0)
+                    rows[k] = a
+            if "ec_wp_pos" in rows:
+                counts = rows["wp_count"][env, slot]
+                P, W = rows["wp_heading"].shape[2:4]
+                keep = (np.arange(P)[:, None] < int(counts[0])) & (np.arange(W)[None, :] < counts[1:, None].astype(np.int64))
+                for k in ("wp_pos", "wp_heading"):
+                    a = np.zeros_like(rows[k])
+                    a[env, slot] = np.where(keep.reshape(keep.shape + (1,) * (rows[k].ndim - 4)), rows["ec_" + k][env, slot], 0)
+                    rows[k] = a
+            if "ec_lidar_point" in rows:
+                rows["lidar_point"] = rows["ec_lidar_point"]
         f = rows["ego_f32"][env, slot]
         v3 = lambda k: np.array(f[E[k]:E[k] + 3], dtype=np.float32)  # noqa: E731
         ego = {
