@@ -268,6 +268,349 @@ __device__ __forceinline__ VehState load_vehicle(const KernelArgs& a, size_t gid
 // lane 0 through shuffles and lane 0 runs the control law and the 24 physics substeps.
 // =================================================================================
 
+// ---- the steps every launch form of the controller shares (k_control, k_control_paths / k_control_law,
+// k_control_fast / k_control_listed, k_control_kinematic), each written once
+
+// Scripted social vehicle (lane follower: no controller, no dynamics), on state words its caller has loaded:
+// lane, offset and crossed flag (SMX_S_MCL_X / MCL_Y / SPD_INT), SMX_S_THROTTLE and the pose's x / y.
+__device__ __forceinline__ void social_vehicle_step(const KernelArgs& a, size_t gid, size_t total, double mcl_x, double mcl_y,
+                                                    double spd_int, double throttle, double prev_x, double prev_y) {
+  const smx_config& c = a.cfg;
+  int lane = (int)mcl_x, crossed = (int)spd_int;
+  double offset = mcl_y, speed, x, y, heading;
+  SF(SMX_S_PREV_X) = prev_x;
+  SF(SMX_S_PREV_Y) = prev_y;
+  // SMX_SOCIAL_IDM: k_social decided this tick's speed from the state at the start of the tick
+  const double cmd = c.social_model == SMX_SOCIAL_IDM ? throttle : -1.0;
+  social_step(a.map, (int)(gid % c.num_vehicles), c.social_speed_factor, c.dt, lane, offset, crossed, speed, cmd);
+  social_pose(a.map, lane, offset, x, y, heading);
+  SF(SMX_S_X) = x;
+  SF(SMX_S_Y) = y;
+  SF(SMX_S_HEADING) = heading;
+  SF(SMX_S_U) = speed;
+  SF(SMX_S_MCL_X) = (double)lane;
+  SF(SMX_S_MCL_Y) = offset;
+  SF(SMX_S_SPD_INT) = (double)crossed;
+}
+
+// (loads that need the vehicle number only: k_control_fast issues them before it has looked at the flags)
+__device__ __forceinline__ CtrlState load_ctrl_state(const KernelArgs& a, size_t gid, size_t total, int flags) {
+  CtrlState cs;
+  cs.lat_int = SF(SMX_S_LAT_INT);
+  cs.spd_int = SF(SMX_S_SPD_INT);
+  cs.steer = SF(SMX_S_STEER);
+  cs.throttle = SF(SMX_S_THROTTLE);
+  cs.spd_err = SF(SMX_S_SPD_ERR);
+  cs.mcl_x = SF(SMX_S_MCL_X);
+  cs.mcl_y = SF(SMX_S_MCL_Y);
+  cs.mcl_set = (flags & SMX_F_MCL_SET) != 0;
+  return cs;
+}
+
+// The state rows after vehicle_step.
+__device__ __forceinline__ void store_vehicle_state(const KernelArgs& a, size_t gid, size_t total, const VehState& s,
+                                                    const CtrlState& cs, int flags) {
+  SF(SMX_S_X) = s.x;
+  SF(SMX_S_Y) = s.y;
+  SF(SMX_S_HEADING) = s.heading;
+  SF(SMX_S_U) = s.u;
+  SF(SMX_S_V) = s.v;
+  SF(SMX_S_R) = s.r;
+  SF(SMX_S_DELTA) = s.delta;
+  SF(SMX_S_LAT_INT) = cs.lat_int;
+  SF(SMX_S_SPD_INT) = cs.spd_int;
+  SF(SMX_S_STEER) = cs.steer;
+  SF(SMX_S_THROTTLE) = cs.throttle;
+  SF(SMX_S_SPD_ERR) = cs.spd_err;
+  SF(SMX_S_MCL_X) = cs.mcl_x;
+  SF(SMX_S_MCL_Y) = cs.mcl_y;
+  a.st.flags[gid] = cs.mcl_set ? (flags | SMX_F_MCL_SET) : (flags & ~SMX_F_MCL_SET);
+}
+
+// Controllers.perform_action's decoding of a Lane / LaneWithContinuousSpeed action (controllers/__init__.py:113-144),
+// on action words its caller has loaded (`action` for Lane, act0 / act1 for the other).  Without an action the other
+// fields mean nothing and are not read.  (The Lane fields are selects on the code, outside any branch, so that
+// they can sink below k_control's path search: behind the has-action branch k_control<0, true> took 231 registers
+// for 225; the other space's are left unset without an action: zero-filled, k_control_law<3> took 188 for 186 —
+// profiles/r09_controller_shared_steps.txt.)
+struct LaneAction {
+  bool has_action;
+  double target_speed, hg, lg;
+  int lane_change;
+};
+template <int SPACE>
+__device__ __forceinline__ LaneAction decode_lane_action(const KernelArgs& a, int action, float act0, float act1) {
+  LaneAction la;
+  la.has_action = false;
+  if (SPACE == SMX_ACTION_SPACE_LANE) {
+    // the reference looks the action string up in a dict and raises (:137-144); a code that names no action is
+    // reported at the next smx_sync and moves nothing
+    const bool bad_code = action < SMX_ACTION_NONE || action > SMX_ACTION_CHANGE_LANE_RIGHT;
+    if (bad_code) atomicOr(a.status, SMX_DEVICE_BAD_LANE_ACTION);
+    la.has_action = !bad_code && action >= 0;
+    // :125-144
+    la.target_speed = action == SMX_ACTION_KEEP_LANE ? 15.0 : (action == SMX_ACTION_SLOW_DOWN ? 0.0 : 12.5);
+    la.lane_change = action == SMX_ACTION_CHANGE_LANE_LEFT ? 1 : (action == SMX_ACTION_CHANGE_LANE_RIGHT ? -1 : 0);
+    la.hg = la.target_speed > 0.0 ? a.heading_gain_pos : 0.01;
+    la.lg = la.target_speed > 0.0 ? a.lateral_gain_pos : 0.36;
+  } else if (!(act0 != act0)) {  // NaN = no action
+    // :113-124: (target_speed, lane_change)
+    la.has_action = true;
+    la.target_speed = (double)act0;
+    la.lane_change = lane_change_of_action(act1);
+    lateral_gains_for_speed(la.target_speed, la.hg, la.lg);
+  }
+  return la;
+}
+template <int SPACE>
+__device__ __forceinline__ LaneAction load_lane_action(const KernelArgs& a, size_t gid) {
+  if (SPACE == SMX_ACTION_SPACE_LANE) return decode_lane_action<SPACE>(a, a.actions[gid], 0.f, 0.f);
+  return decode_lane_action<SPACE>(a, SMX_ACTION_NONE, a.actions_f32[gid * 3 + 0], a.actions_f32[gid * 3 + 1]);
+}
+
+// No action this tick: wheel torques do not persist, the steer motor target does.
+__device__ __forceinline__ ControlOut idle_command(const CtrlState& cs) {
+  ControlOut co;
+  co.throttle = 0.0;
+  co.brake = 0.0;
+  co.steering = cs.steer;
+  return co;
+}
+// The reference asserts "no waypoints found"; keep the last command.
+__device__ __forceinline__ ControlOut last_command(const CtrlState& cs) {
+  ControlOut co;
+  co.throttle = cs.throttle;
+  co.brake = 0.0;
+  co.steering = cs.steer;
+  return co;
+}
+
+// The Continuous / ActuatorDynamic command (controllers/__init__.py:94-99).
+template <int SPACE>
+__device__ __forceinline__ ControlOut direct_command(float act0, float act1, float act2, CtrlState& cs, double dt) {
+  ControlOut co;
+  co.throttle = clip_ref((double)act0, 0.0, 1.0);
+  co.brake = clip_ref((double)act1, 0.0, 1.0);
+  if (SPACE == SMX_ACTION_SPACE_CONTINUOUS) {
+    co.steering = clip_ref((double)act2, -1.0, 1.0);
+  } else {
+    // ActuatorDynamicController.perform_action (actuator_dynamic_controller.py:47-80): the third
+    // component is a steering *rate*; the held angle is the controller state
+    const double change = clip_ref((double)act2, -1.0, 1.0);
+    co.steering = clip_ref((1.0 - 0.001) * cs.steer + change * dt, -1.0, 1.0);
+  }
+  cs.steer = co.steering;  // last_steering_angle / the persisting steer target
+  return co;
+}
+
+// ---- team helpers: SMX_WP_LANES lanes per vehicle
+__device__ __forceinline__ int team_or(int v) {
+#pragma unroll
+  for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) v |= __shfl_xor(v, msk, SMX_WP_LANES);
+  return v;
+}
+
+// nearest path over the team: smallest distance, then smallest number
+__device__ __forceinline__ void team_nearest(double& my_d, int& my_idx) {
+#pragma unroll
+  for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) {
+    const double od = __shfl_xor(my_d, msk, SMX_WP_LANES);
+    const int oi = __shfl_xor(my_idx, msk, SMX_WP_LANES);
+    if (od < my_d || (od == my_d && oi < my_idx)) {
+      my_d = od;
+      my_idx = oi;
+    }
+  }
+}
+
+// wp_paths[clip(current_lane + lane_change)] (lane_following_controller.py:100-103)
+__device__ __forceinline__ int wanted_path(int nearest, int lane_change, int n_paths) {
+  const int want = nearest + lane_change;
+  return want < 0 ? 0 : (want > n_paths - 1 ? n_paths - 1 : want);
+}
+
+// The team's search of the candidate paths (find_current_lane, lane_following_controller.py:367-374).
+// Paths are numbered in the reference's order: seed lanes by index, branches depth-first.
+// Team lane p walks seed lanes p, p + 4, ... on its own (no lane re-walks another lane's
+// paths) and measures the first waypoint of every path it meets; counts are exchanged by shuffles
+// to turn (lane, branch) into the global number.  FUSED: the first branch of the lane's first seed
+// lane is synthesised in full through `put` while it is walked (n_first waypoints).
+struct TeamSearch {
+  int n_paths;      // of the whole team
+  double my_d;      // this lane's nearest first waypoint and its path's number (team_nearest: the team's)
+  int my_idx;
+  int goff0, cnt0;  // the paths of this lane's first seed lane: number of the first one, how many
+  int n_first;
+};
+template <bool FUSED, class Put>
+__device__ __forceinline__ TeamSearch team_path_search(const MapDev& m, const PathSeeds& seed, int p0, double px, double py,
+                                                       int* knots, Put&& put) {
+  TeamSearch ts;
+  ts.n_paths = 0;
+  ts.my_d = SMX_INF;
+  ts.my_idx = 0x7fffffff;
+  ts.goff0 = ts.cnt0 = ts.n_first = 0;
+  if (seed.road < 0) return ts;
+  for (int r4 = 0; r4 < seed.n_lanes; r4 += SMX_WP_LANES) {  // uniform within a team
+    const int li = r4 + p0;
+    int cnt = 0, bj = 0x7fffffff;
+    double bd = SMX_INF;
+    if (li < seed.n_lanes) {
+      const int start = seed_start(m, seed, li, px, py);
+      if (start >= 0) {
+        BranchState bs;
+        bs.reset();
+        do {
+          double fx = 0.0, fy = 0.0;
+          if (FUSED && r4 == 0 && cnt == 0) {
+            ts.n_first = equally_spaced_path(m, seed.f, bs, start, SMX_CTRL_WPS - 1, px, py, knots, SMX_BLOCK,
+                                             SMX_CTRL_WPS, [&](int i, const WaypointOut& w) {
+                                               put(i, w);
+                                               if (i == 0) {
+                                                 fx = w.x;
+                                                 fy = w.y;
+                                               }
+                                             });
+          } else {
+            equally_spaced_path(m, seed.f, bs, start, SMX_CTRL_WPS - 1, px, py, knots, SMX_BLOCK, 1,
+                                [&](int, const WaypointOut& w) {
+                                  fx = w.x;
+                                  fy = w.y;
+                                });
+          }
+          const double ex = fx - px, ey = fy - py;
+          const double d = sqrt(ex * ex + ey * ey);
+          if (d < bd) {  // strict: the lowest-numbered path wins ties (np.argmin)
+            bd = d;
+            bj = cnt;
+          }
+          ++cnt;
+        } while (bs.advance());
+      }
+    }
+    // exclusive prefix of the counts over the team
+    int incl = cnt;
+    {
+      int t = __shfl_up(incl, 1, SMX_WP_LANES);
+      if (p0 >= 1) incl += t;
+      t = __shfl_up(incl, 2, SMX_WP_LANES);
+      if (p0 >= 2) incl += t;
+    }
+    const int round_total = __shfl(incl, SMX_WP_LANES - 1, SMX_WP_LANES);
+    const int g = ts.n_paths + incl - cnt;
+    if (r4 == 0) {
+      ts.goff0 = g;
+      ts.cnt0 = cnt;
+    }
+    if (bj != 0x7fffffff && (bd < ts.my_d || (bd == ts.my_d && g + bj < ts.my_idx))) {
+      ts.my_d = bd;
+      ts.my_idx = g + bj;
+    }
+    ts.n_paths += round_total;
+  }
+  return ts;
+}
+
+// Branch `branch` of seed lane `li`, walked to again and synthesised through `put` (rare in k_control: branching
+// inside 16 hops).  Returns its waypoints.
+template <class Put>
+__device__ __forceinline__ int rewalk_branch(const MapDev& m, const PathSeeds& seed, int li, double px, double py, int branch,
+                                             int* knots, Put&& put) {
+  const int start = seed_start(m, seed, li, px, py);
+  BranchState bs;
+  bs.reset();
+  int j = 0;
+  do {
+    if (j == branch) return equally_spaced_path(m, seed.f, bs, start, SMX_CTRL_WPS - 1, px, py, knots, SMX_BLOCK, SMX_CTRL_WPS, put);
+    equally_spaced_path(m, seed.f, bs, start, SMX_CTRL_WPS - 1, px, py, knots, SMX_BLOCK, 0, [&](int, const WaypointOut&) {});
+    ++j;
+  } while (bs.advance());
+  return 0;
+}
+
+// ---- reuse of the knot lists the waypoints sensor walked last tick (control_paths_for explains it)
+
+// Is the list walked for this start lanepoint and route filter, without a branching, and not empty?
+__device__ __forceinline__ bool knot_list_reusable(int key0, int key1, int key2, int cnt, int n32, int start, const RouteFilter& f) {
+  return key0 == start && key1 == (f.n > 0 ? f.road[0] : -1) && key2 == (f.n > 1 ? f.road[1] : -1) && cnt == 1 && n32 > 0;
+}
+
+// Distance to the first waypoint of a seed lane's paths: the projection of the vehicle on the start lanepoint's
+// heading line (interpolate_knots at t = 0), the lanepoint itself on a path of one lanepoint.
+__device__ __forceinline__ double first_waypoint_distance(double rx, double ry, double rdx, double rdy, int n32, double px, double py) {
+  const double proj = (px - rx) * rdx + (py - ry) * rdy;
+  const double fx = n32 == 1 ? rx : rx + proj * rdx, fy = n32 == 1 ? ry : ry + proj * rdy;
+  const double ex = fx - px, ey = fy - py;
+  return sqrt(ex * ex + ey * ey);
+}
+
+// The controller's n16 waypoints of knot list `pth` (start record r0, nk16 knots, `last` the last knot when it is
+// not one of the list's): knots into registers (every load in flight together), their arclength in path order
+// (pass 1's additions), then the interpolation through `put`.  ONE_LANE is k_control_fast's form: the knot numbers
+// are loaded whatever nk16 is, and lane, width and speed limit of the waypoints (not the controller's business) are
+// left 0.
+template <bool ONE_LANE, class Put>
+__device__ __forceinline__ void ctrl_waypoints_from_knots(const KernelArgs& a, size_t total, size_t pth, const smx_lp_rec& r0,
+                                                          int nk16, int last, int n16, double px, double py, Put&& put) {
+  const MapDev& m = a.map;
+  const size_t paths = total * SMX_WP_LANES;
+  auto fetch = [&](int k) { return (k == nk16 - 1 && last >= 0) ? last : a.knots.idx[(size_t)(k + 1) * paths + pth]; };
+  constexpr int KP = SMX_WPT_PRELOAD;
+  double kx[KP], ky[KP], kh[KP], kw[KP], ks_[KP];
+  int kl[KP];
+  {
+    int kid[KP];
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+      if (ONE_LANE) {
+        const int id = a.knots.idx[(size_t)(k + 1) * paths + pth];  // (in range whatever nk16 is)
+        kid[k] = (k == nk16 - 1 && last >= 0) ? last : id;
+      } else {
+        kid[k] = k < nk16 ? fetch(k) : 0;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+      const bool have = k < nk16;
+      const smx_lp_rec* r = m.lp_rec + (have ? kid[k] : 0);
+      kx[k] = have ? r->x : 0.0;
+      ky[k] = have ? r->y : 0.0;
+      kh[k] = have ? r->heading : 0.0;
+      kl[k] = (have && !ONE_LANE) ? r->lane : 0;
+    }
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+      const bool ask = !ONE_LANE && k < nk16 && kl[k] != (k == 0 ? (int)r0.lane : kl[k > 0 ? k - 1 : 0]);
+      kw[k] = ask ? m.lane_width[kl[k]] : 0.0;
+      ks_[k] = ask ? m.lane_speed[kl[k]] : 0.0;
+    }
+  }
+  double D = 0.0;
+  {
+    const double proj = (px - r0.x) * r0.dirx + (py - r0.y) * r0.diry;
+    double lastx = r0.x + proj * r0.dirx, lasty = r0.y + proj * r0.diry;
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+      if (k < nk16) {
+        const double ex = kx[k] - lastx, ey = ky[k] - lasty;
+        D += sqrt(ex * ex + ey * ey);
+        lastx = kx[k];
+        lasty = ky[k];
+      }
+    }
+    for (int k = KP; k < nk16; ++k) {
+      const smx_lp_rec* r = m.lp_rec + fetch(k);
+      const double qx = r->x, qy = r->y;
+      const double ex = qx - lastx, ey = qy - lasty;
+      D += sqrt(ex * ex + ey * ey);
+      lastx = qx;
+      lasty = qy;
+    }
+  }
+  interpolate_knots_preloaded<KP>(m, r0, ONE_LANE ? 0.0 : m.lane_width[r0.lane], ONE_LANE ? 0.0 : m.lane_speed[r0.lane], nk16, n16, D,
+                                  px, py, SMX_CTRL_WPS, kx, ky, kh, kl, kw, ks_, fetch, put);
+}
+
 // One instantiation per action space: the Lane kernel does not carry the registers of the others.
 // waves_per_eu(2): at most 256 registers, so that two wavefronts share a SIMD on large batches.
 // LDS_PATH (small batches, lane-following spaces): the candidate path is written to LDS as it is
@@ -299,50 +642,24 @@ __global__ void __attribute__((amdgpu_waves_per_eu(2, 8))) __launch_bounds__(SMX
   if (gid >= total) return;  // whole teams leave together
   int flags = a.st.flags[gid];
   if (!(flags & SMX_F_ALIVE)) return;
-  if (flags & SMX_F_SOCIAL) {  // scripted lane follower: no controller, no dynamics
-    if (p0 != 0) return;
-    int lane = (int)SF(SMX_S_MCL_X), crossed = (int)SF(SMX_S_SPD_INT);
-    double offset = SF(SMX_S_MCL_Y), speed, x, y, heading;
-    SF(SMX_S_PREV_X) = SF(SMX_S_X);
-    SF(SMX_S_PREV_Y) = SF(SMX_S_Y);
-    // SMX_SOCIAL_IDM: k_social decided this tick's speed from the state at the start of the tick
-    const double cmd = c.social_model == SMX_SOCIAL_IDM ? SF(SMX_S_THROTTLE) : -1.0;
-    social_step(m, (int)(gid % c.num_vehicles), c.social_speed_factor, c.dt, lane, offset, crossed, speed, cmd);
-    social_pose(m, lane, offset, x, y, heading);
-    SF(SMX_S_X) = x;
-    SF(SMX_S_Y) = y;
-    SF(SMX_S_HEADING) = heading;
-    SF(SMX_S_U) = speed;
-    SF(SMX_S_MCL_X) = (double)lane;
-    SF(SMX_S_MCL_Y) = offset;
-    SF(SMX_S_SPD_INT) = (double)crossed;
+  if (flags & SMX_F_SOCIAL) {
+    if (p0 == 0)
+      social_vehicle_step(a, gid, total, SF(SMX_S_MCL_X), SF(SMX_S_MCL_Y), SF(SMX_S_SPD_INT), SF(SMX_S_THROTTLE), SF(SMX_S_X), SF(SMX_S_Y));
     return;
   }
   SMX_TSTAMP(tc0);
   VehState s = load_vehicle(a, gid, total);
-  CtrlState cs;
-  cs.lat_int = SF(SMX_S_LAT_INT);
-  cs.spd_int = SF(SMX_S_SPD_INT);
-  cs.steer = SF(SMX_S_STEER);
-  cs.throttle = SF(SMX_S_THROTTLE);
-  cs.spd_err = SF(SMX_S_SPD_ERR);
-  cs.mcl_x = SF(SMX_S_MCL_X);
-  cs.mcl_y = SF(SMX_S_MCL_Y);
-  cs.mcl_set = (flags & SMX_F_MCL_SET) != 0;
+  CtrlState cs = load_ctrl_state(a, gid, total, flags);
   // ---- Controllers.perform_action (controllers/__init__.py:61-152)
   constexpr int space = SPACE;
-  int action = SMX_ACTION_NONE;
+  constexpr bool lane_following =
+      space == SMX_ACTION_SPACE_LANE || space == SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED;
+  LaneAction la = LaneAction{};
   float act0 = 0.f, act1 = 0.f, act2 = 0.f;
   bool has_action;
-  if (space == SMX_ACTION_SPACE_LANE) {
-    action = a.actions[gid];
-    if (action < SMX_ACTION_NONE || action > SMX_ACTION_CHANGE_LANE_RIGHT) {
-      // the reference looks the action string up in a dict and raises (controllers/__init__.py:137-144); a code
-      // that names no action is reported at the next smx_sync and moves nothing
-      if (p0 == 0) atomicOr(a.status, SMX_DEVICE_BAD_LANE_ACTION);
-      action = SMX_ACTION_NONE;
-    }
-    has_action = action >= 0;
+  if (lane_following) {
+    la = load_lane_action<SPACE>(a, gid);
+    has_action = la.has_action;
   } else if (space == SMX_ACTION_SPACE_TRAJECTORY) {
     has_action = a.traj_n[gid] > 0;
   } else {
@@ -352,13 +669,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(2, 8))) __launch_bounds__(SMX
     has_action = !(act0 != act0);  // NaN = no action
   }
   int act_lane = 0;  // the team lane that runs the control law and the physics (uniform in the team)
-  ControlOut co;
-  // no action this tick: wheel torques do not persist, the steer motor target does
-  co.throttle = 0.0;
-  co.brake = 0.0;
-  co.steering = cs.steer;
-  const bool lane_following =
-      space == SMX_ACTION_SPACE_LANE || space == SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED;
+  ControlOut co = idle_command(cs);
   if (has_action && space == SMX_ACTION_SPACE_TRAJECTORY) {
     if (p0 == 0) {
       PackedTraj t;
@@ -367,150 +678,34 @@ __global__ void __attribute__((amdgpu_waves_per_eu(2, 8))) __launch_bounds__(SMX
       co = trajectory_tracking_pd(s, cs, c.dt, t);
     }
   } else if (has_action && !lane_following) {
-    if (space == SMX_ACTION_SPACE_CONTINUOUS) {
-      // :94-99
-      co.throttle = clip_ref((double)act0, 0.0, 1.0);
-      co.brake = clip_ref((double)act1, 0.0, 1.0);
-      co.steering = clip_ref((double)act2, -1.0, 1.0);
-    } else {
-      // ActuatorDynamicController.perform_action (actuator_dynamic_controller.py:47-80): the third
-      // component is a steering *rate*; the held angle is the controller state
-      const double change = clip_ref((double)act2, -1.0, 1.0);
-      co.throttle = clip_ref((double)act0, 0.0, 1.0);
-      co.brake = clip_ref((double)act1, 0.0, 1.0);
-      co.steering = clip_ref((1.0 - 0.001) * cs.steer + change * c.dt, -1.0, 1.0);
-    }
-    cs.steer = co.steering;  // last_steering_angle / the persisting steer target
+    co = direct_command<SPACE>(act0, act1, act2, cs, c.dt);
   }
   if (has_action && lane_following && !SMX_SKIP(a, 1)) {  // uniform within a team
-    double target_speed;
-    int lane_change;
-    double hg, lg;
-    if (space == SMX_ACTION_SPACE_LANE) {
-      // :125-144
-      target_speed = action == SMX_ACTION_KEEP_LANE ? 15.0 : (action == SMX_ACTION_SLOW_DOWN ? 0.0 : 12.5);
-      lane_change = action == SMX_ACTION_CHANGE_LANE_LEFT ? 1 : (action == SMX_ACTION_CHANGE_LANE_RIGHT ? -1 : 0);
-      hg = target_speed > 0.0 ? a.heading_gain_pos : 0.01;
-      lg = target_speed > 0.0 ? a.lateral_gain_pos : 0.36;
-    } else {
-      // :113-124: (target_speed, lane_change)
-      target_speed = (double)act0;
-      lane_change = lane_change_of_action(act1);
-      lateral_gains_for_speed(target_speed, hg, lg);
-    }
+    const double target_speed = la.target_speed, hg = la.hg, lg = la.lg;
+    const int lane_change = la.lane_change;
     const PathSeeds seed = load_seeds(a, gid, total);  // found by k_scan at this very pose
     const double px = s.x, py = s.y;
     CtrlPath path;
     path.n = 0;
 #pragma unroll
     for (int k = 0; k < SMX_CTRL_WPS; ++k) path.x[k] = path.y[k] = path.h[k] = 0.0;
-    // Paths are numbered in the reference's order: seed lanes by index, branches depth-first.
-    // Team lane p walks seed lanes p, p + 4, ... on its own (no lane re-walks another lane's
-    // paths); counts are exchanged by shuffles to turn (lane, branch) into the global number.
-    // The first branch of the lane's first seed lane is synthesised in full while it is walked.
-    int n_paths = 0;
-    double my_d = SMX_INF;
-    int my_idx = 0x7fffffff;
-    int goff0 = 0, cnt0 = 0;
     SMX_TSTAMP(tc1);
     SMX_TACC(15, tc0, tc1);
-    if (seed.road >= 0) {
-      for (int r4 = 0; r4 < seed.n_lanes; r4 += SMX_WP_LANES) {  // uniform within a team
-        const int li = r4 + p0;
-        int cnt = 0, bj = 0x7fffffff;
-        double bd = SMX_INF;
-        if (li < seed.n_lanes) {
-          const int start = seed_start(m, seed, li, px, py);
-          if (start >= 0) {
-            BranchState bs;
-            bs.reset();
-            do {
-              double fx = 0.0, fy = 0.0;
-              if (r4 == 0 && cnt == 0) {
-                path.n = equally_spaced_path(m, seed.f, bs, start, SMX_CTRL_WPS - 1, px, py, knots, SMX_BLOCK,
-                                             SMX_CTRL_WPS, [&](int i, const WaypointOut& w) {
-                                               path_put(path, i, w.x, w.y, w.heading);
-                                               if (i == 0) {
-                                                 fx = w.x;
-                                                 fy = w.y;
-                                               }
-                                             });
-              } else {
-                equally_spaced_path(m, seed.f, bs, start, SMX_CTRL_WPS - 1, px, py, knots, SMX_BLOCK, 1,
-                                    [&](int, const WaypointOut& w) {
-                                      fx = w.x;
-                                      fy = w.y;
-                                    });
-              }
-              const double ex = fx - px, ey = fy - py;
-              const double d = sqrt(ex * ex + ey * ey);
-              if (d < bd) {  // strict: the lowest-numbered path wins ties (np.argmin)
-                bd = d;
-                bj = cnt;
-              }
-              ++cnt;
-            } while (bs.advance());
-          }
-        }
-        // exclusive prefix of the counts over the team
-        int incl = cnt;
-        {
-          int t = __shfl_up(incl, 1, SMX_WP_LANES);
-          if (p0 >= 1) incl += t;
-          t = __shfl_up(incl, 2, SMX_WP_LANES);
-          if (p0 >= 2) incl += t;
-        }
-        const int round_total = __shfl(incl, SMX_WP_LANES - 1, SMX_WP_LANES);
-        const int g = n_paths + incl - cnt;
-        if (r4 == 0) {
-          goff0 = g;
-          cnt0 = cnt;
-        }
-        if (bj != 0x7fffffff && (bd < my_d || (bd == my_d && g + bj < my_idx))) {
-          my_d = bd;
-          my_idx = g + bj;
-        }
-        n_paths += round_total;
-      }
-    }
+    TeamSearch ts = team_path_search<true>(m, seed, p0, px, py, knots,
+                                           [&](int i, const WaypointOut& w) { path_put(path, i, w.x, w.y, w.heading); });
+    path.n = ts.n_first;
+    const int n_paths = ts.n_paths, goff0 = ts.goff0, cnt0 = ts.cnt0;
     SMX_TSTAMP(tc2);
     SMX_TACC(16, tc1, tc2);
-    // nearest path over the team: smallest distance, then smallest number
-#pragma unroll
-    for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) {
-      const double od = __shfl_xor(my_d, msk, SMX_WP_LANES);
-      const int oi = __shfl_xor(my_idx, msk, SMX_WP_LANES);
-      if (od < my_d || (od == my_d && oi < my_idx)) {
-        my_d = od;
-        my_idx = oi;
-      }
-    }
+    team_nearest(ts.my_d, ts.my_idx);
     if (n_paths > 0) {  // uniform within a team
-      int want = my_idx + lane_change;
-      want = want < 0 ? 0 : (want > n_paths - 1 ? n_paths - 1 : want);
+      const int want = wanted_path(ts.my_idx, lane_change, n_paths);
       // the lane whose first seed lane holds path `want`
       const bool own = cnt0 > 0 && want >= goff0 && want < goff0 + cnt0;
-      if (own && want > goff0) {
-        // a later branch of this lane's seed lane: walk to it again (rare: branching inside 16 hops)
-        const int start = seed_start(m, seed, p0, px, py);
-        BranchState bs;
-        bs.reset();
-        int j = 0;
-        do {
-          if (j == want - goff0) {
-            path.n = equally_spaced_path(m, seed.f, bs, start, SMX_CTRL_WPS - 1, px, py, knots, SMX_BLOCK,
-                                         SMX_CTRL_WPS,
-                                         [&](int i, const WaypointOut& w) { path_put(path, i, w.x, w.y, w.heading); });
-            break;
-          }
-          equally_spaced_path(m, seed.f, bs, start, SMX_CTRL_WPS - 1, px, py, knots, SMX_BLOCK, 0,
-                              [&](int, const WaypointOut&) {});
-          ++j;
-        } while (bs.advance());
-      }
-      int owners = own ? (1 << p0) : 0;
-#pragma unroll
-      for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) owners |= __shfl_xor(owners, msk, SMX_WP_LANES);
+      if (own && want > goff0)  // a later branch of this lane's seed lane
+        path.n = rewalk_branch(m, seed, p0, px, py, want - goff0, knots,
+                               [&](int i, const WaypointOut& w) { path_put(path, i, w.x, w.y, w.heading); });
+      const int owners = team_or(own ? (1 << p0) : 0);
       // the lane that holds the wanted path carries on alone (control law, physics, state write):
       // nothing moves between lanes and no second copy of the path is kept in registers
       act_lane = owners ? (__ffs(owners) - 1) : 0;
@@ -528,16 +723,15 @@ __global__ void __attribute__((amdgpu_waves_per_eu(2, 8))) __launch_bounds__(SMX
           }
         }
         // beyond the team's first seed lanes (roads with more than 4 lanes): serial search
-        if (!owners) ctrl_path_serial(m, seed, px, py, want, knots, SMX_BLOCK, path);
+        if (!owners)
+          path.n = ctrl_path_serial(m, seed, px, py, want, knots, SMX_BLOCK,
+                                    [&](int i, const WaypointOut& w) { ctrl_path_put(path, i, w.x, w.y, w.heading); });
         if (!SMX_SKIP(a, 1048576)) co = lane_following_from_path(s, cs, c.dt, target_speed, lane_change, hg, lg, path);
       }
       SMX_TSTAMP(tc4);
       SMX_TACC(18, tc3, tc4);
     } else {
-      // reference asserts "no waypoints found"; keep the last command
-      co.throttle = cs.throttle;
-      co.brake = 0.0;
-      co.steering = cs.steer;
+      co = last_command(cs);
     }
   }
   if (p0 != act_lane) return;
@@ -547,21 +741,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(2, 8))) __launch_bounds__(SMX
   if (!SMX_SKIP(a, 2097152)) vehicle_step(s, co, c.dt);
   SMX_TSTAMP(tc6);
   SMX_TACC(19, tc5, tc6);
-  SF(SMX_S_X) = s.x;
-  SF(SMX_S_Y) = s.y;
-  SF(SMX_S_HEADING) = s.heading;
-  SF(SMX_S_U) = s.u;
-  SF(SMX_S_V) = s.v;
-  SF(SMX_S_R) = s.r;
-  SF(SMX_S_DELTA) = s.delta;
-  SF(SMX_S_LAT_INT) = cs.lat_int;
-  SF(SMX_S_SPD_INT) = cs.spd_int;
-  SF(SMX_S_STEER) = cs.steer;
-  SF(SMX_S_THROTTLE) = cs.throttle;
-  SF(SMX_S_SPD_ERR) = cs.spd_err;
-  SF(SMX_S_MCL_X) = cs.mcl_x;
-  SF(SMX_S_MCL_Y) = cs.mcl_y;
-  a.st.flags[gid] = cs.mcl_set ? (flags | SMX_F_MCL_SET) : (flags & ~SMX_F_MCL_SET);
+  store_vehicle_state(a, gid, total, s, cs, flags);
   SMX_TSTAMP(tc7);
   SMX_TACC(20, tc0, tc7);
 }
@@ -579,31 +759,6 @@ struct CtrlHandoff {
   int32_t* n;    // [E*N] waypoints held; 0 = no path found (the reference asserts; the last command is kept)
 };
 
-// Controllers.perform_action's decoding of the Lane / LaneWithContinuousSpeed action (controllers/__init__.py:113-144)
-template <int SPACE>
-__device__ __forceinline__ bool decode_lane_action(const KernelArgs& a, size_t gid, double& target_speed, int& lane_change,
-                                                   double& hg, double& lg) {
-  if (SPACE == SMX_ACTION_SPACE_LANE) {
-    const int action = a.actions[gid];
-    if (action < SMX_ACTION_NONE || action > SMX_ACTION_CHANGE_LANE_RIGHT) {
-      atomicOr(a.status, SMX_DEVICE_BAD_LANE_ACTION);  // reported at the next smx_sync; the code moves nothing
-      return false;
-    }
-    if (action < 0) return false;
-    target_speed = action == SMX_ACTION_KEEP_LANE ? 15.0 : (action == SMX_ACTION_SLOW_DOWN ? 0.0 : 12.5);
-    lane_change = action == SMX_ACTION_CHANGE_LANE_LEFT ? 1 : (action == SMX_ACTION_CHANGE_LANE_RIGHT ? -1 : 0);
-    hg = target_speed > 0.0 ? a.heading_gain_pos : 0.01;
-    lg = target_speed > 0.0 ? a.lateral_gain_pos : 0.36;
-    return true;
-  }
-  const float act0 = a.actions_f32[gid * 3 + 0], act1 = a.actions_f32[gid * 3 + 1];
-  if (act0 != act0) return false;  // NaN = no action
-  target_speed = (double)act0;
-  lane_change = lane_change_of_action(act1);
-  lateral_gains_for_speed(target_speed, hg, lg);
-  return true;
-}
-
 template <int SPACE>
 __device__ __forceinline__ void control_paths_for(const KernelArgs& a, const CtrlHandoff& ho, const size_t gid, int* knots) {
   const smx_config& c = a.cfg;
@@ -613,9 +768,8 @@ __device__ __forceinline__ void control_paths_for(const KernelArgs& a, const Ctr
   if (gid >= total) return;  // whole teams leave together
   const int flags = a.st.flags[gid];
   if (!(flags & SMX_F_ALIVE) || (flags & SMX_F_SOCIAL)) return;
-  double target_speed, hg, lg;
-  int lane_change;
-  if (!decode_lane_action<SPACE>(a, gid, target_speed, lane_change, hg, lg)) return;  // uniform within a team
+  const LaneAction la = load_lane_action<SPACE>(a, gid);
+  if (!la.has_action) return;  // uniform within a team
   const PathSeeds seed = load_seeds(a, gid, total);  // found by k_scan at this very pose
   const double px = SF(SMX_S_X), py = SF(SMX_S_Y);
   auto put = [&](int i, const WaypointOut& w) {
@@ -631,24 +785,20 @@ __device__ __forceinline__ void control_paths_for(const KernelArgs& a, const Ctr
   // every path of a seed lane is the projection of the vehicle on the start lanepoint's heading line
   // (interpolate_knots at t = 0), so find_current_lane needs the start records only.  Taken when every seed
   // lane of the team has a list for its start and filter and none branches inside the lookahead.
+  // (The choice among the seed lanes is written across the team's lanes here and over per-seed-lane arrays in
+  // k_control_fast: that piece is left separate.)
   if (a.knots.key != nullptr && c.wp_lookahead >= SMX_CTRL_WPS - 1 && seed.road >= 0 && seed.n_lanes <= SMX_WP_LANES) {
     const size_t paths = total * SMX_WP_LANES, path = gid * SMX_WP_LANES + p0;
     const int start = p0 < seed.n_lanes ? seed_start(m, seed, p0, px, py) : -1;
     bool reusable = true;
     int n32 = 0;
     if (start >= 0) {
-      reusable = a.knots.key[path] == start && a.knots.key[paths + path] == (seed.f.n > 0 ? seed.f.road[0] : -1) &&
-                 a.knots.key[2 * paths + path] == (seed.f.n > 1 ? seed.f.road[1] : -1) && a.knots.cnt[path] == 1;
       n32 = a.knots.n[path];
-      reusable = reusable && n32 > 0;
+      reusable = knot_list_reusable(a.knots.key[path], a.knots.key[paths + path], a.knots.key[2 * paths + path], a.knots.cnt[path],
+                                    n32, start, seed.f);
     }
-    int bad = reusable ? 0 : 1;
-#pragma unroll
-    for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) bad |= __shfl_xor(bad, msk, SMX_WP_LANES);
-    if (!bad) {  // uniform within a team
-      int started = start >= 0 ? (1 << p0) : 0;
-#pragma unroll
-      for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) started |= __shfl_xor(started, msk, SMX_WP_LANES);
+    if (!team_or(reusable ? 0 : 1)) {  // uniform within a team
+      const int started = team_or(start >= 0 ? (1 << p0) : 0);
       const int n_paths = __popc(started);
       if (n_paths == 0) {
         if (p0 == 0) ho.n[gid] = 0;
@@ -660,190 +810,32 @@ __device__ __forceinline__ void control_paths_for(const KernelArgs& a, const Ctr
       smx_lp_rec r0 = smx_lp_rec{};
       if (start >= 0) {
         r0 = load_lp(m, start, 46);
-        const double proj = (px - r0.x) * r0.dirx + (py - r0.y) * r0.diry;
-        const double fx = n32 == 1 ? r0.x : r0.x + proj * r0.dirx, fy = n32 == 1 ? r0.y : r0.y + proj * r0.diry;
-        const double ex = fx - px, ey = fy - py;
-        my_d = sqrt(ex * ex + ey * ey);
+        my_d = first_waypoint_distance(r0.x, r0.y, r0.dirx, r0.diry, n32, px, py);
         my_idx = mine;
       }
-#pragma unroll
-      for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) {
-        const double od = __shfl_xor(my_d, msk, SMX_WP_LANES);
-        const int oi = __shfl_xor(my_idx, msk, SMX_WP_LANES);
-        if (od < my_d || (od == my_d && oi < my_idx)) {
-          my_d = od;
-          my_idx = oi;
-        }
-      }
-      int want = my_idx + lane_change;
-      want = want < 0 ? 0 : (want > n_paths - 1 ? n_paths - 1 : want);
-      if (start < 0 || mine != want) return;
-      // ---- the wanted path's 17 waypoints from the list: knots into registers (every load in flight
-      // together), their arclength in path order (pass 1's additions), then the interpolation
+      team_nearest(my_d, my_idx);
+      if (start < 0 || mine != wanted_path(my_idx, la.lane_change, n_paths)) return;
       const int n16 = n32 < SMX_CTRL_WPS ? n32 : SMX_CTRL_WPS;
-      const int nk16 = a.knots.nk16[path];
-      const int last = a.knots.end16[path];  // the last knot when it is not one of the list's
-      auto fetch = [&](int k) { return (k == nk16 - 1 && last >= 0) ? last : a.knots.idx[(size_t)(k + 1) * paths + path]; };
-      constexpr int KP = SMX_WPT_PRELOAD;
-      double kx[KP], ky[KP], kh[KP], kw[KP], ks_[KP];
-      int kl[KP];
-      {
-        int kid[KP];
-#pragma unroll
-        for (int k = 0; k < KP; ++k) kid[k] = k < nk16 ? fetch(k) : 0;
-#pragma unroll
-        for (int k = 0; k < KP; ++k) {
-          const smx_lp_rec* r = m.lp_rec + kid[k];
-          const bool have = k < nk16;
-          kx[k] = have ? r->x : 0.0;
-          ky[k] = have ? r->y : 0.0;
-          kh[k] = have ? r->heading : 0.0;
-          kl[k] = have ? r->lane : 0;
-        }
-#pragma unroll
-        for (int k = 0; k < KP; ++k) {
-          const bool ask = k < nk16 && kl[k] != (k == 0 ? (int)r0.lane : kl[k > 0 ? k - 1 : 0]);
-          kw[k] = ask ? m.lane_width[kl[k]] : 0.0;
-          ks_[k] = ask ? m.lane_speed[kl[k]] : 0.0;
-        }
-      }
-      double D = 0.0;
-      {
-        const double proj = (px - r0.x) * r0.dirx + (py - r0.y) * r0.diry;
-        double lastx = r0.x + proj * r0.dirx, lasty = r0.y + proj * r0.diry;
-#pragma unroll
-        for (int k = 0; k < KP; ++k) {
-          if (k < nk16) {
-            const double ex = kx[k] - lastx, ey = ky[k] - lasty;
-            D += sqrt(ex * ex + ey * ey);
-            lastx = kx[k];
-            lasty = ky[k];
-          }
-        }
-        for (int k = KP; k < nk16; ++k) {
-          const smx_lp_rec* r = m.lp_rec + fetch(k);
-          const double qx = r->x, qy = r->y;
-          const double ex = qx - lastx, ey = qy - lasty;
-          D += sqrt(ex * ex + ey * ey);
-          lastx = qx;
-          lasty = qy;
-        }
-      }
-      interpolate_knots_preloaded<KP>(m, r0, m.lane_width[r0.lane], m.lane_speed[r0.lane], nk16, n16, D, px, py, SMX_CTRL_WPS,
-                                      kx, ky, kh, kl, kw, ks_, fetch, put);
+      ctrl_waypoints_from_knots<false>(a, total, path, r0, a.knots.nk16[path], a.knots.end16[path], n16, px, py, put);
       ho.n[gid] = n16;
       return;
     }
   }
-  // Paths are numbered in the reference's order: seed lanes by index, branches depth-first.  Team lane p
-  // walks seed lanes p, p + 4, ... and measures the first waypoint of every path it meets
-  // (find_current_lane, lane_following_controller.py:367-374); counts exchanged by shuffles turn
-  // (lane, branch) into the global number.
-  int n_paths = 0;
-  double my_d = SMX_INF;
-  int my_idx = 0x7fffffff;
-  int goff0 = 0, cnt0 = 0;
-  if (seed.road >= 0) {
-    for (int r4 = 0; r4 < seed.n_lanes; r4 += SMX_WP_LANES) {  // uniform within a team
-      const int li = r4 + p0;
-      int cnt = 0, bj = 0x7fffffff;
-      double bd = SMX_INF;
-      if (li < seed.n_lanes) {
-        const int start = seed_start(m, seed, li, px, py);
-        if (start >= 0) {
-          BranchState bs;
-          bs.reset();
-          do {
-            double fx = 0.0, fy = 0.0;
-            equally_spaced_path(m, seed.f, bs, start, SMX_CTRL_WPS - 1, px, py, knots, SMX_BLOCK, 1,
-                                [&](int, const WaypointOut& w) {
-                                  fx = w.x;
-                                  fy = w.y;
-                                });
-            const double ex = fx - px, ey = fy - py;
-            const double d = sqrt(ex * ex + ey * ey);
-            if (d < bd) {  // strict: the lowest-numbered path wins ties (np.argmin)
-              bd = d;
-              bj = cnt;
-            }
-            ++cnt;
-          } while (bs.advance());
-        }
-      }
-      int incl = cnt;
-      {
-        int t = __shfl_up(incl, 1, SMX_WP_LANES);
-        if (p0 >= 1) incl += t;
-        t = __shfl_up(incl, 2, SMX_WP_LANES);
-        if (p0 >= 2) incl += t;
-      }
-      const int round_total = __shfl(incl, SMX_WP_LANES - 1, SMX_WP_LANES);
-      const int g = n_paths + incl - cnt;
-      if (r4 == 0) {
-        goff0 = g;
-        cnt0 = cnt;
-      }
-      if (bj != 0x7fffffff && (bd < my_d || (bd == my_d && g + bj < my_idx))) {
-        my_d = bd;
-        my_idx = g + bj;
-      }
-      n_paths += round_total;
-    }
-  }
-#pragma unroll
-  for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) {
-    const double od = __shfl_xor(my_d, msk, SMX_WP_LANES);
-    const int oi = __shfl_xor(my_idx, msk, SMX_WP_LANES);
-    if (od < my_d || (od == my_d && oi < my_idx)) {
-      my_d = od;
-      my_idx = oi;
-    }
-  }
-  if (n_paths <= 0) {  // uniform within a team
+  TeamSearch ts = team_path_search<false>(m, seed, p0, px, py, knots, [](int, const WaypointOut&) {});
+  team_nearest(ts.my_d, ts.my_idx);
+  if (ts.n_paths <= 0) {  // uniform within a team
     if (p0 == 0) ho.n[gid] = 0;
     return;
   }
-  int want = my_idx + lane_change;
-  want = want < 0 ? 0 : (want > n_paths - 1 ? n_paths - 1 : want);
+  const int want = wanted_path(ts.my_idx, la.lane_change, ts.n_paths);
   // the lane whose first seed lane holds path `want` walks to it again and writes its waypoints; a path of a
   // later seed lane (roads with more than four lanes) is found by lane 0 the long way
-  const bool own = cnt0 > 0 && want >= goff0 && want < goff0 + cnt0;
-  int owners = own ? (1 << p0) : 0;
-#pragma unroll
-  for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) owners |= __shfl_xor(owners, msk, SMX_WP_LANES);
+  const bool own = ts.cnt0 > 0 && want >= ts.goff0 && want < ts.goff0 + ts.cnt0;
+  const int owners = team_or(own ? (1 << p0) : 0);
   const int act_lane = owners ? (__ffs(owners) - 1) : 0;
   if (p0 != act_lane) return;
-  int n = 0;
-  if (owners) {
-    const int start = seed_start(m, seed, p0, px, py);
-    BranchState bs;
-    bs.reset();
-    int j = 0;
-    do {
-      if (j == want - goff0) {
-        n = equally_spaced_path(m, seed.f, bs, start, SMX_CTRL_WPS - 1, px, py, knots, SMX_BLOCK, SMX_CTRL_WPS, put);
-        break;
-      }
-      equally_spaced_path(m, seed.f, bs, start, SMX_CTRL_WPS - 1, px, py, knots, SMX_BLOCK, 0, [&](int, const WaypointOut&) {});
-      ++j;
-    } while (bs.advance());
-  } else {
-    int idx = 0;
-    for (int li = 0; li < seed.n_lanes && n == 0; ++li) {
-      const int start = seed_start(m, seed, li, px, py);
-      if (start < 0) continue;
-      BranchState bs;
-      bs.reset();
-      do {
-        if (idx == want) {
-          n = equally_spaced_path(m, seed.f, bs, start, SMX_CTRL_WPS - 1, px, py, knots, SMX_BLOCK, SMX_CTRL_WPS, put);
-          break;
-        }
-        equally_spaced_path(m, seed.f, bs, start, SMX_CTRL_WPS - 1, px, py, knots, SMX_BLOCK, 0, [&](int, const WaypointOut&) {});
-        ++idx;
-      } while (bs.advance());
-    }
-  }
+  const int n = owners ? rewalk_branch(m, seed, p0, px, py, want - ts.goff0, knots, put)
+                       : ctrl_path_serial(m, seed, px, py, want, knots, SMX_BLOCK, put);
   ho.n[gid] = n < SMX_CTRL_WPS ? n : SMX_CTRL_WPS;
 }
 
@@ -864,48 +856,21 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_paths(const KernelArgs a,
 template <int SPACE>
 __device__ __forceinline__ void control_law_for(const KernelArgs& a, const CtrlHandoff& ho, const size_t gid) {
   const smx_config& c = a.cfg;
-  const MapDev& m = a.map;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
   if (gid >= total) return;
   int flags = a.st.flags[gid];
   if (!(flags & SMX_F_ALIVE)) return;
-  if (flags & SMX_F_SOCIAL) {  // scripted lane follower: no controller, no dynamics
-    int lane = (int)SF(SMX_S_MCL_X), crossed = (int)SF(SMX_S_SPD_INT);
-    double offset = SF(SMX_S_MCL_Y), speed, x, y, heading;
-    SF(SMX_S_PREV_X) = SF(SMX_S_X);
-    SF(SMX_S_PREV_Y) = SF(SMX_S_Y);
-    const double cmd = c.social_model == SMX_SOCIAL_IDM ? SF(SMX_S_THROTTLE) : -1.0;
-    social_step(m, (int)(gid % c.num_vehicles), c.social_speed_factor, c.dt, lane, offset, crossed, speed, cmd);
-    social_pose(m, lane, offset, x, y, heading);
-    SF(SMX_S_X) = x;
-    SF(SMX_S_Y) = y;
-    SF(SMX_S_HEADING) = heading;
-    SF(SMX_S_U) = speed;
-    SF(SMX_S_MCL_X) = (double)lane;
-    SF(SMX_S_MCL_Y) = offset;
-    SF(SMX_S_SPD_INT) = (double)crossed;
+  if (flags & SMX_F_SOCIAL) {
+    social_vehicle_step(a, gid, total, SF(SMX_S_MCL_X), SF(SMX_S_MCL_Y), SF(SMX_S_SPD_INT), SF(SMX_S_THROTTLE), SF(SMX_S_X), SF(SMX_S_Y));
     return;
   }
   VehState s = load_vehicle(a, gid, total);
-  CtrlState cs;
-  cs.lat_int = SF(SMX_S_LAT_INT);
-  cs.spd_int = SF(SMX_S_SPD_INT);
-  cs.steer = SF(SMX_S_STEER);
-  cs.throttle = SF(SMX_S_THROTTLE);
-  cs.spd_err = SF(SMX_S_SPD_ERR);
-  cs.mcl_x = SF(SMX_S_MCL_X);
-  cs.mcl_y = SF(SMX_S_MCL_Y);
-  cs.mcl_set = (flags & SMX_F_MCL_SET) != 0;
-  ControlOut co;
-  // no action this tick: wheel torques do not persist, the steer motor target does
-  co.throttle = 0.0;
-  co.brake = 0.0;
-  co.steering = cs.steer;
+  CtrlState cs = load_ctrl_state(a, gid, total, flags);
+  ControlOut co = idle_command(cs);
   constexpr bool lane_following = SPACE == SMX_ACTION_SPACE_LANE || SPACE == SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED;
   if (lane_following) {
-    double target_speed, hg, lg;
-    int lane_change;
-    if (decode_lane_action<SPACE>(a, gid, target_speed, lane_change, hg, lg)) {
+    const LaneAction la = load_lane_action<SPACE>(a, gid);
+    if (la.has_action) {
       const int n = ho.n[gid];
       if (n > 0) {
         CtrlPath path;
@@ -918,12 +883,9 @@ __device__ __forceinline__ void control_law_for(const KernelArgs& a, const CtrlH
           path.y[k] = held ? q[total] : 0.0;
           path.h[k] = held ? q[2 * total] : 0.0;
         }
-        co = lane_following_from_path(s, cs, c.dt, target_speed, lane_change, hg, lg, path);
+        co = lane_following_from_path(s, cs, c.dt, la.target_speed, la.lane_change, la.hg, la.lg, path);
       } else {
-        // reference asserts "no waypoints found"; keep the last command
-        co.throttle = cs.throttle;
-        co.brake = 0.0;
-        co.steering = cs.steer;
+        co = last_command(cs);
       }
     }
   } else if (SPACE == SMX_ACTION_SPACE_TRAJECTORY) {
@@ -935,39 +897,12 @@ __device__ __forceinline__ void control_law_for(const KernelArgs& a, const CtrlH
     }
   } else {
     const float act0 = a.actions_f32[gid * 3 + 0], act1 = a.actions_f32[gid * 3 + 1], act2 = a.actions_f32[gid * 3 + 2];
-    if (!(act0 != act0)) {  // NaN = no action
-      if (SPACE == SMX_ACTION_SPACE_CONTINUOUS) {
-        co.throttle = clip_ref((double)act0, 0.0, 1.0);
-        co.brake = clip_ref((double)act1, 0.0, 1.0);
-        co.steering = clip_ref((double)act2, -1.0, 1.0);
-      } else {
-        // ActuatorDynamicController.perform_action (actuator_dynamic_controller.py:47-80)
-        const double change = clip_ref((double)act2, -1.0, 1.0);
-        co.throttle = clip_ref((double)act0, 0.0, 1.0);
-        co.brake = clip_ref((double)act1, 0.0, 1.0);
-        co.steering = clip_ref((1.0 - 0.001) * cs.steer + change * c.dt, -1.0, 1.0);
-      }
-      cs.steer = co.steering;  // last_steering_angle / the persisting steer target
-    }
+    if (!(act0 != act0)) co = direct_command<SPACE>(act0, act1, act2, cs, c.dt);  // NaN = no action
   }
   SF(SMX_S_PREV_X) = s.x;  // the position recorded by the previous observation
   SF(SMX_S_PREV_Y) = s.y;
   vehicle_step(s, co, c.dt);
-  SF(SMX_S_X) = s.x;
-  SF(SMX_S_Y) = s.y;
-  SF(SMX_S_HEADING) = s.heading;
-  SF(SMX_S_U) = s.u;
-  SF(SMX_S_V) = s.v;
-  SF(SMX_S_R) = s.r;
-  SF(SMX_S_DELTA) = s.delta;
-  SF(SMX_S_LAT_INT) = cs.lat_int;
-  SF(SMX_S_SPD_INT) = cs.spd_int;
-  SF(SMX_S_STEER) = cs.steer;
-  SF(SMX_S_THROTTLE) = cs.throttle;
-  SF(SMX_S_SPD_ERR) = cs.spd_err;
-  SF(SMX_S_MCL_X) = cs.mcl_x;
-  SF(SMX_S_MCL_Y) = cs.mcl_y;
-  a.st.flags[gid] = cs.mcl_set ? (flags | SMX_F_MCL_SET) : (flags & ~SMX_F_MCL_SET);
+  store_vehicle_state(a, gid, total, s, cs, flags);
 }
 
 template <int SPACE>
@@ -1059,21 +994,8 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic(const KernelArg
   if (gid >= total) return;
   const int flags = a.st.flags[gid];
   if (!(flags & SMX_F_ALIVE)) return;
-  if (flags & SMX_F_SOCIAL) {  // scripted lane follower, as in k_control
-    int lane = (int)SF(SMX_S_MCL_X), crossed = (int)SF(SMX_S_SPD_INT);
-    double offset = SF(SMX_S_MCL_Y), speed, x, y, heading;
-    SF(SMX_S_PREV_X) = SF(SMX_S_X);
-    SF(SMX_S_PREV_Y) = SF(SMX_S_Y);
-    const double cmd = c.social_model == SMX_SOCIAL_IDM ? SF(SMX_S_THROTTLE) : -1.0;
-    social_step(a.map, (int)(gid % c.num_vehicles), c.social_speed_factor, c.dt, lane, offset, crossed, speed, cmd);
-    social_pose(a.map, lane, offset, x, y, heading);
-    SF(SMX_S_X) = x;
-    SF(SMX_S_Y) = y;
-    SF(SMX_S_HEADING) = heading;
-    SF(SMX_S_U) = speed;
-    SF(SMX_S_MCL_X) = (double)lane;
-    SF(SMX_S_MCL_Y) = offset;
-    SF(SMX_S_SPD_INT) = (double)crossed;
+  if (flags & SMX_F_SOCIAL) {
+    social_vehicle_step(a, gid, total, SF(SMX_S_MCL_X), SF(SMX_S_MCL_Y), SF(SMX_S_SPD_INT), SF(SMX_S_THROTTLE), SF(SMX_S_X), SF(SMX_S_Y));
     return;
   }
   const double x = SF(SMX_S_X), y = SF(SMX_S_Y);
@@ -1170,25 +1092,8 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_fast(const KernelArgs a) 
     act0 = a.actions_f32[g * 3 + 0];
     act1 = a.actions_f32[g * 3 + 1];
   }
-  VehState s;
-  CtrlState cs;
-  {
-    const double* f = a.st.f64 + g;
-    s.x = f[(size_t)SMX_S_X * total];
-    s.y = f[(size_t)SMX_S_Y * total];
-    s.heading = f[(size_t)SMX_S_HEADING * total];
-    s.u = f[(size_t)SMX_S_U * total];
-    s.v = f[(size_t)SMX_S_V * total];
-    s.r = f[(size_t)SMX_S_R * total];
-    s.delta = f[(size_t)SMX_S_DELTA * total];
-    cs.lat_int = f[(size_t)SMX_S_LAT_INT * total];
-    cs.spd_int = f[(size_t)SMX_S_SPD_INT * total];
-    cs.steer = f[(size_t)SMX_S_STEER * total];
-    cs.throttle = f[(size_t)SMX_S_THROTTLE * total];
-    cs.spd_err = f[(size_t)SMX_S_SPD_ERR * total];
-    cs.mcl_x = f[(size_t)SMX_S_MCL_X * total];
-    cs.mcl_y = f[(size_t)SMX_S_MCL_Y * total];
-  }
+  VehState s = load_vehicle(a, g, total);
+  CtrlState cs = load_ctrl_state(a, g, total, flags);
   const PathSeeds seed = load_seeds(a, g, total);
   const bool lists = a.knots.key != nullptr;
   const size_t paths = total * SMX_WP_LANES;
@@ -1206,42 +1111,11 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_fast(const KernelArgs a) 
     kn_end16[q] = lists ? a.knots.end16[pth] : -1;
   }
   if (in_range && (flags & SMX_F_ALIVE)) {
-    if (flags & SMX_F_SOCIAL) {  // scripted lane follower: no controller, no dynamics
-      int lane = (int)cs.mcl_x, crossed = (int)cs.spd_int;
-      double offset = cs.mcl_y, speed, x, y, heading;
-      SF(SMX_S_PREV_X) = s.x;
-      SF(SMX_S_PREV_Y) = s.y;
-      const double cmd = c.social_model == SMX_SOCIAL_IDM ? cs.throttle : -1.0;
-      social_step(m, (int)(gid % c.num_vehicles), c.social_speed_factor, c.dt, lane, offset, crossed, speed, cmd);
-      social_pose(m, lane, offset, x, y, heading);
-      SF(SMX_S_X) = x;
-      SF(SMX_S_Y) = y;
-      SF(SMX_S_HEADING) = heading;
-      SF(SMX_S_U) = speed;
-      SF(SMX_S_MCL_X) = (double)lane;
-      SF(SMX_S_MCL_Y) = offset;
-      SF(SMX_S_SPD_INT) = (double)crossed;
+    if (flags & SMX_F_SOCIAL) {
+      social_vehicle_step(a, gid, total, cs.mcl_x, cs.mcl_y, cs.spd_int, cs.throttle, s.x, s.y);
     } else {
-      // Controllers.perform_action's decoding (decode_lane_action, on the words loaded above)
-      double target_speed = 0.0, hg = 0.0, lg = 0.0;
-      int lane_change = 0;
-      bool has_action = false;
-      if (SPACE == SMX_ACTION_SPACE_LANE) {
-        if (action < SMX_ACTION_NONE || action > SMX_ACTION_CHANGE_LANE_RIGHT) {
-          atomicOr(a.status, SMX_DEVICE_BAD_LANE_ACTION);  // reported at the next smx_sync; the code moves nothing
-        } else if (action >= 0) {
-          has_action = true;
-          target_speed = action == SMX_ACTION_KEEP_LANE ? 15.0 : (action == SMX_ACTION_SLOW_DOWN ? 0.0 : 12.5);
-          lane_change = action == SMX_ACTION_CHANGE_LANE_LEFT ? 1 : (action == SMX_ACTION_CHANGE_LANE_RIGHT ? -1 : 0);
-          hg = target_speed > 0.0 ? a.heading_gain_pos : 0.01;
-          lg = target_speed > 0.0 ? a.lateral_gain_pos : 0.36;
-        }
-      } else if (!(act0 != act0)) {  // NaN = no action
-        has_action = true;
-        target_speed = (double)act0;
-        lane_change = lane_change_of_action(act1);
-        lateral_gains_for_speed(target_speed, hg, lg);
-      }
+      const LaneAction la = decode_lane_action<SPACE>(a, action, act0, act1);  // (on the words loaded above)
+      const bool has_action = la.has_action;
       CtrlPath path;
       path.n = 0;
       if (has_action && !SMX_SKIP(a, 1 << 26)) {
@@ -1250,7 +1124,6 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_fast(const KernelArgs a) 
         if (!lists || c.wp_lookahead < SMX_CTRL_WPS - 1 || (seed.road >= 0 && seed.n_lanes > SMX_WP_LANES)) {
           slow = true;
         } else if (seed.road >= 0) {
-          const int f0 = seed.f.n > 0 ? seed.f.road[0] : -1, f1 = seed.f.n > 1 ? seed.f.road[1] : -1;
           int started = 0, qw = 0;
           double my_d = SMX_INF;
           int my_idx = 0;
@@ -1272,12 +1145,8 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_fast(const KernelArgs a) 
 #pragma unroll
           for (int q = 0; q < SMX_WP_LANES; ++q) {
             if (st[q] >= 0) {
-              const int n32 = kn_n[q];
-              if (!(kn_key0[q] == st[q] && kn_key1[q] == f0 && kn_key2[q] == f1 && kn_cnt[q] == 1 && n32 > 0)) slow = true;
-              const double proj = (px - rx[q]) * rdx[q] + (py - ry[q]) * rdy[q];
-              const double fx = n32 == 1 ? rx[q] : rx[q] + proj * rdx[q], fy = n32 == 1 ? ry[q] : ry[q] + proj * rdy[q];
-              const double ex = fx - px, ey = fy - py;
-              const double d = sqrt(ex * ex + ey * ey);
+              if (!knot_list_reusable(kn_key0[q], kn_key1[q], kn_key2[q], kn_cnt[q], kn_n[q], st[q], seed.f)) slow = true;
+              const double d = first_waypoint_distance(rx[q], ry[q], rdx[q], rdy[q], kn_n[q], px, py);
               if (d < my_d) {
                 my_d = d;
                 my_idx = __popc(started);
@@ -1287,8 +1156,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_fast(const KernelArgs a) 
           }
           const int n_paths = __popc(started);
           if (!slow && n_paths > 0) {
-            int want = my_idx + lane_change;
-            want = want < 0 ? 0 : (want > n_paths - 1 ? n_paths - 1 : want);
+            const int want = wanted_path(my_idx, la.lane_change, n_paths);
             // the want-th started seed lane
 #pragma unroll
             for (int q = 0; q < SMX_WP_LANES; ++q)
@@ -1309,53 +1177,9 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_fast(const KernelArgs a) 
                 r0.heading = rh[q];
               }
             r0.lane = 0;  // (lane, width and speed limit of the waypoints are not the controller's business)
-            const size_t pth = gid * SMX_WP_LANES + qw;
             const int n16 = n32w < SMX_CTRL_WPS ? n32w : SMX_CTRL_WPS;
-            auto fetch = [&](int k) { return (k == nk16 - 1 && last >= 0) ? last : a.knots.idx[(size_t)(k + 1) * paths + pth]; };
-            constexpr int KP = SMX_WPT_PRELOAD;
-            double kx[KP], ky[KP], kh[KP], kw[KP], ks_[KP];
-            int kl[KP];
-            {
-              int kid[KP];
-#pragma unroll
-              for (int k = 0; k < KP; ++k) kid[k] = a.knots.idx[(size_t)(k + 1) * paths + pth];  // (in range whatever nk16 is)
-#pragma unroll
-              for (int k = 0; k < KP; ++k) {
-                const bool have = k < nk16;
-                const int id = (k == nk16 - 1 && last >= 0) ? last : kid[k];
-                const smx_lp_rec* r = m.lp_rec + (have ? id : 0);
-                kx[k] = have ? r->x : 0.0;
-                ky[k] = have ? r->y : 0.0;
-                kh[k] = have ? r->heading : 0.0;
-                kl[k] = 0;
-                kw[k] = 0.0;
-                ks_[k] = 0.0;
-              }
-            }
-            double D = 0.0;
-            {
-              const double proj = (px - r0.x) * r0.dirx + (py - r0.y) * r0.diry;
-              double lastx = r0.x + proj * r0.dirx, lasty = r0.y + proj * r0.diry;
-#pragma unroll
-              for (int k = 0; k < KP; ++k) {
-                if (k < nk16) {
-                  const double ex = kx[k] - lastx, ey = ky[k] - lasty;
-                  D += sqrt(ex * ex + ey * ey);
-                  lastx = kx[k];
-                  lasty = ky[k];
-                }
-              }
-              for (int k = KP; k < nk16; ++k) {
-                const smx_lp_rec* r = m.lp_rec + fetch(k);
-                const double qx = r->x, qy = r->y;
-                const double ex = qx - lastx, ey = qy - lasty;
-                D += sqrt(ex * ex + ey * ey);
-                lastx = qx;
-                lasty = qy;
-              }
-            }
             double* col = path_lds + threadIdx.x;
-            interpolate_knots_preloaded<KP>(m, r0, 0.0, 0.0, nk16, n16, D, px, py, SMX_CTRL_WPS, kx, ky, kh, kl, kw, ks_, fetch,
+            ctrl_waypoints_from_knots<true>(a, total, gid * SMX_WP_LANES + qw, r0, nk16, last, n16, px, py,
                                             [&](int i, const WaypointOut& w) {
                                               col[(size_t)i * SMX_BLOCK] = w.heading;
                                               if (i < CTRL_XY) {
@@ -1375,40 +1199,18 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_fast(const KernelArgs a) 
         }
       }
       if (!slow) {
-        cs.mcl_set = (flags & SMX_F_MCL_SET) != 0;
-        ControlOut co;
-        // no action this tick: wheel torques do not persist, the steer motor target does
-        co.throttle = 0.0;
-        co.brake = 0.0;
-        co.steering = cs.steer;
+        ControlOut co = idle_command(cs);
         if (has_action) {
           if (path.n > 0 && !SMX_SKIP(a, 1 << 28)) {
-            co = lane_following_from_path(s, cs, c.dt, target_speed, lane_change, hg, lg, path);
+            co = lane_following_from_path(s, cs, c.dt, la.target_speed, la.lane_change, la.hg, la.lg, path);
           } else {
-            // reference asserts "no waypoints found"; keep the last command
-            co.throttle = cs.throttle;
-            co.brake = 0.0;
-            co.steering = cs.steer;
+            co = last_command(cs);
           }
         }
         SF(SMX_S_PREV_X) = s.x;  // the position recorded by the previous observation
         SF(SMX_S_PREV_Y) = s.y;
         if (!SMX_SKIP(a, 1 << 27)) vehicle_step(s, co, c.dt);
-        SF(SMX_S_X) = s.x;
-        SF(SMX_S_Y) = s.y;
-        SF(SMX_S_HEADING) = s.heading;
-        SF(SMX_S_U) = s.u;
-        SF(SMX_S_V) = s.v;
-        SF(SMX_S_R) = s.r;
-        SF(SMX_S_DELTA) = s.delta;
-        SF(SMX_S_LAT_INT) = cs.lat_int;
-        SF(SMX_S_SPD_INT) = cs.spd_int;
-        SF(SMX_S_STEER) = cs.steer;
-        SF(SMX_S_THROTTLE) = cs.throttle;
-        SF(SMX_S_SPD_ERR) = cs.spd_err;
-        SF(SMX_S_MCL_X) = cs.mcl_x;
-        SF(SMX_S_MCL_Y) = cs.mcl_y;
-        a.st.flags[gid] = cs.mcl_set ? (flags | SMX_F_MCL_SET) : (flags & ~SMX_F_MCL_SET);
+        store_vehicle_state(a, gid, total, s, cs, flags);
       }
     }
   }

@@ -367,11 +367,12 @@ __device__ inline ControlOut lane_following_from_path(const VehState& s, CtrlSta
 
 // Serial search (one lane does everything): number the paths in the reference's order (lanes by
 // index, branches depth-first), pick the one nearest by its first waypoint, synthesise
-// wp_paths[clip(nearest + lane_change)].  k_control uses it only when the wanted path is not one of
-// the four its team synthesises in parallel.
-__device__ inline void ctrl_path_serial(const MapDev& m, const PathSeeds& seed, double px, double py, int want,
-                                        int* knots, int kstride, CtrlPath& path) {
-  path.n = 0;
+// wp_paths[clip(nearest + lane_change)] through `put`; returns its waypoints (0: no such path).  The team kernels
+// use it only when the wanted path is not one of the four their team walks in parallel (roads of more than
+// four lanes).
+template <class Put>
+__device__ inline int ctrl_path_serial(const MapDev& m, const PathSeeds& seed, double px, double py, int want,
+                                       int* knots, int kstride, Put&& put) {
   int idx = 0;
   for (int li = 0; li < seed.n_lanes; ++li) {
     int start = seed_start(m, seed, li, px, py);
@@ -379,17 +380,15 @@ __device__ inline void ctrl_path_serial(const MapDev& m, const PathSeeds& seed, 
     BranchState bs;
     bs.reset();
     do {
-      if (idx == want) {
-        path.n = equally_spaced_path(m, seed.f, bs, start, SMX_CTRL_WPS - 1, px, py, knots, kstride, SMX_CTRL_WPS,
-                                     [&](int i, const WaypointOut& w) { ctrl_path_put(path, i, w.x, w.y, w.heading); });
-        return;
-      }
+      if (idx == want)
+        return equally_spaced_path(m, seed.f, bs, start, SMX_CTRL_WPS - 1, px, py, knots, kstride, SMX_CTRL_WPS, put);
       // not the wanted path: walk it only to discover its branchings
       equally_spaced_path(m, seed.f, bs, start, SMX_CTRL_WPS - 1, px, py, knots, kstride, 0,
                           [&](int, const WaypointOut&) {});
       ++idx;
     } while (bs.advance());
   }
+  return 0;
 }
 
 // AckermannChassis.control (chassis.py:678-718) + one SMARTS tick of the body model.

@@ -344,7 +344,7 @@ def test_lane_action_code_that_names_no_action_is_reported_at_sync(compiled_maps
     from smarts_amd import _native as nat
     from smarts_amd.engine import BatchedSim, SimConfig
 
-    for strategy in ("small", "large", "large_one_lane"):
+    for strategy in ("small", "large", "large_one_lane", "large_teams"):
         sim = BatchedSim(compiled_maps("loop"), SimConfig(num_envs=2, num_vehicles=2, launch_strategy=strategy))
         ref = BatchedSim(compiled_maps("loop"), SimConfig(num_envs=2, num_vehicles=2, launch_strategy=strategy))
         sim.reset(), ref.reset()
