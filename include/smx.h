@@ -101,7 +101,12 @@ enum { SMX_SOCIAL_CONSTANT = 0, SMX_SOCIAL_IDM = 1 };
  *   CONTINUOUS                 throttle, brake, steering                  (:94-99)
  *   ACTUATOR_DYNAMIC           throttle, brake, steering rate             (actuator_dynamic_controller.py:47-80)
  *   LANE_WITH_CONTINUOUS_SPEED target speed, lane change (-1 / 0 / +1), - (:113-124)
- * A NaN in the first float means "no action this tick". */
+ *   IMITATION                  acceleration (m/s^2), angular velocity (rad/s), - (imitation_controller.py:57-78); a NaN
+ *                              angular velocity beside a finite first float selects the reference's scalar form: the
+ *                              first float is then a speed to set, the pose is held (:50-56)
+ * A NaN in the first float means "no action this tick".
+ * The values are this interface's own: 7 and 8 follow on, 9 stays invalid (the reference's Python enum has MPC = 7,
+ * Imitation = 9; smarts_amd/env/agent_interface.py keeps those). */
 enum {
   SMX_ACTION_SPACE_LANE = 0,
   SMX_ACTION_SPACE_CONTINUOUS = 1,
@@ -112,8 +117,13 @@ enum {
    * controller, no dynamics model. */
   SMX_ACTION_SPACE_TARGET_POSE = 5,         /* smx_step_target_pose: MotionPlannerProvider + BezierMotionPlanner
                                                (motion_planner_provider.py:65-129, bezier_motion_planner.py:38-121) */
-  SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME = 6 /* smx_step_trajectory_with_time: TrajectoryInterpolationProvider
-                                               (trajectory_interpolation_provider.py:96-193) */
+  SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME = 6, /* smx_step_trajectory_with_time: TrajectoryInterpolationProvider
+                                                (trajectory_interpolation_provider.py:96-193) */
+  SMX_ACTION_SPACE_MPC = 7, /* smx_step_trajectory: the closed-form horizon-5 MPC (trajectory_tracking_controller.py:56-173,
+                               476-609), the sedan's mass, yaw inertia and tyre cornering stiffnesses; a dynamic agent */
+  SMX_ACTION_SPACE_IMITATION = 8 /* smx_step_continuous: ImitationController on a BoxChassis (imitation_controller.py:30-78;
+                                    Imitation is not a dynamic action space in this reference version, smarts.py:163-171,
+                                    so the agent is a kinematic one) */
 };
 
 #define SMX_MAX_ALIVE_LISTS 4
@@ -268,7 +278,8 @@ enum {
 };
 /* Agents of the kinematic action spaces have no dynamics model and no controller; their slots keep the provider's and
  * BoxChassis' state in rows that only those read (as the social slots reuse SMX_S_MCL_X / _Y / SMX_S_SPD_INT):
- *   SMX_S_U       = the provider's speed (VehicleState.speed; SMX_S_V and SMX_S_R stay 0)
+ *   SMX_S_U       = the provider's speed (VehicleState.speed; SMX_S_V and SMX_S_R stay 0); Imitation: the speed the
+ *                   controller hands to BoxChassis.control, which may be negative
  *   SMX_S_DELTA   = TargetPose: the provider's own heading (MotionPlannerProvider._poses[:, 2], never re-normalised,
  *                   motion_planner_provider.py:99), while SMX_S_HEADING holds Heading() of it (:109)
  *   SMX_S_LAT_INT = BoxChassis._last_heading (chassis.py:211-217)
@@ -558,13 +569,14 @@ int smx_reset(smx_handle h, const uint8_t* env_mask_dev, const smx_state* st, co
 /* One tick for every env: actions[E*N] are SMX_ACTION_* (int8, device). */
 int smx_step(smx_handle h, const int8_t* actions_dev, const smx_state* st, const smx_spawns* sp,
              const smx_outputs* out, void* hip_stream);
-/* The same tick for the float action spaces: actions[E*N][3] (float32, device). */
+/* The same tick for the float action spaces, Imitation among them: actions[E*N][3] (float32, device). */
 int smx_step_continuous(smx_handle h, const float* actions_dev, const smx_state* st, const smx_spawns* sp,
                         const smx_outputs* out, void* hip_stream);
-/* The same tick for ActionSpaceType.Trajectory.  trajectories[E*N][4][SMX_TRAJ_COLS] (float64, device):
- * rows x, y, heading, speed; columns 0..9 = the first ten points, column 10 = the LAST point of the
- * trajectory — all the PD controller reads; counts[E*N] (int32, device) = the trajectory's true
- * length, 0 = no action this tick. */
+/* The same tick for ActionSpaceType.Trajectory and ActionSpaceType.MPC.  trajectories[E*N][4][SMX_TRAJ_COLS] (float64,
+ * device): rows x, y, heading, speed; columns 0..9 = the first ten points, column 10 = the LAST point of the
+ * trajectory — all the PD controller reads, and all the MPC one does (curvature_calculation at offsets <= 4 over
+ * five points reaches index 9, the look-ahead index is min(3 or 1, n - 1), the desired speed is the last point's);
+ * counts[E*N] (int32, device) = the trajectory's true length, 0 = no action this tick. */
 #define SMX_TRAJ_COLS 11
 int smx_step_trajectory(smx_handle h, const double* trajectories_dev, const int32_t* counts_dev, const smx_state* st,
                         const smx_spawns* sp, const smx_outputs* out, void* hip_stream);
@@ -584,22 +596,23 @@ int smx_step_trajectory_with_time(smx_handle h, const double* trajectories_dev, 
  * kernel on hip_stream, no synchronisation.  With (px, py, pz, H) the frame, to_world(q) = inv(M) q + (px, py, pz)
  * (world_position_from_ego_frame, math.py:490-505; inv(M) is M's transpose) and headings become
  * wrap_value(h + H, -pi, pi) (no Heading()):
- *   SMX_ACTION_SPACE_TRAJECTORY            [E*N][4][SMX_TRAJ_COLS]: columns < min(count, 10) and column 10; speed copied
+ *   SMX_ACTION_SPACE_TRAJECTORY, _MPC      [E*N][4][SMX_TRAJ_COLS]: columns < min(count, 10) and column 10; speed copied
  *   SMX_ACTION_SPACE_TARGET_POSE           [E*N][4]: x, y, heading; seconds copied (counts_dev is not read)
  *   SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME  [E*N][5][max_points]: rows 1, 2, 3 (x, y, heading) of the first
  *                                          min(count, max_points) points; time and speed copied
  * (the rows smx_step_trajectory_with_time calls x, y and heading; the reference's adapter would rotate rows 0 and 1,
  * DESIGN.md).  Every other element is copied.  An agent is copied through whole when its ec_flags is 0 (last_obs is
- * None), when it sent no action (NaN x, count 0) or when it is a social slot.  action_space must be one of the three
- * and equal cfg.action_space (else SMX_ERR_INVALID); a configuration without SMX_SENSOR_EGO_CENTRIC gives
- * SMX_ERR_STATE. */
+ * None), when it sent no action (NaN x, count 0) or when it is a social slot.  action_space must be one of the four
+ * and equal cfg.action_space (else SMX_ERR_INVALID; Imitation actions hold no position or heading and pass through
+ * the reference's adapter unchanged); a configuration without SMX_SENSOR_EGO_CENTRIC gives SMX_ERR_STATE. */
 int smx_actions_to_world(smx_handle h, int32_t action_space, const double* in_dev, const int32_t* counts_dev,
                          int32_t max_points, double* out_dev, const smx_outputs* out, void* hip_stream);
 /* Waits for the stream, then reports what only the kernels could see since the last smx_sync, as SMX_ERR_INVALID: a
  * Lane action code outside -1..3; a TrajectoryWithTime action the reference raises on (fewer than two points or more
  * than max_points, a value that is not finite, times not strictly increasing, no point later than dt or the first one
- * already later); a TargetPose action that yields a pose that is not finite.  Such an agent is stepped as if it had
- * sent no action. */
+ * already later); a TargetPose action that yields a pose that is not finite; an Imitation action with a finite first
+ * float and an infinite second one, or one that yields a pose or a speed that is not finite.  Such an agent is stepped
+ * as if it had sent no action. */
 int smx_sync(smx_handle h, void* hip_stream);
 /* Device-side timing: while enabled, every smx_step is bracketed by a hipEvent pair recorded on
  * the stream it is launched on (no synchronisation).  smx_read_step_ms waits for the recorded

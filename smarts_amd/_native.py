@@ -23,7 +23,7 @@ EVENT_NAMES = ["collisions", "off_road", "off_route", "on_shoulder", "wrong_way"
                "reached_max_episode_steps", "agents_alive_done"]
 EV = {name.upper(): i for i, name in enumerate(EVENT_NAMES)}
 ACTION_SPACES = {"Lane": 0, "Continuous": 1, "ActuatorDynamic": 2, "LaneWithContinuousSpeed": 3, "Trajectory": 4,
-                 "TargetPose": 5, "TrajectoryWithTime": 6}
+                 "TargetPose": 5, "TrajectoryWithTime": 6, "MPC": 7, "Imitation": 8}
 TRAJ_COLS = 11
 SOCIAL_MODELS = {"constant": 0, "idm": 1}
 PHASES = ["control", "scan", "ogm", "sensors", "commit", "reset"]

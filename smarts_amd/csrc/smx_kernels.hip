@@ -91,7 +91,7 @@ struct KernelArgs {
 enum {
   SMX_DEVICE_BAD_LANE_ACTION = 1,  // a Lane action code outside -1..3 was met (and treated as "no action")
   SMX_DEVICE_BAD_TRAJECTORY = 2,   // a TrajectoryWithTime action the reference raises on (it moved nothing)
-  SMX_DEVICE_BAD_TARGET_POSE = 4   // a TargetPose action whose pose came out not finite (it moved nothing)
+  SMX_DEVICE_BAD_TARGET_POSE = 4   // a TargetPose / Imitation action whose pose or speed came out not finite (it moved nothing)
 };
 
 #define SF(field) a.st.f64[(size_t)(field) * total + gid]
@@ -654,13 +654,14 @@ __global__ void __attribute__((amdgpu_waves_per_eu(2, 8))) __launch_bounds__(SMX
   constexpr int space = SPACE;
   constexpr bool lane_following =
       space == SMX_ACTION_SPACE_LANE || space == SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED;
+  constexpr bool tracking = space == SMX_ACTION_SPACE_TRAJECTORY || space == SMX_ACTION_SPACE_MPC;  // packed trajectories
   LaneAction la = LaneAction{};
   float act0 = 0.f, act1 = 0.f, act2 = 0.f;
   bool has_action;
   if (lane_following) {
     la = load_lane_action<SPACE>(a, gid);
     has_action = la.has_action;
-  } else if (space == SMX_ACTION_SPACE_TRAJECTORY) {
+  } else if (tracking) {
     has_action = a.traj_n[gid] > 0;
   } else {
     act0 = a.actions_f32[gid * 3 + 0];
@@ -670,12 +671,12 @@ __global__ void __attribute__((amdgpu_waves_per_eu(2, 8))) __launch_bounds__(SMX
   }
   int act_lane = 0;  // the team lane that runs the control law and the physics (uniform in the team)
   ControlOut co = idle_command(cs);
-  if (has_action && space == SMX_ACTION_SPACE_TRAJECTORY) {
+  if (has_action && tracking) {
     if (p0 == 0) {
       PackedTraj t;
       t.p = a.traj + gid * (size_t)(4 * SMX_TRAJ_COLS);
       t.n = a.traj_n[gid];
-      co = trajectory_tracking_pd(s, cs, c.dt, t);
+      co = space == SMX_ACTION_SPACE_MPC ? trajectory_tracking_mpc(s, cs, c.dt, t) : trajectory_tracking_pd(s, cs, c.dt, t);
     }
   } else if (has_action && !lane_following) {
     co = direct_command<SPACE>(act0, act1, act2, cs, c.dt);
@@ -888,12 +889,12 @@ __device__ __forceinline__ void control_law_for(const KernelArgs& a, const CtrlH
         co = last_command(cs);
       }
     }
-  } else if (SPACE == SMX_ACTION_SPACE_TRAJECTORY) {
+  } else if (SPACE == SMX_ACTION_SPACE_TRAJECTORY || SPACE == SMX_ACTION_SPACE_MPC) {
     if (a.traj_n[gid] > 0) {
       PackedTraj t;
       t.p = a.traj + gid * (size_t)(4 * SMX_TRAJ_COLS);
       t.n = a.traj_n[gid];
-      co = trajectory_tracking_pd(s, cs, c.dt, t);
+      co = SPACE == SMX_ACTION_SPACE_MPC ? trajectory_tracking_mpc(s, cs, c.dt, t) : trajectory_tracking_pd(s, cs, c.dt, t);
     }
   } else {
     const float act0 = a.actions_f32[gid * 3 + 0], act1 = a.actions_f32[gid * 3 + 1], act2 = a.actions_f32[gid * 3 + 2];
@@ -1020,6 +1021,38 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic(const KernelArg
     // vehicle stays, its speed is 0, and control() is still called
     if (!given) o = bezier_first_point(x, y, raw, x, y, raw, c.dt, c.dt);
     SF(SMX_S_KIN_RAW_HEADING) = o.heading;
+  } else if (SPACE == SMX_ACTION_SPACE_IMITATION) {
+    // ImitationController.perform_action on a BoxChassis (imitation_controller.py:50-78)
+    const float act0 = a.actions_f32[gid * 3 + 0], act1 = a.actions_f32[gid * 3 + 1];
+    if (act0 != act0) return;  // no action: no control() call
+    const double heading = SF(SMX_S_HEADING), speed = SF(SMX_S_U);
+    if (act1 != act1) {
+      // a scalar action, "setting the initial speed" (:50-56): vehicle.control(vehicle.pose, action, dt)
+      o.x = x;
+      o.y = y;
+      o.heading = heading;
+      o.speed = (double)act0;
+    } else {
+      // (acceleration, angular_velocity), from the heading and speed held before the tick (:61-78)
+      const double acceleration = (double)act0, angular_velocity = (double)act1;
+      const double target_heading = py_mod(heading + angular_velocity * c.dt, SMX_TWO_PI);
+      double hvx, hvy;
+      radians_to_vec(heading, hvx, hvy);
+      o.x = x + hvx * speed * c.dt;
+      o.y = y + hvy * speed * c.dt;
+      // Pose(orientation=fast_quaternion_from_angle(target_heading)).heading: yaw_from_quaternion of (0, 0, sin, cos)
+      // of the half angle (math.py:78-106), then Heading() further down
+      double qz, qw;
+      sincos(target_heading * 0.5, &qz, &qw);
+      o.heading = atan2(2.0 * (0.0 * 0.0 + qw * qz), qw * qw + 0.0 * 0.0 - 0.0 * 0.0 - qz * qz);
+      o.speed = speed + acceleration * c.dt;
+    }
+    if (!(isfinite(o.x) && isfinite(o.y) && isfinite(o.heading) && isfinite(o.speed))) {
+      // (an infinite component, or a pose or speed that came out not finite: the reference would carry it on; here it is
+      // reported at the next smx_sync and the agent is stepped as if it had sent nothing)
+      atomicOr(a.status, SMX_DEVICE_BAD_TARGET_POSE);
+      return;
+    }
   } else {
     const int n = a.traj_n[gid];
     if (n == 0) return;  // no action: the vehicle is not updated (no control() call: _last_heading, _last_dt stay)
@@ -1033,7 +1066,9 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic(const KernelArg
   SF(SMX_S_KIN_LAST_DT) = c.dt;
   SF(SMX_S_X) = o.x;
   SF(SMX_S_Y) = o.y;
-  SF(SMX_S_HEADING) = wrap_heading(o.heading);  // Heading(...) (coordinates.py:175-184)
+  // Heading(...) (coordinates.py:175-184); Imitation's scalar form hands the vehicle's own pose back, a Heading already
+  const double held_heading = SF(SMX_S_HEADING);
+  SF(SMX_S_HEADING) = (SPACE == SMX_ACTION_SPACE_IMITATION && o.heading == held_heading) ? held_heading : wrap_heading(o.heading);
   SF(SMX_S_U) = o.speed;
 }
 
@@ -4849,6 +4884,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_actions_to_world(const double* __
                                                                 double* __restrict__ out, const double* __restrict__ frame,
                                                                 const uint8_t* __restrict__ ec_flags, const size_t total,
                                                                 const int n_veh, const int n_social, const int cols) {
+  // (SMX_ACTION_SPACE_MPC takes the Trajectory instance: both are _trajectory_adapter, ego_centric_adapters.py:316-322)
   constexpr bool POSE = SPACE == SMX_ACTION_SPACE_TARGET_POSE, TIMED = SPACE == SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME;
   constexpr int ROWS = POSE ? 4 : TIMED ? 5 : 4;
   constexpr int RX = TIMED ? 1 : 0;  // rows x, y, heading are RX, RX + 1, RX + 2
@@ -5314,7 +5350,7 @@ static int create_impl(const smx_config* cfg, int device, smx_handle* out) {
     return fail(h, SMX_ERR_INVALID, "social_speed_factor must be >= 0");
   if (c.social_model != SMX_SOCIAL_CONSTANT && c.social_model != SMX_SOCIAL_IDM)
     return fail(h, SMX_ERR_INVALID, "unknown social_model");
-  if (c.action_space < SMX_ACTION_SPACE_LANE || c.action_space > SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME)
+  if (c.action_space < SMX_ACTION_SPACE_LANE || c.action_space > SMX_ACTION_SPACE_IMITATION)
     return fail(h, SMX_ERR_INVALID, "unknown action_space");
   if ((c.sensors & SMX_SENSOR_OGM) &&
       (c.ogm_width < 1 || c.ogm_height < 1 || (c.ogm_width * c.ogm_height) % 16 != 0 ||
@@ -6007,7 +6043,9 @@ static ControlKernels control_kernels(int action_space) {
     case SMX_ACTION_SPACE_ACTUATOR_DYNAMIC: return control_kernels_of<SMX_ACTION_SPACE_ACTUATOR_DYNAMIC>();
     case SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED: return control_kernels_of<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED>();
     case SMX_ACTION_SPACE_TRAJECTORY: return control_kernels_of<SMX_ACTION_SPACE_TRAJECTORY>();
+    case SMX_ACTION_SPACE_MPC: return control_kernels_of<SMX_ACTION_SPACE_MPC>();
     case SMX_ACTION_SPACE_TARGET_POSE: return ControlKernels{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_control_kinematic<SMX_ACTION_SPACE_TARGET_POSE>};
+    case SMX_ACTION_SPACE_IMITATION: return ControlKernels{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_control_kinematic<SMX_ACTION_SPACE_IMITATION>};
     default: return ControlKernels{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_control_kinematic<SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME>};
   }
 }
@@ -6288,15 +6326,16 @@ static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const
   if (is_step) {
     const int sp_ = h->cfg.action_space;
     const bool ok = sp_ == SMX_ACTION_SPACE_LANE ? (entry == Entry::LANE && actions != nullptr)
-                    : sp_ == SMX_ACTION_SPACE_TRAJECTORY ? (entry == Entry::TRAJECTORY && traj != nullptr && traj_n != nullptr)
+                    : (sp_ == SMX_ACTION_SPACE_TRAJECTORY || sp_ == SMX_ACTION_SPACE_MPC)
+                        ? (entry == Entry::TRAJECTORY && traj != nullptr && traj_n != nullptr)
                     : sp_ == SMX_ACTION_SPACE_TARGET_POSE ? (entry == Entry::TARGET_POSE && traj != nullptr)
                     : sp_ == SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME
                         ? (entry == Entry::TRAJECTORY_WITH_TIME && traj != nullptr && traj_n != nullptr)
                         : (entry == Entry::FLOATS && actions_f32 != nullptr);
     if (!ok)
       return fail(h, SMX_ERR_INVALID,
-                  "actions do not match cfg.action_space (smx_step: Lane, smx_step_trajectory: Trajectory, "
-                  "smx_step_continuous: the float spaces, smx_step_target_pose: TargetPose, "
+                  "actions do not match cfg.action_space (smx_step: Lane, smx_step_trajectory: Trajectory and MPC, "
+                  "smx_step_continuous: the float spaces and Imitation, smx_step_target_pose: TargetPose, "
                   "smx_step_trajectory_with_time: TrajectoryWithTime)");
   }
   hipStream_t stream = (hipStream_t)stream_;
@@ -6384,10 +6423,11 @@ extern "C" int smx_actions_to_world(smx_handle h, int32_t action_space, const do
   const smx_config& c = h->cfg;
   if (!(c.sensors & SMX_SENSOR_EGO_CENTRIC))
     return fail(h, SMX_ERR_STATE, "smx_actions_to_world: the configuration has no SMX_SENSOR_EGO_CENTRIC (no frame is kept)");
-  const bool traj = action_space == SMX_ACTION_SPACE_TRAJECTORY, pose = action_space == SMX_ACTION_SPACE_TARGET_POSE;
+  const bool traj = action_space == SMX_ACTION_SPACE_TRAJECTORY || action_space == SMX_ACTION_SPACE_MPC;
+  const bool pose = action_space == SMX_ACTION_SPACE_TARGET_POSE;
   const bool timed = action_space == SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME;
   if (!traj && !pose && !timed)
-    return fail(h, SMX_ERR_INVALID, "smx_actions_to_world: only Trajectory, TargetPose and TrajectoryWithTime actions have a frame");
+    return fail(h, SMX_ERR_INVALID, "smx_actions_to_world: only Trajectory, MPC, TargetPose and TrajectoryWithTime actions have a frame");
   if (action_space != c.action_space) return fail(h, SMX_ERR_INVALID, "smx_actions_to_world: action_space is not cfg.action_space");
   if (!in_dev || !out_dev || in_dev == out_dev || (!pose && !counts_dev))
     return fail(h, SMX_ERR_INVALID, "smx_actions_to_world: null action buffer or counts, or the output is the input");
@@ -6430,8 +6470,9 @@ extern "C" int smx_sync(smx_handle h, void* hip_stream) {
                     "point later than dt or the first one already later); the agents that sent one were not moved");
       if (bits & SMX_DEVICE_BAD_TARGET_POSE)
         return fail(h, SMX_ERR_INVALID,
-                    "a TargetPose action whose pose is not finite reached smx_step_target_pose since the last smx_sync; the "
-                    "agents that sent one were stepped as if they had sent no action");
+                    "a TargetPose action whose pose is not finite reached smx_step_target_pose, or an Imitation action "
+                    "with an infinite component or a pose or speed that is not finite reached smx_step_continuous, since the "
+                    "last smx_sync; the agents that sent one were stepped as if they had sent no action");
     }
   }
   return SMX_OK;

@@ -86,7 +86,10 @@ enum class AliveList : uint8_t { NONE, CARRIED, BUILD };  // BUILD: k_alive_list
 // control slow list)
 enum class Control : uint8_t { NONE, ONE, ONE_LDS, PATHS_LAW, LAW, FAST_LISTED, KINEMATIC };
 static constexpr bool smx_kinematic_space(int action_space) {
-  return action_space == SMX_ACTION_SPACE_TARGET_POSE || action_space == SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME;
+  // (one mask test; smx_create holds action_space to 0 .. SMX_ACTION_SPACE_IMITATION)
+  constexpr unsigned kinematic = (1u << SMX_ACTION_SPACE_TARGET_POSE) | (1u << SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME) |
+                                 (1u << SMX_ACTION_SPACE_IMITATION);
+  return ((kinematic >> (action_space & 31)) & 1u) != 0;
 }
 // SCAN: the small form's k_scan (both halves); large form: the one-lane kernel (+ slow list / chain), k_scan_half with the
 // routed instance, with eight lanes a vehicle, with four

@@ -464,6 +464,7 @@ __device__ inline void vehicle_step(VehState& s, ControlOut c, double dt) {
 // 0..9, the last point and the length only, which is the form it travels in (smx.h).
 // Controller state reuse: lat_int = lateral_error, spd_int = integral_velocity_error, spd_err =
 // velocity_error, mcl_x = integral_windup_error, mcl_y = heading_error, steer / throttle = filters.
+// The two helpers are shared with the MPC law further down.
 // ---------------------------------------------------------------------------------
 struct PackedTraj {
   const double* p;  // [4][SMX_TRAJ_COLS]: x, y, heading, speed rows; column 10 = the last point
@@ -495,6 +496,70 @@ __device__ __forceinline__ double low_pass_filter_ref(double input, double prev,
   return clip_ref(prev + raw_value, -1.0, 1.0);
 }
 
+// calculate_heading_lateral_error (:398-441) with speed_reduction_activation on; `ahead_curvature` is
+// |curvature_calculation(trajectory, 4)|, which calculate_raw_throttle_feedback asks for again.  One copy for both
+// control laws; the look-ahead is a compile-time constant of each (the PD's 6, the MPC's 3).
+struct TrackingErrors {
+  double heading, lateral;
+};
+template <int INITIAL_LOOK_AHEAD>
+__device__ __forceinline__ TrackingErrors calculate_heading_lateral_error(const VehState& s, const HeadingTrig& trig,
+                                                                         const PackedTraj& t, double ahead_curvature) {
+  TrackingErrors e;
+  e.heading = min_angles_difference_signed(py_mod(s.heading, SMX_TWO_PI), t.at(2, 0));
+  int look = INITIAL_LOOK_AHEAD;
+  double look_dist = (double)INITIAL_LOOK_AHEAD;
+  if (ahead_curvature < 30.0) {  // speed_reduction_activation = 1
+    look = 1;
+    look_dist = 1.0;
+  }
+  const int k = look < t.n - 1 ? look : t.n - 1;
+  double pvx, pvy;
+  radians_to_vec(t.at(2, k), pvx, pvy);
+  const double lx = s.x - look_dist * trig.sh, ly = s.y + look_dist * trig.ch;
+  e.lateral = signed_dist_to_line(lx, ly, t.at(0, k), t.at(1, k), pvx, pvy);
+  return e;
+}
+
+// calculate_raw_throttle_feedback (:333-395) with speed_reduction_activation on: updates velocity_error (spd_err),
+// integral_windup_error (mcl_x) and throttle_state (throttle), returns the filtered throttle; `desired_speed` comes
+// back for the PD's integral.  The gains are literals at both call sites, so each law keeps its own constants folded
+// in the expression order written here.
+__device__ __forceinline__ double calculate_raw_throttle_feedback(CtrlState& cs, const PackedTraj& t, double speed, double lat,
+                                                                  double ahead_curvature, double velocity_gain,
+                                                                  double velocity_integral_gain, double integral_velocity_error,
+                                                                  double velocity_damping_gain, double windup_gain,
+                                                                  double traction_gain, double throttle_filter_constant,
+                                                                  double dt, double& desired_speed) {
+  desired_speed = t.last(3);
+  if (ahead_curvature < 30.0)
+    desired_speed = clip_ref(0.8 * desired_speed, 0.0, 8.3);
+  else if (ahead_curvature < 100.0)
+    desired_speed *= 0.8;
+  const double velocity_error = speed - desired_speed;
+  const double damping = (velocity_error - cs.spd_err) / dt;
+  const double raw = 3.6 * (-0.5 * velocity_gain * velocity_error -
+                            velocity_integral_gain * (integral_velocity_error + windup_gain * cs.mcl_x) - velocity_damping_gain * damping);
+  cs.spd_err = velocity_error;
+  cs.mcl_x = clip_ref(raw, -1.0, 1.0) - raw;
+  cs.throttle = low_pass_filter_ref(raw, cs.throttle, throttle_filter_constant, dt, -traction_gain * fabs(lat));
+  return cs.throttle;
+}
+
+// the filtered throttle split by sign (:318-321, :92-95); the steering is the caller's
+__device__ __forceinline__ ControlOut throttle_brake_of(double raw_throttle) {
+  ControlOut out;
+  if (raw_throttle > 0.0) {
+    out.brake = 0.0;
+    out.throttle = clip_ref(raw_throttle, 0.0, 1.0);
+  } else {
+    out.brake = clip_ref(-raw_throttle, 0.0, 1.0);
+    out.throttle = 0.0;
+  }
+  out.steering = 0.0;
+  return out;
+}
+
 __device__ inline ControlOut trajectory_tracking_pd(const VehState& s, CtrlState& cs, double dt, const PackedTraj& t) {
   const HeadingTrig trig = heading_trig(s.heading);
   const double speed = vehicle_speed(s, trig);
@@ -504,7 +569,7 @@ __device__ inline ControlOut trajectory_tracking_pd(const VehState& s, CtrlState
   const double final_steering_filter_constant = 23.5, velocity_gain = 5.1, velocity_integral_gain = 0.0,
                traction_gain = 6.0, derivative_activation = 1.0, velocity_damping_gain = 0.001, windup_gain = 0.01;
   double throttle_filter_constant = 22.5;
-  const int initial_look_ahead = 6;
+  constexpr int initial_look_ahead = 6;
   double lateral_gain = 0.61, heading_gain = 0.01, lateral_error_derivative_gain = 0.15,
          heading_error_derivative_gain = 0.5;
   const double normalized_speed = clip_ref((3.6 * t.at(3, 0) - 20.0) / (80.0 - 20.0), 0.0, 1.0);
@@ -520,19 +585,8 @@ __device__ inline ControlOut trajectory_tracking_pd(const VehState& s, CtrlState
     heading_error_derivative_gain = 0.05;
   }
   const double ahead_curvature = fabs(traj_curvature(t, 4, 5));
-  // ---- calculate_heading_lateral_error
-  const double heading_error = min_angles_difference_signed(py_mod(s.heading, SMX_TWO_PI), t.at(2, 0));
-  int look = initial_look_ahead;
-  double look_dist = (double)initial_look_ahead;
-  if (ahead_curvature < 30.0) {  // speed_reduction_activation = 1
-    look = 1;
-    look_dist = 1.0;
-  }
-  const int k = look < t.n - 1 ? look : t.n - 1;
-  double pvx, pvy;
-  radians_to_vec(t.at(2, k), pvx, pvy);
-  const double lx = s.x - look_dist * trig.sh, ly = s.y + look_dist * trig.ch;
-  const double lateral_error = signed_dist_to_line(lx, ly, t.at(0, k), t.at(1, k), pvx, pvy);
+  const TrackingErrors err = calculate_heading_lateral_error<initial_look_ahead>(s, trig, t, ahead_curvature);
+  const double heading_error = err.heading, lateral_error = err.lateral;
   // ---- steering
   const double curvature_radius = traj_curvature(t, 0, 5);
   const double derivative_term =
@@ -542,31 +596,145 @@ __device__ inline ControlOut trajectory_tracking_pd(const VehState& s, CtrlState
                                            1.0 * lateral_gain * lateral_error - feed_forward,
                                        -1.0, 1.0);
   cs.steer = low_pass_filter_ref(steering_raw, cs.steer, steering_filter_constant, dt, 0.0);
-  // ---- calculate_raw_throttle_feedback
-  double desired_speed = t.last(3);
-  if (ahead_curvature < 30.0)
-    desired_speed = clip_ref(0.8 * desired_speed, 0.0, 8.3);
-  else if (ahead_curvature < 100.0)
-    desired_speed *= 0.8;
-  const double velocity_error = speed - desired_speed;
-  const double damping = (velocity_error - cs.spd_err) / dt;
-  const double raw = 3.6 * (-0.5 * velocity_gain * velocity_error -
-                            velocity_integral_gain * (cs.spd_int + windup_gain * cs.mcl_x) - velocity_damping_gain * damping);
-  cs.spd_err = velocity_error;
-  cs.mcl_x = clip_ref(raw, -1.0, 1.0) - raw;
-  cs.throttle = low_pass_filter_ref(raw, cs.throttle, throttle_filter_constant, dt, -traction_gain * fabs(lat));
-  ControlOut out;
-  if (cs.throttle > 0.0) {
-    out.brake = 0.0;
-    out.throttle = clip_ref(cs.throttle, 0.0, 1.0);
-  } else {
-    out.brake = clip_ref(-cs.throttle, 0.0, 1.0);
-    out.throttle = 0.0;
-  }
+  double desired_speed;
+  const double raw_throttle =
+      calculate_raw_throttle_feedback(cs, t, speed, lat, ahead_curvature, velocity_gain, velocity_integral_gain, cs.spd_int,
+                                      velocity_damping_gain, windup_gain, traction_gain, throttle_filter_constant, dt, desired_speed);
+  ControlOut out = throttle_brake_of(raw_throttle);
   out.steering = cs.steer;
   cs.mcl_y = heading_error;
   cs.lat_int = lateral_error;
   cs.spd_int += (speed - desired_speed) * dt;
+  return out;
+}
+
+// ---------------------------------------------------------------------------------
+// ActionSpaceType.MPC: TrajectoryTrackingController.perform_trajectory_tracking_MPC (:56-173) with mpc_drift_matrix
+// (:476-521) and MPC (:523-609) at prediction_horizon 5, for the sedan: chassis mass and yaw inertia
+// (chassis.py:594-599, models/vehicle.urdf) and the tyre model's cornering stiffnesses (models/tire_parameters.yaml).
+//
+// MPC() is the closed form of an unconstrained problem: with A = I + dt S, B = dt b, the stacked matrices
+// M = [A; A^2; ..; A^5] and C (block row k, block column j <= k: A^(k-j) B), Q = 0.1 diag(354, 0, 14, 250) per stage,
+//   H = C'QC + I,  F = C'QM,  F1 = C'Q T~,   u = (2H)^-1 (F x0 + F1),   steering = -clip(-u[0], -1, 1).
+// C is block-Toeplitz in the five vectors g_k = A^k B, so H needs their Gram matrix g_a'Q g_b only, and M, T~ enter
+// through the vectors A^(k+1) x0 and A^k (dt drift[:, 0]): neither the 20 x 5 nor the 20 x 4 array is formed (F x0 is
+// evaluated as C'Q (M x0)).  In T~ the reference hands the drift column i + 1 to np.matmul as its out= argument
+// (:556-566), so every further block is A times the one before and the drift columns 1..4 (curvature(trajectory, i),
+// i = 0..3) never reach the result; they are not evaluated here.  x0 = (lateral_error, 0, heading_error, 0).  S has a
+// zero first column and the rows (0, 1, 0, 0), (0, 0, 0, 1): A v is written without the products by those zeros and
+// ones.  2H is symmetric positive definite (eigenvalues >= 2): eliminated from the last unknown upwards, without
+// pivoting, which leaves u[0] with no back-substitution.
+// The state matrices take max(0.1, longitudinal speed), the drift vector the speed itself (:96-99, :489).
+// Controller state: velocity_error, integral_windup_error and throttle_state in the PD's slots (spd_err, mcl_x,
+// throttle); the law reads no other state.  `steer` takes the steering command: it is the steer motor's target,
+// which an agent that sends no action on a later tick keeps (idle_command), as for the Continuous space.
+// ---------------------------------------------------------------------------------
+#define SMX_MPC_HORIZON 5
+#define SMX_TIRE_C_ALPHA_FRONT 25000.0
+#define SMX_TIRE_C_ALPHA_REAR 25000.0
+
+struct Vec4 {
+  double a, b, c, d;
+};
+
+__device__ inline ControlOut trajectory_tracking_mpc(const VehState& s, CtrlState& cs, double dt, const PackedTraj& t) {
+  const HeadingTrig trig = heading_trig(s.heading);
+  const double speed = vehicle_speed(s, trig);
+  double lng, lat;
+  long_lat_speed(s, trig, lng, lat);
+  const double ahead_curvature = fabs(traj_curvature(t, 4, 5));
+  const TrackingErrors err = calculate_heading_lateral_error<3>(s, trig, t, ahead_curvature);
+  double desired_speed;
+  const double raw_throttle = calculate_raw_throttle_feedback(cs, t, speed, lat, ahead_curvature, 1.0, 0.0, 0.0, 0.0, 0.0, 8.0,
+                                                              10.0, dt, desired_speed);
+  ControlOut out = throttle_brake_of(raw_throttle);
+
+  const double L = 0.5 * SMX_CHASSIS_LENGTH, M = 2356.0, IZ = 2681.95008628;
+  const double CF = SMX_TIRE_C_ALPHA_FRONT, CR = SMX_TIRE_C_ALPHA_REAR;
+  const double v = fmax(0.1, lng);
+  // A = I + dt * state_matrix: rows 1 and 3 beyond the zero first column (rows 0 and 2 are (1, dt, 0, 0), (0, 0, 1, dt))
+  const double a11 = 1.0 + dt * (-(CF + CR) / (M * v)), a12 = 0.0 + dt * ((CF + CR) / M), a13 = 0.0 + dt * (L * (CF + CR) / (M * v));
+  const double a31 = 0.0 + dt * (L * (-CF + CR) / (M * v)), a32 = 0.0 + dt * (L * (CF - CR) / M),
+               a33 = 1.0 + dt * ((L * L) * (CF - CR) / (M * v));
+  auto mul_a = [&](const Vec4& x) {
+    Vec4 y;
+    y.a = x.a + dt * x.b;
+    y.b = a11 * x.b + a12 * x.c + a13 * x.d;
+    y.c = x.c + dt * x.d;
+    y.d = a31 * x.b + a32 * x.c + a33 * x.d;
+    return y;
+  };
+  // stage weights 0.1 * diag(354, 0, 14, 250): the lateral velocity carries none
+  const double q0 = 0.1 * 354.0, q2 = 0.1 * 14.0, q3 = 0.1 * 250.0;
+  auto dot_q = [&](const Vec4& x, const Vec4& y) { return q0 * x.a * y.a + q2 * x.c * y.c + q3 * x.d * y.d; };
+
+  // g[k] = A^k B
+  Vec4 g[SMX_MPC_HORIZON];
+  g[0].a = 0.0;
+  g[0].b = dt * (CF / M);
+  g[0].c = 0.0;
+  g[0].d = dt * (CR / IZ);
+#pragma unroll
+  for (int k = 1; k < SMX_MPC_HORIZON; ++k) g[k] = mul_a(g[k - 1]);
+  // z[k] = A^(k+1) x0 + A^k (dt * drift column 0)
+  const double inv_curvature = 1.0 / traj_curvature(t, 0, 5);  // (`** -1` of the 1e20 sentinel: a plain division)
+  Vec4 x0, td;
+  x0.a = err.lateral;
+  x0.b = 0.0;
+  x0.c = err.heading;
+  x0.d = 0.0;
+  td.a = dt * (inv_curvature * 0.0);
+  td.b = dt * (inv_curvature * ((L * CF + L * CR) / M - lng * lng));
+  td.c = dt * (inv_curvature * 0.0);
+  td.d = dt * (inv_curvature * (((L * L) * CF - (L * L) * CR) / IZ));
+  Vec4 z[SMX_MPC_HORIZON];
+#pragma unroll
+  for (int k = 0; k < SMX_MPC_HORIZON; ++k) {
+    x0 = mul_a(x0);
+    if (k > 0) td = mul_a(td);
+    z[k].a = x0.a + td.a;
+    z[k].b = x0.b + td.b;
+    z[k].c = x0.c + td.c;
+    z[k].d = x0.d + td.d;
+  }
+  // rhs = C'Q z;  H2 = 2 (C'QC + I), lower triangle
+  double rhs[SMX_MPC_HORIZON], H2[SMX_MPC_HORIZON][SMX_MPC_HORIZON];
+#pragma unroll
+  for (int i = 0; i < SMX_MPC_HORIZON; ++i) {
+    double acc = 0.0;
+#pragma unroll
+    for (int k = i; k < SMX_MPC_HORIZON; ++k) acc += dot_q(g[k - i], z[k]);
+    rhs[i] = acc;
+  }
+  double gram[SMX_MPC_HORIZON][SMX_MPC_HORIZON];  // g_a'Q g_b, a >= b
+#pragma unroll
+  for (int a = 0; a < SMX_MPC_HORIZON; ++a)
+#pragma unroll
+    for (int b = 0; b <= a; ++b) gram[a][b] = dot_q(g[a], g[b]);
+#pragma unroll
+  for (int i = 0; i < SMX_MPC_HORIZON; ++i)
+#pragma unroll
+    for (int j = 0; j <= i; ++j) {
+      double acc = 0.0;
+#pragma unroll
+      for (int k = i; k < SMX_MPC_HORIZON; ++k) acc += gram[k - j][k - i];
+      H2[i][j] = 2.0 * (acc + (i == j ? 1.0 : 0.0));
+    }
+  // eliminate unknowns 4, 3, 2, 1 (symmetric: only the lower triangle is kept)
+#pragma unroll
+  for (int p = SMX_MPC_HORIZON - 1; p >= 1; --p) {
+    const double inv_pivot = 1.0 / H2[p][p];
+#pragma unroll
+    for (int i = 0; i < p; ++i) {
+      const double f = H2[p][i] * inv_pivot;
+#pragma unroll
+      for (int j = 0; j <= i; ++j) H2[i][j] -= f * H2[p][j];
+      rhs[i] -= f * rhs[p];
+    }
+  }
+  const double u0 = rhs[0] / H2[0][0];
+  out.steering = -clip_ref(-u0, -1.0, 1.0);
+  cs.steer = out.steering;
   return out;
 }
 

@@ -65,7 +65,8 @@ class SimConfig:
     social_speed_factor: float = 0.8
     social_model: str = "constant"  # "constant" | "idm" (include/smx.h SMX_SOCIAL_*)
     # ActionSpaceType name: Lane | Continuous | ActuatorDynamic | LaneWithContinuousSpeed | Trajectory | TargetPose |
-    # TrajectoryWithTime (the last two: kinematic agents, placed by a provider instead of driven through a controller)
+    # TrajectoryWithTime | MPC | Imitation (TargetPose, TrajectoryWithTime and Imitation: kinematic agents, placed by a
+    # provider or by the Imitation controller instead of driven through a control law and the dynamics model)
     action_space: str = "Lane"
     launch_strategy: str = "auto"  # "auto" | "small" | "large": how a tick is cut into launches (include/smx.h)
     # RoadWaypoints (agent_interface.py RoadWaypoints.horizon = 32; sensors.py:991-1040): dense rows keep the first
@@ -537,8 +538,8 @@ class BatchedSim:
     def step(self, actions: torch.Tensor) -> Dict[str, torch.Tensor]:
         if not self._was_reset:
             raise RuntimeError("step() before reset()")  # SMARTSNotSetupError (smarts.py:207-208)
-        if self.cfg.action_space == "Trajectory":
-            raise ValueError("ActionSpaceType.Trajectory steps through step_trajectory(trajectories, counts)")
+        if self.cfg.action_space in ("Trajectory", "MPC"):
+            raise ValueError(f"ActionSpaceType.{self.cfg.action_space} steps through step_trajectory(trajectories, counts)")
         if self.cfg.action_space == "TargetPose":
             raise ValueError("ActionSpaceType.TargetPose steps through step_target_pose(targets)")
         if self.cfg.action_space == "TrajectoryWithTime":
@@ -560,7 +561,8 @@ class BatchedSim:
                                    C.byref(self._out), self._stream_ptr())
             nat.check(self.lib, self.handle, rc, "smx_step")
         else:
-            # three floats per agent; NaN in the first one = no action this tick
+            # three floats per agent; NaN in the first one = no action this tick (Imitation: acceleration, angular
+            # velocity, -; a NaN angular velocity = the scalar form, the first float a speed to set)
             rc = self.lib.smx_step_continuous(self.handle, actions.data_ptr(), C.byref(self._st), C.byref(self._sp),
                                               C.byref(self._out), self._stream_ptr())
             nat.check(self.lib, self.handle, rc, "smx_step_continuous")
@@ -579,12 +581,13 @@ class BatchedSim:
         (``out["ec_flags"] == 0``), without an action and social slots are copied through."""
         if not self.cfg.ego_centric:
             raise ValueError("actions_to_world needs SimConfig(ego_centric=True)")
-        if space not in ("Trajectory", "TargetPose", "TrajectoryWithTime"):
+        if space not in ("Trajectory", "MPC", "TargetPose", "TrajectoryWithTime"):
             raise ValueError(f"{space} actions hold no position or heading: they are the same in either frame")
         if space != self.cfg.action_space:
             raise ValueError(f"actions_to_world({space!r}) on a {self.cfg.action_space} batch")
         actions = actions.to(device=self.device, dtype=torch.float64).contiguous()
-        want = {"Trajectory": (self.E, self.N, 4, nat.TRAJ_COLS), "TargetPose": (self.E, self.N, 4),
+        want = {"Trajectory": (self.E, self.N, 4, nat.TRAJ_COLS), "MPC": (self.E, self.N, 4, nat.TRAJ_COLS),
+                "TargetPose": (self.E, self.N, 4),
                 "TrajectoryWithTime": (self.E, self.N, 5) + tuple(actions.shape[3:4])}[space]
         if tuple(actions.shape) != want or (space == "TrajectoryWithTime" and (actions.ndim != 4 or actions.shape[3] < 2)):
             raise ValueError(f"{space} actions must have shape {want}, got {tuple(actions.shape)}")
@@ -605,15 +608,15 @@ class BatchedSim:
 
     def step_trajectory(self, trajectories: torch.Tensor, counts: torch.Tensor,
                         ego_centric: bool = False) -> Dict[str, torch.Tensor]:
-        """One tick in ActionSpaceType.Trajectory: ``trajectories`` float64 [E, N, 4, 11] in the packed
+        """One tick in ActionSpaceType.Trajectory or ActionSpaceType.MPC: ``trajectories`` float64 [E, N, 4, 11] in the packed
         form of include/smx.h (``pack_trajectory``), ``counts`` int32 [E, N] (0 = no action).  ``ego_centric``: the
         trajectories are in the frame of each agent's last observation (``actions_to_world`` first)."""
         if not self._was_reset:
             raise RuntimeError("step() before reset()")
-        if self.cfg.action_space != "Trajectory":
-            raise ValueError("step_trajectory needs SimConfig(action_space='Trajectory')")
+        if self.cfg.action_space not in ("Trajectory", "MPC"):
+            raise ValueError("step_trajectory needs SimConfig(action_space='Trajectory') or 'MPC'")
         if ego_centric:
-            trajectories = self.actions_to_world("Trajectory", trajectories, counts)
+            trajectories = self.actions_to_world(self.cfg.action_space, trajectories, counts)
         trajectories = trajectories.to(device=self.device, dtype=torch.float64).contiguous()
         counts = counts.to(device=self.device, dtype=torch.int32).contiguous()
         assert trajectories.shape == (self.E, self.N, 4, nat.TRAJ_COLS) and counts.shape == (self.E, self.N)
