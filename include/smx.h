@@ -90,7 +90,22 @@ enum {
    * smarts/core/utils/math.py:452-505) on the device: every position and heading of this pass's ego, waypoint,
    * neighbour, lidar and road-waypoint rows (those whose sensors are on) in the frame of the agent's own vehicle,
    * written beside the world rows (smx_outputs.ego_frame, ec_*), and the frame kept for smx_actions_to_world. */
-  SMX_SENSOR_EGO_CENTRIC = 1 << 8
+  SMX_SENSOR_EGO_CENTRIC = 1 << 8,
+  /* The top-down RGB camera (RGB of agent_interface.py; sensors.py:761-794 over renderer.py:346-395): the OGM's and the
+   * DAGM's orthographic camera — centred on the vehicle, up its heading, row 0 ahead — over a black clear colour, with
+   * the two substitutions those grids already have.  The image is [rgb_height][rgb_width][3] uint8; pixel centres are
+   * the OGM's.  Every pixel gets the HIGHEST class that holds for its centre:
+   *   0  none of the below                                                                        bytes   0,   0,   0
+   *   1  within half a lane width of a segment of that lane's centre line (the DAGM's test, every
+   *      lane, junction-internal lanes included): SceneColors.Road, colors.py:62                  bytes  80,  80,  80
+   *   2  inside the chassis rectangle of an alive social vehicle of the env (the OGM's test):
+   *      Silver, colors.py:60                                                                     bytes 192, 192, 192
+   *   3  inside the chassis rectangle of an alive agent vehicle of the env, the observer included:
+   *      SceneColors.Agent, colors.py:58                                                          bytes 210,  30,  30
+   * (the vehicles stand above the road; where two vehicles overlap, "agent over social" is this path's rule,
+   * DESIGN.md).  The image is not part of smx_outputs: the caller binds its buffer with smx_set_rgb_output.  The image
+   * of an agent without an observation in the pass is not written. */
+  SMX_SENSOR_RGB = 1 << 9
 };
 #define SMX_TTC_MAX_WAYPOINTS 512
 
@@ -187,6 +202,10 @@ typedef struct smx_config {
   int32_t rw_horizon;        /* 1 .. SMX_RW_HORIZON_MAX; read when SMX_SENSOR_ROAD_WAYPOINTS is set */
   int32_t rw_lanes;
   int32_t rw_paths;
+  /* SMX_SENSOR_RGB (agent_interface.py RGB: 256 x 256 at 50 / 256): the grid of the top-down RGB image; width * height
+   * a multiple of 16 and at most 65536 (the class tile of one image is staged in LDS) */
+  int32_t rgb_width, rgb_height;
+  double rgb_resolution;
 } smx_config;
 #define SMX_RW_LANE_CAP 8
 #define SMX_RW_HORIZON_MAX 64
@@ -562,6 +581,14 @@ int smx_set_mission_goals(smx_handle h, const smx_mission_goal* goals_host, int3
                           const double* lane_end_heading_host, const int32_t* lane_dead_end_host, int32_t n_lanes);
 /* Base ray directions (device, [lidar_rays][3]); reference lidar.py:89-113 */
 int smx_set_lidar_rays(smx_handle h, const double* rays_dev, int32_t n_rays);
+/* The image buffer of SMX_SENSOR_RGB (device, caller-owned, [E*N][rgb_height][rgb_width][3] uint8; `count` = the bytes
+ * allocated; 16-byte aligned: the image is written with 16-byte stores).  It may be called again between ticks to alternate buffers; NULL unbinds.  A buffer shorter than the
+ * configuration implies is SMX_ERR_INVALID (it would be an out-of-bounds device write); smx_reset / smx_step* with the
+ * sensor on and no buffer bound return SMX_ERR_STATE.  smx_check_rgb_output is the validation alone, callable without a
+ * device or a handle: the bit against the grid, the grid limits, and `count` against E * N * rgb_height * rgb_width * 3
+ * (with the bit off any count passes).  SMX_OK, or SMX_ERR_INVALID with the reason in err[err_len]. */
+int smx_set_rgb_output(smx_handle h, uint8_t* rgb_dev, uint64_t count);
+int smx_check_rgb_output(const smx_config* cfg, uint64_t count, char* err, uint64_t err_len);
 /* Re-initialise the envs whose mask byte is non-zero (NULL = all) from the spawn
  * table and produce their first observations. */
 int smx_reset(smx_handle h, const uint8_t* env_mask_dev, const smx_state* st, const smx_spawns* sp,
@@ -625,7 +652,7 @@ int smx_sync(smx_handle h, void* hip_stream);
 enum {
   SMX_PHASE_CONTROL = 0, /* k_control: controllers + vehicle dynamics (a1-a6)            */
   SMX_PHASE_SCAN,        /* k_scan: road facts + lanepoint seeds (a8, a9 front half)      */
-  SMX_PHASE_OGM,         /* k_ogm (a14) and k_dagm                                        */
+  SMX_PHASE_OGM,         /* k_ogm (a14), k_dagm and k_rgb                                 */
   SMX_PHASE_SENSORS,     /* k_sensors: waypoints | observe | lidar roles (a7, a9-a13, a15) */
   SMX_PHASE_COMMIT,      /* k_commit: flags, env done count, auto-reset respawn           */
   SMX_PHASE_RESET,       /* auto-reset pass (parallel_env.py:303-309), all kernels        */

@@ -31,6 +31,7 @@ SENSOR_WAYPOINTS, SENSOR_NEIGHBORS, SENSOR_ACCELEROMETER, SENSOR_OGM, SENSOR_LID
 SENSOR_ROAD_WAYPOINTS = 64
 SENSOR_LANE_TTC = 128
 SENSOR_EGO_CENTRIC = 256  # smx_outputs.ego_frame / ec_* (the ego-centric adapters on the device)
+SENSOR_RGB = 512  # the top-down RGB image, bound with smx_set_rgb_output (not part of smx_outputs)
 EC_VALID = 1  # smx_outputs.ec_flags bit 0
 # columns of smx_outputs.lane_ttc (SMX_TTC_*; "TTC" and "DTC" head three columns: right, current, left lane) and the
 # bits of smx_outputs.lane_ttc_flags
@@ -68,6 +69,7 @@ class SmxConfig(C.Structure):
         ("alive_list_mask", C.c_uint64 * 4),
         ("dagm_width", _i32), ("dagm_height", _i32), ("dagm_resolution", _f64),
         ("social_model", _i32), ("rw_horizon", _i32), ("rw_lanes", _i32), ("rw_paths", _i32),
+        ("rgb_width", _i32), ("rgb_height", _i32), ("rgb_resolution", _f64),
     ]
 
 
@@ -162,7 +164,7 @@ EXPORTS = [
     "smx_create", "smx_load_map", "smx_set_vias", "smx_set_missions", "smx_step_continuous", "smx_step_trajectory", "smx_read_phase_ms", "smx_set_lidar_rays", "smx_reset", "smx_step", "smx_sync", "smx_last_step_ms",
     "smx_set_timing", "smx_last_error", "smx_version", "smx_destroy", "smx_set_controller_gains", "smx_struct_size", "smx_read_step_ms",
     "smx_check_buffers", "smx_set_launch_strategy", "smx_launch_form", "smx_step_target_pose", "smx_step_trajectory_with_time",
-    "smx_set_mission_goals", "smx_check_mission_goals", "smx_actions_to_world",
+    "smx_set_mission_goals", "smx_check_mission_goals", "smx_actions_to_world", "smx_set_rgb_output", "smx_check_rgb_output",
 ]
 LAUNCH_FORMS = {0: "small", 1: "large_teams", 2: "large_one_lane"}
 LAUNCH_STRATEGIES = {"auto": 0, "small": 1, "large": 2, "large_one_lane": 3, "large_teams": 4}
@@ -234,6 +236,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.smx_step_trajectory_with_time.restype = C.c_int
     lib.smx_actions_to_world.argtypes = [h, _i32, _p, _p, _i32, _p, C.POINTER(SmxOutputs), _p]
     lib.smx_actions_to_world.restype = C.c_int
+    lib.smx_set_rgb_output.argtypes = [h, _p, C.c_uint64]
+    lib.smx_set_rgb_output.restype = C.c_int
+    lib.smx_check_rgb_output.argtypes = [C.POINTER(SmxConfig), C.c_uint64, C.c_char_p, C.c_uint64]
+    lib.smx_check_rgb_output.restype = C.c_int
     lib.smx_read_phase_ms.argtypes = [h, C.POINTER(C.c_float), _i32, C.POINTER(_i32)]
     lib.smx_read_phase_ms.restype = C.c_int
     lib.smx_set_timing.argtypes = [h, C.c_int]

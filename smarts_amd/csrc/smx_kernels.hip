@@ -71,6 +71,7 @@ struct KernelArgs {
   int debug_skip;
   int wp_blocks, obs_blocks, lidar_blocks;  // k_sensors: workgroups per role (OGM takes the rest)
   double dagm_reach;        // widest lane's half width (which segments can touch a DAGM view)
+  uint8_t* rgb;             // SMX_SENSOR_RGB: the image buffer bound by smx_set_rgb_output, [E*N][rgb_height][rgb_width][3]
   KnotLists knots;          // library-owned hand-off: k_wp_walk -> k_waypoints_tables
   MissionsDev missions;     // device copy of smx_set_missions (null pointers: every mission endless)
   // large batches: the tick's alive vehicles, compacted by k_alive_list at the start of the tick (null: launch
@@ -3845,6 +3846,53 @@ struct OgmMate {
   int c0, r0, bw, n_px;               // pixel rectangle: first column / row, width, pixel count
 };
 
+// Vehicle `og`'s footprint in the frame of the observer at (ex0, ey0) with right axis (rx, ry) and forward axis
+// (fx, fy), and the pixel rectangle of a W x H grid that can hold it; false (q untouched): the rectangle misses the view.
+__device__ __forceinline__ bool ogm_mate_footprint(const KernelArgs& a, const size_t og, const size_t total, const int W, const int H,
+                                                   const double res, const double ex0, const double ey0, const double rx, const double ry,
+                                                   const double fx, const double fy, OgmMate& q) {
+  const double hl = 0.5 * SMX_CHASSIS_LENGTH, hw = 0.5 * SMX_CHASSIS_WIDTH;
+  const double vx = a.st.f64[(size_t)SMX_S_X * total + og], vy = a.st.f64[(size_t)SMX_S_Y * total + og];
+  const double vh = wrap_heading(a.st.f64[(size_t)SMX_S_HEADING * total + og]);
+  const double dx = vx - ex0, dy = vy - ey0;
+  const double cx = dx * rx + dy * ry, cy = dx * fx + dy * fy;  // centre in the ego frame
+  // the mate's axes in the ego frame from each vehicle's own cos / sin (the rule k_ogm_env shares)
+  const double cm = cos(vh), sm = sin(vh);
+  const double vfx = cm * ry - sm * rx, vfy = sm * ry + cm * rx, vrx = cm * rx + sm * ry, vry = sm * rx - cm * ry;
+  const double ext_x = fabs(vfx) * hl + fabs(vrx) * hw, ext_y = fabs(vfy) * hl + fabs(vry) * hw;
+  // pixel centre (r, col): x = (col + 0.5 - W/2) res, y = (H/2 - (r + 0.5)) res
+  int c0 = (int)floor((cx - ext_x) / res + 0.5 * W - 0.5) - 1, c1 = (int)ceil((cx + ext_x) / res + 0.5 * W - 0.5) + 1;
+  int r0 = (int)floor(0.5 * H - 0.5 - (cy + ext_y) / res) - 1, r1 = (int)ceil(0.5 * H - 0.5 - (cy - ext_y) / res) + 1;
+  c0 = max(c0, 0);
+  r0 = max(r0, 0);
+  c1 = min(c1, W - 1);
+  r1 = min(r1, H - 1);
+  if (c0 > c1 || r0 > r1) return false;
+  q.cx = cx;
+  q.cy = cy;
+  q.vfx = vfx;
+  q.vfy = vfy;
+  q.vrx = vrx;
+  q.vry = vry;
+  q.c0 = c0;
+  q.r0 = r0;
+  q.bw = c1 - c0 + 1;
+  q.n_px = (c1 - c0 + 1) * (r1 - r0 + 1);
+  return true;
+}
+
+// ... drawn by the workgroup's lanes over the rectangle's pixels: VALUE where the pixel centre lies inside the chassis
+template <int VALUE>
+__device__ __forceinline__ void ogm_draw_mate(unsigned char* tile, const OgmMate& q, const int W, const int H, const double res) {
+  const double hl = 0.5 * SMX_CHASSIS_LENGTH, hw = 0.5 * SMX_CHASSIS_WIDTH;
+  for (int p = (int)threadIdx.x; p < q.n_px; p += SMX_BLOCK) {
+    const int r = q.r0 + p / q.bw, col = q.c0 + p % q.bw;
+    const double py = (0.5 * H - (r + 0.5)) * res - q.cy;
+    const double px = (col + 0.5 - 0.5 * W) * res - q.cx;
+    if (fabs(px * q.vfx + py * q.vfy) <= hl && fabs(px * q.vrx + py * q.vry) <= hw) tile[r * W + col] = VALUE;
+  }
+}
+
 __device__ __forceinline__ void ogm_role(const KernelArgs& a, const int block) {
   extern __shared__ __align__(16) unsigned char tile[];
   const smx_config& c = a.cfg;
@@ -3869,55 +3917,19 @@ __device__ __forceinline__ void ogm_role(const KernelArgs& a, const int block) {
   // are drawn one after the other with the wavefront's lanes over the rectangle's pixels — a lane per
   // mate would make every lane wait for the mate with the most pixels while most lanes draw nothing.
   __shared__ OgmMate mates[SMX_BLOCK];
-  const double hl = 0.5 * SMX_CHASSIS_LENGTH, hw = 0.5 * SMX_CHASSIS_WIDTH;
   for (int base = 0; base < n_veh; base += SMX_BLOCK) {
     const int j = base + (int)threadIdx.x;
     bool in_view = false;
     if (j < n_veh) {
       const size_t og = (size_t)env * n_veh + j;
-      if (a.st.flags[og] & SMX_F_ALIVE) {
-        const double vx = a.st.f64[(size_t)SMX_S_X * total + og], vy = a.st.f64[(size_t)SMX_S_Y * total + og];
-        const double vh = wrap_heading(a.st.f64[(size_t)SMX_S_HEADING * total + og]);
-        const double dx = vx - ex0, dy = vy - ey0;
-        const double cx = dx * rx + dy * ry, cy = dx * fx + dy * fy;  // centre in the ego frame
-        // the mate's axes in the ego frame from each vehicle's own cos / sin (the rule k_ogm_env shares)
-        const double cm = cos(vh), sm = sin(vh);
-        const double vfx = cm * ry - sm * rx, vfy = sm * ry + cm * rx, vrx = cm * rx + sm * ry, vry = sm * rx - cm * ry;
-        const double ext_x = fabs(vfx) * hl + fabs(vrx) * hw, ext_y = fabs(vfy) * hl + fabs(vry) * hw;
-        // pixel centre (r, col): x = (col + 0.5 - W/2) res, y = (H/2 - (r + 0.5)) res
-        int c0 = (int)floor((cx - ext_x) / res + 0.5 * W - 0.5) - 1, c1 = (int)ceil((cx + ext_x) / res + 0.5 * W - 0.5) + 1;
-        int r0 = (int)floor(0.5 * H - 0.5 - (cy + ext_y) / res) - 1, r1 = (int)ceil(0.5 * H - 0.5 - (cy - ext_y) / res) + 1;
-        c0 = max(c0, 0);
-        r0 = max(r0, 0);
-        c1 = min(c1, W - 1);
-        r1 = min(r1, H - 1);
-        if (c0 <= c1 && r0 <= r1) {
-          in_view = true;
-          OgmMate& q = mates[threadIdx.x];
-          q.cx = cx;
-          q.cy = cy;
-          q.vfx = vfx;
-          q.vfy = vfy;
-          q.vrx = vrx;
-          q.vry = vry;
-          q.c0 = c0;
-          q.r0 = r0;
-          q.bw = c1 - c0 + 1;
-          q.n_px = (c1 - c0 + 1) * (r1 - r0 + 1);
-        }
-      }
+      if (a.st.flags[og] & SMX_F_ALIVE) in_view = ogm_mate_footprint(a, og, total, W, H, res, ex0, ey0, rx, ry, fx, fy, mates[threadIdx.x]);
     }
     unsigned long long todo = __ballot(in_view);
     __syncthreads();
     while (todo != 0ull) {  // uniform
       const OgmMate q = mates[__ffsll((long long)todo) - 1];
       todo &= todo - 1ull;
-      for (int p = (int)threadIdx.x; p < q.n_px; p += SMX_BLOCK) {
-        const int r = q.r0 + p / q.bw, col = q.c0 + p % q.bw;
-        const double py = (0.5 * H - (r + 0.5)) * res - q.cy;
-        const double px = (col + 0.5 - 0.5 * W) * res - q.cx;
-        if (fabs(px * q.vfx + py * q.vfy) <= hl && fabs(px * q.vrx + py * q.vry) <= hw) tile[r * W + col] = 255;
-      }
+      ogm_draw_mate<255>(tile, q, W, H, res);
     }
     __syncthreads();  // before the stage is reused (envs of more than 64 vehicles do not exist, but the loop is general)
   }
@@ -4092,24 +4104,13 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(SMX
 // Wavefronts take segments, lanes the pixels of a segment's bounding box; a segment listed in
 // several cells is drawn again (same value).
 // =================================================================================
-__device__ __forceinline__ void dagm_role(const KernelArgs& a, const int block) {
-  extern __shared__ __align__(16) unsigned char tile[];
-  const smx_config& c = a.cfg;
+// The road layer of a W x H tile for the observer at (ex0, ey0): VALUE where the pixel centre lies within half a lane
+// width of a segment (wavefronts over the segments of the grid cells the view can reach, lanes over a segment's pixels).
+template <int VALUE>
+__device__ __forceinline__ void road_layer(const KernelArgs& a, unsigned char* tile, const int W, const int H, const double res,
+                                           const double ex0, const double ey0, const double rx, const double ry, const double fx,
+                                           const double fy) {
   const MapDev& m = a.map;
-  const size_t total = (size_t)c.num_envs * c.num_vehicles;
-  const size_t gid = (size_t)block;
-  if (gid >= total) return;
-  const int flags = a.st.flags[gid];
-  const bool live = (flags & SMX_F_ALIVE) && !(flags & SMX_F_SOCIAL) && (!a.first_only || (flags & SMX_F_FIRST));
-  if (!live) return;  // uniform for the whole workgroup
-  const int W = c.dagm_width, H = c.dagm_height;
-  const int bytes = W * H;
-  for (int k = threadIdx.x; k < bytes / 4; k += SMX_BLOCK) reinterpret_cast<int*>(tile)[k] = 0;
-  __syncthreads();
-  const double res = c.dagm_resolution;
-  const double ex0 = SF(SMX_S_X), ey0 = SF(SMX_S_Y), eh = wrap_heading(SF(SMX_S_HEADING));
-  const double rx = cos(eh), ry = sin(eh);    // ego right axis
-  const double fx = -sin(eh), fy = cos(eh);   // ego forward axis
   const double vw = 0.5 * W * res, vh = 0.5 * H * res;
   const double reach = sqrt(vw * vw + vh * vh) + a.dagm_reach + 1e-6;
   int cx0 = (int)floor((ex0 - reach - m.sg_x0) / m.sg_cell), cx1 = (int)floor((ex0 + reach - m.sg_x0) / m.sg_cell);
@@ -4143,13 +4144,115 @@ __device__ __forceinline__ void dagm_role(const KernelArgs& a, const int block) 
       for (int q = lane; q < n_px; q += 64) {
         const int r = r0 + q / bw, col = c0 + q % bw;
         const double px = (col + 0.5 - 0.5 * W) * res, py = (0.5 * H - (r + 0.5)) * res;
-        if (seg_point_dist2(px, py, ax, ay, bx, by) <= hw * hw) tile[r * W + col] = 255;
+        if (seg_point_dist2(px, py, ax, ay, bx, by) <= hw * hw) tile[r * W + col] = VALUE;
       }
     }
   }
+}
+
+__device__ __forceinline__ void dagm_role(const KernelArgs& a, const int block) {
+  extern __shared__ __align__(16) unsigned char tile[];
+  const smx_config& c = a.cfg;
+  const size_t total = (size_t)c.num_envs * c.num_vehicles;
+  const size_t gid = (size_t)block;
+  if (gid >= total) return;
+  const int flags = a.st.flags[gid];
+  const bool live = (flags & SMX_F_ALIVE) && !(flags & SMX_F_SOCIAL) && (!a.first_only || (flags & SMX_F_FIRST));
+  if (!live) return;  // uniform for the whole workgroup
+  const int W = c.dagm_width, H = c.dagm_height;
+  const int bytes = W * H;
+  for (int k = threadIdx.x; k < bytes / 4; k += SMX_BLOCK) reinterpret_cast<int*>(tile)[k] = 0;
+  __syncthreads();
+  const double res = c.dagm_resolution;
+  const double ex0 = SF(SMX_S_X), ey0 = SF(SMX_S_Y), eh = wrap_heading(SF(SMX_S_HEADING));
+  const double rx = cos(eh), ry = sin(eh);    // ego right axis
+  const double fx = -sin(eh), fy = cos(eh);   // ego forward axis
+  road_layer<255>(a, tile, W, H, res, ex0, ey0, rx, ry, fx, fy);
   __syncthreads();
   int4* dst = reinterpret_cast<int4*>(a.out.dagm + gid * (size_t)bytes);
   for (int k = threadIdx.x; k < bytes / 16; k += SMX_BLOCK) dst[k] = reinterpret_cast<const int4*>(tile)[k];
+}
+
+// =================================================================================
+// RGB role: the top-down RGB camera (RGBSensor, sensors.py:761-794; the image is defined in include/smx.h): one
+// workgroup per observing vehicle, a tile of one CLASS byte a pixel in LDS — 0 nothing, 1 road, 2 social vehicle,
+// 3 agent vehicle, the highest class that holds — built from the DAGM's road layer and the OGM's footprints, the very
+// functions those roles call.  The layers are drawn lowest class first with a workgroup barrier between them, so a
+// pixel is only ever raised and plain stores do (no read-modify-write, no race that could lose the larger class).
+// Copy-out: a thread turns 16 class bytes into the 48 bytes of their pixels and stores them as three 16-byte vectors;
+// thread k's 48 bytes follow thread k - 1's, so the workgroup's stores fill one contiguous span of the image, which is
+// written exactly once.
+// =================================================================================
+#define SMX_RGB_LUT_R 0xD2C05000u   // byte c = the red byte of class c:      0, 80, 192, 210 (colors.py:58-62)
+#define SMX_RGB_LUT_GB 0x1EC05000u  // ... its green and its blue byte:       0, 80, 192,  30
+__device__ __forceinline__ unsigned rgb_of_class(const unsigned cls) {  // R | G << 8 | B << 16
+  const unsigned r = (SMX_RGB_LUT_R >> (8u * cls)) & 0xffu, gb = (SMX_RGB_LUT_GB >> (8u * cls)) & 0xffu;
+  return r | (gb << 8) | (gb << 16);
+}
+
+__device__ __forceinline__ void rgb_role(const KernelArgs& a, const int block) {
+  extern __shared__ __align__(16) unsigned char tile[];
+  const smx_config& c = a.cfg;
+  const size_t total = (size_t)c.num_envs * c.num_vehicles;
+  const size_t gid = (size_t)block;
+  if (gid >= total) return;
+  const int flags = a.st.flags[gid];
+  const bool live = (flags & SMX_F_ALIVE) && !(flags & SMX_F_SOCIAL) && (!a.first_only || (flags & SMX_F_FIRST));
+  if (!live) return;  // uniform for the whole workgroup
+  const int W = c.rgb_width, H = c.rgb_height;
+  const int n_veh = c.num_vehicles;
+  const int env = (int)(gid / n_veh);
+  const int bytes = W * H;
+  for (int k = threadIdx.x; k < bytes / 4; k += SMX_BLOCK) reinterpret_cast<int*>(tile)[k] = 0;
+  __syncthreads();
+  const double res = c.rgb_resolution;
+  const double ex0 = SF(SMX_S_X), ey0 = SF(SMX_S_Y), eh = wrap_heading(SF(SMX_S_HEADING));
+  const double rx = cos(eh), ry = sin(eh);    // ego right axis
+  const double fx = -sin(eh), fy = cos(eh);   // ego forward axis
+  road_layer<1>(a, tile, W, H, res, ex0, ey0, rx, ry, fx, fy);
+  __syncthreads();
+  // the env's alive vehicles, the observer among them: the social ones (class 2), then the agents (class 3)
+  __shared__ OgmMate mates[SMX_BLOCK];
+  for (int cls = 2; cls <= 3; ++cls) {
+    for (int base = 0; base < n_veh; base += SMX_BLOCK) {
+      const int j = base + (int)threadIdx.x;
+      bool in_view = false;
+      if (j < n_veh) {
+        const size_t og = (size_t)env * n_veh + j;
+        const int f = a.st.flags[og];
+        if ((f & SMX_F_ALIVE) && ((f & SMX_F_SOCIAL) != 0) == (cls == 2))
+          in_view = ogm_mate_footprint(a, og, total, W, H, res, ex0, ey0, rx, ry, fx, fy, mates[threadIdx.x]);
+      }
+      unsigned long long todo = __ballot(in_view);
+      __syncthreads();
+      while (todo != 0ull) {  // uniform
+        const OgmMate q = mates[__ffsll((long long)todo) - 1];
+        todo &= todo - 1ull;
+        if (cls == 2)
+          ogm_draw_mate<2>(tile, q, W, H, res);
+        else
+          ogm_draw_mate<3>(tile, q, W, H, res);
+      }
+      __syncthreads();  // the stage is reused, and the next class goes on top of this one
+    }
+  }
+  uint4* dst = reinterpret_cast<uint4*>(a.rgb + gid * (size_t)bytes * 3);
+  for (int k = threadIdx.x; k < bytes / 16; k += SMX_BLOCK) {
+    const uint4 cls4 = reinterpret_cast<const uint4*>(tile)[k];
+    const unsigned cw[4] = {cls4.x, cls4.y, cls4.z, cls4.w};
+    unsigned w[12];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {  // four pixels -> twelve bytes: R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
+      const unsigned p0 = rgb_of_class(cw[g] & 3u), p1 = rgb_of_class((cw[g] >> 8) & 3u);
+      const unsigned p2 = rgb_of_class((cw[g] >> 16) & 3u), p3 = rgb_of_class((cw[g] >> 24) & 3u);
+      w[3 * g] = p0 | (p1 << 24);
+      w[3 * g + 1] = (p1 >> 8) | (p2 << 16);
+      w[3 * g + 2] = (p2 >> 16) | (p3 << 8);
+    }
+    dst[3 * k] = make_uint4(w[0], w[1], w[2], w[3]);
+    dst[3 * k + 1] = make_uint4(w[4], w[5], w[6], w[7]);
+    dst[3 * k + 2] = make_uint4(w[8], w[9], w[10], w[11]);
+  }
 }
 
 // =================================================================================
@@ -4409,6 +4512,7 @@ __global__ void __launch_bounds__(SMX_FIRST_BLOCK) k_first(const KernelArgs a, c
 // in spills than it won: +20 % on loop 4096 x 32) and OGM tiles too large to ride along as dynamic LDS of every k_sensors workgroup
 __global__ void __launch_bounds__(SMX_BLOCK) k_ogm(const KernelArgs a) { ogm_role(a, (int)blockIdx.x); }
 __global__ void __launch_bounds__(SMX_BLOCK) k_dagm(const KernelArgs a) { dagm_role(a, (int)blockIdx.x); }
+__global__ void __launch_bounds__(SMX_BLOCK) k_rgb(const KernelArgs a) { rgb_role(a, (int)blockIdx.x); }
 // =================================================================================
 // k_road_waypoints: RoadWaypointsSensor (sensors.py:991-1040).  SMX_RW_LANE_CAP lanes of a wavefront share a
 // vehicle: every lane of the team builds the sensor's lane list for itself (the same serial steps, so the
@@ -4929,7 +5033,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_actions_to_world(const double* __
 // =================================================================================
 // k_tail: the end of every pass, one wavefront per env group (those of the observe role), in one launch:
 //  - the tick's commit (commit_role: teardown, done counts, auto-reset respawn);
-//  - the OGM / DAGM tiles of the group's new vehicles (respawned just now, or by k_reset), one after the other — almost
+//  - the OGM / DAGM / RGB tiles of the group's new vehicles (respawned just now, or by k_reset), one after the other — almost
 //    no group has any, and a group looks at its flags with one load and a ballot;
 //  - the env groups with new vehicles, listed for k_first (the reset pass), one atomic per such group;
 //  - large batches: the next tick's alive list (seg_position), built here instead of by a k_alive_list launch at the
@@ -4941,7 +5045,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_actions_to_world(const double* __
 // =================================================================================
 struct TailArgs {
   int commit;              // the tick's commit (0: smx_reset, which has no tick)
-  int grids;               // OGM / DAGM tiles of the new vehicles
+  int grids;               // OGM / DAGM / RGB tiles of the new vehicles
   int32_t* groups;         // env groups with new vehicles (for k_first)
   int32_t* n_groups;
   int32_t* n_groups_next;  // zeroed: the next pass's counter
@@ -4986,6 +5090,10 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_tail(const KernelArgs a, const Ta
         }
         if (c.sensors & SMX_SENSOR_DAGM) {
           dagm_role(a, (int)(g0 + j));
+          __syncthreads();
+        }
+        if (c.sensors & SMX_SENSOR_RGB) {
+          rgb_role(a, (int)(g0 + j));
           __syncthreads();
         }
       }
@@ -5184,6 +5292,8 @@ struct smx_handle_s {
   int group_parity;  // k_tail's counter of env groups with new vehicles (the other one is zero)
   bool map_junctions;  // lanes of the map split (some lanepoint has several successors)
   double dagm_reach;  // half the widest lane width of the loaded map
+  uint8_t* rgb_out;   // smx_set_rgb_output: the caller's image buffer (null: none bound) and the bytes it holds
+  uint64_t rgb_count;
   int debug_skip;
   int launch_strategy;  // SMX_LAUNCH_*
   bool timing;
@@ -5279,6 +5389,15 @@ static const char* lane_ttc_config_error(const smx_config& c) {
   return nullptr;
 }
 
+// SMX_SENSOR_RGB's grid: the DAGM's limits (smx_create and smx_check_rgb_output both ask)
+static const char* rgb_config_error(const smx_config& c) {
+  if (!(c.sensors & SMX_SENSOR_RGB)) return nullptr;
+  if (c.rgb_width < 1 || c.rgb_height < 1 || ((int64_t)c.rgb_width * c.rgb_height) % 16 != 0 ||
+      (int64_t)c.rgb_width * c.rgb_height > 64 * 1024 || !(c.rgb_resolution > 0.0))
+    return "rgb: need width*height a multiple of 16 and at most 65536 (the class tile of an image is staged in LDS), resolution > 0";
+  return nullptr;
+}
+
 static int create_impl(const smx_config* cfg, int device, smx_handle* out) {
   smx_handle h = new (std::nothrow) smx_handle_s();
   if (!h) return SMX_ERR_NOMEM;
@@ -5305,6 +5424,8 @@ static int create_impl(const smx_config* cfg, int device, smx_handle* out) {
   h->status_dev = nullptr;
   h->side_ready = false;
   h->lidar_rays = nullptr;
+  h->rgb_out = nullptr;
+  h->rgb_count = 0;
   // lane_following_controller.py:426-430: place_poles gains clipped to [0.02, 0.04] / [3.4, 4.1];
   // for the sedan they saturate at (0.04, 3.4) for both Lane-space target speeds.
   h->heading_gain_pos = 0.04;
@@ -5365,6 +5486,7 @@ static int create_impl(const smx_config* cfg, int device, smx_handle* out) {
   if ((c.sensors & SMX_SENSOR_NEIGHBORS) && (c.nb_max < 1 || c.nb_max > 127))
     return fail(h, SMX_ERR_INVALID, "neighbours: need 1 <= nb_max <= 127");
   if (const char* why = lane_ttc_config_error(c)) return fail(h, SMX_ERR_INVALID, why);
+  if (const char* why = rgb_config_error(c)) return fail(h, SMX_ERR_INVALID, why);
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return fail(h, SMX_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
   return SMX_OK;
@@ -5995,12 +6117,64 @@ extern "C" int smx_check_buffers(const smx_config* cfg, int has_vias, const smx_
   return rc;
 }
 
+static int check_rgb_output_impl(const smx_config& c, uint64_t count, std::string& err) {
+  if (const char* why = rgb_config_error(c)) {
+    err = why;
+    return SMX_ERR_INVALID;
+  }
+  if (!(c.sensors & SMX_SENSOR_RGB)) return SMX_OK;
+  if (c.num_envs <= 0 || c.num_vehicles <= 0) {
+    err = "rgb: num_envs and num_vehicles must be > 0";
+    return SMX_ERR_INVALID;
+  }
+  const uint64_t need = (uint64_t)c.num_envs * (uint64_t)c.num_vehicles * (uint64_t)c.rgb_width * (uint64_t)c.rgb_height * 3;
+  if (count < need) {
+    err = "rgb output: " + std::to_string(count) + " bytes declared, the configuration needs " + std::to_string(need) +
+          " (a short buffer would be an out-of-bounds device write)";
+    return SMX_ERR_INVALID;
+  }
+  return SMX_OK;
+}
+
+extern "C" int smx_check_rgb_output(const smx_config* cfg, uint64_t count, char* err, uint64_t err_len) {
+  std::string msg;
+  const int rc = cfg ? check_rgb_output_impl(*cfg, count, msg) : SMX_ERR_INVALID;
+  if (!cfg) msg = "null config";
+  if (err && err_len > 0) {
+    const size_t n = std::min<size_t>(msg.size(), (size_t)err_len - 1);
+    memcpy(err, msg.data(), n);
+    err[n] = 0;
+  }
+  return rc;
+}
+
+extern "C" int smx_set_rgb_output(smx_handle h, uint8_t* rgb_dev, uint64_t count) {
+  if (!h) return SMX_ERR_INVALID;
+  if (!rgb_dev) {  // unbind
+    h->rgb_out = nullptr;
+    h->rgb_count = 0;
+    return SMX_OK;
+  }
+  if (!(h->cfg.sensors & SMX_SENSOR_RGB))
+    return fail(h, SMX_ERR_STATE, "smx_set_rgb_output: the configuration has no SMX_SENSOR_RGB");
+  if ((reinterpret_cast<uintptr_t>(rgb_dev) & 15) != 0)
+    return fail(h, SMX_ERR_INVALID, "rgb output: the buffer must be 16-byte aligned (it is written with 16-byte stores)");
+  std::string msg;
+  const int rc = check_rgb_output_impl(h->cfg, count, msg);
+  if (rc != SMX_OK) return fail(h, rc, msg);
+  h->rgb_out = rgb_dev;
+  h->rgb_count = count;
+  return SMX_OK;
+}
+
 static int check_buffers(smx_handle h, const smx_state* st, const smx_spawns* sp, const smx_outputs* o) {
   std::string msg;
   const int rc = check_buffers_impl(h->cfg, h->n_vias > 0, true, st, sp, o, msg);
   if (rc != SMX_OK) return fail(h, rc, msg);
   if ((h->cfg.sensors & SMX_SENSOR_LIDAR) && !h->lidar_rays)
     return fail(h, SMX_ERR_STATE, "lidar sensor enabled but smx_set_lidar_rays has not been called");
+  if ((h->cfg.sensors & SMX_SENSOR_RGB) && !h->rgb_out)
+    return fail(h, SMX_ERR_STATE, "rgb sensor enabled but no image buffer is bound (smx_set_rgb_output)");
   return SMX_OK;
 }
 
@@ -6100,6 +6274,7 @@ static void launch_grids(smx_handle h, const TickPlan& p, const KernelArgs& k, h
     case Ogm::PER_OBSERVER: launch(k_ogm, total, p.ogm_lds, s, k); break;
   }
   if (p.dagm) launch(k_dagm, total, p.dagm_bytes, s, k);
+  if (p.rgb) launch(k_rgb, total, p.rgb_lds, s, k);
 }
 
 // the slow seeds chain over the vehicles the one-lane seeds kernel left seed_pending: searches from scratch, then their
@@ -6239,7 +6414,7 @@ static int tail_and_reset_pass(smx_handle h, const TickPlan& p, const KernelArgs
     t.flat_next = h->alive_blob + al.flat + h->alive_parity;
     t.slow_next = SlowLists{h->slow_blob, total}.counters(h->alive_parity);
   }
-  hipLaunchKernelGGL(k_tail, dim3(p.obs_blocks), dim3(SMX_BLOCK), p.tail_grids ? std::max(p.ogm_bytes, p.dagm_bytes) : 0, stream, r, t);
+  hipLaunchKernelGGL(k_tail, dim3(p.obs_blocks), dim3(SMX_BLOCK), p.tail_grids ? std::max({p.ogm_bytes, p.dagm_bytes, p.rgb_lds}) : 0, stream, r, t);
   if (ph) SMX_HIP(hipEventRecord(ph[SMX_PHASE_COMMIT + 1], stream));
   h->group_parity ^= 1;
   h->list_ready = p.tail_builds_list;
@@ -6306,6 +6481,7 @@ static KernelArgs kernel_args(smx_handle h, const TickPlan& p, const int8_t* act
   a.seeds_carry = h->scan_carry;
   a.facts_carry = h->scan_carry ? h->scan_carry + 4 * total : nullptr;
   a.dagm_reach = h->dagm_reach;
+  a.rgb = h->rgb_out;
   a.wp_blocks = (int)p.wp_blocks;
   a.obs_blocks = (int)p.obs_blocks;
   a.lidar_blocks = (int)p.lidar_blocks;

@@ -133,6 +133,8 @@ struct TickPlan {
   Ogm ogm;
   Lidar lidar;
   bool dagm, road_waypoints;
+  bool rgb;  // k_rgb (SMX_SENSOR_RGB): wherever k_dagm is launched; rgb_lds = its class tile, a byte a pixel
+  size_t rgb_lds;
   // k_lane_ttc (SMX_SENSOR_LANE_TTC): in a tick over every agent, on the caller's stream once the waypoint, neighbour
   // and ego rows are complete (after the joins); in the reset pass over the env groups k_tail listed, after k_first
   bool lane_ttc;
@@ -262,6 +264,8 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
     p.ogm = p.ogm_bytes * SMX_OGM_WAVES <= 64 * 1024 ? Ogm::ENV1 : Ogm::PER_OBSERVER;
   p.ogm_lds = p.ogm == Ogm::ENV2 ? p.ogm_bytes * SMX_OGM_WAVES * 2 : p.ogm == Ogm::ENV1 ? p.ogm_bytes * SMX_OGM_WAVES : p.ogm_bytes;
   p.dagm = p.dagm_bytes != 0;
+  p.rgb = (c.sensors & SMX_SENSOR_RGB) != 0;
+  p.rgb_lds = p.rgb ? (size_t)c.rgb_width * c.rgb_height : 0;
   p.lidar = !lidar ? Lidar::NONE : small ? Lidar::IN_SENSORS : p.fork ? Lidar::SIDE : Lidar::CALLER;
   p.road_waypoints = (c.sensors & SMX_SENSOR_ROAD_WAYPOINTS) != 0;
   p.lane_ttc = (c.sensors & SMX_SENSOR_LANE_TTC) != 0;
@@ -269,7 +273,7 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
   // k_tail builds the next tick's alive list unless k_social moves vehicles (and can end them) ahead of the list
   p.tail_builds_list = !small && in.alive_blob && in.slow.base && !idm;
   p.reset_pass = !in.is_step || c.auto_reset;  // (in a step, k_tail's commit respawns the envs that ended)
-  p.tail_grids = p.reset_pass && (p.ogm_bytes || p.dagm_bytes);
+  p.tail_grids = p.reset_pass && (p.ogm_bytes || p.dagm_bytes || p.rgb);
   // large batches: the new vehicles' lidar as a launch of its own instead of one after the other inside
   // k_first — at C5 an env restart brings 64 new vehicles, whose serial lidar roles made the reset pass 0.58 ms
   // of a 1.5 ms tick late in a run (many restarts per tick)

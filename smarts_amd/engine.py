@@ -55,6 +55,12 @@ class SimConfig:
     dagm_height: int = 256
     dagm_resolution: float = 50 / 256
     lidar: Optional[SensorParams] = None  # agent_interface.py:132-135
+    # the top-down RGB camera (agent_interface.py:54-64, RGB defaults 256 x 256 @ 50/256): out["rgb"], [E, N, H, W, 3]
+    # uint8 (include/smx.h SMX_SENSOR_RGB); the sim owns the image buffer and binds it with smx_set_rgb_output
+    rgb: bool = False
+    rgb_width: int = 256
+    rgb_height: int = 256
+    rgb_resolution: float = 50 / 256
     # DoneCriteria.agents_alive (agent_interface.py:155-176): minima (None = unset) and up to four
     # (agent slots, minimum alive) lists
     alive_min_ego: Optional[int] = None
@@ -103,6 +109,8 @@ class SimConfig:
             m |= nat.SENSOR_LANE_TTC
         if self.ego_centric:
             m |= nat.SENSOR_EGO_CENTRIC
+        if self.rgb:
+            m |= nat.SENSOR_RGB
         return m
 
     def done_mask(self) -> int:
@@ -254,6 +262,8 @@ class BatchedSim:
             c.dagm_width, c.dagm_height, c.dagm_resolution = cfg.dagm_width, cfg.dagm_height, cfg.dagm_resolution
         if cfg.road_waypoints:
             c.rw_horizon, c.rw_lanes, c.rw_paths = int(cfg.rw_horizon), int(cfg.rw_lanes), int(cfg.rw_paths)
+        if cfg.rgb:
+            c.rgb_width, c.rgb_height, c.rgb_resolution = int(cfg.rgb_width), int(cfg.rgb_height), float(cfg.rgb_resolution)
         self._c = c
         self.handle = C.c_void_p()
         rc = self.lib.smx_create(C.byref(c), idx, C.byref(self.handle))
@@ -409,6 +419,10 @@ class BatchedSim:
         for name in nat.OUTPUT_BUFFERS:
             nat.bind_buffer(so, nat.OUTPUT_BUFFERS, name, o.get(name))
         self._out = so
+        if cfg.rgb:
+            # not a member of smx_outputs (its pointer list is closed): a buffer of its own, bound to the handle
+            o["rgb"] = z((E, N, cfg.rgb_height, cfg.rgb_width, 3), torch.uint8)
+            self.bind_rgb(o["rgb"])
         self._stream = None
         self._was_reset = False
 
@@ -440,7 +454,7 @@ class BatchedSim:
         ctrl_state = 14 * 8 + 4  # SMX_S_X .. SMX_S_MCL_Y + flags: read and written back by k_control
         obs_state_r, obs_state_w = 16 * 8 + 4 + 4, 12 * 8 + 4  # trip meter / accelerometer / driven-path fields, steps
         wp = sum(v for k, v in o.items() if k.startswith("wp_")) if self.cfg.waypoints else 0
-        rows = sum(v for k, v in o.items() if not k.startswith(("wp_", "ogm", "lidar", "dagm", "rw_"))) + 8  # + learner block
+        rows = sum(v for k, v in o.items() if not k.startswith(("wp_", "ogm", "lidar", "dagm", "rw_", "rgb"))) + 8  # + learner block
         kb = {
             "control": (ctrl_state + (12 if self.cfg.action_space != "Lane" else 1), ctrl_state + 2 * 8),
             "scan": (pose, 0),
@@ -449,14 +463,15 @@ class BatchedSim:
         }
         ogm = (pose, o["ogm"]) if self.cfg.ogm else (0, 0)
         dagm = (pose, o["dagm"]) if self.cfg.dagm else (0, 0)
+        rgb = (pose, o["rgb"]) if self.cfg.rgb else (0, 0)
         tile = self.cfg.ogm_width * self.cfg.ogm_height
         ogm_env_small = (self.small_form() and self.E * self.N >= nat.OGM_ENV_MIN_VEHICLES and self.N <= 32
                          and tile * 8 <= 64 * 1024)  # smx_plan.h tick_plan(): k_ogm_env on small batches too
         ogm_inline = (self.cfg.ogm and tile <= 16 * 1024
                       and self.small_form() and not ogm_env_small)  # smx_plan.h tick_plan(): small batches only
         add = lambda a, b: (a[0] + b[0], a[1] + b[1])  # noqa: E731
-        if (self.cfg.ogm and not ogm_inline) or self.cfg.dagm:
-            kb["ogm"] = add((0, 0) if ogm_inline else ogm, dagm)  # their own launches (one timing phase)
+        if (self.cfg.ogm and not ogm_inline) or self.cfg.dagm or self.cfg.rgb:
+            kb["ogm"] = add(add((0, 0) if ogm_inline else ogm, dagm), rgb)  # their own launches (one timing phase)
         if ogm_inline:
             kb["sensors"] = add(kb["sensors"], ogm)
         if self.cfg.lidar is not None:
@@ -505,6 +520,21 @@ class BatchedSim:
                 keep = (h, d)  # noqa: F841 (alive across the call)
             nat.check(self.lib, self.handle, self.lib.smx_set_mission_goals(self.handle, goals, N, heading, dead_end, n_lanes),
                       "smx_set_mission_goals")
+
+    def bind_rgb(self, images: Optional[torch.Tensor]):
+        """Bind the image buffer of the RGB sensor (``smx_set_rgb_output``): uint8 [E, N, rgb_height, rgb_width, 3] on
+        the sim's device, or ``None`` to unbind.  ``out["rgb"]`` follows; a caller may alternate two buffers between
+        ticks, as with the learner block."""
+        if images is None:
+            nat.check(self.lib, self.handle, self.lib.smx_set_rgb_output(self.handle, None, 0), "smx_set_rgb_output")
+            self.out.pop("rgb", None)
+            return
+        want = (self.E, self.N, self.cfg.rgb_height, self.cfg.rgb_width, 3)
+        if images.dtype != torch.uint8 or not images.is_cuda or not images.is_contiguous() or tuple(images.shape) != want:
+            raise ValueError(f"the rgb buffer must be a contiguous uint8 device tensor of shape {want}")
+        rc = self.lib.smx_set_rgb_output(self.handle, images.data_ptr(), int(images.numel()))
+        nat.check(self.lib, self.handle, rc, "smx_set_rgb_output")
+        self.out["rgb"] = images
 
     def small_form(self) -> bool:
         """Whether a tick runs in the SMALL launch form (smx_plan.h: SMX_LARGE_BATCH_VEHICLES)."""

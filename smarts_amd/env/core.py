@@ -119,6 +119,8 @@ def sim_config_from_interface(itf: AgentInterface, num_envs: int, num_agents: in
     if itf.drivable_area_grid_map:
         g = itf.drivable_area_grid_map
         kw.update(dagm=True, dagm_width=g.width, dagm_height=g.height, dagm_resolution=g.resolution)
+    if itf.rgb:  # (validate_for_device refuses it today: DESIGN.md §9)
+        kw.update(rgb=True, rgb_width=itf.rgb.width, rgb_height=itf.rgb.height, rgb_resolution=itf.rgb.resolution)
     if itf.lidar:
         kw.update(lidar=itf.lidar.sensor_params)
     if itf.road_waypoints:
@@ -210,7 +212,7 @@ class BatchCore:
             self.cm.lane_ids, road_ids, vehicle_names, waypoints=self.cfg.waypoints, neighbors=self.cfg.neighbors,
             accelerometer=self.cfg.accelerometer, ogm=first.ogm or None, dagm=first.drivable_area_grid_map or None,
             lidar_rays=base_rays(first.lidar.sensor_params) if first.lidar else None, dt=dt, vias=self.vias,
-            road_waypoints=bool(first.road_waypoints), missions=self.missions)
+            road_waypoints=bool(first.road_waypoints), missions=self.missions, rgb=first.rgb or None)
         self._was_reset = False
         self._destroyed = False
 

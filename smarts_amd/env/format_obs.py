@@ -136,7 +136,8 @@ def std_obs(obs: Observation) -> StdObs:
         dist=np.float32(obs.distance_travelled), ego=_std_ego(obs.ego_vehicle_state), events=_std_events(obs.events),
         dagm=obs.drivable_area_grid_map.data.astype(np.uint8) if obs.drivable_area_grid_map else None,
         lidar=_std_lidar(obs.lidar_point_cloud), neighbors=_std_neighbors(obs.neighborhood_vehicle_states),
-        ogm=obs.occupancy_grid_map.data.astype(np.uint8) if obs.occupancy_grid_map else None, rgb=None,
+        ogm=obs.occupancy_grid_map.data.astype(np.uint8) if obs.occupancy_grid_map else None,
+        rgb=obs.top_down_rgb.data.astype(np.uint8) if obs.top_down_rgb else None,
         ttc=_std_ttc(obs), waypoints=_std_waypoints(obs.waypoint_paths),
     )
 
@@ -247,9 +248,10 @@ class FormatObs:
         if "ogm" in rows:
             ogm = np.array(rows["ogm"][env, slot], dtype=np.uint8)[..., None]
         dagm = np.array(rows["dagm"][env, slot], dtype=np.uint8)[..., None] if "dagm" in rows else None
+        rgb = np.array(rows["rgb"][env, slot], dtype=np.uint8) if "rgb" in rows else None  # (H, W, 3), format_obs.py:313-373
         if "lidar_hit" in rows:
             hit = rows["lidar_hit"][env, slot].astype(np.int8)
             cloud = np.nan_to_num(np.array(rows["lidar_point"][env, slot]), nan=0.0, posinf=0.0, neginf=0.0)
             lidar = {"hit": hit, "point_cloud": cloud}
         return StdObs(dist=np.float32(rows["dist"][env, slot]), ego=ego, events=events, lidar=lidar, neighbors=neighbors,
-                      ogm=ogm, waypoints=waypoints, dagm=dagm, ttc=ttc)
+                      ogm=ogm, waypoints=waypoints, dagm=dagm, ttc=ttc, rgb=rgb)

@@ -167,6 +167,13 @@ class OccupancyGridMap(NamedTuple):
     data: np.ndarray
 
 
+class TopDownRGB(NamedTuple):
+    """sensors.py:127-133: ``data`` is the (height, width, 3) uint8 image (include/smx.h SMX_SENSOR_RGB)."""
+
+    metadata: GridMapMetadata
+    data: np.ndarray
+
+
 @dataclass
 class ViaPoint:
     """sensors.py:145-157."""
@@ -247,13 +254,14 @@ class ObservationBuilder:
 
     def __init__(self, lane_ids: Sequence[str], lane_road_ids: Sequence[str], agent_ids: Sequence[str], *,
                  waypoints: bool, neighbors: bool, accelerometer: bool, ogm=None, lidar_rays: Optional[np.ndarray] = None,
-                 dt: float = 0.1, vias=None, dagm=None, road_waypoints: bool = False, missions=None):
+                 dt: float = 0.1, vias=None, dagm=None, road_waypoints: bool = False, missions=None, rgb=None):
         self.lane_ids = list(lane_ids)
         self.lane_road_ids = list(lane_road_ids)
         self.agent_ids = list(agent_ids)
         self.waypoints, self.neighbors, self.accelerometer = waypoints, neighbors, accelerometer
         self.ogm, self.lidar_rays, self.dt = ogm, lidar_rays, dt
         self.dagm = dagm
+        self.rgb = rgb  # agent_interface.RGB (width, height, resolution) | None
         self.road_waypoints = road_waypoints
         # per vehicle slot: smarts_amd.missions.PlannedMission | None
         self.missions = [
@@ -281,12 +289,12 @@ class ObservationBuilder:
             for k in ("wp_count", "nb_count", "rw_lane", "via_near_count", "collidees"):
                 if k in rows:
                     rows[k] = np.zeros_like(rows[k]) if k != "rw_lane" else np.full_like(rows[k], -1)
-            saved = (self.ogm, self.dagm, self.lidar_rays)
-            self.ogm = self.dagm = self.lidar_rays = None
+            saved = (self.ogm, self.dagm, self.lidar_rays, self.rgb)
+            self.ogm = self.dagm = self.lidar_rays = self.rgb = None
             try:
                 return self.build(rows, slot, step_count, elapsed_sim_time)
             finally:
-                self.ogm, self.dagm, self.lidar_rays = saved
+                self.ogm, self.dagm, self.lidar_rays, self.rgb = saved
         E = nat.EGO
         f = rows["ego_f32"][slot]
         v3 = lambda k: np.array(f[E[k]:E[k] + 3], dtype=np.float64)  # noqa: E731
@@ -384,6 +392,13 @@ class ObservationBuilder:
                 height=self.dagm.height, camera_pos=tuple(float(x) for x in rows["ego_pos"][slot]),
                 camera_heading_in_degrees=float(np.degrees(float(f[E["HEADING"]]))))
             dagm = DrivableAreaGridMap(metadata=meta, data=np.array(rows["dagm"][slot], dtype=np.uint8)[..., None])
+        rgb = None
+        if self.rgb is not None:
+            meta = GridMapMetadata(
+                created_at=int(elapsed_sim_time), resolution=self.rgb.resolution, width=self.rgb.width,
+                height=self.rgb.height, camera_pos=tuple(float(x) for x in rows["ego_pos"][slot]),
+                camera_heading_in_degrees=float(np.degrees(float(f[E["HEADING"]]))))
+            rgb = TopDownRGB(metadata=meta, data=np.array(rows["rgb"][slot], dtype=np.uint8))
         lidar = None
         if self.lidar_rays is not None:
             origin = np.array(rows["ego_pos"][slot], dtype=np.float64) + np.array([0.0, 0.0, 1.0])
@@ -406,5 +421,5 @@ class ObservationBuilder:
         return Observation(
             dt=self.dt, step_count=step_count, elapsed_sim_time=elapsed_sim_time, events=events, ego_vehicle_state=ego,
             neighborhood_vehicle_states=neighbors, waypoint_paths=paths, distance_travelled=float(rows["dist"][slot]),
-            lidar_point_cloud=lidar, drivable_area_grid_map=dagm, occupancy_grid_map=ogm, top_down_rgb=None,
+            lidar_point_cloud=lidar, drivable_area_grid_map=dagm, occupancy_grid_map=ogm, top_down_rgb=rgb,
             road_waypoints=road_wps, via_data=via_data)
