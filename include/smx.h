@@ -154,6 +154,11 @@ typedef struct smx_config {
   int32_t nb_max;            /* dense neighbour rows, format_obs.py:41 -> 10      */
   double nb_radius;          /* NeighborhoodVehicles.radius; < 0 = unlimited      */
   int32_t max_episode_steps; /* <= 0 = None                                       */
+  /* Device-side frame stacking (FrameStack of smarts/env/wrappers/frame_stack.py over (env, slot) rows): 0 = off,
+   * 2..8 = the number of frames kept of every row bound with smx_bind_frame_stack (1 is refused: the reference
+   * asserts num_stack > 1).  It takes the four bytes that were padding ahead of not_moving_time: the struct's size
+   * and every other offset are unchanged, and a zeroed struct of an older caller reads "off". */
+  int32_t frame_stack;
   double not_moving_time;    /* EventConfiguration, agent_interface.py:175-183    */
   double not_moving_distance;
   int32_t auto_reset;        /* ParallelEnv auto_reset, parallel_env.py:303-309   */
@@ -589,6 +594,35 @@ int smx_set_lidar_rays(smx_handle h, const double* rays_dev, int32_t n_rays);
  * (with the bit off any count passes).  SMX_OK, or SMX_ERR_INVALID with the reason in err[err_len]. */
 int smx_set_rgb_output(smx_handle h, uint8_t* rgb_dev, uint64_t count);
 int smx_check_rgb_output(const smx_config* cfg, uint64_t count, char* err, uint64_t err_len);
+/* Frame stacking (smx_config.frame_stack = k): for every agent the device keeps the last k frames of each bound row,
+ * newest first (frame 0 is this pass's row), in a caller-owned device buffer.  At the end of every smx_reset / smx_step*
+ * pass, on the caller's stream, once every row of the pass is complete (under auto_reset: after the reset pass has
+ * written a restarted env's first observation), each agent's stacks are
+ *   pushed  — frames 0..k-2 move to 1..k-1, the row becomes frame 0 (deque.appendleft, frame_stack.py:69-72) — when the
+ *             agent had an observation in the tick: alive at the tick's start and not a social slot (the agents whose
+ *             rgb / ec_* / lane_ttc rows the pass wrote);
+ *   filled  — all k frames become the row (frame_stack.py:104-109) — when the observation is the first of an episode:
+ *             the envs smx_reset selects, and under auto_reset an env that restarts inside the launch (the finishing
+ *             tick's row is not pushed: ParallelEnv's worker calls the wrapped reset(), parallel_env.py:303-309);
+ *   held    — byte for byte — otherwise: an agent that is done while its env goes on, every social slot, the envs a
+ *             masked smx_reset leaves alone.  There is no final_* twin.
+ * `source`: an SMX_OUT_* index of a per-agent row ([E*N]...), read from the smx_outputs the pass is called with, or
+ * SMX_STACK_SOURCE_RGB for the image bound by smx_set_rgb_output when the pass runs (callers may alternate image
+ * buffers).  Refused: SMX_OUT_ENV_DONE, SMX_OUT_LEARNER, the SMX_OUT_FINAL_* rows, a row whose sensor is off.
+ * `layout`: SMX_STACK_FRAMES = [E*N][k][row...]; SMX_STACK_DSTACK (SMX_STACK_SOURCE_RGB only, 16-byte aligned) =
+ * [E*N][H][W][3k], channel 3j + c = frame j's channel c: the array RGBImage.observation returns (rgb_image.py:93-99).
+ * `bytes`: what the caller allocated, at least E * N * k * (the row's bytes per agent).  stack_dev = NULL unbinds
+ * (source, layout).  At most SMX_STACK_MAX_BINDINGS bindings, one per (source, layout); binding again replaces the
+ * buffer.  Errors: SMX_ERR_STATE with frame_stack == 0 or a 17th binding, SMX_ERR_INVALID for a bad source or layout,
+ * too few bytes or a misaligned DSTACK buffer; a pass with a bound source whose row pointer is NULL returns
+ * SMX_ERR_STATE.  smx_check_frame_stack is the validation alone, callable without a device or a handle (it knows no
+ * other bindings): SMX_OK, or the code with the reason in err[err_len]. */
+enum { SMX_STACK_SOURCE_RGB = 1 << 16 };
+enum { SMX_STACK_FRAMES = 0, SMX_STACK_DSTACK = 1 };
+#define SMX_STACK_MAX_FRAMES 8
+#define SMX_STACK_MAX_BINDINGS 16
+int smx_bind_frame_stack(smx_handle h, int32_t source, int32_t layout, void* stack_dev, uint64_t bytes);
+int smx_check_frame_stack(const smx_config* cfg, int32_t source, int32_t layout, uint64_t bytes, char* err, uint64_t err_len);
 /* Re-initialise the envs whose mask byte is non-zero (NULL = all) from the spawn
  * table and produce their first observations. */
 int smx_reset(smx_handle h, const uint8_t* env_mask_dev, const smx_state* st, const smx_spawns* sp,

@@ -33,6 +33,11 @@ SENSOR_LANE_TTC = 128
 SENSOR_EGO_CENTRIC = 256  # smx_outputs.ego_frame / ec_* (the ego-centric adapters on the device)
 SENSOR_RGB = 512  # the top-down RGB image, bound with smx_set_rgb_output (not part of smx_outputs)
 EC_VALID = 1  # smx_outputs.ec_flags bit 0
+# smx_bind_frame_stack: the image's source index (the rows take their SMX_OUT_* index), the two layouts, the limits
+STACK_SOURCE_RGB = 1 << 16
+STACK_FRAMES, STACK_DSTACK = 0, 1
+STACK_LAYOUTS = {"frames": STACK_FRAMES, "dstack": STACK_DSTACK}
+STACK_MAX_FRAMES, STACK_MAX_BINDINGS = 8, 16
 # columns of smx_outputs.lane_ttc (SMX_TTC_*; "TTC" and "DTC" head three columns: right, current, left lane) and the
 # bits of smx_outputs.lane_ttc_flags
 TTC = dict(DIST_FROM_CENTER=0, ANGLE_ERROR=1, TTC=2, DTC=5)
@@ -61,7 +66,9 @@ class SmxConfig(C.Structure):
     _fields_ = [
         ("num_envs", _i32), ("num_vehicles", _i32), ("dt", _f64), ("sensors", C.c_uint32),
         ("done_criteria", C.c_uint32), ("wp_lookahead", _i32), ("wp_paths", _i32), ("wp_len", _i32),
-        ("nb_max", _i32), ("nb_radius", _f64), ("max_episode_steps", _i32), ("not_moving_time", _f64),
+        ("nb_max", _i32), ("nb_radius", _f64), ("max_episode_steps", _i32),
+        ("frame_stack", _i32),  # (in what was padding ahead of not_moving_time: no other offset moves)
+        ("not_moving_time", _f64),
         ("not_moving_distance", _f64), ("auto_reset", _i32), ("reset_elapsed_steps", _i32),
         ("ogm_width", _i32), ("ogm_height", _i32), ("ogm_resolution", _f64), ("lidar_rays", _i32),
         ("lidar_max_distance", _f64), ("action_space", _i32), ("num_social", _i32), ("social_speed_factor", _f64), ("via_max", _i32),
@@ -144,6 +151,16 @@ class SmxOutputs(C.Structure):
         ("count", C.c_uint64 * len(OUTPUT_BUFFERS)), ("dtype", C.c_uint8 * ((len(OUTPUT_BUFFERS) + 7) & ~7))]
 
 
+def stack_source(row: str) -> int:
+    """The ``source`` of ``smx_bind_frame_stack`` for an ``out[...]`` row name: its SMX_OUT_* index, or
+    STACK_SOURCE_RGB for the image.  Rows that cannot be stacked raise ValueError."""
+    if row == "rgb":
+        return STACK_SOURCE_RGB
+    if row not in OUTPUT_BUFFERS or row in ("env_done", "learner") or row.startswith("final_"):
+        raise ValueError(f"{row!r} is not a per-agent row that can be frame-stacked")
+    return OUTPUT_BUFFERS.index(row)
+
+
 def torch_dtype_code(t) -> int:
     """SMX_DT_* of a torch tensor (the dtype enum checked on entry, include/smx.h)."""
     import torch
@@ -165,6 +182,7 @@ EXPORTS = [
     "smx_set_timing", "smx_last_error", "smx_version", "smx_destroy", "smx_set_controller_gains", "smx_struct_size", "smx_read_step_ms",
     "smx_check_buffers", "smx_set_launch_strategy", "smx_launch_form", "smx_step_target_pose", "smx_step_trajectory_with_time",
     "smx_set_mission_goals", "smx_check_mission_goals", "smx_actions_to_world", "smx_set_rgb_output", "smx_check_rgb_output",
+    "smx_bind_frame_stack", "smx_check_frame_stack",
 ]
 LAUNCH_FORMS = {0: "small", 1: "large_teams", 2: "large_one_lane"}
 LAUNCH_STRATEGIES = {"auto": 0, "small": 1, "large": 2, "large_one_lane": 3, "large_teams": 4}
@@ -240,6 +258,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.smx_set_rgb_output.restype = C.c_int
     lib.smx_check_rgb_output.argtypes = [C.POINTER(SmxConfig), C.c_uint64, C.c_char_p, C.c_uint64]
     lib.smx_check_rgb_output.restype = C.c_int
+    lib.smx_bind_frame_stack.argtypes = [h, _i32, _i32, _p, C.c_uint64]
+    lib.smx_bind_frame_stack.restype = C.c_int
+    lib.smx_check_frame_stack.argtypes = [C.POINTER(SmxConfig), _i32, _i32, C.c_uint64, C.c_char_p, C.c_uint64]
+    lib.smx_check_frame_stack.restype = C.c_int
     lib.smx_read_phase_ms.argtypes = [h, C.POINTER(C.c_float), _i32, C.POINTER(_i32)]
     lib.smx_read_phase_ms.restype = C.c_int
     lib.smx_set_timing.argtypes = [h, C.c_int]

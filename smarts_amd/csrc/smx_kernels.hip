@@ -5031,6 +5031,167 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_actions_to_world(const double* __
 }
 
 // =================================================================================
+// k_frame_push / k_frame_dstack (smx_config.frame_stack; include/smx.h smx_bind_frame_stack): FrameStack of
+// smarts/env/wrappers/frame_stack.py over (env, slot) rows — per agent the last k frames of every bound row, newest
+// first, kept in place in the caller's buffers.  The last launches of a pass: every row is complete, the flags are the
+// ones the pass leaves, `done` is this tick's and env_done says which envs restarted inside the launch.  Per agent:
+//   smx_reset            FILL when its env is selected (mask / all) and it is an alive agent, else HOLD
+//   tick, env restarted  FILL (auto_reset and env_done raised: the rows hold the next episode's first observation)
+//   tick, otherwise      PUSH when it was alive at the tick's start — still alive, or done in this tick — else HOLD
+// and HOLD for every social slot.  No per-agent state beyond what the pass already keeps.
+// A thread owns one column of bytes (16, 4 or 1 wide) at a fixed offset of the agent's row: it loads the k - 1 frames
+// that stay and the new one into registers, then stores k — the shift in place has no hazard, a fill is the same thread
+// storing its new value k times.  Pure streaming: 16-byte accesses wherever the row's size and both pointers allow.
+// =================================================================================
+#define SMX_STACK_BLOCK 256
+enum { SMX_STACK_HOLD = 0, SMX_STACK_PUSH = 1, SMX_STACK_FILL = 2 };
+struct FrameStackBinding {
+  const uint8_t* src;  // the row: [total][bytes]
+  uint8_t* dst;        // the stack: [total][k][bytes] (FRAMES) / [total][pixels][3k] (DSTACK)
+  uint32_t bytes;      // per agent and frame
+  uint32_t unit;       // FRAMES: bytes a thread moves per frame (16, 4 or 1), chosen on the host from the alignments
+  uint32_t block0;     // FRAMES: the binding's first workgroup of the launch
+  uint32_t pad;
+};
+struct FrameStackArgs {
+  FrameStackBinding b[SMX_STACK_MAX_BINDINGS];
+  int n;  // bindings of this launch (their workgroups follow one another: block0 ascends)
+  int k;  // frames
+  uint32_t total, n_veh;
+  const int32_t* flags;     // after the pass
+  const uint8_t* done;      // out.done of this tick
+  const uint8_t* env_done;  // out.env_done
+  const uint8_t* env_mask;  // smx_reset's mask (null: every env)
+  int is_step, auto_reset;
+};
+
+__device__ __forceinline__ int frame_stack_action(const FrameStackArgs& f, const uint32_t agent) {
+  const int flags = f.flags[agent];
+  if (flags & SMX_F_SOCIAL) return SMX_STACK_HOLD;
+  const uint32_t env = agent / f.n_veh;
+  const bool alive = (flags & SMX_F_ALIVE) != 0;
+  if (!f.is_step) return (alive && (!f.env_mask || f.env_mask[env])) ? SMX_STACK_FILL : SMX_STACK_HOLD;
+  if (f.auto_reset && f.env_done[env]) return alive ? SMX_STACK_FILL : SMX_STACK_HOLD;
+  return (alive || f.done[agent]) ? SMX_STACK_PUSH : SMX_STACK_HOLD;
+}
+
+// thread `t` of a workgroup whose first unit is u0, `per` units an agent: its agent and its unit inside the agent
+// (one 64-bit division, uniform in the workgroup; the per-thread one is 32-bit: rem + t < per + SMX_STACK_BLOCK)
+__device__ __forceinline__ void frame_stack_split(const uint64_t u0, const uint32_t per, const uint32_t t, uint64_t& agent, uint32_t& col) {
+  const uint64_t a0 = u0 / per;
+  const uint32_t local = (uint32_t)(u0 - a0 * per) + t, q = local / per;
+  agent = a0 + q;
+  col = local - q * per;
+}
+
+template <typename U>
+__device__ __forceinline__ void frame_push_columns(const FrameStackArgs& f, const FrameStackBinding& b, const uint32_t block) {
+  const uint32_t per = b.bytes / (uint32_t)sizeof(U);
+  uint64_t agent;
+  uint32_t col;
+  frame_stack_split((uint64_t)block * SMX_STACK_BLOCK, per, threadIdx.x, agent, col);
+  if (agent >= f.total) return;
+  const int action = frame_stack_action(f, (uint32_t)agent);
+  if (action == SMX_STACK_HOLD) return;
+  const U fresh = reinterpret_cast<const U*>(b.src + agent * b.bytes)[col];
+  U* frame = reinterpret_cast<U*>(b.dst + agent * (uint64_t)f.k * b.bytes) + col;  // frame j: frame[j * per]
+  U v[SMX_STACK_MAX_FRAMES];
+  v[0] = fresh;
+#pragma unroll
+  for (int j = 1; j < SMX_STACK_MAX_FRAMES; ++j) {
+    v[j] = fresh;
+    if (j < f.k && action == SMX_STACK_PUSH) v[j] = frame[(size_t)(j - 1) * per];
+  }
+#pragma unroll
+  for (int j = 0; j < SMX_STACK_MAX_FRAMES; ++j)
+    if (j < f.k) frame[(size_t)j * per] = v[j];
+}
+
+__global__ void __launch_bounds__(SMX_STACK_BLOCK) k_frame_push(const FrameStackArgs f) {
+  int i = 0;  // the binding of this workgroup (uniform)
+  while (i + 1 < f.n && blockIdx.x >= f.b[i + 1].block0) ++i;
+  const FrameStackBinding& b = f.b[i];
+  const uint32_t block = blockIdx.x - b.block0;
+  if (b.unit == 16)
+    frame_push_columns<uint4>(f, b, block);
+  else if (b.unit == 4)
+    frame_push_columns<uint32_t>(f, b, block);
+  else
+    frame_push_columns<uint8_t>(f, b, block);
+}
+
+// The interleaved image, [total][pixels][3K] with channel 3j + c = frame j's channel c (np.dstack, rgb_image.py:93-99).
+// A thread takes four pixels: 12 source bytes, and the 12K contiguous bytes of the stack they own — three dwords in,
+// 3K dwords in and out (16-byte accesses when 12K is a multiple of 16: K = 4, 8).  Pixel p's new 3K bytes are its three
+// new bytes followed by the first 3(K - 1) of its old ones; every index below is a constant once the loops unroll.
+// An image whose pixel count is no multiple of four takes the byte path, a pixel after the other.
+template <int K>
+__global__ void __launch_bounds__(SMX_STACK_BLOCK) k_frame_dstack(const FrameStackArgs f) {
+  constexpr int NW = 3 * K, PB = 3 * K;  // dwords per thread, bytes per pixel
+  const FrameStackBinding& b = f.b[0];
+  const uint32_t pixels = b.bytes / 3, groups = (pixels + 3) / 4;
+  uint64_t agent;
+  uint32_t g;
+  frame_stack_split((uint64_t)blockIdx.x * SMX_STACK_BLOCK, groups, threadIdx.x, agent, g);
+  if (agent >= f.total) return;
+  const int action = frame_stack_action(f, (uint32_t)agent);
+  if (action == SMX_STACK_HOLD) return;
+  const uint8_t* src = b.src + agent * b.bytes + (size_t)12 * g;
+  uint8_t* dst = b.dst + agent * (uint64_t)K * b.bytes + (size_t)4 * PB * g;
+  if ((pixels & 3u) != 0) {  // (uniform over the launch)
+    const int n = (int)min(4u, pixels - 4 * g);
+    for (int p = 0; p < n; ++p)
+      for (int c = 0; c < 3; ++c) {
+        const uint8_t fresh = src[3 * p + c];
+        uint8_t* px = dst + p * PB + c;
+        for (int j = K - 1; j >= 1; --j) px[3 * j] = action == SMX_STACK_PUSH ? px[3 * (j - 1)] : fresh;
+        px[0] = fresh;
+      }
+    return;
+  }
+  uint32_t nw[3], ow[NW], out[NW];
+#pragma unroll
+  for (int w = 0; w < 3; ++w) nw[w] = reinterpret_cast<const uint32_t*>(src)[w];
+  if (action == SMX_STACK_PUSH) {
+    if constexpr (NW % 4 == 0) {
+#pragma unroll
+      for (int q = 0; q < NW / 4; ++q) {
+        const uint4 v = reinterpret_cast<const uint4*>(dst)[q];
+        ow[4 * q] = v.x, ow[4 * q + 1] = v.y, ow[4 * q + 2] = v.z, ow[4 * q + 3] = v.w;
+      }
+    } else {
+#pragma unroll
+      for (int w = 0; w < NW; ++w) ow[w] = reinterpret_cast<const uint32_t*>(dst)[w];
+    }
+  } else {
+#pragma unroll
+    for (int w = 0; w < NW; ++w) ow[w] = 0u;
+  }
+  const bool push = action == SMX_STACK_PUSH;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    uint32_t word = 0u;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int i = 4 * w + q, p = i / PB, r = i % PB;  // byte i: pixel p, channel r of its 3K
+      const int ni = 3 * p + r % 3;                     // the new byte of that colour
+      const int oi = p * PB + (r >= 3 ? r - 3 : 0);     // the old byte that moves here (r >= 3)
+      const uint32_t fresh = (nw[ni >> 2] >> (8 * (ni & 3))) & 255u;
+      const uint32_t old = (ow[oi >> 2] >> (8 * (oi & 3))) & 255u;
+      word |= ((r < 3 || !push) ? fresh : old) << (8 * q);
+    }
+    out[w] = word;
+  }
+  if constexpr (NW % 4 == 0) {
+#pragma unroll
+    for (int q = 0; q < NW / 4; ++q) reinterpret_cast<uint4*>(dst)[q] = make_uint4(out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]);
+  } else {
+#pragma unroll
+    for (int w = 0; w < NW; ++w) reinterpret_cast<uint32_t*>(dst)[w] = out[w];
+  }
+}
+
+// =================================================================================
 // k_tail: the end of every pass, one wavefront per env group (those of the observe role), in one launch:
 //  - the tick's commit (commit_role: teardown, done counts, auto-reset respawn);
 //  - the OGM / DAGM / RGB tiles of the group's new vehicles (respawned just now, or by k_reset), one after the other — almost
@@ -5294,6 +5455,12 @@ struct smx_handle_s {
   double dagm_reach;  // half the widest lane width of the loaded map
   uint8_t* rgb_out;   // smx_set_rgb_output: the caller's image buffer (null: none bound) and the bytes it holds
   uint64_t rgb_count;
+  struct StackBinding {  // smx_bind_frame_stack: one caller-owned stack per (source, layout)
+    int32_t source, layout;
+    uint8_t* dst;
+    uint64_t bytes;
+  };
+  std::vector<StackBinding> stacks;
   int debug_skip;
   int launch_strategy;  // SMX_LAUNCH_*
   bool timing;
@@ -5398,6 +5565,12 @@ static const char* rgb_config_error(const smx_config& c) {
   return nullptr;
 }
 
+// smx_config.frame_stack: off, or FrameStack's num_stack (frame_stack.py:47 asserts num_stack > 1)
+static const char* frame_stack_config_error(const smx_config& c) {
+  if (c.frame_stack == 0 || (c.frame_stack >= 2 && c.frame_stack <= SMX_STACK_MAX_FRAMES)) return nullptr;
+  return "frame_stack: need 0 (off) or 2 <= frame_stack <= " SMX_STR(SMX_STACK_MAX_FRAMES) " (the reference asserts num_stack > 1)";
+}
+
 static int create_impl(const smx_config* cfg, int device, smx_handle* out) {
   smx_handle h = new (std::nothrow) smx_handle_s();
   if (!h) return SMX_ERR_NOMEM;
@@ -5487,6 +5660,7 @@ static int create_impl(const smx_config* cfg, int device, smx_handle* out) {
     return fail(h, SMX_ERR_INVALID, "neighbours: need 1 <= nb_max <= 127");
   if (const char* why = lane_ttc_config_error(c)) return fail(h, SMX_ERR_INVALID, why);
   if (const char* why = rgb_config_error(c)) return fail(h, SMX_ERR_INVALID, why);
+  if (const char* why = frame_stack_config_error(c)) return fail(h, SMX_ERR_INVALID, why);
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return fail(h, SMX_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
   return SMX_OK;
@@ -5537,6 +5711,7 @@ static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_sta
   in.pending_blob = h->pending_blob;
   in.slow = SlowLists{h->slow_blob, (size_t)h->cfg.num_envs * h->cfg.num_vehicles};
   in.slow_parity = h->alive_parity;
+  in.frame_stack_bound = !h->stacks.empty();
   return in;
 }
 
@@ -6167,6 +6342,194 @@ extern "C" int smx_set_rgb_output(smx_handle h, uint8_t* rgb_dev, uint64_t count
   return SMX_OK;
 }
 
+// ---- frame stacking (smx_bind_frame_stack / smx_check_frame_stack) ----
+// bytes per agent of a stackable source, 0 with the reason in `err`: the rows of smx_outputs by their SMX_OUT_* index (the
+// sizes check_buffers_impl asks of them), the image by SMX_STACK_SOURCE_RGB
+static uint64_t stack_row_bytes(const smx_config& c, int32_t source, std::string& err) {
+  const bool wp = (c.sensors & SMX_SENSOR_WAYPOINTS) != 0, nb = (c.sensors & SMX_SENSOR_NEIGHBORS) != 0;
+  const bool lidar = (c.sensors & SMX_SENSOR_LIDAR) != 0, rw = (c.sensors & SMX_SENSOR_ROAD_WAYPOINTS) != 0;
+  const bool ttc = (c.sensors & SMX_SENSOR_LANE_TTC) != 0, ec = (c.sensors & SMX_SENSOR_EGO_CENTRIC) != 0;
+  const uint64_t PW = (uint64_t)c.wp_paths * c.wp_len, K = (uint64_t)c.nb_max, R = (uint64_t)c.lidar_rays;
+  const uint64_t L = (uint64_t)c.rw_lanes, LP = L * (uint64_t)c.rw_paths, LPR = LP * (2 * (uint64_t)c.rw_horizon + 1);
+  const uint64_t V = c.via_max > 0 ? (uint64_t)c.via_max : 0;
+  bool on = true;
+  uint64_t bytes = 0;
+  switch (source) {
+    case SMX_STACK_SOURCE_RGB: on = (c.sensors & SMX_SENSOR_RGB) != 0, bytes = (uint64_t)c.rgb_width * c.rgb_height * 3; break;
+    case SMX_OUT_EGO_POS: bytes = 3 * 8; break;
+    case SMX_OUT_EGO_F32: bytes = SMX_EGO_F32_COUNT * 4; break;
+    case SMX_OUT_EGO_LANE: bytes = 2 * 2; break;
+    case SMX_OUT_EVENTS: bytes = SMX_EV_COUNT; break;
+    case SMX_OUT_REWARD: case SMX_OUT_DIST: case SMX_OUT_COLLIDEES: bytes = 8; break;
+    case SMX_OUT_DONE: case SMX_OUT_ACTIVE: bytes = 1; break;
+    case SMX_OUT_VIA_NEAR: on = V > 0, bytes = V; break;
+    case SMX_OUT_VIA_NEAR_COUNT: on = V > 0, bytes = 1; break;
+    case SMX_OUT_VIA_HIT: on = V > 0, bytes = 4; break;
+    case SMX_OUT_WP_POS: on = wp, bytes = PW * 24; break;
+    case SMX_OUT_WP_HEADING: case SMX_OUT_WP_LANE_WIDTH: case SMX_OUT_WP_SPEED_LIMIT: on = wp, bytes = PW * 4; break;
+    case SMX_OUT_WP_LANE_INDEX: on = wp, bytes = PW; break;
+    case SMX_OUT_WP_LANE_ID: on = wp, bytes = PW * 2; break;
+    case SMX_OUT_WP_COUNT: on = wp, bytes = (uint64_t)c.wp_paths + 1; break;
+    case SMX_OUT_NB_POS: on = nb, bytes = K * 24; break;
+    case SMX_OUT_NB_BOX: on = nb, bytes = K * 12; break;
+    case SMX_OUT_NB_HEADING: case SMX_OUT_NB_SPEED: on = nb, bytes = K * 4; break;
+    case SMX_OUT_NB_LANE_INDEX: case SMX_OUT_NB_SLOT: on = nb, bytes = K; break;
+    case SMX_OUT_NB_LANE_ID: on = nb, bytes = K * 2; break;
+    case SMX_OUT_NB_COUNT: on = nb, bytes = 1; break;
+    case SMX_OUT_OGM: on = (c.sensors & SMX_SENSOR_OGM) != 0, bytes = (uint64_t)c.ogm_width * c.ogm_height; break;
+    case SMX_OUT_LIDAR_HIT: on = lidar, bytes = R; break;
+    case SMX_OUT_LIDAR_POINT: on = lidar, bytes = R * 24; break;
+    case SMX_OUT_DAGM: on = (c.sensors & SMX_SENSOR_DAGM) != 0, bytes = (uint64_t)c.dagm_width * c.dagm_height; break;
+    case SMX_OUT_RW_LANE_COUNT: on = rw, bytes = 1; break;
+    case SMX_OUT_RW_LANE: case SMX_OUT_RW_PATH_COUNT: on = rw, bytes = L * 2; break;
+    case SMX_OUT_RW_COUNT: on = rw, bytes = LP; break;
+    case SMX_OUT_RW_POS: on = rw, bytes = LPR * 24; break;
+    case SMX_OUT_RW_HEADING: case SMX_OUT_RW_LANE_WIDTH: case SMX_OUT_RW_SPEED_LIMIT: on = rw, bytes = LPR * 4; break;
+    case SMX_OUT_RW_LANE_INDEX: on = rw, bytes = LPR; break;
+    case SMX_OUT_RW_LANE_ID: on = rw, bytes = LPR * 2; break;
+    case SMX_OUT_LANE_TTC: on = ttc, bytes = SMX_TTC_COUNT * 8; break;
+    case SMX_OUT_LANE_TTC_FLAGS: on = ttc, bytes = 1; break;
+    case SMX_OUT_EGO_FRAME: on = ec, bytes = 4 * 8; break;
+    case SMX_OUT_EC_FLAGS: on = ec, bytes = 1; break;
+    case SMX_OUT_EC_EGO_F32: on = ec, bytes = SMX_EGO_F32_COUNT * 4; break;
+    case SMX_OUT_EC_WP_POS: on = ec && wp, bytes = PW * 24; break;
+    case SMX_OUT_EC_WP_HEADING: on = ec && wp, bytes = PW * 4; break;
+    case SMX_OUT_EC_NB_POS: on = ec && nb, bytes = K * 24; break;
+    case SMX_OUT_EC_NB_HEADING: on = ec && nb, bytes = K * 4; break;
+    case SMX_OUT_EC_LIDAR_POINT: on = ec && lidar, bytes = R * 24; break;
+    case SMX_OUT_EC_RW_POS: on = ec && rw, bytes = LPR * 24; break;
+    case SMX_OUT_EC_RW_HEADING: on = ec && rw, bytes = LPR * 4; break;
+    default:  // env_done is per env, learner is [2][E*N], the final_* rows are written for restarting envs only
+      err = "frame stack: source " + std::to_string(source) + " is not a per-agent row that can be stacked "
+            "(an SMX_OUT_* index other than env_done, learner and final_*, or SMX_STACK_SOURCE_RGB)";
+      return 0;
+  }
+  if (!on || bytes == 0) {
+    err = "frame stack: the sensor of source " + std::to_string(source) + " is off in this configuration";
+    return 0;
+  }
+  if (bytes > (1ull << 30)) {
+    err = "frame stack: a row of more than 2^30 bytes per agent";
+    return 0;
+  }
+  return bytes;
+}
+
+static int check_frame_stack_impl(const smx_config& c, int32_t source, int32_t layout, uint64_t bytes, std::string& err) {
+  if (const char* why = frame_stack_config_error(c)) {
+    err = why;
+    return SMX_ERR_INVALID;
+  }
+  if (c.frame_stack == 0) {
+    err = "frame stack: smx_config.frame_stack is 0 (off): nothing can be bound";
+    return SMX_ERR_STATE;
+  }
+  if (c.num_envs <= 0 || c.num_vehicles <= 0) {
+    err = "frame stack: num_envs and num_vehicles must be > 0";
+    return SMX_ERR_INVALID;
+  }
+  if (layout != SMX_STACK_FRAMES && layout != SMX_STACK_DSTACK) {
+    err = "frame stack: unknown layout " + std::to_string(layout) + " (SMX_STACK_FRAMES or SMX_STACK_DSTACK)";
+    return SMX_ERR_INVALID;
+  }
+  if (layout == SMX_STACK_DSTACK && source != SMX_STACK_SOURCE_RGB) {
+    err = "frame stack: SMX_STACK_DSTACK is the layout of the RGB image alone (SMX_STACK_SOURCE_RGB); the single-channel "
+          "grids and the rows already have a fixed shape in SMX_STACK_FRAMES";
+    return SMX_ERR_INVALID;
+  }
+  const uint64_t row = stack_row_bytes(c, source, err);
+  if (!row) return SMX_ERR_INVALID;
+  const uint64_t need = (uint64_t)c.num_envs * (uint64_t)c.num_vehicles * (uint64_t)c.frame_stack * row;
+  if (bytes < need) {
+    err = "frame stack: " + std::to_string(bytes) + " bytes declared for source " + std::to_string(source) +
+          ", the configuration needs " + std::to_string(need) + " (a short buffer would be an out-of-bounds device write)";
+    return SMX_ERR_INVALID;
+  }
+  return SMX_OK;
+}
+
+extern "C" int smx_check_frame_stack(const smx_config* cfg, int32_t source, int32_t layout, uint64_t bytes, char* err, uint64_t err_len) {
+  std::string msg;
+  const int rc = cfg ? check_frame_stack_impl(*cfg, source, layout, bytes, msg) : SMX_ERR_INVALID;
+  if (!cfg) msg = "null config";
+  if (err && err_len > 0) {
+    const size_t n = std::min<size_t>(msg.size(), (size_t)err_len - 1);
+    memcpy(err, msg.data(), n);
+    err[n] = 0;
+  }
+  return rc;
+}
+
+extern "C" int smx_bind_frame_stack(smx_handle h, int32_t source, int32_t layout, void* stack_dev, uint64_t bytes) {
+  if (!h) return SMX_ERR_INVALID;
+  auto at = std::find_if(h->stacks.begin(), h->stacks.end(),
+                         [&](const smx_handle_s::StackBinding& b) { return b.source == source && b.layout == layout; });
+  if (!stack_dev) {  // unbind
+    if (at != h->stacks.end()) h->stacks.erase(at);
+    return SMX_OK;
+  }
+  std::string msg;
+  const int rc = check_frame_stack_impl(h->cfg, source, layout, bytes, msg);
+  if (rc != SMX_OK) return fail(h, rc, msg);
+  if (layout == SMX_STACK_DSTACK && (reinterpret_cast<uintptr_t>(stack_dev) & 15) != 0)
+    return fail(h, SMX_ERR_INVALID, "frame stack: an SMX_STACK_DSTACK buffer must be 16-byte aligned (it is moved with up to 16-byte accesses)");
+  if (at != h->stacks.end()) {
+    at->dst = (uint8_t*)stack_dev;
+    at->bytes = bytes;
+    return SMX_OK;
+  }
+  if (h->stacks.size() >= SMX_STACK_MAX_BINDINGS)
+    return fail(h, SMX_ERR_STATE, "frame stack: at most " SMX_STR(SMX_STACK_MAX_BINDINGS) " bindings");
+  h->stacks.push_back({source, layout, (uint8_t*)stack_dev, bytes});
+  return SMX_OK;
+}
+
+// the pass's last launches: every FRAMES binding in one k_frame_push, the interleaved image in one k_frame_dstack
+static int launch_frame_stacks(smx_handle h, const bool is_step, const uint8_t* mask, const smx_state* st, const smx_outputs* out,
+                               hipStream_t stream) {
+  const smx_config& c = h->cfg;
+  FrameStackArgs f{};
+  f.k = c.frame_stack;
+  f.total = (uint32_t)((size_t)c.num_envs * c.num_vehicles);
+  f.n_veh = (uint32_t)c.num_vehicles;
+  f.flags = st->flags;
+  f.done = out->done;
+  f.env_done = out->env_done;
+  f.env_mask = is_step ? nullptr : mask;
+  f.is_step = is_step ? 1 : 0;
+  f.auto_reset = c.auto_reset ? 1 : 0;
+  FrameStackArgs d = f;
+  uint64_t blocks = 0, dstack_blocks = 0;
+  for (const smx_handle_s::StackBinding& s : h->stacks) {
+    std::string msg;
+    const uint64_t row = stack_row_bytes(c, s.source, msg);  // (validated at the bind)
+    const uint8_t* src = s.source == SMX_STACK_SOURCE_RGB ? h->rgb_out
+                                                          : reinterpret_cast<const uint8_t* const*>(out)[s.source];  // (the struct opens with its SMX_OUT_BUFFERS pointers)
+    if (!src || !row)
+      return fail(h, SMX_ERR_STATE, "frame stack: source " + std::to_string(s.source) + " is bound but its row is NULL in this call");
+    FrameStackBinding b{src, s.dst, (uint32_t)row, 0, 0, 0};
+    if (s.layout == SMX_STACK_DSTACK) {
+      d.b[0] = b;
+      d.n = 1;
+      dstack_blocks = ((uint64_t)f.total * ((row / 3 + 3) / 4) + SMX_STACK_BLOCK - 1) / SMX_STACK_BLOCK;
+      continue;
+    }
+    const uintptr_t both = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(s.dst) | (uintptr_t)row;
+    b.unit = (both & 15) == 0 ? 16 : (both & 3) == 0 ? 4 : 1;
+    b.block0 = (uint32_t)blocks;
+    blocks += ((uint64_t)f.total * (row / b.unit) + SMX_STACK_BLOCK - 1) / SMX_STACK_BLOCK;
+    f.b[f.n++] = b;
+  }
+  if (blocks >= (1ull << 31) || dstack_blocks >= (1ull << 31)) return fail(h, SMX_ERR_INVALID, "frame stack: the bound rows need more workgroups than a launch has");
+  if (f.n) hipLaunchKernelGGL(k_frame_push, dim3((unsigned)blocks), dim3(SMX_STACK_BLOCK), 0, stream, f);
+  if (d.n) {
+    void (*const dstack[])(FrameStackArgs) = {k_frame_dstack<2>, k_frame_dstack<3>, k_frame_dstack<4>, k_frame_dstack<5>,
+                                              k_frame_dstack<6>, k_frame_dstack<7>, k_frame_dstack<8>};
+    hipLaunchKernelGGL(dstack[c.frame_stack - 2], dim3((unsigned)dstack_blocks), dim3(SMX_STACK_BLOCK), 0, stream, d);
+  }
+  return SMX_OK;
+}
+
 static int check_buffers(smx_handle h, const smx_state* st, const smx_spawns* sp, const smx_outputs* o) {
   std::string msg;
   const int rc = check_buffers_impl(h->cfg, h->n_vias > 0, true, st, sp, o, msg);
@@ -6175,6 +6538,9 @@ static int check_buffers(smx_handle h, const smx_state* st, const smx_spawns* sp
     return fail(h, SMX_ERR_STATE, "lidar sensor enabled but smx_set_lidar_rays has not been called");
   if ((h->cfg.sensors & SMX_SENSOR_RGB) && !h->rgb_out)
     return fail(h, SMX_ERR_STATE, "rgb sensor enabled but no image buffer is bound (smx_set_rgb_output)");
+  for (const smx_handle_s::StackBinding& s : h->stacks)  // (an optional row the caller left NULL: nothing is launched)
+    if (s.source != SMX_STACK_SOURCE_RGB && !reinterpret_cast<const void* const*>(o)[s.source])
+      return fail(h, SMX_ERR_STATE, "frame stack: source " + std::to_string(s.source) + " is bound but its row is NULL in smx_outputs");
   return SMX_OK;
 }
 
@@ -6549,6 +6915,10 @@ static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const
   }
   rc = tail_and_reset_pass(h, p, a, mask, st, stream, ph);
   if (rc != SMX_OK) return rc;
+  if (p.frame_stack) {  // (after the reset pass: a restarted env's rows hold its first observation)
+    rc = launch_frame_stacks(h, is_step, mask, st, out, stream);
+    if (rc != SMX_OK) return rc;
+  }
   SMX_HIP(hipGetLastError());
   if (ph) {
     SMX_HIP(hipEventRecord(ph[SMX_PHASE_RESET + 1], stream));

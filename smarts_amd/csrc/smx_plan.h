@@ -76,6 +76,7 @@ struct PlanInputs {
   uint8_t* pending_blob;  // [total] seed_pending, or null
   SlowLists slow;         // (base null: no slow lists)
   int slow_parity;        // the counters this tick's one-lane kernels use
+  bool frame_stack_bound;  // smx_bind_frame_stack holds at least one buffer
 };
 
 enum class AliveList : uint8_t { NONE, CARRIED, BUILD };  // BUILD: k_alive_list ahead of the tick
@@ -143,6 +144,10 @@ struct TickPlan {
   // k_ego_frame (SMX_SENSOR_EGO_CENTRIC): the same two sites, after k_lane_ttc (both only read the world rows)
   bool ego_centric;
   unsigned ec_blocks, ec_first_blocks;
+  // k_frame_push / k_frame_dstack (smx_config.frame_stack with something bound): the last launches of the pass, on the
+  // caller's stream, after the observation pass has joined and after k_tail / the reset pass (they read the pass's
+  // finished rows, the flags it left, this tick's done row and env_done) — in a tick and in smx_reset, in either form
+  bool frame_stack;
   bool tail_builds_list;  // k_tail builds the next tick's alive list
   bool tail_grids;        // ... and the new vehicles' grid tiles
   bool reset_pass, lidar_first, first_walks_new;
@@ -301,6 +306,7 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
     p.ttc_first_blocks = p.reset_pass ? p.obs_blocks * (unsigned)(SMX_BLOCK / apb) : 0;  // an env group holds up to SMX_BLOCK vehicles
     p.ttc_lds = apb * smx_ttc_lds_per_agent(c.wp_paths, c.wp_len);
   }
+  p.frame_stack = c.frame_stack > 0 && in.frame_stack_bound;
   p.ego_centric = (c.sensors & SMX_SENSOR_EGO_CENTRIC) != 0;
   if (p.ego_centric) {
     const size_t apb = SMX_BLOCK / SMX_EC_TEAM;

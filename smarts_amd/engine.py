@@ -88,6 +88,12 @@ class SimConfig:
     # out["ec_flags"], out["ec_ego_f32"] and an out["ec_*"] twin of every position / heading row whose sensor is on
     # (include/smx.h SMX_SENSOR_EGO_CENTRIC); actions_to_world turns ego-frame actions back
     ego_centric: bool = False
+    # FrameStack (smarts/env/wrappers/frame_stack.py) on the device: 0 = off, 2..8 = frames kept, newest first, of every
+    # row named in frame_stack_rows — out["stack_<row>"], [E, N, k, ...row shape]; frame_stack_rgb_dstack adds
+    # out["rgb_dstack"], [E, N, H, W, 3k]: the array RGBImage returns (include/smx.h smx_bind_frame_stack)
+    frame_stack: int = 0
+    frame_stack_rows: Sequence[str] = ()
+    frame_stack_rgb_dstack: bool = False
 
     def sensors_mask(self) -> int:
         m = 0
@@ -264,6 +270,11 @@ class BatchedSim:
             c.rw_horizon, c.rw_lanes, c.rw_paths = int(cfg.rw_horizon), int(cfg.rw_lanes), int(cfg.rw_paths)
         if cfg.rgb:
             c.rgb_width, c.rgb_height, c.rgb_resolution = int(cfg.rgb_width), int(cfg.rgb_height), float(cfg.rgb_resolution)
+        if cfg.frame_stack == 1 or not 0 <= cfg.frame_stack <= nat.STACK_MAX_FRAMES:
+            raise ValueError(f"frame_stack must be 0 (off) or 2..{nat.STACK_MAX_FRAMES} (the reference asserts num_stack > 1)")
+        if (cfg.frame_stack_rows or cfg.frame_stack_rgb_dstack) and not cfg.frame_stack:
+            raise ValueError("frame_stack_rows / frame_stack_rgb_dstack need SimConfig(frame_stack >= 2)")
+        c.frame_stack = int(cfg.frame_stack)
         self._c = c
         self.handle = C.c_void_p()
         rc = self.lib.smx_create(C.byref(c), idx, C.byref(self.handle))
@@ -423,6 +434,18 @@ class BatchedSim:
             # not a member of smx_outputs (its pointer list is closed): a buffer of its own, bound to the handle
             o["rgb"] = z((E, N, cfg.rgb_height, cfg.rgb_width, 3), torch.uint8)
             self.bind_rgb(o["rgb"])
+        if cfg.frame_stack:
+            if cfg.frame_stack_rgb_dstack and not cfg.rgb:
+                raise ValueError("frame_stack_rgb_dstack needs SimConfig(rgb=True)")
+            for row in cfg.frame_stack_rows:
+                nat.stack_source(row)  # (a row that cannot be stacked: ValueError)
+                if row not in o:
+                    raise ValueError(f"frame_stack_rows: {row!r} is not a row of this configuration (its sensor is off)")
+            for row in cfg.frame_stack_rows:
+                self.bind_frame_stack(row, z((E, N, cfg.frame_stack) + tuple(o[row].shape[2:]), o[row].dtype))
+            if cfg.frame_stack_rgb_dstack:
+                self.bind_frame_stack("rgb", z((E, N, cfg.rgb_height, cfg.rgb_width, 3 * cfg.frame_stack), torch.uint8),
+                                      layout="dstack")
         self._stream = None
         self._was_reset = False
 
@@ -431,7 +454,8 @@ class BatchedSim:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def output_bytes_per_agent_step(self) -> int:
-        """Bytes of observation/reward/done written per agent-step (dense layout)."""
+        """Bytes of observation/reward/done written per agent-step (dense layout); with frame stacking on, the k
+        frames of every stack the pass rewrites among them."""
         per = 0
         for name, t in self.out.items():
             if name in ("env_done", "learner") or name.startswith("final_"):
@@ -449,7 +473,8 @@ class BatchedSim:
         (L2 / Infinity-Cache resident) and the hand-off buffers between the kernels of a tick (path seeds,
         road facts: ``handoff_bytes_per_agent_step``) — traffic this design adds, not traffic the path needs."""
         o = {k: (t[0, 0].numel() * t.element_size()) for k, t in self.out.items()
-             if k not in ("env_done", "learner") and not k.startswith("final_")}  # (final_*: copied for restarting envs only)
+             if k not in ("env_done", "learner", "rgb_dstack")
+             and not k.startswith(("final_", "stack_"))}  # (final_*: copied for restarting envs only; the stacks: below)
         pose = 3 * 8 + 4  # x, y, heading + flags: what every sensor kernel reads of a vehicle
         ctrl_state = 14 * 8 + 4  # SMX_S_X .. SMX_S_MCL_Y + flags: read and written back by k_control
         obs_state_r, obs_state_w = 16 * 8 + 4 + 4, 12 * 8 + 4  # trip meter / accelerometer / driven-path fields, steps
@@ -476,6 +501,9 @@ class BatchedSim:
             kb["sensors"] = add(kb["sensors"], ogm)
         if self.cfg.lidar is not None:
             kb["sensors"] = add(kb["sensors"], (pose, o["lidar_hit"] + o["lidar_point"]))
+        stacks = sum(t[0, 0].numel() * t.element_size() for k, t in self.out.items() if k.startswith("stack_") or k == "rgb_dstack")
+        if stacks:  # k_frame_push / k_frame_dstack shift in place: k frames read (k - 1 old, one new), k written
+            kb["frame_stack"] = (stacks + 4 + 1, stacks)
         return kb
 
     def set_missions(self, missions: Optional[Sequence]):
@@ -535,6 +563,33 @@ class BatchedSim:
         rc = self.lib.smx_set_rgb_output(self.handle, images.data_ptr(), int(images.numel()))
         nat.check(self.lib, self.handle, rc, "smx_set_rgb_output")
         self.out["rgb"] = images
+
+    def bind_frame_stack(self, row: str, stack: Optional[torch.Tensor], layout: str = "frames"):
+        """Bind the frame stack of ``out[row]`` (``smx_bind_frame_stack``; needs ``SimConfig(frame_stack=k)``): a
+        contiguous device tensor of the row's dtype, ``[E, N, k, ...row shape]`` for ``layout="frames"`` or, for the
+        image alone, ``[E, N, H, W, 3k]`` uint8 for ``layout="dstack"``; ``None`` unbinds.  The device keeps the last k
+        frames of the row in it, newest first; ``out["stack_<row>"]`` (``out["rgb_dstack"]``) follows."""
+        key = "rgb_dstack" if layout == "dstack" else "stack_" + row
+        if layout not in nat.STACK_LAYOUTS:
+            raise ValueError(f"layout must be one of {sorted(nat.STACK_LAYOUTS)}")
+        source, code = nat.stack_source(row), nat.STACK_LAYOUTS[layout]
+        if stack is None:
+            nat.check(self.lib, self.handle, self.lib.smx_bind_frame_stack(self.handle, source, code, None, 0), "smx_bind_frame_stack")
+            self.out.pop(key, None)
+            return
+        if row not in self.out:
+            raise ValueError(f"{row!r} is not a row of this configuration (its sensor is off)")
+        if layout == "dstack" and row != "rgb":
+            raise ValueError("layout='dstack' is the image's alone (row 'rgb')")
+        k, src = self.cfg.frame_stack, self.out[row]
+        want = (tuple(src.shape[:4]) + (3 * k,)) if layout == "dstack" else (self.E, self.N, k) + tuple(src.shape[2:])
+        if not self.cfg.frame_stack:
+            want = tuple(stack.shape)  # (the library refuses the bind: SMX_ERR_STATE)
+        if stack.dtype != src.dtype or not stack.is_cuda or not stack.is_contiguous() or tuple(stack.shape) != want:
+            raise ValueError(f"the {key} buffer must be a contiguous {src.dtype} device tensor of shape {want}")
+        rc = self.lib.smx_bind_frame_stack(self.handle, source, code, stack.data_ptr(), int(stack.numel() * stack.element_size()))
+        nat.check(self.lib, self.handle, rc, "smx_bind_frame_stack")
+        self.out[key] = stack
 
     def small_form(self) -> bool:
         """Whether a tick runs in the SMALL launch form (smx_plan.h: SMX_LARGE_BATCH_VEHICLES)."""

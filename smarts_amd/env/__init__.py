@@ -1,5 +1,5 @@
 """Host-side mirror of the reference's environment surface for the accelerated path
-(``smarts.env:hiway-v0``, ``AgentSpec`` / ``AgentInterface``, ``ParallelEnv``, ``FormatObs``)."""
+(``smarts.env:hiway-v0``, ``AgentSpec`` / ``AgentInterface``, ``ParallelEnv``, ``FormatObs``, ``FrameStack``, ``RGBImage``, ``SingleAgent``)."""
 from .agent import Agent, AgentSpec  # noqa: F401
 from .agent_interface import (  # noqa: F401
     OGM, RGB, Accelerometer, ActionSpaceType, AgentInterface, AgentType, DoneCriteria, DrivableAreaGridMap,
@@ -15,6 +15,7 @@ from .observations import (  # noqa: F401
 )
 from ..vias import Via  # noqa: F401
 from .parallel_env import ParallelEnv  # noqa: F401
+from .wrappers import FrameStack, RGBImage, SingleAgent  # noqa: F401
 
 
 def make(env_id: str, **kwargs) -> HiWayEnv:

@@ -175,7 +175,8 @@ class FormatObs:
 
     # -------------------------------------------------------------- dense rows -> StdObs, no objects
     @staticmethod
-    def from_rows(rows: Dict[str, np.ndarray], env: int, slot: int, ego_centric: bool = False) -> StdObs:
+    def from_rows(rows: Dict[str, np.ndarray], env: int, slot: int, ego_centric: bool = False,
+                  frame: Optional[int] = None) -> StdObs:
         """Slice ``StdObs`` of agent (env, slot) straight out of host copies of the dense device
         rows.  The ttc block comes from ``rows["lane_ttc"]`` / ``rows["lane_ttc_flags"]`` where the rows hold them
         (``SimConfig(lane_ttc=True)``, or ``lane_ttc_rows`` on the host) and the agent's flags say the reference's
@@ -183,8 +184,16 @@ class FormatObs:
         objects).  ``ego_centric``: the position, heading and linear velocity / acceleration / jerk fields come from the
         ``ec_*`` rows (``SimConfig(ego_centric=True)``, or ``ego_centric_rows`` on the host) — ``StdObs`` of the
         observation ``ego_centric_observation_adapter`` returns; everything else is frame-independent and read from
-        the world rows (the ttc block included: ``lane_ttc`` of the world rows)."""
+        the world rows (the ttc block included: ``lane_ttc`` of the world rows).  ``frame``: read frame ``frame``
+        (0 = newest) of the stacked rows ``rows["stack_<row>"]`` (``SimConfig(frame_stack=k)``, or ``frame_stack_rows``
+        on the host) wherever the rows hold them, the unstacked row elsewhere; ``None``: the unstacked rows."""
         E = nat.EGO
+        if frame is not None:
+            rows = dict(rows)
+            for key in [k for k in rows if k.startswith("stack_")]:
+                if not 0 <= frame < rows[key].shape[2]:
+                    raise ValueError(f"frame {frame} of a stack of {rows[key].shape[2]}")
+                rows[key[len("stack_"):]] = rows[key][:, :, frame]
         if ego_centric:
             if "ec_flags" not in rows or not int(rows["ec_flags"][env, slot]) & nat.EC_VALID:
                 raise ValueError(f"agent ({env}, {slot}) has no ego-centric rows (ec_flags)")
