@@ -312,7 +312,8 @@ enum { SMX_S_KIN_RAW_HEADING = SMX_S_DELTA, SMX_S_KIN_LAST_HEADING = SMX_S_LAT_I
 enum {
   SMX_F_ALIVE = 1 << 0,
   SMX_F_MCL_SET = 1 << 1,
-  SMX_F_RESERVED2 = 1 << 2, /* (was the trip-meter bit; now facts_i32[SMX_FI_TRIP_HAS_WP]) */
+  SMX_F_GUARDED = 1 << 2, /* the state guard has ended this agent (smx_set_guard): done at its next observation; cleared
+                             when the slot's vehicle is created again.  Never set while the guard is off. */
   SMX_F_HIST_SHIFT = 3, /* bits 3-4: accelerometer samples held (0..2) */
   SMX_F_FIRST = 1 << 5, /* vehicle was just (re)created: its next observation is a reset observation */
   SMX_F_SOCIAL = 1 << 6 /* scripted social vehicle (no controller, no observation) */
@@ -594,6 +595,41 @@ int smx_set_lidar_rays(smx_handle h, const double* rays_dev, int32_t n_rays);
  * (with the bit off any count passes).  SMX_OK, or SMX_ERR_INVALID with the reason in err[err_len]. */
 int smx_set_rgb_output(smx_handle h, uint8_t* rgb_dev, uint64_t count);
 int smx_check_rgb_output(const smx_config* cfg, uint64_t count, char* err, uint64_t err_len);
+/* The state guard, off by default.  State rows, spawn tables and action buffers are the caller's; while a guard buffer
+ * is bound, no alive agent vehicle's pose reaches a map search, a sensor or another vehicle's sensor unless it is IN
+ * BOUNDS: the seven words x, y, heading, u, v, r, delta of its state finite (a kinematic agent: x, y, heading, u; a
+ * spawn row: its four words) and (x, y) inside the guard box — the union of the extents of the map's lanepoint grid
+ * (lpg_*) and segment grid (sg_*), grown by `margin` metres on every side.  The offending agent's episode ends instead
+ * (the reference destroys the simulation and asks for a reset, smarts.py:214-227, 1014-1046):
+ *   - every smx_reset / smx_step* pass writes guard_dev[e * N + slot] for every slot: 0 for a social slot, an agent
+ *     absent from the pass and an agent in bounds, else the bits below;
+ *   - SMX_GUARD_STEP: all state rows 0 .. SMX_S_MCL_Y and the flags word keep their values from the start of the tick
+ *     (the flags word gains SMX_F_GUARDED); the kinematic spaces' "not finite -> no action" (smx_sync) is unchanged;
+ *   - SMX_GUARD_STATE: neither controller nor dynamics run; the vehicle is parked — the pose of lanepoint 0
+ *     (lp_rec[0], always on the map), velocities, yaw rate and steer 0, the controller state as after a reset;
+ *   - SMX_GUARD_SPAWN: the vehicle is created parked; the bit is reported by the reset pass and again by the first
+ *     step, whose observation ends the agent (reset passes report no done);
+ *   - the agent's observation is built from the held or parked pose like any other (`events` is whatever that pose
+ *     yields; no tenth event column), with done = 1 and active = 0; it counts in env_done_count, its vehicle is removed
+ *     like any done agent's, and under auto_reset the env restarts as usual.
+ * The same launches run either way; with the guard off the kernels are the ones without it (a compile-time choice).
+ * Out of scope: social slots (the library derives their pose from its own tables), the controller-state rows as such
+ * (a NaN there surfaces as SMX_GUARD_STEP one tick later) and what smx_sync reports (unchanged).
+ * `margin`: finite, 0 <= margin <= SMX_GUARD_MARGIN_MAX.  The cap keeps the cell index of every in-bounds point inside
+ * int32 with room to spare and bounds every ring loop of the searches: |index| <= (2.5 side + 1024) / cell + 1, `side`
+ * the longer side of the grown box and `cell` the smaller of the two grids' cells, must stay below 2^30 — checked
+ * against the map here, and by smx_load_map when the guard is bound first (which also recomputes the box for a new map
+ * and keeps the guard bound).  At 1.0e6 m and cells of a metre or more that leaves room for a map 4.2e8 m across; the
+ * derivation is in smarts_amd/csrc/smx_guard.h.  guard_dev = NULL switches the guard off.  smx_check_guard is the
+ * validation alone (count >= E * N, the margin), callable without a device or a handle: SMX_OK, or SMX_ERR_INVALID
+ * with the reason in err[err_len]. */
+enum { SMX_GUARD_STEP = 1 << 0,   /* this tick's step produced an out-of-bounds state: not stored, the vehicle is held */
+       SMX_GUARD_STATE = 1 << 1,  /* the state at the start of the tick was out of bounds already (the caller wrote it) */
+       SMX_GUARD_SPAWN = 1 << 2   /* the spawn row of this episode was out of bounds */ };
+#define SMX_GUARD_MARGIN_DEFAULT 1000.0
+#define SMX_GUARD_MARGIN_MAX 1.0e6
+int smx_set_guard(smx_handle h, uint8_t* guard_dev, uint64_t count, double margin);   /* [E*N]; NULL = guard off */
+int smx_check_guard(const smx_config* cfg, uint64_t count, double margin, char* err, uint64_t err_len);
 /* Frame stacking (smx_config.frame_stack = k): for every agent the device keeps the last k frames of each bound row,
  * newest first (frame 0 is this pass's row), in a caller-owned device buffer.  At the end of every smx_reset / smx_step*
  * pass, on the caller's stream, once every row of the pass is complete (under auto_reset: after the reset pass has

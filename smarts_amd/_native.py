@@ -50,6 +50,10 @@ STATE_FIELDS = ["X", "Y", "HEADING", "U", "V", "R", "DELTA", "LAT_INT", "SPD_INT
 S = {name: i for i, name in enumerate(STATE_FIELDS)}
 S_COUNT = len(STATE_FIELDS)
 F_ALIVE, F_MCL_SET, F_TRIP_HAS_WP, F_HIST_SHIFT, F_FIRST, F_SOCIAL = 1, 2, 4, 3, 32, 64
+F_GUARDED = 4  # SMX_F_GUARDED: the bit F_TRIP_HAS_WP once named (that name is kept for older callers; the library never set it)
+# the state guard (smx_set_guard): bits of the per-agent byte, the default and the largest margin (metres)
+GUARD_STEP, GUARD_STATE, GUARD_SPAWN = 1, 2, 4
+GUARD_MARGIN_DEFAULT, GUARD_MARGIN_MAX = 1000.0, 1.0e6
 FACT_I_COUNT, FACT_F_COUNT = 7, 2
 DRIVEN_PATH_LEN = 500
 SEED_COUNT = 9
@@ -182,7 +186,7 @@ EXPORTS = [
     "smx_set_timing", "smx_last_error", "smx_version", "smx_destroy", "smx_set_controller_gains", "smx_struct_size", "smx_read_step_ms",
     "smx_check_buffers", "smx_set_launch_strategy", "smx_launch_form", "smx_step_target_pose", "smx_step_trajectory_with_time",
     "smx_set_mission_goals", "smx_check_mission_goals", "smx_actions_to_world", "smx_set_rgb_output", "smx_check_rgb_output",
-    "smx_bind_frame_stack", "smx_check_frame_stack",
+    "smx_bind_frame_stack", "smx_check_frame_stack", "smx_set_guard", "smx_check_guard",
 ]
 LAUNCH_FORMS = {0: "small", 1: "large_teams", 2: "large_one_lane"}
 LAUNCH_STRATEGIES = {"auto": 0, "small": 1, "large": 2, "large_one_lane": 3, "large_teams": 4}
@@ -262,6 +266,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.smx_bind_frame_stack.restype = C.c_int
     lib.smx_check_frame_stack.argtypes = [C.POINTER(SmxConfig), _i32, _i32, C.c_uint64, C.c_char_p, C.c_uint64]
     lib.smx_check_frame_stack.restype = C.c_int
+    lib.smx_set_guard.argtypes = [h, _p, C.c_uint64, _f64]
+    lib.smx_set_guard.restype = C.c_int
+    lib.smx_check_guard.argtypes = [C.POINTER(SmxConfig), C.c_uint64, _f64, C.c_char_p, C.c_uint64]
+    lib.smx_check_guard.restype = C.c_int
     lib.smx_read_phase_ms.argtypes = [h, C.POINTER(C.c_float), _i32, C.POINTER(_i32)]
     lib.smx_read_phase_ms.restype = C.c_int
     lib.smx_set_timing.argtypes = [h, C.c_int]

@@ -34,6 +34,7 @@
 #include <string>
 #include <vector>
 
+#include "smx_guard.h"
 #include "smx_plan.h"
 #include "smx_scan.h"
 #include "smx_vehicle.h"
@@ -88,6 +89,10 @@ struct KernelArgs {
   int32_t* slow_count;
   // [E*N], 1: the vehicle's path seeds, walks and rows are the slow chain's this tick (k_scan_fast<1> decides; null: none)
   uint8_t* seed_pending;
+  // the state guard (smx_set_guard; smx_guard.h): the per-agent byte and the box a vehicle state has to lie in.  Read by
+  // the GUARD instantiations of the control, reset and tail kernels only (null: the plan launches the others).
+  uint8_t* guard;
+  GuardBox guard_box;
 };
 enum {
   SMX_DEVICE_BAD_LANE_ACTION = 1,  // a Lane action code outside -1..3 was met (and treated as "no action")
@@ -326,6 +331,46 @@ __device__ __forceinline__ void store_vehicle_state(const KernelArgs& a, size_t 
   SF(SMX_S_MCL_X) = cs.mcl_x;
   SF(SMX_S_MCL_Y) = cs.mcl_y;
   a.st.flags[gid] = cs.mcl_set ? (flags | SMX_F_MCL_SET) : (flags & ~SMX_F_MCL_SET);
+}
+
+// ---- the state guard's steps in the control phase (GUARD instantiations only; smx_guard.h holds the test and the table)
+// The parked vehicle: lanepoint 0's pose at rest, state and controller words as after a reset (respawn_vehicle), the
+// previous-observation position at the same place (the driven path then sees a step of length 0, not the bad pose).
+__device__ __forceinline__ void guard_park(const KernelArgs& a, size_t gid, size_t total, int flags, uint8_t byte) {
+  const GuardParked p = guard_parked_pose(a.map.lp_rec[0]);
+  for (int f = SMX_S_X; f <= SMX_S_MCL_Y; ++f) SF(f) = 0.0;
+  SF(SMX_S_X) = p.x;
+  SF(SMX_S_Y) = p.y;
+  SF(SMX_S_HEADING) = p.heading;
+  if (smx_kinematic_space(a.cfg.action_space)) SF(SMX_S_KIN_RAW_HEADING) = p.heading;
+  SF(SMX_S_PREV_X) = p.x;
+  SF(SMX_S_PREV_Y) = p.y;
+  a.st.flags[gid] = (flags & ~SMX_F_MCL_SET) | SMX_F_GUARDED;
+  a.guard[gid] = byte;
+}
+// The verdict at the load: may the controller, its path search and the dynamics run for this vehicle?  (No writes: the
+// teams of k_control and k_control_paths ask with every lane.)
+__device__ __forceinline__ GuardVerdict guard_at_load(const KernelArgs& a, int flags, const VehState& s) {
+  return guard_resolve((flags & SMX_F_GUARDED) != 0, guard_in_bounds(a.guard_box, s), true);
+}
+// ... carried out by the one lane that owns the vehicle's words when the answer is no: parked, or held (a parked spawn
+// waiting for its first observation with done: nothing moves).
+__device__ __forceinline__ void guard_refuse(const KernelArgs& a, size_t gid, size_t total, int flags, const GuardVerdict v) {
+  if (v.action == GUARD_PARK) {
+    guard_park(a, gid, total, flags, v.byte);
+  } else {
+    a.guard[gid] = v.byte;
+    a.st.flags[gid] = flags | SMX_F_GUARDED;
+  }
+}
+// The verdict on the stepped state, ahead of store_vehicle_state: true = store it.  Held: the state rows, the controller
+// rows and the flags word keep what they held at the start of the tick, but for SMX_F_GUARDED.
+__device__ __forceinline__ bool guard_before_store(const KernelArgs& a, size_t gid, int flags, const VehState& s) {
+  const GuardVerdict v = guard_resolve(false, true, guard_in_bounds(a.guard_box, s));
+  a.guard[gid] = v.byte;
+  if (v.action == GUARD_STORE) return true;
+  a.st.flags[gid] = flags | SMX_F_GUARDED;
+  return false;
 }
 
 // Controllers.perform_action's decoding of a Lane / LaneWithContinuousSpeed action (controllers/__init__.py:113-144),
@@ -619,7 +664,9 @@ __device__ __forceinline__ void ctrl_waypoints_from_knots(const KernelArgs& a, s
 // put at a run-time index is a 17-way compare / select chain over every live element (~90
 // instructions per waypoint); the LDS copy costs 26 KB per workgroup, which would halve the
 // wavefronts per CU on large batches, so those keep the register form.
-template <int SPACE, bool LDS_PATH = false>
+// GUARD (every control kernel and k_reset / k_tail): the state guard as a compile-time choice — the plan launches the
+// GUARD instantiation while a guard buffer is bound, and the other one is the kernel without a guard, word for word.
+template <int SPACE, bool LDS_PATH = false, bool GUARD = false>
 __global__ void __attribute__((amdgpu_waves_per_eu(2, 8))) __launch_bounds__(SMX_BLOCK) k_control(const KernelArgs a) {
   __shared__ int knot_scratch[SMX_MAX_KNOTS * SMX_BLOCK];
   __shared__ double path_lds[LDS_PATH ? 3 * SMX_CTRL_WPS * SMX_BLOCK : 1];
@@ -650,6 +697,13 @@ __global__ void __attribute__((amdgpu_waves_per_eu(2, 8))) __launch_bounds__(SMX
   }
   SMX_TSTAMP(tc0);
   VehState s = load_vehicle(a, gid, total);
+  if constexpr (GUARD) {
+    const GuardVerdict gv = guard_at_load(a, flags, s);  // (the same for the team's four lanes)
+    if (gv.action != GUARD_STORE) {
+      if (p0 == 0) guard_refuse(a, gid, total, flags, gv);
+      return;
+    }
+  }
   CtrlState cs = load_ctrl_state(a, gid, total, flags);
   // ---- Controllers.perform_action (controllers/__init__.py:61-152)
   constexpr int space = SPACE;
@@ -743,6 +797,8 @@ __global__ void __attribute__((amdgpu_waves_per_eu(2, 8))) __launch_bounds__(SMX
   if (!SMX_SKIP(a, 2097152)) vehicle_step(s, co, c.dt);
   SMX_TSTAMP(tc6);
   SMX_TACC(19, tc5, tc6);
+  if constexpr (GUARD)
+    if (!guard_before_store(a, gid, flags, s)) return;
   store_vehicle_state(a, gid, total, s, cs, flags);
   SMX_TSTAMP(tc7);
   SMX_TACC(20, tc0, tc7);
@@ -761,7 +817,7 @@ struct CtrlHandoff {
   int32_t* n;    // [E*N] waypoints held; 0 = no path found (the reference asserts; the last command is kept)
 };
 
-template <int SPACE>
+template <int SPACE, bool GUARD>
 __device__ __forceinline__ void control_paths_for(const KernelArgs& a, const CtrlHandoff& ho, const size_t gid, int* knots) {
   const smx_config& c = a.cfg;
   const MapDev& m = a.map;
@@ -770,6 +826,8 @@ __device__ __forceinline__ void control_paths_for(const KernelArgs& a, const Ctr
   if (gid >= total) return;  // whole teams leave together
   const int flags = a.st.flags[gid];
   if (!(flags & SMX_F_ALIVE) || (flags & SMX_F_SOCIAL)) return;
+  if constexpr (GUARD)  // no path search for a vehicle the law kernel will park or hold
+    if (guard_at_load(a, flags, load_vehicle(a, gid, total)).action != GUARD_STORE) return;
   const LaneAction la = load_lane_action<SPACE>(a, gid);
   if (!la.has_action) return;  // uniform within a team
   const PathSeeds seed = load_seeds(a, gid, total);  // found by k_scan at this very pose
@@ -846,16 +904,16 @@ __device__ __forceinline__ void control_paths_for(const KernelArgs& a, const Ctr
 // (the list form is a kernel of its own: with both forms in one kernel the role was inlined twice and the team cut's
 // launch paid for it — 111 -> 137 registers here, 168 -> 256 in k_control_law, one wavefront per SIMD: C5's control
 // phase 0.169 -> 0.209 ms)
-template <int SPACE>
+template <int SPACE, bool GUARD = false>
 __global__ void __launch_bounds__(SMX_BLOCK) k_control_paths(const KernelArgs a, const CtrlHandoff ho) {
   __shared__ int knot_scratch[SMX_MAX_KNOTS * SMX_BLOCK];
   const size_t total = (size_t)a.cfg.num_envs * a.cfg.num_vehicles;
-  control_paths_for<SPACE>(a, ho, launch_vehicle(a, ((size_t)blockIdx.x * SMX_BLOCK + threadIdx.x) / SMX_WP_LANES, total), knot_scratch + threadIdx.x);
+  control_paths_for<SPACE, GUARD>(a, ho, launch_vehicle(a, ((size_t)blockIdx.x * SMX_BLOCK + threadIdx.x) / SMX_WP_LANES, total), knot_scratch + threadIdx.x);
 }
 
 // Control law + vehicle dynamics, one lane per vehicle (see k_control_paths).  Every action space; the
 // lane-following ones read the wanted path from the hand-off.
-template <int SPACE>
+template <int SPACE, bool GUARD>
 __device__ __forceinline__ void control_law_for(const KernelArgs& a, const CtrlHandoff& ho, const size_t gid) {
   const smx_config& c = a.cfg;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
@@ -867,6 +925,13 @@ __device__ __forceinline__ void control_law_for(const KernelArgs& a, const CtrlH
     return;
   }
   VehState s = load_vehicle(a, gid, total);
+  if constexpr (GUARD) {
+    const GuardVerdict gv = guard_at_load(a, flags, s);
+    if (gv.action != GUARD_STORE) {
+      guard_refuse(a, gid, total, flags, gv);
+      return;
+    }
+  }
   CtrlState cs = load_ctrl_state(a, gid, total, flags);
   ControlOut co = idle_command(cs);
   constexpr bool lane_following = SPACE == SMX_ACTION_SPACE_LANE || SPACE == SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED;
@@ -904,12 +969,14 @@ __device__ __forceinline__ void control_law_for(const KernelArgs& a, const CtrlH
   SF(SMX_S_PREV_X) = s.x;  // the position recorded by the previous observation
   SF(SMX_S_PREV_Y) = s.y;
   vehicle_step(s, co, c.dt);
+  if constexpr (GUARD)
+    if (!guard_before_store(a, gid, flags, s)) return;
   store_vehicle_state(a, gid, total, s, cs, flags);
 }
 
-template <int SPACE>
+template <int SPACE, bool GUARD = false>
 __global__ void __launch_bounds__(SMX_BLOCK) k_control_law(const KernelArgs a, const CtrlHandoff ho) {
-  control_law_for<SPACE>(a, ho, (size_t)blockIdx.x * SMX_BLOCK + threadIdx.x);
+  control_law_for<SPACE, GUARD>(a, ho, (size_t)blockIdx.x * SMX_BLOCK + threadIdx.x);
 }
 // =================================================================================
 // k_control_kinematic: the kinematic action spaces, one lane per vehicle, in the place of controller + vehicle_step.
@@ -988,7 +1055,7 @@ __device__ __forceinline__ bool interpolate_trajectory(const double* tr, int n, 
   return true;
 }
 
-template <int SPACE>
+template <int SPACE, bool GUARD = false>
 __global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic(const KernelArgs a) {
   const smx_config& c = a.cfg;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
@@ -1001,6 +1068,23 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic(const KernelArg
     return;
   }
   const double x = SF(SMX_S_X), y = SF(SMX_S_Y);
+  if constexpr (GUARD) {
+    // the kinematic vehicle's words: x, y, heading, speed
+    const GuardVerdict gv = guard_resolve((flags & SMX_F_GUARDED) != 0, guard_in_bounds_kin(a.guard_box, x, y, SF(SMX_S_HEADING), SF(SMX_S_U)), true);
+    if (gv.action != GUARD_STORE) {
+      guard_refuse(a, gid, total, flags, gv);
+      return;
+    }
+    a.guard[gid] = 0;  // (the tick may end below without a placement: no action, an action the reference raises on)
+  }
+  // the placement's test, ahead of its first store: held = nothing of the vehicle is stored
+  auto guard_holds = [&](const KinPose& q) {
+    const GuardVerdict gv = guard_resolve(false, true, guard_in_bounds_kin(a.guard_box, q.x, q.y, q.heading, q.speed));
+    if (gv.action == GUARD_STORE) return false;
+    a.guard[gid] = gv.byte;
+    a.st.flags[gid] = flags | SMX_F_GUARDED;
+    return true;
+  };
   SF(SMX_S_PREV_X) = x;  // the position recorded by the previous observation
   SF(SMX_S_PREV_Y) = y;
   KinPose o;
@@ -1021,6 +1105,8 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic(const KernelArg
     // no target pose from the agent: the pose the provider holds, dt ahead (_normalize_target_pose, :119-129) — the
     // vehicle stays, its speed is 0, and control() is still called
     if (!given) o = bezier_first_point(x, y, raw, x, y, raw, c.dt, c.dt);
+    if constexpr (GUARD)
+      if (guard_holds(o)) return;
     SF(SMX_S_KIN_RAW_HEADING) = o.heading;
   } else if (SPACE == SMX_ACTION_SPACE_IMITATION) {
     // ImitationController.perform_action on a BoxChassis (imitation_controller.py:50-78)
@@ -1062,6 +1148,8 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic(const KernelArg
       return;
     }
   }
+  if constexpr (GUARD && SPACE != SMX_ACTION_SPACE_TARGET_POSE)
+    if (guard_holds(o)) return;
   // Vehicle.control(pose, speed, dt) -> BoxChassis.control (vehicle.py:578, chassis.py:211-217)
   SF(SMX_S_KIN_LAST_HEADING) = SF(SMX_S_HEADING);
   SF(SMX_S_KIN_LAST_DT) = c.dt;
@@ -1078,17 +1166,17 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic(const KernelArg
 // their control law + dynamics on sixteen lanes, the wanted path passed through the hand-off in device memory.  (One
 // launch: the list is under 1 % of the vehicles on a map whose lanes do not split, and a second launch over it was
 // a launch boundary on the tick's longest chain.)
-template <int SPACE>
+template <int SPACE, bool GUARD = false>
 __global__ void __launch_bounds__(SMX_BLOCK) k_control_listed(const KernelArgs a, const CtrlHandoff ho) {
   __shared__ int knot_scratch[SMX_MAX_KNOTS * SMX_BLOCK];
   constexpr int VPB = SMX_BLOCK / SMX_WP_LANES;
   const int count = *a.slow_count;
   for (int i0 = (int)blockIdx.x * VPB; i0 < count; i0 += (int)gridDim.x * VPB) {  // (uniform in the workgroup)
     const int i = i0 + (int)threadIdx.x / SMX_WP_LANES;
-    if (i < count) control_paths_for<SPACE>(a, ho, (size_t)a.slow_list[i], knot_scratch + threadIdx.x);
+    if (i < count) control_paths_for<SPACE, GUARD>(a, ho, (size_t)a.slow_list[i], knot_scratch + threadIdx.x);
     __threadfence_block();
     __syncthreads();
-    if ((int)threadIdx.x < VPB && i0 + (int)threadIdx.x < count) control_law_for<SPACE>(a, ho, (size_t)a.slow_list[i0 + threadIdx.x]);
+    if ((int)threadIdx.x < VPB && i0 + (int)threadIdx.x < count) control_law_for<SPACE, GUARD>(a, ho, (size_t)a.slow_list[i0 + threadIdx.x]);
   }
 }
 
@@ -1102,7 +1190,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_listed(const KernelArgs a
 // cannot be reused — a new vehicle, a branching inside the lookahead, a road of more than four lanes — goes to the
 // slow list and through k_control_paths / k_control_law as before.
 // =================================================================================
-template <int SPACE>
+template <int SPACE, bool GUARD = false>
 __global__ void __launch_bounds__(SMX_BLOCK) k_control_fast(const KernelArgs a) {
   SMX_TSTAMP(span0);
   // the wanted path's waypoints, [element][lane]: 17 headings, then x and y of the first ten (lane_following_from_path
@@ -1147,8 +1235,12 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_fast(const KernelArgs a) 
     kn_end16[q] = lists ? a.knots.end16[pth] : -1;
   }
   if (in_range && (flags & SMX_F_ALIVE)) {
+    GuardVerdict gv = {0, GUARD_STORE};
+    if constexpr (GUARD) gv = guard_at_load(a, flags, s);
     if (flags & SMX_F_SOCIAL) {
       social_vehicle_step(a, gid, total, cs.mcl_x, cs.mcl_y, cs.spd_int, cs.throttle, s.x, s.y);
+    } else if (GUARD && gv.action != GUARD_STORE) {
+      guard_refuse(a, gid, total, flags, gv);  // (never on the slow list: no search sees the pose)
     } else {
       const LaneAction la = decode_lane_action<SPACE>(a, action, act0, act1);  // (on the words loaded above)
       const bool has_action = la.has_action;
@@ -1246,7 +1338,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_fast(const KernelArgs a) 
         SF(SMX_S_PREV_X) = s.x;  // the position recorded by the previous observation
         SF(SMX_S_PREV_Y) = s.y;
         if (!SMX_SKIP(a, 1 << 27)) vehicle_step(s, co, c.dt);
-        store_vehicle_state(a, gid, total, s, cs, flags);
+        if (!GUARD || guard_before_store(a, gid, flags, s)) store_vehicle_state(a, gid, total, s, cs, flags);
       }
     }
   }
@@ -3119,20 +3211,41 @@ __device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const i
 // =================================================================================
 // A vehicle of a freshly reset env: state from the spawn table row of `episode`
 // (SMARTS.reset / TrapManager, smarts.py:365-460, trap_manager.py:212-230).
+// (GUARD: an agent's spawn row that is out of bounds — smx_guard.h — creates the vehicle parked at lanepoint 0 at rest,
+// flagged SMX_F_GUARDED, its byte SMX_GUARD_SPAWN; a social slot's pose comes from the library's own tables)
+template <bool GUARD>
 __device__ __forceinline__ void respawn_vehicle(const KernelArgs& a, size_t gid, size_t total, int episode) {
   const int row = a.sp.episodes > 0 ? (((episode % a.sp.episodes) + a.sp.episodes) % a.sp.episodes) : 0;
   const double* sp = a.sp.pose + ((size_t)row * total + gid) * 4;
   for (int f = 0; f < SMX_S_COUNT; ++f) SF(f) = 0.0;
-  SF(SMX_S_X) = sp[0];
-  SF(SMX_S_Y) = sp[1];
-  SF(SMX_S_HEADING) = wrap_heading(sp[2]);
-  SF(SMX_S_U) = sp[3];
-  // kinematic spaces: MotionPlannerProvider.create_vehicle takes pose.heading (:164-168); _last_dt is 0
-  if (smx_kinematic_space(a.cfg.action_space)) SF(SMX_S_KIN_RAW_HEADING) = SF(SMX_S_HEADING);
-  SF(SMX_S_PREV_X) = sp[0];
-  SF(SMX_S_PREV_Y) = sp[1];
   int fl = SMX_F_ALIVE | SMX_F_FIRST;
   const int n_veh = a.cfg.num_vehicles;
+  bool parked = false;
+  if constexpr (GUARD) {
+    const bool agent = (int)(gid % n_veh) < n_veh - a.cfg.num_social;
+    const GuardVerdict gv = guard_resolve_spawn(!agent || guard_in_bounds_kin(a.guard_box, sp[0], sp[1], sp[2], sp[3]));
+    a.guard[gid] = gv.byte;
+    parked = gv.action == GUARD_PARK;
+  }
+  if (GUARD && parked) {
+    const GuardParked p = guard_parked_pose(a.map.lp_rec[0]);
+    SF(SMX_S_X) = p.x;
+    SF(SMX_S_Y) = p.y;
+    SF(SMX_S_HEADING) = p.heading;
+    if (smx_kinematic_space(a.cfg.action_space)) SF(SMX_S_KIN_RAW_HEADING) = p.heading;
+    SF(SMX_S_PREV_X) = p.x;
+    SF(SMX_S_PREV_Y) = p.y;
+    fl |= SMX_F_GUARDED;
+  } else {
+    SF(SMX_S_X) = sp[0];
+    SF(SMX_S_Y) = sp[1];
+    SF(SMX_S_HEADING) = wrap_heading(sp[2]);
+    SF(SMX_S_U) = sp[3];
+    // kinematic spaces: MotionPlannerProvider.create_vehicle takes pose.heading (:164-168); _last_dt is 0
+    if (smx_kinematic_space(a.cfg.action_space)) SF(SMX_S_KIN_RAW_HEADING) = SF(SMX_S_HEADING);
+    SF(SMX_S_PREV_X) = sp[0];
+    SF(SMX_S_PREV_Y) = sp[1];
+  }
   if ((int)(gid % n_veh) >= n_veh - a.cfg.num_social) {
     const double* so = a.sp.social + ((size_t)row * total + gid) * 2;
     SF(SMX_S_MCL_X) = so[0];  // lane
@@ -3764,6 +3877,10 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
 // =================================================================================
 // (`tick`: the tick's commit — every agent's teardown, done counts, auto-reset respawn; else the reset pass's, which
 // only applies the new vehicles' flags)
+// (GUARD, the tick's commit only: an agent that carries SMX_F_GUARDED ends with this tick's observation — done = 1, not
+// active, its vehicle gone —, applied here as lap_goal_gate applies its correction: the observe role is the kernel
+// without a guard; and the byte of every slot without an agent in the tick reads 0)
+template <bool GUARD>
 __device__ __forceinline__ void commit_role(const KernelArgs& a, const int block, const bool tick) {
   __shared__ int env_new_done[SMX_BLOCK];
   __shared__ int env_respawn[SMX_BLOCK];
@@ -3787,7 +3904,24 @@ __device__ __forceinline__ void commit_role(const KernelArgs& a, const int block
   if (valid) {
     if (__builtin_expect(a.missions.goal_kind != nullptr, 0)) lap_goal_gate(a, gid, total, slot, tick);
     const int old_flags = a.st.flags[gid];
-    const int new_flags = a.st.facts_i32[(size_t)SMX_FI_FLAGS_NEXT * total + gid];
+    int new_flags = a.st.facts_i32[(size_t)SMX_FI_FLAGS_NEXT * total + gid];
+    if constexpr (GUARD) {
+      if (tick) {
+        const bool agent = (old_flags & SMX_F_ALIVE) && !(old_flags & SMX_F_SOCIAL);
+        if (!agent) {
+          a.guard[gid] = 0;
+        } else if (old_flags & SMX_F_GUARDED) {  // (set by the control phase, or by the reset that created it parked)
+          // The observe role's done path writes four words per agent — SMX_F_ALIVE off in the next flags, active,
+          // done, the learner block's done — and these are the four: no other per-agent row depends on done (events,
+          // reward and the learner's reward are what the held / parked pose yields, as for any agent), and what reads
+          // done afterwards (the env's done count below, the frame pushes that end the pass) reads it as set here.
+          new_flags &= ~SMX_F_ALIVE;
+          o.active[gid] = 0;
+          o.done[gid] = 1;
+          if (o.learner) o.learner[total + gid] = 1.0f;
+        }
+      }
+    }
     a.st.flags[gid] = new_flags;
     if ((old_flags & SMX_F_ALIVE) && !(new_flags & SMX_F_ALIVE)) atomicAdd(&env_new_done[env_local], 1);
     if (slot == 0) env_first_alive[env_local] = (new_flags & SMX_F_ALIVE) ? 1 : 0;
@@ -3821,7 +3955,7 @@ __device__ __forceinline__ void commit_role(const KernelArgs& a, const int block
   }
   if (respawn) {
     next_episode = a.st.env_episode[env] + 1;
-    respawn_vehicle(a, gid, total, next_episode);
+    respawn_vehicle<GUARD>(a, gid, total, next_episode);
   }
   __syncthreads();  // every thread of the env has read env_episode
   if (respawn && slot == 0) {
@@ -4477,7 +4611,7 @@ __device__ __forceinline__ void first_role(const KernelArgs& a, const int block)
   __syncthreads();
   // ---- commit
   SMX_TSTAMP(tk4);
-  commit_role(a, block, false);
+  commit_role<false>(a, block, false);  // (the reset pass's commit has no guard work: respawn_vehicle wrote the bytes)
   SMX_TSTAMP(tk5);
   SMX_TACC_ALL(60, tk4, tk5);
   SMX_TACC_ALL(61, tk0, tk5);
@@ -5217,6 +5351,7 @@ struct TailArgs {
   int32_t* slow_next;      // zeroed: the next tick's four slow-list counters
 };
 
+template <bool GUARD = false>
 __global__ void __launch_bounds__(SMX_BLOCK) k_tail(const KernelArgs a, const TailArgs t) {
   const smx_config& c = a.cfg;
   const int block = (int)blockIdx.x;
@@ -5227,7 +5362,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_tail(const KernelArgs a, const Ta
   const size_t g1 = min(total, g0 + (size_t)epb * n_veh);
   const int lane = (int)threadIdx.x;
   const size_t gid = g0 + lane;
-  if (t.commit) commit_role(a, block, true);  // (lane l commits vehicle g0 + l: its flags word is read back below)
+  if (t.commit) commit_role<GUARD>(a, block, true);  // (lane l commits vehicle g0 + l: its flags word is read back below)
   if (block == 0 && lane == 0) {
     *t.n_groups_next = 0;
     if (t.list) {
@@ -5346,6 +5481,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_lidar_first(const KernelArgs a) {
 // spawn poses (AckermannChassis._initialize_speed, chassis.py:668-671); the observation kernels
 // that follow produce their first observations.
 // =================================================================================
+template <bool GUARD = false>
 __global__ void __launch_bounds__(SMX_BLOCK) k_reset(const KernelArgs a) {
   const smx_config& c = a.cfg;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
@@ -5360,8 +5496,11 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_reset(const KernelArgs a) {
     sel = a.env_mask[env] != 0;
   else
     sel = a.st.env_reset_pending[env] != 0;
-  if (!sel) return;
-  respawn_vehicle(a, gid, total, a.st.env_episode[env] + 1);  // every reset starts the next spawn row
+  if (!sel) {
+    if constexpr (GUARD) a.guard[gid] = 0;  // (an agent absent from the pass)
+    return;
+  }
+  respawn_vehicle<GUARD>(a, gid, total, a.st.env_episode[env] + 1);  // every reset starts the next spawn row
   // per-env words are written by every thread of the env with the same values (no ordering needed
   // inside this kernel; the env's own threads never read them here)
   (void)slot;
@@ -5453,6 +5592,10 @@ struct smx_handle_s {
   int group_parity;  // k_tail's counter of env groups with new vehicles (the other one is zero)
   bool map_junctions;  // lanes of the map split (some lanepoint has several successors)
   double dagm_reach;  // half the widest lane width of the loaded map
+  uint8_t* guard_out;  // smx_set_guard: the caller's byte buffer (null: guard off), its margin and the box of the loaded map
+  uint64_t guard_count;
+  double guard_margin;
+  GuardBox guard_box;
   uint8_t* rgb_out;   // smx_set_rgb_output: the caller's image buffer (null: none bound) and the bytes it holds
   uint64_t rgb_count;
   struct StackBinding {  // smx_bind_frame_stack: one caller-owned stack per (source, layout)
@@ -5485,7 +5628,7 @@ static int fail(smx_handle h, int code, const std::string& msg) {
     if (e__ != hipSuccess) return fail(h, SMX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
   } while (0)
 
-extern "C" const char* smx_version(void) { return "smarts-mi355x 0.1 (gfx950)"; }
+extern "C" const char* smx_version(void) { return "smarts-mi355x 0.2 (gfx950)"; }
 
 #ifdef SMX_DEBUG_TIMING
 extern "C" int smx_span_read(unsigned int* out) {  // developer: [kernel][wavefront] spans of the last launches, 10 ns units
@@ -5599,6 +5742,10 @@ static int create_impl(const smx_config* cfg, int device, smx_handle* out) {
   h->lidar_rays = nullptr;
   h->rgb_out = nullptr;
   h->rgb_count = 0;
+  h->guard_out = nullptr;
+  h->guard_count = 0;
+  h->guard_margin = SMX_GUARD_MARGIN_DEFAULT;
+  h->guard_box = GuardBox{1.0, 1.0, 0.0, 0.0};
   // lane_following_controller.py:426-430: place_poles gains clipped to [0.02, 0.04] / [3.4, 4.1];
   // for the sedan they saturate at (0.04, 3.4) for both Lane-space target speeds.
   h->heading_gain_pos = 0.04;
@@ -5712,6 +5859,7 @@ static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_sta
   in.slow = SlowLists{h->slow_blob, (size_t)h->cfg.num_envs * h->cfg.num_vehicles};
   in.slow_parity = h->alive_parity;
   in.frame_stack_bound = !h->stacks.empty();
+  in.guard_bound = h->guard_out != nullptr;
   return in;
 }
 
@@ -5771,6 +5919,9 @@ extern "C" int smx_load_map(smx_handle h, const smx_map_tables* t) {
     if (t->lane_in_idx[i] < 0 || t->lane_in_idx[i] >= t->n_lanes) return fail(h, SMX_ERR_INVALID, "incoming lane out of range");
   for (int i = 0; i < t->road_par_off[nr]; ++i)
     if (t->road_par_idx[i] < 0 || t->road_par_idx[i] >= t->n_roads) return fail(h, SMX_ERR_INVALID, "parallel road out of range");
+  // a bound guard stays bound: its margin against this map's cells (smx_guard.h), its box recomputed below
+  if (h->guard_out && !guard_map_ok(*t, h->guard_margin))
+    return fail(h, SMX_ERR_INVALID, "state guard: with this margin a cell index of this map's grids would not fit (smx_guard.h, SMX_GUARD_INDEX_MAX)");
   h->dagm_reach = 0.0;
   for (size_t i = 0; i < nl; ++i) h->dagm_reach = std::max(h->dagm_reach, 0.5 * t->lane_width[i]);
   // The slow lists' kernels run a fixed grid that strides a list whose length only the device knows.  On a map
@@ -5938,6 +6089,7 @@ extern "C" int smx_load_map(smx_handle h, const smx_map_tables* t) {
     SMX_HIP(hipEventCreateWithFlags(&h->ev_fork_grid, hipEventDisableTiming));
     h->side_ready = true;
   }
+  h->guard_box = guard_box_of(*t, h->guard_margin);
   h->map_loaded = true;
   return SMX_OK;
 }
@@ -6342,6 +6494,57 @@ extern "C" int smx_set_rgb_output(smx_handle h, uint8_t* rgb_dev, uint64_t count
   return SMX_OK;
 }
 
+// ---- the state guard (smx_set_guard / smx_check_guard) ----
+static int check_guard_impl(const smx_config& c, uint64_t count, double margin, std::string& err) {
+  if (c.num_envs <= 0 || c.num_vehicles <= 0) {
+    err = "state guard: num_envs and num_vehicles must be > 0";
+    return SMX_ERR_INVALID;
+  }
+  if (!guard_margin_ok(margin)) {
+    err = "state guard: the margin must be finite and 0 <= margin <= " + std::to_string((long long)SMX_GUARD_MARGIN_MAX) + " m";
+    return SMX_ERR_INVALID;
+  }
+  const uint64_t need = (uint64_t)c.num_envs * (uint64_t)c.num_vehicles;
+  if (count < need) {
+    err = "state guard: " + std::to_string(count) + " bytes declared, the configuration needs " + std::to_string(need) +
+          " (a short buffer would be an out-of-bounds device write)";
+    return SMX_ERR_INVALID;
+  }
+  return SMX_OK;
+}
+
+extern "C" int smx_check_guard(const smx_config* cfg, uint64_t count, double margin, char* err, uint64_t err_len) {
+  std::string msg;
+  const int rc = cfg ? check_guard_impl(*cfg, count, margin, msg) : SMX_ERR_INVALID;
+  if (!cfg) msg = "null config";
+  if (err && err_len > 0) {
+    const size_t n = std::min<size_t>(msg.size(), (size_t)err_len - 1);
+    memcpy(err, msg.data(), n);
+    err[n] = 0;
+  }
+  return rc;
+}
+
+extern "C" int smx_set_guard(smx_handle h, uint8_t* guard_dev, uint64_t count, double margin) {
+  if (!h) return SMX_ERR_INVALID;
+  if (!guard_dev) {  // guard off
+    h->guard_out = nullptr;
+    h->guard_count = 0;
+    return SMX_OK;
+  }
+  std::string msg;
+  const int rc = check_guard_impl(h->cfg, count, margin, msg);
+  if (rc != SMX_OK) return fail(h, rc, msg);
+  // (before a map is loaded, smx_load_map makes this check)
+  if (h->map_loaded && !guard_map_ok(h->map, margin))
+    return fail(h, SMX_ERR_INVALID, "state guard: with this margin a cell index of the loaded map's grids would not fit (smx_guard.h, SMX_GUARD_INDEX_MAX)");
+  h->guard_out = guard_dev;
+  h->guard_count = count;
+  h->guard_margin = margin;
+  if (h->map_loaded) h->guard_box = guard_box_of(h->map, margin);
+  return SMX_OK;
+}
+
 // ---- frame stacking (smx_bind_frame_stack / smx_check_frame_stack) ----
 // bytes per agent of a stackable source, 0 with the reason in `err`: the rows of smx_outputs by their SMX_OUT_* index (the
 // sizes check_buffers_impl asks of them), the image by SMX_STACK_SOURCE_RGB
@@ -6565,33 +6768,39 @@ struct ControlKernels {
   HandoffKernel listed, paths, law;
   Kernel kinematic;  // (the kinematic spaces have this one alone)
 };
-template <int SPACE>
+template <int SPACE, bool GUARD>
 static ControlKernels control_kernels_of() {
-  ControlKernels k{k_control<SPACE>, nullptr, nullptr, nullptr, nullptr, k_control_law<SPACE>, nullptr};
-  if constexpr (SPACE == SMX_ACTION_SPACE_LANE || SPACE == SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED) {
-    k.one_lds = k_control<SPACE, true>;
-    k.fast = k_control_fast<SPACE>;
-    k.listed = k_control_listed<SPACE>;
-    k.paths = k_control_paths<SPACE>;
+  if constexpr (smx_kinematic_space(SPACE)) {
+    return ControlKernels{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_control_kinematic<SPACE, GUARD>};
+  } else {
+    ControlKernels k{k_control<SPACE, false, GUARD>, nullptr, nullptr, nullptr, nullptr, k_control_law<SPACE, GUARD>, nullptr};
+    if constexpr (SPACE == SMX_ACTION_SPACE_LANE || SPACE == SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED) {
+      k.one_lds = k_control<SPACE, true, GUARD>;
+      k.fast = k_control_fast<SPACE, GUARD>;
+      k.listed = k_control_listed<SPACE, GUARD>;
+      k.paths = k_control_paths<SPACE, GUARD>;
+    }
+    return k;
   }
-  return k;
 }
+// (`guard`: TickPlan::guard — the instantiations with the state guard)
+template <bool GUARD>
 static ControlKernels control_kernels(int action_space) {
   switch (action_space) {
-    case SMX_ACTION_SPACE_LANE: return control_kernels_of<SMX_ACTION_SPACE_LANE>();
-    case SMX_ACTION_SPACE_CONTINUOUS: return control_kernels_of<SMX_ACTION_SPACE_CONTINUOUS>();
-    case SMX_ACTION_SPACE_ACTUATOR_DYNAMIC: return control_kernels_of<SMX_ACTION_SPACE_ACTUATOR_DYNAMIC>();
-    case SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED: return control_kernels_of<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED>();
-    case SMX_ACTION_SPACE_TRAJECTORY: return control_kernels_of<SMX_ACTION_SPACE_TRAJECTORY>();
-    case SMX_ACTION_SPACE_MPC: return control_kernels_of<SMX_ACTION_SPACE_MPC>();
-    case SMX_ACTION_SPACE_TARGET_POSE: return ControlKernels{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_control_kinematic<SMX_ACTION_SPACE_TARGET_POSE>};
-    case SMX_ACTION_SPACE_IMITATION: return ControlKernels{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_control_kinematic<SMX_ACTION_SPACE_IMITATION>};
-    default: return ControlKernels{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_control_kinematic<SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME>};
+    case SMX_ACTION_SPACE_LANE: return control_kernels_of<SMX_ACTION_SPACE_LANE, GUARD>();
+    case SMX_ACTION_SPACE_CONTINUOUS: return control_kernels_of<SMX_ACTION_SPACE_CONTINUOUS, GUARD>();
+    case SMX_ACTION_SPACE_ACTUATOR_DYNAMIC: return control_kernels_of<SMX_ACTION_SPACE_ACTUATOR_DYNAMIC, GUARD>();
+    case SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED: return control_kernels_of<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED, GUARD>();
+    case SMX_ACTION_SPACE_TRAJECTORY: return control_kernels_of<SMX_ACTION_SPACE_TRAJECTORY, GUARD>();
+    case SMX_ACTION_SPACE_MPC: return control_kernels_of<SMX_ACTION_SPACE_MPC, GUARD>();
+    case SMX_ACTION_SPACE_TARGET_POSE: return control_kernels_of<SMX_ACTION_SPACE_TARGET_POSE, GUARD>();
+    case SMX_ACTION_SPACE_IMITATION: return control_kernels_of<SMX_ACTION_SPACE_IMITATION, GUARD>();
+    default: return control_kernels_of<SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME, GUARD>();
   }
 }
 
 static void launch_control(smx_handle h, const TickPlan& p, const KernelArgs& a, hipStream_t stream) {
-  const ControlKernels k = control_kernels(h->cfg.action_space);
+  const ControlKernels k = p.guard ? control_kernels<true>(h->cfg.action_space) : control_kernels<false>(h->cfg.action_space);
   switch (p.control) {
     case Control::NONE: break;
     case Control::ONE: launch(k.one, p.wp_blocks, 0, stream, a); break;
@@ -6764,7 +6973,7 @@ static int tail_and_reset_pass(smx_handle h, const TickPlan& p, const KernelArgs
   r.reset_all = (!p.is_step && mask == nullptr) ? 1 : 0;
   r.env_mask = p.is_step ? nullptr : mask;
   if (!p.is_step) {
-    launch(k_reset, p.veh_blocks, 0, stream, r);
+    launch(p.guard ? k_reset<true> : k_reset<false>, p.veh_blocks, 0, stream, r);
     launch(k_reset_env, p.env_blocks, 0, stream, r);
   }
   TailArgs t{};
@@ -6780,7 +6989,7 @@ static int tail_and_reset_pass(smx_handle h, const TickPlan& p, const KernelArgs
     t.flat_next = h->alive_blob + al.flat + h->alive_parity;
     t.slow_next = SlowLists{h->slow_blob, total}.counters(h->alive_parity);
   }
-  hipLaunchKernelGGL(k_tail, dim3(p.obs_blocks), dim3(SMX_BLOCK), p.tail_grids ? std::max({p.ogm_bytes, p.dagm_bytes, p.rgb_lds}) : 0, stream, r, t);
+  hipLaunchKernelGGL(p.guard ? k_tail<true> : k_tail<false>, dim3(p.obs_blocks), dim3(SMX_BLOCK), p.tail_grids ? std::max({p.ogm_bytes, p.dagm_bytes, p.rgb_lds}) : 0, stream, r, t);
   if (ph) SMX_HIP(hipEventRecord(ph[SMX_PHASE_COMMIT + 1], stream));
   h->group_parity ^= 1;
   h->list_ready = p.tail_builds_list;
@@ -6848,6 +7057,8 @@ static KernelArgs kernel_args(smx_handle h, const TickPlan& p, const int8_t* act
   a.facts_carry = h->scan_carry ? h->scan_carry + 4 * total : nullptr;
   a.dagm_reach = h->dagm_reach;
   a.rgb = h->rgb_out;
+  a.guard = h->guard_out;
+  a.guard_box = h->guard_box;
   a.wp_blocks = (int)p.wp_blocks;
   a.obs_blocks = (int)p.obs_blocks;
   a.lidar_blocks = (int)p.lidar_blocks;

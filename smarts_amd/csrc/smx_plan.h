@@ -77,6 +77,7 @@ struct PlanInputs {
   SlowLists slow;         // (base null: no slow lists)
   int slow_parity;        // the counters this tick's one-lane kernels use
   bool frame_stack_bound;  // smx_bind_frame_stack holds at least one buffer
+  bool guard_bound;        // smx_set_guard holds a buffer: the state guard is on
 };
 
 enum class AliveList : uint8_t { NONE, CARRIED, BUILD };  // BUILD: k_alive_list ahead of the tick
@@ -148,6 +149,9 @@ struct TickPlan {
   // caller's stream, after the observation pass has joined and after k_tail / the reset pass (they read the pass's
   // finished rows, the flags it left, this tick's done row and env_done) — in a tick and in smx_reset, in either form
   bool frame_stack;
+  // the state guard (smx_set_guard): the GUARD instantiations of the control kernels, k_reset and k_tail in the places of
+  // the plain ones — the same launches on the same streams, no kernel and no edge more
+  bool guard;
   bool tail_builds_list;  // k_tail builds the next tick's alive list
   bool tail_grids;        // ... and the new vehicles' grid tiles
   bool reset_pass, lidar_first, first_walks_new;
@@ -307,6 +311,7 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
     p.ttc_lds = apb * smx_ttc_lds_per_agent(c.wp_paths, c.wp_len);
   }
   p.frame_stack = c.frame_stack > 0 && in.frame_stack_bound;
+  p.guard = in.guard_bound;
   p.ego_centric = (c.sensors & SMX_SENSOR_EGO_CENTRIC) != 0;
   if (p.ego_centric) {
     const size_t apb = SMX_BLOCK / SMX_EC_TEAM;

@@ -20,6 +20,15 @@ from .lidar import SensorParams, base_rays, ray_count
 from .map_compiler import CompiledMap
 
 
+def checked_guard_margin(margin):
+    """``margin`` if it is a valid state-guard margin (include/smx.h smx_set_guard: a finite number of metres,
+    0 <= margin <= SMX_GUARD_MARGIN_MAX), else ValueError.  SimConfig and the env layer validate with this."""
+    m = margin
+    if isinstance(m, bool) or not isinstance(m, (int, float)) or not math.isfinite(m) or not 0.0 <= m <= nat.GUARD_MARGIN_MAX:
+        raise ValueError(f"state_guard_margin must be a finite number of metres in [0, {nat.GUARD_MARGIN_MAX:g}], got {m!r}")
+    return m
+
+
 @dataclass
 class SimConfig:
     """Mirror of ``smx_config``; defaults follow the reference's AgentInterface / HiWayEnv."""
@@ -94,6 +103,14 @@ class SimConfig:
     frame_stack: int = 0
     frame_stack_rows: Sequence[str] = ()
     frame_stack_rgb_dstack: bool = False
+    # the state guard (include/smx.h smx_set_guard), off by default: an agent whose state or spawn row is not finite or
+    # lies more than state_guard_margin metres outside the map's grids ends (done = 1) instead of reaching a map search;
+    # out["guard"], [E, N] uint8, holds the reason (nat.GUARD_STEP / GUARD_STATE / GUARD_SPAWN)
+    state_guard: bool = False
+    state_guard_margin: float = nat.GUARD_MARGIN_DEFAULT
+
+    def __post_init__(self):
+        checked_guard_margin(self.state_guard_margin)
 
     def sensors_mask(self) -> int:
         m = 0
@@ -206,6 +223,19 @@ def make_spawns(cm: CompiledMap, num_envs: int, num_vehicles: int, episodes: int
 
 
 from .map_compiler import map_tables_struct  # noqa: E402,F401  (torch-free; also used by tests/native)
+
+
+def check_guard(num_envs: int, num_vehicles: int, count: int, margin: float = nat.GUARD_MARGIN_DEFAULT) -> None:
+    """``smx_check_guard``: would ``smx_set_guard`` take a byte buffer of ``count`` elements and this margin for a
+    shard of ``num_envs`` x ``num_vehicles``?  Needs the built library, no device and no handle; raises ``ValueError``
+    with the library's reason when not.  (The margin against a map's cell sizes is checked where the map is known:
+    ``smx_set_guard`` / ``smx_load_map``.)"""
+    lib = nat.load_library()
+    c = nat.SmxConfig()
+    c.num_envs, c.num_vehicles = int(num_envs), int(num_vehicles)
+    err = C.create_string_buffer(512)
+    if lib.smx_check_guard(C.byref(c), int(count), float(margin), err, len(err)) != 0:
+        raise ValueError(err.value.decode())
 
 
 class BatchedSim:
@@ -434,6 +464,9 @@ class BatchedSim:
             # not a member of smx_outputs (its pointer list is closed): a buffer of its own, bound to the handle
             o["rgb"] = z((E, N, cfg.rgb_height, cfg.rgb_width, 3), torch.uint8)
             self.bind_rgb(o["rgb"])
+        if cfg.state_guard:
+            # like the image: a buffer of its own, bound to the handle
+            self.bind_guard(z((E, N), torch.uint8))
         if cfg.frame_stack:
             if cfg.frame_stack_rgb_dstack and not cfg.rgb:
                 raise ValueError("frame_stack_rgb_dstack needs SimConfig(rgb=True)")
@@ -563,6 +596,21 @@ class BatchedSim:
         rc = self.lib.smx_set_rgb_output(self.handle, images.data_ptr(), int(images.numel()))
         nat.check(self.lib, self.handle, rc, "smx_set_rgb_output")
         self.out["rgb"] = images
+
+    def bind_guard(self, guard: Optional[torch.Tensor], margin: Optional[float] = None):
+        """Bind the byte buffer of the state guard (``smx_set_guard``): uint8 [E, N] on the sim's device — which switches
+        the guard on — or ``None`` to switch it off.  ``margin`` defaults to ``SimConfig.state_guard_margin``.
+        ``out["guard"]`` follows."""
+        if guard is None:
+            nat.check(self.lib, self.handle, self.lib.smx_set_guard(self.handle, None, 0, 0.0), "smx_set_guard")
+            self.out.pop("guard", None)
+            return
+        if guard.dtype != torch.uint8 or tuple(guard.shape) != (self.E, self.N) or guard.device != self.device or not guard.is_contiguous():
+            raise ValueError(f"the guard buffer must be a contiguous uint8 device tensor of shape {(self.E, self.N)}")
+        margin = float(self.cfg.state_guard_margin if margin is None else margin)
+        rc = self.lib.smx_set_guard(self.handle, guard.data_ptr(), int(guard.numel()), margin)
+        nat.check(self.lib, self.handle, rc, "smx_set_guard")
+        self.out["guard"] = guard
 
     def bind_frame_stack(self, row: str, stack: Optional[torch.Tensor], layout: str = "frames"):
         """Bind the frame stack of ``out[row]`` (``smx_bind_frame_stack``; needs ``SimConfig(frame_stack=k)``): a

@@ -135,11 +135,16 @@ class BatchCore:
                  auto_reset: bool, device: str = "cuda:0", waypoint_window: Optional[Tuple[int, int]] = (4, 20),
                  num_social: int = 0, vias: Optional[Dict[str, Sequence]] = None, social_model: str = "constant",
                  missions: Optional[Dict[str, Any]] = None, spawns: str = "reference", shuffle_scenarios: bool = True,
-                 ego_centric: bool = False):
-        """``ego_centric``: the dense rows carry their ego-frame twins (``SimConfig(ego_centric=True)``) and the
+                 ego_centric: bool = False, state_guard: bool = False,
+                 state_guard_margin: float = nat.GUARD_MARGIN_DEFAULT):
+        """``state_guard`` / ``state_guard_margin``: ``SimConfig``'s (the state guard, include/smx.h smx_set_guard):
+        ``info[agent]["guard"]`` then holds the agent's guard byte whenever it is non-zero.  One exception: the infos
+        ``ParallelEnv.step`` returns for an env that restarted inside the launch (``auto_reset``) describe the finishing
+        tick, whose bytes the new episode's have replaced already, so they carry no ``"guard"``.
+        ``ego_centric``: the dense rows carry their ego-frame twins (``SimConfig(ego_centric=True)``) and the
         agents' Trajectory / TargetPose / TrajectoryWithTime actions are given in the frame of their last
         observation: ``step_actions`` converts them on the device (the reference's ``get_egocentric_adapters``)."""
-        from ..engine import BatchedSim, make_spawns
+        from ..engine import BatchedSim, checked_guard_margin, make_spawns
         from ..scenario_build import load_compiled_map
 
         self.agent_ids: List[str] = list(agent_specs.keys())
@@ -159,6 +164,7 @@ class BatchCore:
         self.num_social = num_social
         self.cfg.social_model = social_model
         self.ego_centric = self.cfg.ego_centric = bool(ego_centric)
+        self.cfg.state_guard, self.cfg.state_guard_margin = bool(state_guard), checked_guard_margin(state_guard_margin)
         # Start poses.  "reference": what hiway-v0 gives agents of a scenario without missions.pkl — a random endless
         # mission each, from CPython's random stream (missions.reference_spawn_table); "synthetic": the benchmark's
         # spawn table (PCG64(seed + env), 8 m apart on a lane, at the speed limit).  Scripted social

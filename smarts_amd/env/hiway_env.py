@@ -48,6 +48,8 @@ class HiWayEnv:
         vias: Optional[Dict[str, Sequence]] = None,
         missions: Optional[Union[Dict[str, Any], str]] = None,
         spawns: str = "reference",
+        state_guard: bool = False,
+        state_guard_margin: float = 1000.0,
     ):
         self._log = logging.getLogger(self.__class__.__name__)
         if not headless or envision_record_data_replay_path or envision_endpoint:
@@ -90,6 +92,8 @@ class HiWayEnv:
         # (missions.reference_spawn_table); "synthetic" = the benchmark's spawn table (engine.make_spawns)
         self._spawns = spawns
         self._shuffle_scenarios = bool(shuffle_scenarios)
+        # the state guard (include/smx.h smx_set_guard), off by default
+        self._state_guard, self._state_guard_margin = bool(state_guard), state_guard_margin
         self._dones_registered = 0
         self._core: Optional[BatchCore] = None
         self._seed = seed
@@ -121,7 +125,7 @@ class HiWayEnv:
         specs = self._agent_specs
         return (self._scenario, tuple(specs.keys()), tuple(repr(s.interface) for s in specs.values()), self._dt,
                 self._waypoint_window, self._num_social, self._social_model, repr(self._vias), repr(self._missions),
-                self._spawns, self._shuffle_scenarios)
+                self._spawns, self._shuffle_scenarios, self._state_guard, self._state_guard_margin)
 
     def seed(self, seed: int) -> int:
         """hiway_env.py:204-214.  Takes effect at the next ``reset`` that (re)builds the spawn table."""
@@ -141,7 +145,8 @@ class HiWayEnv:
             self._core = BatchCore(self._scenario, self._agent_specs, num_envs=1, dt=self._dt, seed=self._seed,
                                    auto_reset=False, device=self._device, waypoint_window=self._waypoint_window,
                                    num_social=self._num_social, vias=self._vias, social_model=self._social_model,
-                                   missions=self._missions, spawns=self._spawns, shuffle_scenarios=self._shuffle_scenarios)
+                                   missions=self._missions, spawns=self._spawns, shuffle_scenarios=self._shuffle_scenarios,
+                                   state_guard=self._state_guard, state_guard_margin=self._state_guard_margin)
         return self._core
 
     def step(self, agent_actions) -> Tuple[Dict[str, Observation], Dict[str, float], Dict[str, bool], Dict[str, Any]]:
@@ -202,6 +207,8 @@ def unpack_env(core: BatchCore, rows: Dict[str, np.ndarray], env: int):
         info = {"score": float(rows["dist"][env, i]), "env_obs": obs}  # agent_manager.py:233-234
         rewards[aid] = spec.reward_adapter(obs, reward)
         observations[aid] = spec.observation_adapter(obs)
+        if "guard" in rows and rows["guard"][env, i]:  # the state guard ended this agent: the reason (SMX_GUARD_* bits)
+            info["guard"] = int(rows["guard"][env, i])
         infos[aid] = spec.info_adapter(obs, reward, info)
         dones[aid] = bool(done_row[i])
     return observations, rewards, dones, infos

@@ -64,7 +64,8 @@ class ParallelEnv:
         self._core = BatchCore(p._scenario, p.agent_specs, num_envs=self._num_envs, dt=p._dt, seed=seed,
                                auto_reset=self._auto_reset, device=self._device, waypoint_window=p._waypoint_window or STD_WAYPOINT_WINDOW,
                                num_social=p._num_social, vias=p._vias, social_model=p._social_model, missions=p._missions,
-                               spawns=p._spawns, shuffle_scenarios=p._shuffle_scenarios)
+                               spawns=p._spawns, shuffle_scenarios=p._shuffle_scenarios,
+                               state_guard=p._state_guard, state_guard_margin=p._state_guard_margin)
         self._seed = seed
         return [seed + i for i in range(self._num_envs)]
 
@@ -109,6 +110,9 @@ class ParallelEnv:
                     if done_row[i]:
                         spec = core.agent_specs[aid]
                         info = {"score": float(rows["final_dist"][e, i]), "env_obs": last[aid]}
+                        # (no info["guard"] here: the env restarted inside the launch, so its guard byte is the new
+                        # episode's already and says nothing of the tick this info describes — there is no final_* twin
+                        # of the byte; a spawn row of the new episode that was out of bounds shows in the next step's info)
                         infos[aid] = spec.info_adapter(last[aid], float(rows["reward"][e, i]), info)
                         rewards[aid] = spec.reward_adapter(last[aid], rewards[aid])
                 self._dones_registered[e] = 0
