@@ -456,6 +456,17 @@ __device__ __forceinline__ int team_or(int v) {
   return v;
 }
 
+// exclusive prefix of `cnt` over the team: the sum over the lanes below p0; `total`: the sum over the whole team
+__device__ __forceinline__ int team_exclusive_prefix(int cnt, int p0, int& total) {
+  int incl = cnt;
+  int t = __shfl_up(incl, 1, SMX_WP_LANES);
+  if (p0 >= 1) incl += t;
+  t = __shfl_up(incl, 2, SMX_WP_LANES);
+  if (p0 >= 2) incl += t;
+  total = __shfl(incl, SMX_WP_LANES - 1, SMX_WP_LANES);
+  return incl - cnt;
+}
+
 // nearest path over the team: smallest distance, then smallest number
 __device__ __forceinline__ void team_nearest(double& my_d, int& my_idx) {
 #pragma unroll
@@ -534,16 +545,8 @@ __device__ __forceinline__ TeamSearch team_path_search(const MapDev& m, const Pa
         } while (bs.advance());
       }
     }
-    // exclusive prefix of the counts over the team
-    int incl = cnt;
-    {
-      int t = __shfl_up(incl, 1, SMX_WP_LANES);
-      if (p0 >= 1) incl += t;
-      t = __shfl_up(incl, 2, SMX_WP_LANES);
-      if (p0 >= 2) incl += t;
-    }
-    const int round_total = __shfl(incl, SMX_WP_LANES - 1, SMX_WP_LANES);
-    const int g = ts.n_paths + incl - cnt;
+    int round_total;
+    const int g = ts.n_paths + team_exclusive_prefix(cnt, p0, round_total);
     if (r4 == 0) {
       ts.goff0 = g;
       ts.cnt0 = cnt;
@@ -1727,6 +1730,8 @@ __global__ void __attribute__((amdgpu_waves_per_eu(ROLE == 0 ? 4 : 3, 8))) __lau
 // more than four lanes) the team numbers the paths the long way and rewrites the rows.
 // Rows are written whole every tick (unused waypoints and paths as zeros, format_obs.py:589-596),
 // each lane streaming its own row in order, so L2 assembles full lines before they leave.
+// The steps below the row helpers — one path into one row, the branching case, the long way, closing the rows,
+// the trip meter — are written once and shared with the staged and the emit-parallel form further down.
 // =================================================================================
 struct WpRows {
   double* pos;
@@ -1784,12 +1789,227 @@ __device__ __forceinline__ void wp_zero(const WpRows& r, int from, int W) {
   }
 }
 
-// `knots`: this thread's column of a [SMX_MAX_KNOTS][KSTRIDE] LDS scratch owned by the kernel
+// ---- the steps every emitter shares (waypoints_for, waypoints_tables_role, waypoints_emit_role) ----
+// first waypoint of a path (of the vehicle's path 0: what the trip meter reads)
+struct WpFirst {
+  bool have;
+  double x, y, h;
+};
+
+// One path into one output row: wp_rows, the interpolation with a wp_put sink, zeros behind the path, the row's wp_count
+// byte.  `knots`: this thread's column of a [SMX_MAX_KNOTS][KSTRIDE] LDS scratch owned by the kernel.
+// `kept` false: nothing is stored and the path is only walked (the caller enumerates its branchings), as far as its
+// first waypoint when that is wanted.  `want_first`: the path's first waypoint goes to `*first` (which call sites name
+// directly, or as nullptr: a pointer chosen at run time would keep the caller's WpFirst out of registers).
+// `count_byte` false: the caller's row book holds the count.  `store` false: the developer switch SMX_DEBUG_SKIP & 32768,
+// compute and do not store.  Returns the number of lanepoints on the path.
+template <int KSTRIDE>
+__device__ __forceinline__ int wp_emit_path(const KernelArgs& a, const RouteFilter& f, BranchState& bs, int start, size_t gid,
+                                            double px, double py, int* knots, int slot, bool kept, bool want_first,
+                                            WpFirst* first, bool count_byte = true, bool store = true) {
+  const MapDev& m = a.map;
+  const int P = a.cfg.wp_paths, W = a.cfg.wp_len, lookahead = a.cfg.wp_lookahead;
+  if (!kept && !want_first)
+    return equally_spaced_path(m, f, bs, start, lookahead, px, py, knots, KSTRIDE, 0, [&](int, const WaypointOut&) {});
+  WpRows rows = wp_rows(a.out, gid, P, W, slot);
+  if (!store) rows.pos = nullptr;
+  const int n = equally_spaced_path(m, f, bs, start, lookahead, px, py, knots, KSTRIDE, kept ? W : 1,
+                                    [&](int i, const WaypointOut& w) {
+                                      if (want_first && i == 0) {
+                                        first->have = true;
+                                        first->x = w.x;
+                                        first->y = w.y;
+                                        first->h = w.heading;
+                                      }
+                                      if (kept) wp_put(m, rows, i, w);
+                                    });
+  if (kept) {
+    wp_zero(rows, n < W ? n : W, W);
+    if (count_byte) a.out.wp_count[gid * (P + 1) + 1 + slot] = (uint8_t)(n < W ? n : W);
+  }
+  return n;
+}
+
+// Closing a vehicle's rows: the rows of the paths that do not exist, spread over the team, and the path count (lane 0)
+__device__ __forceinline__ void wp_close_rows(const KernelArgs& a, size_t gid, int p0, int n_paths_total) {
+  const smx_outputs& o = a.out;
+  const int P = a.cfg.wp_paths, W = a.cfg.wp_len;
+  for (int slot = n_paths_total + ((p0 - n_paths_total) & (SMX_WP_LANES - 1)); slot < P; slot += SMX_WP_LANES) {
+    wp_zero(wp_rows(o, gid, P, W, slot), 0, W);
+    o.wp_count[gid * (P + 1) + 1 + slot] = 0;
+  }
+  if (p0 == 0) o.wp_count[gid * (P + 1)] = (uint8_t)(n_paths_total > 255 ? 255 : n_paths_total);
+}
+
+// Path 0 is the lowest started lane's first path: its first waypoint (`g`: every lane's own), for the whole team
+__device__ __forceinline__ WpFirst team_first_waypoint(int started, const WpFirst& g, bool have) {
+  const int src = started ? (__ffs(started) - 1) : 0;
+  WpFirst fw;
+  fw.have = have;
+  fw.x = __shfl(g.x, src, SMX_WP_LANES);
+  fw.y = __shfl(g.y, src, SMX_WP_LANES);
+  fw.h = __shfl(g.h, src, SMX_WP_LANES);
+  return fw;
+}
+
+// A lane branches inside the lookahead: paths are numbered lanes by index, branches depth-first, i.e. lane p's paths
+// follow those of the lower lanes.  The counts are known (waypoints_for's first pass, k_wp_walk), so an exclusive prefix
+// over the team gives every lane the numbers of its own paths, and each lane writes its own branches, with its own
+// walks, into the right rows.  `start`: this lane's start lanepoint (< 0: no path starts here).  `in_place`: the row
+// this lane's first path already stands in (waypoints_for's provisional one; -1: none).  Only a first path whose row
+// was already the right one stays as written and is only walked, to learn the branchings the enumeration continues
+// from: provisional rows are distinct (a lane's rank among the started lanes), so nobody else wrote there in the first
+// pass, and whoever owns another lane's stale provisional row rewrites it here, later.  `first`: takes the first
+// waypoint of path 0 if that path is written here (one in place keeps what the first pass learnt).  Returns the
+// team's number of paths.
+template <int KSTRIDE>
+__device__ __forceinline__ int wp_emit_branches(const KernelArgs& a, const RouteFilter& f, size_t gid, int p0, double px,
+                                                double py, int* knots, int start, int cnt, int in_place, WpFirst& first) {
+  const int P = a.cfg.wp_paths;
+  int n_paths_total;
+  const int base = team_exclusive_prefix(cnt, p0, n_paths_total);
+  const bool first_in_place = base == in_place;
+  if (start >= 0 && base < P && !(cnt == 1 && first_in_place)) {
+    BranchState bs;
+    bs.reset();
+    int idx = base;
+    do {
+      if (idx >= P) break;
+      if (idx == base && first_in_place)
+        wp_emit_path<KSTRIDE>(a, f, bs, start, gid, px, py, knots, 0, false, false, nullptr);
+      else
+        wp_emit_path<KSTRIDE>(a, f, bs, start, gid, px, py, knots, idx, true, idx == 0, &first);
+      ++idx;
+    } while (bs.advance());
+  }
+  return n_paths_total;
+}
+
+// Roads with more than four lanes: every path of the vehicle the long way (lanes by index, branches depth-first): every
+// team lane walks every path to discover the branchings, lane (idx % 4) writes kept path idx.  Returns the number of
+// paths; lane 0 of the team learns the first waypoint.
+template <int KSTRIDE>
+__device__ __forceinline__ int waypoints_long_way(const KernelArgs& a, const PathSeeds& seed, size_t gid, int p0, double px,
+                                                  double py, int* knots, WpFirst& fw) {
+  const int P = a.cfg.wp_paths;
+  int idx = 0;
+  for (int li = 0; li < seed.n_lanes; ++li) {
+    const int st = seed_start(a.map, seed, li, px, py);
+    if (st < 0) continue;
+    BranchState bs;
+    bs.reset();
+    do {
+      const bool kept = idx < P && (idx % SMX_WP_LANES) == p0;
+      const bool first_path = (idx == 0 && p0 == 0);
+      if (kept || first_path)
+        wp_emit_path<KSTRIDE>(a, seed.f, bs, st, gid, px, py, knots, kept ? idx : 0, kept, first_path, &fw);
+      else if (p0 == 0 || idx < P)
+        wp_emit_path<KSTRIDE>(a, seed.f, bs, st, gid, px, py, knots, 0, false, false, nullptr);
+      ++idx;
+    } while (bs.advance() && (p0 == 0 || idx < P));
+  }
+  return __shfl(idx, 0, SMX_WP_LANES);  // lane 0 counts them all
+}
+
+// Trip meter (sensors.py:880-947) and reward = its increment (agent_manager.py:233-234): lane 0 of the team.
+// The meter's words as loaded (the emit-parallel form loads them early, with everything else of the vehicle):
+struct TripMeter {
+  double dist, last_dist;         // the total, and what it was when this tick began
+  double trip_x, trip_y, trip_h;  // the waypoint the meter last advanced to
+  bool has_wp;                    // ... if there is one
+};
+
+__device__ __forceinline__ TripMeter trip_meter_of(double dist, double trip_x, double trip_y, double trip_h, bool has_wp) {
+  TripMeter t;
+  t.dist = t.last_dist = dist;
+  t.trip_x = trip_x;
+  t.trip_y = trip_y;
+  t.trip_h = trip_h;
+  t.has_wp = has_wp;
+  return t;
+}
+
+// A new vehicle (TripMeterSensor.__init__): the meter's waypoint is the first one of the lowest lane, lookahead-1 path,
+// no route; it goes to the state rows.  Returns whether there is one.
+template <int KSTRIDE>
+__device__ __forceinline__ bool trip_meter_start(const KernelArgs& a, size_t gid, size_t total, double px, double py, int* knots) {
+  bool has_wp = false;
+  const int ts = a.st.facts_i32[(size_t)SMX_FI_TRIP_START * total + gid];
+  if (ts >= 0) {
+    BranchState bs;
+    bs.reset();
+    RouteFilter nof;
+    nof.none();
+    equally_spaced_path(a.map, nof, bs, ts, 1, px, py, knots, KSTRIDE, 1, [&](int, const WaypointOut& w) {
+      SF(SMX_S_TRIP_X) = w.x;
+      SF(SMX_S_TRIP_Y) = w.y;
+      SF(SMX_S_TRIP_H) = w.heading;
+      has_wp = true;
+    });
+  }
+  return has_wp;
+}
+
+// The first waypoint of path 0, when it counts (trip_counts_waypoint), is appended: the meter moves on to it once it
+// lies more than half a metre away.  (The new waypoint goes straight to the state rows: held in the struct until
+// trip_meter_store it cost k_waypoints_tables two registers.)
+__device__ __forceinline__ void trip_meter_advance(const KernelArgs& a, size_t gid, size_t total, TripMeter& t, const WpFirst& fw) {
+  if (!t.has_wp) {
+    SF(SMX_S_TRIP_X) = fw.x;
+    SF(SMX_S_TRIP_Y) = fw.y;
+    SF(SMX_S_TRIP_H) = fw.h;
+    t.has_wp = true;
+  } else {
+    double dx = fw.x - t.trip_x, dy = fw.y - t.trip_y;
+    double nrm = sqrt(dx * dx + dy * dy);
+    if (nrm > 0.5) {
+      double hvx, hvy;
+      radians_to_vec(t.trip_h, hvx, hvy);
+      double dot = hvx * dx + hvy * dy;
+      double sgn = dot > 0.0 ? 1.0 : (dot < 0.0 ? -1.0 : 0.0);
+      t.dist += sgn * nrm;
+      SF(SMX_S_TRIP_X) = fw.x;
+      SF(SMX_S_TRIP_Y) = fw.y;
+      SF(SMX_S_TRIP_H) = fw.h;
+    }
+  }
+}
+
+__device__ __forceinline__ void trip_meter_store(const KernelArgs& a, size_t gid, size_t total, const TripMeter& t) {
+  const smx_outputs& o = a.out;
+  SF(SMX_S_DIST) = t.dist;
+  o.dist[gid] = t.dist;
+  if (!a.keep_reward_done) {
+    o.reward[gid] = t.dist - t.last_dist;
+    if (o.learner) o.learner[gid] = (float)(t.dist - t.last_dist);
+  }
+  // the flags word itself is not written here (the observe role owns it)
+  a.st.facts_i32[(size_t)SMX_FI_TRIP_HAS_WP * total + gid] = t.has_wp ? 1 : 0;
+}
+
+// The three in turn, on the state rows (the serial emitter, the staged form): the meter's waypoint is loaded behind
+// the start, which may just have written it, and only when it is needed
+template <int KSTRIDE>
+__device__ __forceinline__ void trip_meter_update(const KernelArgs& a, size_t gid, size_t total, int flags, double px, double py,
+                                                  int* knots, const WpFirst& fw) {
+  double dist = SF(SMX_S_DIST);
+  bool has_wp = a.st.facts_i32[(size_t)SMX_FI_TRIP_HAS_WP * total + gid] != 0;
+  if (flags & SMX_F_FIRST) {
+    has_wp = trip_meter_start<KSTRIDE>(a, gid, total, px, py, knots);
+    dist = 0.0;
+  }
+  const bool counts = fw.have && trip_counts_waypoint(a, a.map, gid, total);
+  TripMeter t = trip_meter_of(dist, counts ? SF(SMX_S_TRIP_X) : 0.0, counts ? SF(SMX_S_TRIP_Y) : 0.0,
+                              counts ? SF(SMX_S_TRIP_H) : 0.0, has_wp);
+  if (counts) trip_meter_advance(a, gid, total, t, fw);
+  trip_meter_store(a, gid, total, t);
+}
+
+// The serial emitter: every row of the vehicle and its trip meter, a team of SMX_WP_LANES lanes
 template <int KSTRIDE>
 __device__ __forceinline__ void waypoints_for(const KernelArgs& a, const size_t gid, int* knots) {
   const smx_config& c = a.cfg;
   const MapDev& m = a.map;
-  const smx_outputs& o = a.out;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
   const int p0 = threadIdx.x % SMX_WP_LANES;
   if (gid >= total) return;  // whole teams leave together
@@ -1798,12 +2018,11 @@ __device__ __forceinline__ void waypoints_for(const KernelArgs& a, const size_t 
   int flags = a.st.flags[gid];
   if (!(flags & SMX_F_ALIVE) || (flags & SMX_F_SOCIAL) || (a.first_only && !(flags & SMX_F_FIRST))) return;
   const bool wp_on = (c.sensors & SMX_SENSOR_WAYPOINTS) != 0;
-  const int P = c.wp_paths, W = c.wp_len;
+  const int P = c.wp_paths;
   const VehState s = load_vehicle(a, gid, total);
   const double px = s.x, py = s.y;
 
-  bool have_first_wp = false;  // first waypoint of path 0 (trip meter), valid on team lane 0
-  double fwx = 0, fwy = 0, fwh = 0;
+  WpFirst fw = {false, 0.0, 0.0, 0.0};  // first waypoint of path 0 (trip meter), valid on team lane 0
   if (!wp_on) {
     // only the first waypoint of the first path is needed (trip meter)
     const int os = a.st.facts_i32[(size_t)SMX_FI_OBS_START * total + gid];
@@ -1813,207 +2032,52 @@ __device__ __forceinline__ void waypoints_for(const KernelArgs& a, const size_t 
       RouteFilter nof;
       nof.none();
       equally_spaced_path(m, nof, bs, os, 1, px, py, knots, KSTRIDE, 1, [&](int, const WaypointOut& w) {
-        have_first_wp = true;
-        fwx = w.x;
-        fwy = w.y;
-        fwh = w.heading;
+        fw.have = true;
+        fw.x = w.x;
+        fw.y = w.y;
+        fw.h = w.heading;
       });
     }
   } else {
     const PathSeeds seed = load_seeds(a, gid, total);
-    const int lookahead = c.wp_lookahead;
     int n_paths_total = 0;
     SMX_TSTAMP(tw1);
     SMX_TACC(0, tw0, tw1);
     if (seed.road >= 0 && !SMX_SKIP(a, 16)) {
       // ---- the guess: seed lane p holds exactly one path
       const int start = (p0 < seed.n_lanes) ? seed_start(m, seed, p0, px, py) : -1;
-      int started = start >= 0 ? (1 << p0) : 0;
-#pragma unroll
-      for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) started |= __shfl_xor(started, msk, SMX_WP_LANES);
+      const int started = team_or(start >= 0 ? (1 << p0) : 0);
       const int prov = __popc(started & ((1 << p0) - 1));
       int cnt = 0;
-      double gx = 0, gy = 0, gh = 0;  // first waypoint of this lane's first path
+      WpFirst g = {false, 0.0, 0.0, 0.0};  // first waypoint of this lane's first path
       if (start >= 0) {
         BranchState bs;
         bs.reset();
         do {
-          if (cnt == 0 && prov < P) {
-            WpRows rows = wp_rows(o, gid, P, W, prov);
-            if (SMX_SKIP(a, 32768)) rows.pos = nullptr;
-            const int n = equally_spaced_path(m, seed.f, bs, start, lookahead, px, py, knots, KSTRIDE, W,
-                                              [&](int i, const WaypointOut& w) {
-                                                if (i == 0) {
-                                                  gx = w.x;
-                                                  gy = w.y;
-                                                  gh = w.heading;
-                                                }
-                                                wp_put(m, rows, i, w);
-                                              });
-            wp_zero(rows, n < W ? n : W, W);
-            o.wp_count[gid * (P + 1) + 1 + prov] = (uint8_t)(n < W ? n : W);
-          } else {
-            equally_spaced_path(m, seed.f, bs, start, lookahead, px, py, knots, KSTRIDE, 0,
-                                [&](int, const WaypointOut&) {});
-          }
+          if (cnt == 0 && prov < P)
+            wp_emit_path<KSTRIDE>(a, seed.f, bs, start, gid, px, py, knots, prov, true, true, &g, true, !SMX_SKIP(a, 32768));
+          else
+            wp_emit_path<KSTRIDE>(a, seed.f, bs, start, gid, px, py, knots, 0, false, false, nullptr);
           ++cnt;
         } while (bs.advance());
       }
-      int branching = (cnt > 1) ? 1 : 0;
-#pragma unroll
-      for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) branching |= __shfl_xor(branching, msk, SMX_WP_LANES);
-      if (!branching && seed.n_lanes <= SMX_WP_LANES) {
-        // ---- the guess held: path numbers are the provisional ones
-        n_paths_total = __popc(started);
-        const int src = started ? (__ffs(started) - 1) : 0;
-        fwx = __shfl(gx, src, SMX_WP_LANES);
-        fwy = __shfl(gy, src, SMX_WP_LANES);
-        fwh = __shfl(gh, src, SMX_WP_LANES);
-        have_first_wp = n_paths_total > 0;
-      } else if (seed.n_lanes <= SMX_WP_LANES) {
-        // ---- a lane branches inside the lookahead: paths are numbered lanes by index, branches
-        // depth-first, i.e. lane p's paths follow those of the lower lanes.  The counts are known from
-        // the first pass, so an exclusive prefix over the team gives every lane the numbers of its
-        // own paths, and each lane writes its own branches again, now into the right rows.  Only a
-        // first path whose provisional row was already the right one stays as written: provisional
-        // rows are distinct (a lane's rank among the started lanes), so nobody else wrote there in the
-        // first pass, and whoever owns another lane's stale provisional row rewrites it here, later.
-        int incl = cnt;
-        {
-          int t = __shfl_up(incl, 1, SMX_WP_LANES);
-          if (p0 >= 1) incl += t;
-          t = __shfl_up(incl, 2, SMX_WP_LANES);
-          if (p0 >= 2) incl += t;
-        }
-        n_paths_total = __shfl(incl, SMX_WP_LANES - 1, SMX_WP_LANES);
-        const int base = incl - cnt;
-        const bool first_in_place = base == prov;
-        if (start >= 0 && base < P && !(cnt == 1 && first_in_place)) {
-          BranchState bs;
-          bs.reset();
-          int idx = base;
-          do {
-            if (idx >= P) break;
-            if (idx == base && first_in_place) {
-              // only walked, to learn the branchings the enumeration continues from
-              equally_spaced_path(m, seed.f, bs, start, lookahead, px, py, knots, KSTRIDE, 0,
-                                  [&](int, const WaypointOut&) {});
-            } else {
-              WpRows rows = wp_rows(o, gid, P, W, idx);
-              const int n = equally_spaced_path(m, seed.f, bs, start, lookahead, px, py, knots, KSTRIDE, W,
-                                                [&](int i, const WaypointOut& w) { wp_put(m, rows, i, w); });
-              wp_zero(rows, n < W ? n : W, W);
-              o.wp_count[gid * (P + 1) + 1 + idx] = (uint8_t)(n < W ? n : W);
-            }
-            ++idx;
-          } while (bs.advance());
-        }
-        const int src = started ? (__ffs(started) - 1) : 0;  // path 0 is the lowest started lane's first path
-        fwx = __shfl(gx, src, SMX_WP_LANES);
-        fwy = __shfl(gy, src, SMX_WP_LANES);
-        fwh = __shfl(gh, src, SMX_WP_LANES);
-        have_first_wp = n_paths_total > 0;
+      const bool branching = team_or(cnt > 1 ? 1 : 0) != 0;
+      if (seed.n_lanes > SMX_WP_LANES) {
+        n_paths_total = waypoints_long_way<KSTRIDE>(a, seed, gid, p0, px, py, knots, fw);
       } else {
-        // ---- roads with more than four lanes: number the paths the long way (lanes by index, branches
-        // depth-first): every lane walks every path to discover the branchings, lane (idx % 4) writes kept path idx
-        int idx = 0;
-        for (int li = 0; li < seed.n_lanes; ++li) {
-          const int st = seed_start(m, seed, li, px, py);
-          if (st < 0) continue;
-          BranchState bs;
-          bs.reset();
-          do {
-            const bool kept = idx < P && (idx % SMX_WP_LANES) == p0;
-            const bool first_path = (idx == 0 && p0 == 0);
-            if (kept || first_path) {
-              WpRows rows = wp_rows(o, gid, P, W, kept ? idx : 0);
-              const int n = equally_spaced_path(m, seed.f, bs, st, lookahead, px, py, knots, KSTRIDE, kept ? W : 1,
-                                                [&](int i, const WaypointOut& w) {
-                                                  if (first_path && i == 0) {
-                                                    have_first_wp = true;
-                                                    fwx = w.x;
-                                                    fwy = w.y;
-                                                    fwh = w.heading;
-                                                  }
-                                                  if (kept) wp_put(m, rows, i, w);
-                                                });
-              if (kept) {
-                wp_zero(rows, n < W ? n : W, W);
-                o.wp_count[gid * (P + 1) + 1 + idx] = (uint8_t)(n < W ? n : W);
-              }
-            } else if (p0 == 0 || idx < P) {
-              equally_spaced_path(m, seed.f, bs, st, lookahead, px, py, knots, KSTRIDE, 0,
-                                  [&](int, const WaypointOut&) {});
-            }
-            ++idx;
-          } while (bs.advance() && (p0 == 0 || idx < P));
-        }
-        n_paths_total = __shfl(idx, 0, SMX_WP_LANES);  // lane 0 counts them all
+        // the guess held (path numbers are the provisional ones) unless a lane branches inside the lookahead
+        n_paths_total = branching ? wp_emit_branches<KSTRIDE>(a, seed.f, gid, p0, px, py, knots, start, cnt, prov, g)
+                                  : __popc(started);
+        fw = team_first_waypoint(started, g, n_paths_total > 0);
       }
     }
     SMX_TSTAMP(tw2);
     SMX_TACC(1, tw1, tw2);
-    // rows of the paths that do not exist
-    for (int slot = n_paths_total + ((p0 - n_paths_total) & (SMX_WP_LANES - 1)); slot < P; slot += SMX_WP_LANES) {
-      wp_zero(wp_rows(o, gid, P, W, slot), 0, W);
-      o.wp_count[gid * (P + 1) + 1 + slot] = 0;
-    }
-    if (p0 == 0) o.wp_count[gid * (P + 1)] = (uint8_t)(n_paths_total > 255 ? 255 : n_paths_total);
+    wp_close_rows(a, gid, p0, n_paths_total);
   }
 
   if (p0 != 0) return;
-  // ---- trip meter (sensors.py:880-947); reward = increment (agent_manager.py:233-234)
-  double dist = SF(SMX_S_DIST);
-  int32_t* trip_has_wp_p = a.st.facts_i32 + (size_t)SMX_FI_TRIP_HAS_WP * total + gid;
-  bool trip_has_wp = *trip_has_wp_p != 0;
-  if (flags & SMX_F_FIRST) {
-    // TripMeterSensor.__init__: first waypoint of the lowest lane, lookahead-1 path, no route
-    trip_has_wp = false;
-    const int ts = a.st.facts_i32[(size_t)SMX_FI_TRIP_START * total + gid];
-    if (ts >= 0) {
-      BranchState bs;
-      bs.reset();
-      RouteFilter nof;
-      nof.none();
-      equally_spaced_path(m, nof, bs, ts, 1, px, py, knots, KSTRIDE, 1, [&](int, const WaypointOut& w) {
-        SF(SMX_S_TRIP_X) = w.x;
-        SF(SMX_S_TRIP_Y) = w.y;
-        SF(SMX_S_TRIP_H) = w.heading;
-        trip_has_wp = true;
-      });
-    }
-    dist = 0.0;
-  }
-  const double last_dist = dist;
-  if (have_first_wp && trip_counts_waypoint(a, m, gid, total)) {
-    if (!trip_has_wp) {
-      SF(SMX_S_TRIP_X) = fwx;
-      SF(SMX_S_TRIP_Y) = fwy;
-      SF(SMX_S_TRIP_H) = fwh;
-      trip_has_wp = true;
-    } else {
-      double tx = SF(SMX_S_TRIP_X), ty = SF(SMX_S_TRIP_Y), th = SF(SMX_S_TRIP_H);
-      double dx = fwx - tx, dy = fwy - ty;
-      double nrm = sqrt(dx * dx + dy * dy);
-      if (nrm > 0.5) {
-        double hvx, hvy;
-        radians_to_vec(th, hvx, hvy);
-        double dot = hvx * dx + hvy * dy;
-        double sgn = dot > 0.0 ? 1.0 : (dot < 0.0 ? -1.0 : 0.0);
-        dist += sgn * nrm;
-        SF(SMX_S_TRIP_X) = fwx;
-        SF(SMX_S_TRIP_Y) = fwy;
-        SF(SMX_S_TRIP_H) = fwh;
-      }
-    }
-  }
-  SF(SMX_S_DIST) = dist;
-  o.dist[gid] = dist;
-  if (!a.keep_reward_done) {
-    o.reward[gid] = dist - last_dist;
-    if (o.learner) o.learner[gid] = (float)(dist - last_dist);
-  }
-  *trip_has_wp_p = trip_has_wp ? 1 : 0;  // the flags word itself is not written here (the observe role owns it)
+  trip_meter_update<KSTRIDE>(a, gid, total, flags, px, py, knots, fw);
   SMX_TSTAMP(tw3);
   SMX_TACC(3, tw0, tw3);
 }
@@ -2040,8 +2104,8 @@ __device__ __forceinline__ void waypoints_role(const KernelArgs& a, const int bl
 // Steps 2-3 run twice over the same stage: positions (x, y: 16 bytes), then heading / lane width / speed limit
 // / lane id / lane index (packed into 16 bytes); the interpolation is cheap next to a second stage's LDS.
 // Teams that need more — a branching inside the lookahead, a road with more than four lanes, a knot list
-// cut at SMX_WPK_CAP — write their rows afterwards with the serial emitter, exactly as waypoints_for does;
-// their rows are skipped in step 3.
+// cut at SMX_WPK_CAP — write their rows afterwards with the serial emitter's own steps (wp_emit_branches,
+// waypoints_long_way, wp_emit_path, wp_close_rows), exactly as waypoints_for does; their rows are skipped in step 3.
 // =================================================================================
 // floor(e / d) for 0 <= e < 4096, 1 <= d <= 64, rcp = 1.0f / d: (e + 0.5) / d is at least 0.5 / d away from an integer,
 // the float32 product is off by less than 4096 / d * 2^-22
@@ -2057,112 +2121,86 @@ struct WpRowBook {  // which table column feeds which output row of the workgrou
   unsigned int veh[SMX_WPT_VEHICLES];                        // the vehicle of team v (launch_vehicle: the alive list)
 };
 
-// Every path of the vehicle the long way (lanes by index, branches depth-first): every team lane walks
-// every path to discover the branchings, lane (idx % 4) writes kept path idx; rows of the paths that do
-// not exist are zeroed.  Returns the number of paths; lane 0 of the team learns the first waypoint.
-template <int KSTRIDE>
-__device__ inline int waypoints_long_way(const KernelArgs& a, const MapDev& m, const PathSeeds& seed, size_t gid, int p0,
-                                         double px, double py, int* knots, bool& have_first_wp, double& fwx, double& fwy,
-                                         double& fwh) {
-  const smx_outputs& o = a.out;
-  const int P = a.cfg.wp_paths, W = a.cfg.wp_len, lookahead = a.cfg.wp_lookahead;
-  int idx = 0;
-  for (int li = 0; li < seed.n_lanes; ++li) {
-    const int st = seed_start(m, seed, li, px, py);
-    if (st < 0) continue;
-    BranchState bs;
-    bs.reset();
-    do {
-      const bool kept = idx < P && (idx % SMX_WP_LANES) == p0;
-      const bool first_path = (idx == 0 && p0 == 0);
-      if (kept || first_path) {
-        WpRows rows = wp_rows(o, gid, P, W, kept ? idx : 0);
-        const int n = equally_spaced_path(m, seed.f, bs, st, lookahead, px, py, knots, KSTRIDE, kept ? W : 1,
-                                          [&](int i, const WaypointOut& w) {
-                                            if (first_path && i == 0) {
-                                              have_first_wp = true;
-                                              fwx = w.x;
-                                              fwy = w.y;
-                                              fwh = w.heading;
-                                            }
-                                            if (kept) wp_put(m, rows, i, w);
-                                          });
-        if (kept) {
-          wp_zero(rows, n < W ? n : W, W);
-          o.wp_count[gid * (P + 1) + 1 + idx] = (uint8_t)(n < W ? n : W);
-        }
-      } else if (p0 == 0 || idx < P) {
-        equally_spaced_path(m, seed.f, bs, st, lookahead, px, py, knots, KSTRIDE, 0, [&](int, const WaypointOut&) {});
-      }
-      ++idx;
-    } while (bs.advance() && (p0 == 0 || idx < P));
+// A team opens its vehicle's part of the book.  `tabled`: the vehicle's rows and counts leave through the book, rows
+// without a path as zeros; otherwise (a dead / absent vehicle, a team that goes the serial way) they are not the
+// sweep's to write.  The caller's barrier comes before the path lanes bind their rows.
+__device__ __forceinline__ void wp_book_open(WpRowBook& book, int v, int p0, int P, size_t gid, size_t total, bool tabled,
+                                             int n_paths) {
+  if (p0 == 0) {
+    book.veh[v] = (unsigned int)(gid < total ? gid : 0);
+    book.tabled[v] = tabled ? 1 : 0;
+    book.paths[v] = (unsigned char)n_paths;
   }
-  const int n_paths_total = __shfl(idx, 0, SMX_WP_LANES);  // lane 0 counts them all
-  for (int slot = n_paths_total + ((p0 - n_paths_total) & (SMX_WP_LANES - 1)); slot < P; slot += SMX_WP_LANES) {
-    wp_zero(wp_rows(o, gid, P, W, slot), 0, W);
-    o.wp_count[gid * (P + 1) + 1 + slot] = 0;
+  for (int slot = p0; slot < P; slot += SMX_WP_LANES) {
+    book.src[v * P + slot] = (short)(tabled ? SMX_ROW_ZERO : SMX_ROW_SKIP);
+    book.count[v * P + slot] = 0;
   }
-  if (p0 == 0) o.wp_count[gid * (P + 1)] = (uint8_t)(n_paths_total > 255 ? 255 : n_paths_total);
-  return n_paths_total;
 }
 
-// Trip meter (sensors.py:880-947) and reward = its increment (agent_manager.py:233-234): lane 0 of the team.
-template <int KSTRIDE>
-__device__ __forceinline__ void trip_meter_update(const KernelArgs& a, const MapDev& m, size_t gid, size_t total, int flags,
-                                                  double px, double py, int* knots, bool have_first_wp, double fwx,
-                                                  double fwy, double fwh) {
-  const smx_outputs& o = a.out;
-  double dist = SF(SMX_S_DIST);
-  int32_t* trip_has_wp_p = a.st.facts_i32 + (size_t)SMX_FI_TRIP_HAS_WP * total + gid;
-  bool trip_has_wp = *trip_has_wp_p != 0;
-  if (flags & SMX_F_FIRST) {
-    // TripMeterSensor.__init__: first waypoint of the lowest lane, lookahead-1 path, no route
-    trip_has_wp = false;
-    const int ts = a.st.facts_i32[(size_t)SMX_FI_TRIP_START * total + gid];
-    if (ts >= 0) {
-      BranchState bs;
-      bs.reset();
-      RouteFilter nof;
-      nof.none();
-      equally_spaced_path(m, nof, bs, ts, 1, px, py, knots, KSTRIDE, 1, [&](int, const WaypointOut& w) {
-        SF(SMX_S_TRIP_X) = w.x;
-        SF(SMX_S_TRIP_Y) = w.y;
-        SF(SMX_S_TRIP_H) = w.heading;
-        trip_has_wp = true;
-      });
-    }
-    dist = 0.0;
+// wp_count of the tabled vehicles: [vehicle][0] = number of paths, [1 + slot] = waypoints kept of the path in that row
+__device__ __forceinline__ void wp_book_store_counts(const WpRowBook& book, uint8_t* wp_count, int P) {
+  const int cells = SMX_WPT_VEHICLES * (P + 1);
+  for (int e = threadIdx.x; e < cells; e += SMX_BLOCK) {
+    const int vv = e / (P + 1), qq = e - vv * (P + 1);
+    if (!book.tabled[vv]) continue;
+    wp_count[(size_t)book.veh[vv] * (P + 1) + qq] = qq == 0 ? book.paths[vv] : book.count[vv * P + qq - 1];
   }
-  const double last_dist = dist;
-  if (have_first_wp && trip_counts_waypoint(a, m, gid, total)) {
-    if (!trip_has_wp) {
-      SF(SMX_S_TRIP_X) = fwx;
-      SF(SMX_S_TRIP_Y) = fwy;
-      SF(SMX_S_TRIP_H) = fwh;
-      trip_has_wp = true;
-    } else {
-      double tx = SF(SMX_S_TRIP_X), ty = SF(SMX_S_TRIP_Y), th = SF(SMX_S_TRIP_H);
-      double dx = fwx - tx, dy = fwy - ty;
-      double nrm = sqrt(dx * dx + dy * dy);
-      if (nrm > 0.5) {
-        double hvx, hvy;
-        radians_to_vec(th, hvx, hvy);
-        double dot = hvx * dx + hvy * dy;
-        double sgn = dot > 0.0 ? 1.0 : (dot < 0.0 ? -1.0 : 0.0);
-        dist += sgn * nrm;
-        SF(SMX_S_TRIP_X) = fwx;
-        SF(SMX_S_TRIP_Y) = fwy;
-        SF(SMX_S_TRIP_H) = fwh;
-      }
+}
+
+// Element e of the workgroup's rows, advanced by SMX_BLOCK: e = row * W + i, and row = vv * P + slot (team vv's path
+// row `slot`) where the rows swept are the book's own (a sweep of a list of rows reads `row` as its place in the list)
+struct WpCursor {
+  int row, i, vv, slot;
+  int W, P, drow, di;
+  __device__ __forceinline__ WpCursor(int W_, int P_) : W(W_), P(P_) {
+    row = threadIdx.x / W;
+    i = threadIdx.x - row * W;
+    vv = row / P;
+    slot = row - vv * P;
+    drow = SMX_BLOCK / W;
+    di = SMX_BLOCK - drow * W;
+  }
+  __device__ __forceinline__ void advance() {
+    row += drow;
+    slot += drow;
+    i += di;
+    if (i >= W) {
+      i -= W;
+      ++row;
+      ++slot;
+    }
+    while (slot >= P) {
+      slot -= P;
+      ++vv;
     }
   }
-  SF(SMX_S_DIST) = dist;
-  o.dist[gid] = dist;
-  if (!a.keep_reward_done) {
-    o.reward[gid] = dist - last_dist;
-    if (o.learner) o.learner[gid] = (float)(dist - last_dist);
-  }
-  *trip_has_wp_p = trip_has_wp ? 1 : 0;  // the flags word itself is not written here (the observe role owns it)
+};
+
+// How the team numbers its paths from what k_wp_walk found (the staged and the emit-parallel form)
+struct WpTeam {
+  int started;       // bit p: a path starts on seed lane p
+  int prov;          // this lane's path number if nobody branches
+  int n_paths;       // ... and the vehicle's number of paths then
+  bool branching;    // a lane branches inside the lookahead
+  bool long_way;     // a road with more than four lanes
+  bool serial_team;  // the team has to number its paths the long way: its rows do not come from the table
+  bool staged;       // this lane's path leaves through the table (or the serial emitter alone)
+  bool listed;       // ... k_wp_walk's knot list holds all its knots
+  bool my_row;       // ... and one of the kept rows holds it
+};
+// (`seeded`, `n_lanes` and therefore long_way, branching and serial_team are uniform in the team)
+__device__ __forceinline__ WpTeam wp_team_number(bool seeded, int n_lanes, int p0, int n_first, int nk, int cnt, int P) {
+  WpTeam t;
+  t.long_way = seeded && n_lanes > SMX_WP_LANES;
+  t.started = team_or(n_first > 0 ? (1 << p0) : 0);
+  t.prov = __popc(t.started & ((1 << p0) - 1));
+  t.branching = team_or(cnt > 1 ? 1 : 0) != 0;
+  t.serial_team = seeded && (t.long_way || t.branching);
+  t.n_paths = __popc(t.started);
+  t.staged = n_first > 0 && !t.serial_team;
+  t.listed = nk <= SMX_WPK_CAP;
+  t.my_row = t.staged && t.prov < P;
+  return t;
 }
 
 // k_alive_list: the alive vehicles of the tick, compacted (large batches).  Late in an episode most agents of an env
@@ -2311,7 +2349,7 @@ __device__ __forceinline__ void waypoints_tables_role(const KernelArgs& a, const
   const MapDev& m = a.map;
   const smx_outputs& o = a.out;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
-  const int P = c.wp_paths, W = c.wp_len, lookahead = c.wp_lookahead;
+  const int P = c.wp_paths, W = c.wp_len;
   const int p0 = threadIdx.x % SMX_WP_LANES, v = threadIdx.x / SMX_WP_LANES;
   // team v works on the v-th vehicle of the workgroup's sixteen launch slots (alive vehicles only when the tick
   // has its list): the rows of a vehicle are contiguous in the outputs, the vehicles of a workgroup need not be
@@ -2339,44 +2377,22 @@ __device__ __forceinline__ void waypoints_tables_role(const KernelArgs& a, const
   }
   SMX_TSTAMP(tw1);
   SMX_TACC(0, tw0, tw1);
-  // ---- 1. number the paths
+  // ---- 1. number the paths; the team's rows come from the stage unless it has to number them the long way
   const bool seeded = live && seed.road >= 0;
-  const bool long_way = seeded && seed.n_lanes > SMX_WP_LANES;  // uniform in the team
-  int started = n_first > 0 ? (1 << p0) : 0;
-#pragma unroll
-  for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) started |= __shfl_xor(started, msk, SMX_WP_LANES);
-  const int prov = __popc(started & ((1 << p0) - 1));  // this lane's path number if nobody branches
-  int branching = (cnt > 1) ? 1 : 0;
-#pragma unroll
-  for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) branching |= __shfl_xor(branching, msk, SMX_WP_LANES);
-  // the team's rows come from the stage unless it has to number its paths the long way
-  const bool serial_team = seeded && (long_way || branching != 0);  // uniform in the team
-  const int n_paths_staged = __popc(started);
-  const bool staged = n_first > 0 && !serial_team;            // this lane interpolates a path
-  const bool listed = nk <= SMX_WPK_CAP;                      // ... from a complete knot list
-  const bool my_row = staged && prov < P;                     // ... that one of the kept rows holds
-  if (p0 == 0) {
-    book.veh[v] = (unsigned int)(gid < total ? gid : 0);
-    book.tabled[v] = (live && !serial_team) ? 1 : 0;
-    book.paths[v] = (unsigned char)(seeded ? n_paths_staged : 0);
-  }
-  for (int slot = p0; slot < P; slot += SMX_WP_LANES) {
-    // rows without a path read zeros; a dead / absent vehicle's rows are not this kernel's to write
-    book.src[v * P + slot] = (short)((live && !serial_team) ? SMX_ROW_ZERO : SMX_ROW_SKIP);
-    book.count[v * P + slot] = 0;
-  }
+  const WpTeam tm = wp_team_number(seeded, seed.n_lanes, p0, n_first, nk, cnt, P);
+  wp_book_open(book, v, p0, P, gid, total, live && !tm.serial_team, seeded ? tm.n_paths : 0);
   __syncthreads();  // (one wavefront: orders the LDS writes of the team's other lanes)
-  if (my_row) {
-    book.src[v * P + prov] = (short)(listed ? col : SMX_ROW_SKIP);
-    book.count[v * P + prov] = (unsigned char)min(n_first, W);
+  if (tm.my_row) {
+    book.src[v * P + tm.prov] = (short)(tm.listed ? col : SMX_ROW_SKIP);
+    book.count[v * P + tm.prov] = (unsigned char)min(n_first, W);
   }
   // ---- 2 + 3, positions
-  const smx_lp_rec r0 = (staged && listed) ? load_lp(m, a.knots.idx[path], 46) : smx_lp_rec{};
+  const bool pre = tm.staged && tm.listed;
+  const smx_lp_rec r0 = pre ? load_lp(m, a.knots.idx[path], 46) : smx_lp_rec{};
   auto fetch = [&](int k) { return a.knots.idx[(size_t)(k + 1) * paths + path]; };
   // the knots of the path into registers, every load issued before anything waits for one (paths of more
   // knots than SMX_WPT_PRELOAD interpolate straight from the list, a dependent load per knot)
   constexpr int KP = SMX_WPT_PRELOAD;
-  const bool pre = staged && listed;
   double kx[KP], ky[KP], kh[KP], kw[KP], ks_[KP];
   int kl[KP];
   double w0 = 0.0, s0 = 0.0;
@@ -2406,45 +2422,31 @@ __device__ __forceinline__ void waypoints_tables_role(const KernelArgs& a, const
     }
   }
   const int elems = SMX_WPT_VEHICLES * P * W;
-  double gx = 0.0, gy = 0.0, gh = 0.0;  // first waypoint of this lane's path
+  WpFirst g = {false, 0.0, 0.0, 0.0};  // first waypoint of this lane's path
   {
     double2* stage = reinterpret_cast<double2*>(stage_raw);
     auto put_xy = [&](int i, const WaypointOut& w) {
       if (i == 0) {
-        gx = w.x;
-        gy = w.y;
+        g.x = w.x;
+        g.y = w.y;
       }
       stage[i * SMX_BLOCK + col] = make_double2(w.x, w.y);
     };
     if (pre)
-      interpolate_knots_preloaded<KP>(m, r0, w0, s0, nk, n_first, D, px, py, my_row ? W : 1, kx, ky, kh, kl, kw, ks_, fetch, put_xy);
+      interpolate_knots_preloaded<KP>(m, r0, w0, s0, nk, n_first, D, px, py, tm.my_row ? W : 1, kx, ky, kh, kl, kw, ks_, fetch, put_xy);
     __syncthreads();
     SMX_TSTAMP(tw2);
     SMX_TACC(1, tw1, tw2);
-    int row = threadIdx.x / W, i = threadIdx.x - row * W;  // element e = row * W + i, advanced by 64 per round
-    int vv = row / P, slot = row - vv * P;                 // row = vv * P + slot: team vv's path row `slot`
-    const int drow = SMX_BLOCK / W, di = SMX_BLOCK - drow * W;
-    for (int e = threadIdx.x; e < elems; e += SMX_BLOCK) {
-      const int src = book.src[row];
+    WpCursor cur(W, P);
+    for (int e = threadIdx.x; e < elems; e += SMX_BLOCK, cur.advance()) {
+      const int src = book.src[cur.row];
       if (src != SMX_ROW_SKIP) {
         double2 xy = make_double2(0.0, 0.0);
-        if (src >= 0 && i < (int)book.count[row]) xy = stage[i * SMX_BLOCK + src];
-        double* dst = o.wp_pos + (((size_t)book.veh[vv] * P + slot) * W + i) * 3;
+        if (src >= 0 && cur.i < (int)book.count[cur.row]) xy = stage[cur.i * SMX_BLOCK + src];
+        double* dst = o.wp_pos + (((size_t)book.veh[cur.vv] * P + cur.slot) * W + cur.i) * 3;
         dst[0] = xy.x;
         dst[1] = xy.y;
         dst[2] = 0.0;
-      }
-      row += drow;
-      slot += drow;
-      i += di;
-      if (i >= W) {
-        i -= W;
-        ++row;
-        ++slot;
-      }
-      while (slot >= P) {
-        slot -= P;
-        ++vv;
       }
     }
     __syncthreads();  // the stage is reused
@@ -2455,10 +2457,10 @@ __device__ __forceinline__ void waypoints_tables_role(const KernelArgs& a, const
   // ---- 2 + 3, the other fields
   {
     WpStageCell* stage = reinterpret_cast<WpStageCell*>(stage_raw);
-    if (staged && listed) {
+    if (pre) {
       int cached_lane = -1, cached_index = 0;  // consecutive waypoints mostly share their lane
       auto put_rest = [&](int i, const WaypointOut& w) {
-        if (i == 0) gh = w.heading;
+        if (i == 0) g.h = w.heading;
         if (w.lane != cached_lane) {
           cached_lane = w.lane;
           cached_index = m.lane_index[w.lane];
@@ -2472,16 +2474,14 @@ __device__ __forceinline__ void waypoints_tables_role(const KernelArgs& a, const
         cell.pad = 0;
         stage[i * SMX_BLOCK + col] = cell;
       };
-      interpolate_knots_preloaded<KP>(m, r0, w0, s0, nk, n_first, D, px, py, my_row ? W : 1, kx, ky, kh, kl, kw, ks_, fetch, put_rest);
+      interpolate_knots_preloaded<KP>(m, r0, w0, s0, nk, n_first, D, px, py, tm.my_row ? W : 1, kx, ky, kh, kl, kw, ks_, fetch, put_rest);
     }
     __syncthreads();
     SMX_TSTAMP(tw3b);
     SMX_TACC(25, tw3, tw3b);
-    int row = threadIdx.x / W, i = threadIdx.x - row * W;
-    int vv = row / P, slot = row - vv * P;
-    const int drow = SMX_BLOCK / W, di = SMX_BLOCK - drow * W;
-    for (int e = threadIdx.x; e < elems; e += SMX_BLOCK) {
-      const int src = book.src[row];
+    WpCursor cur(W, P);
+    for (int e = threadIdx.x; e < elems; e += SMX_BLOCK, cur.advance()) {
+      const int src = book.src[cur.row];
       if (src != SMX_ROW_SKIP) {
         WpStageCell cell;
         cell.heading = 0.0f;
@@ -2489,34 +2489,16 @@ __device__ __forceinline__ void waypoints_tables_role(const KernelArgs& a, const
         cell.speed = 0.0f;
         cell.lane = -1;
         cell.lane_index = 0;
-        if (src >= 0 && i < (int)book.count[row]) cell = stage[i * SMX_BLOCK + src];
-        const size_t q = ((size_t)book.veh[vv] * P + slot) * W + i;
+        if (src >= 0 && cur.i < (int)book.count[cur.row]) cell = stage[cur.i * SMX_BLOCK + src];
+        const size_t q = ((size_t)book.veh[cur.vv] * P + cur.slot) * W + cur.i;
         o.wp_heading[q] = cell.heading;
         o.wp_lane_width[q] = cell.width;
         o.wp_speed_limit[q] = cell.speed;
         o.wp_lane_id[q] = cell.lane;
         o.wp_lane_index[q] = cell.lane_index;
       }
-      row += drow;
-      slot += drow;
-      i += di;
-      if (i >= W) {
-        i -= W;
-        ++row;
-        ++slot;
-      }
-      while (slot >= P) {
-        slot -= P;
-        ++vv;
-      }
     }
-    // wp_count: [vehicle][0] = number of paths, [1 + slot] = waypoints kept of the path in that row
-    const int cells = SMX_WPT_VEHICLES * (P + 1);
-    for (int e = threadIdx.x; e < cells; e += SMX_BLOCK) {
-      const int vv = e / (P + 1), qq = e - vv * (P + 1);
-      if (!book.tabled[vv]) continue;
-      o.wp_count[(size_t)book.veh[vv] * (P + 1) + qq] = qq == 0 ? book.paths[vv] : book.count[vv * P + qq - 1];
-    }
+    wp_book_store_counts(book, o.wp_count, P);
     SMX_TSTAMP(tw3c);
     SMX_TACC(26, tw3b, tw3c);
   }
@@ -2524,84 +2506,32 @@ __device__ __forceinline__ void waypoints_tables_role(const KernelArgs& a, const
   SMX_TSTAMP(tw4);
   SMX_TACC(2, tw3, tw4);
   int* knots = reinterpret_cast<int*>(stage_raw) + threadIdx.x;
-  bool have_first_wp = false;
-  double fwx = 0.0, fwy = 0.0, fwh = 0.0;
+  WpFirst fw = {false, 0.0, 0.0, 0.0};
   if (live) {
-    if (long_way) {
-      waypoints_long_way<SMX_BLOCK>(a, m, seed, gid, p0, px, py, knots, have_first_wp, fwx, fwy, fwh);
-    } else if (serial_team) {
-      // ---- a lane branches inside the lookahead: paths are numbered lanes by index, branches depth-first,
-      // i.e. lane p's paths follow those of the lower lanes.  k_wp_walk counted them, so an exclusive prefix
-      // over the team gives every lane the numbers of its own paths, and each lane writes its own branches
-      // with the serial emitter (its own walks: the knot list only holds the first one).
-      int incl = cnt;
-      {
-        int t = __shfl_up(incl, 1, SMX_WP_LANES);
-        if (p0 >= 1) incl += t;
-        t = __shfl_up(incl, 2, SMX_WP_LANES);
-        if (p0 >= 2) incl += t;
+    if (tm.serial_team) {
+      // the team's rows with the serial emitter, exactly as waypoints_for writes them (its own walks: the knot list
+      // only holds the first path of a lane, whose start k_wp_walk left)
+      int n_paths_total;
+      if (tm.long_way) {
+        n_paths_total = waypoints_long_way<SMX_BLOCK>(a, seed, gid, p0, px, py, knots, fw);
+      } else {
+        n_paths_total = wp_emit_branches<SMX_BLOCK>(a, seed.f, gid, p0, px, py, knots, cnt > 0 ? a.knots.idx[path] : -1, cnt, -1, g);
+        fw = team_first_waypoint(tm.started, g, n_paths_total > 0);
       }
-      const int n_paths_total = __shfl(incl, SMX_WP_LANES - 1, SMX_WP_LANES);
-      const int base = incl - cnt;
-      if (cnt > 0 && base < P) {
-        const int start = a.knots.idx[path];
-        BranchState bs;
-        bs.reset();
-        int idx = base;
-        do {
-          if (idx >= P) break;
-          WpRows rows = wp_rows(o, gid, P, W, idx);
-          const int n = equally_spaced_path(m, seed.f, bs, start, lookahead, px, py, knots, SMX_BLOCK, W,
-                                            [&](int i, const WaypointOut& w) {
-                                              if (i == 0 && idx == 0) {
-                                                gx = w.x;
-                                                gy = w.y;
-                                                gh = w.heading;
-                                              }
-                                              wp_put(m, rows, i, w);
-                                            });
-          wp_zero(rows, n < W ? n : W, W);
-          o.wp_count[gid * (P + 1) + 1 + idx] = (uint8_t)(n < W ? n : W);
-          ++idx;
-        } while (bs.advance());
-      }
-      for (int slot = n_paths_total + ((p0 - n_paths_total) & (SMX_WP_LANES - 1)); slot < P; slot += SMX_WP_LANES) {
-        wp_zero(wp_rows(o, gid, P, W, slot), 0, W);
-        o.wp_count[gid * (P + 1) + 1 + slot] = 0;
-      }
-      if (p0 == 0) o.wp_count[gid * (P + 1)] = (uint8_t)(n_paths_total > 255 ? 255 : n_paths_total);
-      const int src = started ? (__ffs(started) - 1) : 0;  // path 0 is the lowest started lane's first path
-      fwx = __shfl(gx, src, SMX_WP_LANES);
-      fwy = __shfl(gy, src, SMX_WP_LANES);
-      fwh = __shfl(gh, src, SMX_WP_LANES);
-      have_first_wp = n_paths_total > 0;
+      wp_close_rows(a, gid, p0, n_paths_total);
     } else {
-      if (staged && !listed) {
-        // more knots than the list holds: this path leaves through the serial emitter (its own walk)
+      if (tm.staged && !tm.listed) {
+        // more knots than the list holds: this path leaves through the serial emitter (its own walk; the book has its count)
         BranchState bs;
         bs.reset();
-        WpRows rows = wp_rows(o, gid, P, W, my_row ? prov : 0);
-        const int n = equally_spaced_path(m, seed.f, bs, a.knots.idx[path], lookahead, px, py, knots, SMX_BLOCK, my_row ? W : 1,
-                                          [&](int i, const WaypointOut& w) {
-                                            if (i == 0) {
-                                              gx = w.x;
-                                              gy = w.y;
-                                              gh = w.heading;
-                                            }
-                                            if (my_row) wp_put(m, rows, i, w);
-                                          });
-        if (my_row) wp_zero(rows, n < W ? n : W, W);
+        wp_emit_path<SMX_BLOCK>(a, seed.f, bs, a.knots.idx[path], gid, px, py, knots, tm.my_row ? tm.prov : 0, tm.my_row, true, &g, false);
       }
-      const int src = started ? (__ffs(started) - 1) : 0;  // path 0 is the lowest started lane's
-      fwx = __shfl(gx, src, SMX_WP_LANES);
-      fwy = __shfl(gy, src, SMX_WP_LANES);
-      fwh = __shfl(gh, src, SMX_WP_LANES);
-      have_first_wp = n_paths_staged > 0;
+      fw = team_first_waypoint(tm.started, g, tm.n_paths > 0);
     }
   }
   SMX_TSTAMP(tw5);
   SMX_TACC(5, tw4, tw5);
-  if (live && p0 == 0) trip_meter_update<SMX_BLOCK>(a, m, gid, total, flags, px, py, knots, have_first_wp, fwx, fwy, fwh);
+  if (live && p0 == 0) trip_meter_update<SMX_BLOCK>(a, gid, total, flags, px, py, knots, fw);
   SMX_TSTAMP(tw6);
   SMX_TACC(3, tw0, tw6);
 }
@@ -2704,19 +2634,7 @@ __device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const i
   }
   // ---- 1. number the paths (as the staged form does)
   const bool seeded = live && seed.road >= 0;
-  const bool long_way = seeded && seed.n_lanes > SMX_WP_LANES;  // uniform in the team
-  int started = n_first > 0 ? (1 << p0) : 0;
-#pragma unroll
-  for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) started |= __shfl_xor(started, msk, SMX_WP_LANES);
-  const int prov = __popc(started & ((1 << p0) - 1));  // this lane's path number if nobody branches
-  int branching = (cnt > 1) ? 1 : 0;
-#pragma unroll
-  for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) branching |= __shfl_xor(branching, msk, SMX_WP_LANES);
-  const bool serial_team = seeded && (long_way || branching != 0);  // uniform in the team
-  const int n_paths_staged = __popc(started);
-  const bool staged = n_first > 0 && !serial_team;  // this lane's path leaves through the table (or the serial emitter alone)
-  const bool listed = nk <= SMX_WPK_CAP;            // ... k_wp_walk's knot list holds all its knots
-  const bool my_row = staged && prov < P;           // ... and one of the kept rows holds it
+  const WpTeam tm = wp_team_number(seeded, seed.n_lanes, p0, n_first, nk, cnt, P);
   // ---- 2. the path lane's walk over its knots: arclength, unwrapped headings, how many it needs
   SMX_TSTAMP(te1);
   SMX_TACC(32, te0, te1);
@@ -2731,7 +2649,7 @@ __device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const i
     kx[k] = ky[k] = kh[k] = cum[k] = 0.0;
     kl[k] = kstrict[k] = 0;
   }
-  const bool walk = my_row && listed && !SMX_SKIP(a, 1 << 22);
+  const bool walk = tm.my_row && tm.listed && !SMX_SKIP(a, 1 << 22);
   if (walk) {
     const smx_lp_rec r0 = load_lp(m, kid0, 46);
     lane0 = r0.lane;
@@ -2818,28 +2736,17 @@ __device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const i
   // (so does a new vehicle, whose trip meter starts with a walk of its own: none comes here on a tick, whose new
   // vehicles are the reset pass's)
   // (developer counts of the reasons, per path lane)
-  SMX_COUNT(50, live && p0 == 0 && long_way);
-  SMX_COUNT(51, live && p0 == 0 && branching != 0);
-  SMX_COUNT(52, my_row && !listed);
-  SMX_COUNT(53, my_row && listed && nrec == 0);
-  SMX_COUNT(54, my_row && listed && nrec > 0 && !tabled_path);
+  SMX_COUNT(50, live && p0 == 0 && tm.long_way);
+  SMX_COUNT(51, live && p0 == 0 && tm.branching);
+  SMX_COUNT(52, tm.my_row && !tm.listed);
+  SMX_COUNT(53, tm.my_row && tm.listed && nrec == 0);
+  SMX_COUNT(54, tm.my_row && tm.listed && nrec > 0 && !tabled_path);
   SMX_COUNT(55, live && p0 == 0 && (flags & SMX_F_FIRST));
   SMX_COUNT(56, live && p0 == 0);
-  int slow_i = (live && (serial_team || (my_row && !tabled_path) || (flags & SMX_F_FIRST))) ? 1 : 0;
-#pragma unroll
-  for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) slow_i |= __shfl_xor(slow_i, msk, SMX_WP_LANES);
-  const bool slow_team = slow_i != 0;  // uniform in the team
+  const bool slow_team =  // uniform in the team
+      team_or((live && (tm.serial_team || (tm.my_row && !tabled_path) || (flags & SMX_F_FIRST))) ? 1 : 0) != 0;
   if (slow_team) tabled_path = false;
-  if (p0 == 0) {
-    book.veh[v] = (unsigned int)(gid < total ? gid : 0);
-    book.tabled[v] = (live && !slow_team) ? 1 : 0;
-    book.paths[v] = (unsigned char)(seeded ? n_paths_staged : 0);
-  }
-  for (int slot = p0; slot < P; slot += SMX_WP_LANES) {
-    // rows without a path read zeros; a dead / absent vehicle's rows are not this kernel's to write
-    book.src[v * P + slot] = (short)((live && !slow_team) ? SMX_ROW_ZERO : SMX_ROW_SKIP);
-    book.count[v * P + slot] = 0;
-  }
+  wp_book_open(book, v, p0, P, gid, total, live && !slow_team, seeded ? tm.n_paths : 0);
   {
     // the wavefront's slow vehicles, appended with one atomic
     const bool app = slow_team && p0 == 0;
@@ -2853,9 +2760,9 @@ __device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const i
     }
   }
   __syncthreads();  // (one wavefront: orders the LDS writes of the team's other lanes)
-  if (my_row && !slow_team) {
-    book.src[v * P + prov] = (short)col;
-    book.count[v * P + prov] = (unsigned char)min(n_first, W);
+  if (tm.my_row && !slow_team) {
+    book.src[v * P + tm.prov] = (short)col;
+    book.count[v * P + tm.prov] = (unsigned char)min(n_first, W);
   }
   if (tabled_path) {
     hdr_step[col] = n_first > 1 ? D / (double)(n_first - 1) : 0.0;
@@ -2872,35 +2779,16 @@ __device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const i
       for (int k = 0; k < KP; ++k) one = one && (k + 1 >= nrec || kl[k] == lane0);
       hdr_one_lane[col] = one ? 1 : 0;
     }
-    WpKnot r;
-    r.x = k0x;
-    r.y = k0y;
-    r.h = k0h;
-    r.cum = 0.0;
-    WpKnotLanes rl;
-    rl.lane = (short)lane0;
-    rl.strict = (short)lane0;
-    if (!spilled) {
-      pool[off] = r;
-      pool_lanes[off] = rl;
-#pragma unroll
-      for (int k = 0; k < KP; ++k) {
-        if (k + 1 < nrec) {
-          WpKnot q;
-          q.x = kx[k];
-          q.y = ky[k];
-          q.h = kh[k];
-          q.cum = cum[k];
-          pool[off + k + 1] = q;
-          WpKnotLanes ql;
-          ql.lane = (short)kl[k];
-          ql.strict = (short)kstrict[k];
-          pool_lanes[off + k + 1] = ql;
-        }
-      }
-    } else {
-      WpKnot* gk = spill_knots + col * (SMX_WPE_KNOTS + 1);
-      WpKnotLanes* gl = spill_lanes + col * (SMX_WPE_KNOTS + 1);
+    // the path's records out of the registers: the projected start, then the knots it needs
+    auto put_records = [&](WpKnot* gk, WpKnotLanes* gl) {
+      WpKnot r;
+      r.x = k0x;
+      r.y = k0y;
+      r.h = k0h;
+      r.cum = 0.0;
+      WpKnotLanes rl;
+      rl.lane = (short)lane0;
+      rl.strict = (short)lane0;
       gk[0] = r;
       gl[0] = rl;
 #pragma unroll
@@ -2918,7 +2806,11 @@ __device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const i
           gl[k + 1] = ql;
         }
       }
-    }
+    };
+    if (!spilled)
+      put_records(pool + off, pool_lanes + off);
+    else
+      put_records(spill_knots + col * (SMX_WPE_KNOTS + 1), spill_lanes + col * (SMX_WPE_KNOTS + 1));
   }
   hdr_spill[col] = spilled ? 1 : 0;
   __threadfence_block();  // (the overflow area is read back by other lanes of the workgroup)
@@ -2956,11 +2848,11 @@ __device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const i
     const float rcp_p = 1.0f / (float)P;  // (row -> vehicle: small_quotient, rows below 128)
     const int drow = SMX_BLOCK / W, di = SMX_BLOCK - drow * W;
     {  // the empty rows of the workgroup's tabled vehicles: zeros, lane ids -1
-      int ridx = threadIdx.x / W, i = threadIdx.x - ridx * W;
-      for (int e = threadIdx.x; e < n_rows_zero * W; e += SMX_BLOCK) {
-        const int row = rows_zero[ridx];
+      WpCursor cur(W, P);
+      for (int e = threadIdx.x; e < n_rows_zero * W; e += SMX_BLOCK, cur.advance()) {
+        const int row = rows_zero[cur.row];
         const int vq = small_quotient(row, rcp_p);
-        const size_t q = ((size_t)book.veh[vq] * P + (row - vq * P)) * W + i;
+        const size_t q = ((size_t)book.veh[vq] * P + (row - vq * P)) * W + cur.i;
         double* dst = o.wp_pos + q * 3;
         dst[0] = 0.0;
         dst[1] = 0.0;
@@ -2970,12 +2862,6 @@ __device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const i
         o.wp_speed_limit[q] = 0.0f;
         o.wp_lane_id[q] = (int16_t)-1;
         o.wp_lane_index[q] = (int8_t)0;
-        ridx += drow;
-        i += di;
-        if (i >= W) {
-          i -= W;
-          ++ridx;
-        }
       }
     }
     const int elems = n_rows_live * W;
@@ -3091,9 +2977,9 @@ __device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const i
     // the rows whose knots lie in the overflow area (seldom any): the same expressions, one slot at a time, the knot
     // records read back from device memory
     if (n_rows_spill > 0) {
-      int ridx = threadIdx.x / W, i = threadIdx.x - ridx * W;
-      for (int e = threadIdx.x; e < n_rows_spill * W; e += SMX_BLOCK) {
-        const int row = rows_spill[ridx];
+      WpCursor cur(W, P);
+      for (int e = threadIdx.x; e < n_rows_spill * W; e += SMX_BLOCK, cur.advance()) {
+        const int row = rows_spill[cur.row], i = cur.i;
         const int vq = small_quotient(row, rcp_p), slot_q = row - vq * P;
         const int sc = (int)book.src[row];
         const bool have = i < (int)book.count[row];
@@ -3144,61 +3030,23 @@ __device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const i
         o.wp_speed_limit[q] = os;
         o.wp_lane_id[q] = (int16_t)oln;
         o.wp_lane_index[q] = (int8_t)oli;
-        ridx += drow;
-        i += di;
-        if (i >= W) {
-          i -= W;
-          ++ridx;
-        }
       }
     }
     SMX_TSTAMP(te4);
     SMX_TACC(35, te3, te4);
-    // wp_count: [vehicle][0] = number of paths, [1 + slot] = waypoints kept of the path in that row
-    const int cells = SMX_WPT_VEHICLES * (P + 1);
-    for (int e = threadIdx.x; e < cells; e += SMX_BLOCK) {
-      const int vq = e / (P + 1), qq = e - vq * (P + 1);
-      if (!book.tabled[vq]) continue;
-      o.wp_count[(size_t)book.veh[vq] * (P + 1) + qq] = qq == 0 ? book.paths[vq] : book.count[vq * P + qq - 1];
-    }
+    wp_book_store_counts(book, o.wp_count, P);
   }
   __syncthreads();  // first_wp is complete
   SMX_TSTAMP(te5);
   // ---- trip meter + reward (lane 0 of the team): path 0 is the lowest started lane's, row 0 of the vehicle
   if (live && !slow_team && p0 == 0) {
-    // trip_meter_update on the words loaded at the top (no new vehicle comes here)
-    double dist = trip_dist;
-    bool trip_has_wp = trip_has != 0;
-    const double last_dist = dist;
-    if (n_paths_staged > 0 && trip_counts_waypoint(a, m, gid, total)) {
-      const double fwx = first_wp[v][0], fwy = first_wp[v][1], fwh = first_wp[v][2];
-      if (!trip_has_wp) {
-        SF(SMX_S_TRIP_X) = fwx;
-        SF(SMX_S_TRIP_Y) = fwy;
-        SF(SMX_S_TRIP_H) = fwh;
-        trip_has_wp = true;
-      } else {
-        const double dx = fwx - trip_x, dy = fwy - trip_y;
-        const double nrm = sqrt(dx * dx + dy * dy);
-        if (nrm > 0.5) {
-          double hvx, hvy;
-          radians_to_vec(trip_h, hvx, hvy);
-          const double dot = hvx * dx + hvy * dy;
-          const double sgn = dot > 0.0 ? 1.0 : (dot < 0.0 ? -1.0 : 0.0);
-          dist += sgn * nrm;
-          SF(SMX_S_TRIP_X) = fwx;
-          SF(SMX_S_TRIP_Y) = fwy;
-          SF(SMX_S_TRIP_H) = fwh;
-        }
-      }
+    // the advance and the store, on the words loaded at the top (no new vehicle comes here: nothing to start)
+    TripMeter t = trip_meter_of(trip_dist, trip_x, trip_y, trip_h, trip_has != 0);
+    if (tm.n_paths > 0 && trip_counts_waypoint(a, m, gid, total)) {
+      const WpFirst fw = {true, first_wp[v][0], first_wp[v][1], first_wp[v][2]};
+      trip_meter_advance(a, gid, total, t, fw);
     }
-    SF(SMX_S_DIST) = dist;
-    o.dist[gid] = dist;
-    if (!a.keep_reward_done) {
-      o.reward[gid] = dist - last_dist;
-      if (o.learner) o.learner[gid] = (float)(dist - last_dist);
-    }
-    a.st.facts_i32[(size_t)SMX_FI_TRIP_HAS_WP * total + gid] = trip_has_wp ? 1 : 0;
+    trip_meter_store(a, gid, total, t);
   }
   SMX_TSTAMP(te6);
   SMX_TACC(36, te5, te6);
