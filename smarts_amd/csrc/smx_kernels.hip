@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "smx_guard.h"
+#include "smx_host.h"
 #include "smx_plan.h"
 #include "smx_scan.h"
 #include "smx_vehicle.h"
@@ -5395,6 +5396,7 @@ static double radius_threshold(double radius) {
   return t;
 }
 
+// (created by `new smx_handle_s()`: every member without an initialiser starts as zero)
 struct smx_handle_s {
   smx_config cfg;
   int device;
@@ -5404,7 +5406,7 @@ struct smx_handle_s {
   size_t map_bytes;
   void* knots_blob;  // KnotLists of the waypoints sensor (k_wp_walk -> k_waypoints_tables)
   void* spill_blob;  // k_waypoints_emit's overflow area (KernelArgs::wp_spill)
-  int wp_pool_limit; // records of k_waypoints_emit's LDS pool in use (smx_debug_set_wp_pool)
+  int wp_pool_limit = SMX_WPE_POOL; // records of k_waypoints_emit's LDS pool in use (smx_debug_set_wp_pool)
   int32_t* alive_blob;  // [total] alive list + two counters (ticks alternate), large batches
   uint8_t* pending_blob;  // [total] seed_pending
   int32_t* slow_blob;   // [4][total] slow lists of the fast kernels (scan facts, scan seeds, control, waypoint rows) + [2][4] counters (ticks alternate)
@@ -5429,9 +5431,11 @@ struct smx_handle_s {
   void* goals_blob;         // device copy of smx_set_mission_goals: goal kinds | lane end headings | dead-end lanes
   std::vector<int32_t> host_route_last;  // smx_set_missions' last roads (-1: empty route), kept for smx_set_mission_goals
   MissionsDev missions;
-  double heading_gain_pos, lateral_gain_pos;
+  // lane_following_controller.py:426-430: place_poles gains clipped to [0.02, 0.04] / [3.4, 4.1];
+  // for the sedan they saturate at (0.04, 3.4) for both Lane-space target speeds.
+  double heading_gain_pos = 0.04, lateral_gain_pos = 3.4;
   double nb_d2_max;
-  int slow_blocks;  // grid of the slow lists' kernels (smx_load_map)
+  int slow_blocks = SMX_SLOW_BLOCKS;  // grid of the slow lists' kernels (smx_load_map)
   // the alive list k_tail built for the next tick: counters of parity `seg_parity` (the other parity's are zero), built
   // from the flags of `list_state`; the next large-form tick takes it instead of launching k_alive_list
   bool list_ready;
@@ -5442,18 +5446,19 @@ struct smx_handle_s {
   double dagm_reach;  // half the widest lane width of the loaded map
   uint8_t* guard_out;  // smx_set_guard: the caller's byte buffer (null: guard off), its margin and the box of the loaded map
   uint64_t guard_count;
-  double guard_margin;
-  GuardBox guard_box;
+  double guard_margin = SMX_GUARD_MARGIN_DEFAULT;
+  GuardBox guard_box = {1.0, 1.0, 0.0, 0.0};
   uint8_t* rgb_out;   // smx_set_rgb_output: the caller's image buffer (null: none bound) and the bytes it holds
   uint64_t rgb_count;
   struct StackBinding {  // smx_bind_frame_stack: one caller-owned stack per (source, layout)
     int32_t source, layout;
     uint8_t* dst;
     uint64_t bytes;
+    uint32_t row;  // bytes per agent and frame (the configuration's: it does not change while the handle lives)
   };
   std::vector<StackBinding> stacks;
   int debug_skip;
-  int launch_strategy;  // SMX_LAUNCH_*
+  int launch_strategy = SMX_LAUNCH_AUTO;  // SMX_LAUNCH_*
   bool timing;
   std::vector<hipEvent_t> ev_pool;  // pairs: [2*i] start, [2*i+1] stop
   size_t ev_used;                   // pairs recorded since the last read
@@ -5535,145 +5540,26 @@ static AliveLayout alive_layout(const smx_config& c) {
   return l;
 }
 
-// SMX_SENSOR_LANE_TTC reads the waypoint and neighbour rows (smx_create and smx_check_buffers both ask)
-#define SMX_STR_(x) #x
-#define SMX_STR(x) SMX_STR_(x)
-static const char* lane_ttc_config_error(const smx_config& c) {
-  if (!(c.sensors & SMX_SENSOR_LANE_TTC)) return nullptr;
-  if (!(c.sensors & SMX_SENSOR_WAYPOINTS) || !(c.sensors & SMX_SENSOR_NEIGHBORS))
-    return "lane_ttc: SMX_SENSOR_LANE_TTC needs SMX_SENSOR_WAYPOINTS and SMX_SENSOR_NEIGHBORS (it is a function of their rows)";
-  if ((int64_t)c.wp_paths * c.wp_len > SMX_TTC_MAX_WAYPOINTS)
-    return "lane_ttc: need wp_paths * wp_len <= " SMX_STR(SMX_TTC_MAX_WAYPOINTS) " (an agent's waypoints are staged in LDS)";
-  return nullptr;
-}
+// the constants smx_host.h decides with are the device side's
+static_assert(SMX_HOST_BLOCK == SMX_BLOCK && SMX_HOST_WP_LANES == SMX_WP_LANES && SMX_HOST_MAX_KNOTS == SMX_MAX_KNOTS &&
+                  SMX_HOST_SLOW_BLOCKS == SMX_SLOW_BLOCKS && SMX_HOST_STACK_BLOCK == SMX_STACK_BLOCK,
+              "smx_host.h mirrors these");
 
-// SMX_SENSOR_RGB's grid: the DAGM's limits (smx_create and smx_check_rgb_output both ask)
-static const char* rgb_config_error(const smx_config& c) {
-  if (!(c.sensors & SMX_SENSOR_RGB)) return nullptr;
-  if (c.rgb_width < 1 || c.rgb_height < 1 || ((int64_t)c.rgb_width * c.rgb_height) % 16 != 0 ||
-      (int64_t)c.rgb_width * c.rgb_height > 64 * 1024 || !(c.rgb_resolution > 0.0))
-    return "rgb: need width*height a multiple of 16 and at most 65536 (the class tile of an image is staged in LDS), resolution > 0";
-  return nullptr;
-}
-
-// smx_config.frame_stack: off, or FrameStack's num_stack (frame_stack.py:47 asserts num_stack > 1)
-static const char* frame_stack_config_error(const smx_config& c) {
-  if (c.frame_stack == 0 || (c.frame_stack >= 2 && c.frame_stack <= SMX_STACK_MAX_FRAMES)) return nullptr;
-  return "frame_stack: need 0 (off) or 2 <= frame_stack <= " SMX_STR(SMX_STACK_MAX_FRAMES) " (the reference asserts num_stack > 1)";
-}
-
-static int create_impl(const smx_config* cfg, int device, smx_handle* out) {
+// On failure no handle is left behind for the caller to remember to destroy.
+extern "C" int smx_create(const smx_config* cfg, int device, smx_handle* out) {
+  if (out) *out = nullptr;
+  if (!cfg || !out) return refuse(g_create_err, "smx_create: null config or handle pointer");
+  if (const char* why = config_error(*cfg)) return refuse(g_create_err, why);
+  const hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return refuse(g_create_err, std::string("hipSetDevice: ") + hipGetErrorString(e), SMX_ERR_HIP);
   smx_handle h = new (std::nothrow) smx_handle_s();
-  if (!h) return SMX_ERR_NOMEM;
+  if (!h) return refuse(g_create_err, "out of memory", SMX_ERR_NOMEM);
   h->cfg = *cfg;
   h->device = device;
-  h->map_loaded = false;
-  h->map_blob = nullptr;
-  h->map_bytes = 0;
-  h->knots_blob = nullptr;
-  h->spill_blob = nullptr;
-  h->wp_pool_limit = SMX_WPE_POOL;
-  h->alive_blob = nullptr;
-  h->scan_carry = nullptr;
-  h->slow_blob = nullptr;
-  h->pending_blob = nullptr;
-  h->alive_parity = 0;
-  h->list_ready = false;
-  h->seg_parity = 0;
-  h->list_state = smx_state{};
-  h->group_parity = 0;
-  h->knots = KnotLists{};
-  h->ctrl_blob = nullptr;
-  h->ctrl = CtrlHandoff{nullptr, nullptr};
-  h->status_dev = nullptr;
-  h->side_ready = false;
-  h->lidar_rays = nullptr;
-  h->rgb_out = nullptr;
-  h->rgb_count = 0;
-  h->guard_out = nullptr;
-  h->guard_count = 0;
-  h->guard_margin = SMX_GUARD_MARGIN_DEFAULT;
-  h->guard_box = GuardBox{1.0, 1.0, 0.0, 0.0};
-  // lane_following_controller.py:426-430: place_poles gains clipped to [0.02, 0.04] / [3.4, 4.1];
-  // for the sedan they saturate at (0.04, 3.4) for both Lane-space target speeds.
-  h->heading_gain_pos = 0.04;
-  h->lateral_gain_pos = 3.4;
   h->nb_d2_max = radius_threshold(h->cfg.nb_radius);
-  h->slow_blocks = SMX_SLOW_BLOCKS;
-  h->map_junctions = false;
-  h->timing = false;
-  h->ev_used = 0;
-  h->phase_timing = false;
-  h->ph_used = 0;
-  h->vias_dev = nullptr;
-  h->via_off_dev = nullptr;
-  h->n_vias = 0;
-  h->missions_blob = nullptr;
-  h->goals_blob = nullptr;
-  h->missions = MissionsDev{nullptr, nullptr};
-  h->map.route_pos = nullptr;
-  h->map.route_lane_ok = nullptr;
-  h->launch_strategy = SMX_LAUNCH_AUTO;
-  h->debug_skip = 0;
 #ifdef SMX_DEBUG_TIMING
   if (const char* dbg = getenv("SMX_DEBUG_SKIP")) h->debug_skip = atoi(dbg);
 #endif
-  *out = h;
-  const smx_config& c = h->cfg;
-  if (c.num_envs <= 0 || c.num_vehicles <= 0 || c.num_vehicles > SMX_BLOCK)
-    return fail(h, SMX_ERR_INVALID, "num_envs must be > 0 and 0 < num_vehicles <= 64");
-  if (!(c.dt > 0.0)) return fail(h, SMX_ERR_INVALID, "dt must be > 0");
-  if ((c.sensors & SMX_SENSOR_ROAD_WAYPOINTS) &&
-      (c.rw_horizon < 1 || c.rw_horizon > SMX_RW_HORIZON_MAX || c.rw_lanes < 1 || c.rw_lanes > SMX_RW_LANE_CAP || c.rw_paths < 1 ||
-       c.rw_paths > 64))
-    return fail(h, SMX_ERR_INVALID, "road waypoints: need 1 <= rw_horizon <= 64, 1 <= rw_lanes <= 8, 1 <= rw_paths <= 64");
-  if ((c.sensors & SMX_SENSOR_WAYPOINTS) &&
-      (c.wp_lookahead < 1 || c.wp_lookahead > SMX_MAX_KNOTS - 2 || c.wp_paths < 1 || c.wp_paths > 64 || c.wp_len < 1 || c.wp_len > c.wp_lookahead + 1))
-    return fail(h, SMX_ERR_INVALID, "waypoints: need lookahead >= 1, 1 <= wp_paths <= 64, 1 <= wp_len <= lookahead + 1");
-  if (c.via_max < 0 || c.via_max > 32) return fail(h, SMX_ERR_INVALID, "via_max must be in 0..32");
-  if (c.alive_lists < 0 || c.alive_lists > SMX_MAX_ALIVE_LISTS || c.alive_min_ego < 0 || c.alive_min_total < 0)
-    return fail(h, SMX_ERR_INVALID, "agents_alive: at most 4 lists, non-negative minima");
-  if (c.num_social < 0 || c.num_social >= c.num_vehicles)
-    return fail(h, SMX_ERR_INVALID, "num_social must leave at least one agent slot");
-  if (c.num_social > 0 && !(c.social_speed_factor >= 0.0))
-    return fail(h, SMX_ERR_INVALID, "social_speed_factor must be >= 0");
-  if (c.social_model != SMX_SOCIAL_CONSTANT && c.social_model != SMX_SOCIAL_IDM)
-    return fail(h, SMX_ERR_INVALID, "unknown social_model");
-  if (c.action_space < SMX_ACTION_SPACE_LANE || c.action_space > SMX_ACTION_SPACE_IMITATION)
-    return fail(h, SMX_ERR_INVALID, "unknown action_space");
-  if ((c.sensors & SMX_SENSOR_OGM) &&
-      (c.ogm_width < 1 || c.ogm_height < 1 || (c.ogm_width * c.ogm_height) % 16 != 0 ||
-       c.ogm_width * c.ogm_height > 64 * 1024 || !(c.ogm_resolution > 0.0)))
-    return fail(h, SMX_ERR_INVALID, "ogm: need width*height a multiple of 16 and at most 65536, resolution > 0");
-  if ((c.sensors & SMX_SENSOR_DAGM) &&
-      (c.dagm_width < 1 || c.dagm_height < 1 || (c.dagm_width * c.dagm_height) % 16 != 0 ||
-       c.dagm_width * c.dagm_height > 64 * 1024 || !(c.dagm_resolution > 0.0)))
-    return fail(h, SMX_ERR_INVALID, "dagm: need width*height a multiple of 16 and at most 65536, resolution > 0");
-  if ((c.sensors & SMX_SENSOR_LIDAR) && (c.lidar_rays < 1 || c.lidar_rays > 65536))
-    return fail(h, SMX_ERR_INVALID, "lidar: need 1 <= lidar_rays <= 65536");
-  if ((c.sensors & SMX_SENSOR_NEIGHBORS) && (c.nb_max < 1 || c.nb_max > 127))
-    return fail(h, SMX_ERR_INVALID, "neighbours: need 1 <= nb_max <= 127");
-  if (const char* why = lane_ttc_config_error(c)) return fail(h, SMX_ERR_INVALID, why);
-  if (const char* why = rgb_config_error(c)) return fail(h, SMX_ERR_INVALID, why);
-  if (const char* why = frame_stack_config_error(c)) return fail(h, SMX_ERR_INVALID, why);
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return fail(h, SMX_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-  return SMX_OK;
-}
-
-extern "C" int smx_create(const smx_config* cfg, int device, smx_handle* out) {
-  if (out) *out = nullptr;
-  if (!cfg || !out) {
-    g_create_err = "smx_create: null config or handle pointer";
-    return SMX_ERR_INVALID;
-  }
-  smx_handle h = nullptr;
-  const int rc = create_impl(cfg, device, &h);
-  if (rc != SMX_OK) {  // no half-made handle for the caller to remember to destroy
-    g_create_err = h ? h->err : "out of memory";
-    delete h;
-    return rc;
-  }
   *out = h;
   return SMX_OK;
 }
@@ -5724,97 +5610,19 @@ extern "C" int smx_set_controller_gains(smx_handle h, double heading_gain, doubl
   return SMX_OK;
 }
 
-namespace {
-struct BlobWriter {
-  std::string host;
-  size_t add(const void* p, size_t bytes) {
-    size_t off = (host.size() + 255) & ~size_t(255);
-    host.resize(off + bytes);
-    if (bytes) memcpy(&host[off], p, bytes);
-    return off;
-  }
-};
-}  // namespace
-
 extern "C" int smx_load_map(smx_handle h, const smx_map_tables* t) {
   if (!h || !t) return SMX_ERR_INVALID;
-  if (t->n_lanes <= 0 || t->n_roads <= 0 || t->n_lanepoints <= 0) return fail(h, SMX_ERR_INVALID, "empty map tables");
-  if (t->n_lanes > 32767) return fail(h, SMX_ERR_INVALID, "lane ids are reported as int16: at most 32767 lanes");
-  SMX_HIP(hipSetDevice(h->device));
-  BlobWriter w;
-  const size_t nl = t->n_lanes, nr = t->n_roads, np_ = t->n_lanepoints, nv = t->n_shape_pts;
-  const size_t lpg_cells = (size_t)t->lpg_nx * t->lpg_ny, sg_cells = (size_t)t->sg_nx * t->sg_ny;
-  // every record index stored in the tables is range-checked here, once, so that the kernels can
-  // follow them without bounds tests
-  for (size_t i = 0; i < np_; ++i) {
-    const smx_lp_rec& r = t->lp_rec[i];
-    if (r.lane < 0 || r.lane >= t->n_lanes || r.next0 >= t->n_lanepoints || r.knot_next >= t->n_lanepoints ||
-        (r.n_next > 0 && (r.next_off < 0 || r.next_off + r.n_next > t->n_succ || r.next0 < 0 || r.knot_next < 0)))
-      return fail(h, SMX_ERR_INVALID, "lanepoint record out of range");
-  }
-  for (int i = 0; i < t->n_succ; ++i) {
-    const smx_succ_rec& r = t->succ_rec[i];
-    if (r.idx < 0 || r.idx >= t->n_lanepoints || r.knot < 0 || r.knot >= t->n_lanepoints || r.lane < 0 ||
-        r.lane >= t->n_lanes || r.hops < 1)
-      return fail(h, SMX_ERR_INVALID, "successor record out of range");
-  }
-  for (int i = 0; i < t->sg_off[sg_cells]; ++i)
-    if (t->sg_rec[i].lane < 0 || t->sg_rec[i].lane >= t->n_lanes || t->sg_rec[i].v0 < 0 || t->sg_rec[i].v0 + 1 >= t->n_shape_pts)
-      return fail(h, SMX_ERR_INVALID, "segment record out of range");
-  if (!t->lane_in_off || !t->lane_in_idx || !t->road_par_off || !t->road_par_idx)
-    return fail(h, SMX_ERR_INVALID, "map tables: lane_in_* / road_par_* missing");
-  for (int i = 0; i < t->lane_in_off[nl]; ++i)
-    if (t->lane_in_idx[i] < 0 || t->lane_in_idx[i] >= t->n_lanes) return fail(h, SMX_ERR_INVALID, "incoming lane out of range");
-  for (int i = 0; i < t->road_par_off[nr]; ++i)
-    if (t->road_par_idx[i] < 0 || t->road_par_idx[i] >= t->n_roads) return fail(h, SMX_ERR_INVALID, "parallel road out of range");
+  if (const char* why = map_tables_error(*t)) return fail(h, SMX_ERR_INVALID, why);
   // a bound guard stays bound: its margin against this map's cells (smx_guard.h), its box recomputed below
   if (h->guard_out && !guard_map_ok(*t, h->guard_margin))
     return fail(h, SMX_ERR_INVALID, "state guard: with this margin a cell index of this map's grids would not fit (smx_guard.h, SMX_GUARD_INDEX_MAX)");
-  h->dagm_reach = 0.0;
-  for (size_t i = 0; i < nl; ++i) h->dagm_reach = std::max(h->dagm_reach, 0.5 * t->lane_width[i]);
-  // The slow lists' kernels run a fixed grid that strides a list whose length only the device knows.  On a map
-  // whose lanes never split the lists hold a few vehicles of a hundred thousand and the grid is an empty launch's latency;
-  // where lanes branch or cross, a third of the vehicles is on them (minicity, 262 144 vehicles: 77 000 rows through
-  // 512 workgroups were half a wavefront per SIMD for nine passes, 1.4 ms of a 2.8 ms tick) — a team slot for every
-  // second vehicle then.
-  {
-    // (a lanepoint with several successors: lanes that split.  Junction-internal lanes alone do not tell — the loop map's
-    // two edges are joined by six of them, one successor each)
-    bool junctions = false;
-    for (int i = 0; i < t->n_lanepoints && !junctions; ++i) junctions = t->lp_rec[i].n_next > 1;
-    const size_t tv = (size_t)h->cfg.num_envs * h->cfg.num_vehicles;
-    const size_t teams_per_block = SMX_BLOCK / SMX_WP_LANES;
-    h->map_junctions = junctions;
-    h->slow_blocks = SMX_SLOW_BLOCKS;
-    if (junctions) h->slow_blocks = (int)std::min<size_t>(8192, std::max<size_t>(SMX_SLOW_BLOCKS, tv / (2 * teams_per_block)));
-  }
-#define ADD(field, count, type) size_t off_##field = w.add(t->field, (size_t)(count) * sizeof(type))
-  ADD(lane_road, nl, int32_t);
-  ADD(lane_index, nl, int32_t);
-  ADD(lane_width, nl, double);
-  ADD(lane_speed, nl, double);
-  ADD(lane_length, nl, double);
-  ADD(lane_in_junction, nl, uint8_t);
-  ADD(lane_shape_off, nl + 1, int32_t);
-  ADD(shape_x, nv, double);
-  ADD(shape_y, nv, double);
-  ADD(shape_rec, nv, smx_shape_rec);
-  ADD(lane_out_off, nl + 1, int32_t);
-  ADD(lane_out_idx, t->lane_out_off[nl], int32_t);
-  ADD(lane_in_off, nl + 1, int32_t);
-  ADD(lane_in_idx, t->lane_in_off[nl], int32_t);
-  ADD(road_par_off, nr + 1, int32_t);
-  ADD(road_par_idx, t->road_par_off[nr], int32_t);
-  ADD(road_lane_off, nr + 1, int32_t);
-  ADD(road_lanes, t->road_lane_off[nr], int32_t);
-  ADD(road_is_junction, nr, uint8_t);
-  ADD(road_out_road, nr, int32_t);
-  ADD(lp_rec, np_, smx_lp_rec);
-  ADD(succ_rec, t->n_succ, smx_succ_rec);
-  ADD(lpg_off, lpg_cells + 1, int32_t);
-  ADD(lpg_pts, t->lpg_off[lpg_cells], smx_pt_rec);
-  ADD(sg_off, sg_cells + 1, int32_t);
-  ADD(sg_rec, t->sg_off[sg_cells], smx_seg_rec);
+  SMX_HIP(hipSetDevice(h->device));
+  h->dagm_reach = map_dagm_reach(*t);
+  h->map_junctions = map_lanes_split(*t);
+  h->slow_blocks = slow_list_blocks(h->map_junctions, (size_t)h->cfg.num_envs * h->cfg.num_vehicles);
+  BlobWriter w;
+#define ADD(field, type, count) const size_t off_##field = w.add(t->field, (size_t)(count) * sizeof(type));
+  SMX_MAP_TABLES(ADD, *t)
 #undef ADD
   if (h->map_blob) {
     (void)hipFree(h->map_blob);
@@ -5826,6 +5634,10 @@ extern "C" int smx_load_map(smx_handle h, const smx_map_tables* t) {
   char* base = (char*)h->map_blob;
   MapDev& m = h->map;
   m = *t;  // scalars; every pointer is re-pointed into the device blob below
+#define PTR(field, type, count) m.field = (const type*)(base + off_##field);
+  SMX_MAP_TABLES(PTR, *t)
+#undef PTR
+  const size_t nl = t->n_lanes;
   h->host_lane_road.assign(t->lane_road, t->lane_road + nl);
   h->host_lane_out_off.assign(t->lane_out_off, t->lane_out_off + nl + 1);
   h->host_lane_out_idx.assign(t->lane_out_idx, t->lane_out_idx + t->lane_out_off[nl]);
@@ -5836,34 +5648,6 @@ extern "C" int smx_load_map(smx_handle h, const smx_map_tables* t) {
   h->goals_blob = nullptr;
   h->host_route_last.clear();
   h->missions = MissionsDev{nullptr, nullptr};
-#define PTR(field, type) m.field = (const type*)(base + off_##field)
-  PTR(lane_road, int32_t);
-  PTR(lane_index, int32_t);
-  PTR(lane_width, double);
-  PTR(lane_speed, double);
-  PTR(lane_length, double);
-  PTR(lane_in_junction, uint8_t);
-  PTR(lane_shape_off, int32_t);
-  PTR(shape_x, double);
-  PTR(shape_y, double);
-  PTR(shape_rec, smx_shape_rec);
-  PTR(lane_out_off, int32_t);
-  PTR(lane_out_idx, int32_t);
-  PTR(lane_in_off, int32_t);
-  PTR(lane_in_idx, int32_t);
-  PTR(road_par_off, int32_t);
-  PTR(road_par_idx, int32_t);
-  PTR(road_lane_off, int32_t);
-  PTR(road_lanes, int32_t);
-  PTR(road_is_junction, uint8_t);
-  PTR(road_out_road, int32_t);
-  PTR(lp_rec, smx_lp_rec);
-  PTR(succ_rec, smx_succ_rec);
-  PTR(lpg_off, int32_t);
-  PTR(lpg_pts, smx_pt_rec);
-  PTR(sg_off, int32_t);
-  PTR(sg_rec, smx_seg_rec);
-#undef PTR
   if (!h->alive_blob) {  // the tick's alive list (large batches) + its counters, the env groups with new vehicles (alive_layout)
     const size_t n = alive_layout(h->cfg).size;
     SMX_HIP(hipMalloc((void**)&h->alive_blob, n * sizeof(int32_t)));
@@ -5981,45 +5765,10 @@ extern "C" int smx_set_missions(smx_handle h, const smx_mission* missions_host, 
   const int nv = h->cfg.num_vehicles, nr = h->map.n_roads;
   if (n_slots != 0 && n_slots != nv) return fail(h, SMX_ERR_INVALID, "smx_set_missions: one mission per vehicle slot (cfg.num_vehicles)");
   if ((size_t)nv * (size_t)nr > 0x7fffffffull) return fail(h, SMX_ERR_INVALID, "smx_set_missions: slots x roads too large");
-  const int nl = h->map.n_lanes;
-  std::vector<int16_t> pos((size_t)n_slots * nr, (int16_t)-1);
-  std::vector<uint8_t> lane_ok((size_t)n_slots * nl, (uint8_t)0);
-  std::vector<int32_t> last((size_t)n_slots, -1);
-  std::vector<double> goal((size_t)n_slots * 3, 0.0);
-  bool any = false;
-  for (int s = 0; s < n_slots; ++s) {
-    const smx_mission& ms = missions_host[s];
-    if (ms.route_len == 0) continue;  // endless mission: empty route (plan.py:321-323)
-    if (ms.route_len < 0 || ms.route_len > 32767 || ms.route_off < 0 || (int64_t)ms.route_off + ms.route_len > n_route_roads)
-      return fail(h, SMX_ERR_INVALID, "smx_set_missions: route range outside route_roads (at most 32767 roads)");
-    if (!(ms.goal_radius >= 0.0) || !std::isfinite(ms.goal_x) || !std::isfinite(ms.goal_y))
-      return fail(h, SMX_ERR_INVALID, "smx_set_missions: a fixed route needs a PositionalGoal (finite position, radius >= 0)");
-    for (int k = 0; k < ms.route_len; ++k) {
-      const int road = route_roads_host[ms.route_off + k];
-      if (road < 0 || road >= nr) return fail(h, SMX_ERR_INVALID, "smx_set_missions: road index out of range");
-      int16_t& p = pos[(size_t)s * nr + road];
-      if (p < 0) p = (int16_t)k;  // first occurrence: `min` over the route keeps the first minimum
-    }
-    last[s] = route_roads_host[ms.route_off + ms.route_len - 1];
-    // lanepoints.py:666-683 per lane (the rule lane_allowed evaluates for the short in-junction lists): on a road
-    // of the route, and — unless that is the route's last road — leading on to a road of the route
-    const int16_t* on = &pos[(size_t)s * nr];
-    for (int lane = 0; lane < nl; ++lane) {
-      const int road = h->host_lane_road[lane];
-      bool ok = on[road] >= 0;
-      if (ok && road != last[s]) {
-        bool any = false;
-        for (int k = h->host_lane_out_off[lane]; k < h->host_lane_out_off[lane + 1]; ++k)
-          any = any || on[h->host_lane_road[h->host_lane_out_idx[k]]] >= 0;
-        ok = any;
-      }
-      lane_ok[(size_t)s * nl + lane] = ok ? 1 : 0;
-    }
-    goal[3 * s] = ms.goal_x;
-    goal[3 * s + 1] = ms.goal_y;
-    goal[3 * s + 2] = ms.goal_radius;
-    any = true;
-  }
+  RouteTables rt;
+  if (const char* why = route_tables(missions_host, n_slots, route_roads_host, n_route_roads, nr, h->map.n_lanes, h->host_lane_road,
+                                     h->host_lane_out_off, h->host_lane_out_idx, rt))
+    return fail(h, SMX_ERR_INVALID, why);
   SMX_HIP(hipSetDevice(h->device));
   SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
   if (h->missions_blob) (void)hipFree(h->missions_blob);
@@ -6033,20 +5782,20 @@ extern "C" int smx_set_missions(smx_handle h, const smx_mission* missions_host, 
   // the knot lists of the previous tick were walked under the old routes
   if (h->knots_blob && h->knots.key)
     SMX_HIP(hipMemset(h->knots.key, 0xff, 3 * (size_t)h->cfg.num_envs * nv * SMX_WP_LANES * sizeof(int32_t)));
-  h->host_route_last = last;
-  if (!any) return SMX_OK;
-  const size_t goal_bytes = goal.size() * sizeof(double), last_bytes = last.size() * sizeof(int32_t),
-               pos_bytes = pos.size() * sizeof(int16_t);
+  h->host_route_last = rt.last;
+  if (!rt.any) return SMX_OK;
+  const size_t goal_bytes = rt.goal.size() * sizeof(double), last_bytes = rt.last.size() * sizeof(int32_t),
+               pos_bytes = rt.pos.size() * sizeof(int16_t);
   const size_t off_last = goal_bytes, off_pos = (goal_bytes + last_bytes + 7) & ~(size_t)7;
   const size_t off_lane = (off_pos + pos_bytes + 7) & ~(size_t)7;
-  SMX_HIP(hipMalloc(&h->missions_blob, off_lane + lane_ok.size()));
+  SMX_HIP(hipMalloc(&h->missions_blob, off_lane + rt.lane_ok.size()));
   char* base = (char*)h->missions_blob;
-  SMX_HIP(hipMemcpy(base, goal.data(), goal_bytes, hipMemcpyHostToDevice));
-  SMX_HIP(hipMemcpy(base + off_last, last.data(), last_bytes, hipMemcpyHostToDevice));
-  SMX_HIP(hipMemcpy(base + off_pos, pos.data(), pos_bytes, hipMemcpyHostToDevice));
+  SMX_HIP(hipMemcpy(base, rt.goal.data(), goal_bytes, hipMemcpyHostToDevice));
+  SMX_HIP(hipMemcpy(base + off_last, rt.last.data(), last_bytes, hipMemcpyHostToDevice));
+  SMX_HIP(hipMemcpy(base + off_pos, rt.pos.data(), pos_bytes, hipMemcpyHostToDevice));
   h->missions.goal = (const double*)base;
   h->missions.route_last = (const int32_t*)(base + off_last);
-  SMX_HIP(hipMemcpy(base + off_lane, lane_ok.data(), lane_ok.size(), hipMemcpyHostToDevice));
+  SMX_HIP(hipMemcpy(base + off_lane, rt.lane_ok.data(), rt.lane_ok.size(), hipMemcpyHostToDevice));
   h->map.route_pos = (const int16_t*)(base + off_pos);
   h->map.route_lane_ok = (const uint8_t*)(base + off_lane);
   return SMX_OK;
@@ -6055,53 +5804,19 @@ extern "C" int smx_set_missions(smx_handle h, const smx_mission* missions_host, 
 extern "C" int smx_check_mission_goals(const smx_mission_goal* goals, int32_t n_slots, int32_t num_vehicles,
                                        const double* lane_end_heading, const int32_t* lane_dead_end, int32_t n_lanes,
                                        int32_t map_lanes, char* err, uint64_t err_len) {
-  auto bad = [&](const std::string& msg) {
-    if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", msg.c_str());
-    return (int)SMX_ERR_INVALID;
-  };
-  if (err && err_len > 0) err[0] = 0;
-  if (n_slots < 0 || (n_slots > 0 && !goals)) return bad("smx_set_mission_goals: null table");
-  if (n_slots != 0 && n_slots != num_vehicles) return bad("smx_set_mission_goals: one goal per vehicle slot (cfg.num_vehicles)");
-  bool traverse = false;
-  for (int s = 0; s < n_slots; ++s) {
-    const smx_mission_goal& g = goals[s];
-    const std::string at = "smx_set_mission_goals: slot " + std::to_string(s);
-    if (g.kind == SMX_GOAL_LAP) {
-      if (g.num_laps < 1) return bad(at + ": num_laps must be >= 1");
-      if (!std::isfinite(g.route_length) || g.route_length < 0.0) return bad(at + ": route_length must be finite and >= 0");
-    } else if (g.kind == SMX_GOAL_TRAVERSE) {
-      traverse = true;
-    } else if (g.kind != SMX_GOAL_POSITIONAL) {
-      return bad(at + ": unknown goal kind " + std::to_string(g.kind));
-    }
-  }
-  if (traverse) {
-    if (!lane_end_heading || !lane_dead_end) return bad("smx_set_mission_goals: a traverse goal needs the lane tables (lane_end_heading, lane_dead_end)");
-    if (n_lanes != map_lanes) return bad("smx_set_mission_goals: n_lanes is not the map's lane count");
-    for (int l = 0; l < n_lanes; ++l)
-      if (!std::isfinite(lane_end_heading[l])) return bad("smx_set_mission_goals: lane_end_heading not finite");
-  }
-  return SMX_OK;
+  const std::string msg = mission_goals_error(goals, n_slots, num_vehicles, lane_end_heading, lane_dead_end, n_lanes, map_lanes);
+  return report(msg.empty() ? SMX_OK : SMX_ERR_INVALID, msg, err, err_len);
 }
 
 extern "C" int smx_set_mission_goals(smx_handle h, const smx_mission_goal* goals_host, int32_t n_slots,
                                      const double* lane_end_heading_host, const int32_t* lane_dead_end_host, int32_t n_lanes) {
   if (!h) return SMX_ERR_INVALID;
   if (!h->map_loaded) return fail(h, SMX_ERR_STATE, "smx_set_mission_goals needs the map (the lane tables are checked against it)");
-  char why[192];
   const int nv = h->cfg.num_vehicles, nl = h->map.n_lanes;
-  if (smx_check_mission_goals(goals_host, n_slots, nv, lane_end_heading_host, lane_dead_end_host, n_lanes, nl, why, sizeof(why)) != SMX_OK)
-    return fail(h, SMX_ERR_INVALID, why);
+  const std::string msg = mission_goals_error(goals_host, n_slots, nv, lane_end_heading_host, lane_dead_end_host, n_lanes, nl);
+  if (!msg.empty()) return fail(h, SMX_ERR_INVALID, msg);
   bool any = false, traverse = false;
-  for (int s = 0; s < n_slots; ++s) {
-    const bool routed = s < (int)h->host_route_last.size() && h->host_route_last[s] >= 0;
-    if (goals_host[s].kind == SMX_GOAL_LAP && !routed)
-      return fail(h, SMX_ERR_INVALID, "smx_set_mission_goals: a lap goal needs the slot's fixed route and PositionalGoal (smx_set_missions)");
-    if (goals_host[s].kind == SMX_GOAL_TRAVERSE && routed)
-      return fail(h, SMX_ERR_INVALID, "smx_set_mission_goals: a traverse goal has an empty route (smx_mission.route_len = 0)");
-    any = any || goals_host[s].kind != SMX_GOAL_POSITIONAL;
-    traverse = traverse || goals_host[s].kind == SMX_GOAL_TRAVERSE;
-  }
+  if (const char* why = mission_goals_route_error(goals_host, n_slots, h->host_route_last, any, traverse)) return fail(h, SMX_ERR_INVALID, why);
   SMX_HIP(hipSetDevice(h->device));
   SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
   if (h->goals_blob) (void)hipFree(h->goals_blob);
@@ -6128,199 +5843,31 @@ extern "C" int smx_set_lidar_rays(smx_handle h, const double* rays_dev, int32_t 
   return SMX_OK;
 }
 
-// ---- entry check of every smx_reset / smx_step* (and smx_check_buffers, which needs no device) ----
-namespace {
-struct BufSpec {
-  const char* name;
-  const void* ptr;
-  uint64_t have;   // elements the caller declared
-  uint8_t dtype;   // SMX_DT_* the caller declared
-  uint64_t need;   // elements the configuration implies
-  uint8_t want;    // SMX_DT_* of the ABI
-  bool required;   // NULL is an error
-};
-const char* dtype_name(int d) {
-  static const char* n[] = {"none", "f64", "f32", "i32", "i16", "i8", "u8", "u64"};
-  return (d >= 0 && d <= SMX_DT_U64) ? n[d] : "?";
-}
-bool check_spec(const BufSpec& b, std::string& err) {
-  if (!b.ptr) {
-    if (!b.required) return true;
-    err = std::string(b.name) + " is NULL but the configuration needs it";
-    return false;
-  }
-  if (b.dtype != b.want) {
-    err = std::string(b.name) + ": declared dtype " + dtype_name(b.dtype) + ", the ABI says " + dtype_name(b.want);
-    return false;
-  }
-  if (b.have < b.need) {
-    err = std::string(b.name) + ": " + std::to_string(b.have) + " elements declared, the configuration needs " +
-          std::to_string(b.need) + " (a short buffer would be an out-of-bounds device write)";
-    return false;
-  }
-  return true;
-}
-}  // namespace
-
-static int check_buffers_impl(const smx_config& c, bool has_vias, bool need_lidar_rays_set, const smx_state* st,
-                              const smx_spawns* sp, const smx_outputs* o, std::string& err) {
-  if (!st || !sp || !o) {
-    err = "null state / spawns / outputs";
-    return SMX_ERR_INVALID;
-  }
-  (void)need_lidar_rays_set;
-  const uint64_t E = (uint64_t)c.num_envs, T = E * (uint64_t)c.num_vehicles;
-  const bool wp = (c.sensors & SMX_SENSOR_WAYPOINTS) != 0, nb = (c.sensors & SMX_SENSOR_NEIGHBORS) != 0;
-  const bool ogm = (c.sensors & SMX_SENSOR_OGM) != 0, dagm = (c.sensors & SMX_SENSOR_DAGM) != 0;
-  const bool lidar = (c.sensors & SMX_SENSOR_LIDAR) != 0, vias = c.via_max > 0 && has_vias;
-  const bool rw = (c.sensors & SMX_SENSOR_ROAD_WAYPOINTS) != 0;
-  const bool ttc = (c.sensors & SMX_SENSOR_LANE_TTC) != 0;
-  const bool ec = (c.sensors & SMX_SENSOR_EGO_CENTRIC) != 0;
-  if (const char* why = lane_ttc_config_error(c)) {
-    err = why;
-    return SMX_ERR_INVALID;
-  }
-  const uint64_t RWL = rw ? (uint64_t)c.rw_lanes : 0, RWP = rw ? (uint64_t)c.rw_paths : 0, RWR = rw ? 2 * (uint64_t)c.rw_horizon + 1 : 0;
-  const uint64_t PW = (uint64_t)c.wp_paths * c.wp_len, K = (uint64_t)c.nb_max, R = (uint64_t)c.lidar_rays;
-#define ST(field, idx, need, want, req) \
-  {"state." #field, st->field, st->count[idx], st->dtype[idx], (uint64_t)(need), want, req}
-#define OUT(field, idx, need, want, req) \
-  {"out." #field, o->field, o->count[idx], o->dtype[idx], (uint64_t)(need), want, req}
-  const BufSpec specs[] = {
-      ST(f64, SMX_ST_F64, SMX_S_COUNT * T, SMX_DT_F64, true),
-      ST(flags, SMX_ST_FLAGS, T, SMX_DT_I32, true),
-      ST(steps, SMX_ST_STEPS, T, SMX_DT_I32, true),
-      ST(env_ticks, SMX_ST_ENV_TICKS, E, SMX_DT_I32, true),
-      ST(env_done_count, SMX_ST_ENV_DONE_COUNT, E, SMX_DT_I32, true),
-      ST(env_episode, SMX_ST_ENV_EPISODE, E, SMX_DT_I32, true),
-      ST(driven_path, SMX_ST_DRIVEN_PATH, T * SMX_DRIVEN_PATH_LEN, SMX_DT_F64, (c.done_criteria & SMX_DONE_NOT_MOVING) != 0),
-      ST(seed_cache, SMX_ST_SEED_CACHE, SMX_SEED_COUNT * T, SMX_DT_I32, true),
-      ST(facts_i32, SMX_ST_FACTS_I32, SMX_FACT_I_COUNT * T, SMX_DT_I32, true),
-      ST(facts_f64, SMX_ST_FACTS_F64, SMX_FACT_F_COUNT * T, SMX_DT_F64, true),
-      ST(env_reset_pending, SMX_ST_ENV_RESET_PENDING, E, SMX_DT_I32, true),
-      {"spawns.pose", sp->pose, sp->pose_count, SMX_DT_F64, (uint64_t)(sp->episodes > 0 ? sp->episodes : 0) * T * 4, SMX_DT_F64, true},
-      {"spawns.social", sp->social, sp->social_count, SMX_DT_F64, (uint64_t)(sp->episodes > 0 ? sp->episodes : 0) * T * 2, SMX_DT_F64,
-       c.num_social > 0},
-      OUT(ego_pos, SMX_OUT_EGO_POS, 3 * T, SMX_DT_F64, true),
-      OUT(ego_f32, SMX_OUT_EGO_F32, SMX_EGO_F32_COUNT * T, SMX_DT_F32, true),
-      OUT(ego_lane, SMX_OUT_EGO_LANE, 2 * T, SMX_DT_I16, true),
-      OUT(events, SMX_OUT_EVENTS, SMX_EV_COUNT * T, SMX_DT_U8, true),
-      OUT(reward, SMX_OUT_REWARD, T, SMX_DT_F64, true),
-      OUT(dist, SMX_OUT_DIST, T, SMX_DT_F64, true),
-      OUT(done, SMX_OUT_DONE, T, SMX_DT_U8, true),
-      OUT(active, SMX_OUT_ACTIVE, T, SMX_DT_U8, true),
-      OUT(env_done, SMX_OUT_ENV_DONE, E, SMX_DT_U8, true),
-      OUT(via_near, SMX_OUT_VIA_NEAR, T * (uint64_t)(c.via_max > 0 ? c.via_max : 0), SMX_DT_I8, vias),
-      OUT(via_near_count, SMX_OUT_VIA_NEAR_COUNT, T, SMX_DT_U8, vias),
-      OUT(via_hit, SMX_OUT_VIA_HIT, T, SMX_DT_I32, vias),
-      OUT(learner, SMX_OUT_LEARNER, 2 * T, SMX_DT_F32, false),
-      OUT(wp_pos, SMX_OUT_WP_POS, T * PW * 3, SMX_DT_F64, wp),
-      OUT(wp_heading, SMX_OUT_WP_HEADING, T * PW, SMX_DT_F32, wp),
-      OUT(wp_lane_width, SMX_OUT_WP_LANE_WIDTH, T * PW, SMX_DT_F32, wp),
-      OUT(wp_speed_limit, SMX_OUT_WP_SPEED_LIMIT, T * PW, SMX_DT_F32, wp),
-      OUT(wp_lane_index, SMX_OUT_WP_LANE_INDEX, T * PW, SMX_DT_I8, wp),
-      OUT(wp_lane_id, SMX_OUT_WP_LANE_ID, T * PW, SMX_DT_I16, wp),
-      OUT(wp_count, SMX_OUT_WP_COUNT, T * (uint64_t)(c.wp_paths + 1), SMX_DT_U8, wp),
-      OUT(nb_pos, SMX_OUT_NB_POS, T * K * 3, SMX_DT_F64, nb),
-      OUT(nb_box, SMX_OUT_NB_BOX, T * K * 3, SMX_DT_F32, nb),
-      OUT(nb_heading, SMX_OUT_NB_HEADING, T * K, SMX_DT_F32, nb),
-      OUT(nb_speed, SMX_OUT_NB_SPEED, T * K, SMX_DT_F32, nb),
-      OUT(nb_lane_index, SMX_OUT_NB_LANE_INDEX, T * K, SMX_DT_I8, nb),
-      OUT(nb_lane_id, SMX_OUT_NB_LANE_ID, T * K, SMX_DT_I16, nb),
-      OUT(nb_slot, SMX_OUT_NB_SLOT, T * K, SMX_DT_I8, nb),
-      OUT(nb_count, SMX_OUT_NB_COUNT, T, SMX_DT_U8, nb),
-      OUT(ogm, SMX_OUT_OGM, T * (uint64_t)c.ogm_width * c.ogm_height, SMX_DT_U8, ogm),
-      OUT(lidar_hit, SMX_OUT_LIDAR_HIT, T * R, SMX_DT_U8, lidar),
-      OUT(lidar_point, SMX_OUT_LIDAR_POINT, T * R * 3, SMX_DT_F64, lidar),
-      OUT(dagm, SMX_OUT_DAGM, T * (uint64_t)c.dagm_width * c.dagm_height, SMX_DT_U8, dagm),
-      OUT(collidees, SMX_OUT_COLLIDEES, T, SMX_DT_U64, false),
-      OUT(rw_lane_count, SMX_OUT_RW_LANE_COUNT, T, SMX_DT_U8, rw),
-      OUT(rw_lane, SMX_OUT_RW_LANE, T * RWL, SMX_DT_I16, rw),
-      OUT(rw_path_count, SMX_OUT_RW_PATH_COUNT, T * RWL, SMX_DT_I16, rw),
-      OUT(rw_count, SMX_OUT_RW_COUNT, T * RWL * RWP, SMX_DT_U8, rw),
-      OUT(rw_pos, SMX_OUT_RW_POS, T * RWL * RWP * RWR * 3, SMX_DT_F64, rw),
-      OUT(rw_heading, SMX_OUT_RW_HEADING, T * RWL * RWP * RWR, SMX_DT_F32, rw),
-      OUT(rw_lane_width, SMX_OUT_RW_LANE_WIDTH, T * RWL * RWP * RWR, SMX_DT_F32, rw),
-      OUT(rw_speed_limit, SMX_OUT_RW_SPEED_LIMIT, T * RWL * RWP * RWR, SMX_DT_F32, rw),
-      OUT(rw_lane_index, SMX_OUT_RW_LANE_INDEX, T * RWL * RWP * RWR, SMX_DT_I8, rw),
-      OUT(rw_lane_id, SMX_OUT_RW_LANE_ID, T * RWL * RWP * RWR, SMX_DT_I16, rw),
-      OUT(final_ego_pos, SMX_OUT_FINAL_EGO_POS, 3 * T, SMX_DT_F64, false),
-      OUT(final_ego_f32, SMX_OUT_FINAL_EGO_F32, SMX_EGO_F32_COUNT * T, SMX_DT_F32, false),
-      OUT(final_ego_lane, SMX_OUT_FINAL_EGO_LANE, 2 * T, SMX_DT_I16, false),
-      OUT(final_events, SMX_OUT_FINAL_EVENTS, SMX_EV_COUNT * T, SMX_DT_U8, false),
-      OUT(final_dist, SMX_OUT_FINAL_DIST, T, SMX_DT_F64, false),
-      OUT(lane_ttc, SMX_OUT_LANE_TTC, SMX_TTC_COUNT * T, SMX_DT_F64, ttc),
-      OUT(lane_ttc_flags, SMX_OUT_LANE_TTC_FLAGS, T, SMX_DT_U8, ttc),
-      OUT(ego_frame, SMX_OUT_EGO_FRAME, 4 * T, SMX_DT_F64, ec),
-      OUT(ec_flags, SMX_OUT_EC_FLAGS, T, SMX_DT_U8, ec),
-      OUT(ec_ego_f32, SMX_OUT_EC_EGO_F32, SMX_EGO_F32_COUNT * T, SMX_DT_F32, ec),
-      OUT(ec_wp_pos, SMX_OUT_EC_WP_POS, T * PW * 3, SMX_DT_F64, ec && wp),
-      OUT(ec_wp_heading, SMX_OUT_EC_WP_HEADING, T * PW, SMX_DT_F32, ec && wp),
-      OUT(ec_nb_pos, SMX_OUT_EC_NB_POS, T * K * 3, SMX_DT_F64, ec && nb),
-      OUT(ec_nb_heading, SMX_OUT_EC_NB_HEADING, T * K, SMX_DT_F32, ec && nb),
-      OUT(ec_lidar_point, SMX_OUT_EC_LIDAR_POINT, T * R * 3, SMX_DT_F64, ec && lidar),
-      OUT(ec_rw_pos, SMX_OUT_EC_RW_POS, T * RWL * RWP * RWR * 3, SMX_DT_F64, ec && rw),
-      OUT(ec_rw_heading, SMX_OUT_EC_RW_HEADING, T * RWL * RWP * RWR, SMX_DT_F32, ec && rw),
-  };
-#undef ST
-#undef OUT
-  if (sp->episodes < 1) {
-    err = "spawn table is empty (episodes < 1)";
-    return SMX_ERR_INVALID;
-  }
-  for (const BufSpec& b : specs)
-    if (!check_spec(b, err)) return SMX_ERR_INVALID;
-  const int finals = (o->final_ego_pos != nullptr) + (o->final_ego_f32 != nullptr) + (o->final_ego_lane != nullptr) +
-                     (o->final_events != nullptr) + (o->final_dist != nullptr);
-  if (finals != 0 && finals != 5) {
-    err = "out.final_*: give all five buffers or none";
-    return SMX_ERR_INVALID;
-  }
-  return SMX_OK;
-}
-
+// ---- the smx_check_* entry points: smx_host.h's checks, callable without a device or a handle ----
 extern "C" int smx_check_buffers(const smx_config* cfg, int has_vias, const smx_state* st, const smx_spawns* sp,
                                  const smx_outputs* out, char* err, uint64_t err_len) {
   std::string msg;
-  int rc = cfg ? check_buffers_impl(*cfg, has_vias != 0, false, st, sp, out, msg) : SMX_ERR_INVALID;
-  if (!cfg) msg = "null config";
-  if (err && err_len > 0) {
-    const size_t n = std::min<size_t>(msg.size(), (size_t)err_len - 1);
-    memcpy(err, msg.data(), n);
-    err[n] = 0;
-  }
-  return rc;
-}
-
-static int check_rgb_output_impl(const smx_config& c, uint64_t count, std::string& err) {
-  if (const char* why = rgb_config_error(c)) {
-    err = why;
-    return SMX_ERR_INVALID;
-  }
-  if (!(c.sensors & SMX_SENSOR_RGB)) return SMX_OK;
-  if (c.num_envs <= 0 || c.num_vehicles <= 0) {
-    err = "rgb: num_envs and num_vehicles must be > 0";
-    return SMX_ERR_INVALID;
-  }
-  const uint64_t need = (uint64_t)c.num_envs * (uint64_t)c.num_vehicles * (uint64_t)c.rgb_width * (uint64_t)c.rgb_height * 3;
-  if (count < need) {
-    err = "rgb output: " + std::to_string(count) + " bytes declared, the configuration needs " + std::to_string(need) +
-          " (a short buffer would be an out-of-bounds device write)";
-    return SMX_ERR_INVALID;
-  }
-  return SMX_OK;
+  const int rc = cfg ? check_buffers_impl(*cfg, has_vias != 0, st, sp, out, msg) : refuse(msg, "null config");
+  return report(rc, msg, err, err_len);
 }
 
 extern "C" int smx_check_rgb_output(const smx_config* cfg, uint64_t count, char* err, uint64_t err_len) {
   std::string msg;
-  const int rc = cfg ? check_rgb_output_impl(*cfg, count, msg) : SMX_ERR_INVALID;
-  if (!cfg) msg = "null config";
-  if (err && err_len > 0) {
-    const size_t n = std::min<size_t>(msg.size(), (size_t)err_len - 1);
-    memcpy(err, msg.data(), n);
-    err[n] = 0;
-  }
-  return rc;
+  const int rc = cfg ? check_rgb_output_impl(*cfg, count, msg) : refuse(msg, "null config");
+  return report(rc, msg, err, err_len);
+}
+
+extern "C" int smx_check_guard(const smx_config* cfg, uint64_t count, double margin, char* err, uint64_t err_len) {
+  std::string msg;
+  const int rc = cfg ? check_guard_impl(*cfg, count, margin, msg) : refuse(msg, "null config");
+  return report(rc, msg, err, err_len);
+}
+
+extern "C" int smx_check_frame_stack(const smx_config* cfg, int32_t source, int32_t layout, uint64_t bytes, char* err, uint64_t err_len) {
+  std::string msg;
+  uint64_t row;
+  const int rc = cfg ? check_frame_stack_impl(*cfg, source, layout, bytes, row, msg) : refuse(msg, "null config");
+  return report(rc, msg, err, err_len);
 }
 
 extern "C" int smx_set_rgb_output(smx_handle h, uint8_t* rgb_dev, uint64_t count) {
@@ -6340,37 +5887,6 @@ extern "C" int smx_set_rgb_output(smx_handle h, uint8_t* rgb_dev, uint64_t count
   h->rgb_out = rgb_dev;
   h->rgb_count = count;
   return SMX_OK;
-}
-
-// ---- the state guard (smx_set_guard / smx_check_guard) ----
-static int check_guard_impl(const smx_config& c, uint64_t count, double margin, std::string& err) {
-  if (c.num_envs <= 0 || c.num_vehicles <= 0) {
-    err = "state guard: num_envs and num_vehicles must be > 0";
-    return SMX_ERR_INVALID;
-  }
-  if (!guard_margin_ok(margin)) {
-    err = "state guard: the margin must be finite and 0 <= margin <= " + std::to_string((long long)SMX_GUARD_MARGIN_MAX) + " m";
-    return SMX_ERR_INVALID;
-  }
-  const uint64_t need = (uint64_t)c.num_envs * (uint64_t)c.num_vehicles;
-  if (count < need) {
-    err = "state guard: " + std::to_string(count) + " bytes declared, the configuration needs " + std::to_string(need) +
-          " (a short buffer would be an out-of-bounds device write)";
-    return SMX_ERR_INVALID;
-  }
-  return SMX_OK;
-}
-
-extern "C" int smx_check_guard(const smx_config* cfg, uint64_t count, double margin, char* err, uint64_t err_len) {
-  std::string msg;
-  const int rc = cfg ? check_guard_impl(*cfg, count, margin, msg) : SMX_ERR_INVALID;
-  if (!cfg) msg = "null config";
-  if (err && err_len > 0) {
-    const size_t n = std::min<size_t>(msg.size(), (size_t)err_len - 1);
-    memcpy(err, msg.data(), n);
-    err[n] = 0;
-  }
-  return rc;
 }
 
 extern "C" int smx_set_guard(smx_handle h, uint8_t* guard_dev, uint64_t count, double margin) {
@@ -6393,124 +5909,6 @@ extern "C" int smx_set_guard(smx_handle h, uint8_t* guard_dev, uint64_t count, d
   return SMX_OK;
 }
 
-// ---- frame stacking (smx_bind_frame_stack / smx_check_frame_stack) ----
-// bytes per agent of a stackable source, 0 with the reason in `err`: the rows of smx_outputs by their SMX_OUT_* index (the
-// sizes check_buffers_impl asks of them), the image by SMX_STACK_SOURCE_RGB
-static uint64_t stack_row_bytes(const smx_config& c, int32_t source, std::string& err) {
-  const bool wp = (c.sensors & SMX_SENSOR_WAYPOINTS) != 0, nb = (c.sensors & SMX_SENSOR_NEIGHBORS) != 0;
-  const bool lidar = (c.sensors & SMX_SENSOR_LIDAR) != 0, rw = (c.sensors & SMX_SENSOR_ROAD_WAYPOINTS) != 0;
-  const bool ttc = (c.sensors & SMX_SENSOR_LANE_TTC) != 0, ec = (c.sensors & SMX_SENSOR_EGO_CENTRIC) != 0;
-  const uint64_t PW = (uint64_t)c.wp_paths * c.wp_len, K = (uint64_t)c.nb_max, R = (uint64_t)c.lidar_rays;
-  const uint64_t L = (uint64_t)c.rw_lanes, LP = L * (uint64_t)c.rw_paths, LPR = LP * (2 * (uint64_t)c.rw_horizon + 1);
-  const uint64_t V = c.via_max > 0 ? (uint64_t)c.via_max : 0;
-  bool on = true;
-  uint64_t bytes = 0;
-  switch (source) {
-    case SMX_STACK_SOURCE_RGB: on = (c.sensors & SMX_SENSOR_RGB) != 0, bytes = (uint64_t)c.rgb_width * c.rgb_height * 3; break;
-    case SMX_OUT_EGO_POS: bytes = 3 * 8; break;
-    case SMX_OUT_EGO_F32: bytes = SMX_EGO_F32_COUNT * 4; break;
-    case SMX_OUT_EGO_LANE: bytes = 2 * 2; break;
-    case SMX_OUT_EVENTS: bytes = SMX_EV_COUNT; break;
-    case SMX_OUT_REWARD: case SMX_OUT_DIST: case SMX_OUT_COLLIDEES: bytes = 8; break;
-    case SMX_OUT_DONE: case SMX_OUT_ACTIVE: bytes = 1; break;
-    case SMX_OUT_VIA_NEAR: on = V > 0, bytes = V; break;
-    case SMX_OUT_VIA_NEAR_COUNT: on = V > 0, bytes = 1; break;
-    case SMX_OUT_VIA_HIT: on = V > 0, bytes = 4; break;
-    case SMX_OUT_WP_POS: on = wp, bytes = PW * 24; break;
-    case SMX_OUT_WP_HEADING: case SMX_OUT_WP_LANE_WIDTH: case SMX_OUT_WP_SPEED_LIMIT: on = wp, bytes = PW * 4; break;
-    case SMX_OUT_WP_LANE_INDEX: on = wp, bytes = PW; break;
-    case SMX_OUT_WP_LANE_ID: on = wp, bytes = PW * 2; break;
-    case SMX_OUT_WP_COUNT: on = wp, bytes = (uint64_t)c.wp_paths + 1; break;
-    case SMX_OUT_NB_POS: on = nb, bytes = K * 24; break;
-    case SMX_OUT_NB_BOX: on = nb, bytes = K * 12; break;
-    case SMX_OUT_NB_HEADING: case SMX_OUT_NB_SPEED: on = nb, bytes = K * 4; break;
-    case SMX_OUT_NB_LANE_INDEX: case SMX_OUT_NB_SLOT: on = nb, bytes = K; break;
-    case SMX_OUT_NB_LANE_ID: on = nb, bytes = K * 2; break;
-    case SMX_OUT_NB_COUNT: on = nb, bytes = 1; break;
-    case SMX_OUT_OGM: on = (c.sensors & SMX_SENSOR_OGM) != 0, bytes = (uint64_t)c.ogm_width * c.ogm_height; break;
-    case SMX_OUT_LIDAR_HIT: on = lidar, bytes = R; break;
-    case SMX_OUT_LIDAR_POINT: on = lidar, bytes = R * 24; break;
-    case SMX_OUT_DAGM: on = (c.sensors & SMX_SENSOR_DAGM) != 0, bytes = (uint64_t)c.dagm_width * c.dagm_height; break;
-    case SMX_OUT_RW_LANE_COUNT: on = rw, bytes = 1; break;
-    case SMX_OUT_RW_LANE: case SMX_OUT_RW_PATH_COUNT: on = rw, bytes = L * 2; break;
-    case SMX_OUT_RW_COUNT: on = rw, bytes = LP; break;
-    case SMX_OUT_RW_POS: on = rw, bytes = LPR * 24; break;
-    case SMX_OUT_RW_HEADING: case SMX_OUT_RW_LANE_WIDTH: case SMX_OUT_RW_SPEED_LIMIT: on = rw, bytes = LPR * 4; break;
-    case SMX_OUT_RW_LANE_INDEX: on = rw, bytes = LPR; break;
-    case SMX_OUT_RW_LANE_ID: on = rw, bytes = LPR * 2; break;
-    case SMX_OUT_LANE_TTC: on = ttc, bytes = SMX_TTC_COUNT * 8; break;
-    case SMX_OUT_LANE_TTC_FLAGS: on = ttc, bytes = 1; break;
-    case SMX_OUT_EGO_FRAME: on = ec, bytes = 4 * 8; break;
-    case SMX_OUT_EC_FLAGS: on = ec, bytes = 1; break;
-    case SMX_OUT_EC_EGO_F32: on = ec, bytes = SMX_EGO_F32_COUNT * 4; break;
-    case SMX_OUT_EC_WP_POS: on = ec && wp, bytes = PW * 24; break;
-    case SMX_OUT_EC_WP_HEADING: on = ec && wp, bytes = PW * 4; break;
-    case SMX_OUT_EC_NB_POS: on = ec && nb, bytes = K * 24; break;
-    case SMX_OUT_EC_NB_HEADING: on = ec && nb, bytes = K * 4; break;
-    case SMX_OUT_EC_LIDAR_POINT: on = ec && lidar, bytes = R * 24; break;
-    case SMX_OUT_EC_RW_POS: on = ec && rw, bytes = LPR * 24; break;
-    case SMX_OUT_EC_RW_HEADING: on = ec && rw, bytes = LPR * 4; break;
-    default:  // env_done is per env, learner is [2][E*N], the final_* rows are written for restarting envs only
-      err = "frame stack: source " + std::to_string(source) + " is not a per-agent row that can be stacked "
-            "(an SMX_OUT_* index other than env_done, learner and final_*, or SMX_STACK_SOURCE_RGB)";
-      return 0;
-  }
-  if (!on || bytes == 0) {
-    err = "frame stack: the sensor of source " + std::to_string(source) + " is off in this configuration";
-    return 0;
-  }
-  if (bytes > (1ull << 30)) {
-    err = "frame stack: a row of more than 2^30 bytes per agent";
-    return 0;
-  }
-  return bytes;
-}
-
-static int check_frame_stack_impl(const smx_config& c, int32_t source, int32_t layout, uint64_t bytes, std::string& err) {
-  if (const char* why = frame_stack_config_error(c)) {
-    err = why;
-    return SMX_ERR_INVALID;
-  }
-  if (c.frame_stack == 0) {
-    err = "frame stack: smx_config.frame_stack is 0 (off): nothing can be bound";
-    return SMX_ERR_STATE;
-  }
-  if (c.num_envs <= 0 || c.num_vehicles <= 0) {
-    err = "frame stack: num_envs and num_vehicles must be > 0";
-    return SMX_ERR_INVALID;
-  }
-  if (layout != SMX_STACK_FRAMES && layout != SMX_STACK_DSTACK) {
-    err = "frame stack: unknown layout " + std::to_string(layout) + " (SMX_STACK_FRAMES or SMX_STACK_DSTACK)";
-    return SMX_ERR_INVALID;
-  }
-  if (layout == SMX_STACK_DSTACK && source != SMX_STACK_SOURCE_RGB) {
-    err = "frame stack: SMX_STACK_DSTACK is the layout of the RGB image alone (SMX_STACK_SOURCE_RGB); the single-channel "
-          "grids and the rows already have a fixed shape in SMX_STACK_FRAMES";
-    return SMX_ERR_INVALID;
-  }
-  const uint64_t row = stack_row_bytes(c, source, err);
-  if (!row) return SMX_ERR_INVALID;
-  const uint64_t need = (uint64_t)c.num_envs * (uint64_t)c.num_vehicles * (uint64_t)c.frame_stack * row;
-  if (bytes < need) {
-    err = "frame stack: " + std::to_string(bytes) + " bytes declared for source " + std::to_string(source) +
-          ", the configuration needs " + std::to_string(need) + " (a short buffer would be an out-of-bounds device write)";
-    return SMX_ERR_INVALID;
-  }
-  return SMX_OK;
-}
-
-extern "C" int smx_check_frame_stack(const smx_config* cfg, int32_t source, int32_t layout, uint64_t bytes, char* err, uint64_t err_len) {
-  std::string msg;
-  const int rc = cfg ? check_frame_stack_impl(*cfg, source, layout, bytes, msg) : SMX_ERR_INVALID;
-  if (!cfg) msg = "null config";
-  if (err && err_len > 0) {
-    const size_t n = std::min<size_t>(msg.size(), (size_t)err_len - 1);
-    memcpy(err, msg.data(), n);
-    err[n] = 0;
-  }
-  return rc;
-}
-
 extern "C" int smx_bind_frame_stack(smx_handle h, int32_t source, int32_t layout, void* stack_dev, uint64_t bytes) {
   if (!h) return SMX_ERR_INVALID;
   auto at = std::find_if(h->stacks.begin(), h->stacks.end(),
@@ -6520,7 +5918,8 @@ extern "C" int smx_bind_frame_stack(smx_handle h, int32_t source, int32_t layout
     return SMX_OK;
   }
   std::string msg;
-  const int rc = check_frame_stack_impl(h->cfg, source, layout, bytes, msg);
+  uint64_t row;
+  const int rc = check_frame_stack_impl(h->cfg, source, layout, bytes, row, msg);
   if (rc != SMX_OK) return fail(h, rc, msg);
   if (layout == SMX_STACK_DSTACK && (reinterpret_cast<uintptr_t>(stack_dev) & 15) != 0)
     return fail(h, SMX_ERR_INVALID, "frame stack: an SMX_STACK_DSTACK buffer must be 16-byte aligned (it is moved with up to 16-byte accesses)");
@@ -6531,7 +5930,7 @@ extern "C" int smx_bind_frame_stack(smx_handle h, int32_t source, int32_t layout
   }
   if (h->stacks.size() >= SMX_STACK_MAX_BINDINGS)
     return fail(h, SMX_ERR_STATE, "frame stack: at most " SMX_STR(SMX_STACK_MAX_BINDINGS) " bindings");
-  h->stacks.push_back({source, layout, (uint8_t*)stack_dev, bytes});
+  h->stacks.push_back({source, layout, (uint8_t*)stack_dev, bytes, (uint32_t)row});
   return SMX_OK;
 }
 
@@ -6552,26 +5951,22 @@ static int launch_frame_stacks(smx_handle h, const bool is_step, const uint8_t* 
   FrameStackArgs d = f;
   uint64_t blocks = 0, dstack_blocks = 0;
   for (const smx_handle_s::StackBinding& s : h->stacks) {
-    std::string msg;
-    const uint64_t row = stack_row_bytes(c, s.source, msg);  // (validated at the bind)
-    const uint8_t* src = s.source == SMX_STACK_SOURCE_RGB ? h->rgb_out
-                                                          : reinterpret_cast<const uint8_t* const*>(out)[s.source];  // (the struct opens with its SMX_OUT_BUFFERS pointers)
-    if (!src || !row)
+    const uint8_t* src = s.source == SMX_STACK_SOURCE_RGB ? h->rgb_out : (const uint8_t*)buffer_ptr(*out, s.source);
+    if (!src || !s.row)
       return fail(h, SMX_ERR_STATE, "frame stack: source " + std::to_string(s.source) + " is bound but its row is NULL in this call");
-    FrameStackBinding b{src, s.dst, (uint32_t)row, 0, 0, 0};
+    FrameStackBinding b{src, s.dst, s.row, 0, 0, 0};
     if (s.layout == SMX_STACK_DSTACK) {
       d.b[0] = b;
       d.n = 1;
-      dstack_blocks = ((uint64_t)f.total * ((row / 3 + 3) / 4) + SMX_STACK_BLOCK - 1) / SMX_STACK_BLOCK;
+      dstack_blocks = stack_dstack_blocks(s.row, f.total);
       continue;
     }
-    const uintptr_t both = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(s.dst) | (uintptr_t)row;
-    b.unit = (both & 15) == 0 ? 16 : (both & 3) == 0 ? 4 : 1;
-    b.block0 = (uint32_t)blocks;
-    blocks += ((uint64_t)f.total * (row / b.unit) + SMX_STACK_BLOCK - 1) / SMX_STACK_BLOCK;
+    const StackColumns at = stack_push_place(s.row, reinterpret_cast<uintptr_t>(src), reinterpret_cast<uintptr_t>(s.dst), f.total, blocks);
+    b.unit = at.unit;
+    b.block0 = at.block0;
     f.b[f.n++] = b;
   }
-  if (blocks >= (1ull << 31) || dstack_blocks >= (1ull << 31)) return fail(h, SMX_ERR_INVALID, "frame stack: the bound rows need more workgroups than a launch has");
+  if (blocks >= STACK_BLOCKS_CAP || dstack_blocks >= STACK_BLOCKS_CAP) return fail(h, SMX_ERR_INVALID, "frame stack: the bound rows need more workgroups than a launch has");
   if (f.n) hipLaunchKernelGGL(k_frame_push, dim3((unsigned)blocks), dim3(SMX_STACK_BLOCK), 0, stream, f);
   if (d.n) {
     void (*const dstack[])(FrameStackArgs) = {k_frame_dstack<2>, k_frame_dstack<3>, k_frame_dstack<4>, k_frame_dstack<5>,
@@ -6583,14 +5978,14 @@ static int launch_frame_stacks(smx_handle h, const bool is_step, const uint8_t* 
 
 static int check_buffers(smx_handle h, const smx_state* st, const smx_spawns* sp, const smx_outputs* o) {
   std::string msg;
-  const int rc = check_buffers_impl(h->cfg, h->n_vias > 0, true, st, sp, o, msg);
+  const int rc = check_buffers_impl(h->cfg, h->n_vias > 0, st, sp, o, msg);
   if (rc != SMX_OK) return fail(h, rc, msg);
   if ((h->cfg.sensors & SMX_SENSOR_LIDAR) && !h->lidar_rays)
     return fail(h, SMX_ERR_STATE, "lidar sensor enabled but smx_set_lidar_rays has not been called");
   if ((h->cfg.sensors & SMX_SENSOR_RGB) && !h->rgb_out)
     return fail(h, SMX_ERR_STATE, "rgb sensor enabled but no image buffer is bound (smx_set_rgb_output)");
   for (const smx_handle_s::StackBinding& s : h->stacks)  // (an optional row the caller left NULL: nothing is launched)
-    if (s.source != SMX_STACK_SOURCE_RGB && !reinterpret_cast<const void* const*>(o)[s.source])
+    if (s.source != SMX_STACK_SOURCE_RGB && !buffer_ptr(*o, s.source))
       return fail(h, SMX_ERR_STATE, "frame stack: source " + std::to_string(s.source) + " is bound but its row is NULL in smx_outputs");
   return SMX_OK;
 }
