@@ -75,6 +75,10 @@ struct KernelArgs {
   double dagm_reach;        // widest lane's half width (which segments can touch a DAGM view)
   uint8_t* rgb;             // SMX_SENSOR_RGB: the image buffer bound by smx_set_rgb_output, [E*N][rgb_height][rgb_width][3]
   KnotLists knots;          // library-owned hand-off: k_wp_walk -> k_waypoints_tables
+  // the map's knot table (smx_roadmap.h KnotRow), [n_lanepoints]; set in the one-lane cut's tick only: k_waypoints_emit
+  // and k_control_fast take their knot lists from it and k_wp_walk is not launched (null: the walked lists)
+  const KnotRow* knot_table;
+  unsigned long long* knot_served;  // developer (smx_debug_set_knot_table(h, 2)): path lanes k_waypoints_emit served from a row
   MissionsDev missions;     // device copy of smx_set_missions (null pointers: every mission endless)
   // large batches: the tick's alive vehicles, compacted by k_alive_list at the start of the tick (null: launch
   // index = vehicle).  The per-vehicle team kernels then run over full wavefronts however many agents are gone.
@@ -600,11 +604,11 @@ __device__ __forceinline__ double first_waypoint_distance(double rx, double ry, 
 // are loaded whatever nk16 is, and lane, width and speed limit of the waypoints (not the controller's business) are
 // left 0.
 template <bool ONE_LANE, class Put>
-__device__ __forceinline__ void ctrl_waypoints_from_knots(const KernelArgs& a, size_t total, size_t pth, const smx_lp_rec& r0,
+__device__ __forceinline__ void ctrl_waypoints_from_knots(const KernelArgs& a, const int32_t* knot1, size_t kstride, const smx_lp_rec& r0,
                                                           int nk16, int last, int n16, double px, double py, Put&& put) {
+  // (knot k + 1 of the list is knot1[k * kstride]: a column of KnotLists::idx, or a row of the knot table)
   const MapDev& m = a.map;
-  const size_t paths = total * SMX_WP_LANES;
-  auto fetch = [&](int k) { return (k == nk16 - 1 && last >= 0) ? last : a.knots.idx[(size_t)(k + 1) * paths + pth]; };
+  auto fetch = [&](int k) { return (k == nk16 - 1 && last >= 0) ? last : knot1[(size_t)k * kstride]; };
   constexpr int KP = SMX_WPT_PRELOAD;
   double kx[KP], ky[KP], kh[KP], kw[KP], ks_[KP];
   int kl[KP];
@@ -613,7 +617,7 @@ __device__ __forceinline__ void ctrl_waypoints_from_knots(const KernelArgs& a, s
 #pragma unroll
     for (int k = 0; k < KP; ++k) {
       if (ONE_LANE) {
-        const int id = a.knots.idx[(size_t)(k + 1) * paths + pth];  // (in range whatever nk16 is)
+        const int id = knot1[(size_t)k * kstride];  // (in range whatever nk16 is)
         kid[k] = (k == nk16 - 1 && last >= 0) ? last : id;
       } else {
         kid[k] = k < nk16 ? fetch(k) : 0;
@@ -880,7 +884,7 @@ __device__ __forceinline__ void control_paths_for(const KernelArgs& a, const Ctr
       team_nearest(my_d, my_idx);
       if (start < 0 || mine != wanted_path(my_idx, la.lane_change, n_paths)) return;
       const int n16 = n32 < SMX_CTRL_WPS ? n32 : SMX_CTRL_WPS;
-      ctrl_waypoints_from_knots<false>(a, total, path, r0, a.knots.nk16[path], a.knots.end16[path], n16, px, py, put);
+      ctrl_waypoints_from_knots<false>(a, a.knots.idx + paths + path, paths, r0, a.knots.nk16[path], a.knots.end16[path], n16, px, py, put);
       ho.n[gid] = n16;
       return;
     }
@@ -1223,20 +1227,37 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_fast(const KernelArgs a) 
   VehState s = load_vehicle(a, g, total);
   CtrlState cs = load_ctrl_state(a, g, total, flags);
   const PathSeeds seed = load_seeds(a, g, total);
-  const bool lists = a.knots.key != nullptr;
+  const bool table = a.knot_table != nullptr;
+  const bool lists = table || a.knots.key != nullptr;
   const size_t paths = total * SMX_WP_LANES;
   int kn_n[SMX_WP_LANES], kn_key0[SMX_WP_LANES], kn_key1[SMX_WP_LANES], kn_key2[SMX_WP_LANES], kn_cnt[SMX_WP_LANES],
       kn_nk16[SMX_WP_LANES], kn_end16[SMX_WP_LANES];
+  // with the knot table: the rows of the four start lanepoints (the seeds hold them: one level behind the seeds' loads);
+  // kn_key0 = the row's flags, kn_key1 / kn_key2 = the filter it was walked with, kn_cnt = its road
+  int st[SMX_WP_LANES];
 #pragma unroll
   for (int q = 0; q < SMX_WP_LANES; ++q) {
+    st[q] = (seed.road >= 0 && seed.n_lanes <= SMX_WP_LANES && q < seed.n_lanes) ? seed_start(m, seed, q, s.x, s.y) : -1;
     const size_t pth = g * SMX_WP_LANES + q;
-    kn_n[q] = lists ? (int)a.knots.n[pth] : 0;
-    kn_key0[q] = lists ? a.knots.key[pth] : -1;
-    kn_key1[q] = lists ? a.knots.key[paths + pth] : -1;
-    kn_key2[q] = lists ? a.knots.key[2 * paths + pth] : -1;
-    kn_cnt[q] = lists ? (int)a.knots.cnt[pth] : 0;
-    kn_nk16[q] = lists ? (int)a.knots.nk16[pth] : 0;
-    kn_end16[q] = lists ? a.knots.end16[pth] : -1;
+    if (table) {
+      // (a dead slot's seeds are words of any age: the row index is held to the table whatever they say)
+      const KnotRow* row = a.knot_table + ((unsigned)st[q] < (unsigned)m.n_lanepoints ? st[q] : 0);
+      kn_n[q] = row->n;
+      kn_key0[q] = row->flags;
+      kn_key1[q] = row->f0;
+      kn_key2[q] = row->f1;
+      kn_cnt[q] = row->road;
+      kn_nk16[q] = row->nk16;
+      kn_end16[q] = row->end16;
+    } else {
+      kn_n[q] = lists ? (int)a.knots.n[pth] : 0;
+      kn_key0[q] = lists ? a.knots.key[pth] : -1;
+      kn_key1[q] = lists ? a.knots.key[paths + pth] : -1;
+      kn_key2[q] = lists ? a.knots.key[2 * paths + pth] : -1;
+      kn_cnt[q] = lists ? (int)a.knots.cnt[pth] : 0;
+      kn_nk16[q] = lists ? (int)a.knots.nk16[pth] : 0;
+      kn_end16[q] = lists ? a.knots.end16[pth] : -1;
+    }
   }
   if (in_range && (flags & SMX_F_ALIVE)) {
     GuardVerdict gv = {0, GUARD_STORE};
@@ -1261,10 +1282,8 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_fast(const KernelArgs a) 
           int my_idx = 0;
           // the start lanepoints' records, together
           double rx[SMX_WP_LANES], ry[SMX_WP_LANES], rdx[SMX_WP_LANES], rdy[SMX_WP_LANES], rh[SMX_WP_LANES];
-          int st[SMX_WP_LANES];
 #pragma unroll
           for (int q = 0; q < SMX_WP_LANES; ++q) {
-            st[q] = q < seed.n_lanes ? seed_start(m, seed, q, px, py) : -1;
             const smx_lp_rec* r = m.lp_rec + (st[q] >= 0 ? st[q] : 0);
             rx[q] = r->x;
             ry[q] = r->y;
@@ -1277,7 +1296,10 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_fast(const KernelArgs a) 
 #pragma unroll
           for (int q = 0; q < SMX_WP_LANES; ++q) {
             if (st[q] >= 0) {
-              if (!knot_list_reusable(kn_key0[q], kn_key1[q], kn_key2[q], kn_cnt[q], kn_n[q], st[q], seed.f)) slow = true;
+              const bool usable = table ? knot_row_serves(kn_key0[q], kn_key1[q], kn_key2[q], kn_cnt[q], seed.f)
+                                        : knot_list_reusable(kn_key0[q], kn_key1[q], kn_key2[q], kn_cnt[q], kn_n[q], st[q], seed.f);
+              SMX_COUNT(57, !usable);
+              if (!usable) slow = true;
               const double d = first_waypoint_distance(rx[q], ry[q], rdx[q], rdy[q], kn_n[q], px, py);
               if (d < my_d) {
                 my_d = d;
@@ -1294,11 +1316,12 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_fast(const KernelArgs a) 
             for (int q = 0; q < SMX_WP_LANES; ++q)
               if ((started >> q) & 1)
                 if (__popc(started & ((1 << q) - 1)) == want) qw = q;
-            int n32w = 0, nk16 = 0, last = -1;
+            int n32w = 0, nk16 = 0, last = -1, stw = 0;
             smx_lp_rec r0 = smx_lp_rec{};
 #pragma unroll
             for (int q = 0; q < SMX_WP_LANES; ++q)
               if (q == qw) {
+                stw = st[q];
                 n32w = kn_n[q];
                 nk16 = kn_nk16[q];
                 last = kn_end16[q];  // the last knot when it is not one of the list's
@@ -1311,7 +1334,8 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_fast(const KernelArgs a) 
             r0.lane = 0;  // (lane, width and speed limit of the waypoints are not the controller's business)
             const int n16 = n32w < SMX_CTRL_WPS ? n32w : SMX_CTRL_WPS;
             double* col = path_lds + threadIdx.x;
-            ctrl_waypoints_from_knots<true>(a, total, gid * SMX_WP_LANES + qw, r0, nk16, last, n16, px, py,
+            const int32_t* const knot1 = table ? a.knot_table[stw].idx : a.knots.idx + paths + gid * SMX_WP_LANES + qw;
+            ctrl_waypoints_from_knots<true>(a, knot1, table ? (size_t)1 : paths, r0, nk16, last, n16, px, py,
                                             [&](int i, const WaypointOut& w) {
                                               col[(size_t)i * SMX_BLOCK] = w.heading;
                                               if (i < CTRL_XY) {
@@ -2263,51 +2287,17 @@ __device__ __forceinline__ void wp_walk_for(const KernelArgs& a, const size_t gi
       const int start = seed_start(m, seed, p0, px, py);
       if (start >= 0) {
         a.knots.idx[path] = start;
-        BranchState bs;
-        bs.reset();
-        int below16 = 0;        // knots less than 16 hops down
-        bool knot_at_16 = false;
-        int base_idx = start, base_hop = 0;  // the last lanepoint of the list less than 16 hops down (the start if no knot is)
-        const PathWalk w = walk_knots(m, seed.f, bs, start, c.wp_lookahead, px, py, [&](int k, int idx, int hop) {
-          if (k <= SMX_WPK_CAP) a.knots.idx[(size_t)k * paths + path] = idx;
-          if (hop < SMX_CTRL_WPS - 1) {
-            ++below16;
-            base_idx = idx;
-            base_hop = hop;
-          }
-          if (hop == SMX_CTRL_WPS - 1) knot_at_16 = true;
-        });
+        const KnotListHead w = walk_knot_list(m, seed.f, start, c.wp_lookahead, SMX_CTRL_WPS, px, py,
+                                              [&](int k, int idx, double) { a.knots.idx[(size_t)k * paths + path] = idx; });
         n = w.n;
         nk = w.nk;
         D = w.D;
-        // the lookahead-16 path: the whole path when it is no longer than that, else the knots less than 16
-        // hops down and the lanepoint 16 hops down (a knot of the list, or the probed interpolated lanepoint)
-        a.knots.nk16[path] = (uint8_t)(w.n <= SMX_CTRL_WPS ? w.nk : below16 + 1);
-        // (an interpolated lanepoint of the run that leaves the last knot before it: followed here, after the walk,
-        // from that knot's record — the successor the route filter allows where the knot branches; the list is only
-        // reused when exactly one path starts on this seed lane, so there is exactly one)
-        int end16 = -1;
-        if (w.n > SMX_CTRL_WPS && !knot_at_16) {
-          const smx_lp_rec br = load_lp(m, base_idx, 47);
-          int first = br.next0;
-          if (br.n_next > 1) {
-            first = -1;
-            for (int k = br.next_off; k < br.next_off + br.n_next && first < 0; ++k) {
-              const smx_succ_rec sr = m.succ_rec[k];
-              if (lane_allowed(m, seed.f, sr.lane)) first = sr.idx;
-            }
-          }
-          if (first >= 0) end16 = chain_at(m, first, SMX_CTRL_WPS - 1 - base_hop - 1, (br.flags & 1) != 0);
-        }
-        a.knots.end16[path] = end16;
+        cnt = w.cnt;
+        a.knots.nk16[path] = (uint8_t)w.nk16;
+        a.knots.end16[path] = w.end16;
         a.knots.key[path] = start;
         a.knots.key[paths + path] = seed.f.n > 0 ? seed.f.road[0] : -1;
         a.knots.key[2 * paths + path] = seed.f.n > 1 ? seed.f.road[1] : -1;
-        cnt = 1;
-        while (bs.advance()) {
-          walk_knots(m, seed.f, bs, start, c.wp_lookahead, px, py, [](int, int, int) {});
-          if (cnt < 255) ++cnt;
-        }
       }
     }
   }
@@ -2316,6 +2306,18 @@ __device__ __forceinline__ void wp_walk_for(const KernelArgs& a, const size_t gi
   a.knots.cnt[path] = (uint8_t)cnt;
   a.knots.D[path] = D;
   if (n == 0) a.knots.key[path] = -1;  // nothing here for the next tick's controller to reuse
+}
+
+// The map's knot table, once per map: one lane per lanepoint walks its row (build_knot_row: wp_walk_for's own walk).
+// stats: rows tabled, rows that touch their start road only.
+__global__ void __launch_bounds__(SMX_BLOCK) k_knot_table(const MapDev m, const int lookahead, KnotRow* rows, int32_t* stats) {
+  const int lp = (int)(blockIdx.x * SMX_BLOCK + threadIdx.x);
+  if (lp >= m.n_lanepoints) return;
+  KnotRow row;
+  build_knot_row(m, lp, lookahead, SMX_CTRL_WPS, row);
+  rows[lp] = row;
+  if (row.flags & SMX_KROW_TABLED) atomicAdd(stats, 1);
+  if (row.flags & SMX_KROW_SINGLE_ROAD) atomicAdd(stats + 1, 1);
 }
 
 __global__ void __launch_bounds__(SMX_BLOCK) k_wp_walk(const KernelArgs a) {
@@ -2613,13 +2615,42 @@ __device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const i
   const int pend = a.seed_pending != nullptr ? (int)a.seed_pending[g] : 0;
   double px = a.st.f64[(size_t)SMX_S_X * total + g], py = a.st.f64[(size_t)SMX_S_Y * total + g];
   PathSeeds seed = load_seeds(a, g, total);
-  int n_first = a.knots.n[pth];  // what k_wp_walk found on seed lane p0 (0: no path starts there)
-  int nk = a.knots.nk[pth], cnt = a.knots.cnt[pth];
-  double D = a.knots.D[pth];
-  const int kid0 = a.knots.idx[pth];
+  const bool table = a.knot_table != nullptr;
+  int n_first, nk, cnt, kid0;  // what the walk found on seed lane p0 (n_first 0: no path starts there)
+  double D = 0.0;
   int kid[KP];
+  // (table) the terms of D behind the first: those of knots 2 .. KD + 1 from here (a path of more knots is a bend: it reads
+  // the rest of its row where it sums D; the whole row in registers cost the kernel its third wavefront per SIMD)
+  constexpr int KD = 6;
+  double kd[KD];
+  bool untabled = false;       // (table) a path starts here and the table does not hold it for this vehicle's filter
+  if (table) {
+    // the row of the start lanepoint: one level behind the seeds' loads, and D is summed below in walk_knots' order —
+    // its first term is the only one the vehicle's position enters
+    kid0 = (seed.road >= 0 && seed.n_lanes <= SMX_WP_LANES && p0 < seed.n_lanes) ? seed_start(m, seed, p0, px, py) : -1;
+    if ((unsigned)kid0 >= (unsigned)m.n_lanepoints) kid0 = -1;  // (a dead slot's seeds are words of any age)
+    const KnotRow* row = a.knot_table + (kid0 >= 0 ? kid0 : 0);
+    const bool serves = knot_row_serves(row->flags, row->f0, row->f1, row->road, seed.f);
+    untabled = kid0 >= 0 && !serves;
+    n_first = (kid0 >= 0 && serves) ? (int)row->n : 0;
+    nk = (kid0 >= 0 && serves) ? (int)row->nk : 0;
+    cnt = (kid0 >= 0 && serves) ? 1 : 0;
 #pragma unroll
-  for (int k = 0; k < KP; ++k) kid[k] = a.knots.idx[(size_t)(k + 1) * paths + pth];
+    for (int k = 0; k < KP; ++k) kid[k] = row->idx[k];
+#pragma unroll
+    for (int k = 0; k < KD; ++k) kd[k] = row->d[k];
+    if (kid0 < 0) kid0 = 0;
+  } else {
+    n_first = a.knots.n[pth];
+    nk = a.knots.nk[pth];
+    cnt = a.knots.cnt[pth];
+    D = a.knots.D[pth];
+    kid0 = a.knots.idx[pth];
+#pragma unroll
+    for (int k = 0; k < KP; ++k) kid[k] = a.knots.idx[(size_t)(k + 1) * paths + pth];
+#pragma unroll
+    for (int k = 0; k < KD; ++k) kd[k] = 0.0;
+  }
   // the trip meter's words (lane 0 of the team uses them)
   const double trip_dist = a.st.f64[(size_t)SMX_S_DIST * total + g], trip_x = a.st.f64[(size_t)SMX_S_TRIP_X * total + g],
                trip_y = a.st.f64[(size_t)SMX_S_TRIP_Y * total + g], trip_h = a.st.f64[(size_t)SMX_S_TRIP_H * total + g];
@@ -2632,6 +2663,7 @@ __device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const i
     seed.f.none();
     n_first = nk = cnt = 0;
     D = 0.0;
+    untabled = false;
   }
   // ---- 1. number the paths (as the staged form does)
   const bool seeded = live && seed.road >= 0;
@@ -2679,6 +2711,17 @@ __device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const i
       k0x = r0.x + proj * r0.dirx;
       k0y = r0.y + proj * r0.diry;
       k0h = r0.heading;
+      if (table) {
+        // walk_knots' D: the distance from the projected start to knot 1 (cum[0] below), then the row's terms in order
+        const double ex = kx[0] - k0x, ey = ky[0] - k0y;
+        D = sqrt(ex * ex + ey * ey);
+#pragma unroll
+        for (int k = 2; k <= KD + 1; ++k)
+          if (k <= nk) D += kd[k - 2];
+        const double* const rest = a.knot_table[kid0].d;
+#pragma unroll 4
+        for (int k = KD + 2; k <= nk; ++k) D += rest[k - 2];
+      }
       const int n_emit = n < W ? n : W;
       const double step = D / (double)(n - 1);  // np.linspace(0, D, n)
       const double t_last = (n_emit - 1 == n - 1) ? D : (double)(n_emit - 1) * step;
@@ -2744,9 +2787,16 @@ __device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const i
   SMX_COUNT(54, tm.my_row && tm.listed && nrec > 0 && !tabled_path);
   SMX_COUNT(55, live && p0 == 0 && (flags & SMX_F_FIRST));
   SMX_COUNT(56, live && p0 == 0);
+  // (the knot table: path lanes it could not serve, by reason — the row is not tabled, its filter is another)
+  SMX_COUNT(58, untabled && !(a.knot_table[kid0].flags & SMX_KROW_TABLED));
+  SMX_COUNT(62, untabled && (a.knot_table[kid0].flags & SMX_KROW_TABLED));
   const bool slow_team =  // uniform in the team
-      team_or((live && (tm.serial_team || (tm.my_row && !tabled_path) || (flags & SMX_F_FIRST))) ? 1 : 0) != 0;
+      team_or((live && (tm.serial_team || (tm.my_row && !tabled_path) || untabled || (flags & SMX_F_FIRST))) ? 1 : 0) != 0;
   if (slow_team) tabled_path = false;
+  if (a.knot_served != nullptr) {  // (developer count, uniform branch)
+    const unsigned long long served = __ballot(table && tabled_path);
+    if (threadIdx.x == 0 && served != 0ull) atomicAdd(a.knot_served, (unsigned long long)__popcll(served));
+  }
   wp_book_open(book, v, p0, P, gid, total, live && !slow_team, seeded ? tm.n_paths : 0);
   {
     // the wavefront's slow vehicles, appended with one atomic
@@ -5407,6 +5457,12 @@ struct smx_handle_s {
   void* knots_blob;  // KnotLists of the waypoints sensor (k_wp_walk -> k_waypoints_tables)
   void* spill_blob;  // k_waypoints_emit's overflow area (KernelArgs::wp_spill)
   int wp_pool_limit = SMX_WPE_POOL; // records of k_waypoints_emit's LDS pool in use (smx_debug_set_wp_pool)
+  // the map's knot table (k_knot_table, at smx_load_map: the map and cfg.wp_lookahead are what it depends on), its
+  // counters — [0] rows tabled, [1] rows on one road, then as 64 bits at [2] the path lanes served
+  // (smx_debug_set_knot_table(h, 2)) — and the developer switch
+  KnotRow* knot_table;
+  int32_t* knot_stats;
+  int knot_table_mode = 1;  // 0: the walked lists; 1: the table; 2: the table, counting what it serves
   int32_t* alive_blob;  // [total] alive list + two counters (ticks alternate), large batches
   uint8_t* pending_blob;  // [total] seed_pending
   int32_t* slow_blob;   // [4][total] slow lists of the fast kernels (scan facts, scan seeds, control, waypoint rows) + [2][4] counters (ticks alternate)
@@ -5588,6 +5644,7 @@ static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_sta
                   (SMX_SKIP(*h, SMX_SKIP_FORCE_SCAN_SPLIT) ? SMX_SKIP_FORCE_SCAN_SPLIT : 0);
   in.alive_blob = h->alive_blob != nullptr;
   in.knots_blob = h->knots_blob != nullptr;
+  in.knot_table = h->knot_table != nullptr && h->knot_table_mode != 0;
   in.ctrl_blob = h->ctrl_blob != nullptr;
   in.pending_blob = h->pending_blob;
   in.slow = SlowLists{h->slow_blob, (size_t)h->cfg.num_envs * h->cfg.num_vehicles};
@@ -5688,6 +5745,19 @@ extern "C" int smx_load_map(smx_handle h, const smx_map_tables* t) {
     h->knots.key = (int32_t*)(kb + off_key);
     h->knots.cnt = (uint8_t*)(kb + off_cnt);
     h->knots.nk16 = (uint8_t*)(kb + off_nk16);
+  }
+  if (h->knot_table) {  // (the rows of the map before)
+    (void)hipFree(h->knot_table);
+    h->knot_table = nullptr;
+  }
+  if (h->cfg.sensors & SMX_SENSOR_WAYPOINTS) {
+    if (!h->knot_stats) SMX_HIP(hipMalloc((void**)&h->knot_stats, 4 * sizeof(int32_t)));
+    SMX_HIP(hipMemset(h->knot_stats, 0, 4 * sizeof(int32_t)));
+    SMX_HIP(hipMalloc((void**)&h->knot_table, (size_t)t->n_lanepoints * sizeof(KnotRow)));
+    hipLaunchKernelGGL(k_knot_table, dim3(smx_blocks((size_t)t->n_lanepoints)), dim3(SMX_BLOCK), 0, 0, h->map, (int)h->cfg.wp_lookahead,
+                       h->knot_table, h->knot_stats);
+    SMX_HIP(hipGetLastError());
+    SMX_HIP(hipDeviceSynchronize());
   }
   if ((h->cfg.sensors & SMX_SENSOR_WAYPOINTS) && !h->spill_blob) {
     // a region of (SMX_WPE_KNOTS + 1) knot records + lanes per column of every k_waypoints_emit workgroup: 1.6 KB per
@@ -6175,7 +6245,7 @@ static void observation_pass(smx_handle h, const TickPlan& p, const KernelArgs& 
     case Rows::EMIT:
     case Rows::EMIT_CHAIN_SIDE:
     case Rows::EMIT_CHAIN_AFTER:
-      launch(k_wp_walk, walk_blocks, 0, stream, kw);
+      if (!p.knot_table) launch(k_wp_walk, walk_blocks, 0, stream, kw);  // (the table: k_waypoints_emit reads the rows)
       kw = with_slow(kw, p.rows_slow);
       launch(k_waypoints_emit, p.wp_blocks, 0, stream, kw);
       launch(k_waypoints_listed, p.slow_blocks, 0, stream, kw);
@@ -6289,6 +6359,8 @@ static KernelArgs kernel_args(smx_handle h, const TickPlan& p, const int8_t* act
   a.lateral_gain_pos = h->lateral_gain_pos;
   a.debug_skip = h->debug_skip;
   a.knots = h->knots;
+  a.knot_table = p.knot_table ? h->knot_table : nullptr;
+  a.knot_served = (p.knot_table && h->knot_table_mode == 2) ? (unsigned long long*)(h->knot_stats + 2) : nullptr;
   a.status = h->status_dev;
   a.alive_list = nullptr;
   a.alive_count = nullptr;
@@ -6498,6 +6570,32 @@ extern "C" int smx_debug_set_wp_pool(smx_handle h, int32_t records) {
   return SMX_OK;
 }
 
+// developer / tests: the one-lane cut's knot lists from the map's knot table (1, the default), from the walks of
+// k_wp_walk as before the table (0), or from the table with a count of the path lanes it serves (2)
+extern "C" int smx_debug_set_knot_table(smx_handle h, int32_t mode) {
+  if (!h) return SMX_ERR_INVALID;
+  if (mode < 0 || mode > 2) return fail(h, SMX_ERR_INVALID, "smx_debug_set_knot_table: 0 (walked lists), 1 (table), 2 (table, counting)");
+  h->knot_table_mode = mode;
+  return SMX_OK;
+}
+
+// the loaded map's knot table after a synchronisation of the device: rows in all, rows tabled, tabled rows that stay on
+// their start road, path lanes served from a row while the switch above was 2
+extern "C" int smx_debug_knot_table_stats(smx_handle h, int64_t* out4) {
+  if (!h || !out4) return SMX_ERR_INVALID;
+  if (!h->knot_table) return fail(h, SMX_ERR_STATE, "no knot table (no map loaded, or no waypoints sensor)");
+  SMX_HIP(hipDeviceSynchronize());
+  int32_t st[4];
+  SMX_HIP(hipMemcpy(st, h->knot_stats, sizeof(st), hipMemcpyDeviceToHost));
+  unsigned long long served;
+  std::memcpy(&served, st + 2, sizeof(served));
+  out4[0] = h->map.n_lanepoints;
+  out4[1] = st[0];
+  out4[2] = st[1];
+  out4[3] = (int64_t)served;
+  return SMX_OK;
+}
+
 extern "C" int smx_set_timing(smx_handle h, int level) {
   if (!h) return SMX_ERR_INVALID;
   h->timing = level == 1;
@@ -6558,6 +6656,8 @@ extern "C" void smx_destroy(smx_handle h) {
   if (h->slow_blob) (void)hipFree(h->slow_blob);
   if (h->pending_blob) (void)hipFree(h->pending_blob);
   if (h->spill_blob) (void)hipFree(h->spill_blob);
+  if (h->knot_table) (void)hipFree(h->knot_table);
+  if (h->knot_stats) (void)hipFree(h->knot_stats);
   if (h->ctrl_blob) (void)hipFree(h->ctrl_blob);
   if (h->status_dev) (void)hipFree(h->status_dev);
   if (h->side_ready) {

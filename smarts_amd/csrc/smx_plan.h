@@ -73,6 +73,7 @@ struct PlanInputs {
   bool list_carried;  // the last pass's k_tail built this tick's alive list from these flags
   int debug_skip;     // developer timing switches; 0 in the shipped library
   bool alive_blob, knots_blob, ctrl_blob;
+  bool knot_table;  // the map's knot table is built and switched on
   uint8_t* pending_blob;  // [total] seed_pending, or null
   SlowLists slow;         // (base null: no slow lists)
   int slow_parity;        // the counters this tick's one-lane kernels use
@@ -99,7 +100,8 @@ enum class Seeds : uint8_t { SCAN, ONE_LANE, ROUTED, WIDE, FOUR };
 enum class Facts : uint8_t { SCAN, ONE_LANE, WIDE, FOUR };
 enum class FactsStart : uint8_t { CALLER, WITH_GRIDS, AFTER_SEEDS };  // (side stream 1 unless CALLER)
 // The waypoint rows, and with them the seeds kernel that may feed them: SENSORS the role inside k_sensors (small form);
-// large form: k_wp_walk -> k_waypoints_emit + k_waypoints_listed (EMIT, one-lane cut) or -> k_waypoints_tables (TABLES,
+// large form: k_wp_walk -> k_waypoints_emit + k_waypoints_listed (EMIT, one-lane cut; without k_wp_walk where the knot
+// table serves the tick: TickPlan::knot_table) or -> k_waypoints_tables (TABLES,
 // teams cut) while the rows fit the staged form, else k_waypoints (UNSTAGED), which reads every vehicle's seeds (no
 // seed_pending) and so cannot run beside or ahead of a slow seeds chain.  Only the two *_CHAIN_* values have the one-lane
 // seeds kernel, which leaves the vehicles it cannot serve seed_pending: the walk / emit kernels then pass over those
@@ -155,6 +157,9 @@ struct TickPlan {
   bool tail_builds_list;  // k_tail builds the next tick's alive list
   bool tail_grids;        // ... and the new vehicles' grid tiles
   bool reset_pass, lidar_first, first_walks_new;
+  // the one-lane cut's tick takes its knot lists from the map's knot table: k_waypoints_emit and k_control_fast read
+  // rows, k_wp_walk is not launched, and k_first walks no list for the new vehicles (first_walks_new is then false)
+  bool knot_table;
   unsigned veh_blocks, wp_blocks, obs_blocks, env_blocks, lidar_blocks, seeds_blocks, facts_blocks, slow_blocks, sensor_blocks;
   size_t ogm_bytes, dagm_bytes, ogm_lds, sensor_lds;
   uint8_t* pending;  // seed_pending of the one-lane seeds kernel, its chain and the walk / emit kernels; else null
@@ -289,7 +294,13 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
   p.lidar_first = p.reset_pass && lidar && !small;
   // large batches: k_first also walks the new vehicles' knot lists, for the next tick's k_control_fast
   // (only k_control_fast reads them: not on the maps that keep the team kernels)
-  p.first_walks_new = p.reset_pass && !small && one_lane_cut && staged;
+  // The table serves the lookaheads the controller's reuse is defined for (k_control_fast sends every vehicle to its slow
+  // list below that, with or without it), and batches without fixed routes: a route's filter names an agent slot, which
+  // no row is walked for, so with routes set the tick keeps the walked lists and every launch it had.
+  const bool table = in.knot_table && !in.routed && staged && c.wp_lookahead >= 16;
+  p.knot_table = table && one_lane;
+  // (the reset pass of a tick whose form is the one-lane cut: the next tick's k_control_fast reads rows, not lists)
+  p.first_walks_new = p.reset_pass && !small && one_lane_cut && staged && !(table && p.form == SMX_FORM_LARGE_ONE_LANE);
 
   const int vpb = SMX_BLOCK / SMX_WP_LANES, epb = SMX_BLOCK / c.num_vehicles;
   p.veh_blocks = smx_blocks(total);

@@ -829,11 +829,12 @@ struct PathWalk {
   double D;   // arclength over all knots
 };
 
-// Pass 1 of equally_spaced_path: sink(k, lanepoint index, hops from the start) is called for every knot
-// k = 1..nk in path order.
+// Pass 1 of equally_spaced_path: sink(k, lanepoint index, hops from the start, term) is called for every knot
+// k = 1..nk in path order; `term` is what the knot added to D (the distance from the knot before it; for k = 1 from
+// the projected query point).
 template <class Sink>
-__device__ inline PathWalk walk_knots(const MapDev& m, const RouteFilter& f, BranchState& bs, int start, int lookahead,
-                                      double px, double py, Sink&& sink) {
+__device__ inline PathWalk walk_knots_terms(const MapDev& m, const RouteFilter& f, BranchState& bs, int start, int lookahead,
+                                            double px, double py, Sink&& sink) {
   KnotWalk w;
   w.begin(m, start, lookahead);
   const smx_lp_rec r0 = w.cur;
@@ -849,12 +850,78 @@ __device__ inline PathWalk walk_knots(const MapDev& m, const RouteFilter& f, Bra
     if (idx < 0) break;
     ++out.nk;
     const double ex = rec.x - lastx, ey = rec.y - lasty;
-    out.D += sqrt(ex * ex + ey * ey);
+    const double term = sqrt(ex * ex + ey * ey);
+    out.D += term;
     lastx = rec.x;
     lasty = rec.y;
-    sink(out.nk, idx, w.n - 1);
+    sink(out.nk, idx, w.n - 1, term);
   }
   out.n = w.n;
+  return out;
+}
+
+// ... sink(k, lanepoint index, hops from the start)
+template <class Sink>
+__device__ inline PathWalk walk_knots(const MapDev& m, const RouteFilter& f, BranchState& bs, int start, int lookahead,
+                                      double px, double py, Sink&& sink) {
+  return walk_knots_terms(m, f, bs, start, lookahead, px, py, [&](int k, int idx, int hop, double) { sink(k, idx, hop); });
+}
+
+// What the chain walk of one seed lane leaves for the kernels behind it (KnotLists, KnotRow): the first path's knots
+// through put(k, lanepoint index, term) for k = 1 .. SMX_WPK_CAP, and the head below.  `ctrl_wps`: waypoints of the
+// controller's path (SMX_CTRL_WPS; its lookahead is ctrl_wps - 1 hops).
+struct KnotListHead {
+  int n, nk, cnt;  // lanepoints and knots of the first path; paths that start on this seed lane
+  int nk16, end16; // the controller's path: see KnotLists
+  double D;
+};
+template <class Put>
+__device__ inline KnotListHead walk_knot_list(const MapDev& m, const RouteFilter& f, int start, int lookahead, int ctrl_wps,
+                                              double px, double py, Put&& put) {
+  BranchState bs;
+  bs.reset();
+  int below16 = 0;        // knots less than 16 hops down
+  bool knot_at_16 = false;
+  int base_idx = start, base_hop = 0;  // the last lanepoint of the list less than 16 hops down (the start if no knot is)
+  const PathWalk w = walk_knots_terms(m, f, bs, start, lookahead, px, py, [&](int k, int idx, int hop, double term) {
+    if (k <= SMX_WPK_CAP) put(k, idx, term);
+    if (hop < ctrl_wps - 1) {
+      ++below16;
+      base_idx = idx;
+      base_hop = hop;
+    }
+    if (hop == ctrl_wps - 1) knot_at_16 = true;
+  });
+  KnotListHead out;
+  out.n = w.n;
+  out.nk = w.nk;
+  out.D = w.D;
+  // the lookahead-16 path: the whole path when it is no longer than that, else the knots less than 16
+  // hops down and the lanepoint 16 hops down (a knot of the list, or the probed interpolated lanepoint)
+  out.nk16 = w.n <= ctrl_wps ? w.nk : below16 + 1;
+  // (an interpolated lanepoint of the run that leaves the last knot before it: followed here, after the walk,
+  // from that knot's record — the successor the route filter allows where the knot branches; the list is only
+  // reused when exactly one path starts on this seed lane, so there is exactly one)
+  int end16 = -1;
+  if (w.n > ctrl_wps && !knot_at_16) {
+    const smx_lp_rec br = load_lp(m, base_idx, 47);
+    int first = br.next0;
+    if (br.n_next > 1) {
+      first = -1;
+      for (int k = br.next_off; k < br.next_off + br.n_next && first < 0; ++k) {
+        const smx_succ_rec sr = m.succ_rec[k];
+        if (lane_allowed(m, f, sr.lane)) first = sr.idx;
+      }
+    }
+    if (first >= 0) end16 = chain_at(m, first, ctrl_wps - 1 - base_hop - 1, (br.flags & 1) != 0);
+  }
+  out.end16 = end16;
+  int cnt = 1;
+  while (bs.advance()) {
+    walk_knots(m, f, bs, start, lookahead, px, py, [](int, int, int) {});
+    if (cnt < 255) ++cnt;
+  }
+  out.cnt = cnt;
   return out;
 }
 
@@ -915,6 +982,21 @@ __device__ inline int closest_on_route(const MapDev& m, const RouteFilter& f, do
   return b.idx == 0x7fffffff ? -1 : b.idx;
 }
 
+// _resolve_in_junction (sumo_road_network.py:842-860): the filter of an agent whose closest lanepoint lies on junction
+// road `road` — that road and the road it leads to
+__device__ __forceinline__ RouteFilter junction_filter(const MapDev& m, int road) {
+  RouteFilter f;
+  f.n = 1;
+  f.road[0] = road;
+  f.road[1] = -1;
+  const int nr = m.road_out_road[road];
+  if (nr >= 0) {
+    f.n = 2;
+    f.road[1] = nr;
+  }
+  return f;
+}
+
 // has_route_object: the agent carries a (possibly empty) Route — the controller and the
 // waypoints sensor do; TripMeterSensor's constructor query does not.  `ms`, `slot`: the missions
 // table and the agent's slot (a fixed route replaces the in-junction rule: sumo_road_network.py:822-829).
@@ -940,13 +1022,7 @@ __device__ inline PathSeeds compute_path_seeds(const MapDev& m, double px, doubl
     if (lp >= 0) {
       int road = m.lane_road[SMX_BCHK(19, m.lp_rec[lp].lane, m.n_lanes)];
       if (m.road_is_junction[SMX_BCHK(20, road, m.n_roads)]) {
-        s.f.n = 1;
-        s.f.road[0] = road;
-        int nr = m.road_out_road[road];
-        if (nr >= 0) {
-          s.f.n = 2;
-          s.f.road[1] = nr;
-        }
+        s.f = junction_filter(m, road);
         // _waypoint_paths_along_route (:862-882): nearest lanepoint over the route roads; the
         // reference compares np.linalg.norm distances, first minimum wins
         int idx4[4];
@@ -993,4 +1069,72 @@ __device__ __forceinline__ int seed_start(const MapDev& m, const PathSeeds& s, i
   int idx[4];
   closest_filtered4(m, px, py, key, 1, false, idx, nullptr);
   return idx[0];
+}
+
+// ---------------------------------------------------------------------------------
+// Knot table: the knot list of every lanepoint of the map, walked once.
+// ---------------------------------------------------------------------------------
+// A knot list is a function of (map, lookahead, start lanepoint, route filter) alone but for D, which the query point
+// enters through its first term only (the distance from the projected start to knot 1; every later term joins two
+// lanepoints).  So a row per lanepoint, walked with the lanepoint's natural filter — none off the junction roads,
+// junction_filter on them — serves every vehicle that starts there with that filter: the one-lane cut's
+// k_waypoints_emit and k_control_fast read rows instead of lists, and no kernel walks in between.
+// One 256-byte row per lanepoint (a path lane reads its whole row; the rows of a wavefront are scattered).
+#define SMX_KROW_TABLED 1       // the walk met no branching, n > 0, nk <= SMX_WPK_CAP
+#define SMX_KROW_SINGLE_ROAD 2  // every lane the walk touched lies on the start lanepoint's road
+struct alignas(256) KnotRow {
+  int32_t idx[SMX_WPK_CAP];    // knots 1 .. SMX_WPK_CAP
+  double d[SMX_WPK_CAP - 1];   // d[k - 2]: distance from knot k - 1 to knot k, k = 2 .. SMX_WPK_CAP (walk_knots' terms)
+  int16_t n, nk;               // lanepoints on the path, knots after the start
+  uint8_t nk16, flags;
+  int16_t pad;
+  int32_t end16;
+  int32_t f0, f1;              // the filter the row was walked with (-1: none)
+  int32_t road;                // the start lanepoint's road
+};
+static_assert(sizeof(KnotRow) == 256, "KnotRow is one 256-byte row");
+
+// the filter row `lp` is walked with
+__device__ __forceinline__ RouteFilter knot_row_filter(const MapDev& m, int lp) {
+  const int road = m.lane_road[m.lp_rec[lp].lane];
+  RouteFilter f;
+  f.none();
+  if (m.road_is_junction[road]) f = junction_filter(m, road);
+  return f;
+}
+
+// the row of lanepoint `lp` (one lane of the one-off kernel; the host tests call it as it is)
+__device__ inline void build_knot_row(const MapDev& m, int lp, int lookahead, int ctrl_wps, KnotRow& row) {
+  const smx_lp_rec r0 = m.lp_rec[lp];
+  const RouteFilter f = knot_row_filter(m, lp);
+  const int road = m.lane_road[r0.lane];
+  for (int k = 0; k < SMX_WPK_CAP; ++k) row.idx[k] = lp;  // (entries past nk: a valid index, never a knot)
+  for (int k = 0; k < SMX_WPK_CAP - 1; ++k) row.d[k] = 0.0;
+  bool single = true;
+  const KnotListHead hd = walk_knot_list(m, f, lp, lookahead, ctrl_wps, r0.x, r0.y, [&](int k, int idx, double term) {
+    row.idx[k - 1] = idx;
+    if (k >= 2) row.d[k - 2] = term;
+    single = single && m.lane_road[m.lp_rec[idx].lane] == road;
+  });
+  const bool tabled = hd.cnt == 1 && hd.n > 0 && hd.nk <= SMX_WPK_CAP;
+  row.n = (int16_t)hd.n;
+  row.nk = (int16_t)hd.nk;
+  row.nk16 = (uint8_t)hd.nk16;
+  row.flags = (uint8_t)((tabled ? SMX_KROW_TABLED : 0) | (tabled && single ? SMX_KROW_SINGLE_ROAD : 0));
+  row.pad = 0;
+  row.end16 = hd.end16;
+  row.f0 = f.n > 0 ? f.road[0] : -1;
+  row.f1 = f.n > 1 ? f.road[1] : -1;
+  row.road = road;
+}
+
+// May a vehicle whose walk would start on the row's lanepoint with filter `f` take the row for its knot list?
+//  1. the row was walked with this very filter (knot_list_reusable's key, the start implicit);
+//  2. the row was walked without a filter, touched its start road only, and `f` is a junction filter whose last road is
+//     that road: lane_allowed(f, lane) holds for every lane of the filter's last road, and a walk without a branching
+//     asks it of the lanes it touches only, so the filtered walk is the unfiltered one.
+__device__ __forceinline__ bool knot_row_serves(int flags, int f0, int f1, int road, const RouteFilter& f) {
+  if (!(flags & SMX_KROW_TABLED) || f.n == SMX_ROUTE_FIXED) return false;
+  if (f0 == (f.n > 0 ? f.road[0] : -1) && f1 == (f.n > 1 ? f.road[1] : -1)) return true;
+  return f0 < 0 && (flags & SMX_KROW_SINGLE_ROAD) && f.n > 0 && f.last() == road;
 }
