@@ -630,6 +630,44 @@ enum { SMX_GUARD_STEP = 1 << 0,   /* this tick's step produced an out-of-bounds 
 #define SMX_GUARD_MARGIN_MAX 1.0e6
 int smx_set_guard(smx_handle h, uint8_t* guard_dev, uint64_t count, double margin);   /* [E*N]; NULL = guard off */
 int smx_check_guard(const smx_config* cfg, uint64_t count, double margin, char* err, uint64_t err_len);
+/* Traffic-history replay (TrafficHistoryProvider, smarts/core/traffic_history_provider.py:94-170 over
+ * traffic_history.py): while a history is bound, the social slots (the last cfg.num_social of every env) take pose,
+ * speed and presence from a recorded table instead of the scripted lane follower; without one nothing changes.
+ *   frames_host[n_frames][num_social][4]  x, y, heading, speed of the vehicle CENTRE, heading in the reference's
+ *                                         convention and already wrapped as Heading.__new__ wraps it: the device copies
+ *                                         the four words bit for bit into SMX_S_X / _Y / _HEADING / _U
+ *   vehicle_host[n_frames][num_social]    the history's vehicle id in that slot and frame, < 0 = the slot is empty
+ * Host pointers; the handle keeps a device copy (dropped by smx_load_map: the rows were checked against that map).  The
+ * two device tables stay the caller's and are read in every pass, so rewriting them in place takes effect with the next
+ * tick; any value in them is safe.
+ *   frame  = (int64) start_frame[episode mod rows][env] + env_ticks, env_ticks the tick count the pass's observation
+ *            reports (cfg.reset_elapsed_steps at a reset observation); outside [0, n_frames) every slot is empty
+ *   present = vehicle[frame][slot] >= 0 and != replaced[episode mod rows][env]   (replaced_dev NULL: nothing hidden)
+ * A present slot is an alive social vehicle at the frame's row: seen by every sensor and collision test, with the
+ * sedan's box.  SMX_S_PREV_X / _Y behave as for the scripted vehicle, SMX_S_MCL_X / _Y / SMX_S_SPD_INT stay 0;
+ * spawns.social and the slot's spawns.pose rows are not read (the entry check still wants the buffer).  An absent slot
+ * is not alive; it never counts in env_done_count or env_done.  SMX_F_ALIVE of a social slot is decided at the end of
+ * the pass before (from the tables as they were then): after an in-place rewrite a vehicle that the new frame lacks
+ * leaves at once, one that it adds enters a tick late.
+ * Refused (SMX_ERR_INVALID, the reason in smx_last_error): num_social different from the configuration's or 0;
+ * n_frames < 1 or sizes that overflow; cfg.social_model == SMX_SOCIAL_IDM (the replay replaces the speed model);
+ * start_count / replaced_count below rows * num_envs; rows < 1; a row of a non-empty slot that is not finite or lies
+ * outside the union of the map's two grids (smx_set_guard's box with margin 0: the state guard does not cover social
+ * slots, this check does).  Needs the map (SMX_ERR_STATE before smx_load_map).  hist = NULL unbinds.  Waits for the
+ * device.  smx_check_social_history is the validation alone, callable without a device or a handle (`map`: only the
+ * grid extents lpg_* / sg_* are read). */
+typedef struct smx_social_history {
+  const double* frames_host;   /* [n_frames][num_social][4] */
+  const int32_t* vehicle_host; /* [n_frames][num_social], < 0 = empty */
+  int32_t n_frames, num_social;
+  const int32_t* start_frame_dev; /* device, caller-owned, [rows][num_envs]; read every tick */
+  const int32_t* replaced_dev;    /* device, caller-owned, [rows][num_envs] vehicle id hidden in that env; -1 none; may be NULL */
+  int32_t rows;
+  uint64_t start_count, replaced_count; /* int32 elements the caller allocated for each */
+} smx_social_history;
+int smx_set_social_history(smx_handle h, const smx_social_history* hist);
+int smx_check_social_history(const smx_config* cfg, const smx_map_tables* map, const smx_social_history* hist, char* err,
+                             uint64_t err_len);
 /* Frame stacking (smx_config.frame_stack = k): for every agent the device keeps the last k frames of each bound row,
  * newest first (frame 0 is this pass's row), in a caller-owned device buffer.  At the end of every smx_reset / smx_step*
  * pass, on the caller's stream, once every row of the pass is complete (under auto_reset: after the reset pass has

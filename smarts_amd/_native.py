@@ -126,6 +126,12 @@ class SmxMissionGoal(C.Structure):
     _fields_ = [("kind", _i32), ("num_laps", _i32), ("route_length", _f64)]
 
 
+class SmxSocialHistory(C.Structure):  # smx_social_history (smx_set_social_history)
+    _fields_ = [("frames_host", _p), ("vehicle_host", _p), ("n_frames", _i32), ("num_social", _i32),
+                ("start_frame_dev", _p), ("replaced_dev", _p), ("rows", _i32), ("start_count", C.c_uint64),
+                ("replaced_count", C.c_uint64)]
+
+
 class SmxSpawns(C.Structure):
     _fields_ = [("episodes", _i32), ("pose", _p), ("social", _p), ("pose_count", C.c_uint64), ("social_count", C.c_uint64)]
 
@@ -187,6 +193,7 @@ EXPORTS = [
     "smx_check_buffers", "smx_set_launch_strategy", "smx_launch_form", "smx_step_target_pose", "smx_step_trajectory_with_time",
     "smx_set_mission_goals", "smx_check_mission_goals", "smx_actions_to_world", "smx_set_rgb_output", "smx_check_rgb_output",
     "smx_bind_frame_stack", "smx_check_frame_stack", "smx_set_guard", "smx_check_guard",
+    "smx_set_social_history", "smx_check_social_history",
 ]
 LAUNCH_FORMS = {0: "small", 1: "large_teams", 2: "large_one_lane"}
 LAUNCH_STRATEGIES = {"auto": 0, "small": 1, "large": 2, "large_one_lane": 3, "large_teams": 4}
@@ -270,6 +277,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.smx_set_guard.restype = C.c_int
     lib.smx_check_guard.argtypes = [C.POINTER(SmxConfig), C.c_uint64, _f64, C.c_char_p, C.c_uint64]
     lib.smx_check_guard.restype = C.c_int
+    lib.smx_set_social_history.argtypes = [h, C.POINTER(SmxSocialHistory)]
+    lib.smx_set_social_history.restype = C.c_int
+    lib.smx_check_social_history.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxMapTables), C.POINTER(SmxSocialHistory),
+                                             C.c_char_p, C.c_uint64]
+    lib.smx_check_social_history.restype = C.c_int
     lib.smx_read_phase_ms.argtypes = [h, C.POINTER(C.c_float), _i32, C.POINTER(_i32)]
     lib.smx_read_phase_ms.restype = C.c_int
     lib.smx_set_timing.argtypes = [h, C.c_int]

@@ -1,0 +1,56 @@
+// smx_history.h — traffic-history replay (include/smx.h, smx_set_social_history): which frame of the recorded table an
+// env replays in a pass, whether a social slot holds a vehicle there, and the row it takes its pose from, each written
+// once.  social_vehicle_step (every control form), respawn_vehicle (k_reset and the commit-time respawn) and commit_role
+// call these; the header holds no HIP and also compiles for the host (tests/native/host_history.cpp drives it under
+// AddressSanitizer + UBSan).
+//
+// Nothing read from the two caller-owned tables can take an index out of a table: the row of start_frame / replaced is
+// (episode mod rows) brought into [0, rows), the env is the kernel's own, the frame is formed in 64 bits (an int32 start
+// plus an int32 tick count cannot overflow them) and compared against [0, n_frames) before it indexes anything, and a
+// replaced id is only ever compared.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/smx.h"
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define SMX_HISTORY_FN __host__ __device__ __forceinline__
+#else
+#define SMX_HISTORY_FN inline
+#endif
+
+// The bound history as the kernels see it (vehicle == null: none bound).  frames / vehicle: the handle's device copy of
+// smx_social_history's host tables; start_frame / replaced: the caller's device tables.
+struct HistoryDev {
+  const double* frames;        // [n_frames][num_social][4] x, y, heading, speed
+  const int32_t* vehicle;      // [n_frames][num_social], < 0 = empty
+  const int32_t* start_frame;  // [rows][num_envs]
+  const int32_t* replaced;     // [rows][num_envs], or null
+  int32_t n_frames, num_social, rows, num_envs;
+};
+
+// the row of the two per-env tables that episode `episode` reads (Python's modulo: a negative episode counts from the end)
+SMX_HISTORY_FN int history_table_row(const HistoryDev& h, int episode) {
+  const int r = episode % h.rows;
+  return r < 0 ? r + h.rows : r;
+}
+
+// The frame env `env` replays when its observation reports `env_ticks` ticks.
+SMX_HISTORY_FN int64_t history_frame(const HistoryDev& h, int episode, int env, int env_ticks) {
+  const size_t at = (size_t)history_table_row(h, episode) * (size_t)h.num_envs + (size_t)env;
+  return (int64_t)h.start_frame[at] + (int64_t)env_ticks;
+}
+
+// Does social slot `slot` (0 .. num_social - 1) of env `env` hold a vehicle in `frame`?
+SMX_HISTORY_FN bool history_present(const HistoryDev& h, int episode, int env, int64_t frame, int slot) {
+  if (frame < 0 || frame >= (int64_t)h.n_frames) return false;
+  const int32_t id = h.vehicle[(size_t)frame * (size_t)h.num_social + (size_t)slot];
+  if (id < 0) return false;
+  if (h.replaced == nullptr) return true;
+  return id != h.replaced[(size_t)history_table_row(h, episode) * (size_t)h.num_envs + (size_t)env];
+}
+
+// The four words of a present slot (only called when history_present said yes: the frame is in range).
+SMX_HISTORY_FN const double* history_row(const HistoryDev& h, int64_t frame, int slot) {
+  return h.frames + ((size_t)frame * (size_t)h.num_social + (size_t)slot) * 4;
+}

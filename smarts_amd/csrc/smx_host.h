@@ -341,6 +341,44 @@ inline int check_guard_impl(const smx_config& c, uint64_t count, double margin, 
   return SMX_OK;
 }
 
+// ---- Traffic-history replay (smx_set_social_history / smx_check_social_history) ----
+// The kernels copy a present slot's row into the state without a test, and the map searches then form cell indices from
+// it: every row of a non-empty slot is checked here, once, against the union of the map's two grids (the state guard's
+// box with margin 0; the guard itself does not cover social slots).  Rows of empty slots are never read by a kernel and
+// may hold anything.  `map`: only its grid extents are read.
+inline int check_social_history_impl(const smx_config& c, const smx_map_tables& map, const smx_social_history& hs, std::string& err) {
+  if (c.num_envs <= 0 || c.num_vehicles <= 0) return refuse(err, "social history: num_envs and num_vehicles must be > 0");
+  if (c.num_social <= 0) return refuse(err, "social history: the configuration has no social slots (num_social is 0)");
+  if (hs.num_social != c.num_social)
+    return refuse(err, "social history: the table has " + std::to_string(hs.num_social) + " slots, the configuration's num_social is " +
+                           std::to_string(c.num_social));
+  if (c.social_model == SMX_SOCIAL_IDM)
+    return refuse(err, "social history: social_model is SMX_SOCIAL_IDM (the replay replaces the speed model; use SMX_SOCIAL_CONSTANT)");
+  if (hs.n_frames < 1) return refuse(err, "social history: n_frames must be >= 1");
+  if (hs.rows < 1) return refuse(err, "social history: rows must be >= 1");
+  const uint64_t cells = (uint64_t)hs.n_frames * (uint64_t)hs.num_social;
+  if (cells > 0x7fffffffull) return refuse(err, "social history: n_frames * num_social must stay below 2^31");
+  if (!hs.frames_host || !hs.vehicle_host) return refuse(err, "social history: null table (frames_host / vehicle_host)");
+  if (!hs.start_frame_dev) return refuse(err, "social history: start_frame_dev is NULL");
+  const uint64_t need = (uint64_t)hs.rows * (uint64_t)c.num_envs;
+  if (hs.start_count < need)
+    return refuse(err, "social history: start_frame " + std::to_string(hs.start_count) + " elements declared, rows * num_envs is " +
+                           std::to_string(need) + " (a short table would be an out-of-bounds device read)");
+  if (hs.replaced_dev && hs.replaced_count < need)
+    return refuse(err, "social history: replaced " + std::to_string(hs.replaced_count) + " elements declared, rows * num_envs is " +
+                           std::to_string(need) + " (a short table would be an out-of-bounds device read)");
+  const GuardBox box = guard_box_of(map, 0.0);
+  for (uint64_t i = 0; i < cells; ++i) {
+    if (hs.vehicle_host[i] < 0) continue;
+    const double* r = hs.frames_host + i * 4;
+    if (!guard_in_bounds_kin(box, r[0], r[1], r[2], r[3]))
+      return refuse(err, "social history: frame " + std::to_string(i / (uint64_t)hs.num_social) + ", slot " +
+                             std::to_string(i % (uint64_t)hs.num_social) + " (vehicle " + std::to_string(hs.vehicle_host[i]) +
+                             ") is not finite or lies outside the map's grids");
+  }
+  return SMX_OK;
+}
+
 // ---- Frame stacking (smx_bind_frame_stack / smx_check_frame_stack) ----
 // bytes per agent of a stackable source, 0 with the reason in `err`: a row of smx_outputs by its SMX_OUT_* index — stackable,
 // its sensor on, its elements times the size of its dtype — or the image by SMX_STACK_SOURCE_RGB

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "smx_guard.h"
+#include "smx_history.h"
 #include "smx_host.h"
 #include "smx_plan.h"
 #include "smx_scan.h"
@@ -98,6 +99,9 @@ struct KernelArgs {
   // the GUARD instantiations of the control, reset and tail kernels only (null: the plan launches the others).
   uint8_t* guard;
   GuardBox guard_box;
+  // traffic-history replay (smx_set_social_history; smx_history.h): history.vehicle null = none bound, the social slots are
+  // the scripted lane followers.  Every branch on it is marked as the rare side.
+  HistoryDev history;
 };
 enum {
   SMX_DEVICE_BAD_LANE_ACTION = 1,  // a Lane action code outside -1..3 was met (and treated as "no action")
@@ -282,11 +286,46 @@ __device__ __forceinline__ VehState load_vehicle(const KernelArgs& a, size_t gid
 // ---- the steps every launch form of the controller shares (k_control, k_control_paths / k_control_law,
 // k_control_fast / k_control_listed, k_control_kinematic), each written once
 
+// ---- traffic-history replay (smx_set_social_history; smx_history.h holds the frame arithmetic and the presence rule).
+// The three callers are on the rare side of a branch on the bound pointer.  Inlined on purpose: out of line, with the
+// argument block by reference, the compiler spills the whole block to scratch in every kernel that holds a call
+// (profiles/r16_traffic_history_resources.txt).
+// Is social slot `slot` of `env` present when the env's observation reports `env_ticks` ticks, and in which frame.
+__device__ __forceinline__ bool history_slot_present(const KernelArgs& a, int env, int slot, int episode, int env_ticks, int64_t& frame) {
+  frame = history_frame(a.history, episode, env, env_ticks);
+  return history_present(a.history, episode, env, frame, slot);
+}
+// The replayed vehicle's step, in the scripted step's place in the tick (before collisions and sensors): the pose and
+// speed of the frame this tick's observation belongs to — env_ticks + 1, smarts.py:261-262 —, copied word for word.
+// SMX_S_PREV_X / _Y as for the scripted vehicle.  The slot is alive because the last commit found it in this frame; if
+// the caller has rewritten its tables since and the frame lacks it now, it leaves here, ahead of every sensor.
+__device__ __forceinline__ void history_vehicle_step(const KernelArgs& a, size_t gid, size_t total, double prev_x, double prev_y) {
+  const int n_veh = a.cfg.num_vehicles;
+  const int env = (int)(gid / (size_t)n_veh);
+  const int slot = (int)(gid - (size_t)env * n_veh) - (n_veh - a.cfg.num_social);
+  int64_t frame;
+  if (!history_slot_present(a, env, slot, a.st.env_episode[env], a.st.env_ticks[env] + 1, frame)) {
+    a.st.flags[gid] = a.st.flags[gid] & ~SMX_F_ALIVE;
+    return;
+  }
+  const double* row = history_row(a.history, frame, slot);
+  SF(SMX_S_PREV_X) = prev_x;
+  SF(SMX_S_PREV_Y) = prev_y;
+  SF(SMX_S_X) = row[0];
+  SF(SMX_S_Y) = row[1];
+  SF(SMX_S_HEADING) = row[2];
+  SF(SMX_S_U) = row[3];
+}
+
 // Scripted social vehicle (lane follower: no controller, no dynamics), on state words its caller has loaded:
 // lane, offset and crossed flag (SMX_S_MCL_X / MCL_Y / SPD_INT), SMX_S_THROTTLE and the pose's x / y.
 __device__ __forceinline__ void social_vehicle_step(const KernelArgs& a, size_t gid, size_t total, double mcl_x, double mcl_y,
                                                     double spd_int, double throttle, double prev_x, double prev_y) {
   const smx_config& c = a.cfg;
+  if (__builtin_expect(a.history.vehicle != nullptr, 0)) {
+    history_vehicle_step(a, gid, total, prev_x, prev_y);
+    return;
+  }
   int lane = (int)mcl_x, crossed = (int)spd_int;
   double offset = mcl_y, speed, x, y, heading;
   SF(SMX_S_PREV_X) = prev_x;
@@ -3112,6 +3151,31 @@ __device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const i
 // (SMARTS.reset / TrapManager, smarts.py:365-460, trap_manager.py:212-230).
 // (GUARD: an agent's spawn row that is out of bounds — smx_guard.h — creates the vehicle parked at lanepoint 0 at rest,
 // flagged SMX_F_GUARDED, its byte SMX_GUARD_SPAWN; a social slot's pose comes from the library's own tables)
+// A replayed social slot of a freshly reset env (smx_set_social_history): its first pose and SMX_F_ALIVE come from the
+// frame of the reset observation, cfg.reset_elapsed_steps ticks into `episode`'s window; every other state word is 0.
+// Returns the flags word.  An empty slot is not alive; it carries SMX_F_FIRST all the same, so that the reset pass's
+// observe role makes its rows an absent agent's (every other reader of SMX_F_FIRST asks for SMX_F_ALIVE first).
+__device__ __forceinline__ int history_respawn(const KernelArgs& a, size_t gid, size_t total, int episode) {
+  const int n_veh = a.cfg.num_vehicles;
+  const int env = (int)(gid / (size_t)n_veh);
+  const int slot = (int)(gid - (size_t)env * n_veh) - (n_veh - a.cfg.num_social);
+  int64_t frame;
+  const bool present = history_slot_present(a, env, slot, episode, a.cfg.reset_elapsed_steps, frame);
+  double x = 0.0, y = 0.0, heading = 0.0, speed = 0.0;
+  if (present) {
+    const double* row = history_row(a.history, frame, slot);
+    x = row[0], y = row[1], heading = row[2], speed = row[3];
+  }
+  SF(SMX_S_X) = x;
+  SF(SMX_S_Y) = y;
+  SF(SMX_S_HEADING) = heading;
+  SF(SMX_S_U) = speed;
+  SF(SMX_S_KIN_RAW_HEADING) = 0.0;
+  SF(SMX_S_PREV_X) = x;
+  SF(SMX_S_PREV_Y) = y;
+  return SMX_F_SOCIAL | SMX_F_FIRST | (present ? SMX_F_ALIVE : 0);
+}
+
 template <bool GUARD>
 __device__ __forceinline__ void respawn_vehicle(const KernelArgs& a, size_t gid, size_t total, int episode) {
   const int row = a.sp.episodes > 0 ? (((episode % a.sp.episodes) + a.sp.episodes) % a.sp.episodes) : 0;
@@ -3146,10 +3210,14 @@ __device__ __forceinline__ void respawn_vehicle(const KernelArgs& a, size_t gid,
     SF(SMX_S_PREV_Y) = sp[1];
   }
   if ((int)(gid % n_veh) >= n_veh - a.cfg.num_social) {
-    const double* so = a.sp.social + ((size_t)row * total + gid) * 2;
-    SF(SMX_S_MCL_X) = so[0];  // lane
-    SF(SMX_S_MCL_Y) = so[1];  // arclength offset
-    fl |= SMX_F_SOCIAL;
+    if (__builtin_expect(a.history.vehicle != nullptr, 0)) {
+      fl = history_respawn(a, gid, total, episode);  // (the spawn rows written above are overwritten or unused: not alive)
+    } else {
+      const double* so = a.sp.social + ((size_t)row * total + gid) * 2;
+      SF(SMX_S_MCL_X) = so[0];  // lane
+      SF(SMX_S_MCL_Y) = so[1];  // arclength offset
+      fl |= SMX_F_SOCIAL;
+    }
   }
   a.st.flags[gid] = fl;
   // the slot's knot lists belong to the vehicle that is gone (k_wp_walk only visits alive vehicles)
@@ -3364,8 +3432,9 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
   const bool mine = valid && alive && !social && (!a.first_only || first);
   bool done = false;
   int new_flags = flags;  // what the commit kernel makes the vehicle's flags word after this pass
-  if (valid && alive && social && first) {
-    // nothing to observe: its rows read as an absent agent's
+  if (valid && social && first) {
+    // nothing to observe: its rows read as an absent agent's (a scripted vehicle is alive here; a replayed slot that is
+    // empty in the reset observation's frame carries SMX_F_FIRST without SMX_F_ALIVE for the same treatment)
     atomicOr(&zero_mask, 1ull << local);
     o.active[gid] = 0;
     o.done[gid] = 0;
@@ -3779,6 +3848,24 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
 // (GUARD, the tick's commit only: an agent that carries SMX_F_GUARDED ends with this tick's observation — done = 1, not
 // active, its vehicle gone —, applied here as lap_goal_gate applies its correction: the observe role is the kernel
 // without a guard; and the byte of every slot without an agent in the tick reads 0)
+// A replayed social slot at the end of a pass (smx_set_social_history): SMX_F_ALIVE for the next tick is the slot's
+// presence in the next tick's frame — the env's tick count after this pass (the tick's commit has not incremented it
+// yet) plus one.  The same rule in the tick's commit and in the reset pass's, whose env groups also hold envs that were
+// not reset: for those it finds what the tick's commit found.  An env that restarts is respawned after this, from its
+// next episode's window.
+// A vehicle that appears may be anywhere on the map, far from where the slot's last occupant left: its road facts must
+// not be searched for from that occupant's carry.  The appearing vehicle's carry is invalidated (SMX_FI_LANE = -1 is "no
+// usable carry" to both scan forms: scan_role starts from scratch, k_scan_fast hands the vehicle to its slow list); the
+// path seeds are never asked of a social slot.
+__device__ __forceinline__ int history_commit(const KernelArgs& a, size_t gid, size_t total, int env, int slot_in_env, int old_flags,
+                                           int new_flags, bool tick) {
+  const int slot = slot_in_env - (a.cfg.num_vehicles - a.cfg.num_social);
+  int64_t frame;
+  const bool present = history_slot_present(a, env, slot, a.st.env_episode[env], a.st.env_ticks[env] + (tick ? 2 : 1), frame);
+  if (present && !(old_flags & SMX_F_ALIVE)) a.st.facts_i32[(size_t)SMX_FI_LANE * total + gid] = -1;
+  return present ? (new_flags | SMX_F_ALIVE) : (new_flags & ~SMX_F_ALIVE);
+}
+
 template <bool GUARD>
 __device__ __forceinline__ void commit_role(const KernelArgs& a, const int block, const bool tick) {
   __shared__ int env_new_done[SMX_BLOCK];
@@ -3821,8 +3908,11 @@ __device__ __forceinline__ void commit_role(const KernelArgs& a, const int block
         }
       }
     }
+    if (__builtin_expect(a.history.vehicle != nullptr, 0) && (old_flags & SMX_F_SOCIAL))
+      new_flags = history_commit(a, gid, total, env, slot, old_flags, new_flags, tick);
     a.st.flags[gid] = new_flags;
-    if ((old_flags & SMX_F_ALIVE) && !(new_flags & SMX_F_ALIVE)) atomicAdd(&env_new_done[env_local], 1);
+    // (agents only: a replayed social vehicle that leaves its history is not a finished agent; a scripted one never ends)
+    if ((old_flags & SMX_F_ALIVE) && !(new_flags & SMX_F_ALIVE) && !(old_flags & SMX_F_SOCIAL)) atomicAdd(&env_new_done[env_local], 1);
     if (slot == 0) env_first_alive[env_local] = (new_flags & SMX_F_ALIVE) ? 1 : 0;
   }
   __syncthreads();
@@ -5506,6 +5596,8 @@ struct smx_handle_s {
   GuardBox guard_box = {1.0, 1.0, 0.0, 0.0};
   uint8_t* rgb_out;   // smx_set_rgb_output: the caller's image buffer (null: none bound) and the bytes it holds
   uint64_t rgb_count;
+  void* history_blob;  // smx_set_social_history: device copy of the table, frames | vehicle ids (null: none bound)
+  HistoryDev history;  // ... and what the kernels get (vehicle null: none bound)
   struct StackBinding {  // smx_bind_frame_stack: one caller-owned stack per (source, layout)
     int32_t source, layout;
     uint8_t* dst;
@@ -5651,6 +5743,7 @@ static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_sta
   in.slow_parity = h->alive_parity;
   in.frame_stack_bound = !h->stacks.empty();
   in.guard_bound = h->guard_out != nullptr;
+  in.history_bound = h->history.vehicle != nullptr;
   return in;
 }
 
@@ -5705,6 +5798,10 @@ extern "C" int smx_load_map(smx_handle h, const smx_map_tables* t) {
   h->goals_blob = nullptr;
   h->host_route_last.clear();
   h->missions = MissionsDev{nullptr, nullptr};
+  // a bound traffic history was checked against the old map's grids: a new map starts without one
+  if (h->history_blob) (void)hipFree(h->history_blob);
+  h->history_blob = nullptr;
+  h->history = HistoryDev{};
   if (!h->alive_blob) {  // the tick's alive list (large batches) + its counters, the env groups with new vehicles (alive_layout)
     const size_t n = alive_layout(h->cfg).size;
     SMX_HIP(hipMalloc((void**)&h->alive_blob, n * sizeof(int32_t)));
@@ -5976,6 +6073,48 @@ extern "C" int smx_set_guard(smx_handle h, uint8_t* guard_dev, uint64_t count, d
   h->guard_count = count;
   h->guard_margin = margin;
   if (h->map_loaded) h->guard_box = guard_box_of(h->map, margin);
+  return SMX_OK;
+}
+
+extern "C" int smx_check_social_history(const smx_config* cfg, const smx_map_tables* map, const smx_social_history* hist, char* err,
+                                        uint64_t err_len) {
+  std::string msg;
+  const int rc = (cfg && map && hist) ? check_social_history_impl(*cfg, *map, *hist, msg) : refuse(msg, "null config / map / history");
+  return report(rc, msg, err, err_len);
+}
+
+extern "C" int smx_set_social_history(smx_handle h, const smx_social_history* hist) {
+  if (!h) return SMX_ERR_INVALID;
+  if (hist) {
+    if (!h->map_loaded) return fail(h, SMX_ERR_STATE, "smx_set_social_history needs the map (the rows are checked against its grids)");
+    std::string msg;
+    const int rc = check_social_history_impl(h->cfg, h->map, *hist, msg);  // (the grid extents are scalars: the device copy of the tables has them)
+    if (rc != SMX_OK) return fail(h, rc, msg);
+  }
+  SMX_HIP(hipSetDevice(h->device));
+  SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
+  if (h->history_blob) (void)hipFree(h->history_blob);
+  h->history_blob = nullptr;
+  h->history = HistoryDev{};
+  // the alive list k_tail built for the next tick was built under the other rule (smx_plan.h: tail_builds_list)
+  h->list_ready = false;
+  if (!hist) return SMX_OK;
+  const size_t cells = (size_t)hist->n_frames * (size_t)hist->num_social;
+  const size_t frame_bytes = cells * 4 * sizeof(double), id_bytes = cells * sizeof(int32_t);
+  SMX_HIP(hipMalloc(&h->history_blob, frame_bytes + id_bytes));
+  char* base = (char*)h->history_blob;
+  SMX_HIP(hipMemcpy(base, hist->frames_host, frame_bytes, hipMemcpyHostToDevice));
+  SMX_HIP(hipMemcpy(base + frame_bytes, hist->vehicle_host, id_bytes, hipMemcpyHostToDevice));
+  HistoryDev d;
+  d.frames = (const double*)base;
+  d.vehicle = (const int32_t*)(base + frame_bytes);
+  d.start_frame = hist->start_frame_dev;
+  d.replaced = hist->replaced_dev;
+  d.n_frames = hist->n_frames;
+  d.num_social = hist->num_social;
+  d.rows = hist->rows;
+  d.num_envs = h->cfg.num_envs;
+  h->history = d;
   return SMX_OK;
 }
 
@@ -6374,6 +6513,7 @@ static KernelArgs kernel_args(smx_handle h, const TickPlan& p, const int8_t* act
   a.rgb = h->rgb_out;
   a.guard = h->guard_out;
   a.guard_box = h->guard_box;
+  a.history = h->history;
   a.wp_blocks = (int)p.wp_blocks;
   a.obs_blocks = (int)p.obs_blocks;
   a.lidar_blocks = (int)p.lidar_blocks;
@@ -6673,6 +6813,7 @@ extern "C" void smx_destroy(smx_handle h) {
   if (h->via_off_dev) (void)hipFree(h->via_off_dev);
   if (h->missions_blob) (void)hipFree(h->missions_blob);
   if (h->goals_blob) (void)hipFree(h->goals_blob);
+  if (h->history_blob) (void)hipFree(h->history_blob);
   for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ph_pool) (void)hipEventDestroy(e);
   delete h;

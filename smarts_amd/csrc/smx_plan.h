@@ -79,6 +79,7 @@ struct PlanInputs {
   int slow_parity;        // the counters this tick's one-lane kernels use
   bool frame_stack_bound;  // smx_bind_frame_stack holds at least one buffer
   bool guard_bound;        // smx_set_guard holds a buffer: the state guard is on
+  bool history_bound;      // smx_set_social_history holds a table: the social slots replay it
 };
 
 enum class AliveList : uint8_t { NONE, CARRIED, BUILD };  // BUILD: k_alive_list ahead of the tick
@@ -284,8 +285,10 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
   p.road_waypoints = (c.sensors & SMX_SENSOR_ROAD_WAYPOINTS) != 0;
   p.lane_ttc = (c.sensors & SMX_SENSOR_LANE_TTC) != 0;
 
-  // k_tail builds the next tick's alive list unless k_social moves vehicles (and can end them) ahead of the list
-  p.tail_builds_list = !small && in.alive_blob && in.slow.base && !idm;
+  // k_tail builds the next tick's alive list unless k_social moves vehicles (and can end them) ahead of the list, or a
+  // traffic history is bound: the reset pass's commit then still changes SMX_F_ALIVE of the new envs' social slots (a
+  // slot shows the reset observation's frame in that pass and the next frame in the tick after it), behind k_tail
+  p.tail_builds_list = !small && in.alive_blob && in.slow.base && !idm && !in.history_bound;
   p.reset_pass = !in.is_step || c.auto_reset;  // (in a step, k_tail's commit respawns the envs that ended)
   p.tail_grids = p.reset_pass && (p.ogm_bytes || p.dagm_bytes || p.rgb);
   // large batches: the new vehicles' lidar as a launch of its own instead of one after the other inside

@@ -612,6 +612,47 @@ class BatchedSim:
         nat.check(self.lib, self.handle, rc, "smx_set_guard")
         self.out["guard"] = guard
 
+    def set_traffic_history(self, table, start_frames: Optional[torch.Tensor] = None, replaced: Optional[torch.Tensor] = None):
+        """Bind a recorded traffic history (``smx_set_social_history``; ``smarts_amd.traffic_history``): from the next
+        pass on the social slots take pose, speed and presence from ``table`` (a ``TrafficHistoryTable`` with
+        ``num_social`` slots) instead of the scripted lane follower.  ``start_frames``: int32 ``[R, E]`` on the sim's
+        device, the table frame at which episode ``k`` of env ``e`` has tick count 0 (row ``k mod R``; any value is
+        safe, frames outside the table are empty); ``None`` = one row of zeros.  ``replaced``: int32 ``[R, E]``, the
+        vehicle id hidden in that env (an agent stands in for it; see ``table.spawn_of``), -1 for none; ``None`` = nothing
+        hidden.  Both tensors stay the caller's and are read by every pass: rewriting them in place takes effect with
+        the next tick (``include/smx.h`` says how presence follows).  ``table=None`` unbinds.  Refused with the
+        library's reason (``SmxError``): a slot count other than ``num_social``, ``social_model="idm"``, a row of a
+        present vehicle that is not finite or lies outside the map's grids."""
+        if table is None:
+            nat.check(self.lib, self.handle, self.lib.smx_set_social_history(self.handle, None), "smx_set_social_history")
+            self.traffic_history = self.history_start_frames = self.history_replaced = None
+            return
+        E = self.E
+        if start_frames is None:
+            start_frames = torch.zeros((1, E), dtype=torch.int32, device=self.device)
+        for name, t in (("start_frames", start_frames), ("replaced", replaced)):
+            if t is None:
+                continue
+            if t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous() or t.ndim != 2 or t.shape[1] != E or t.shape[0] < 1:
+                raise ValueError(f"{name} must be a contiguous int32 tensor of shape [R, {E}] on {self.device}")
+        if replaced is not None and replaced.shape != start_frames.shape:
+            raise ValueError("start_frames and replaced must have the same shape [R, E]")
+        frames = np.ascontiguousarray(table.frames, dtype=np.float64)
+        vehicle = np.ascontiguousarray(table.vehicle, dtype=np.int32)
+        hs = nat.SmxSocialHistory()
+        hs.frames_host, hs.vehicle_host = frames.ctypes.data, vehicle.ctypes.data
+        hs.n_frames, hs.num_social = int(frames.shape[0]), int(frames.shape[1])
+        hs.start_frame_dev, hs.start_count, hs.rows = start_frames.data_ptr(), int(start_frames.numel()), int(start_frames.shape[0])
+        if replaced is not None:
+            hs.replaced_dev, hs.replaced_count = replaced.data_ptr(), int(replaced.numel())
+        nat.check(self.lib, self.handle, self.lib.smx_set_social_history(self.handle, C.byref(hs)), "smx_set_social_history")
+        # (the library reads the two tensors in every pass: they live as long as the binding)
+        self.traffic_history, self.history_start_frames, self.history_replaced = table, start_frames, replaced
+
+    traffic_history = None
+    history_start_frames = None
+    history_replaced = None
+
     def bind_frame_stack(self, row: str, stack: Optional[torch.Tensor], layout: str = "frames"):
         """Bind the frame stack of ``out[row]`` (``smx_bind_frame_stack``; needs ``SimConfig(frame_stack=k)``): a
         contiguous device tensor of the row's dtype, ``[E, N, k, ...row shape]`` for ``layout="frames"`` or, for the

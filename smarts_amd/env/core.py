@@ -136,8 +136,13 @@ class BatchCore:
                  num_social: int = 0, vias: Optional[Dict[str, Sequence]] = None, social_model: str = "constant",
                  missions: Optional[Dict[str, Any]] = None, spawns: str = "reference", shuffle_scenarios: bool = True,
                  ego_centric: bool = False, state_guard: bool = False,
-                 state_guard_margin: float = nat.GUARD_MARGIN_DEFAULT):
-        """``state_guard`` / ``state_guard_margin``: ``SimConfig``'s (the state guard, include/smx.h smx_set_guard):
+                 state_guard_margin: float = nat.GUARD_MARGIN_DEFAULT, traffic_history=None, history_start_frames=None):
+        """``traffic_history``: a ``smarts_amd.traffic_history.TrafficHistoryTable`` or the path of a converted dataset
+        (SQLite): the ``num_social`` slots replay it (``BatchedSim.set_traffic_history``) and are named
+        ``history-vehicle-<id>`` in the observations, the reference provider's prefix.  ``history_start_frames``: int
+        ``[R, E]`` (or ``[E]``), the table frame at which episode ``k`` of env ``e`` starts (row ``k mod R``); ``None`` =
+        every env replays from frame 0.
+        ``state_guard`` / ``state_guard_margin``: ``SimConfig``'s (the state guard, include/smx.h smx_set_guard):
         ``info[agent]["guard"]`` then holds the agent's guard byte whenever it is non-zero.  One exception: the infos
         ``ParallelEnv.step`` returns for an env that restarted inside the launch (``auto_reset``) describe the finishing
         tick, whose bytes the new episode's have replaced already, so they carry no ``"guard"``.
@@ -212,13 +217,33 @@ class BatchCore:
                     spawns.reshape(spawns.shape[0], num_envs, slots, 4)[:, :, i] = (x, y, h, 0.0)
         self.sim = BatchedSim(self.cm, self.cfg, device=device, spawns=spawns, seed=seed, social_spawns=where,
                               vias=self.vias, missions=self.missions)
+        self.traffic_history = None
+        if traffic_history is not None:
+            import torch
+
+            from ..traffic_history import TrafficHistoryTable
+
+            if num_social < 1:
+                raise ValueError("traffic_history needs num_social >= 1 (the slots that replay it)")
+            table = traffic_history
+            if not isinstance(table, TrafficHistoryTable):
+                table = TrafficHistoryTable.from_sqlite(os.fspath(traffic_history), dt, num_social)
+            start = np.zeros((1, num_envs), dtype=np.int32) if history_start_frames is None else \
+                np.atleast_2d(np.asarray(history_start_frames)).astype(np.int32)
+            if start.shape[1:] != (num_envs,):
+                raise ValueError(f"history_start_frames must have shape [R, {num_envs}] or [{num_envs}]")
+            self.sim.set_traffic_history(table, torch.from_numpy(np.ascontiguousarray(start)).to(self.sim.device))
+            self.traffic_history = table
+        elif history_start_frames is not None:
+            raise ValueError("history_start_frames needs traffic_history")
         road_ids = [self.cm.road_ids[r] for r in self.cm.lane_road]
         vehicle_names = self.agent_ids + [f"social-{k}" for k in range(num_social)]
         self.builder = ObservationBuilder(
             self.cm.lane_ids, road_ids, vehicle_names, waypoints=self.cfg.waypoints, neighbors=self.cfg.neighbors,
             accelerometer=self.cfg.accelerometer, ogm=first.ogm or None, dagm=first.drivable_area_grid_map or None,
             lidar_rays=base_rays(first.lidar.sensor_params) if first.lidar else None, dt=dt, vias=self.vias,
-            road_waypoints=bool(first.road_waypoints), missions=self.missions, rgb=first.rgb or None)
+            road_waypoints=bool(first.road_waypoints), missions=self.missions, rgb=first.rgb or None,
+            history=self.traffic_history)
         self._was_reset = False
         self._destroyed = False
 
@@ -341,12 +366,19 @@ class BatchCore:
         # the learner block is [2, E, N] (reward / done axis first) and exists for the device-side gather only
         rows = {k: v.cpu().numpy() for k, v in out.items() if k != "learner"}
         rows["env_ticks"] = self.sim.env_ticks.cpu().numpy()
+        if self.traffic_history is not None:
+            # the table frame every env's observation shows (include/smx.h smx_set_social_history): names the neighbours
+            start = self.sim.history_start_frames.cpu().numpy().astype(np.int64)
+            episode = self.sim.env_episode.cpu().numpy().astype(np.int64)
+            rows["history_frame"] = start[episode % start.shape[0], np.arange(self.E)] + rows["env_ticks"]
         return rows
 
-    PER_ENV_ROWS = ("env_done", "env_ticks")  # [E]; every other row is [E, N, ...]
+    PER_ENV_ROWS = ("env_done", "env_ticks", "history_frame")  # [E]; every other row is [E, N, ...]
 
     def observations(self, rows: Dict[str, np.ndarray], env: int, present: np.ndarray) -> Dict[str, Observation]:
         er = {k: v[env] for k, v in rows.items() if k not in self.PER_ENV_ROWS}
+        if "history_frame" in rows:
+            er["history_frame"] = int(rows["history_frame"][env])
         t = int(rows["env_ticks"][env])  # device clock: already that of the new episode after an auto-reset
         elapsed = round(t * self.dt, 6)
         return {self.agent_ids[i]: self.builder.build(er, i, t, elapsed) for i in range(self.N) if present[i]}

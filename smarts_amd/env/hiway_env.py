@@ -50,6 +50,8 @@ class HiWayEnv:
         spawns: str = "reference",
         state_guard: bool = False,
         state_guard_margin: float = 1000.0,
+        traffic_history=None,
+        history_start_frames=None,
     ):
         self._log = logging.getLogger(self.__class__.__name__)
         if not headless or envision_record_data_replay_path or envision_endpoint:
@@ -94,6 +96,14 @@ class HiWayEnv:
         self._shuffle_scenarios = bool(shuffle_scenarios)
         # the state guard (include/smx.h smx_set_guard), off by default
         self._state_guard, self._state_guard_margin = bool(state_guard), state_guard_margin
+        # traffic-history replay (smarts_amd.traffic_history; the reference's TrafficHistoryProvider): a
+        # TrafficHistoryTable or the path of a converted dataset, replayed by the num_social slots; the table frame at
+        # which this env's episode k starts (an int, or a sequence used cyclically over the episodes; None = frame 0)
+        self._traffic_history = traffic_history
+        if history_start_frames is not None and traffic_history is None:
+            raise ValueError("history_start_frames needs traffic_history")
+        self._history_start_frames = None if history_start_frames is None else \
+            [int(v) for v in np.atleast_1d(np.asarray(history_start_frames)).reshape(-1)]
         self._dones_registered = 0
         self._core: Optional[BatchCore] = None
         self._seed = seed
@@ -125,7 +135,9 @@ class HiWayEnv:
         specs = self._agent_specs
         return (self._scenario, tuple(specs.keys()), tuple(repr(s.interface) for s in specs.values()), self._dt,
                 self._waypoint_window, self._num_social, self._social_model, repr(self._vias), repr(self._missions),
-                self._spawns, self._shuffle_scenarios, self._state_guard, self._state_guard_margin)
+                self._spawns, self._shuffle_scenarios, self._state_guard, self._state_guard_margin,
+                self._traffic_history if isinstance(self._traffic_history, (str, type(None))) else id(self._traffic_history),
+                None if self._history_start_frames is None else len(self._history_start_frames))
 
     def seed(self, seed: int) -> int:
         """hiway_env.py:204-214.  Takes effect at the next ``reset`` that (re)builds the spawn table."""
@@ -146,7 +158,10 @@ class HiWayEnv:
                                    auto_reset=False, device=self._device, waypoint_window=self._waypoint_window,
                                    num_social=self._num_social, vias=self._vias, social_model=self._social_model,
                                    missions=self._missions, spawns=self._spawns, shuffle_scenarios=self._shuffle_scenarios,
-                                   state_guard=self._state_guard, state_guard_margin=self._state_guard_margin)
+                                   state_guard=self._state_guard, state_guard_margin=self._state_guard_margin,
+                                   traffic_history=self._traffic_history,
+                                   history_start_frames=None if self._history_start_frames is None
+                                   else np.asarray(self._history_start_frames, dtype=np.int32).reshape(-1, 1))
         return self._core
 
     def step(self, agent_actions) -> Tuple[Dict[str, Observation], Dict[str, float], Dict[str, bool], Dict[str, Any]]:

@@ -254,7 +254,7 @@ class ObservationBuilder:
 
     def __init__(self, lane_ids: Sequence[str], lane_road_ids: Sequence[str], agent_ids: Sequence[str], *,
                  waypoints: bool, neighbors: bool, accelerometer: bool, ogm=None, lidar_rays: Optional[np.ndarray] = None,
-                 dt: float = 0.1, vias=None, dagm=None, road_waypoints: bool = False, missions=None, rgb=None):
+                 dt: float = 0.1, vias=None, dagm=None, road_waypoints: bool = False, missions=None, rgb=None, history=None):
         self.lane_ids = list(lane_ids)
         self.lane_road_ids = list(lane_road_ids)
         self.agent_ids = list(agent_ids)
@@ -268,12 +268,25 @@ class ObservationBuilder:
             FixedRouteMission(tuple(m.start_position), float(m.start_heading), PositionalGoal(tuple(m.goal[:2]), float(m.goal[2])),
                               tuple(m.route_roads)) if m is not None and m.route_roads else None for m in (missions or [])]
         self.vias = vias  # per vehicle slot: resolved mission vias (smarts_amd.vias.ResolvedVia)
+        self.history = history  # smarts_amd.traffic_history.TrafficHistoryTable | None: the last num_slots slots replay it
 
-    def vehicle_id(self, slot: int) -> str:
-        # Vehicle.build_agent_vehicle (vehicle.py:371-372) names agent vehicles after their agent;
-        # scripted social vehicles (slots after the agents) keep their own name
+    def actor_id(self, slot: int, rows=None) -> str:
+        """The name of the vehicle slot's owner: the agent id, the scripted social vehicle's own name, or — with a
+        traffic history bound — ``history-vehicle-<id>`` (TrafficHistoryProvider._vehicle_id_prefix) of the vehicle the
+        table holds in that slot at the env's frame (``rows["history_frame"]``)."""
         name = self.agent_ids[slot]
-        return name if name.startswith("social-") else f"{name}-vehicle"
+        if self.history is not None and name.startswith("social-") and rows is not None and "history_frame" in rows:
+            from ..traffic_history import HISTORY_VEHICLE_PREFIX
+
+            k = slot - (len(self.agent_ids) - self.history.num_slots)
+            return f"{HISTORY_VEHICLE_PREFIX}{self.history.vehicle_at(int(rows['history_frame']), k)}"
+        return name
+
+    def vehicle_id(self, slot: int, rows=None) -> str:
+        # Vehicle.build_agent_vehicle (vehicle.py:371-372) names agent vehicles after their agent;
+        # scripted social vehicles (slots after the agents) keep their own name, replayed ones the provider's
+        name = self.actor_id(slot, rows)
+        return name if name.startswith(("social-", "history-vehicle-")) else f"{name}-vehicle"
 
     def _lane(self, lane: int, lane_index: int):
         if lane < 0:
@@ -322,7 +335,7 @@ class ObservationBuilder:
         # collisions come in slot order, each naming the owner of the vehicle hit (an agent id, or the
         # scripted social vehicle's own name)
         mask = int(rows["collidees"][slot]) & 0xFFFFFFFFFFFFFFFF if "collidees" in rows else 0
-        collisions = [Collision(collidee_id=self.agent_ids[j]) for j in range(len(self.agent_ids)) if (mask >> j) & 1]
+        collisions = [Collision(collidee_id=self.actor_id(j, rows)) for j in range(len(self.agent_ids)) if (mask >> j) & 1]
         if ev[nat.EV["COLLISIONS"]] and not collisions:  # rows from a caller that passed no collidee buffer
             collisions = [Collision(collidee_id=None)]
         events = Events(
@@ -339,7 +352,7 @@ class ObservationBuilder:
             for k in range(min(int(rows["nb_count"][slot]), rows["nb_slot"].shape[1])):
                 r, l, li = self._lane(int(rows["nb_lane_id"][slot, k]), int(rows["nb_lane_index"][slot, k]))
                 neighbors.append(VehicleObservation(
-                    id=self.vehicle_id(int(rows["nb_slot"][slot, k])),
+                    id=self.vehicle_id(int(rows["nb_slot"][slot, k]), rows),
                     position=tuple(float(x) for x in rows["nb_pos"][slot, k]),
                     bounding_box=Dimensions(*[float(x) for x in rows["nb_box"][slot, k]]),
                     heading=Heading(float(rows["nb_heading"][slot, k])), speed=float(rows["nb_speed"][slot, k]),

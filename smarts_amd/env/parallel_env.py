@@ -39,6 +39,9 @@ class ParallelEnv:
             # the reference raises ValueError when the spaces differ (parallel_env.py:160-188)
             raise ValueError("environments of one accelerated batch must share scenario, agents, interface and timestep")
         self._proto = envs[0]
+        # every env replays its own window of the shared traffic history: column e holds env e's start frames
+        starts = [e._history_start_frames for e in envs]
+        self._history_start_frames = None if starts[0] is None else np.asarray(starts, dtype=np.int32).T
         self._num_envs = len(envs)
         self._auto_reset = auto_reset
         self._device = device
@@ -65,7 +68,8 @@ class ParallelEnv:
                                auto_reset=self._auto_reset, device=self._device, waypoint_window=p._waypoint_window or STD_WAYPOINT_WINDOW,
                                num_social=p._num_social, vias=p._vias, social_model=p._social_model, missions=p._missions,
                                spawns=p._spawns, shuffle_scenarios=p._shuffle_scenarios,
-                               state_guard=p._state_guard, state_guard_margin=p._state_guard_margin)
+                               state_guard=p._state_guard, state_guard_margin=p._state_guard_margin,
+                               traffic_history=p._traffic_history, history_start_frames=self._history_start_frames)
         self._seed = seed
         return [seed + i for i in range(self._num_envs)]
 

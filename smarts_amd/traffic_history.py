@@ -1,0 +1,228 @@
+"""Traffic-history replay, host side: a recorded dataset resampled into the dense table the device replays.
+
+The reference replays a converted dataset (NGSIM, INTERACTION: ``smarts/sstudio/genhistories.py`` writes the SQLite
+file) tick by tick through ``TrafficHistoryProvider.step`` (``smarts/core/traffic_history_provider.py:96-136`` over
+``TrafficHistory.vehicles_active_between``, ``traffic_history.py:221-231``).  ``TrafficHistoryTable`` holds what that
+provider would hand out at every tick of a run that starts at history time 0, in ``num_slots`` vehicle slots: the table
+``smx_set_social_history`` (include/smx.h) copies to the device, where every env replays its own window of it
+(``BatchedSim.set_traffic_history``).
+
+Frame ``k`` is history time ``k * dt``.  Per vehicle it holds the latest sample with
+``rounder(rounder(k * dt) - dt) < sim_time <= rounder(k * dt)`` — the provider's ``ORDER BY sim_time DESC``, first row per
+id, ``rounder_for_dt(dt)`` — as a copy: x, y, speed untouched, the heading wrapped as ``Heading.__new__`` wraps it
+(``coordinates.py:175-184``).  A vehicle without a sample in a window is absent from that frame, exactly as in the
+reference: data recorded at a period longer than ``dt`` flickers (present in the frames that hold a sample, absent in
+between), here as there.
+
+Deviations from the reference, all stated in DESIGN.md section 5:
+ - a window starts at a frame, i.e. at a multiple of ``dt`` (``frame_of`` raises otherwise); the reference's
+   ``start_time`` is any non-negative float;
+ - every replayed vehicle has the sedan's box on the device; the per-vehicle ``length, width, height`` kept here are
+   host metadata that nothing on the device reads;
+ - ``Trajectory`` rows of a vehicle type other than the passenger car are replayed too (the provider does the same; only
+   the reference's mission discovery filters on the type).
+"""
+from __future__ import annotations
+
+import math
+import sqlite3
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+HISTORY_VEHICLE_PREFIX = "history-vehicle-"  # TrafficHistoryProvider._vehicle_id_prefix
+
+
+def round_param_for_dt(dt: float) -> int:
+    """The digits ``round()`` keeps for a time step (smarts/core/utils/math.py:553-563)."""
+    strep = np.format_float_positional(dt)
+    decimal = strep.find(".")
+    if decimal >= len(strep) - 1:
+        return 1 - decimal
+    return len(strep) - decimal - 1
+
+
+def wrap_heading(value: float) -> float:
+    """``Heading.__new__`` (coordinates.py:175-184): into (-pi, pi], with Python's float modulo."""
+    value = float(value) % (2 * math.pi)
+    if value > math.pi:
+        value -= 2 * math.pi
+    return value
+
+
+def _window_samples(vehicle_rows, trajectory_rows, dt: float, exclude_ids: Iterable[int]):
+    """Per frame, ``{vehicle id: (x, y, heading, speed)}`` of what the provider returns at that frame's tick."""
+    if not dt > 0.0:
+        raise ValueError("dt must be > 0")
+    known = {int(r[0]) for r in vehicle_rows}  # (the provider's INNER JOIN: a trajectory needs its Vehicle row)
+    hidden = {int(v) for v in exclude_ids}
+    rp = round_param_for_dt(dt)
+    traj = sorted(((float(r[1]), int(r[0]), float(r[2]), float(r[3]), float(r[4]), float(r[5] if r[5] is not None else 0.0))
+                   for r in trajectory_rows if int(r[0]) in known and int(r[0]) not in hidden))
+    if not traj:
+        return [dict()]
+    if any(not math.isfinite(t[0]) for t in traj):
+        raise ValueError("trajectory times must be finite")
+    last = traj[-1][0]
+    frames: List[Dict[int, Tuple[float, float, float, float]]] = []
+    i, k = 0, 0
+    while True:
+        hi = round(k * dt, rp)
+        lo = round(hi - dt, rp)
+        while i < len(traj) and traj[i][0] <= lo:  # (samples at or before the window's open end: never shown by this or a later frame)
+            i += 1
+        cur: Dict[int, Tuple[float, float, float, float]] = {}
+        j = i
+        while j < len(traj) and traj[j][0] <= hi:  # ascending time: a later sample of the same vehicle replaces the earlier
+            _, vid, x, y, h, s = traj[j]
+            cur[vid] = (x, y, wrap_heading(h), s)
+            j += 1
+        frames.append(cur)
+        if hi >= last:
+            break
+        k += 1
+    return frames
+
+
+def _assign_slots(frames) -> Tuple[List[Dict[int, int]], int]:
+    """Slot of every vehicle in every frame, and the slots needed.  A vehicle keeps its slot while it is present in
+    consecutive frames; a slot is free for another vehicle only once it has stood empty for a frame; vehicles that
+    appear in the same frame take the lowest free slots in ascending id order."""
+    prev: Dict[int, int] = {}
+    out: List[Dict[int, int]] = []
+    needed = 0
+    for cur in frames:
+        held = {vid: prev[vid] for vid in cur if vid in prev}
+        blocked = set(prev.values())  # occupied in the frame before: kept by its vehicle, or cooling off for one frame
+        now = dict(held)
+        slot = 0
+        for vid in sorted(v for v in cur if v not in prev):
+            while slot in blocked:
+                slot += 1
+            now[vid] = slot
+            blocked.add(slot)
+        needed = max(needed, max(now.values()) + 1 if now else 0)
+        out.append(now)
+        prev = now
+    return out, needed
+
+
+def slots_needed(vehicle_rows, trajectory_rows, dt: float, exclude_ids: Iterable[int] = ()) -> int:
+    """The smallest ``num_slots`` ``TrafficHistoryTable.from_rows`` accepts for these rows (nothing is built)."""
+    return _assign_slots(_window_samples(vehicle_rows, trajectory_rows, dt, exclude_ids))[1]
+
+
+class TrafficHistoryTable:
+    """``frames`` [F, S, 4] float64 (x, y, heading, speed: the vehicle centre, the reference's heading convention,
+    wrapped), ``vehicle`` [F, S] int32 (the history's vehicle id, < 0 = the slot is empty), ``dims`` {id: (length, width,
+    height)} with ``None`` where the dataset has none (host metadata only)."""
+
+    def __init__(self, frames: np.ndarray, vehicle: np.ndarray, dt: float, dims: Optional[Dict[int, Tuple]] = None):
+        frames = np.ascontiguousarray(frames, dtype=np.float64)
+        vehicle = np.ascontiguousarray(vehicle, dtype=np.int32)
+        if frames.ndim != 3 or frames.shape[2] != 4 or vehicle.shape != frames.shape[:2] or frames.shape[0] < 1:
+            raise ValueError(f"frames must be [F >= 1, S, 4] and vehicle [F, S], got {frames.shape} and {vehicle.shape}")
+        self.frames, self.vehicle, self.dt = frames, vehicle, float(dt)
+        self.dims = dict(dims or {})
+        self._rp = round_param_for_dt(self.dt)
+
+    # ------------------------------------------------------------------ constructors
+    @classmethod
+    def from_rows(cls, vehicle_rows: Sequence[Sequence], trajectory_rows: Sequence[Sequence], dt: float, num_slots: int,
+                  exclude_ids: Iterable[int] = ()) -> "TrafficHistoryTable":
+        """``vehicle_rows``: (id, type, length, width, height[, is_ego_vehicle]) as in the ``Vehicle`` table;
+        ``trajectory_rows``: (vehicle_id, sim_time, position_x, position_y, heading_rad, speed[, lane_id]) as in
+        ``Trajectory``.  ``exclude_ids`` never enter the table (for a vehicle an agent replaces in every env; to hide one
+        per env, keep it and use ``replaced`` of ``BatchedSim.set_traffic_history``).  More vehicles at once than
+        ``num_slots`` holds raises ``ValueError`` naming the number needed."""
+        samples = _window_samples(vehicle_rows, trajectory_rows, dt, exclude_ids)
+        slots, needed = _assign_slots(samples)
+        if needed > num_slots:
+            raise ValueError(f"the history needs {needed} slots (vehicles present at once, and a free frame before a slot "
+                             f"is reused), num_slots is {num_slots}")
+        frames = np.zeros((len(samples), num_slots, 4), dtype=np.float64)
+        vehicle = np.full((len(samples), num_slots), -1, dtype=np.int32)
+        for k, (cur, where) in enumerate(zip(samples, slots)):
+            for vid, row in cur.items():
+                if not 0 <= vid <= 0x7FFFFFFF:
+                    raise ValueError(f"vehicle id {vid} does not fit the table's int32 ids (>= 0)")
+                frames[k, where[vid]] = row
+                vehicle[k, where[vid]] = vid
+        dims = {int(r[0]): tuple(None if v is None else float(v) for v in r[2:5]) for r in vehicle_rows}
+        return cls(frames, vehicle, dt, dims)
+
+    @classmethod
+    def from_sqlite(cls, path: str, dt: float, num_slots: int, exclude_ids: Iterable[int] = ()) -> "TrafficHistoryTable":
+        """From a converted dataset: the ``Vehicle`` and ``Trajectory`` tables ``genhistories.py`` writes."""
+        vehicle_rows, trajectory_rows = read_sqlite(path)
+        return cls.from_rows(vehicle_rows, trajectory_rows, dt, num_slots, exclude_ids)
+
+    # ------------------------------------------------------------------ helpers
+    @property
+    def num_frames(self) -> int:
+        return int(self.frames.shape[0])
+
+    @property
+    def num_slots(self) -> int:
+        return int(self.frames.shape[1])
+
+    def frame_of(self, time: float) -> int:
+        """The frame of history time ``time``, which must be a multiple of ``dt`` (a deviation: the reference's
+        ``start_time`` may be any non-negative time; a window here starts at a frame)."""
+        time = float(time)
+        k = int(round(time / self.dt)) if math.isfinite(time) else 0
+        if not math.isfinite(time) or abs(k * self.dt - time) > 1e-9 * max(1.0, abs(time)):
+            raise ValueError(f"history time {time!r} is not a multiple of dt = {self.dt}")
+        return k
+
+    def vehicle_at(self, frame: int, slot: int) -> int:
+        """The vehicle id in ``slot`` at ``frame``; -1 for an empty slot and for a frame outside the table."""
+        if not 0 <= slot < self.num_slots:
+            raise IndexError(f"slot {slot} of {self.num_slots}")
+        if not 0 <= frame < self.num_frames:
+            return -1
+        return int(self.vehicle[frame, slot])
+
+    def spawn_of(self, vehicle_id: int, frame: int) -> Tuple[float, float, float, float]:
+        """(x, y, heading, speed) of ``vehicle_id`` at ``frame``: the spawn row of an agent that replaces it."""
+        if 0 <= frame < self.num_frames:
+            hit = np.nonzero(self.vehicle[frame] == int(vehicle_id))[0]
+            if len(hit):
+                return tuple(float(v) for v in self.frames[frame, hit[0]])
+        raise KeyError(f"vehicle {vehicle_id} is not present in frame {frame}")
+
+    def dimensions(self, vehicle_id: int) -> Tuple:
+        """(length, width, height) of the dataset, ``None`` where it has none.  Host metadata only."""
+        return self.dims[int(vehicle_id)]
+
+    def vehicle_ids(self) -> List[int]:
+        return sorted(int(v) for v in np.unique(self.vehicle) if v >= 0)
+
+
+def read_sqlite(path: str):
+    """(vehicle_rows, trajectory_rows) of a converted dataset, in the column order ``from_rows`` takes."""
+    with sqlite3.connect(f"file:{path}?mode=ro", uri=True) as db:
+        vehicle_rows = db.execute("SELECT id, type, length, width, height, is_ego_vehicle FROM Vehicle ORDER BY id").fetchall()
+        trajectory_rows = db.execute("SELECT vehicle_id, sim_time, position_x, position_y, heading_rad, speed, lane_id "
+                                     "FROM Trajectory ORDER BY vehicle_id, sim_time").fetchall()
+    return vehicle_rows, trajectory_rows
+
+
+def read_spec(path: str) -> Dict[str, str]:
+    """The ``Spec`` table of a converted dataset (source, lane width, speed limit, ...) as a dict."""
+    with sqlite3.connect(f"file:{path}?mode=ro", uri=True) as db:
+        return {str(k): v for k, v in db.execute("SELECT key, value FROM Spec").fetchall()}
+
+
+def write_sqlite(path: str, vehicle_rows: Sequence[Sequence], trajectory_rows: Sequence[Sequence], spec: Optional[Dict] = None):
+    """A dataset file with the three tables of the converter's layout (for tests and small synthetic histories)."""
+    with sqlite3.connect(path) as db:
+        db.execute("CREATE TABLE Spec (key TEXT PRIMARY KEY, value TEXT) WITHOUT ROWID")
+        db.execute("CREATE TABLE Vehicle (id INTEGER PRIMARY KEY, type INTEGER NOT NULL, length REAL, width REAL, height REAL, "
+                   "is_ego_vehicle INTEGER DEFAULT 0) WITHOUT ROWID")
+        db.execute("CREATE TABLE Trajectory (vehicle_id INTEGER NOT NULL, sim_time REAL NOT NULL, position_x REAL NOT NULL, "
+                   "position_y REAL NOT NULL, heading_rad REAL NOT NULL, speed REAL DEFAULT 0.0, lane_id INTEGER DEFAULT 0, "
+                   "PRIMARY KEY (vehicle_id, sim_time)) WITHOUT ROWID")
+        db.executemany("INSERT INTO Spec VALUES (?, ?)", [(str(k), str(v)) for k, v in (spec or {}).items()])
+        db.executemany("INSERT INTO Vehicle VALUES (?, ?, ?, ?, ?, ?)", [(tuple(r) + (0,))[:6] for r in vehicle_rows])
+        db.executemany("INSERT INTO Trajectory VALUES (?, ?, ?, ?, ?, ?, ?)", [(tuple(r) + (0,))[:7] for r in trajectory_rows])

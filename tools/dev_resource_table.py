@@ -7,7 +7,8 @@ One line per kernel: VGPRs, AGPRs, SGPRs, scratch bytes per lane, LDS bytes per 
 the demangled name (template arguments kept: a trailing `false` / `true` is the GUARD parameter of the control, reset
 and tail kernels).  FILTER: keep kernels whose name contains one of the words.  With --compare OTHER.txt the kernels of
 OTHER whose name, less a trailing `, false` / `<false>` argument, equals one here are put beside them and every
-difference is marked.  profiles/r12_guard_resources.txt was made with it.
+difference is marked.  profiles/r12_guard_resources.txt was made with it.  With --same-names as well the kernels are
+paired by their full names (both builds have the same kernels: profiles/r16_traffic_history_resources.txt).
 """
 import re
 import subprocess
@@ -54,6 +55,8 @@ def base(name):
 
 def main(argv):
     compare = None
+    same_names = "--same-names" in argv
+    argv = [a for a in argv if a != "--same-names"]
     if "--compare" in argv:
         i = argv.index("--compare")
         compare = parse(argv[i + 1])
@@ -70,10 +73,10 @@ def main(argv):
         if compare is None:
             print(row + "   " + name)
             continue
-        if guarded(name) and name.endswith("true>"):
+        if not same_names and guarded(name) and name.endswith("true>"):
             print(row + "   |" + " " * len(head) + "   " + name)
             continue
-        other = compare.get(base(name))
+        other = compare.get(name if same_names else base(name))
         if other is None:
             print(row + "   |" + f"{'(absent)':>{len(head)}}" + "   " + name)
             continue
