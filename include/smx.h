@@ -644,7 +644,7 @@ int smx_check_guard(const smx_config* cfg, uint64_t count, double margin, char* 
  *            reports (cfg.reset_elapsed_steps at a reset observation); outside [0, n_frames) every slot is empty
  *   present = vehicle[frame][slot] >= 0 and != replaced[episode mod rows][env]   (replaced_dev NULL: nothing hidden)
  * A present slot is an alive social vehicle at the frame's row: seen by every sensor and collision test, with the
- * sedan's box.  SMX_S_PREV_X / _Y behave as for the scripted vehicle, SMX_S_MCL_X / _Y / SMX_S_SPD_INT stay 0;
+ * sedan's box (or its own: smx_set_social_history_dims below).  SMX_S_PREV_X / _Y behave as for the scripted vehicle, SMX_S_MCL_X / _Y / SMX_S_SPD_INT stay 0;
  * spawns.social and the slot's spawns.pose rows are not read (the entry check still wants the buffer).  An absent slot
  * is not alive; it never counts in env_done_count or env_done.  SMX_F_ALIVE of a social slot is decided at the end of
  * the pass before (from the tables as they were then): after an in-place rewrite a vehicle that the new frame lacks
@@ -668,6 +668,33 @@ typedef struct smx_social_history {
 int smx_set_social_history(smx_handle h, const smx_social_history* hist);
 int smx_check_social_history(const smx_config* cfg, const smx_map_tables* map, const smx_social_history* hist, char* err,
                              uint64_t err_len);
+/* ... at each vehicle's own dimensions (TrafficHistoryProvider.step, traffic_history_provider.py:112-126).  Opt-in: with
+ * a history bound and no dimensions every replayed vehicle has the sedan's box, as before.
+ *   dims_host[n_ids][3]   length, width, height in metres of the history's vehicle `id`, the provider's rule already
+ *                         applied (the dataset's value, or the default of the vehicle's type where it has none)
+ * A host pointer; the handle keeps a device copy and a triple per (env, slot).  The triple is written wherever the
+ * replayed slot's pose is written, looked up through the frame's vehicle id: the size a pass's sensors see is that of
+ * the vehicle whose pose they see, a slot reused by another vehicle changes size with it, and an in-place rewrite of
+ * start_frame / replaced takes effect together with the pose.  Read by: the collision test (two sizes; the broad phase
+ * reaches the sedan's half diagonal plus the mate's plus the leeway), nb_box (cast to float32), the OGM, the RGB image
+ * and the lidar (the mate's half length and half width; vertically the box keeps the sedan's underside,
+ * SMX_BASE_HEIGHT + 0.1, and rises by the vehicle's height — the reference centres a BoxChassis box on z = 0, this path
+ * stands every vehicle on the ground).  Not read by: the state rows of replayed slots (unchanged), the scripted models,
+ * the ego's own box row, the off-route and path-seed radii, the neighbours' lane lookup (the EGO's length,
+ * sensors.py:244-246).  Agents stay sedans, an agent that stands in for a recorded truck (`replaced`) included.
+ * Needs a bound history (SMX_ERR_STATE without one); smx_set_social_history, with a table or NULL, and smx_load_map
+ * drop the dimensions.  dims = NULL unbinds: the sedan's box again from the next tick.  Refused (SMX_ERR_INVALID, the
+ * reason in smx_last_error): n_ids < 1; a non-empty cell of the bound vehicle_host whose id is >= n_ids; a value that is
+ * not finite or <= 0; length or width above 25 m; height above 10 m.  Waits for the device.
+ * smx_check_social_history_dims is the validation alone, without a device or a handle (`hist`: vehicle_host, n_frames
+ * and num_social are read). */
+typedef struct smx_social_dims {
+  const double* dims_host; /* [n_ids][3] length, width, height */
+  int32_t n_ids;
+} smx_social_dims;
+int smx_set_social_history_dims(smx_handle h, const smx_social_dims* dims);
+int smx_check_social_history_dims(const smx_config* cfg, const smx_social_history* hist, const smx_social_dims* dims, char* err,
+                                  uint64_t err_len);
 /* Frame stacking (smx_config.frame_stack = k): for every agent the device keeps the last k frames of each bound row,
  * newest first (frame 0 is this pass's row), in a caller-owned device buffer.  At the end of every smx_reset / smx_step*
  * pass, on the caller's stream, once every row of the pass is complete (under auto_reset: after the reset pass has

@@ -132,6 +132,10 @@ class SmxSocialHistory(C.Structure):  # smx_social_history (smx_set_social_histo
                 ("replaced_count", C.c_uint64)]
 
 
+class SmxSocialDims(C.Structure):  # smx_social_dims (smx_set_social_history_dims)
+    _fields_ = [("dims_host", _p), ("n_ids", _i32)]
+
+
 class SmxSpawns(C.Structure):
     _fields_ = [("episodes", _i32), ("pose", _p), ("social", _p), ("pose_count", C.c_uint64), ("social_count", C.c_uint64)]
 
@@ -193,7 +197,7 @@ EXPORTS = [
     "smx_check_buffers", "smx_set_launch_strategy", "smx_launch_form", "smx_step_target_pose", "smx_step_trajectory_with_time",
     "smx_set_mission_goals", "smx_check_mission_goals", "smx_actions_to_world", "smx_set_rgb_output", "smx_check_rgb_output",
     "smx_bind_frame_stack", "smx_check_frame_stack", "smx_set_guard", "smx_check_guard",
-    "smx_set_social_history", "smx_check_social_history",
+    "smx_set_social_history", "smx_check_social_history", "smx_set_social_history_dims", "smx_check_social_history_dims",
 ]
 LAUNCH_FORMS = {0: "small", 1: "large_teams", 2: "large_one_lane"}
 LAUNCH_STRATEGIES = {"auto": 0, "small": 1, "large": 2, "large_one_lane": 3, "large_teams": 4}
@@ -282,6 +286,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.smx_check_social_history.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxMapTables), C.POINTER(SmxSocialHistory),
                                              C.c_char_p, C.c_uint64]
     lib.smx_check_social_history.restype = C.c_int
+    lib.smx_set_social_history_dims.argtypes = [h, C.POINTER(SmxSocialDims)]
+    lib.smx_set_social_history_dims.restype = C.c_int
+    lib.smx_check_social_history_dims.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxSocialHistory), C.POINTER(SmxSocialDims),
+                                                  C.c_char_p, C.c_uint64]
+    lib.smx_check_social_history_dims.restype = C.c_int
     lib.smx_read_phase_ms.argtypes = [h, C.POINTER(C.c_float), _i32, C.POINTER(_i32)]
     lib.smx_read_phase_ms.restype = C.c_int
     lib.smx_set_timing.argtypes = [h, C.c_int]

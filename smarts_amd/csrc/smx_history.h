@@ -1,8 +1,9 @@
 // smx_history.h — traffic-history replay (include/smx.h, smx_set_social_history): which frame of the recorded table an
 // env replays in a pass, whether a social slot holds a vehicle there, and the row it takes its pose from, each written
 // once.  social_vehicle_step (every control form), respawn_vehicle (k_reset and the commit-time respawn) and commit_role
-// call these; the header holds no HIP and also compiles for the host (tests/native/host_history.cpp drives it under
-// AddressSanitizer + UBSan).
+// call these; the header holds no HIP and also compiles for the host (tests/native/host_history.cpp and
+// host_history_dims.cpp drive it under AddressSanitizer + UBSan).  The second half is the per-vehicle dimensions
+// (smx_set_social_history_dims): the id -> (length, width, height) lookup the same writers use.
 //
 // Nothing read from the two caller-owned tables can take an index out of a table: the row of start_frame / replaced is
 // (episode mod rows) brought into [0, rows), the env is the kernel's own, the frame is formed in 64 bits (an int32 start
@@ -53,4 +54,21 @@ SMX_HISTORY_FN bool history_present(const HistoryDev& h, int episode, int env, i
 // The four words of a present slot (only called when history_present said yes: the frame is in range).
 SMX_HISTORY_FN const double* history_row(const HistoryDev& h, int64_t frame, int slot) {
   return h.frames + ((size_t)frame * (size_t)h.num_social + (size_t)slot) * 4;
+}
+
+// ---- per-vehicle dimensions (smx_set_social_history_dims) ----
+// table: the handle's device copy of smx_social_dims (null: none bound, every vehicle has the sedan's box); slot: the
+// handle's triple per (env, vehicle), which the writers of a replayed slot's pose write beside it and every consumer
+// reads (agents' triples are the sedan's from the bind on and never written).
+struct HistoryDimsDev {
+  const double* table;  // [n_ids][3] length, width, height
+  double* slot;         // [num_envs * num_vehicles][3]
+  int32_t n_ids;
+};
+
+// The triple of the vehicle in `slot` of `frame` (only called when history_present said yes).  The bind-time check
+// found every id of the table below n_ids; an id outside it all the same reads row 0, never outside the table.
+SMX_HISTORY_FN const double* history_dims_row(const HistoryDev& h, const HistoryDimsDev& d, int64_t frame, int slot) {
+  const int32_t id = h.vehicle[(size_t)frame * (size_t)h.num_social + (size_t)slot];
+  return d.table + 3 * (size_t)((id >= 0 && id < d.n_ids) ? id : 0);
 }

@@ -379,6 +379,44 @@ inline int check_social_history_impl(const smx_config& c, const smx_map_tables& 
   return SMX_OK;
 }
 
+// ---- ... at each vehicle's own dimensions (smx_set_social_history_dims / smx_check_social_history_dims) ----
+// The caps bound every reach and pixel rectangle the kernels form from a triple (the largest default, the trailer, is
+// 10 x 2.5 x 4); the id check makes every lookup through a cell of the bound table an index inside dims_host.
+#define SMX_DIMS_MAX_PLANAR 25.0
+#define SMX_DIMS_MAX_HEIGHT 10.0
+// the largest vehicle id of a history's table, -1 when every cell is empty
+inline int32_t social_history_max_id(const smx_social_history& hs) {
+  int32_t max_id = -1;
+  const uint64_t cells = (uint64_t)hs.n_frames * (uint64_t)hs.num_social;
+  for (uint64_t i = 0; i < cells; ++i) max_id = hs.vehicle_host[i] > max_id ? hs.vehicle_host[i] : max_id;
+  return max_id;
+}
+// `max_id`: of the history the dimensions are bound to
+inline int check_social_dims_impl(const smx_social_dims& d, int32_t max_id, std::string& err) {
+  if (d.n_ids < 1) return refuse(err, "history dimensions: n_ids must be >= 1");
+  if (!d.dims_host) return refuse(err, "history dimensions: null table (dims_host)");
+  if (max_id >= d.n_ids)
+    return refuse(err, "history dimensions: the bound history holds vehicle id " + std::to_string(max_id) + ", the table has n_ids = " +
+                           std::to_string(d.n_ids) + " rows (a short table would be an out-of-bounds device read)");
+  for (int32_t id = 0; id < d.n_ids; ++id) {
+    const double* r = d.dims_host + (size_t)id * 3;
+    for (int q = 0; q < 3; ++q) {
+      const double cap = q < 2 ? SMX_DIMS_MAX_PLANAR : SMX_DIMS_MAX_HEIGHT;
+      if (!(std::isfinite(r[q]) && r[q] > 0.0 && r[q] <= cap))
+        return refuse(err, "history dimensions: vehicle " + std::to_string(id) + (q == 0 ? ", length " : (q == 1 ? ", width " : ", height ")) +
+                               std::to_string(r[q]) + " must be finite, > 0 and <= " + std::to_string((int)cap) + " m");
+    }
+  }
+  return SMX_OK;
+}
+inline int check_social_history_dims_impl(const smx_config& c, const smx_social_history& hs, const smx_social_dims& d, std::string& err) {
+  if (hs.num_social != c.num_social || hs.num_social <= 0)
+    return refuse(err, "history dimensions: the history has " + std::to_string(hs.num_social) + " slots, the configuration's num_social is " +
+                           std::to_string(c.num_social));
+  if (hs.n_frames < 1 || !hs.vehicle_host) return refuse(err, "history dimensions: the history has no table (n_frames / vehicle_host)");
+  return check_social_dims_impl(d, social_history_max_id(hs), err);
+}
+
 // ---- Frame stacking (smx_bind_frame_stack / smx_check_frame_stack) ----
 // bytes per agent of a stackable source, 0 with the reason in `err`: a row of smx_outputs by its SMX_OUT_* index — stackable,
 // its sensor on, its elements times the size of its dtype — or the image by SMX_STACK_SOURCE_RGB

@@ -102,6 +102,9 @@ struct KernelArgs {
   // traffic-history replay (smx_set_social_history; smx_history.h): history.vehicle null = none bound, the social slots are
   // the scripted lane followers.  Every branch on it is marked as the rare side.
   HistoryDev history;
+  // ... at each vehicle's own dimensions (smx_set_social_history_dims): dims.table null = none bound, every box is the
+  // sedan's.  dims.slot holds a triple per vehicle of the batch, written beside a replayed slot's pose.
+  HistoryDimsDev dims;
 };
 enum {
   SMX_DEVICE_BAD_LANE_ACTION = 1,  // a Lane action code outside -1..3 was met (and treated as "no action")
@@ -178,22 +181,23 @@ __device__ __forceinline__ double seg_point_dist2(double px, double py, double a
   return ex * ex + ey * ey;
 }
 
+// (box a: len x wid, box b: blen x bwid.  Two equal boxes: 0.5 d + 0.5 d is d exactly, the reach of one full diagonal.)
 __device__ inline bool boxes_within(double ax, double ay, double ah, double bx, double by, double bh, double len,
-                                    double wid, double leeway) {
+                                    double wid, double blen, double bwid, double leeway) {
   // broad phase: circumscribed circles
   double dx = ax - bx, dy = ay - by;
-  double reach = sqrt(len * len + wid * wid) + leeway;
+  double reach = 0.5 * sqrt(len * len + wid * wid) + 0.5 * sqrt(blen * blen + bwid * bwid) + leeway;
   if (dx * dx + dy * dy > reach * reach) return false;
   double cax[4], cay[4], cbx[4], cby[4];
   double sa, ca, sb, cb;
   sincos(ah, &sa, &ca);
   sincos(bh, &sb, &cb);
   box_corners(ax, ay, sa, ca, len, wid, cax, cay);
-  box_corners(bx, by, sb, cb, len, wid, cbx, cby);
+  box_corners(bx, by, sb, cb, blen, bwid, cbx, cby);
   double best = SMX_INF;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    if (point_in_box(cax[i], cay[i], bx, by, sb, cb, len, wid)) return true;
+    if (point_in_box(cax[i], cay[i], bx, by, sb, cb, blen, bwid)) return true;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
       best = fmin(best, seg_point_dist2(cax[i], cay[i], cbx[k], cby[k], cbx[(k + 1) & 3], cby[(k + 1) & 3]));
@@ -295,6 +299,35 @@ __device__ __forceinline__ bool history_slot_present(const KernelArgs& a, int en
   frame = history_frame(a.history, episode, env, env_ticks);
   return history_present(a.history, episode, env, frame, slot);
 }
+// The dimensions of the vehicle a present slot holds in `frame` (smx_set_social_history_dims), written wherever the
+// slot's pose is: a sensor sees the size of the vehicle whose pose it sees.  Nothing bound: nothing written.
+__device__ __forceinline__ void history_store_dims(const KernelArgs& a, size_t gid, int64_t frame, int slot) {
+  if (a.dims.table == nullptr) return;
+  const double* d = history_dims_row(a.history, a.dims, frame, slot);
+  double* w = a.dims.slot + gid * 3;
+  w[0] = d[0];
+  w[1] = d[1];
+  w[2] = d[2];
+}
+// Vehicle `gid`'s box as every consumer reads it: the slot's triple with dimensions bound, else the sedan's.
+struct VehBox {
+  double length, width, height;
+};
+// (`sized`: dimensions are bound.  The kernels the launch plan instantiates with and without them — smx_plan.h,
+// TickPlan::sized — pass their template argument; the others ask the argument block, marked as the rare side.)
+__device__ __forceinline__ VehBox vehicle_box(const KernelArgs& a, size_t gid, bool sized) {
+  VehBox b = {SMX_CHASSIS_LENGTH, SMX_CHASSIS_WIDTH, SMX_CHASSIS_HEIGHT};
+  if (sized) {
+    const double* d = a.dims.slot + gid * 3;
+    b.length = d[0];
+    b.width = d[1];
+    b.height = d[2];
+  }
+  return b;
+}
+__device__ __forceinline__ VehBox vehicle_box(const KernelArgs& a, size_t gid) {
+  return vehicle_box(a, gid, __builtin_expect(a.dims.table != nullptr, 0));
+}
 // The replayed vehicle's step, in the scripted step's place in the tick (before collisions and sensors): the pose and
 // speed of the frame this tick's observation belongs to — env_ticks + 1, smarts.py:261-262 —, copied word for word.
 // SMX_S_PREV_X / _Y as for the scripted vehicle.  The slot is alive because the last commit found it in this frame; if
@@ -315,6 +348,7 @@ __device__ __forceinline__ void history_vehicle_step(const KernelArgs& a, size_t
   SF(SMX_S_Y) = row[1];
   SF(SMX_S_HEADING) = row[2];
   SF(SMX_S_U) = row[3];
+  history_store_dims(a, gid, frame, slot);
 }
 
 // Scripted social vehicle (lane follower: no controller, no dynamics), on state words its caller has loaded:
@@ -3165,6 +3199,7 @@ __device__ __forceinline__ int history_respawn(const KernelArgs& a, size_t gid, 
   if (present) {
     const double* row = history_row(a.history, frame, slot);
     x = row[0], y = row[1], heading = row[2], speed = row[3];
+    history_store_dims(a, gid, frame, slot);
   }
   SF(SMX_S_X) = x;
   SF(SMX_S_Y) = y;
@@ -3479,12 +3514,31 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
         }
       }
       const double my_h = wrap_heading(s.heading);
+      const bool sized = __builtin_expect(a.dims.table != nullptr, 0);
+      if (sized && want_col) {
+        // Dimensions bound (smx_set_social_history_dims): the candidates again, in a pass of its own so that the loop
+        // above stays what it is without them.  The reach is the sedan's half diagonal (the observer is an agent) plus
+        // the mate's plus the leeway — boxes_within's own broad phase; between two agents the one full diagonal.
+        const double my_half_diag = 0.5 * sqrt(SMX_CHASSIS_LENGTH * SMX_CHASSIS_LENGTH + SMX_CHASSIS_WIDTH * SMX_CHASSIS_WIDTH);
+        cand = 0ull;
+        for (int j = 0; j < n_veh; ++j) {
+          if (j == slot) continue;
+          const SharedPose& q = env_pose[j];
+          if (!q.alive) continue;
+          const VehBox mb = vehicle_box(a, gid - slot + j, true);
+          const double dx = px - q.x, dy = py - q.y;
+          const double r = my_half_diag + 0.5 * sqrt(mb.length * mb.length + mb.width * mb.width) + SMX_COLLISION_LEEWAY;
+          if (!(dx * dx + dy * dy > r * r)) cand |= 1ull << j;
+        }
+      }
       // one Collision per collidee (smarts.py:1270-1291): every survivor is tested, not just the first hit
+      // (one call site for both: a second inlined copy of the box test made the kernel spill)
       while (cand != 0ull) {
         const int j = __ffsll((long long)cand) - 1;
         cand &= cand - 1ull;
         const SharedPose& q = env_pose[j];
-        if (boxes_within(px, py, my_h, q.x, q.y, q.heading, SMX_CHASSIS_LENGTH, SMX_CHASSIS_WIDTH,
+        const VehBox mb = vehicle_box(a, gid - slot + j, sized);  // (the observer is an agent: a sedan)
+        if (boxes_within(px, py, my_h, q.x, q.y, q.heading, SMX_CHASSIS_LENGTH, SMX_CHASSIS_WIDTH, mb.length, mb.width,
                          SMX_COLLISION_LEEWAY))
           collidee_mask |= 1ull << j;
       }
@@ -3586,12 +3640,13 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
           o.nb_pos[w * 3 + 0] = q.x;
           o.nb_pos[w * 3 + 1] = q.y;
           o.nb_pos[w * 3 + 2] = SMX_BASE_HEIGHT;
-          o.nb_box[w * 3 + 0] = (float)SMX_CHASSIS_LENGTH;
-          o.nb_box[w * 3 + 1] = (float)SMX_CHASSIS_WIDTH;
-          o.nb_box[w * 3 + 2] = (float)SMX_CHASSIS_HEIGHT;
+          const VehBox mb = vehicle_box(a, gid - slot + j);
+          o.nb_box[w * 3 + 0] = (float)mb.length;
+          o.nb_box[w * 3 + 1] = (float)mb.width;
+          o.nb_box[w * 3 + 2] = (float)mb.height;
           o.nb_heading[w] = (float)q.heading;
           o.nb_speed[w] = (float)q.speed;
-          // nearest_lane(nv.pose.point, radius=vehicle.length) (sensors.py:244-246)
+          // nearest_lane(nv.pose.point, radius=vehicle.length) (sensors.py:244-246: the EGO's length)
           int nl = (q.lane >= 0 && q.lane_dist < SMX_CHASSIS_LENGTH) ? q.lane : -1;
           o.nb_lane_id[w] = (int16_t)nl;
           o.nb_lane_index[w] = (int8_t)(nl >= 0 ? m.lane_index[nl] : -1);
@@ -3811,10 +3866,12 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
         const int v = small_quotient(e, rcp_k3), r = e - v * (K * 3), k = r / 3, q = r - k * 3;
         if (!stage.mode[v]) continue;
         const bool held = k < (int)stage.nb_kept[v];
-        const SharedPose& P = pose[small_quotient(v, rcp_veh) * n_veh + (held ? (int)stage.nb_list[v][k] : 0)];
+        const int mate = small_quotient(v, rcp_veh) * n_veh + (held ? (int)stage.nb_list[v][k] : 0);
+        const SharedPose& P = pose[mate];
         o.nb_pos[g0 * K * 3 + e] = held ? (q == 0 ? P.x : (q == 1 ? P.y : SMX_BASE_HEIGHT)) : 0.0;
-        o.nb_box[g0 * K * 3 + e] =
-            held ? (float)(q == 0 ? SMX_CHASSIS_LENGTH : (q == 1 ? SMX_CHASSIS_WIDTH : SMX_CHASSIS_HEIGHT)) : 0.0f;
+        float box = held ? (float)(q == 0 ? SMX_CHASSIS_LENGTH : (q == 1 ? SMX_CHASSIS_WIDTH : SMX_CHASSIS_HEIGHT)) : 0.0f;
+        if (__builtin_expect(a.dims.table != nullptr, 0) && held) box = (float)a.dims.slot[(g0 + mate) * 3 + q];
+        o.nb_box[g0 * K * 3 + e] = box;
       }
       for (int e = local; e < wg_veh * K; e += nth) {         // the scalar neighbour rows
         const int v = small_quotient(e, rcp_k), k = e - v * K;
@@ -3974,7 +4031,8 @@ struct OgmMate {
 __device__ __forceinline__ bool ogm_mate_footprint(const KernelArgs& a, const size_t og, const size_t total, const int W, const int H,
                                                    const double res, const double ex0, const double ey0, const double rx, const double ry,
                                                    const double fx, const double fy, OgmMate& q) {
-  const double hl = 0.5 * SMX_CHASSIS_LENGTH, hw = 0.5 * SMX_CHASSIS_WIDTH;
+  const VehBox box = vehicle_box(a, og);
+  const double hl = 0.5 * box.length, hw = 0.5 * box.width;
   const double vx = a.st.f64[(size_t)SMX_S_X * total + og], vy = a.st.f64[(size_t)SMX_S_Y * total + og];
   const double vh = wrap_heading(a.st.f64[(size_t)SMX_S_HEADING * total + og]);
   const double dx = vx - ex0, dy = vy - ey0;
@@ -4005,9 +4063,12 @@ __device__ __forceinline__ bool ogm_mate_footprint(const KernelArgs& a, const si
 }
 
 // ... drawn by the workgroup's lanes over the rectangle's pixels: VALUE where the pixel centre lies inside the chassis
+// of vehicle `og` (the rectangle is clamped to the view and walked whole, whatever the vehicle's size)
 template <int VALUE>
-__device__ __forceinline__ void ogm_draw_mate(unsigned char* tile, const OgmMate& q, const int W, const int H, const double res) {
-  const double hl = 0.5 * SMX_CHASSIS_LENGTH, hw = 0.5 * SMX_CHASSIS_WIDTH;
+__device__ __forceinline__ void ogm_draw_mate(const KernelArgs& a, const size_t og, unsigned char* tile, const OgmMate& q, const int W,
+                                              const int H, const double res) {
+  const VehBox box = vehicle_box(a, og);
+  const double hl = 0.5 * box.length, hw = 0.5 * box.width;
   for (int p = (int)threadIdx.x; p < q.n_px; p += SMX_BLOCK) {
     const int r = q.r0 + p / q.bw, col = q.c0 + p % q.bw;
     const double py = (0.5 * H - (r + 0.5)) * res - q.cy;
@@ -4050,9 +4111,10 @@ __device__ __forceinline__ void ogm_role(const KernelArgs& a, const int block) {
     unsigned long long todo = __ballot(in_view);
     __syncthreads();
     while (todo != 0ull) {  // uniform
-      const OgmMate q = mates[__ffsll((long long)todo) - 1];
+      const int idx = __ffsll((long long)todo) - 1;
+      const OgmMate q = mates[idx];
       todo &= todo - 1ull;
-      ogm_draw_mate<255>(tile, q, W, H, res);
+      ogm_draw_mate<255>(a, (size_t)env * n_veh + base + idx, tile, q, W, H, res);
     }
     __syncthreads();  // before the stage is reused (envs of more than 64 vehicles do not exist, but the loop is general)
   }
@@ -4092,7 +4154,10 @@ __device__ __forceinline__ double readlane_f64(double v, int src) {
 // envs is full; the footprints in view are then drawn two at a time, each by a half wavefront of 8 rows x 4 columns
 // (a car ahead is 3 x 6 pixels at 0.78 m per pixel: one step), its record fetched from the lane that holds it with
 // ds_bpermute.  390 -> 1xx vector instructions per tile (a third of the headline tick's were this kernel's).
-template <int OBS>
+// (SIZED: per-vehicle dimensions are bound, smx_set_social_history_dims — a compile-time choice of the launch plan's: as a
+// branch on the bound pointer the extents cost the kernel without them ten registers and a wavefront per SIMD,
+// profiles/r17_vehicle_dims_resources.txt)
+template <int OBS, bool SIZED>
 __global__ void __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(SMX_OGM_WAVES * 64) k_ogm_env(const KernelArgs a) {
   SMX_TSTAMP(span0);
   extern __shared__ __align__(16) unsigned char tiles[];  // [SMX_OGM_WAVES][OBS][H * W]
@@ -4129,10 +4194,13 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(SMX
   const double res = c.ogm_resolution;
   const double inv_res = 1.0 / res;  // for the pixel RECTANGLES only (an enumeration bound with a margin on every
                                      // side); the pixel test itself keeps the oracle's arithmetic
-  const double hl = 0.5 * SMX_CHASSIS_LENGTH, hw = 0.5 * SMX_CHASSIS_WIDTH;
   const int half = lane >> 5, in_half = lane & 31;
   const int mate = OBS == 2 ? in_half : lane;
   const int mate_clamped = min(mate, n_veh - 1);  // (every lane computes; lanes past the env's vehicles are masked below)
+  // this lane's mate's half extents: the sedan's, or with dimensions bound (smx_set_social_history_dims) its own — a
+  // drawing step then fetches them from the lane that holds the footprint, as it fetches the rest of the record
+  const VehBox mate_box = vehicle_box(a, (size_t)env * n_veh + mate_clamped, SIZED);
+  const double hl = 0.5 * mate_box.length, hw = 0.5 * mate_box.width;
   const int lr = in_half >> 2, lc = in_half & 3;  // this lane's pixel of a drawing step: 8 rows x 4 columns per half
   // pixel centre (r, col): x = (col + 0.5 - W/2) res, y = (H/2 - (r + 0.5)) res; the sums in front of `res` are
   // exact in any order (integers and halves), so the constants are folded
@@ -4187,6 +4255,8 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(SMX
       const double qcx = __shfl(cx, src), qcy = __shfl(cy, src);
       const double qvfx = __shfl(vfx, src), qvfy = __shfl(vfy, src), qvrx = __shfl(vrx, src), qvry = __shfl(vry, src);
       const int qc0 = __shfl(c0, src), qr0 = __shfl(r0, src), qbw = __shfl(bw, src), qbh = __shfl(bh, src);
+      double qhl = 0.5 * SMX_CHASSIS_LENGTH, qhw = 0.5 * SMX_CHASSIS_WIDTH;
+      if constexpr (SIZED) qhl = __shfl(hl, src), qhw = __shfl(hw, src);
       unsigned char* dst_tile = tile + (OBS == 2 ? (src >> 5) * bytes : 0);
       const int bh_max = max(__builtin_amdgcn_readlane(bh, s0), __builtin_amdgcn_readlane(bh, s1));
       const int bw_max = max(__builtin_amdgcn_readlane(bw, s0), __builtin_amdgcn_readlane(bw, s1));
@@ -4200,7 +4270,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(SMX
           const int r = qr0 + dr, col = qc0 + dc;
           const double py = (row_bias - (double)r) * res - qcy;
           const double px = ((double)col + col_bias) * res - qcx;
-          if (drawing && dr < qbh && dc < qbw && fabs(px * qvfx + py * qvfy) <= hl && fabs(px * qvrx + py * qvry) <= hw)
+          if (drawing && dr < qbh && dc < qbw && fabs(px * qvfx + py * qvfy) <= qhl && fabs(px * qvrx + py * qvry) <= qhw)
             dst_tile[r * W + col] = 255;
         }
       }
@@ -4349,12 +4419,14 @@ __device__ __forceinline__ void rgb_role(const KernelArgs& a, const int block) {
       unsigned long long todo = __ballot(in_view);
       __syncthreads();
       while (todo != 0ull) {  // uniform
-        const OgmMate q = mates[__ffsll((long long)todo) - 1];
+        const int idx = __ffsll((long long)todo) - 1;
+        const OgmMate q = mates[idx];
         todo &= todo - 1ull;
+        const size_t og = (size_t)env * n_veh + base + idx;
         if (cls == 2)
-          ogm_draw_mate<2>(tile, q, W, H, res);
+          ogm_draw_mate<2>(a, og, tile, q, W, H, res);
         else
-          ogm_draw_mate<3>(tile, q, W, H, res);
+          ogm_draw_mate<3>(a, og, tile, q, W, H, res);
       }
       __syncthreads();  // the stage is reused, and the next class goes on top of this one
     }
@@ -4387,11 +4459,15 @@ __device__ __forceinline__ void rgb_role(const KernelArgs& a, const int block) {
 // =================================================================================
 struct LidarPose {
   double x, y, fx, fy;  // centre, forward axis
-  int alive;
+  int slot;             // its slot in the env (the compacted list's order is not the env's)
 };
 
+// (SIZED: per-vehicle dimensions, smx_set_social_history_dims — 1 bound, 0 not: the launches of its own, for which the
+// launch plan picks the instantiation; -1: the role inside k_sensors / k_first, which asks the argument block)
+template <int SIZED>
 __device__ __forceinline__ void lidar_role(const KernelArgs& a, const int block) {
   __shared__ LidarPose mates[SMX_BLOCK];
+  const bool sized = SIZED < 0 ? __builtin_expect(a.dims.table != nullptr, 0) : SIZED != 0;
   const smx_config& c = a.cfg;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
   const size_t gid = (size_t)block;
@@ -4403,7 +4479,8 @@ __device__ __forceinline__ void lidar_role(const KernelArgs& a, const int block)
   const int env = (int)(gid / n_veh);
   const int slot = (int)(gid - (size_t)env * n_veh);
   // env-mates that a ray can reach at all (|ray| = max_distance; a chassis box lies within 2.1 m of
-  // its centre), compacted into LDS by ballot / prefix count — the order does not matter for a min
+  // its centre — with dimensions bound, smx_set_social_history_dims, within the mate's own half diagonal),
+  // compacted into LDS by ballot / prefix count — the order does not matter for a min
   __shared__ int n_mates;
   {
     const double ex = SF(SMX_S_X), ey = SF(SMX_S_Y);
@@ -4411,14 +4488,20 @@ __device__ __forceinline__ void lidar_role(const KernelArgs& a, const int block)
     bool keep = false;
     LidarPose p;
     p.x = p.y = p.fx = p.fy = 0.0;
-    p.alive = 1;
+    p.slot = (int)threadIdx.x;
     if ((int)threadIdx.x < n_veh && (int)threadIdx.x != slot) {
       const size_t og = (size_t)env * n_veh + threadIdx.x;
       if (a.st.flags[og] & SMX_F_ALIVE) {
         p.x = a.st.f64[(size_t)SMX_S_X * total + og];
         p.y = a.st.f64[(size_t)SMX_S_Y * total + og];
         const double dx = p.x - ex, dy = p.y - ey;
-        if (dx * dx + dy * dy <= reach * reach) {
+        double mate_reach = reach;
+        if (sized) {
+          const VehBox mb = vehicle_box(a, og, true);
+          // (+ 0.12 m: the slack the sedan's 2.1 has over its 1.98 — a corner exactly at max_distance must not be lost to rounding)
+          mate_reach = c.lidar_max_distance + 0.5 * sqrt(mb.length * mb.length + mb.width * mb.width) + 0.12;
+        }
+        if (dx * dx + dy * dy <= mate_reach * mate_reach) {
           const double h = wrap_heading(a.st.f64[(size_t)SMX_S_HEADING * total + og]);
           p.fx = -sin(h);
           p.fy = cos(h);
@@ -4444,7 +4527,15 @@ __device__ __forceinline__ void lidar_role(const KernelArgs& a, const int block)
     }
     for (int j = 0; j < mates_n; ++j) {
       const LidarPose p = mates[j];
-      const double relx = ox - p.x, rely = oy - p.y, relz = oz - bz;
+      double mhl = hl, mhw = hw, mhh = hh, mbz = bz;
+      if (sized) {
+        // the mate's own half length and half width; vertically the box keeps the sedan's underside, SMX_BASE_HEIGHT
+        // + 0.1, and rises by the vehicle's height (a stated deviation: the reference centres a BoxChassis box on z = 0)
+        const VehBox mb = vehicle_box(a, (size_t)env * n_veh + p.slot, true);
+        mhl = 0.5 * mb.length, mhw = 0.5 * mb.width, mhh = 0.5 * mb.height;
+        mbz = bz + (mhh - hh);  // (a sedan-high mate: bz itself)
+      }
+      const double relx = ox - p.x, rely = oy - p.y, relz = oz - mbz;
       // slabs along the box axes: forward f, right r = (f.y, -f.x), up
       double tmin = 0.0, tmax = 1.0;
       bool miss = false;
@@ -4454,15 +4545,15 @@ __device__ __forceinline__ void lidar_role(const KernelArgs& a, const int block)
         if (ax == 0) {
           o = relx * p.fx + rely * p.fy;
           d = dx * p.fx + dy * p.fy;
-          half = hl;
+          half = mhl;
         } else if (ax == 1) {
           o = relx * p.fy + rely * (-p.fx);
           d = dx * p.fy + dy * (-p.fx);
-          half = hw;
+          half = mhw;
         } else {
           o = relz;
           d = dz;
-          half = hh;
+          half = mhh;
         }
         if (d == 0.0) {
           if (fabs(o) > half) miss = true;
@@ -4510,7 +4601,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_sensors(const KernelArgs a) {
   } else if (b < a.wp_blocks + a.obs_blocks) {
     observe_role(a, b - a.wp_blocks);
   } else if (b < a.wp_blocks + a.obs_blocks + a.lidar_blocks) {
-    lidar_role(a, b - a.wp_blocks - a.obs_blocks);
+    lidar_role<-1>(a, b - a.wp_blocks - a.obs_blocks);
   } else {
     ogm_role(a, b - a.wp_blocks - a.obs_blocks - a.lidar_blocks);
   }
@@ -4593,7 +4684,7 @@ __device__ __forceinline__ void first_role(const KernelArgs& a, const int block)
   SMX_TACC_ALL(59, tk2, tk3);
   if ((c.sensors & SMX_SENSOR_LIDAR) && a.lidar_blocks != 0)  // (0: the reset pass launched k_lidar for the new vehicles)
     for (size_t gid = g0; gid < g1; ++gid) {
-      lidar_role(a, (int)gid);
+      lidar_role<-1>(a, (int)gid);
       __syncthreads();  // the role's LDS block is reused by the next vehicle
     }
   __threadfence();
@@ -5443,12 +5534,14 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_observe(const KernelArgs a) {
   SMX_TSTAMP(span1);
   SMX_TSPAN(5, span0, span1);
 }
-__global__ void __launch_bounds__(SMX_BLOCK) k_lidar(const KernelArgs a) { lidar_role(a, (int)blockIdx.x); }
+template <bool SIZED>
+__global__ void __launch_bounds__(SMX_BLOCK) k_lidar(const KernelArgs a) { lidar_role<SIZED ? 1 : 0>(a, (int)blockIdx.x); }
 // The lidar of the reset pass on large batches: almost no vehicle is new in a given tick, and when an env restarts
 // all its vehicles are — neighbours in memory.  Workgroup w looks at the vehicles v = w (mod gridDim.x), 64 flags per
 // load and ballot, and runs the lidar role for the new ones it finds: an env's 64 new vehicles land in 64 different
 // workgroups instead of one after the other in k_first's, and a tick without restarts pays a few microseconds.
 #define SMX_LIDAR_FIRST_BLOCKS 1024
+template <bool SIZED>
 __global__ void __launch_bounds__(SMX_BLOCK) k_lidar_first(const KernelArgs a) {
   const size_t total = (size_t)a.cfg.num_envs * a.cfg.num_vehicles;
   const size_t stride = (size_t)gridDim.x;
@@ -5459,7 +5552,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_lidar_first(const KernelArgs a) {
     while (fresh != 0ull) {  // uniform in the (one-wavefront) workgroup
       const int l = __ffsll((long long)fresh) - 1;
       fresh &= fresh - 1ull;
-      lidar_role(a, (int)(base + (size_t)l * stride));
+      lidar_role<SIZED ? 1 : 0>(a, (int)(base + (size_t)l * stride));
       __syncthreads();  // the role's LDS block is reused
     }
   }
@@ -5598,6 +5691,9 @@ struct smx_handle_s {
   uint64_t rgb_count;
   void* history_blob;  // smx_set_social_history: device copy of the table, frames | vehicle ids (null: none bound)
   HistoryDev history;  // ... and what the kernels get (vehicle null: none bound)
+  int32_t history_max_id;  // the largest vehicle id of the bound table (-1: every cell empty)
+  void* dims_blob;      // smx_set_social_history_dims: device copy of the table | the triple per vehicle (null: none bound)
+  HistoryDimsDev dims;  // ... and what the kernels get (table null: none bound)
   struct StackBinding {  // smx_bind_frame_stack: one caller-owned stack per (source, layout)
     int32_t source, layout;
     uint8_t* dst;
@@ -5617,6 +5713,13 @@ struct smx_handle_s {
 };
 
 static thread_local std::string g_create_err;  // the reason of this thread's last failed smx_create
+
+// the per-vehicle dimensions go with the history they were checked against (the caller has waited for the device)
+static void drop_social_dims(smx_handle h) {
+  if (h->dims_blob) (void)hipFree(h->dims_blob);
+  h->dims_blob = nullptr;
+  h->dims = HistoryDimsDev{};
+}
 
 static int fail(smx_handle h, int code, const std::string& msg) {
   if (h) h->err = msg;
@@ -5743,6 +5846,7 @@ static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_sta
   in.slow_parity = h->alive_parity;
   in.frame_stack_bound = !h->stacks.empty();
   in.guard_bound = h->guard_out != nullptr;
+  in.dims_bound = h->dims.table != nullptr;
   in.history_bound = h->history.vehicle != nullptr;
   return in;
 }
@@ -5802,6 +5906,7 @@ extern "C" int smx_load_map(smx_handle h, const smx_map_tables* t) {
   if (h->history_blob) (void)hipFree(h->history_blob);
   h->history_blob = nullptr;
   h->history = HistoryDev{};
+  drop_social_dims(h);
   if (!h->alive_blob) {  // the tick's alive list (large batches) + its counters, the env groups with new vehicles (alive_layout)
     const size_t n = alive_layout(h->cfg).size;
     SMX_HIP(hipMalloc((void**)&h->alive_blob, n * sizeof(int32_t)));
@@ -6096,6 +6201,7 @@ extern "C" int smx_set_social_history(smx_handle h, const smx_social_history* hi
   if (h->history_blob) (void)hipFree(h->history_blob);
   h->history_blob = nullptr;
   h->history = HistoryDev{};
+  drop_social_dims(h);
   // the alive list k_tail built for the next tick was built under the other rule (smx_plan.h: tail_builds_list)
   h->list_ready = false;
   if (!hist) return SMX_OK;
@@ -6115,6 +6221,45 @@ extern "C" int smx_set_social_history(smx_handle h, const smx_social_history* hi
   d.rows = hist->rows;
   d.num_envs = h->cfg.num_envs;
   h->history = d;
+  h->history_max_id = social_history_max_id(*hist);
+  return SMX_OK;
+}
+
+extern "C" int smx_check_social_history_dims(const smx_config* cfg, const smx_social_history* hist, const smx_social_dims* dims,
+                                             char* err, uint64_t err_len) {
+  std::string msg;
+  const int rc = (cfg && hist && dims) ? check_social_history_dims_impl(*cfg, *hist, *dims, msg) : refuse(msg, "null config / history / dims");
+  return report(rc, msg, err, err_len);
+}
+
+extern "C" int smx_set_social_history_dims(smx_handle h, const smx_social_dims* dims) {
+  if (!h) return SMX_ERR_INVALID;
+  if (dims) {
+    if (h->history.vehicle == nullptr) return fail(h, SMX_ERR_STATE, "smx_set_social_history_dims needs a bound history (smx_set_social_history)");
+    std::string msg;
+    const int rc = check_social_dims_impl(*dims, h->history_max_id, msg);
+    if (rc != SMX_OK) return fail(h, rc, msg);
+  }
+  SMX_HIP(hipSetDevice(h->device));
+  SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
+  drop_social_dims(h);
+  if (!dims) return SMX_OK;
+  // table | a triple per vehicle of the batch, the sedan's until a replayed slot's pose is written (agents: for good)
+  const size_t table_words = (size_t)dims->n_ids * 3, total = (size_t)h->cfg.num_envs * (size_t)h->cfg.num_vehicles;
+  std::vector<double> host(table_words + total * 3);
+  std::copy(dims->dims_host, dims->dims_host + table_words, host.begin());
+  for (size_t g = 0; g < total; ++g) {
+    host[table_words + g * 3 + 0] = SMX_CHASSIS_LENGTH;
+    host[table_words + g * 3 + 1] = SMX_CHASSIS_WIDTH;
+    host[table_words + g * 3 + 2] = SMX_CHASSIS_HEIGHT;
+  }
+  SMX_HIP(hipMalloc(&h->dims_blob, host.size() * sizeof(double)));
+  SMX_HIP(hipMemcpy(h->dims_blob, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice));
+  HistoryDimsDev d;
+  d.table = (const double*)h->dims_blob;
+  d.slot = (double*)h->dims_blob + table_words;
+  d.n_ids = dims->n_ids;
+  h->dims = d;
   return SMX_OK;
 }
 
@@ -6296,8 +6441,8 @@ static void launch_grids(smx_handle h, const TickPlan& p, const KernelArgs& k, h
   switch (p.ogm) {
     case Ogm::NONE:
     case Ogm::IN_SENSORS: break;
-    case Ogm::ENV2: hipLaunchKernelGGL(k_ogm_env<2>, dim3((unsigned)h->cfg.num_envs), dim3(SMX_OGM_WAVES * 64), p.ogm_lds, s, k); break;
-    case Ogm::ENV1: hipLaunchKernelGGL(k_ogm_env<1>, dim3((unsigned)h->cfg.num_envs), dim3(SMX_OGM_WAVES * 64), p.ogm_lds, s, k); break;
+    case Ogm::ENV2: hipLaunchKernelGGL((p.sized ? k_ogm_env<2, true> : k_ogm_env<2, false>), dim3((unsigned)h->cfg.num_envs), dim3(SMX_OGM_WAVES * 64), p.ogm_lds, s, k); break;
+    case Ogm::ENV1: hipLaunchKernelGGL((p.sized ? k_ogm_env<1, true> : k_ogm_env<1, false>), dim3((unsigned)h->cfg.num_envs), dim3(SMX_OGM_WAVES * 64), p.ogm_lds, s, k); break;
     case Ogm::PER_OBSERVER: launch(k_ogm, total, p.ogm_lds, s, k); break;
   }
   if (p.dagm) launch(k_dagm, total, p.dagm_bytes, s, k);
@@ -6326,7 +6471,7 @@ static void observation_pass(smx_handle h, const TickPlan& p, const KernelArgs& 
     (void)hipEventRecord(h->ev_fork_grid, stream);
     (void)hipStreamWaitEvent(s_grid, h->ev_fork_grid, 0);
     launch_grids(h, p, k, s_grid);
-    if (p.lidar == Lidar::SIDE) launch(k_lidar, p.lidar_blocks, 0, s_grid, k);
+    if (p.lidar == Lidar::SIDE) launch(p.sized ? k_lidar<true> : k_lidar<false>, p.lidar_blocks, 0, s_grid, k);
   }
   // the scan's halves as two launches in the large form, on two streams when forked: path seeds (-> waypoint kernels) on
   // the caller's, road facts (-> observe) on side 1; each half appends to its own slow list
@@ -6392,7 +6537,7 @@ static void observation_pass(smx_handle h, const TickPlan& p, const KernelArgs& 
       break;
   }
   if (!p.small()) launch(k_observe, p.obs_blocks, 0, s_obs, k);
-  if (p.lidar == Lidar::CALLER) launch(k_lidar, p.lidar_blocks, 0, stream, k);
+  if (p.lidar == Lidar::CALLER) launch(p.sized ? k_lidar<true> : k_lidar<false>, p.lidar_blocks, 0, stream, k);
   if (p.fork) {
     // (each side stream joins the caller's directly: chaining side 0 through side 1 puts one more hop behind the
     // last kernel when k_observe ends the tick — 1 % late in a run)
@@ -6453,7 +6598,7 @@ static int tail_and_reset_pass(smx_handle h, const TickPlan& p, const KernelArgs
     if (p.road_waypoints)  // before k_first clears SMX_F_FIRST
       launch(k_road_waypoints, smx_blocks(total * SMX_RW_LANE_CAP), 0, stream, r);
     if (p.lidar_first) {
-      launch(k_lidar_first, (unsigned)std::min<size_t>(SMX_LIDAR_FIRST_BLOCKS, total), 0, stream, r);
+      launch(p.sized ? k_lidar_first<true> : k_lidar_first<false>, (unsigned)std::min<size_t>(SMX_LIDAR_FIRST_BLOCKS, total), 0, stream, r);
       r.lidar_blocks = 0;
     }
     r.walk_new = p.first_walks_new ? 1 : 0;
@@ -6514,6 +6659,7 @@ static KernelArgs kernel_args(smx_handle h, const TickPlan& p, const int8_t* act
   a.guard = h->guard_out;
   a.guard_box = h->guard_box;
   a.history = h->history;
+  a.dims = h->dims;
   a.wp_blocks = (int)p.wp_blocks;
   a.obs_blocks = (int)p.obs_blocks;
   a.lidar_blocks = (int)p.lidar_blocks;
@@ -6814,6 +6960,7 @@ extern "C" void smx_destroy(smx_handle h) {
   if (h->missions_blob) (void)hipFree(h->missions_blob);
   if (h->goals_blob) (void)hipFree(h->goals_blob);
   if (h->history_blob) (void)hipFree(h->history_blob);
+  if (h->dims_blob) (void)hipFree(h->dims_blob);
   for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ph_pool) (void)hipEventDestroy(e);
   delete h;

@@ -80,6 +80,7 @@ struct PlanInputs {
   bool frame_stack_bound;  // smx_bind_frame_stack holds at least one buffer
   bool guard_bound;        // smx_set_guard holds a buffer: the state guard is on
   bool history_bound;      // smx_set_social_history holds a table: the social slots replay it
+  bool dims_bound;         // smx_set_social_history_dims holds a table: ... at each vehicle's own dimensions
 };
 
 enum class AliveList : uint8_t { NONE, CARRIED, BUILD };  // BUILD: k_alive_list ahead of the tick
@@ -155,6 +156,9 @@ struct TickPlan {
   // the state guard (smx_set_guard): the GUARD instantiations of the control kernels, k_reset and k_tail in the places of
   // the plain ones — the same launches on the same streams, no kernel and no edge more
   bool guard;
+  // per-vehicle dimensions (smx_set_social_history_dims): the SIZED instantiations of k_ogm_env, k_lidar and k_lidar_first
+  // in the places of the plain ones — the same launches on the same streams; every other reader branches on the pointer
+  bool sized;
   bool tail_builds_list;  // k_tail builds the next tick's alive list
   bool tail_grids;        // ... and the new vehicles' grid tiles
   bool reset_pass, lidar_first, first_walks_new;
@@ -326,6 +330,7 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
   }
   p.frame_stack = c.frame_stack > 0 && in.frame_stack_bound;
   p.guard = in.guard_bound;
+  p.sized = in.dims_bound;
   p.ego_centric = (c.sensors & SMX_SENSOR_EGO_CENTRIC) != 0;
   if (p.ego_centric) {
     const size_t apb = SMX_BLOCK / SMX_EC_TEAM;

@@ -612,7 +612,8 @@ class BatchedSim:
         nat.check(self.lib, self.handle, rc, "smx_set_guard")
         self.out["guard"] = guard
 
-    def set_traffic_history(self, table, start_frames: Optional[torch.Tensor] = None, replaced: Optional[torch.Tensor] = None):
+    def set_traffic_history(self, table, start_frames: Optional[torch.Tensor] = None, replaced: Optional[torch.Tensor] = None,
+                            dims: bool = False):
         """Bind a recorded traffic history (``smx_set_social_history``; ``smarts_amd.traffic_history``): from the next
         pass on the social slots take pose, speed and presence from ``table`` (a ``TrafficHistoryTable`` with
         ``num_social`` slots) instead of the scripted lane follower.  ``start_frames``: int32 ``[R, E]`` on the sim's
@@ -620,12 +621,16 @@ class BatchedSim:
         safe, frames outside the table are empty); ``None`` = one row of zeros.  ``replaced``: int32 ``[R, E]``, the
         vehicle id hidden in that env (an agent stands in for it; see ``table.spawn_of``), -1 for none; ``None`` = nothing
         hidden.  Both tensors stay the caller's and are read by every pass: rewriting them in place takes effect with
-        the next tick (``include/smx.h`` says how presence follows).  ``table=None`` unbinds.  Refused with the
+        the next tick (``include/smx.h`` says how presence follows).  ``dims=True`` also binds ``table.device_dims()``
+        (``smx_set_social_history_dims``): collisions, ``nb_box``, OGM, RGB and lidar then see every replayed vehicle at
+        its own size — the dataset's, or its type's default; off, every one has the sedan's box.  ``set_history_dims``
+        switches that while the history stays bound.  ``table=None`` unbinds.  Refused with the
         library's reason (``SmxError``): a slot count other than ``num_social``, ``social_model="idm"``, a row of a
         present vehicle that is not finite or lies outside the map's grids."""
         if table is None:
             nat.check(self.lib, self.handle, self.lib.smx_set_social_history(self.handle, None), "smx_set_social_history")
             self.traffic_history = self.history_start_frames = self.history_replaced = None
+            self.history_dims = False
             return
         E = self.E
         if start_frames is None:
@@ -648,7 +653,26 @@ class BatchedSim:
         nat.check(self.lib, self.handle, self.lib.smx_set_social_history(self.handle, C.byref(hs)), "smx_set_social_history")
         # (the library reads the two tensors in every pass: they live as long as the binding)
         self.traffic_history, self.history_start_frames, self.history_replaced = table, start_frames, replaced
+        self.history_dims = False  # (binding a history drops the dimensions of the one before)
+        if dims:
+            self.set_history_dims(True)
 
+    def set_history_dims(self, on: bool):
+        """Bind (``True``) the bound history's ``device_dims()`` or unbind them (``False``: the sedan's box again from the
+        next tick), ``smx_set_social_history_dims``."""
+        if not on:
+            nat.check(self.lib, self.handle, self.lib.smx_set_social_history_dims(self.handle, None), "smx_set_social_history_dims")
+            self.history_dims = False
+            return
+        if self.traffic_history is None:
+            raise ValueError("set_history_dims needs a bound traffic history")
+        table = np.ascontiguousarray(self.traffic_history.device_dims(), dtype=np.float64)
+        sd = nat.SmxSocialDims()
+        sd.dims_host, sd.n_ids = table.ctypes.data, int(table.shape[0])
+        nat.check(self.lib, self.handle, self.lib.smx_set_social_history_dims(self.handle, C.byref(sd)), "smx_set_social_history_dims")
+        self.history_dims = True
+
+    history_dims = False
     traffic_history = None
     history_start_frames = None
     history_replaced = None

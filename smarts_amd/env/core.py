@@ -136,12 +136,15 @@ class BatchCore:
                  num_social: int = 0, vias: Optional[Dict[str, Sequence]] = None, social_model: str = "constant",
                  missions: Optional[Dict[str, Any]] = None, spawns: str = "reference", shuffle_scenarios: bool = True,
                  ego_centric: bool = False, state_guard: bool = False,
-                 state_guard_margin: float = nat.GUARD_MARGIN_DEFAULT, traffic_history=None, history_start_frames=None):
+                 state_guard_margin: float = nat.GUARD_MARGIN_DEFAULT, traffic_history=None, history_start_frames=None,
+                 history_dims: bool = False):
         """``traffic_history``: a ``smarts_amd.traffic_history.TrafficHistoryTable`` or the path of a converted dataset
         (SQLite): the ``num_social`` slots replay it (``BatchedSim.set_traffic_history``) and are named
         ``history-vehicle-<id>`` in the observations, the reference provider's prefix.  ``history_start_frames``: int
         ``[R, E]`` (or ``[E]``), the table frame at which episode ``k`` of env ``e`` starts (row ``k mod R``); ``None`` =
-        every env replays from frame 0.
+        every env replays from frame 0.  ``history_dims``: replay every vehicle at its own dimensions
+        (``BatchedSim.set_traffic_history(dims=True)``): a neighbour's ``bounding_box`` is then the table's
+        ``resolved_dimensions``; off, the sedan's box.
         ``state_guard`` / ``state_guard_margin``: ``SimConfig``'s (the state guard, include/smx.h smx_set_guard):
         ``info[agent]["guard"]`` then holds the agent's guard byte whenever it is non-zero.  One exception: the infos
         ``ParallelEnv.step`` returns for an env that restarted inside the launch (``auto_reset``) describe the finishing
@@ -233,9 +236,13 @@ class BatchCore:
             if start.shape[1:] != (num_envs,):
                 raise ValueError(f"history_start_frames must have shape [R, {num_envs}] or [{num_envs}]")
             self.sim.set_traffic_history(table, torch.from_numpy(np.ascontiguousarray(start)).to(self.sim.device))
+            if history_dims:
+                self.sim.set_history_dims(True)
             self.traffic_history = table
         elif history_start_frames is not None:
             raise ValueError("history_start_frames needs traffic_history")
+        elif history_dims:
+            raise ValueError("history_dims needs traffic_history")
         road_ids = [self.cm.road_ids[r] for r in self.cm.lane_road]
         vehicle_names = self.agent_ids + [f"social-{k}" for k in range(num_social)]
         self.builder = ObservationBuilder(

@@ -52,6 +52,7 @@ class HiWayEnv:
         state_guard_margin: float = 1000.0,
         traffic_history=None,
         history_start_frames=None,
+        history_dims: bool = False,
     ):
         self._log = logging.getLogger(self.__class__.__name__)
         if not headless or envision_record_data_replay_path or envision_endpoint:
@@ -99,7 +100,12 @@ class HiWayEnv:
         # traffic-history replay (smarts_amd.traffic_history; the reference's TrafficHistoryProvider): a
         # TrafficHistoryTable or the path of a converted dataset, replayed by the num_social slots; the table frame at
         # which this env's episode k starts (an int, or a sequence used cyclically over the episodes; None = frame 0)
+        # history_dims: every replayed vehicle at its own dimensions (BatchedSim.set_traffic_history(dims=True)); off by
+        # default: the sedan's box
         self._traffic_history = traffic_history
+        self._history_dims = bool(history_dims)
+        if self._history_dims and traffic_history is None:
+            raise ValueError("history_dims needs traffic_history")
         if history_start_frames is not None and traffic_history is None:
             raise ValueError("history_start_frames needs traffic_history")
         self._history_start_frames = None if history_start_frames is None else \
@@ -137,7 +143,7 @@ class HiWayEnv:
                 self._waypoint_window, self._num_social, self._social_model, repr(self._vias), repr(self._missions),
                 self._spawns, self._shuffle_scenarios, self._state_guard, self._state_guard_margin,
                 self._traffic_history if isinstance(self._traffic_history, (str, type(None))) else id(self._traffic_history),
-                None if self._history_start_frames is None else len(self._history_start_frames))
+                None if self._history_start_frames is None else len(self._history_start_frames), self._history_dims)
 
     def seed(self, seed: int) -> int:
         """hiway_env.py:204-214.  Takes effect at the next ``reset`` that (re)builds the spawn table."""
@@ -159,7 +165,7 @@ class HiWayEnv:
                                    num_social=self._num_social, vias=self._vias, social_model=self._social_model,
                                    missions=self._missions, spawns=self._spawns, shuffle_scenarios=self._shuffle_scenarios,
                                    state_guard=self._state_guard, state_guard_margin=self._state_guard_margin,
-                                   traffic_history=self._traffic_history,
+                                   traffic_history=self._traffic_history, history_dims=self._history_dims,
                                    history_start_frames=None if self._history_start_frames is None
                                    else np.asarray(self._history_start_frames, dtype=np.int32).reshape(-1, 1))
         return self._core

@@ -42,6 +42,7 @@ class ParallelEnv:
         # every env replays its own window of the shared traffic history: column e holds env e's start frames
         starts = [e._history_start_frames for e in envs]
         self._history_start_frames = None if starts[0] is None else np.asarray(starts, dtype=np.int32).T
+        self._history_dims = self._proto._history_dims  # (part of the envs' signature: they agree on it)
         self._num_envs = len(envs)
         self._auto_reset = auto_reset
         self._device = device
@@ -69,7 +70,8 @@ class ParallelEnv:
                                num_social=p._num_social, vias=p._vias, social_model=p._social_model, missions=p._missions,
                                spawns=p._spawns, shuffle_scenarios=p._shuffle_scenarios,
                                state_guard=p._state_guard, state_guard_margin=p._state_guard_margin,
-                               traffic_history=p._traffic_history, history_start_frames=self._history_start_frames)
+                               traffic_history=p._traffic_history, history_start_frames=self._history_start_frames,
+                               history_dims=self._history_dims)
         self._seed = seed
         return [seed + i for i in range(self._num_envs)]
 

@@ -17,8 +17,12 @@ between), here as there.
 Deviations from the reference, all stated in DESIGN.md section 5:
  - a window starts at a frame, i.e. at a multiple of ``dt`` (``frame_of`` raises otherwise); the reference's
    ``start_time`` is any non-negative float;
- - every replayed vehicle has the sedan's box on the device; the per-vehicle ``length, width, height`` kept here are
-   host metadata that nothing on the device reads;
+ - the per-vehicle dimensions are opt-in (``BatchedSim.set_traffic_history(..., dims=True)``): ``device_dims()`` applies
+   the provider's rule — the dataset's ``length, width, height``, or where it has none (``None``, 0, -1) the default of
+   the vehicle's type (``traffic_history_provider.py:112-126``) — and the device then replays every vehicle at its own
+   size; without them every replayed vehicle has the sedan's box.  An agent that stands in for a recorded vehicle
+   (``replaced``) is a sedan whatever that vehicle was, and the lidar stands every box on the ground instead of centring
+   it on z = 0;
  - ``Trajectory`` rows of a vehicle type other than the passenger car are replayed too (the provider does the same; only
    the reference's mission discovery filters on the type).
 """
@@ -31,6 +35,19 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 HISTORY_VEHICLE_PREFIX = "history-vehicle-"  # TrafficHistoryProvider._vehicle_id_prefix
+
+# The default (length, width, height) of a dataset type: TrafficHistory.decode_vehicle_type (traffic_history.py:127-146:
+# 1 motorcycle, 2 passenger, 3 truck, 4 pedestrian, anything else passenger) into VEHICLE_CONFIGS (vehicle.py:97-140).
+PASSENGER_DIMENSIONS = (3.68, 1.47, 1.4)
+TYPE_DIMENSIONS = {1: (2.5, 1.0, 1.4), 2: PASSENGER_DIMENSIONS, 3: (5.0, 1.91, 1.89), 4: (0.5, 0.5, 1.6)}
+MAX_DEVICE_ID = 1 << 20  # device_dims() holds a row per id up to the largest
+
+
+def resolve_dimensions(vehicle_type, length, width, height) -> Tuple[float, float, float]:
+    """``Dimensions.init_with_defaults`` (coordinates.py:55-66) over the type's default: a value that is ``None``, 0 or
+    -1 takes the default's."""
+    defaults = TYPE_DIMENSIONS.get(vehicle_type, PASSENGER_DIMENSIONS)
+    return tuple(float(d) if (not v or v == -1) else float(v) for v, d in zip((length, width, height), defaults))
 
 
 def round_param_for_dt(dt: float) -> int:
@@ -115,15 +132,18 @@ def slots_needed(vehicle_rows, trajectory_rows, dt: float, exclude_ids: Iterable
 class TrafficHistoryTable:
     """``frames`` [F, S, 4] float64 (x, y, heading, speed: the vehicle centre, the reference's heading convention,
     wrapped), ``vehicle`` [F, S] int32 (the history's vehicle id, < 0 = the slot is empty), ``dims`` {id: (length, width,
-    height)} with ``None`` where the dataset has none (host metadata only)."""
+    height)} with ``None`` where the dataset has none, ``types`` {id: the dataset's type} (both as the dataset has
+    them; ``device_dims`` / ``resolved_dimensions`` apply the provider's rule)."""
 
-    def __init__(self, frames: np.ndarray, vehicle: np.ndarray, dt: float, dims: Optional[Dict[int, Tuple]] = None):
+    def __init__(self, frames: np.ndarray, vehicle: np.ndarray, dt: float, dims: Optional[Dict[int, Tuple]] = None,
+                 types: Optional[Dict[int, int]] = None):
         frames = np.ascontiguousarray(frames, dtype=np.float64)
         vehicle = np.ascontiguousarray(vehicle, dtype=np.int32)
         if frames.ndim != 3 or frames.shape[2] != 4 or vehicle.shape != frames.shape[:2] or frames.shape[0] < 1:
             raise ValueError(f"frames must be [F >= 1, S, 4] and vehicle [F, S], got {frames.shape} and {vehicle.shape}")
         self.frames, self.vehicle, self.dt = frames, vehicle, float(dt)
         self.dims = dict(dims or {})
+        self.types = dict(types or {})
         self._rp = round_param_for_dt(self.dt)
 
     # ------------------------------------------------------------------ constructors
@@ -149,7 +169,8 @@ class TrafficHistoryTable:
                 frames[k, where[vid]] = row
                 vehicle[k, where[vid]] = vid
         dims = {int(r[0]): tuple(None if v is None else float(v) for v in r[2:5]) for r in vehicle_rows}
-        return cls(frames, vehicle, dt, dims)
+        types = {int(r[0]): (None if r[1] is None else int(r[1])) for r in vehicle_rows}
+        return cls(frames, vehicle, dt, dims, types)
 
     @classmethod
     def from_sqlite(cls, path: str, dt: float, num_slots: int, exclude_ids: Iterable[int] = ()) -> "TrafficHistoryTable":
@@ -192,8 +213,27 @@ class TrafficHistoryTable:
         raise KeyError(f"vehicle {vehicle_id} is not present in frame {frame}")
 
     def dimensions(self, vehicle_id: int) -> Tuple:
-        """(length, width, height) of the dataset, ``None`` where it has none.  Host metadata only."""
+        """(length, width, height) of the dataset, ``None`` where it has none (``resolved_dimensions``: the rule applied)."""
         return self.dims[int(vehicle_id)]
+
+    def resolved_dimensions(self, vehicle_id: int) -> Tuple[float, float, float]:
+        """(length, width, height) the reference's provider gives ``vehicle_id``: the dataset's values over the default
+        of its type.  An id without a ``Vehicle`` row (a table from the plain constructor): the passenger default."""
+        vid = int(vehicle_id)
+        return resolve_dimensions(self.types.get(vid, 2), *self.dims.get(vid, (None, None, None)))
+
+    def device_dims(self) -> np.ndarray:
+        """float64 ``[max id + 1, 3]``: ``resolved_dimensions`` by vehicle id, the table ``smx_set_social_history_dims``
+        takes.  Ids that never occur in ``vehicle`` hold the passenger default."""
+        ids = self.vehicle_ids()
+        top = ids[-1] if ids else 0
+        if top > MAX_DEVICE_ID:
+            raise ValueError(f"vehicle id {top} is above {MAX_DEVICE_ID} (2^20): the device table holds a row per id up "
+                             f"to the largest; renumber the dataset's vehicles")
+        out = np.tile(np.asarray(PASSENGER_DIMENSIONS, dtype=np.float64), (top + 1, 1))
+        for vid in ids:
+            out[vid] = self.resolved_dimensions(vid)
+        return out
 
     def vehicle_ids(self) -> List[int]:
         return sorted(int(v) for v in np.unique(self.vehicle) if v >= 0)
