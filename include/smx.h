@@ -316,7 +316,9 @@ enum {
                              when the slot's vehicle is created again.  Never set while the guard is off. */
   SMX_F_HIST_SHIFT = 3, /* bits 3-4: accelerometer samples held (0..2) */
   SMX_F_FIRST = 1 << 5, /* vehicle was just (re)created: its next observation is a reset observation */
-  SMX_F_SOCIAL = 1 << 6 /* scripted social vehicle (no controller, no observation) */
+  SMX_F_SOCIAL = 1 << 6, /* scripted social vehicle (no controller, no observation) */
+  SMX_F_LEFT = 1 << 7 /* a history agent whose recorded vehicle has left the table (smx_set_history_agents): done at this
+                         tick's observation; cleared when the slot's vehicle is created again.  Never set without a binding. */
 };
 
 #define SMX_DRIVEN_PATH_LEN 500 /* DrivenPathSensor deque, sensors.py:838 */
@@ -695,6 +697,52 @@ typedef struct smx_social_dims {
 int smx_set_social_history_dims(smx_handle h, const smx_social_dims* dims);
 int smx_check_social_history_dims(const smx_config* cfg, const smx_social_history* hist, const smx_social_dims* dims, char* err,
                                   uint64_t err_len);
+/* History agents (the reference's SMARTS.attach_sensors_to_vehicles + observe_from over a traffic history, smarts.py:
+ * 914-921: a recorded vehicle that carries sensors is a BoxChassis moved by Vehicle.control(pose, speed, dt)).  While
+ * bound, agent slot `a` of env `e` follows recorded vehicle
+ *   v = vehicle_dev[episode mod rows][e][a]      (rows = the bound history's; A = num_vehicles - num_social agents an env)
+ * of the bound history; v < 0 = the slot follows nothing.  `frame` as for the social slots (smx_social_history).
+ *   hidden twin  a social slot whose id equals any v >= 0 of its env's agents is absent (beside `replaced`), in every
+ *                pass and through every entry point, whatever became of the follower.
+ *   reset        a follower's spawn is v's row of the reset observation's frame — x, y, heading, speed word for word,
+ *                SMX_S_KIN_RAW_HEADING that heading, SMX_S_KIN_LAST_DT 0 — instead of spawns.pose (still wanted by the
+ *                entry check).  With v < 0, or v not in that frame, the agent does not enter: not alive, its rows an
+ *                absent agent's, status SMX_HA_ABSENT, and the env's done count starts at the number of such agents (an
+ *                env with no agent present is done after its first tick).
+ *   step         smx_step_history_agents is a tick in which no agent sends an action: a follower whose vehicle is in
+ *                the frame of the coming observation is placed on its row (SMX_S_PREV_X / _Y as in every tick,
+ *                SMX_S_KIN_LAST_HEADING the heading held, SMX_S_KIN_LAST_DT dt, then the four words, no wrap: the table
+ *                is wrapped).  One whose vehicle the frame lacks LEAVES: nothing of its state is stored, the tick's
+ *                observation is built from the held pose with done = 1, active = 0, status SMX_HA_LEFT, and it counts as
+ *                a finished agent (SMX_F_LEFT, applied by the tick's commit).  It does not come back.  The state guard,
+ *                if on, tests the held state as in every tick; the byte of a follower reads 0 (the table was checked
+ *                against the grids when it was bound).
+ *   action_dev   (optional) [E*N][3] float32 in smx_step_continuous' Imitation layout, written wherever a follower's
+ *                pose is written (the reset pass, every following tick): the inverse of ImitationController between
+ *                frame f and f + 1, acceleration = (speed[f+1] - speed[f]) / dt, angular_velocity =
+ *                min_angles_difference_signed(heading[f+1], heading[f]) / dt, in float64, rounded once, third word 0;
+ *                NaN, NaN, 0 where the vehicle is not in f + 1 and for absent / left agents.  Social rows never written.
+ *   status_dev   (optional) [E*N] SMX_HA_*, agents' bytes only.
+ * smx_step_continuous keeps working on a bound sim: that tick drives every agent by its Imitation action from the
+ * recorded state it holds, the twins stay hidden, action_dev / status_dev are not written; a following tick afterwards
+ * puts the vehicles back on the recording.  Agents stay sedans.
+ * Needs cfg.action_space == SMX_ACTION_SPACE_IMITATION (SMX_ERR_INVALID otherwise) and a bound history (SMX_ERR_STATE
+ * without one); refused (SMX_ERR_INVALID): vehicle_dev NULL, vehicle_count < rows * num_envs * A, action_count < 3 * E * N
+ * or status_count < E * N for a pointer that is given, no agent slot.  Any value in vehicle_dev is safe: ids are only
+ * compared.  ha = NULL unbinds; smx_set_social_history (table or NULL) and smx_load_map drop the binding.  Waits for the
+ * device.  smx_check_history_agents is the validation alone, without a device or a handle (`hist`: rows is read).
+ * smx_step_history_agents without a binding: SMX_ERR_STATE. */
+typedef struct smx_history_agents {
+  const int32_t* vehicle_dev; /* device, caller-owned, [rows][num_envs][A] followed vehicle id, < 0 = none; read every pass */
+  uint64_t vehicle_count;     /* int32 elements allocated */
+  float* action_dev;          /* device, caller-owned, [E*N][3] expert action; may be NULL */
+  uint8_t* status_dev;        /* device, caller-owned, [E*N]; may be NULL */
+  uint64_t action_count, status_count;
+} smx_history_agents;
+enum { SMX_HA_FOLLOWING = 0, SMX_HA_LEFT = 1, SMX_HA_ABSENT = 2 };
+int smx_set_history_agents(smx_handle h, const smx_history_agents* ha);
+int smx_check_history_agents(const smx_config* cfg, const smx_social_history* hist, const smx_history_agents* ha, char* err,
+                             uint64_t err_len);
 /* Frame stacking (smx_config.frame_stack = k): for every agent the device keeps the last k frames of each bound row,
  * newest first (frame 0 is this pass's row), in a caller-owned device buffer.  At the end of every smx_reset / smx_step*
  * pass, on the caller's stream, once every row of the pass is complete (under auto_reset: after the reset pass has
@@ -734,6 +782,8 @@ int smx_step(smx_handle h, const int8_t* actions_dev, const smx_state* st, const
 /* The same tick for the float action spaces, Imitation among them: actions[E*N][3] (float32, device). */
 int smx_step_continuous(smx_handle h, const float* actions_dev, const smx_state* st, const smx_spawns* sp,
                         const smx_outputs* out, void* hip_stream);
+/* The following tick of the history agents (smx_set_history_agents, above): no actions. */
+int smx_step_history_agents(smx_handle h, const smx_state* st, const smx_spawns* sp, const smx_outputs* out, void* hip_stream);
 /* The same tick for ActionSpaceType.Trajectory and ActionSpaceType.MPC.  trajectories[E*N][4][SMX_TRAJ_COLS] (float64,
  * device): rows x, y, heading, speed; columns 0..9 = the first ten points, column 10 = the LAST point of the
  * trajectory — all the PD controller reads, and all the MPC one does (curvature_calculation at offsets <= 4 over

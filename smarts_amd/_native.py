@@ -50,6 +50,7 @@ STATE_FIELDS = ["X", "Y", "HEADING", "U", "V", "R", "DELTA", "LAT_INT", "SPD_INT
 S = {name: i for i, name in enumerate(STATE_FIELDS)}
 S_COUNT = len(STATE_FIELDS)
 F_ALIVE, F_MCL_SET, F_TRIP_HAS_WP, F_HIST_SHIFT, F_FIRST, F_SOCIAL = 1, 2, 4, 3, 32, 64
+F_LEFT = 128  # SMX_F_LEFT: a history agent whose recorded vehicle has left (smx_set_history_agents)
 F_GUARDED = 4  # SMX_F_GUARDED: the bit F_TRIP_HAS_WP once named (that name is kept for older callers; the library never set it)
 # the state guard (smx_set_guard): bits of the per-agent byte, the default and the largest margin (metres)
 GUARD_STEP, GUARD_STATE, GUARD_SPAWN = 1, 2, 4
@@ -136,6 +137,14 @@ class SmxSocialDims(C.Structure):  # smx_social_dims (smx_set_social_history_dim
     _fields_ = [("dims_host", _p), ("n_ids", _i32)]
 
 
+class SmxHistoryAgents(C.Structure):  # smx_history_agents (smx_set_history_agents)
+    _fields_ = [("vehicle_dev", _p), ("vehicle_count", C.c_uint64), ("action_dev", _p), ("status_dev", _p),
+                ("action_count", C.c_uint64), ("status_count", C.c_uint64)]
+
+
+HA_FOLLOWING, HA_LEFT, HA_ABSENT = 0, 1, 2  # SMX_HA_*
+
+
 class SmxSpawns(C.Structure):
     _fields_ = [("episodes", _i32), ("pose", _p), ("social", _p), ("pose_count", C.c_uint64), ("social_count", C.c_uint64)]
 
@@ -198,6 +207,7 @@ EXPORTS = [
     "smx_set_mission_goals", "smx_check_mission_goals", "smx_actions_to_world", "smx_set_rgb_output", "smx_check_rgb_output",
     "smx_bind_frame_stack", "smx_check_frame_stack", "smx_set_guard", "smx_check_guard",
     "smx_set_social_history", "smx_check_social_history", "smx_set_social_history_dims", "smx_check_social_history_dims",
+    "smx_set_history_agents", "smx_check_history_agents", "smx_step_history_agents",
 ]
 LAUNCH_FORMS = {0: "small", 1: "large_teams", 2: "large_one_lane"}
 LAUNCH_STRATEGIES = {"auto": 0, "small": 1, "large": 2, "large_one_lane": 3, "large_teams": 4}
@@ -291,6 +301,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.smx_check_social_history_dims.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxSocialHistory), C.POINTER(SmxSocialDims),
                                                   C.c_char_p, C.c_uint64]
     lib.smx_check_social_history_dims.restype = C.c_int
+    lib.smx_set_history_agents.argtypes = [h, C.POINTER(SmxHistoryAgents)]
+    lib.smx_set_history_agents.restype = C.c_int
+    lib.smx_check_history_agents.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxSocialHistory), C.POINTER(SmxHistoryAgents),
+                                             C.c_char_p, C.c_uint64]
+    lib.smx_check_history_agents.restype = C.c_int
+    lib.smx_step_history_agents.argtypes = [h, C.POINTER(SmxState), C.POINTER(SmxSpawns), C.POINTER(SmxOutputs), _p]
+    lib.smx_step_history_agents.restype = C.c_int
     lib.smx_read_phase_ms.argtypes = [h, C.POINTER(C.c_float), _i32, C.POINTER(_i32)]
     lib.smx_read_phase_ms.restype = C.c_int
     lib.smx_set_timing.argtypes = [h, C.c_int]

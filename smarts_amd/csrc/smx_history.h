@@ -1,8 +1,9 @@
 // smx_history.h — traffic-history replay (include/smx.h, smx_set_social_history): which frame of the recorded table an
 // env replays in a pass, whether a social slot holds a vehicle there, and the row it takes its pose from, each written
 // once.  social_vehicle_step (every control form), respawn_vehicle (k_reset and the commit-time respawn) and commit_role
-// call these; the header holds no HIP and also compiles for the host (tests/native/host_history.cpp and
-// host_history_dims.cpp drive it under AddressSanitizer + UBSan).  The second half is the per-vehicle dimensions
+// call these, and the history agents (smx_set_history_agents: respawn_vehicle, k_control_kinematic's FOLLOW form); the
+// header holds no HIP and also compiles for the host (tests/native/host_history.cpp, host_history_dims.cpp and
+// host_history_agents.cpp drive it under AddressSanitizer + UBSan).  The second half is the per-vehicle dimensions
 // (smx_set_social_history_dims): the id -> (length, width, height) lookup the same writers use.
 //
 // Nothing read from the two caller-owned tables can take an index out of a table: the row of start_frame / replaced is
@@ -28,6 +29,9 @@ struct HistoryDev {
   const int32_t* start_frame;  // [rows][num_envs]
   const int32_t* replaced;     // [rows][num_envs], or null
   int32_t n_frames, num_social, rows, num_envs;
+  // history agents (smx_set_history_agents; follow == null: none bound): the caller's table of followed vehicle ids
+  const int32_t* follow;  // [rows][num_envs][n_agents], < 0 = the agent follows nothing
+  int32_t n_agents;       // agent slots of an env (num_vehicles - num_social)
 };
 
 // the row of the two per-env tables that episode `episode` reads (Python's modulo: a negative episode counts from the end)
@@ -47,13 +51,36 @@ SMX_HISTORY_FN bool history_present(const HistoryDev& h, int episode, int env, i
   if (frame < 0 || frame >= (int64_t)h.n_frames) return false;
   const int32_t id = h.vehicle[(size_t)frame * (size_t)h.num_social + (size_t)slot];
   if (id < 0) return false;
-  if (h.replaced == nullptr) return true;
-  return id != h.replaced[(size_t)history_table_row(h, episode) * (size_t)h.num_envs + (size_t)env];
+  const size_t cell = (size_t)history_table_row(h, episode) * (size_t)h.num_envs + (size_t)env;
+  if (h.replaced != nullptr && id == h.replaced[cell]) return false;
+  if (h.follow == nullptr) return true;
+  // history agents: the recorded vehicle an agent of this env follows is that agent (any value in the table is safe:
+  // ids are only compared)
+  const int32_t* v = h.follow + cell * (size_t)h.n_agents;
+  for (int k = 0; k < h.n_agents; ++k)
+    if (v[k] == id) return false;
+  return true;
 }
 
 // The four words of a present slot (only called when history_present said yes: the frame is in range).
 SMX_HISTORY_FN const double* history_row(const HistoryDev& h, int64_t frame, int slot) {
   return h.frames + ((size_t)frame * (size_t)h.num_social + (size_t)slot) * 4;
+}
+
+// ---- history agents (smx_set_history_agents) ----
+// The vehicle agent `agent` (0 .. n_agents - 1) of env `env` follows in `episode` (only called with follow bound).
+SMX_HISTORY_FN int32_t history_followed(const HistoryDev& h, int episode, int env, int agent) {
+  return h.follow[((size_t)history_table_row(h, episode) * (size_t)h.num_envs + (size_t)env) * (size_t)h.n_agents + (size_t)agent];
+}
+
+// The slot that holds vehicle `id` in `frame`, -1: the frame is outside the table, the id is none (< 0), or the frame
+// lacks it.  (`replaced` is not asked: a followed vehicle is hidden from the social slots by its follower.)
+SMX_HISTORY_FN int history_find(const HistoryDev& h, int64_t frame, int32_t id) {
+  if (id < 0 || frame < 0 || frame >= (int64_t)h.n_frames) return -1;
+  const int32_t* ids = h.vehicle + (size_t)frame * (size_t)h.num_social;
+  for (int s = 0; s < h.num_social; ++s)
+    if (ids[s] == id) return s;
+  return -1;
 }
 
 // ---- per-vehicle dimensions (smx_set_social_history_dims) ----

@@ -417,6 +417,32 @@ inline int check_social_history_dims_impl(const smx_config& c, const smx_social_
   return check_social_dims_impl(d, social_history_max_id(hs), err);
 }
 
+// ---- History agents (smx_set_history_agents / smx_check_history_agents) ----
+// The kernels index vehicle_dev by (episode mod rows, env, agent) and the two optional rows by vehicle: the counts are
+// checked against those shapes here; the ids the table holds are only ever compared.  `rows`: the bound history's.
+inline int check_history_agents_impl(const smx_config& c, int32_t rows, const smx_history_agents& ha, std::string& err) {
+  if (c.num_envs <= 0 || c.num_vehicles <= 0) return refuse(err, "history agents: num_envs and num_vehicles must be > 0");
+  if (c.action_space != SMX_ACTION_SPACE_IMITATION)
+    return refuse(err, "history agents: cfg.action_space is " + std::to_string(c.action_space) +
+                           ", a followed vehicle is the BoxChassis agent of SMX_ACTION_SPACE_IMITATION");
+  if (c.num_social <= 0 || c.num_social >= c.num_vehicles)
+    return refuse(err, "history agents: the configuration needs social slots (the history's) and at least one agent slot");
+  if (rows < 1) return refuse(err, "history agents: the history's rows must be >= 1");
+  if (!ha.vehicle_dev) return refuse(err, "history agents: vehicle_dev is NULL");
+  const uint64_t agents = (uint64_t)(c.num_vehicles - c.num_social), total = (uint64_t)c.num_envs * (uint64_t)c.num_vehicles;
+  const uint64_t need = (uint64_t)rows * (uint64_t)c.num_envs * agents;
+  if (ha.vehicle_count < need)
+    return refuse(err, "history agents: vehicle " + std::to_string(ha.vehicle_count) + " elements declared, rows * num_envs * agents is " +
+                           std::to_string(need) + " (a short table would be an out-of-bounds device read)");
+  if (ha.action_dev && ha.action_count < 3 * total)
+    return refuse(err, "history agents: action " + std::to_string(ha.action_count) + " elements declared, 3 * num_envs * num_vehicles is " +
+                           std::to_string(3 * total) + " (a short row would be an out-of-bounds device write)");
+  if (ha.status_dev && ha.status_count < total)
+    return refuse(err, "history agents: status " + std::to_string(ha.status_count) + " elements declared, num_envs * num_vehicles is " +
+                           std::to_string(total) + " (a short row would be an out-of-bounds device write)");
+  return SMX_OK;
+}
+
 // ---- Frame stacking (smx_bind_frame_stack / smx_check_frame_stack) ----
 // bytes per agent of a stackable source, 0 with the reason in `err`: a row of smx_outputs by its SMX_OUT_* index — stackable,
 // its sensor on, its elements times the size of its dtype — or the image by SMX_STACK_SOURCE_RGB

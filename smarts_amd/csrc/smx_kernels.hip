@@ -105,6 +105,10 @@ struct KernelArgs {
   // ... at each vehicle's own dimensions (smx_set_social_history_dims): dims.table null = none bound, every box is the
   // sedan's.  dims.slot holds a triple per vehicle of the batch, written beside a replayed slot's pose.
   HistoryDimsDev dims;
+  // history agents (smx_set_history_agents; the table itself is history.follow): the caller's optional expert-action and
+  // status rows, written where a follower's pose is (respawn_vehicle, k_control_kinematic's FOLLOW form); null: not wanted
+  float* ha_action;
+  uint8_t* ha_status;
 };
 enum {
   SMX_DEVICE_BAD_LANE_ACTION = 1,  // a Lane action code outside -1..3 was met (and treated as "no action")
@@ -349,6 +353,65 @@ __device__ __forceinline__ void history_vehicle_step(const KernelArgs& a, size_t
   SF(SMX_S_HEADING) = row[2];
   SF(SMX_S_U) = row[3];
   history_store_dims(a, gid, frame, slot);
+}
+
+// ---- history agents (smx_set_history_agents): an agent slot placed on a recorded vehicle's rows.  Called on the rare
+// side of a branch on history.follow (respawn_vehicle) or from the FOLLOW form of k_control_kinematic, which the plan
+// launches for smx_step_history_agents alone; inlined for the reason above.
+// The follower's status byte and its expert action, wherever its pose is written: the inverse of ImitationController
+// (imitation_controller.py:61-78) between `frame`, whose row of the followed vehicle `v` is `row`, and the next frame —
+// float64, rounded once; NaN, NaN where the next frame lacks the vehicle and for a follower that is absent or has left.
+__device__ __forceinline__ void history_agent_report(const KernelArgs& a, size_t gid, int status, int64_t frame, const double* row, int32_t v) {
+  if (a.ha_status != nullptr) a.ha_status[gid] = (uint8_t)status;
+  if (a.ha_action == nullptr) return;
+  float acceleration = __builtin_nanf(""), angular_velocity = __builtin_nanf("");
+  if (status == SMX_HA_FOLLOWING) {
+    const int next = history_find(a.history, frame + 1, v);
+    if (next >= 0) {
+      const double* to = history_row(a.history, frame + 1, next);
+      acceleration = (float)((to[3] - row[3]) / a.cfg.dt);
+      angular_velocity = (float)(min_angles_difference_signed(to[2], row[2]) / a.cfg.dt);
+    }
+  }
+  a.ha_action[gid * 3 + 0] = acceleration;
+  a.ha_action[gid * 3 + 1] = angular_velocity;
+  a.ha_action[gid * 3 + 2] = 0.0f;
+}
+// A follower of a freshly reset env: its vehicle's row of the reset observation's frame in the place of the spawn row
+// (every other state word is 0 already; SMX_S_KIN_LAST_DT = 0 is "no control() call yet").  Returns the flags word: a
+// follower of nothing, or of a vehicle that frame lacks, does not enter — not alive, SMX_F_FIRST all the same so that
+// the reset pass's observe role makes its rows an absent agent's, as for an empty replayed slot.
+__device__ __forceinline__ int history_agent_respawn(const KernelArgs& a, size_t gid, size_t total, int episode) {
+  const int n_veh = a.cfg.num_vehicles;
+  const int env = (int)(gid / (size_t)n_veh);
+  const int32_t v = history_followed(a.history, episode, env, (int)(gid - (size_t)env * n_veh));
+  const int64_t frame = history_frame(a.history, episode, env, a.cfg.reset_elapsed_steps);
+  const int at = history_find(a.history, frame, v);
+  double x = 0.0, y = 0.0, heading = 0.0, speed = 0.0;
+  if (at >= 0) {
+    const double* row = history_row(a.history, frame, at);
+    x = row[0], y = row[1], heading = row[2], speed = row[3];
+    history_agent_report(a, gid, SMX_HA_FOLLOWING, frame, row, v);
+  } else {
+    history_agent_report(a, gid, SMX_HA_ABSENT, frame, nullptr, v);
+  }
+  SF(SMX_S_X) = x;
+  SF(SMX_S_Y) = y;
+  SF(SMX_S_HEADING) = heading;
+  SF(SMX_S_U) = speed;
+  SF(SMX_S_KIN_RAW_HEADING) = heading;
+  SF(SMX_S_PREV_X) = x;
+  SF(SMX_S_PREV_Y) = y;
+  return SMX_F_FIRST | (at >= 0 ? SMX_F_ALIVE : 0);
+}
+// The agents of env `env` that did not enter at its reset (read after the env's respawn_vehicle calls are complete): what
+// the env's done count starts at, so that the env ends when its present agents have ended.
+__device__ __forceinline__ int history_agents_absent(const KernelArgs& a, int env) {
+  const int n_veh = a.cfg.num_vehicles;
+  int absent = 0;
+  for (int k = 0; k < n_veh - a.cfg.num_social; ++k)
+    if (!(a.st.flags[(size_t)env * n_veh + k] & SMX_F_ALIVE)) ++absent;
+  return absent;
 }
 
 // Scripted social vehicle (lane follower: no controller, no dynamics), on state words its caller has loaded:
@@ -1136,7 +1199,10 @@ __device__ __forceinline__ bool interpolate_trajectory(const double* tr, int n, 
   return true;
 }
 
-template <int SPACE, bool GUARD = false>
+// (FOLLOW, Imitation only: the tick of smx_step_history_agents — every agent is placed on the row its recorded vehicle
+// has in the frame of the coming observation, Vehicle.update_state -> control(pose, speed, dt), smarts.py:919-921,
+// vehicle.py:573-579; no action is read)
+template <int SPACE, bool GUARD = false, bool FOLLOW = false>
 __global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic(const KernelArgs a) {
   const smx_config& c = a.cfg;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
@@ -1157,6 +1223,32 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic(const KernelArg
       return;
     }
     a.guard[gid] = 0;  // (the tick may end below without a placement: no action, an action the reference raises on)
+  }
+  if constexpr (FOLLOW) {
+    // (no placement test under GUARD: every row of the table was checked against the grids when it was bound)
+    const int env = (int)(gid / (size_t)c.num_vehicles);
+    const int episode = a.st.env_episode[env];
+    const int32_t v = history_followed(a.history, episode, env, (int)(gid - (size_t)env * c.num_vehicles));
+    const int64_t frame = history_frame(a.history, episode, env, a.st.env_ticks[env] + 1);
+    const int at = history_find(a.history, frame, v);
+    if (at < 0) {
+      // The vehicle has left the recording: the agent's done_this_step (agent_manager.py:153-157).  Nothing of its state
+      // is stored; the observation is built from the held pose and the tick's commit ends the agent.
+      a.st.flags[gid] = flags | SMX_F_LEFT;
+      history_agent_report(a, gid, SMX_HA_LEFT, frame, nullptr, v);
+      return;
+    }
+    const double* row = history_row(a.history, frame, at);
+    SF(SMX_S_PREV_X) = x;  // the position recorded by the previous observation
+    SF(SMX_S_PREV_Y) = y;
+    SF(SMX_S_KIN_LAST_HEADING) = SF(SMX_S_HEADING);
+    SF(SMX_S_KIN_LAST_DT) = c.dt;
+    SF(SMX_S_X) = row[0];
+    SF(SMX_S_Y) = row[1];
+    SF(SMX_S_HEADING) = row[2];  // (wrapped already, as Heading.__new__ wraps it: include/smx.h, frames_host)
+    SF(SMX_S_U) = row[3];
+    history_agent_report(a, gid, SMX_HA_FOLLOWING, frame, row, v);
+    return;
   }
   // the placement's test, ahead of its first store: held = nothing of the vehicle is stored
   auto guard_holds = [&](const KinPose& q) {
@@ -3253,6 +3345,10 @@ __device__ __forceinline__ void respawn_vehicle(const KernelArgs& a, size_t gid,
       SF(SMX_S_MCL_Y) = so[1];  // arclength offset
       fl |= SMX_F_SOCIAL;
     }
+  } else if (__builtin_expect(a.history.follow != nullptr, 0)) {
+    // a history agent (smx_set_history_agents): the recording's row, not the spawn row (whose guard verdict goes with it)
+    fl = history_agent_respawn(a, gid, total, episode);
+    if constexpr (GUARD) a.guard[gid] = 0;
   }
   a.st.flags[gid] = fl;
   // the slot's knot lists belong to the vehicle that is gone (k_wp_walk only visits alive vehicles)
@@ -3467,9 +3563,10 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
   const bool mine = valid && alive && !social && (!a.first_only || first);
   bool done = false;
   int new_flags = flags;  // what the commit kernel makes the vehicle's flags word after this pass
-  if (valid && social && first) {
+  if (valid && first && (social || !alive)) {
     // nothing to observe: its rows read as an absent agent's (a scripted vehicle is alive here; a replayed slot that is
-    // empty in the reset observation's frame carries SMX_F_FIRST without SMX_F_ALIVE for the same treatment)
+    // empty in the reset observation's frame carries SMX_F_FIRST without SMX_F_ALIVE for the same treatment, and so
+    // does a history agent that did not enter, the one agent that is created not alive)
     atomicOr(&zero_mask, 1ull << local);
     o.active[gid] = 0;
     o.done[gid] = 0;
@@ -3967,6 +4064,14 @@ __device__ __forceinline__ void commit_role(const KernelArgs& a, const int block
     }
     if (__builtin_expect(a.history.vehicle != nullptr, 0) && (old_flags & SMX_F_SOCIAL))
       new_flags = history_commit(a, gid, total, env, slot, old_flags, new_flags, tick);
+    // A history agent whose vehicle left the recording in this tick (SMX_F_LEFT, k_control_kinematic's FOLLOW form) ends
+    // with this tick's observation, applied as the guard's done above is: the same four words.
+    if (__builtin_expect(a.history.follow != nullptr, 0) && tick && (old_flags & (SMX_F_ALIVE | SMX_F_LEFT | SMX_F_SOCIAL)) == (SMX_F_ALIVE | SMX_F_LEFT)) {
+      new_flags &= ~SMX_F_ALIVE;
+      o.active[gid] = 0;
+      o.done[gid] = 1;
+      if (o.learner) o.learner[total + gid] = 1.0f;
+    }
     a.st.flags[gid] = new_flags;
     // (agents only: a replayed social vehicle that leaves its history is not a finished agent; a scripted one never ends)
     if ((old_flags & SMX_F_ALIVE) && !(new_flags & SMX_F_ALIVE) && !(old_flags & SMX_F_SOCIAL)) atomicAdd(&env_new_done[env_local], 1);
@@ -4006,7 +4111,8 @@ __device__ __forceinline__ void commit_role(const KernelArgs& a, const int block
   __syncthreads();  // every thread of the env has read env_episode
   if (respawn && slot == 0) {
     a.st.env_episode[env] = next_episode;
-    a.st.env_done_count[env] = 0;
+    // (history agents that do not enter count as finished from the start; the barrier above has the env's new flags)
+    a.st.env_done_count[env] = __builtin_expect(a.history.follow != nullptr, 0) ? history_agents_absent(a, env) : 0;
     a.st.env_ticks[env] = c.reset_elapsed_steps;
   }
 }
@@ -5602,7 +5708,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_reset_env(const KernelArgs a) {
     sel = a.st.env_reset_pending[env] != 0;
   if (!sel) return;
   a.st.env_episode[env] = a.st.env_episode[env] + 1;
-  a.st.env_done_count[env] = 0;
+  a.st.env_done_count[env] = __builtin_expect(a.history.follow != nullptr, 0) ? history_agents_absent(a, env) : 0;
   a.st.env_ticks[env] = c.reset_elapsed_steps;
   a.st.env_reset_pending[env] = 0;
   if (!a.keep_reward_done) a.out.env_done[env] = 0;
@@ -5690,7 +5796,9 @@ struct smx_handle_s {
   uint8_t* rgb_out;   // smx_set_rgb_output: the caller's image buffer (null: none bound) and the bytes it holds
   uint64_t rgb_count;
   void* history_blob;  // smx_set_social_history: device copy of the table, frames | vehicle ids (null: none bound)
-  HistoryDev history;  // ... and what the kernels get (vehicle null: none bound)
+  HistoryDev history;  // ... and what the kernels get (vehicle null: none bound; follow: smx_set_history_agents' table)
+  float* ha_action;    // smx_set_history_agents: the caller's optional expert-action and status rows
+  uint8_t* ha_status;
   int32_t history_max_id;  // the largest vehicle id of the bound table (-1: every cell empty)
   void* dims_blob;      // smx_set_social_history_dims: device copy of the table | the triple per vehicle (null: none bound)
   HistoryDimsDev dims;  // ... and what the kernels get (table null: none bound)
@@ -5719,6 +5827,13 @@ static void drop_social_dims(smx_handle h) {
   if (h->dims_blob) (void)hipFree(h->dims_blob);
   h->dims_blob = nullptr;
   h->dims = HistoryDimsDev{};
+}
+// ... and so do the history agents (every buffer is the caller's)
+static void drop_history_agents(smx_handle h) {
+  h->history.follow = nullptr;
+  h->history.n_agents = 0;
+  h->ha_action = nullptr;
+  h->ha_status = nullptr;
 }
 
 static int fail(smx_handle h, int code, const std::string& msg) {
@@ -5824,7 +5939,8 @@ extern "C" int smx_set_launch_strategy(smx_handle h, int strategy) {
 
 // What a call's plan (smx_plan.h) may depend on, read off the handle.  `st`: the caller's state block, for the carried
 // alive list (null: no tick is planned, only the form is asked for).
-static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_state* st) {
+// `follow`: the call is smx_step_history_agents.
+static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_state* st, bool follow = false) {
   PlanInputs in{};
   in.cfg = &h->cfg;
   in.launch_strategy = h->launch_strategy;
@@ -5848,6 +5964,7 @@ static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_sta
   in.guard_bound = h->guard_out != nullptr;
   in.dims_bound = h->dims.table != nullptr;
   in.history_bound = h->history.vehicle != nullptr;
+  in.follow_entry = follow;
   return in;
 }
 
@@ -5907,6 +6024,7 @@ extern "C" int smx_load_map(smx_handle h, const smx_map_tables* t) {
   h->history_blob = nullptr;
   h->history = HistoryDev{};
   drop_social_dims(h);
+  drop_history_agents(h);
   if (!h->alive_blob) {  // the tick's alive list (large batches) + its counters, the env groups with new vehicles (alive_layout)
     const size_t n = alive_layout(h->cfg).size;
     SMX_HIP(hipMalloc((void**)&h->alive_blob, n * sizeof(int32_t)));
@@ -6202,6 +6320,7 @@ extern "C" int smx_set_social_history(smx_handle h, const smx_social_history* hi
   h->history_blob = nullptr;
   h->history = HistoryDev{};
   drop_social_dims(h);
+  drop_history_agents(h);
   // the alive list k_tail built for the next tick was built under the other rule (smx_plan.h: tail_builds_list)
   h->list_ready = false;
   if (!hist) return SMX_OK;
@@ -6211,7 +6330,7 @@ extern "C" int smx_set_social_history(smx_handle h, const smx_social_history* hi
   char* base = (char*)h->history_blob;
   SMX_HIP(hipMemcpy(base, hist->frames_host, frame_bytes, hipMemcpyHostToDevice));
   SMX_HIP(hipMemcpy(base + frame_bytes, hist->vehicle_host, id_bytes, hipMemcpyHostToDevice));
-  HistoryDev d;
+  HistoryDev d{};
   d.frames = (const double*)base;
   d.vehicle = (const int32_t*)(base + frame_bytes);
   d.start_frame = hist->start_frame_dev;
@@ -6260,6 +6379,32 @@ extern "C" int smx_set_social_history_dims(smx_handle h, const smx_social_dims* 
   d.slot = (double*)h->dims_blob + table_words;
   d.n_ids = dims->n_ids;
   h->dims = d;
+  return SMX_OK;
+}
+
+extern "C" int smx_check_history_agents(const smx_config* cfg, const smx_social_history* hist, const smx_history_agents* ha, char* err,
+                                        uint64_t err_len) {
+  std::string msg;
+  const int rc = (cfg && hist && ha) ? check_history_agents_impl(*cfg, hist->rows, *ha, msg) : refuse(msg, "null config / history / history agents");
+  return report(rc, msg, err, err_len);
+}
+
+extern "C" int smx_set_history_agents(smx_handle h, const smx_history_agents* ha) {
+  if (!h) return SMX_ERR_INVALID;
+  if (ha) {
+    if (h->history.vehicle == nullptr) return fail(h, SMX_ERR_STATE, "smx_set_history_agents needs a bound history (smx_set_social_history)");
+    std::string msg;
+    const int rc = check_history_agents_impl(h->cfg, h->history.rows, *ha, msg);
+    if (rc != SMX_OK) return fail(h, rc, msg);
+  }
+  SMX_HIP(hipSetDevice(h->device));
+  SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
+  drop_history_agents(h);
+  if (!ha) return SMX_OK;
+  h->history.follow = ha->vehicle_dev;
+  h->history.n_agents = h->cfg.num_vehicles - h->cfg.num_social;
+  h->ha_action = ha->action_dev;
+  h->ha_status = ha->status_dev;
   return SMX_OK;
 }
 
@@ -6414,6 +6559,10 @@ static void launch_control(smx_handle h, const TickPlan& p, const KernelArgs& a,
       break;
     }
     case Control::KINEMATIC: launch(k.kinematic, p.veh_blocks, 0, stream, a); break;
+    case Control::KINEMATIC_FOLLOW:  // (smx_set_history_agents holds the binding to Imitation)
+      launch(p.guard ? k_control_kinematic<SMX_ACTION_SPACE_IMITATION, true, true> : k_control_kinematic<SMX_ACTION_SPACE_IMITATION, false, true>,
+             p.veh_blocks, 0, stream, a);
+      break;
   }
 }
 
@@ -6660,6 +6809,8 @@ static KernelArgs kernel_args(smx_handle h, const TickPlan& p, const int8_t* act
   a.guard_box = h->guard_box;
   a.history = h->history;
   a.dims = h->dims;
+  a.ha_action = h->ha_action;
+  a.ha_status = h->ha_status;
   a.wp_blocks = (int)p.wp_blocks;
   a.obs_blocks = (int)p.obs_blocks;
   a.lidar_blocks = (int)p.lidar_blocks;
@@ -6667,7 +6818,7 @@ static KernelArgs kernel_args(smx_handle h, const TickPlan& p, const int8_t* act
 }
 
 // which entry point a call came through (each hands over its own pointers and leaves the others null)
-enum class Entry { RESET, LANE, FLOATS, TRAJECTORY, TARGET_POSE, TRAJECTORY_WITH_TIME };
+enum class Entry { RESET, LANE, FLOATS, TRAJECTORY, TARGET_POSE, TRAJECTORY_WITH_TIME, HISTORY_AGENTS };
 // (traj_max: columns per row of a TrajectoryWithTime action)
 static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const float* actions_f32, const double* traj,
                    const int32_t* traj_n, int32_t traj_max, const uint8_t* mask, const smx_state* st,
@@ -6677,7 +6828,10 @@ static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const
   int rc = check_buffers(h, st, sp, out);
   if (rc != SMX_OK) return rc;
   const bool is_step = entry != Entry::RESET;
-  if (is_step) {
+  const bool follow = entry == Entry::HISTORY_AGENTS;
+  if (follow) {  // (the binding holds cfg.action_space to Imitation; the tick reads no action)
+    if (h->history.follow == nullptr) return fail(h, SMX_ERR_STATE, "smx_step_history_agents: no history agents are bound (smx_set_history_agents)");
+  } else if (is_step) {
     const int sp_ = h->cfg.action_space;
     const bool ok = sp_ == SMX_ACTION_SPACE_LANE ? (entry == Entry::LANE && actions != nullptr)
                     : (sp_ == SMX_ACTION_SPACE_TRAJECTORY || sp_ == SMX_ACTION_SPACE_MPC)
@@ -6693,7 +6847,7 @@ static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const
                   "smx_step_trajectory_with_time: TrajectoryWithTime)");
   }
   hipStream_t stream = (hipStream_t)stream_;
-  const TickPlan p = tick_plan(plan_inputs(h, is_step, st));
+  const TickPlan p = tick_plan(plan_inputs(h, is_step, st, follow));
   KernelArgs a = kernel_args(h, p, actions, actions_f32, traj, traj_n, traj_max, mask, st, sp, out);
   const bool timed = h->timing && is_step && h->ev_used < 65536;
   if (timed) {
@@ -6756,6 +6910,10 @@ extern "C" int smx_step(smx_handle h, const int8_t* actions_dev, const smx_state
 extern "C" int smx_step_continuous(smx_handle h, const float* actions_dev, const smx_state* st, const smx_spawns* sp,
                                    const smx_outputs* out, void* hip_stream) {
   return enqueue(h, Entry::FLOATS, nullptr, actions_dev, nullptr, nullptr, 0, nullptr, st, sp, out, hip_stream);
+}
+
+extern "C" int smx_step_history_agents(smx_handle h, const smx_state* st, const smx_spawns* sp, const smx_outputs* out, void* hip_stream) {
+  return enqueue(h, Entry::HISTORY_AGENTS, nullptr, nullptr, nullptr, nullptr, 0, nullptr, st, sp, out, hip_stream);
 }
 
 extern "C" int smx_step_trajectory(smx_handle h, const double* trajectories_dev, const int32_t* counts_dev,

@@ -631,6 +631,7 @@ class BatchedSim:
             nat.check(self.lib, self.handle, self.lib.smx_set_social_history(self.handle, None), "smx_set_social_history")
             self.traffic_history = self.history_start_frames = self.history_replaced = None
             self.history_dims = False
+            self._drop_history_agents()
             return
         E = self.E
         if start_frames is None:
@@ -654,6 +655,7 @@ class BatchedSim:
         # (the library reads the two tensors in every pass: they live as long as the binding)
         self.traffic_history, self.history_start_frames, self.history_replaced = table, start_frames, replaced
         self.history_dims = False  # (binding a history drops the dimensions of the one before)
+        self._drop_history_agents()  # (... and its history agents)
         if dims:
             self.set_history_dims(True)
 
@@ -672,6 +674,65 @@ class BatchedSim:
         nat.check(self.lib, self.handle, self.lib.smx_set_social_history_dims(self.handle, C.byref(sd)), "smx_set_social_history_dims")
         self.history_dims = True
 
+    def set_history_agents(self, vehicle: Optional[torch.Tensor], expert_actions: bool = True):
+        """Bind the history agents (``smx_set_history_agents``; needs ``action_space="Imitation"`` and a bound traffic
+        history): agent slot ``a`` of env ``e`` follows recorded vehicle ``vehicle[k mod R, e, a]`` in episode ``k`` —
+        int32 ``[R, E, A]`` on the sim's device, ``R`` the rows of the bound ``start_frames``, ``A = N - num_social``,
+        < 0 = follows nothing; the tensor stays the caller's and is read by every pass (any value is safe).  From the
+        next ``reset`` on a follower starts on its vehicle's row of the reset observation's frame, that vehicle is
+        hidden from the env's social slots, and ``step_history_agents()`` moves every follower along the recording
+        (``include/smx.h`` has the rules: leaving, never entering, the hand-over to ``step(actions)``).
+        ``out["history_agent_status"]`` ``(E, N)`` uint8 holds ``HA_FOLLOWING / HA_LEFT / HA_ABSENT`` per agent and,
+        with ``expert_actions``, ``out["expert_action"]`` ``(E, N, 3)`` float32 the Imitation action that takes the
+        vehicle to its next recorded frame (NaN, NaN, 0: none), in the layout ``step`` takes.  ``vehicle=None``
+        unbinds; so do ``set_traffic_history`` and a new map."""
+        if vehicle is None:
+            nat.check(self.lib, self.handle, self.lib.smx_set_history_agents(self.handle, None), "smx_set_history_agents")
+            self._drop_history_agents()
+            return
+        A = self.N - self.cfg.num_social
+        if (vehicle.dtype != torch.int32 or vehicle.device != self.device or not vehicle.is_contiguous() or vehicle.ndim != 3
+                or tuple(vehicle.shape[1:]) != (self.E, A) or vehicle.shape[0] < 1):
+            raise ValueError(f"vehicle must be a contiguous int32 tensor of shape [R, {self.E}, {A}] on {self.device}")
+        if self.history_start_frames is not None and vehicle.shape[0] != self.history_start_frames.shape[0]:
+            raise ValueError(f"vehicle has {vehicle.shape[0]} rows, the bound start_frames {self.history_start_frames.shape[0]}")
+        status = torch.full((self.E, self.N), nat.HA_ABSENT, dtype=torch.uint8, device=self.device)
+        action = None
+        if expert_actions:
+            action = torch.full((self.E, self.N, 3), float("nan"), dtype=torch.float32, device=self.device)
+            action[..., 2] = 0.0
+        ha = nat.SmxHistoryAgents()
+        ha.vehicle_dev, ha.vehicle_count = vehicle.data_ptr(), int(vehicle.numel())
+        ha.status_dev, ha.status_count = status.data_ptr(), int(status.numel())
+        if action is not None:
+            ha.action_dev, ha.action_count = action.data_ptr(), int(action.numel())
+        nat.check(self.lib, self.handle, self.lib.smx_set_history_agents(self.handle, C.byref(ha)), "smx_set_history_agents")
+        self._drop_history_agents()
+        self.history_agents = vehicle  # (read by every pass: lives as long as the binding)
+        self.out["history_agent_status"] = status
+        if action is not None:
+            self.out["expert_action"] = action
+
+    def _drop_history_agents(self):
+        self.history_agents = None
+        self.out.pop("history_agent_status", None)
+        self.out.pop("expert_action", None)
+
+    def step_history_agents(self) -> Dict[str, torch.Tensor]:
+        """One tick in which every agent follows its recorded vehicle (``smx_step_history_agents``; no actions)."""
+        if not self._was_reset:
+            raise RuntimeError("step() before reset()")
+        self._out.learner = self.next_learner_block.data_ptr()
+        rc = self.lib.smx_step_history_agents(self.handle, C.byref(self._st), C.byref(self._sp), C.byref(self._out),
+                                              self._stream_ptr())
+        if rc != 0:  # (no binding: refused before anything was launched, the learner block does not flip)
+            self._out.learner = self.out["learner"].data_ptr()
+        nat.check(self.lib, self.handle, rc, "smx_step_history_agents")
+        self._learner_k ^= 1
+        self.out["learner"] = self._learner[self._learner_k]
+        return self.out
+
+    history_agents = None
     history_dims = False
     traffic_history = None
     history_start_frames = None

@@ -8,6 +8,7 @@ from .agent_interface import (  # noqa: F401
 from .core import SMARTSDestroyedError, SMARTSNotSetupError  # noqa: F401
 from .ego_centric_adapters import ego_centric_observation_adapter, get_egocentric_adapters  # noqa: F401
 from .format_obs import FormatObs, StdObs  # noqa: F401
+from .history_observer import HistoryObserver  # noqa: F401
 from .hiway_env import HiWayEnv  # noqa: F401
 from .observations import (  # noqa: F401
     Collision, Dimensions, EgoVehicleObservation, Events, GridMapMetadata, Heading, Observation, OccupancyGridMap,

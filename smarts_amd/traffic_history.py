@@ -238,6 +238,71 @@ class TrafficHistoryTable:
     def vehicle_ids(self) -> List[int]:
         return sorted(int(v) for v in np.unique(self.vehicle) if v >= 0)
 
+    # ------------------------------------------------------------------ history agents (BatchedSim.set_history_agents)
+    def frames_of(self, vehicle_id: int) -> np.ndarray:
+        """The frames that hold ``vehicle_id``, ascending (empty for an id the table lacks)."""
+        return np.nonzero((self.vehicle == int(vehicle_id)).any(axis=1))[0] if int(vehicle_id) >= 0 else np.zeros(0, dtype=np.int64)
+
+    def first_seen_frames(self) -> Dict[int, int]:
+        """``{vehicle id: the first frame that holds it}``: ``TrafficHistory.first_seen_times`` (traffic_history.py:
+        148-155) on the table's frame grid."""
+        out: Dict[int, int] = {}
+        for k in range(self.num_frames):
+            for vid in self.vehicle[k]:
+                if vid >= 0:
+                    out.setdefault(int(vid), k)
+        return dict(sorted(out.items()))
+
+    def last_seen_frame(self, vehicle_id: int) -> int:
+        """The last frame that holds ``vehicle_id`` (``KeyError`` for an id the table lacks)."""
+        held = self.frames_of(vehicle_id)
+        if not len(held):
+            raise KeyError(f"vehicle {vehicle_id} is not in the table")
+        return int(held[-1])
+
+    def expert_actions(self, vehicle_id: int) -> np.ndarray:
+        """float64 ``[frames present, 2]``: per frame ``f`` that holds the vehicle, the Imitation action that takes its
+        recorded heading and speed to frame ``f + 1``'s — the exact inverse of ``ImitationController``
+        (imitation_controller.py:61-78): ``acceleration = (speed[f+1] - speed[f]) / dt``, ``angular_velocity =
+        min_angles_difference_signed(heading[f+1], heading[f]) / dt`` — and NaN, NaN ("no action") where frame ``f + 1``
+        lacks the vehicle.  What the device writes to ``out["expert_action"]`` (rounded once to float32)."""
+        held = self.frames_of(vehicle_id)
+        out = np.full((len(held), 2), np.nan, dtype=np.float64)
+        for i, f in enumerate(held):
+            if f + 1 >= self.num_frames:
+                continue
+            nxt = np.nonzero(self.vehicle[f + 1] == int(vehicle_id))[0]
+            if not len(nxt):
+                continue
+            h0, s0 = self.frames[f, np.nonzero(self.vehicle[f] == int(vehicle_id))[0][0], 2:4]
+            h1, s1 = self.frames[f + 1, nxt[0], 2:4]
+            out[i, 0] = (float(s1) - float(s0)) / self.dt
+            out[i, 1] = ((((float(h1) - float(h0)) + math.pi) % (2 * math.pi)) - math.pi) / self.dt
+        return out
+
+    def history_agent_windows(self, ids: Sequence[int], num_envs: int, num_agents: int,
+                              reset_elapsed_steps: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """``(start_frames [1, E] int32, vehicle [1, E, A] int32)`` for one env per recorded vehicle: env ``k`` follows
+        ``ids[k]`` in agent slot 0 from that vehicle's first frame (``start = first_seen - reset_elapsed_steps``, so the
+        reset observation is its first frame; a negative start is fine), its other agent slots follow the further
+        vehicles present in that frame in ascending id order, and ``-1`` fills what is left (and every env past
+        ``len(ids)``, which starts at frame 0)."""
+        ids = [int(v) for v in ids]
+        if len(ids) > num_envs:
+            raise ValueError(f"{len(ids)} vehicles for {num_envs} envs")
+        if num_agents < 1:
+            raise ValueError("num_agents must be >= 1")
+        first = self.first_seen_frames()
+        start = np.zeros((1, num_envs), dtype=np.int32)
+        vehicle = np.full((1, num_envs, num_agents), -1, dtype=np.int32)
+        for k, vid in enumerate(ids):
+            if vid not in first:
+                raise KeyError(f"vehicle {vid} is not in the table")
+            start[0, k] = first[vid] - int(reset_elapsed_steps)
+            others = sorted(int(v) for v in self.vehicle[first[vid]] if v >= 0 and v != vid)
+            vehicle[0, k, :] = ([vid] + others + [-1] * num_agents)[:num_agents]
+        return start, vehicle
+
 
 def read_sqlite(path: str):
     """(vehicle_rows, trajectory_rows) of a converted dataset, in the column order ``from_rows`` takes."""
