@@ -459,7 +459,12 @@ typedef struct smx_outputs {
   int16_t* nb_lane_id;
   int8_t* nb_slot;       /* vehicle slot of each neighbour, -1 = padding      */
   uint8_t* nb_count;     /* [E*N] neighbours found (may exceed nb_max)        */
-  /* occupancy grid sensor [E*N][ogm_height][ogm_width], NULL if unused       */
+  /* occupancy grid sensor [E*N][ogm_height][ogm_width], NULL if unused.
+   * These rows are the handle's to maintain between calls: a tile is mostly zeros that stay zeros, so a call stores only the
+   * pieces of a tile that are non-zero now or were after the last call (the handle keeps a bit per piece) and the rows
+   * read after every call exactly as if whole tiles had been stored.  Reading them is free.  A caller that WRITES into
+   * them calls smx_invalidate_outputs before the next call; passing another buffer than the last call's is detected, and
+   * either makes that call store whole tiles.  smx_set_ogm_delta(h, 0) stores whole tiles always. */
   uint8_t* ogm;
   /* lidar sensor [E*N][lidar_rays]: hit flag + point, NULL if unused         */
   uint8_t* lidar_hit;
@@ -869,6 +874,11 @@ int smx_set_launch_strategy(smx_handle h, int strategy);
  * end the tick of a smaller batch).  Same results either way. */
 enum { SMX_FORM_SMALL = 0, SMX_FORM_LARGE_TEAMS = 1, SMX_FORM_LARGE_ONE_LANE = 2 };
 int smx_launch_form(smx_handle h);
+/* The OGM rows (smx_outputs.ogm) and the pieces the handle knows to be zero in them.  smx_invalidate_outputs: the caller
+ * wrote into the rows itself, the next call stores whole tiles.  smx_set_ogm_delta: on (the default) stores only the
+ * pieces that changed; off stores every piece in every call, and the rows may then be written freely. */
+int smx_invalidate_outputs(smx_handle h);
+int smx_set_ogm_delta(smx_handle h, int on);
 const char* smx_version(void);
 void smx_destroy(smx_handle h);
 

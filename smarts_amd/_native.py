@@ -208,6 +208,7 @@ EXPORTS = [
     "smx_bind_frame_stack", "smx_check_frame_stack", "smx_set_guard", "smx_check_guard",
     "smx_set_social_history", "smx_check_social_history", "smx_set_social_history_dims", "smx_check_social_history_dims",
     "smx_set_history_agents", "smx_check_history_agents", "smx_step_history_agents",
+    "smx_invalidate_outputs", "smx_set_ogm_delta",
 ]
 LAUNCH_FORMS = {0: "small", 1: "large_teams", 2: "large_one_lane"}
 LAUNCH_STRATEGIES = {"auto": 0, "small": 1, "large": 2, "large_one_lane": 3, "large_teams": 4}
@@ -327,6 +328,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.smx_set_launch_strategy.restype = C.c_int
     lib.smx_launch_form.argtypes = [h]
     lib.smx_launch_form.restype = C.c_int
+    lib.smx_invalidate_outputs.argtypes = [h]
+    lib.smx_invalidate_outputs.restype = C.c_int
+    lib.smx_set_ogm_delta.argtypes = [h, C.c_int]
+    lib.smx_set_ogm_delta.restype = C.c_int
     lib.smx_struct_size.argtypes = [C.c_int]
     lib.smx_struct_size.restype = C.c_uint64
     for which, mirror in enumerate((SmxConfig, SmxMapTables, SmxState, SmxSpawns, SmxOutputs)):

@@ -109,6 +109,13 @@ struct KernelArgs {
   // status rows, written where a follower's pose is (respawn_vehicle, k_control_kinematic's FOLLOW form); null: not wanted
   float* ha_action;
   uint8_t* ha_status;
+  // OGM delta stores (TickPlan::ogm_delta), library-owned, [E*N][smx_ogm_mask_words(tile)]: bit p of an agent's words = piece
+  // p (SMX_OGM_PIECE bytes) of its tile in the caller's out.ogm may be non-zero; a clear bit says the piece IS zero there.
+  // A kernel stores a piece iff it is non-zero now or its bit was set, and leaves the bit = non-zero now (ogm_store_tile;
+  // zero_dense_rows zeroes the tile and clears the words).  Null: every piece is stored.  No two kernels of a tick that can
+  // run beside each other touch the same agent's words: k_ogm_env / the OGM role draw for the agents alive at the tick's
+  // start, zero_dense_rows runs for agents that were not, and k_tail's tiles of new vehicles come after both have joined.
+  unsigned long long* ogm_mask;
 };
 enum {
   SMX_DEVICE_BAD_LANE_ACTION = 1,  // a Lane action code outside -1..3 was met (and treated as "no action")
@@ -3367,6 +3374,62 @@ struct __align__(16) SharedPose {
   int pad;
 };
 
+// OGM delta stores (KernelArgs::ogm_mask).  A step of a wavefront's copy-out is 64 int4: SMX_OGM_PIECE / 16 lanes share a
+// piece, so a step covers 64 or 16 pieces and a mask word one step or four.
+#define SMX_OGM_LPP (SMX_OGM_PIECE / 16)  // lanes per piece
+#define SMX_OGM_PPS (64 / SMX_OGM_LPP)    // pieces per step
+// the lanes' ballot -> a bit per piece of the step (a piece is non-zero when one of its lanes is)
+__device__ __forceinline__ unsigned long long ogm_pieces_of_lanes(unsigned long long b) {
+  if constexpr (SMX_OGM_LPP == 1) return b;
+  b |= b >> 1;
+  b |= b >> 2;
+  b &= 0x1111111111111111ull;  // piece j at bit 4 j; packed below
+  b = (b | (b >> 3)) & 0x0303030303030303ull;
+  b = (b | (b >> 6)) & 0x000f000f000f000full;
+  b = (b | (b >> 12)) & 0x000000ff000000ffull;
+  return (b | (b >> 24)) & 0xffffull;
+}
+// ... and back: a bit per piece of the step -> the lanes of those pieces
+__device__ __forceinline__ unsigned long long ogm_lanes_of_pieces(unsigned long long q) {
+  if constexpr (SMX_OGM_LPP == 1) return q;
+  q &= 0xffffull;
+  q = (q | (q << 24)) & 0x000000ff000000ffull;
+  q = (q | (q << 12)) & 0x000f000f000f000full;
+  q = (q | (q << 6)) & 0x0303030303030303ull;
+  q = (q | (q << 3)) & 0x1111111111111111ull;
+  return q * 0xfull;
+}
+// One wavefront (every lane calls) copies a finished tile of n16 int4 from LDS to the agent's row `dst` of out.ogm under
+// the agent's mask words: a piece leaves iff it is non-zero or its bit was set, and its bit becomes "non-zero".  The ballot
+// and the words are uniform in the wavefront; lane 0 writes a word back once its pieces are through.  mask null: the plain
+// copy.  (The words fetched once per tile into lanes and written back in one store took eight registers more and
+// k_ogm_env a wavefront per SIMD: 70 -> 78 VGPRs.)
+__device__ __forceinline__ void ogm_store_tile(const int4* src, int4* dst, unsigned long long* mask, const int n16, const int lane) {
+  if (mask == nullptr) {
+    for (int k = lane; k < n16; k += 64) dst[k] = src[k];
+    return;
+  }
+  const int steps = (n16 + 63) >> 6;
+  unsigned long long old_word = 0ull, new_word = 0ull;
+#pragma nounroll
+  for (int i = 0; i < steps; ++i) {
+    const int k = i * 64 + lane;
+    const bool mine = k < n16;
+    int4 v = make_int4(0, 0, 0, 0);
+    if (mine) v = src[k];
+    const unsigned long long nz = ogm_pieces_of_lanes(__ballot((v.x | v.y | v.z | v.w) != 0));
+    const int sub = i % SMX_OGM_LPP, shift = sub * SMX_OGM_PPS;  // the step's place in its mask word
+    if (sub == 0) {
+      old_word = mask[i / SMX_OGM_LPP];
+      new_word = 0ull;
+    }
+    const unsigned long long leaving = ogm_lanes_of_pieces(nz | (old_word >> shift));
+    if (mine && ((leaving >> lane) & 1ull)) dst[k] = v;
+    new_word |= nz << shift;
+    if ((sub == SMX_OGM_LPP - 1 || i == steps - 1) && lane == 0) mask[i / SMX_OGM_LPP] = new_word;
+  }
+}
+
 // The rows of an agent that is gone read as an absent agent's: zeros (lane ids and slots -1).  Written by the whole
 // workgroup, thread t of nth striding each array — one lane on its own took 4 096 byte stores for an OGM tile and
 // 640 for the waypoint rows, one after the other, and the wavefront that held such a lane ended the kernel (C4: 380
@@ -3427,7 +3490,13 @@ __device__ __forceinline__ void zero_dense_rows(const KernelArgs& a, size_t gid,
       for (size_t k = t; k < n; k += nth) p[k] = 0;
     }
   };
-  if ((c.sensors & SMX_SENSOR_OGM) && o.ogm) zero_bytes(o.ogm, (size_t)c.ogm_width * c.ogm_height);
+  if ((c.sensors & SMX_SENSOR_OGM) && o.ogm) {
+    zero_bytes(o.ogm, (size_t)c.ogm_width * c.ogm_height);
+    if (a.ogm_mask) {  // the whole tile is zero now (nobody else holds this agent's words in this tick: KernelArgs::ogm_mask)
+      const size_t words = smx_ogm_mask_words((size_t)c.ogm_width * c.ogm_height);
+      for (size_t k = t; k < words; k += nth) a.ogm_mask[gid * words + k] = 0ull;
+    }
+  }
   if ((c.sensors & SMX_SENSOR_DAGM) && o.dagm) zero_bytes(o.dagm, (size_t)c.dagm_width * c.dagm_height);
   if ((c.sensors & SMX_SENSOR_LIDAR) && o.lidar_hit) {
     for (int k = t; k < c.lidar_rays; k += nth) o.lidar_hit[gid * (size_t)c.lidar_rays + k] = 0;
@@ -4225,8 +4294,10 @@ __device__ __forceinline__ void ogm_role(const KernelArgs& a, const int block) {
     __syncthreads();  // before the stage is reused (envs of more than 64 vehicles do not exist, but the loop is general)
   }
   __syncthreads();
+  static_assert(SMX_BLOCK == 64, "ogm_store_tile: the workgroup is one wavefront");
   int4* dst = reinterpret_cast<int4*>(a.out.ogm + gid * (size_t)bytes);
-  for (int k = threadIdx.x; k < bytes / 16; k += SMX_BLOCK) dst[k] = reinterpret_cast<const int4*>(tile)[k];
+  ogm_store_tile(reinterpret_cast<const int4*>(tile), dst, a.ogm_mask ? a.ogm_mask + gid * smx_ogm_mask_words((size_t)bytes) : nullptr,
+                 bytes / 16, (int)threadIdx.x);
 }
 
 // k_ogm_env (large batches): the same tiles, one workgroup of four wavefronts per ENV.  The env's poses are
@@ -4314,6 +4385,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(SMX
   const int n_obs = n_observers;
   const int per_round = SMX_OGM_WAVES * OBS;
   const int rounds = (n_obs + per_round - 1) / per_round;
+  const size_t mask_words = smx_ogm_mask_words((size_t)bytes);
   // Each wavefront owns its tiles: inside the loop only lanes of ONE wavefront exchange data through LDS, whose
   // operations a wavefront issues in order — a scheduling fence is all that is needed (four workgroup barriers per
   // round made the four wavefronts wait for the slowest one's rectangles)
@@ -4384,8 +4456,9 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(SMX
     SMX_WAVE_SYNC();
     for (int t = 0; t < n_live; ++t) {
       const int4* src_tile = reinterpret_cast<const int4*>(tile + (size_t)t * bytes);
-      int4* dst = reinterpret_cast<int4*>(a.out.ogm + ((size_t)env * n_veh + (int)observers[turn0 + t]) * (size_t)bytes);
-      for (int k = lane; k < bytes / 16; k += 64) dst[k] = src_tile[k];
+      const size_t gid = (size_t)env * n_veh + (int)observers[turn0 + t];
+      int4* dst = reinterpret_cast<int4*>(a.out.ogm + gid * (size_t)bytes);
+      ogm_store_tile(src_tile, dst, a.ogm_mask ? a.ogm_mask + gid * mask_words : nullptr, bytes / 16, lane);
     }
     SMX_WAVE_SYNC();  // the tiles are reused
   }
@@ -5800,6 +5873,15 @@ struct smx_handle_s {
   float* ha_action;    // smx_set_history_agents: the caller's optional expert-action and status rows
   uint8_t* ha_status;
   int32_t history_max_id;  // the largest vehicle id of the bound table (-1: every cell empty)
+  // OGM delta stores (KernelArgs::ogm_mask): the tiles' piece mask, allocated with the handle when the OGM sensor is on.
+  // The caller's out.ogm arrives with every call, so the masks describe the buffer of the last call only: `ogm_rows` is
+  // that pointer, and a call that brings another one — or the first call, or the one after smx_invalidate_outputs /
+  // smx_set_ogm_delta — sets every bit ahead of its pass (ogm_known false) and so stores whole tiles.
+  unsigned long long* ogm_mask;
+  size_t ogm_mask_bytes;
+  const uint8_t* ogm_rows;
+  bool ogm_known;
+  bool ogm_delta = true;  // smx_set_ogm_delta
   void* dims_blob;      // smx_set_social_history_dims: device copy of the table | the triple per vehicle (null: none bound)
   HistoryDimsDev dims;  // ... and what the kernels get (table null: none bound)
   struct StackBinding {  // smx_bind_frame_stack: one caller-owned stack per (source, layout)
@@ -5923,6 +6005,15 @@ extern "C" int smx_create(const smx_config* cfg, int device, smx_handle* out) {
   h->cfg = *cfg;
   h->device = device;
   h->nb_d2_max = radius_threshold(h->cfg.nb_radius);
+  if (h->cfg.sensors & SMX_SENSOR_OGM) {  // the OGM tiles' piece mask; its bits are set by the first call (ogm_known)
+    h->ogm_mask_bytes = (size_t)cfg->num_envs * cfg->num_vehicles * smx_ogm_mask_words((size_t)cfg->ogm_width * cfg->ogm_height) * sizeof(unsigned long long);
+    const hipError_t em = hipMalloc((void**)&h->ogm_mask, h->ogm_mask_bytes);
+    if (em != hipSuccess) {
+      h->ogm_mask = nullptr;
+      smx_destroy(h);
+      return refuse(g_create_err, std::string("hipMalloc (OGM piece mask): ") + hipGetErrorString(em), SMX_ERR_HIP);
+    }
+  }
 #ifdef SMX_DEBUG_TIMING
   if (const char* dbg = getenv("SMX_DEBUG_SKIP")) h->debug_skip = atoi(dbg);
 #endif
@@ -5965,6 +6056,7 @@ static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_sta
   in.dims_bound = h->dims.table != nullptr;
   in.history_bound = h->history.vehicle != nullptr;
   in.follow_entry = follow;
+  in.ogm_mask = h->ogm_mask != nullptr && h->ogm_delta;
   return in;
 }
 
@@ -6811,6 +6903,7 @@ static KernelArgs kernel_args(smx_handle h, const TickPlan& p, const int8_t* act
   a.dims = h->dims;
   a.ha_action = h->ha_action;
   a.ha_status = h->ha_status;
+  a.ogm_mask = (p.ogm_delta && out->ogm) ? h->ogm_mask : nullptr;
   a.wp_blocks = (int)p.wp_blocks;
   a.obs_blocks = (int)p.obs_blocks;
   a.lidar_blocks = (int)p.lidar_blocks;
@@ -6872,6 +6965,13 @@ static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const
     ph = &h->ph_pool[h->ph_used * (SMX_PHASE_COUNT + 1)];
     SMX_HIP(hipEventRecord(ph[0], stream));
   }
+  if (a.ogm_mask && !(h->ogm_known && h->ogm_rows == out->ogm)) {
+    // the masks do not describe these rows (KernelArgs::ogm_mask): every piece may be non-zero, this pass stores whole tiles
+    SMX_HIP(hipMemsetAsync(h->ogm_mask, 0xff, h->ogm_mask_bytes, stream));
+    h->ogm_rows = out->ogm;
+    h->ogm_known = true;
+  }
+  if (!a.ogm_mask) h->ogm_known = false;  // a pass that stores without the masks leaves them stale
   if (p.social) launch(k_social, p.veh_blocks, 0, stream, a);
   alive_list(h, p, a, stream);
   if (is_step) {
@@ -7040,6 +7140,21 @@ extern "C" int smx_debug_knot_table_stats(smx_handle h, int64_t* out4) {
   return SMX_OK;
 }
 
+// The caller wrote into the OGM rows itself: the next call stores whole tiles (the masks describe what the library stored).
+extern "C" int smx_invalidate_outputs(smx_handle h) {
+  if (!h) return SMX_ERR_INVALID;
+  h->ogm_known = false;
+  return SMX_OK;
+}
+
+// OGM delta stores on (the default) or off: off passes the kernels the null mask and every call stores every piece.
+extern "C" int smx_set_ogm_delta(smx_handle h, int on) {
+  if (!h) return SMX_ERR_INVALID;
+  h->ogm_delta = on != 0;
+  h->ogm_known = false;
+  return SMX_OK;
+}
+
 extern "C" int smx_set_timing(smx_handle h, int level) {
   if (!h) return SMX_ERR_INVALID;
   h->timing = level == 1;
@@ -7119,6 +7234,7 @@ extern "C" void smx_destroy(smx_handle h) {
   if (h->goals_blob) (void)hipFree(h->goals_blob);
   if (h->history_blob) (void)hipFree(h->history_blob);
   if (h->dims_blob) (void)hipFree(h->dims_blob);
+  if (h->ogm_mask) (void)hipFree(h->ogm_mask);
   for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ph_pool) (void)hipEventDestroy(e);
   delete h;

@@ -17,6 +17,16 @@
 #endif
 #define SMX_WPT_MAX_PATHS 8  // dense rows per vehicle (wp_paths) the staged form handles
 #define SMX_OGM_WAVES 4
+// OGM delta stores: the bytes of a tile's piece the handle keeps one "may be non-zero in device memory" bit for (16: one
+// lane's int4 of the copy-out; 64: a whole sector, four lanes').  profiles/r19_ogm_delta.txt has both measured: at 16 a
+// tile of the headline workload stores 377 B that reach memory as 753 (partial sectors), at 64 1 120 B as 1 120, and the
+// tick is the same or 1 % shorter at 64, with a quarter of the mask.
+#ifndef SMX_OGM_PIECE
+#define SMX_OGM_PIECE 64
+#endif
+static_assert(SMX_OGM_PIECE == 16 || SMX_OGM_PIECE == 64, "a piece is one int4 or one 64-byte sector");
+// 64-bit mask words per agent tile ([E*N][words], a tile's last word padded)
+static constexpr size_t smx_ogm_mask_words(size_t tile_bytes) { return (tile_bytes / SMX_OGM_PIECE + 63) / 64; }
 #define SMX_TTC_TEAM 16  // lanes of a wavefront that share one agent in k_lane_ttc
 // ... and in k_ego_frame: a team's access to a float64 row is one 128-byte line; the shortest rows (ten neighbours: 30
 // float64, one path of 20 waypoints: 60) still fill it, and four agents' rows share a wavefront
@@ -82,6 +92,7 @@ struct PlanInputs {
   bool history_bound;      // smx_set_social_history holds a table: the social slots replay it
   bool dims_bound;         // smx_set_social_history_dims holds a table: ... at each vehicle's own dimensions
   bool follow_entry;       // the call is smx_step_history_agents: the agents are placed on their recorded vehicles' rows
+  bool ogm_mask;           // the handle holds the OGM tiles' piece mask and smx_set_ogm_delta has not switched it off
 };
 
 enum class AliveList : uint8_t { NONE, CARRIED, BUILD };  // BUILD: k_alive_list ahead of the tick
@@ -138,6 +149,9 @@ struct TickPlan {
   bool chain_fused;  // SIDE on a map without splits: eight-lane searches, walk and rows in one kernel
   SlowRef facts_slow, seeds_slow, rows_slow;
   Ogm ogm;
+  // the OGM kernels store only the pieces of a tile that are, or a call ago were, non-zero (KernelArgs::ogm_mask); false:
+  // the null mask, every piece is stored.  Tiles that are no whole number of pieces keep the null mask.
+  bool ogm_delta;
   Lidar lidar;
   bool dagm, road_waypoints;
   bool rgb;  // k_rgb (SMX_SENSOR_RGB): wherever k_dagm is launched; rgb_lds = its class tile, a byte a pixel
@@ -283,6 +297,7 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
   else
     p.ogm = p.ogm_bytes * SMX_OGM_WAVES <= 64 * 1024 ? Ogm::ENV1 : Ogm::PER_OBSERVER;
   p.ogm_lds = p.ogm == Ogm::ENV2 ? p.ogm_bytes * SMX_OGM_WAVES * 2 : p.ogm == Ogm::ENV1 ? p.ogm_bytes * SMX_OGM_WAVES : p.ogm_bytes;
+  p.ogm_delta = in.ogm_mask && p.ogm_bytes != 0 && p.ogm_bytes % SMX_OGM_PIECE == 0;
   p.dagm = p.dagm_bytes != 0;
   p.rgb = (c.sensors & SMX_SENSOR_RGB) != 0;
   p.rgb_lds = p.rgb ? (size_t)c.rgb_width * c.rgb_height : 0;

@@ -597,6 +597,26 @@ class BatchedSim:
         nat.check(self.lib, self.handle, rc, "smx_set_rgb_output")
         self.out["rgb"] = images
 
+    def invalidate_outputs(self):
+        """Tell the library that the caller wrote into ``out["ogm"]`` itself (``smx_invalidate_outputs``): the next call
+        stores whole tiles.  The library stores only the pieces of an OGM tile that changed since its last call, so
+        reading the rows is free, writing into them needs this call, and binding another tensor (``bind_ogm``) is
+        noticed by itself."""
+        nat.check(self.lib, self.handle, self.lib.smx_invalidate_outputs(self.handle), "smx_invalidate_outputs")
+
+    def set_ogm_delta(self, on: bool):
+        """OGM tiles stored as the pieces that changed (True, the default) or whole in every call (False:
+        ``smx_set_ogm_delta``).  The rows read the same either way."""
+        nat.check(self.lib, self.handle, self.lib.smx_set_ogm_delta(self.handle, 1 if on else 0), "smx_set_ogm_delta")
+
+    def bind_ogm(self, tiles: torch.Tensor):
+        """Point ``out["ogm"]`` at another tensor of the same shape; the next call stores whole tiles into it."""
+        want = (self.E, self.N, self.cfg.ogm_height, self.cfg.ogm_width)
+        if not self.cfg.ogm or tiles.dtype != torch.uint8 or tiles.device != self.device or not tiles.is_contiguous() or tuple(tiles.shape) != want:
+            raise ValueError(f"the OGM rows must be a contiguous uint8 device tensor of shape {want} (SimConfig(ogm=True))")
+        nat.bind_buffer(self._out, nat.OUTPUT_BUFFERS, "ogm", tiles)
+        self.out["ogm"] = tiles
+
     def bind_guard(self, guard: Optional[torch.Tensor], margin: Optional[float] = None):
         """Bind the byte buffer of the state guard (``smx_set_guard``): uint8 [E, N] on the sim's device — which switches
         the guard on — or ``None`` to switch it off.  ``margin`` defaults to ``SimConfig.state_guard_margin``.
