@@ -748,6 +748,44 @@ enum { SMX_HA_FOLLOWING = 0, SMX_HA_LEFT = 1, SMX_HA_ABSENT = 2 };
 int smx_set_history_agents(smx_handle h, const smx_history_agents* ha);
 int smx_check_history_agents(const smx_config* cfg, const smx_social_history* hist, const smx_history_agents* ha, char* err,
                              uint64_t err_len);
+/* Handing history agents over to actions one by one, inside a tick (the reference's SMARTS.add_agent_and_switch_control /
+ * switch_control_to_agent, smarts.py:505-561, vehicle_index.py:392-457, and a bubble over a replayed history,
+ * bubble_manager.py:208-218: one recorded vehicle leaves the TrafficHistoryProvider and is a BoxChassis at the pose and
+ * speed it holds, moved by its agent's action while every other recorded vehicle keeps replaying).  A handover table
+ * beside the follow table, and a tick that reads both: with
+ *   H = tick_dev[episode mod rows][e][a]          (indexed exactly as vehicle_dev is)
+ *   driven       in an smx_step_history_handover tick that starts with env_ticks[e] = t, agent `a` is DRIVEN iff
+ *                H >= 0 && t >= H; otherwise it FOLLOWS.  The rule is stateless: the table is read every tick, so a
+ *                caller may rewrite it in place; any value is safe (it is only compared); H = 0 drives from the first
+ *                tick after the reset, H < 0 never drives.
+ *   a follower   does, word for word, what smx_step_history_agents does with it: placed on its vehicle's row of the
+ *                coming frame with SMX_S_KIN_LAST_HEADING / _LAST_DT, or it leaves (SMX_F_LEFT, SMX_HA_LEFT); its
+ *                expert action, status SMX_HA_FOLLOWING, a guard byte of 0.
+ *   a driven one does, word for word, what smx_step_continuous does with an Imitation agent, from the state it holds and
+ *                its row of actions_dev: a NaN first word = no control() call, a NaN second word = the scalar form;
+ *                under the guard it gets the placement test.  Its status byte is SMX_HA_DRIVEN, its action_dev row
+ *                NaN, NaN, 0.  It never sets SMX_F_LEFT: a driven agent whose recorded vehicle ends keeps driving.  Its
+ *                recorded twin stays hidden from the social slots (the hidden-twin rule above).
+ *   back         a driven agent that the table later turns into a follower again is put back on the recording, or
+ *                leaves if the frame lacks its vehicle: what a following tick after smx_step_continuous does.
+ *   not alive    SMX_HA_ABSENT and SMX_HA_LEFT agents are not alive: their H is ignored.
+ *   reset        the reset pass (under auto_reset, inside the tick) is unchanged: the spawn comes from the recording, the
+ *                status is FOLLOWING / ABSENT, the expert action is written; the next tick reads the new episode's row.
+ * smx_step_history_agents and smx_step_continuous behave on a sim with a handover bound exactly as without: the table is
+ * ignored.  Followers' and social rows of actions_dev are never read.
+ * smx_set_history_handover needs bound history agents (SMX_ERR_STATE otherwise); refused (SMX_ERR_INVALID): tick_dev NULL,
+ * tick_count < rows * num_envs * A.  ho = NULL unbinds; smx_set_history_agents (table or NULL), smx_set_social_history
+ * and smx_load_map drop the binding.  Waits for the device.  smx_check_history_handover is the validation alone, without
+ * a device or a handle (`hist`: rows is read).  smx_step_history_handover without a binding: SMX_ERR_STATE; with
+ * actions_dev == NULL: SMX_ERR_INVALID. */
+typedef struct smx_history_handover {
+  const int32_t* tick_dev; /* device, caller-owned, [rows][num_envs][A]; read every pass */
+  uint64_t tick_count;     /* int32 elements allocated */
+} smx_history_handover;
+enum { SMX_HA_DRIVEN = 3 }; /* a history agent driven by its action in this tick (smx_step_history_handover) */
+int smx_set_history_handover(smx_handle h, const smx_history_handover* ho);
+int smx_check_history_handover(const smx_config* cfg, const smx_social_history* hist, const smx_history_handover* ho, char* err,
+                               uint64_t err_len);
 /* Frame stacking (smx_config.frame_stack = k): for every agent the device keeps the last k frames of each bound row,
  * newest first (frame 0 is this pass's row), in a caller-owned device buffer.  At the end of every smx_reset / smx_step*
  * pass, on the caller's stream, once every row of the pass is complete (under auto_reset: after the reset pass has
@@ -789,6 +827,10 @@ int smx_step_continuous(smx_handle h, const float* actions_dev, const smx_state*
                         const smx_outputs* out, void* hip_stream);
 /* The following tick of the history agents (smx_set_history_agents, above): no actions. */
 int smx_step_history_agents(smx_handle h, const smx_state* st, const smx_spawns* sp, const smx_outputs* out, void* hip_stream);
+/* The mixed tick (smx_set_history_handover, above): every agent follows or is driven by actions[E*N][3], as its handover
+ * tick says. */
+int smx_step_history_handover(smx_handle h, const float* actions_dev, const smx_state* st, const smx_spawns* sp,
+                              const smx_outputs* out, void* hip_stream);
 /* The same tick for ActionSpaceType.Trajectory and ActionSpaceType.MPC.  trajectories[E*N][4][SMX_TRAJ_COLS] (float64,
  * device): rows x, y, heading, speed; columns 0..9 = the first ten points, column 10 = the LAST point of the
  * trajectory — all the PD controller reads, and all the MPC one does (curvature_calculation at offsets <= 4 over

@@ -143,6 +143,11 @@ class SmxHistoryAgents(C.Structure):  # smx_history_agents (smx_set_history_agen
 
 
 HA_FOLLOWING, HA_LEFT, HA_ABSENT = 0, 1, 2  # SMX_HA_*
+HA_DRIVEN = 3  # SMX_HA_DRIVEN: driven by its action in a tick of smx_step_history_handover
+
+
+class SmxHistoryHandover(C.Structure):  # smx_history_handover (smx_set_history_handover)
+    _fields_ = [("tick_dev", _p), ("tick_count", C.c_uint64)]
 
 
 class SmxSpawns(C.Structure):
@@ -208,6 +213,7 @@ EXPORTS = [
     "smx_bind_frame_stack", "smx_check_frame_stack", "smx_set_guard", "smx_check_guard",
     "smx_set_social_history", "smx_check_social_history", "smx_set_social_history_dims", "smx_check_social_history_dims",
     "smx_set_history_agents", "smx_check_history_agents", "smx_step_history_agents",
+    "smx_set_history_handover", "smx_check_history_handover", "smx_step_history_handover",
     "smx_invalidate_outputs", "smx_set_ogm_delta",
 ]
 LAUNCH_FORMS = {0: "small", 1: "large_teams", 2: "large_one_lane"}
@@ -309,6 +315,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.smx_check_history_agents.restype = C.c_int
     lib.smx_step_history_agents.argtypes = [h, C.POINTER(SmxState), C.POINTER(SmxSpawns), C.POINTER(SmxOutputs), _p]
     lib.smx_step_history_agents.restype = C.c_int
+    lib.smx_set_history_handover.argtypes = [h, C.POINTER(SmxHistoryHandover)]
+    lib.smx_set_history_handover.restype = C.c_int
+    lib.smx_check_history_handover.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxSocialHistory), C.POINTER(SmxHistoryHandover),
+                                               C.c_char_p, C.c_uint64]
+    lib.smx_check_history_handover.restype = C.c_int
+    lib.smx_step_history_handover.argtypes = [h, _p, C.POINTER(SmxState), C.POINTER(SmxSpawns), C.POINTER(SmxOutputs), _p]
+    lib.smx_step_history_handover.restype = C.c_int
     lib.smx_read_phase_ms.argtypes = [h, C.POINTER(C.c_float), _i32, C.POINTER(_i32)]
     lib.smx_read_phase_ms.restype = C.c_int
     lib.smx_set_timing.argtypes = [h, C.c_int]

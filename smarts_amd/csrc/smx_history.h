@@ -1,9 +1,9 @@
 // smx_history.h — traffic-history replay (include/smx.h, smx_set_social_history): which frame of the recorded table an
 // env replays in a pass, whether a social slot holds a vehicle there, and the row it takes its pose from, each written
 // once.  social_vehicle_step (every control form), respawn_vehicle (k_reset and the commit-time respawn) and commit_role
-// call these, and the history agents (smx_set_history_agents: respawn_vehicle, k_control_kinematic's FOLLOW form); the
-// header holds no HIP and also compiles for the host (tests/native/host_history.cpp, host_history_dims.cpp and
-// host_history_agents.cpp drive it under AddressSanitizer + UBSan).  The second half is the per-vehicle dimensions
+// call these, and the history agents (smx_set_history_agents: respawn_vehicle, k_control_kinematic's FOLLOW and HANDOVER
+// forms); the header holds no HIP and also compiles for the host (tests/native/host_history.cpp, host_history_dims.cpp,
+// host_history_agents.cpp and host_history_handover.cpp drive it under AddressSanitizer + UBSan).  The second half is the per-vehicle dimensions
 // (smx_set_social_history_dims): the id -> (length, width, height) lookup the same writers use.
 //
 // Nothing read from the two caller-owned tables can take an index out of a table: the row of start_frame / replaced is
@@ -32,6 +32,9 @@ struct HistoryDev {
   // history agents (smx_set_history_agents; follow == null: none bound): the caller's table of followed vehicle ids
   const int32_t* follow;  // [rows][num_envs][n_agents], < 0 = the agent follows nothing
   int32_t n_agents;       // agent slots of an env (num_vehicles - num_social)
+  // the handover table (smx_set_history_handover; null: none bound), indexed as follow is: the tick from which the agent
+  // is driven by its action in a tick of smx_step_history_handover, < 0 = never
+  const int32_t* handover;  // [rows][num_envs][n_agents]
 };
 
 // the row of the two per-env tables that episode `episode` reads (Python's modulo: a negative episode counts from the end)
@@ -72,6 +75,14 @@ SMX_HISTORY_FN const double* history_row(const HistoryDev& h, int64_t frame, int
 SMX_HISTORY_FN int32_t history_followed(const HistoryDev& h, int episode, int env, int agent) {
   return h.follow[((size_t)history_table_row(h, episode) * (size_t)h.num_envs + (size_t)env) * (size_t)h.n_agents + (size_t)agent];
 }
+
+// The handover tick of the same agent (only called with follow and handover bound: one index for both tables).
+SMX_HISTORY_FN int32_t history_handover(const HistoryDev& h, int episode, int env, int agent) {
+  return h.handover[((size_t)history_table_row(h, episode) * (size_t)h.num_envs + (size_t)env) * (size_t)h.n_agents + (size_t)agent];
+}
+// Is an agent whose handover tick is `handover` driven in the tick that starts with env_ticks = `env_ticks`?  Stateless:
+// the value is only compared, so any value is safe (0: from the first tick after the reset; < 0: never).
+SMX_HISTORY_FN bool history_driven(int32_t handover, int env_ticks) { return handover >= 0 && env_ticks >= handover; }
 
 // The slot that holds vehicle `id` in `frame`, -1: the frame is outside the table, the id is none (< 0), or the frame
 // lacks it.  (`replaced` is not asked: a followed vehicle is hidden from the social slots by its follower.)

@@ -443,6 +443,21 @@ inline int check_history_agents_impl(const smx_config& c, int32_t rows, const sm
   return SMX_OK;
 }
 
+// ---- The handover table (smx_set_history_handover / smx_check_history_handover) ----
+// Indexed exactly as vehicle_dev is, (episode mod rows, env, agent): the same count; the ticks it holds are only compared.
+inline int check_history_handover_impl(const smx_config& c, int32_t rows, const smx_history_handover& ho, std::string& err) {
+  if (c.num_envs <= 0 || c.num_vehicles <= 0) return refuse(err, "history handover: num_envs and num_vehicles must be > 0");
+  if (c.num_social <= 0 || c.num_social >= c.num_vehicles)
+    return refuse(err, "history handover: the configuration needs social slots (the history's) and at least one agent slot");
+  if (rows < 1) return refuse(err, "history handover: the history's rows must be >= 1");
+  if (!ho.tick_dev) return refuse(err, "history handover: tick_dev is NULL");
+  const uint64_t need = (uint64_t)rows * (uint64_t)c.num_envs * (uint64_t)(c.num_vehicles - c.num_social);
+  if (ho.tick_count < need)
+    return refuse(err, "history handover: tick " + std::to_string(ho.tick_count) + " elements declared, rows * num_envs * agents is " +
+                           std::to_string(need) + " (a short table would be an out-of-bounds device read)");
+  return SMX_OK;
+}
+
 // ---- Frame stacking (smx_bind_frame_stack / smx_check_frame_stack) ----
 // bytes per agent of a stackable source, 0 with the reason in `err`: a row of smx_outputs by its SMX_OUT_* index — stackable,
 // its sensor on, its elements times the size of its dtype — or the image by SMX_STACK_SOURCE_RGB

@@ -421,6 +421,36 @@ __device__ __forceinline__ int history_agents_absent(const KernelArgs& a, int en
   return absent;
 }
 
+// A follower's tick (k_control_kinematic's FOLLOW form for every agent, its HANDOVER form for the agents the table does
+// not drive), on the flags word and position its caller has loaded: the agent is placed on the row its recorded vehicle
+// has in the frame of the coming observation, or leaves.
+__device__ __forceinline__ void history_agent_follow(const KernelArgs& a, size_t gid, size_t total, int flags, int env, int episode, double x,
+                                                     double y) {
+  const smx_config& c = a.cfg;
+  // (no placement test under the guard: every row of the table was checked against the grids when it was bound, and a
+  // follower's byte reads 0 — also in a mixed tick, and for an agent that was driven a tick ago: it lands on a row too)
+  const int32_t v = history_followed(a.history, episode, env, (int)(gid - (size_t)env * c.num_vehicles));
+  const int64_t frame = history_frame(a.history, episode, env, a.st.env_ticks[env] + 1);
+  const int at = history_find(a.history, frame, v);
+  if (at < 0) {
+    // The vehicle has left the recording: the agent's done_this_step (agent_manager.py:153-157).  Nothing of its state
+    // is stored; the observation is built from the held pose and the tick's commit ends the agent.
+    a.st.flags[gid] = flags | SMX_F_LEFT;
+    history_agent_report(a, gid, SMX_HA_LEFT, frame, nullptr, v);
+    return;
+  }
+  const double* row = history_row(a.history, frame, at);
+  SF(SMX_S_PREV_X) = x;  // the position recorded by the previous observation
+  SF(SMX_S_PREV_Y) = y;
+  SF(SMX_S_KIN_LAST_HEADING) = SF(SMX_S_HEADING);
+  SF(SMX_S_KIN_LAST_DT) = c.dt;
+  SF(SMX_S_X) = row[0];
+  SF(SMX_S_Y) = row[1];
+  SF(SMX_S_HEADING) = row[2];  // (wrapped already, as Heading.__new__ wraps it: include/smx.h, frames_host)
+  SF(SMX_S_U) = row[3];
+  history_agent_report(a, gid, SMX_HA_FOLLOWING, frame, row, v);
+}
+
 // Scripted social vehicle (lane follower: no controller, no dynamics), on state words its caller has loaded:
 // lane, offset and crossed flag (SMX_S_MCL_X / MCL_Y / SPD_INT), SMX_S_THROTTLE and the pose's x / y.
 __device__ __forceinline__ void social_vehicle_step(const KernelArgs& a, size_t gid, size_t total, double mcl_x, double mcl_y,
@@ -1208,8 +1238,10 @@ __device__ __forceinline__ bool interpolate_trajectory(const double* tr, int n, 
 
 // (FOLLOW, Imitation only: the tick of smx_step_history_agents — every agent is placed on the row its recorded vehicle
 // has in the frame of the coming observation, Vehicle.update_state -> control(pose, speed, dt), smarts.py:919-921,
-// vehicle.py:573-579; no action is read)
-template <int SPACE, bool GUARD = false, bool FOLLOW = false>
+// vehicle.py:573-579; no action is read.  HANDOVER, Imitation only, never with FOLLOW: the tick of
+// smx_step_history_handover — each lane decides from the handover table whether its agent follows, as above, or is driven
+// by its action as in the plain form, switch_control_to_agent's BoxChassis at the held pose and speed, smarts.py:505-561)
+template <int SPACE, bool GUARD = false, bool FOLLOW = false, bool HANDOVER = false>
 __global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic(const KernelArgs a) {
   const smx_config& c = a.cfg;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
@@ -1231,31 +1263,18 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic(const KernelArg
     }
     a.guard[gid] = 0;  // (the tick may end below without a placement: no action, an action the reference raises on)
   }
-  if constexpr (FOLLOW) {
-    // (no placement test under GUARD: every row of the table was checked against the grids when it was bound)
+  if constexpr (FOLLOW || HANDOVER) {
     const int env = (int)(gid / (size_t)c.num_vehicles);
     const int episode = a.st.env_episode[env];
-    const int32_t v = history_followed(a.history, episode, env, (int)(gid - (size_t)env * c.num_vehicles));
-    const int64_t frame = history_frame(a.history, episode, env, a.st.env_ticks[env] + 1);
-    const int at = history_find(a.history, frame, v);
-    if (at < 0) {
-      // The vehicle has left the recording: the agent's done_this_step (agent_manager.py:153-157).  Nothing of its state
-      // is stored; the observation is built from the held pose and the tick's commit ends the agent.
-      a.st.flags[gid] = flags | SMX_F_LEFT;
-      history_agent_report(a, gid, SMX_HA_LEFT, frame, nullptr, v);
+    bool follows = true;
+    if constexpr (HANDOVER)
+      follows = !history_driven(history_handover(a.history, episode, env, (int)(gid - (size_t)env * c.num_vehicles)), a.st.env_ticks[env]);
+    if (follows) {
+      history_agent_follow(a, gid, total, flags, env, episode, x, y);
       return;
     }
-    const double* row = history_row(a.history, frame, at);
-    SF(SMX_S_PREV_X) = x;  // the position recorded by the previous observation
-    SF(SMX_S_PREV_Y) = y;
-    SF(SMX_S_KIN_LAST_HEADING) = SF(SMX_S_HEADING);
-    SF(SMX_S_KIN_LAST_DT) = c.dt;
-    SF(SMX_S_X) = row[0];
-    SF(SMX_S_Y) = row[1];
-    SF(SMX_S_HEADING) = row[2];  // (wrapped already, as Heading.__new__ wraps it: include/smx.h, frames_host)
-    SF(SMX_S_U) = row[3];
-    history_agent_report(a, gid, SMX_HA_FOLLOWING, frame, row, v);
-    return;
+    // a driven agent: the Imitation branch below from the state it holds — no expert label, and SMX_F_LEFT is never set
+    history_agent_report(a, gid, SMX_HA_DRIVEN, 0, nullptr, -1);
   }
   // the placement's test, ahead of its first store: held = nothing of the vehicle is stored
   auto guard_holds = [&](const KinPose& q) {
@@ -5914,6 +5933,7 @@ static void drop_social_dims(smx_handle h) {
 static void drop_history_agents(smx_handle h) {
   h->history.follow = nullptr;
   h->history.n_agents = 0;
+  h->history.handover = nullptr;  // (the handover table is indexed as the follow table is: it goes with it)
   h->ha_action = nullptr;
   h->ha_status = nullptr;
 }
@@ -6030,8 +6050,8 @@ extern "C" int smx_set_launch_strategy(smx_handle h, int strategy) {
 
 // What a call's plan (smx_plan.h) may depend on, read off the handle.  `st`: the caller's state block, for the carried
 // alive list (null: no tick is planned, only the form is asked for).
-// `follow`: the call is smx_step_history_agents.
-static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_state* st, bool follow = false) {
+// `follow`: the call is smx_step_history_agents; `handover`: smx_step_history_handover.
+static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_state* st, bool follow = false, bool handover = false) {
   PlanInputs in{};
   in.cfg = &h->cfg;
   in.launch_strategy = h->launch_strategy;
@@ -6057,6 +6077,7 @@ static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_sta
   in.history_bound = h->history.vehicle != nullptr;
   in.follow_entry = follow;
   in.ogm_mask = h->ogm_mask != nullptr && h->ogm_delta;
+  in.handover_entry = handover;
   return in;
 }
 
@@ -6500,6 +6521,27 @@ extern "C" int smx_set_history_agents(smx_handle h, const smx_history_agents* ha
   return SMX_OK;
 }
 
+extern "C" int smx_check_history_handover(const smx_config* cfg, const smx_social_history* hist, const smx_history_handover* ho, char* err,
+                                          uint64_t err_len) {
+  std::string msg;
+  const int rc = (cfg && hist && ho) ? check_history_handover_impl(*cfg, hist->rows, *ho, msg) : refuse(msg, "null config / history / history handover");
+  return report(rc, msg, err, err_len);
+}
+
+extern "C" int smx_set_history_handover(smx_handle h, const smx_history_handover* ho) {
+  if (!h) return SMX_ERR_INVALID;
+  if (ho) {
+    if (h->history.follow == nullptr) return fail(h, SMX_ERR_STATE, "smx_set_history_handover needs bound history agents (smx_set_history_agents)");
+    std::string msg;
+    const int rc = check_history_handover_impl(h->cfg, h->history.rows, *ho, msg);
+    if (rc != SMX_OK) return fail(h, rc, msg);
+  }
+  SMX_HIP(hipSetDevice(h->device));
+  SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
+  h->history.handover = ho ? ho->tick_dev : nullptr;
+  return SMX_OK;
+}
+
 extern "C" int smx_bind_frame_stack(smx_handle h, int32_t source, int32_t layout, void* stack_dev, uint64_t bytes) {
   if (!h) return SMX_ERR_INVALID;
   auto at = std::find_if(h->stacks.begin(), h->stacks.end(),
@@ -6653,6 +6695,10 @@ static void launch_control(smx_handle h, const TickPlan& p, const KernelArgs& a,
     case Control::KINEMATIC: launch(k.kinematic, p.veh_blocks, 0, stream, a); break;
     case Control::KINEMATIC_FOLLOW:  // (smx_set_history_agents holds the binding to Imitation)
       launch(p.guard ? k_control_kinematic<SMX_ACTION_SPACE_IMITATION, true, true> : k_control_kinematic<SMX_ACTION_SPACE_IMITATION, false, true>,
+             p.veh_blocks, 0, stream, a);
+      break;
+    case Control::KINEMATIC_HANDOVER:  // (the binding again; smx_step_history_handover holds actions_f32 to non-null)
+      launch(p.guard ? k_control_kinematic<SMX_ACTION_SPACE_IMITATION, true, false, true> : k_control_kinematic<SMX_ACTION_SPACE_IMITATION, false, false, true>,
              p.veh_blocks, 0, stream, a);
       break;
   }
@@ -6911,7 +6957,7 @@ static KernelArgs kernel_args(smx_handle h, const TickPlan& p, const int8_t* act
 }
 
 // which entry point a call came through (each hands over its own pointers and leaves the others null)
-enum class Entry { RESET, LANE, FLOATS, TRAJECTORY, TARGET_POSE, TRAJECTORY_WITH_TIME, HISTORY_AGENTS };
+enum class Entry { RESET, LANE, FLOATS, TRAJECTORY, TARGET_POSE, TRAJECTORY_WITH_TIME, HISTORY_AGENTS, HISTORY_HANDOVER };
 // (traj_max: columns per row of a TrajectoryWithTime action)
 static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const float* actions_f32, const double* traj,
                    const int32_t* traj_n, int32_t traj_max, const uint8_t* mask, const smx_state* st,
@@ -6921,9 +6967,13 @@ static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const
   int rc = check_buffers(h, st, sp, out);
   if (rc != SMX_OK) return rc;
   const bool is_step = entry != Entry::RESET;
-  const bool follow = entry == Entry::HISTORY_AGENTS;
+  const bool follow = entry == Entry::HISTORY_AGENTS, handover = entry == Entry::HISTORY_HANDOVER;
   if (follow) {  // (the binding holds cfg.action_space to Imitation; the tick reads no action)
     if (h->history.follow == nullptr) return fail(h, SMX_ERR_STATE, "smx_step_history_agents: no history agents are bound (smx_set_history_agents)");
+  } else if (handover) {  // (the binding holds cfg.action_space to Imitation; the driven agents' rows are read)
+    if (h->history.follow == nullptr || h->history.handover == nullptr)
+      return fail(h, SMX_ERR_STATE, "smx_step_history_handover: no handover table is bound (smx_set_history_handover)");
+    if (actions_f32 == nullptr) return fail(h, SMX_ERR_INVALID, "smx_step_history_handover: actions_dev is NULL");
   } else if (is_step) {
     const int sp_ = h->cfg.action_space;
     const bool ok = sp_ == SMX_ACTION_SPACE_LANE ? (entry == Entry::LANE && actions != nullptr)
@@ -6940,7 +6990,7 @@ static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const
                   "smx_step_trajectory_with_time: TrajectoryWithTime)");
   }
   hipStream_t stream = (hipStream_t)stream_;
-  const TickPlan p = tick_plan(plan_inputs(h, is_step, st, follow));
+  const TickPlan p = tick_plan(plan_inputs(h, is_step, st, follow, handover));
   KernelArgs a = kernel_args(h, p, actions, actions_f32, traj, traj_n, traj_max, mask, st, sp, out);
   const bool timed = h->timing && is_step && h->ev_used < 65536;
   if (timed) {
@@ -7014,6 +7064,11 @@ extern "C" int smx_step_continuous(smx_handle h, const float* actions_dev, const
 
 extern "C" int smx_step_history_agents(smx_handle h, const smx_state* st, const smx_spawns* sp, const smx_outputs* out, void* hip_stream) {
   return enqueue(h, Entry::HISTORY_AGENTS, nullptr, nullptr, nullptr, nullptr, 0, nullptr, st, sp, out, hip_stream);
+}
+
+extern "C" int smx_step_history_handover(smx_handle h, const float* actions_dev, const smx_state* st, const smx_spawns* sp,
+                                         const smx_outputs* out, void* hip_stream) {
+  return enqueue(h, Entry::HISTORY_HANDOVER, nullptr, actions_dev, nullptr, nullptr, 0, nullptr, st, sp, out, hip_stream);
 }
 
 extern "C" int smx_step_trajectory(smx_handle h, const double* trajectories_dev, const int32_t* counts_dev,

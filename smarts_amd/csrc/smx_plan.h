@@ -93,6 +93,7 @@ struct PlanInputs {
   bool dims_bound;         // smx_set_social_history_dims holds a table: ... at each vehicle's own dimensions
   bool follow_entry;       // the call is smx_step_history_agents: the agents are placed on their recorded vehicles' rows
   bool ogm_mask;           // the handle holds the OGM tiles' piece mask and smx_set_ogm_delta has not switched it off
+  bool handover_entry;     // the call is smx_step_history_handover: each agent follows or is driven, as its handover tick says
 };
 
 enum class AliveList : uint8_t { NONE, CARRIED, BUILD };  // BUILD: k_alive_list ahead of the tick
@@ -100,8 +101,9 @@ enum class AliveList : uint8_t { NONE, CARRIED, BUILD };  // BUILD: k_alive_list
 // large batches: candidate paths by teams of four, then law + physics with one lane per vehicle (PATHS_LAW), the float
 // spaces and Trajectory the law alone (LAW); FAST_LISTED: one lane per vehicle, the rest through the slow list;
 // KINEMATIC: the kinematic spaces' k_control_kinematic, one lane per vehicle in either form (no candidate paths, no
-// control slow list); KINEMATIC_FOLLOW: its FOLLOW form, the tick of smx_step_history_agents — the same launch
-enum class Control : uint8_t { NONE, ONE, ONE_LDS, PATHS_LAW, LAW, FAST_LISTED, KINEMATIC, KINEMATIC_FOLLOW };
+// control slow list); KINEMATIC_FOLLOW: its FOLLOW form, the tick of smx_step_history_agents — the same launch;
+// KINEMATIC_HANDOVER: its HANDOVER form, the tick of smx_step_history_handover — the same launch again
+enum class Control : uint8_t { NONE, ONE, ONE_LDS, PATHS_LAW, LAW, FAST_LISTED, KINEMATIC, KINEMATIC_FOLLOW, KINEMATIC_HANDOVER };
 static constexpr bool smx_kinematic_space(int action_space) {
   // (one mask test; smx_create holds action_space to 0 .. SMX_ACTION_SPACE_IMITATION)
   constexpr unsigned kinematic = (1u << SMX_ACTION_SPACE_TARGET_POSE) | (1u << SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME) |
@@ -242,7 +244,7 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
   if (!in.is_step)
     p.control = Control::NONE;
   else if (smx_kinematic_space(c.action_space))
-    p.control = in.follow_entry ? Control::KINEMATIC_FOLLOW : Control::KINEMATIC;
+    p.control = in.handover_entry ? Control::KINEMATIC_HANDOVER : in.follow_entry ? Control::KINEMATIC_FOLLOW : Control::KINEMATIC;
   else if (!small && in.ctrl_blob)
     p.control = !lane_space ? Control::LAW : one_lane ? Control::FAST_LISTED : Control::PATHS_LAW;
   else

@@ -735,6 +735,7 @@ class BatchedSim:
 
     def _drop_history_agents(self):
         self.history_agents = None
+        self.history_handover = None  # (the library drops the handover table with the follow table)
         self.out.pop("history_agent_status", None)
         self.out.pop("expert_action", None)
 
@@ -752,7 +753,52 @@ class BatchedSim:
         self.out["learner"] = self._learner[self._learner_k]
         return self.out
 
+    def set_history_handover(self, ticks: Optional[torch.Tensor]):
+        """Bind the handover table (``smx_set_history_handover``; needs bound history agents): int32 ``[R, E, A]`` on the
+        sim's device, indexed exactly as ``set_history_agents``' ``vehicle``.  In a ``step_history_handover(actions)``
+        tick that starts with ``env_ticks[e] = t``, agent ``a`` of env ``e`` is driven by its action iff
+        ``H = ticks[k mod R, e, a]`` has ``H >= 0 and t >= H``; otherwise it follows its recorded vehicle.  The tensor
+        stays the caller's and is read by every such tick: rewriting it in place takes effect with the next one, and any
+        value is safe.  ``step_history_agents()`` and ``step(actions)`` ignore it.  ``ticks=None`` unbinds; so does
+        everything that drops the history agents."""
+        if ticks is None:
+            nat.check(self.lib, self.handle, self.lib.smx_set_history_handover(self.handle, None), "smx_set_history_handover")
+            self.history_handover = None
+            return
+        A = self.N - self.cfg.num_social
+        if (ticks.dtype != torch.int32 or ticks.device != self.device or not ticks.is_contiguous() or ticks.ndim != 3
+                or tuple(ticks.shape[1:]) != (self.E, A) or ticks.shape[0] < 1):
+            raise ValueError(f"ticks must be a contiguous int32 tensor of shape [R, {self.E}, {A}] on {self.device}")
+        if self.history_agents is not None and ticks.shape[0] != self.history_agents.shape[0]:
+            raise ValueError(f"ticks has {ticks.shape[0]} rows, the bound follow table {self.history_agents.shape[0]}")
+        ho = nat.SmxHistoryHandover()
+        ho.tick_dev, ho.tick_count = ticks.data_ptr(), int(ticks.numel())
+        nat.check(self.lib, self.handle, self.lib.smx_set_history_handover(self.handle, C.byref(ho)), "smx_set_history_handover")
+        self.history_handover = ticks  # (read by every mixed tick: lives as long as the binding)
+
+    def step_history_handover(self, actions: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """One tick in which every agent follows its recorded vehicle or is driven by its row of ``actions`` — float32
+        ``(E, N, 3)`` in ``step``'s Imitation layout — as the handover table says (``smx_step_history_handover``).
+        Followers' and social rows of ``actions`` are ignored.  ``out["history_agent_status"]`` reads ``HA_DRIVEN`` for a
+        driven agent and its ``out["expert_action"]`` row NaN, NaN, 0."""
+        if not self._was_reset:
+            raise RuntimeError("step() before reset()")
+        if actions.dtype != torch.float32 or actions.device != self.device or not actions.is_contiguous():
+            actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(actions.shape) != (self.E, self.N, 3):
+            raise ValueError(f"actions must have shape {(self.E, self.N, 3)}, got {tuple(actions.shape)}")
+        self._out.learner = self.next_learner_block.data_ptr()
+        rc = self.lib.smx_step_history_handover(self.handle, actions.data_ptr(), C.byref(self._st), C.byref(self._sp),
+                                                C.byref(self._out), self._stream_ptr())
+        if rc != 0:  # (no binding: refused before anything was launched, the learner block does not flip)
+            self._out.learner = self.out["learner"].data_ptr()
+        nat.check(self.lib, self.handle, rc, "smx_step_history_handover")
+        self._learner_k ^= 1
+        self.out["learner"] = self._learner[self._learner_k]
+        return self.out
+
     history_agents = None
+    history_handover = None
     history_dims = False
     traffic_history = None
     history_start_frames = None

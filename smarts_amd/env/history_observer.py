@@ -7,6 +7,10 @@ in that frame, and the social slots replay the rest of the history.  ``reset()``
 ``Observation`` of every followed vehicle under the reference's agent id ``Agent-history-vehicle-<id>``, built from the
 interface's sensors like any agent's, and ``expert_actions()`` the Imitation action that takes each vehicle to its next
 recorded frame: a behaviour-cloning dataset is the two side by side.
+
+With ``handover`` the followers are handed over to actions one by one (``BatchedSim.set_history_handover``, the
+reference's ``SMARTS.switch_control_to_agent``): a log-replay warm-up, then ``step(actions)`` drives the agents whose
+handover tick has come while every other vehicle keeps replaying.
 """
 from __future__ import annotations
 
@@ -58,11 +62,14 @@ class HistoryObserver:
     observe, one env each (``None``: every vehicle of the table); ``num_envs``: at least ``len(vehicle_ids)`` (the
     default); ``num_agents``: agent slots per env — 1 observes the env's own vehicle alone, more also the other
     vehicles present in its first frame.  An env ends when every followed vehicle has left the recording (or ended by
-    the interface's done criteria); nothing restarts."""
+    the interface's done criteria); nothing restarts.  ``handover`` (default ``None``: nobody is ever driven, every method
+    behaves as without it): an int — the recorded ticks before every agent drives —, a mapping ``{vehicle id: ticks}``
+    (vehicles it lacks are never driven), or a ready int32 table ``[1, E, A]`` (``TrafficHistoryTable.handover_ticks``
+    makes one from zone entry frames: a bubble)."""
 
     def __init__(self, scenario: str, table_or_path, agent_interface: AgentInterface, vehicle_ids: Optional[Sequence[int]] = None,
                  num_envs: Optional[int] = None, dt: float = 0.1, num_agents: int = 1, device: str = "cuda:0",
-                 waypoint_window: Optional[Tuple[int, int]] = (4, 20), seed: int = 0):
+                 waypoint_window: Optional[Tuple[int, int]] = (4, 20), seed: int = 0, handover=None):
         import torch
 
         from ..engine import BatchedSim, make_spawns
@@ -92,6 +99,9 @@ class HistoryObserver:
         self.start_frames, self.followed = start, vehicle
         self.sim.set_traffic_history(table, torch.from_numpy(start).to(self.sim.device))
         self.sim.set_history_agents(torch.from_numpy(vehicle).to(self.sim.device))
+        self.handover = None if handover is None else self._handover_table(handover)
+        if self.handover is not None:
+            self.sim.set_history_handover(torch.from_numpy(self.handover).to(self.sim.device))
         road_ids = [self.cm.road_ids[r] for r in self.cm.lane_road]
         names = [f"follower-{a}" for a in range(self.A)] + [f"social-{k}" for k in range(self.S)]
         self.builder = _FollowerNames(
@@ -107,26 +117,85 @@ class HistoryObserver:
         v = int(self.followed[0, env, agent])
         return f"{AGENT_PREFIX}{HISTORY_VEHICLE_PREFIX}{v}" if v >= 0 else None
 
+    def _handover_table(self, handover) -> np.ndarray:
+        """int32 ``[1, E, A]`` from an int, a mapping vehicle id -> ticks, or a ready table."""
+        if isinstance(handover, (int, np.integer)):
+            return np.where(self.followed >= 0, int(handover), -1).astype(np.int32)
+        if hasattr(handover, "keys"):
+            table = np.full(self.followed.shape, -1, dtype=np.int32)
+            for idx in np.ndindex(*self.followed.shape):
+                v = int(self.followed[idx])
+                if v >= 0 and v in handover:
+                    table[idx] = int(handover[v])
+            return table
+        table = np.ascontiguousarray(handover, dtype=np.int32)
+        if table.shape != self.followed.shape:
+            raise ValueError(f"a handover table must have shape {self.followed.shape}, got {table.shape}")
+        return table
+
+    def driven(self) -> List[List[str]]:
+        """Per env, the ids of the agents the next ``step`` drives: alive, and their handover tick has come."""
+        if self.handover is None:
+            return [[] for _ in range(self.E)]
+        import torch
+
+        torch.cuda.synchronize(self.sim.device)
+        ticks = self.sim.env_ticks.cpu().numpy()
+        alive = (self.sim.flags[:, :self.A].cpu().numpy() & nat.F_ALIVE) != 0
+        return [[self.agent_id(e, a) for a in range(self.A)
+                 if alive[e, a] and self.followed[0, e, a] >= 0 and 0 <= self.handover[0, e, a] <= ticks[e]] for e in range(self.E)]
+
+    def _action_rows(self, actions) -> np.ndarray:
+        """float32 ``(E, N, 3)`` in ``BatchedSim.step``'s Imitation layout from ``{agent id: (acceleration,
+        angular_velocity) | speed}`` — one mapping for every env, or a sequence of one per env; a missing id = no action."""
+        rows = np.full((self.E, self.A + self.S, 3), np.nan, dtype=np.float32)
+        rows[..., 2] = 0.0
+        if actions is None:
+            return rows
+        per_env = [actions] * self.E if hasattr(actions, "keys") else list(actions)
+        if len(per_env) != self.E:
+            raise ValueError(f"{len(per_env)} action mappings for {self.E} envs")
+        for e, given in enumerate(per_env):
+            for a in range(self.A):
+                act = given.get(self.agent_id(e, a)) if given else None
+                if act is None:
+                    continue
+                if np.ndim(act) == 0:
+                    rows[e, a, 0] = float(act)  # the scalar form: a speed to set (the second word stays NaN)
+                else:
+                    rows[e, a, 0], rows[e, a, 1] = float(act[0]), float(act[1])
+        return rows
+
     def reset(self):
         out = self.sim.reset()
         self._was_reset = True
         return self._collect(out)
 
-    def step(self):
+    def step(self, actions=None):
+        """One tick.  ``actions`` (only with ``handover``): ``{agent id: (acceleration, angular_velocity) | speed}`` for
+        the agents ``driven()`` names — one mapping for every env or a sequence of one per env; a missing id means no
+        action, and what is given for a follower is ignored."""
         if not self._was_reset:
             raise RuntimeError("step() before reset()")
-        return self._collect(self.sim.step_history_agents())
+        if self.handover is None:
+            if actions is not None:
+                raise ValueError("actions need a handover: without one every agent follows its recorded vehicle")
+            return self._collect(self.sim.step_history_agents())
+        import torch
+
+        return self._collect(self.sim.step_history_handover(torch.from_numpy(self._action_rows(actions)).to(self.sim.device)))
 
     def expert_actions(self) -> List[Dict[str, np.ndarray]]:
         """Per env ``{agent id: float32 (acceleration, angular_velocity)}`` of the followers still on the recording: the
-        action that takes the vehicle from the frame just observed to the next (NaN, NaN where that frame lacks it)."""
+        action that takes the vehicle from the frame just observed to the next (NaN, NaN where that frame lacks it, and
+        for an agent the last tick drove: nobody labels a driven agent)."""
         import torch
 
         torch.cuda.synchronize(self.sim.device)
         act = self.sim.out["expert_action"].cpu().numpy()
         status = self.sim.out["history_agent_status"].cpu().numpy()
         return [{self.agent_id(e, a): act[e, a, :2].copy() for a in range(self.A)
-                 if self.followed[0, e, a] >= 0 and status[e, a] == nat.HA_FOLLOWING} for e in range(self.E)]
+                 if self.followed[0, e, a] >= 0 and status[e, a] in (nat.HA_FOLLOWING, nat.HA_DRIVEN)} for e in range(self.E)]
 
     def _collect(self, out):
         import torch

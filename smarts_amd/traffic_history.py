@@ -303,6 +303,38 @@ class TrafficHistoryTable:
             vehicle[0, k, :] = ([vid] + others + [-1] * num_agents)[:num_agents]
         return start, vehicle
 
+    # ------------------------------------------------------------------ handover (BatchedSim.set_history_handover)
+    def zone_entry_frames(self, pos: Sequence[float], size: Sequence[float]) -> Dict[int, int]:
+        """``{vehicle id: the first frame whose recorded position lies strictly inside the zone}``: the axis-aligned
+        rectangle of the reference's ``PositionalZone(pos, size)`` (sstudio/types.py:686-700) — centre ``pos``, extent
+        ``size[0]`` along x and ``size[1]`` along y.  A point on the boundary is outside, as ``Point.within`` has it; a
+        vehicle that never enters is absent from the result.  With ``handover_ticks`` a bubble over a replayed history
+        is one host pass: no polygon test on the device."""
+        x0, x1 = float(pos[0]) - float(size[0]) / 2, float(pos[0]) + float(size[0]) / 2
+        y0, y1 = float(pos[1]) - float(size[1]) / 2, float(pos[1]) + float(size[1]) / 2
+        x, y = self.frames[..., 0], self.frames[..., 1]
+        inside = (self.vehicle >= 0) & (x > x0) & (x < x1) & (y > y0) & (y < y1)
+        out: Dict[int, int] = {}
+        for k, s in zip(*np.nonzero(inside)):  # (row-major: ascending frames)
+            out.setdefault(int(self.vehicle[k, s]), int(k))
+        return dict(sorted(out.items()))
+
+    @staticmethod
+    def handover_ticks(vehicle: np.ndarray, start_frames: np.ndarray, frame_of: Dict[int, int]) -> np.ndarray:
+        """The handover table of ``BatchedSim.set_history_handover``, int32 ``[R, E, A]``, for the follow table
+        ``vehicle`` ``[R, E, A]`` and ``start_frames`` ``[R, E]``: agent ``a`` of env ``e`` is driven from the tick at
+        which its env shows frame ``frame_of[v]`` of its vehicle ``v`` — ``max(frame_of[v] - start_frames[r, e], 0)`` —
+        and never (``-1``) where ``v < 0`` or ``v`` has no entry in ``frame_of``."""
+        vehicle, start_frames = np.asarray(vehicle), np.asarray(start_frames)
+        if vehicle.ndim != 3 or start_frames.shape != vehicle.shape[:2]:
+            raise ValueError(f"vehicle must be [R, E, A] and start_frames [R, E], got {vehicle.shape} and {start_frames.shape}")
+        out = np.full(vehicle.shape, -1, dtype=np.int32)
+        for idx in np.ndindex(*vehicle.shape):
+            v = int(vehicle[idx])
+            if v >= 0 and v in frame_of:
+                out[idx] = min(max(int(frame_of[v]) - int(start_frames[idx[:2]]), 0), np.iinfo(np.int32).max)
+        return out
+
 
 def read_sqlite(path: str):
     """(vehicle_rows, trajectory_rows) of a converted dataset, in the column order ``from_rows`` takes."""
