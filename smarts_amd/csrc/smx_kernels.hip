@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "smx_guard.h"
+#include "smx_handle.h"
 #include "smx_history.h"
 #include "smx_host.h"
 #include "smx_plan.h"
@@ -130,7 +131,6 @@ enum {
 // segment (g / 64) % 8 — the workgroups of 64-vehicle env groups then add to their own XCD's counter — and list
 // position i holds entry ((i / 512) * 64 + i % 64) of segment (i / 64) % 8: a wavefront's 64 positions are 64
 // consecutive entries of one segment, and a segment has exactly as many positions below E*N as it can have entries.
-#define SMX_SEG_STRIDE 32  // ints between two segment counters (a cache line each)
 __device__ __forceinline__ size_t seg_position(const size_t seg, const size_t off) {
   return ((off >> 6) << 9) | (seg << 6) | (off & 63);
 }
@@ -993,11 +993,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(2, 8))) __launch_bounds__(SMX
 // and k_control_law runs law + physics with one lane per vehicle: a quarter of the wavefronts, every lane
 // busy.  Small batches keep the single launch (one wavefront's latency is what they wait for).
 // =================================================================================
-struct CtrlHandoff {
-  double* path;  // [SMX_CTRL_WPS][3][E*N]: x, y, heading of the wanted path's waypoints
-  int32_t* n;    // [E*N] waypoints held; 0 = no path found (the reference asserts; the last command is kept)
-};
-
 template <int SPACE, bool GUARD>
 __device__ __forceinline__ void control_paths_for(const KernelArgs& a, const CtrlHandoff& ho, const size_t gid, int* knots) {
   const smx_config& c = a.cfg;
@@ -5809,146 +5804,6 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_reset_env(const KernelArgs a) {
 // =================================================================================
 // C-ABI (include/smx.h)
 // =================================================================================
-// sqrt(d2) <= radius without the square root: the correctly rounded root does not decrease with its argument, so
-// the test holds exactly for the squared distances up to a threshold — the largest double whose rounded root is
-// still <= radius (found from radius * radius by stepping a few units in the last place).  k_observe takes the
-// 32 x 32 distances of an env per tick; the root and its comparison were twenty instructions each.
-static double radius_threshold(double radius) {
-  if (!(radius >= 0.0)) return -1.0;           // (unlimited: the kernels do not look at it)
-  if (std::isinf(radius)) return radius;
-  double t = radius * radius;
-  if (std::isinf(t)) return t;
-  while (t > 0.0 && std::sqrt(t) > radius) t = std::nextafter(t, 0.0);
-  for (;;) {
-    const double up = std::nextafter(t, INFINITY);
-    if (std::isinf(up) || !(std::sqrt(up) <= radius)) break;
-    t = up;
-  }
-  return t;
-}
-
-// (created by `new smx_handle_s()`: every member without an initialiser starts as zero)
-struct smx_handle_s {
-  smx_config cfg;
-  int device;
-  bool map_loaded;
-  MapDev map;
-  void* map_blob;  // one device allocation holding every table
-  size_t map_bytes;
-  void* knots_blob;  // KnotLists of the waypoints sensor (k_wp_walk -> k_waypoints_tables)
-  void* spill_blob;  // k_waypoints_emit's overflow area (KernelArgs::wp_spill)
-  int wp_pool_limit = SMX_WPE_POOL; // records of k_waypoints_emit's LDS pool in use (smx_debug_set_wp_pool)
-  // the map's knot table (k_knot_table, at smx_load_map: the map and cfg.wp_lookahead are what it depends on), its
-  // counters — [0] rows tabled, [1] rows on one road, then as 64 bits at [2] the path lanes served
-  // (smx_debug_set_knot_table(h, 2)) — and the developer switch
-  KnotRow* knot_table;
-  int32_t* knot_stats;
-  int knot_table_mode = 1;  // 0: the walked lists; 1: the table; 2: the table, counting what it serves
-  int32_t* alive_blob;  // [total] alive list + two counters (ticks alternate), large batches
-  uint8_t* pending_blob;  // [total] seed_pending
-  int32_t* slow_blob;   // [4][total] slow lists of the fast kernels (scan facts, scan seeds, control, waypoint rows) + [2][4] counters (ticks alternate)
-  double* scan_carry;   // [6][total]: seeds_carry (x, y, d10^2, d1^2) | facts_carry (x, y) of the seeded scan
-  int alive_parity;
-  KnotLists knots;
-  void* ctrl_blob;   // CtrlHandoff of the two-launch controller (k_control_paths -> k_control_law)
-  CtrlHandoff ctrl;
-  int32_t* status_dev;  // SMX_DEVICE_* bits raised by the kernels
-  // Large batches: the sensor kernels of a tick are independent of each other (they read the pose and write
-  // disjoint rows) and are bound by different things — waypoint chain walks by load latency, OGM tiles by
-  // their own write stream — so they are enqueued on side streams between two events and overlap.
-  hipStream_t side[3];
-  hipEvent_t ev_fork, ev_fork_grid, ev_join[3];
-  bool side_ready;
-  const double* lidar_rays;
-  smx_via* vias_dev;
-  int32_t* via_off_dev;
-  int32_t n_vias;
-  void* missions_blob;      // device copy of smx_set_missions: goals | last roads | route positions | lane table
-  std::vector<int32_t> host_lane_road, host_lane_out_off, host_lane_out_idx;  // kept for smx_set_missions
-  void* goals_blob;         // device copy of smx_set_mission_goals: goal kinds | lane end headings | dead-end lanes
-  std::vector<int32_t> host_route_last;  // smx_set_missions' last roads (-1: empty route), kept for smx_set_mission_goals
-  MissionsDev missions;
-  // lane_following_controller.py:426-430: place_poles gains clipped to [0.02, 0.04] / [3.4, 4.1];
-  // for the sedan they saturate at (0.04, 3.4) for both Lane-space target speeds.
-  double heading_gain_pos = 0.04, lateral_gain_pos = 3.4;
-  double nb_d2_max;
-  int slow_blocks = SMX_SLOW_BLOCKS;  // grid of the slow lists' kernels (smx_load_map)
-  // the alive list k_tail built for the next tick: counters of parity `seg_parity` (the other parity's are zero), built
-  // from the flags of `list_state`; the next large-form tick takes it instead of launching k_alive_list
-  bool list_ready;
-  int seg_parity;
-  smx_state list_state;
-  int group_parity;  // k_tail's counter of env groups with new vehicles (the other one is zero)
-  bool map_junctions;  // lanes of the map split (some lanepoint has several successors)
-  double dagm_reach;  // half the widest lane width of the loaded map
-  uint8_t* guard_out;  // smx_set_guard: the caller's byte buffer (null: guard off), its margin and the box of the loaded map
-  uint64_t guard_count;
-  double guard_margin = SMX_GUARD_MARGIN_DEFAULT;
-  GuardBox guard_box = {1.0, 1.0, 0.0, 0.0};
-  uint8_t* rgb_out;   // smx_set_rgb_output: the caller's image buffer (null: none bound) and the bytes it holds
-  uint64_t rgb_count;
-  void* history_blob;  // smx_set_social_history: device copy of the table, frames | vehicle ids (null: none bound)
-  HistoryDev history;  // ... and what the kernels get (vehicle null: none bound; follow: smx_set_history_agents' table)
-  float* ha_action;    // smx_set_history_agents: the caller's optional expert-action and status rows
-  uint8_t* ha_status;
-  int32_t history_max_id;  // the largest vehicle id of the bound table (-1: every cell empty)
-  // OGM delta stores (KernelArgs::ogm_mask): the tiles' piece mask, allocated with the handle when the OGM sensor is on.
-  // The caller's out.ogm arrives with every call, so the masks describe the buffer of the last call only: `ogm_rows` is
-  // that pointer, and a call that brings another one — or the first call, or the one after smx_invalidate_outputs /
-  // smx_set_ogm_delta — sets every bit ahead of its pass (ogm_known false) and so stores whole tiles.
-  unsigned long long* ogm_mask;
-  size_t ogm_mask_bytes;
-  const uint8_t* ogm_rows;
-  bool ogm_known;
-  bool ogm_delta = true;  // smx_set_ogm_delta
-  void* dims_blob;      // smx_set_social_history_dims: device copy of the table | the triple per vehicle (null: none bound)
-  HistoryDimsDev dims;  // ... and what the kernels get (table null: none bound)
-  struct StackBinding {  // smx_bind_frame_stack: one caller-owned stack per (source, layout)
-    int32_t source, layout;
-    uint8_t* dst;
-    uint64_t bytes;
-    uint32_t row;  // bytes per agent and frame (the configuration's: it does not change while the handle lives)
-  };
-  std::vector<StackBinding> stacks;
-  int debug_skip;
-  int launch_strategy = SMX_LAUNCH_AUTO;  // SMX_LAUNCH_*
-  bool timing;
-  std::vector<hipEvent_t> ev_pool;  // pairs: [2*i] start, [2*i+1] stop
-  size_t ev_used;                   // pairs recorded since the last read
-  bool phase_timing;
-  std::vector<hipEvent_t> ph_pool;  // SMX_PHASE_COUNT + 1 boundary events per step
-  size_t ph_used;
-  std::string err;
-};
-
-static thread_local std::string g_create_err;  // the reason of this thread's last failed smx_create
-
-// the per-vehicle dimensions go with the history they were checked against (the caller has waited for the device)
-static void drop_social_dims(smx_handle h) {
-  if (h->dims_blob) (void)hipFree(h->dims_blob);
-  h->dims_blob = nullptr;
-  h->dims = HistoryDimsDev{};
-}
-// ... and so do the history agents (every buffer is the caller's)
-static void drop_history_agents(smx_handle h) {
-  h->history.follow = nullptr;
-  h->history.n_agents = 0;
-  h->history.handover = nullptr;  // (the handover table is indexed as the follow table is: it goes with it)
-  h->ha_action = nullptr;
-  h->ha_status = nullptr;
-}
-
-static int fail(smx_handle h, int code, const std::string& msg) {
-  if (h) h->err = msg;
-  return code;
-}
-
-#define SMX_HIP(call)                                                                         \
-  do {                                                                                        \
-    hipError_t e__ = (call);                                                                  \
-    if (e__ != hipSuccess) return fail(h, SMX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-  } while (0)
-
 extern "C" const char* smx_version(void) { return "smarts-mi355x 0.2 (gfx950)"; }
 
 #ifdef SMX_DEBUG_TIMING
@@ -5992,53 +5847,27 @@ extern "C" uint64_t smx_struct_size(int which) {
   }
 }
 
-// alive_blob: [E*N] alive list, k_alive_list's two counters, k_tail's [2][8] segment counters and [2] counters of env
-// groups with new vehicles (SMX_SEG_STRIDE apart), the list of those groups
-struct AliveLayout {
-  size_t flat, seg, group_count, groups, size;
-};
-static AliveLayout alive_layout(const smx_config& c) {
-  AliveLayout l;
-  const size_t total = (size_t)c.num_envs * c.num_vehicles;
-  l.flat = total;
-  l.seg = (total + 2 + SMX_SEG_STRIDE - 1) / SMX_SEG_STRIDE * SMX_SEG_STRIDE;
-  l.group_count = l.seg + 2 * 8 * SMX_SEG_STRIDE;
-  l.groups = l.group_count + 2 * SMX_SEG_STRIDE;
-  l.size = l.groups + (size_t)c.num_envs;  // (at least one env a group)
-  return l;
-}
-
 // the constants smx_host.h decides with are the device side's
 static_assert(SMX_HOST_BLOCK == SMX_BLOCK && SMX_HOST_WP_LANES == SMX_WP_LANES && SMX_HOST_MAX_KNOTS == SMX_MAX_KNOTS &&
                   SMX_HOST_SLOW_BLOCKS == SMX_SLOW_BLOCKS && SMX_HOST_STACK_BLOCK == SMX_STACK_BLOCK,
               "smx_host.h mirrors these");
 
-// On failure no handle is left behind for the caller to remember to destroy.
-extern "C" int smx_create(const smx_config* cfg, int device, smx_handle* out) {
-  if (out) *out = nullptr;
-  if (!cfg || !out) return refuse(g_create_err, "smx_create: null config or handle pointer");
-  if (const char* why = config_error(*cfg)) return refuse(g_create_err, why);
-  const hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return refuse(g_create_err, std::string("hipSetDevice: ") + hipGetErrorString(e), SMX_ERR_HIP);
-  smx_handle h = new (std::nothrow) smx_handle_s();
-  if (!h) return refuse(g_create_err, "out of memory", SMX_ERR_NOMEM);
-  h->cfg = *cfg;
-  h->device = device;
-  h->nb_d2_max = radius_threshold(h->cfg.nb_radius);
-  if (h->cfg.sensors & SMX_SENSOR_OGM) {  // the OGM tiles' piece mask; its bits are set by the first call (ogm_known)
-    h->ogm_mask_bytes = (size_t)cfg->num_envs * cfg->num_vehicles * smx_ogm_mask_words((size_t)cfg->ogm_width * cfg->ogm_height) * sizeof(unsigned long long);
-    const hipError_t em = hipMalloc((void**)&h->ogm_mask, h->ogm_mask_bytes);
-    if (em != hipSuccess) {
-      h->ogm_mask = nullptr;
-      smx_destroy(h);
-      return refuse(g_create_err, std::string("hipMalloc (OGM piece mask): ") + hipGetErrorString(em), SMX_ERR_HIP);
-    }
-  }
-#ifdef SMX_DEBUG_TIMING
-  if (const char* dbg = getenv("SMX_DEBUG_SKIP")) h->debug_skip = atoi(dbg);
-#endif
-  *out = h;
+// the map's knot table, for load_map_impl (smx_handle.h)
+static int build_knot_table(smx_handle h, KnotRow* table) {
+  hipLaunchKernelGGL(k_knot_table, dim3(smx_blocks((size_t)h->map.n_lanepoints)), dim3(SMX_BLOCK), 0, 0, h->map, (int)h->cfg.wp_lookahead,
+                     table, h->knot_stats.get<int32_t>());
+  SMX_HIP(hipGetLastError());
+  SMX_HIP(hipDeviceSynchronize());
   return SMX_OK;
+}
+
+extern "C" int smx_create(const smx_config* cfg, int device, smx_handle* out) {
+  const int rc = create_impl(cfg, device, out, KernelSide{SMX_WPE_POOL, SMX_WPE_SPILL_GROUP_BYTES, SMX_SIDE_PRIO, build_knot_table});
+#ifdef SMX_DEBUG_TIMING
+  if (const char* dbg = getenv("SMX_DEBUG_SKIP"))
+    if (rc == SMX_OK) (*out)->debug_skip = atoi(dbg);
+#endif
+  return rc;
 }
 
 extern "C" int smx_set_launch_strategy(smx_handle h, int strategy) {
@@ -6060,23 +5889,23 @@ static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_sta
   in.routed = h->missions.route_last != nullptr;
   in.is_step = is_step;
   in.phase_timing = h->phase_timing && h->ph_used < 16384;
-  in.side_ready = h->side_ready;
+  in.side_ready = h->streams.ready;
   in.list_carried = st && h->list_ready && std::memcmp(&h->list_state, st, sizeof(smx_state)) == 0;
   in.debug_skip = (SMX_SKIP(*h, SMX_SKIP_FORCE_SMALL) ? SMX_SKIP_FORCE_SMALL : 0) |
                   (SMX_SKIP(*h, SMX_SKIP_FORCE_SCAN_SPLIT) ? SMX_SKIP_FORCE_SCAN_SPLIT : 0);
-  in.alive_blob = h->alive_blob != nullptr;
-  in.knots_blob = h->knots_blob != nullptr;
-  in.knot_table = h->knot_table != nullptr && h->knot_table_mode != 0;
-  in.ctrl_blob = h->ctrl_blob != nullptr;
-  in.pending_blob = h->pending_blob;
-  in.slow = SlowLists{h->slow_blob, (size_t)h->cfg.num_envs * h->cfg.num_vehicles};
+  in.alive_blob = (bool)h->alive_blob;
+  in.knots_blob = (bool)h->knots_blob;
+  in.knot_table = h->knot_table && h->knot_table_mode != 0;
+  in.ctrl_blob = (bool)h->ctrl_blob;
+  in.pending_blob = h->pending_blob.get<uint8_t>();
+  in.slow = SlowLists{h->slow_blob.get<int32_t>(), (size_t)h->cfg.num_envs * h->cfg.num_vehicles};
   in.slow_parity = h->alive_parity;
   in.frame_stack_bound = !h->stacks.empty();
   in.guard_bound = h->guard_out != nullptr;
   in.dims_bound = h->dims.table != nullptr;
   in.history_bound = h->history.vehicle != nullptr;
   in.follow_entry = follow;
-  in.ogm_mask = h->ogm_mask != nullptr && h->ogm_delta;
+  in.ogm_mask = h->ogm_mask && h->ogm_delta;
   in.handover_entry = handover;
   return in;
 }
@@ -6094,214 +5923,15 @@ extern "C" int smx_set_controller_gains(smx_handle h, double heading_gain, doubl
   return SMX_OK;
 }
 
-extern "C" int smx_load_map(smx_handle h, const smx_map_tables* t) {
-  if (!h || !t) return SMX_ERR_INVALID;
-  if (const char* why = map_tables_error(*t)) return fail(h, SMX_ERR_INVALID, why);
-  // a bound guard stays bound: its margin against this map's cells (smx_guard.h), its box recomputed below
-  if (h->guard_out && !guard_map_ok(*t, h->guard_margin))
-    return fail(h, SMX_ERR_INVALID, "state guard: with this margin a cell index of this map's grids would not fit (smx_guard.h, SMX_GUARD_INDEX_MAX)");
-  SMX_HIP(hipSetDevice(h->device));
-  h->dagm_reach = map_dagm_reach(*t);
-  h->map_junctions = map_lanes_split(*t);
-  h->slow_blocks = slow_list_blocks(h->map_junctions, (size_t)h->cfg.num_envs * h->cfg.num_vehicles);
-  BlobWriter w;
-#define ADD(field, type, count) const size_t off_##field = w.add(t->field, (size_t)(count) * sizeof(type));
-  SMX_MAP_TABLES(ADD, *t)
-#undef ADD
-  if (h->map_blob) {
-    (void)hipFree(h->map_blob);
-    h->map_blob = nullptr;
-  }
-  SMX_HIP(hipMalloc(&h->map_blob, w.host.size()));
-  SMX_HIP(hipMemcpy(h->map_blob, w.host.data(), w.host.size(), hipMemcpyHostToDevice));
-  h->map_bytes = w.host.size();
-  char* base = (char*)h->map_blob;
-  MapDev& m = h->map;
-  m = *t;  // scalars; every pointer is re-pointed into the device blob below
-#define PTR(field, type, count) m.field = (const type*)(base + off_##field);
-  SMX_MAP_TABLES(PTR, *t)
-#undef PTR
-  const size_t nl = t->n_lanes;
-  h->host_lane_road.assign(t->lane_road, t->lane_road + nl);
-  h->host_lane_out_off.assign(t->lane_out_off, t->lane_out_off + nl + 1);
-  h->host_lane_out_idx.assign(t->lane_out_idx, t->lane_out_idx + t->lane_out_off[nl]);
-  // missions name roads of the map they were set for: a new map starts without any
-  if (h->missions_blob) (void)hipFree(h->missions_blob);
-  h->missions_blob = nullptr;
-  if (h->goals_blob) (void)hipFree(h->goals_blob);  // goal kinds go with the missions they refine
-  h->goals_blob = nullptr;
-  h->host_route_last.clear();
-  h->missions = MissionsDev{nullptr, nullptr};
-  // a bound traffic history was checked against the old map's grids: a new map starts without one
-  if (h->history_blob) (void)hipFree(h->history_blob);
-  h->history_blob = nullptr;
-  h->history = HistoryDev{};
-  drop_social_dims(h);
-  drop_history_agents(h);
-  if (!h->alive_blob) {  // the tick's alive list (large batches) + its counters, the env groups with new vehicles (alive_layout)
-    const size_t n = alive_layout(h->cfg).size;
-    SMX_HIP(hipMalloc((void**)&h->alive_blob, n * sizeof(int32_t)));
-    SMX_HIP(hipMemset(h->alive_blob, 0, n * sizeof(int32_t)));
-  }
-  if (!h->slow_blob) {
-    const size_t n = SlowLists::size((size_t)h->cfg.num_envs * h->cfg.num_vehicles);
-    SMX_HIP(hipMalloc((void**)&h->slow_blob, n * sizeof(int32_t)));
-    SMX_HIP(hipMemset(h->slow_blob, 0, n * sizeof(int32_t)));
-  }
-  if (!h->pending_blob) {
-    const size_t n = (size_t)h->cfg.num_envs * h->cfg.num_vehicles;
-    SMX_HIP(hipMalloc((void**)&h->pending_blob, n));
-    SMX_HIP(hipMemset(h->pending_blob, 0, n));
-  }
-  if (!h->scan_carry) {  // all ones = NaN: nothing to start a seeded search from yet
-    const size_t n = 6 * (size_t)h->cfg.num_envs * h->cfg.num_vehicles;
-    SMX_HIP(hipMalloc((void**)&h->scan_carry, n * sizeof(double)));
-    SMX_HIP(hipMemset(h->scan_carry, 0xff, n * sizeof(double)));
-  }
-  // hand-off storage of the waypoints sensor's chain walks (the library's own: it never leaves the tick)
-  if ((h->cfg.sensors & SMX_SENSOR_WAYPOINTS) && !h->knots_blob) {
-    const size_t paths = (size_t)h->cfg.num_envs * h->cfg.num_vehicles * SMX_WP_LANES;
-    const size_t off_D = (size_t)(SMX_WPK_CAP + 1) * paths * sizeof(int32_t);
-    const size_t off_n = off_D + paths * sizeof(double), off_nk = off_n + paths * sizeof(int16_t);
-    const size_t off_end = off_nk + paths * sizeof(int16_t), off_key = off_end + paths * sizeof(int32_t);
-    const size_t off_cnt = off_key + 3 * paths * sizeof(int32_t), off_nk16 = off_cnt + paths;
-    const size_t bytes = off_nk16 + paths;
-    SMX_HIP(hipMalloc(&h->knots_blob, bytes));
-    SMX_HIP(hipMemset(h->knots_blob, 0, bytes));
-    SMX_HIP(hipMemset((char*)h->knots_blob + off_key, 0xff, 3 * paths * sizeof(int32_t)));  // no list is valid yet
-    char* kb = (char*)h->knots_blob;
-    h->knots.idx = (int32_t*)kb;
-    h->knots.D = (double*)(kb + off_D);
-    h->knots.n = (int16_t*)(kb + off_n);
-    h->knots.nk = (int16_t*)(kb + off_nk);
-    h->knots.end16 = (int32_t*)(kb + off_end);
-    h->knots.key = (int32_t*)(kb + off_key);
-    h->knots.cnt = (uint8_t*)(kb + off_cnt);
-    h->knots.nk16 = (uint8_t*)(kb + off_nk16);
-  }
-  if (h->knot_table) {  // (the rows of the map before)
-    (void)hipFree(h->knot_table);
-    h->knot_table = nullptr;
-  }
-  if (h->cfg.sensors & SMX_SENSOR_WAYPOINTS) {
-    if (!h->knot_stats) SMX_HIP(hipMalloc((void**)&h->knot_stats, 4 * sizeof(int32_t)));
-    SMX_HIP(hipMemset(h->knot_stats, 0, 4 * sizeof(int32_t)));
-    SMX_HIP(hipMalloc((void**)&h->knot_table, (size_t)t->n_lanepoints * sizeof(KnotRow)));
-    hipLaunchKernelGGL(k_knot_table, dim3(smx_blocks((size_t)t->n_lanepoints)), dim3(SMX_BLOCK), 0, 0, h->map, (int)h->cfg.wp_lookahead,
-                       h->knot_table, h->knot_stats);
-    SMX_HIP(hipGetLastError());
-    SMX_HIP(hipDeviceSynchronize());
-  }
-  if ((h->cfg.sensors & SMX_SENSOR_WAYPOINTS) && !h->spill_blob) {
-    // a region of (SMX_WPE_KNOTS + 1) knot records + lanes per column of every k_waypoints_emit workgroup: 1.6 KB per
-    // vehicle (the outputs are 8 KB), touched only by the few workgroups of a tick whose paths outgrow the LDS pool
-    const size_t tv = (size_t)h->cfg.num_envs * h->cfg.num_vehicles;
-    const size_t groups = (tv + SMX_WPT_VEHICLES - 1) / SMX_WPT_VEHICLES;
-    SMX_HIP(hipMalloc(&h->spill_blob, groups * SMX_WPE_SPILL_GROUP_BYTES));
-  }
-  if (!h->status_dev) {
-    SMX_HIP(hipMalloc((void**)&h->status_dev, sizeof(int32_t)));
-    SMX_HIP(hipMemset(h->status_dev, 0, sizeof(int32_t)));
-  }
-  if (!h->ctrl_blob) {
-    const size_t tv = (size_t)h->cfg.num_envs * h->cfg.num_vehicles;
-    const size_t path_bytes = (size_t)SMX_CTRL_WPS * 3 * tv * sizeof(double);
-    SMX_HIP(hipMalloc(&h->ctrl_blob, path_bytes + tv * sizeof(int32_t)));
-    SMX_HIP(hipMemset(h->ctrl_blob, 0, path_bytes + tv * sizeof(int32_t)));
-    h->ctrl.path = (double*)h->ctrl_blob;
-    h->ctrl.n = (int32_t*)((char*)h->ctrl_blob + path_bytes);
-  }
-  if (!h->side_ready) {
-    // lowest priority: the caller's stream carries the tick's critical chain (control -> seeds -> waypoints);
-    // the side kernels fill the chip around it instead of sharing it evenly
-    int prio_least = 0, prio_greatest = 0;
-    SMX_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    for (int i = 0; i < 3; ++i) {
-      SMX_HIP(hipStreamCreateWithPriority(&h->side[i], hipStreamNonBlocking, ((SMX_SIDE_PRIO >> i) & 1) ? 0 : prio_least));
-      SMX_HIP(hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming));
-    }
-    SMX_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    SMX_HIP(hipEventCreateWithFlags(&h->ev_fork_grid, hipEventDisableTiming));
-    h->side_ready = true;
-  }
-  h->guard_box = guard_box_of(*t, h->guard_margin);
-  h->map_loaded = true;
-  return SMX_OK;
-}
+extern "C" int smx_load_map(smx_handle h, const smx_map_tables* t) { return load_map_impl(h, t); }
 
 extern "C" int smx_set_vias(smx_handle h, const smx_via* vias_host, int32_t n, const int32_t* slot_off_host) {
-  if (!h) return SMX_ERR_INVALID;
-  if (n < 0 || (n > 0 && (!vias_host || !slot_off_host))) return fail(h, SMX_ERR_INVALID, "smx_set_vias: null table");
-  if (n > 0 && h->cfg.via_max <= 0) return fail(h, SMX_ERR_INVALID, "smx_set_vias: cfg.via_max is 0");
-  if (n > 0 && !h->map_loaded) return fail(h, SMX_ERR_STATE, "smx_set_vias needs the map (lane indices are checked)");
-  const int nv = h->cfg.num_vehicles;
-  if (n > 0) {
-    if (slot_off_host[0] != 0 || slot_off_host[nv] != n) return fail(h, SMX_ERR_INVALID, "smx_set_vias: slot offsets");
-    for (int s = 0; s < nv; ++s)
-      if (slot_off_host[s + 1] < slot_off_host[s] || slot_off_host[s + 1] - slot_off_host[s] > 32)
-        return fail(h, SMX_ERR_INVALID, "smx_set_vias: at most 32 vias per agent, offsets ascending");
-    for (int i = 0; i < n; ++i)
-      if (vias_host[i].lane < 0 || vias_host[i].lane >= h->map.n_lanes)
-        return fail(h, SMX_ERR_INVALID, "smx_set_vias: lane index out of range");
-  }
-  SMX_HIP(hipSetDevice(h->device));
-  if (h->vias_dev) (void)hipFree(h->vias_dev);
-  if (h->via_off_dev) (void)hipFree(h->via_off_dev);
-  h->vias_dev = nullptr;
-  h->via_off_dev = nullptr;
-  h->n_vias = 0;
-  if (n == 0) return SMX_OK;
-  SMX_HIP(hipMalloc(&h->vias_dev, (size_t)n * sizeof(smx_via)));
-  SMX_HIP(hipMalloc(&h->via_off_dev, (size_t)(nv + 1) * sizeof(int32_t)));
-  SMX_HIP(hipMemcpy(h->vias_dev, vias_host, (size_t)n * sizeof(smx_via), hipMemcpyHostToDevice));
-  SMX_HIP(hipMemcpy(h->via_off_dev, slot_off_host, (size_t)(nv + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-  h->n_vias = n;
-  return SMX_OK;
+  return set_vias_impl(h, vias_host, n, slot_off_host);
 }
 
 extern "C" int smx_set_missions(smx_handle h, const smx_mission* missions_host, int32_t n_slots,
                                 const int32_t* route_roads_host, int32_t n_route_roads) {
-  if (!h) return SMX_ERR_INVALID;
-  if (!h->map_loaded) return fail(h, SMX_ERR_STATE, "smx_set_missions needs the map (road indices are checked)");
-  if (n_slots < 0 || n_route_roads < 0 || (n_slots > 0 && !missions_host) || (n_route_roads > 0 && !route_roads_host))
-    return fail(h, SMX_ERR_INVALID, "smx_set_missions: null table");
-  const int nv = h->cfg.num_vehicles, nr = h->map.n_roads;
-  if (n_slots != 0 && n_slots != nv) return fail(h, SMX_ERR_INVALID, "smx_set_missions: one mission per vehicle slot (cfg.num_vehicles)");
-  if ((size_t)nv * (size_t)nr > 0x7fffffffull) return fail(h, SMX_ERR_INVALID, "smx_set_missions: slots x roads too large");
-  RouteTables rt;
-  if (const char* why = route_tables(missions_host, n_slots, route_roads_host, n_route_roads, nr, h->map.n_lanes, h->host_lane_road,
-                                     h->host_lane_out_off, h->host_lane_out_idx, rt))
-    return fail(h, SMX_ERR_INVALID, why);
-  SMX_HIP(hipSetDevice(h->device));
-  SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
-  if (h->missions_blob) (void)hipFree(h->missions_blob);
-  h->missions_blob = nullptr;
-  if (h->goals_blob) (void)hipFree(h->goals_blob);  // goal kinds go with the missions they refine
-  h->goals_blob = nullptr;
-  h->host_route_last.clear();
-  h->missions = MissionsDev{nullptr, nullptr};
-  h->map.route_pos = nullptr;
-  h->map.route_lane_ok = nullptr;
-  // the knot lists of the previous tick were walked under the old routes
-  if (h->knots_blob && h->knots.key)
-    SMX_HIP(hipMemset(h->knots.key, 0xff, 3 * (size_t)h->cfg.num_envs * nv * SMX_WP_LANES * sizeof(int32_t)));
-  h->host_route_last = rt.last;
-  if (!rt.any) return SMX_OK;
-  const size_t goal_bytes = rt.goal.size() * sizeof(double), last_bytes = rt.last.size() * sizeof(int32_t),
-               pos_bytes = rt.pos.size() * sizeof(int16_t);
-  const size_t off_last = goal_bytes, off_pos = (goal_bytes + last_bytes + 7) & ~(size_t)7;
-  const size_t off_lane = (off_pos + pos_bytes + 7) & ~(size_t)7;
-  SMX_HIP(hipMalloc(&h->missions_blob, off_lane + rt.lane_ok.size()));
-  char* base = (char*)h->missions_blob;
-  SMX_HIP(hipMemcpy(base, rt.goal.data(), goal_bytes, hipMemcpyHostToDevice));
-  SMX_HIP(hipMemcpy(base + off_last, rt.last.data(), last_bytes, hipMemcpyHostToDevice));
-  SMX_HIP(hipMemcpy(base + off_pos, rt.pos.data(), pos_bytes, hipMemcpyHostToDevice));
-  h->missions.goal = (const double*)base;
-  h->missions.route_last = (const int32_t*)(base + off_last);
-  SMX_HIP(hipMemcpy(base + off_lane, rt.lane_ok.data(), rt.lane_ok.size(), hipMemcpyHostToDevice));
-  h->map.route_pos = (const int16_t*)(base + off_pos);
-  h->map.route_lane_ok = (const uint8_t*)(base + off_lane);
-  return SMX_OK;
+  return set_missions_impl(h, missions_host, n_slots, route_roads_host, n_route_roads);
 }
 
 extern "C" int smx_check_mission_goals(const smx_mission_goal* goals, int32_t n_slots, int32_t num_vehicles,
@@ -6313,38 +5943,10 @@ extern "C" int smx_check_mission_goals(const smx_mission_goal* goals, int32_t n_
 
 extern "C" int smx_set_mission_goals(smx_handle h, const smx_mission_goal* goals_host, int32_t n_slots,
                                      const double* lane_end_heading_host, const int32_t* lane_dead_end_host, int32_t n_lanes) {
-  if (!h) return SMX_ERR_INVALID;
-  if (!h->map_loaded) return fail(h, SMX_ERR_STATE, "smx_set_mission_goals needs the map (the lane tables are checked against it)");
-  const int nv = h->cfg.num_vehicles, nl = h->map.n_lanes;
-  const std::string msg = mission_goals_error(goals_host, n_slots, nv, lane_end_heading_host, lane_dead_end_host, n_lanes, nl);
-  if (!msg.empty()) return fail(h, SMX_ERR_INVALID, msg);
-  bool any = false, traverse = false;
-  if (const char* why = mission_goals_route_error(goals_host, n_slots, h->host_route_last, any, traverse)) return fail(h, SMX_ERR_INVALID, why);
-  SMX_HIP(hipSetDevice(h->device));
-  SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
-  if (h->goals_blob) (void)hipFree(h->goals_blob);
-  h->goals_blob = nullptr;
-  h->missions.goal_kind = nullptr;
-  if (!any) return SMX_OK;
-  const size_t kind_bytes = (size_t)nv * sizeof(smx_mission_goal);
-  const size_t head_bytes = traverse ? (size_t)nl * sizeof(double) : 0, dead_bytes = traverse ? (size_t)nl * sizeof(int32_t) : 0;
-  SMX_HIP(hipMalloc(&h->goals_blob, kind_bytes + head_bytes + dead_bytes));
-  char* base = (char*)h->goals_blob;
-  SMX_HIP(hipMemcpy(base, goals_host, kind_bytes, hipMemcpyHostToDevice));
-  if (traverse) {
-    SMX_HIP(hipMemcpy(base + kind_bytes, lane_end_heading_host, head_bytes, hipMemcpyHostToDevice));
-    SMX_HIP(hipMemcpy(base + kind_bytes + head_bytes, lane_dead_end_host, dead_bytes, hipMemcpyHostToDevice));
-  }
-  h->missions.goal_kind = (const smx_mission_goal*)base;
-  return SMX_OK;
+  return set_mission_goals_impl(h, goals_host, n_slots, lane_end_heading_host, lane_dead_end_host, n_lanes);
 }
 
-extern "C" int smx_set_lidar_rays(smx_handle h, const double* rays_dev, int32_t n_rays) {
-  if (!h) return SMX_ERR_INVALID;
-  if (n_rays != h->cfg.lidar_rays) return fail(h, SMX_ERR_INVALID, "n_rays != cfg.lidar_rays");
-  h->lidar_rays = rays_dev;
-  return SMX_OK;
-}
+extern "C" int smx_set_lidar_rays(smx_handle h, const double* rays_dev, int32_t n_rays) { return set_lidar_rays_impl(h, rays_dev, n_rays); }
 
 // ---- the smx_check_* entry points: smx_host.h's checks, callable without a device or a handle ----
 extern "C" int smx_check_buffers(const smx_config* cfg, int has_vias, const smx_state* st, const smx_spawns* sp,
@@ -6373,43 +5975,10 @@ extern "C" int smx_check_frame_stack(const smx_config* cfg, int32_t source, int3
   return report(rc, msg, err, err_len);
 }
 
-extern "C" int smx_set_rgb_output(smx_handle h, uint8_t* rgb_dev, uint64_t count) {
-  if (!h) return SMX_ERR_INVALID;
-  if (!rgb_dev) {  // unbind
-    h->rgb_out = nullptr;
-    h->rgb_count = 0;
-    return SMX_OK;
-  }
-  if (!(h->cfg.sensors & SMX_SENSOR_RGB))
-    return fail(h, SMX_ERR_STATE, "smx_set_rgb_output: the configuration has no SMX_SENSOR_RGB");
-  if ((reinterpret_cast<uintptr_t>(rgb_dev) & 15) != 0)
-    return fail(h, SMX_ERR_INVALID, "rgb output: the buffer must be 16-byte aligned (it is written with 16-byte stores)");
-  std::string msg;
-  const int rc = check_rgb_output_impl(h->cfg, count, msg);
-  if (rc != SMX_OK) return fail(h, rc, msg);
-  h->rgb_out = rgb_dev;
-  h->rgb_count = count;
-  return SMX_OK;
-}
+extern "C" int smx_set_rgb_output(smx_handle h, uint8_t* rgb_dev, uint64_t count) { return set_rgb_output_impl(h, rgb_dev, count); }
 
 extern "C" int smx_set_guard(smx_handle h, uint8_t* guard_dev, uint64_t count, double margin) {
-  if (!h) return SMX_ERR_INVALID;
-  if (!guard_dev) {  // guard off
-    h->guard_out = nullptr;
-    h->guard_count = 0;
-    return SMX_OK;
-  }
-  std::string msg;
-  const int rc = check_guard_impl(h->cfg, count, margin, msg);
-  if (rc != SMX_OK) return fail(h, rc, msg);
-  // (before a map is loaded, smx_load_map makes this check)
-  if (h->map_loaded && !guard_map_ok(h->map, margin))
-    return fail(h, SMX_ERR_INVALID, "state guard: with this margin a cell index of the loaded map's grids would not fit (smx_guard.h, SMX_GUARD_INDEX_MAX)");
-  h->guard_out = guard_dev;
-  h->guard_count = count;
-  h->guard_margin = margin;
-  if (h->map_loaded) h->guard_box = guard_box_of(h->map, margin);
-  return SMX_OK;
+  return set_guard_impl(h, guard_dev, count, margin);
 }
 
 extern "C" int smx_check_social_history(const smx_config* cfg, const smx_map_tables* map, const smx_social_history* hist, char* err,
@@ -6419,43 +5988,7 @@ extern "C" int smx_check_social_history(const smx_config* cfg, const smx_map_tab
   return report(rc, msg, err, err_len);
 }
 
-extern "C" int smx_set_social_history(smx_handle h, const smx_social_history* hist) {
-  if (!h) return SMX_ERR_INVALID;
-  if (hist) {
-    if (!h->map_loaded) return fail(h, SMX_ERR_STATE, "smx_set_social_history needs the map (the rows are checked against its grids)");
-    std::string msg;
-    const int rc = check_social_history_impl(h->cfg, h->map, *hist, msg);  // (the grid extents are scalars: the device copy of the tables has them)
-    if (rc != SMX_OK) return fail(h, rc, msg);
-  }
-  SMX_HIP(hipSetDevice(h->device));
-  SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
-  if (h->history_blob) (void)hipFree(h->history_blob);
-  h->history_blob = nullptr;
-  h->history = HistoryDev{};
-  drop_social_dims(h);
-  drop_history_agents(h);
-  // the alive list k_tail built for the next tick was built under the other rule (smx_plan.h: tail_builds_list)
-  h->list_ready = false;
-  if (!hist) return SMX_OK;
-  const size_t cells = (size_t)hist->n_frames * (size_t)hist->num_social;
-  const size_t frame_bytes = cells * 4 * sizeof(double), id_bytes = cells * sizeof(int32_t);
-  SMX_HIP(hipMalloc(&h->history_blob, frame_bytes + id_bytes));
-  char* base = (char*)h->history_blob;
-  SMX_HIP(hipMemcpy(base, hist->frames_host, frame_bytes, hipMemcpyHostToDevice));
-  SMX_HIP(hipMemcpy(base + frame_bytes, hist->vehicle_host, id_bytes, hipMemcpyHostToDevice));
-  HistoryDev d{};
-  d.frames = (const double*)base;
-  d.vehicle = (const int32_t*)(base + frame_bytes);
-  d.start_frame = hist->start_frame_dev;
-  d.replaced = hist->replaced_dev;
-  d.n_frames = hist->n_frames;
-  d.num_social = hist->num_social;
-  d.rows = hist->rows;
-  d.num_envs = h->cfg.num_envs;
-  h->history = d;
-  h->history_max_id = social_history_max_id(*hist);
-  return SMX_OK;
-}
+extern "C" int smx_set_social_history(smx_handle h, const smx_social_history* hist) { return set_social_history_impl(h, hist); }
 
 extern "C" int smx_check_social_history_dims(const smx_config* cfg, const smx_social_history* hist, const smx_social_dims* dims,
                                              char* err, uint64_t err_len) {
@@ -6464,36 +5997,7 @@ extern "C" int smx_check_social_history_dims(const smx_config* cfg, const smx_so
   return report(rc, msg, err, err_len);
 }
 
-extern "C" int smx_set_social_history_dims(smx_handle h, const smx_social_dims* dims) {
-  if (!h) return SMX_ERR_INVALID;
-  if (dims) {
-    if (h->history.vehicle == nullptr) return fail(h, SMX_ERR_STATE, "smx_set_social_history_dims needs a bound history (smx_set_social_history)");
-    std::string msg;
-    const int rc = check_social_dims_impl(*dims, h->history_max_id, msg);
-    if (rc != SMX_OK) return fail(h, rc, msg);
-  }
-  SMX_HIP(hipSetDevice(h->device));
-  SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
-  drop_social_dims(h);
-  if (!dims) return SMX_OK;
-  // table | a triple per vehicle of the batch, the sedan's until a replayed slot's pose is written (agents: for good)
-  const size_t table_words = (size_t)dims->n_ids * 3, total = (size_t)h->cfg.num_envs * (size_t)h->cfg.num_vehicles;
-  std::vector<double> host(table_words + total * 3);
-  std::copy(dims->dims_host, dims->dims_host + table_words, host.begin());
-  for (size_t g = 0; g < total; ++g) {
-    host[table_words + g * 3 + 0] = SMX_CHASSIS_LENGTH;
-    host[table_words + g * 3 + 1] = SMX_CHASSIS_WIDTH;
-    host[table_words + g * 3 + 2] = SMX_CHASSIS_HEIGHT;
-  }
-  SMX_HIP(hipMalloc(&h->dims_blob, host.size() * sizeof(double)));
-  SMX_HIP(hipMemcpy(h->dims_blob, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice));
-  HistoryDimsDev d;
-  d.table = (const double*)h->dims_blob;
-  d.slot = (double*)h->dims_blob + table_words;
-  d.n_ids = dims->n_ids;
-  h->dims = d;
-  return SMX_OK;
-}
+extern "C" int smx_set_social_history_dims(smx_handle h, const smx_social_dims* dims) { return set_social_history_dims_impl(h, dims); }
 
 extern "C" int smx_check_history_agents(const smx_config* cfg, const smx_social_history* hist, const smx_history_agents* ha, char* err,
                                         uint64_t err_len) {
@@ -6502,24 +6006,7 @@ extern "C" int smx_check_history_agents(const smx_config* cfg, const smx_social_
   return report(rc, msg, err, err_len);
 }
 
-extern "C" int smx_set_history_agents(smx_handle h, const smx_history_agents* ha) {
-  if (!h) return SMX_ERR_INVALID;
-  if (ha) {
-    if (h->history.vehicle == nullptr) return fail(h, SMX_ERR_STATE, "smx_set_history_agents needs a bound history (smx_set_social_history)");
-    std::string msg;
-    const int rc = check_history_agents_impl(h->cfg, h->history.rows, *ha, msg);
-    if (rc != SMX_OK) return fail(h, rc, msg);
-  }
-  SMX_HIP(hipSetDevice(h->device));
-  SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
-  drop_history_agents(h);
-  if (!ha) return SMX_OK;
-  h->history.follow = ha->vehicle_dev;
-  h->history.n_agents = h->cfg.num_vehicles - h->cfg.num_social;
-  h->ha_action = ha->action_dev;
-  h->ha_status = ha->status_dev;
-  return SMX_OK;
-}
+extern "C" int smx_set_history_agents(smx_handle h, const smx_history_agents* ha) { return set_history_agents_impl(h, ha); }
 
 extern "C" int smx_check_history_handover(const smx_config* cfg, const smx_social_history* hist, const smx_history_handover* ho, char* err,
                                           uint64_t err_len) {
@@ -6528,43 +6015,10 @@ extern "C" int smx_check_history_handover(const smx_config* cfg, const smx_socia
   return report(rc, msg, err, err_len);
 }
 
-extern "C" int smx_set_history_handover(smx_handle h, const smx_history_handover* ho) {
-  if (!h) return SMX_ERR_INVALID;
-  if (ho) {
-    if (h->history.follow == nullptr) return fail(h, SMX_ERR_STATE, "smx_set_history_handover needs bound history agents (smx_set_history_agents)");
-    std::string msg;
-    const int rc = check_history_handover_impl(h->cfg, h->history.rows, *ho, msg);
-    if (rc != SMX_OK) return fail(h, rc, msg);
-  }
-  SMX_HIP(hipSetDevice(h->device));
-  SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
-  h->history.handover = ho ? ho->tick_dev : nullptr;
-  return SMX_OK;
-}
+extern "C" int smx_set_history_handover(smx_handle h, const smx_history_handover* ho) { return set_history_handover_impl(h, ho); }
 
 extern "C" int smx_bind_frame_stack(smx_handle h, int32_t source, int32_t layout, void* stack_dev, uint64_t bytes) {
-  if (!h) return SMX_ERR_INVALID;
-  auto at = std::find_if(h->stacks.begin(), h->stacks.end(),
-                         [&](const smx_handle_s::StackBinding& b) { return b.source == source && b.layout == layout; });
-  if (!stack_dev) {  // unbind
-    if (at != h->stacks.end()) h->stacks.erase(at);
-    return SMX_OK;
-  }
-  std::string msg;
-  uint64_t row;
-  const int rc = check_frame_stack_impl(h->cfg, source, layout, bytes, row, msg);
-  if (rc != SMX_OK) return fail(h, rc, msg);
-  if (layout == SMX_STACK_DSTACK && (reinterpret_cast<uintptr_t>(stack_dev) & 15) != 0)
-    return fail(h, SMX_ERR_INVALID, "frame stack: an SMX_STACK_DSTACK buffer must be 16-byte aligned (it is moved with up to 16-byte accesses)");
-  if (at != h->stacks.end()) {
-    at->dst = (uint8_t*)stack_dev;
-    at->bytes = bytes;
-    return SMX_OK;
-  }
-  if (h->stacks.size() >= SMX_STACK_MAX_BINDINGS)
-    return fail(h, SMX_ERR_STATE, "frame stack: at most " SMX_STR(SMX_STACK_MAX_BINDINGS) " bindings");
-  h->stacks.push_back({source, layout, (uint8_t*)stack_dev, bytes, (uint32_t)row});
-  return SMX_OK;
+  return bind_frame_stack_impl(h, source, layout, stack_dev, bytes);
 }
 
 // the pass's last launches: every FRAMES binding in one k_frame_push, the interleaved image in one k_frame_dstack
@@ -6709,15 +6163,15 @@ static void launch_control(smx_handle h, const TickPlan& p, const KernelArgs& a,
 static void alive_list(smx_handle h, const TickPlan& p, KernelArgs& a, hipStream_t stream) {
   if (p.alive == AliveList::NONE) return;
   const AliveLayout al = alive_layout(h->cfg);
-  int32_t* counters = h->alive_blob + al.flat;
-  a.alive_list = h->alive_blob;
+  int32_t* counters = h->alive_blob.get<int32_t>() + al.flat;
+  a.alive_list = h->alive_blob.get<int32_t>();
   if (p.alive == AliveList::CARRIED) {
-    a.alive_count = h->alive_blob + al.seg + (size_t)8 * SMX_SEG_STRIDE * (h->seg_parity ^ 1);
+    a.alive_count = h->alive_blob.get<int32_t>() + al.seg + (size_t)8 * SMX_SEG_STRIDE * (h->seg_parity ^ 1);
     a.alive_segmented = 1;
   } else {
     const size_t total = (size_t)h->cfg.num_envs * h->cfg.num_vehicles;
     a.alive_count = counters + h->alive_parity;
-    hipLaunchKernelGGL(k_alive_list, dim3(smx_blocks(total, SMX_ALIVE_BLOCK)), dim3(SMX_ALIVE_BLOCK), 0, stream, a, h->alive_blob,
+    hipLaunchKernelGGL(k_alive_list, dim3(smx_blocks(total, SMX_ALIVE_BLOCK)), dim3(SMX_ALIVE_BLOCK), 0, stream, a, h->alive_blob.get<int32_t>(),
                        counters + h->alive_parity, counters + (h->alive_parity ^ 1), p.alive_zero);
   }
   h->alive_parity ^= 1;
@@ -6753,10 +6207,10 @@ static void launch_slow_chain(const TickPlan& p, const KernelArgs& ks, hipStream
 // waypoints (`ph`: the call's phase events, null unless the plan is phased)
 static void observation_pass(smx_handle h, const TickPlan& p, const KernelArgs& k, hipStream_t stream, hipEvent_t* ph) {
   const size_t total = (size_t)h->cfg.num_envs * h->cfg.num_vehicles;
-  const hipStream_t s_grid = p.fork ? h->side[0] : stream, s_obs = p.fork ? h->side[1] : stream;
+  const hipStream_t s_grid = p.fork ? h->streams.side[0] : stream, s_obs = p.fork ? h->streams.side[1] : stream;
   if (p.fork) {
-    (void)hipEventRecord(h->ev_fork_grid, stream);
-    (void)hipStreamWaitEvent(s_grid, h->ev_fork_grid, 0);
+    (void)hipEventRecord(h->streams.ev_fork_grid, stream);
+    (void)hipStreamWaitEvent(s_grid, h->streams.ev_fork_grid, 0);
     launch_grids(h, p, k, s_grid);
     if (p.lidar == Lidar::SIDE) launch(p.sized ? k_lidar<true> : k_lidar<false>, p.lidar_blocks, 0, s_grid, k);
   }
@@ -6779,15 +6233,15 @@ static void observation_pass(smx_handle h, const TickPlan& p, const KernelArgs& 
     // the slow chain runs beside the main chain (k_wp_walk -> k_waypoints_emit pass over its vehicles)
     // (one event after the seeds half serves this fork and the facts half's below: every record on the caller's
     // stream is a packet its next kernel waits behind, ten microseconds of the tick's longest chain)
-    (void)hipEventRecord(h->ev_fork, stream);
-    (void)hipStreamWaitEvent(h->side[2], h->ev_fork, 0);
-    launch_slow_chain(p, ks, h->side[2]);
+    (void)hipEventRecord(h->streams.ev_fork, stream);
+    (void)hipStreamWaitEvent(h->streams.side[2], h->streams.ev_fork, 0);
+    launch_slow_chain(p, ks, h->streams.side[2]);
   }
   if (p.facts_start == FactsStart::WITH_GRIDS) {
-    (void)hipStreamWaitEvent(s_obs, h->ev_fork_grid, 0);
+    (void)hipStreamWaitEvent(s_obs, h->streams.ev_fork_grid, 0);
   } else if (p.facts_start == FactsStart::AFTER_SEEDS) {
-    if (p.chain() != SlowChain::SIDE) (void)hipEventRecord(h->ev_fork, stream);
-    (void)hipStreamWaitEvent(s_obs, h->ev_fork, 0);
+    if (p.chain() != SlowChain::SIDE) (void)hipEventRecord(h->streams.ev_fork, stream);
+    (void)hipStreamWaitEvent(s_obs, h->streams.ev_fork, 0);
   }
   const KernelArgs kf = with_slow(k, p.facts_slow);
   switch (p.facts) {
@@ -6829,8 +6283,8 @@ static void observation_pass(smx_handle h, const TickPlan& p, const KernelArgs& 
     // (each side stream joins the caller's directly: chaining side 0 through side 1 puts one more hop behind the
     // last kernel when k_observe ends the tick — 1 % late in a run)
     for (int i = 0; i < (p.chain() == SlowChain::SIDE ? 3 : 2); ++i) {
-      (void)hipEventRecord(h->ev_join[i], h->side[i]);
-      (void)hipStreamWaitEvent(stream, h->ev_join[i], 0);
+      (void)hipEventRecord(h->streams.ev_join[i], h->streams.side[i]);
+      (void)hipStreamWaitEvent(stream, h->streams.ev_join[i], 0);
     }
   }
   if (p.road_waypoints)  // (poses are the tick's new ones; flags still those of its start)
@@ -6863,15 +6317,15 @@ static int tail_and_reset_pass(smx_handle h, const TickPlan& p, const KernelArgs
   TailArgs t{};
   t.commit = p.is_step ? 1 : 0;
   t.grids = p.tail_grids ? 1 : 0;
-  t.groups = h->alive_blob + al.groups;
-  t.n_groups = h->alive_blob + al.group_count + SMX_SEG_STRIDE * h->group_parity;
-  t.n_groups_next = h->alive_blob + al.group_count + SMX_SEG_STRIDE * (h->group_parity ^ 1);
+  t.groups = h->alive_blob.get<int32_t>() + al.groups;
+  t.n_groups = h->alive_blob.get<int32_t>() + al.group_count + SMX_SEG_STRIDE * h->group_parity;
+  t.n_groups_next = h->alive_blob.get<int32_t>() + al.group_count + SMX_SEG_STRIDE * (h->group_parity ^ 1);
   if (p.tail_builds_list) {  // (the next tick's parity is h->alive_parity now)
-    t.list = h->alive_blob;
-    t.seg_count = h->alive_blob + al.seg + (size_t)8 * SMX_SEG_STRIDE * h->seg_parity;
-    t.seg_next = h->alive_blob + al.seg + (size_t)8 * SMX_SEG_STRIDE * (h->seg_parity ^ 1);
-    t.flat_next = h->alive_blob + al.flat + h->alive_parity;
-    t.slow_next = SlowLists{h->slow_blob, total}.counters(h->alive_parity);
+    t.list = h->alive_blob.get<int32_t>();
+    t.seg_count = h->alive_blob.get<int32_t>() + al.seg + (size_t)8 * SMX_SEG_STRIDE * h->seg_parity;
+    t.seg_next = h->alive_blob.get<int32_t>() + al.seg + (size_t)8 * SMX_SEG_STRIDE * (h->seg_parity ^ 1);
+    t.flat_next = h->alive_blob.get<int32_t>() + al.flat + h->alive_parity;
+    t.slow_next = SlowLists{h->slow_blob.get<int32_t>(), total}.counters(h->alive_parity);
   }
   hipLaunchKernelGGL(p.guard ? k_tail<true> : k_tail<false>, dim3(p.obs_blocks), dim3(SMX_BLOCK), p.tail_grids ? std::max({p.ogm_bytes, p.dagm_bytes, p.rgb_lds}) : 0, stream, r, t);
   if (ph) SMX_HIP(hipEventRecord(ph[SMX_PHASE_COMMIT + 1], stream));
@@ -6916,31 +6370,31 @@ static KernelArgs kernel_args(smx_handle h, const TickPlan& p, const int8_t* act
   a.traj_max = traj_max;
   a.env_mask = mask;
   a.lidar_rays = h->lidar_rays;
-  a.vias = h->n_vias > 0 ? h->vias_dev : nullptr;
+  a.vias = h->n_vias > 0 ? h->vias_dev.get<smx_via>() : nullptr;
   a.missions = h->missions;
-  a.via_slot_off = h->via_off_dev;
+  a.via_slot_off = h->via_off_dev.get<int32_t>();
   a.first_only = 0;
   a.keep_reward_done = 0;
   a.reset_all = 0;
   a.heading_gain_pos = h->heading_gain_pos;
   a.nb_d2_max = h->nb_d2_max;
   a.walk_new = 0;
-  a.wp_spill = (char*)h->spill_blob;
+  a.wp_spill = h->spill_blob.get<char>();
   a.wp_pool_limit = h->wp_pool_limit;
   a.lateral_gain_pos = h->lateral_gain_pos;
   a.debug_skip = h->debug_skip;
   a.knots = h->knots;
-  a.knot_table = p.knot_table ? h->knot_table : nullptr;
-  a.knot_served = (p.knot_table && h->knot_table_mode == 2) ? (unsigned long long*)(h->knot_stats + 2) : nullptr;
-  a.status = h->status_dev;
+  a.knot_table = p.knot_table ? h->knot_table.get<KnotRow>() : nullptr;
+  a.knot_served = (p.knot_table && h->knot_table_mode == 2) ? (unsigned long long*)(h->knot_stats.get<int32_t>() + 2) : nullptr;
+  a.status = h->status_dev.get<int32_t>();
   a.alive_list = nullptr;
   a.alive_count = nullptr;
   a.alive_segmented = 0;
   a.slow_list = nullptr;
   a.slow_count = nullptr;
   a.seed_pending = nullptr;
-  a.seeds_carry = h->scan_carry;
-  a.facts_carry = h->scan_carry ? h->scan_carry + 4 * total : nullptr;
+  a.seeds_carry = h->scan_carry.get<double>();
+  a.facts_carry = h->scan_carry ? h->scan_carry.get<double>() + 4 * total : nullptr;
   a.dagm_reach = h->dagm_reach;
   a.rgb = h->rgb_out;
   a.guard = h->guard_out;
@@ -6949,7 +6403,7 @@ static KernelArgs kernel_args(smx_handle h, const TickPlan& p, const int8_t* act
   a.dims = h->dims;
   a.ha_action = h->ha_action;
   a.ha_status = h->ha_status;
-  a.ogm_mask = (p.ogm_delta && out->ogm) ? h->ogm_mask : nullptr;
+  a.ogm_mask = (p.ogm_delta && out->ogm) ? h->ogm_mask.get<unsigned long long>() : nullptr;
   a.wp_blocks = (int)p.wp_blocks;
   a.obs_blocks = (int)p.obs_blocks;
   a.lidar_blocks = (int)p.lidar_blocks;
@@ -6994,30 +6448,30 @@ static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const
   KernelArgs a = kernel_args(h, p, actions, actions_f32, traj, traj_n, traj_max, mask, st, sp, out);
   const bool timed = h->timing && is_step && h->ev_used < 65536;
   if (timed) {
-    if (h->ev_pool.size() < 2 * (h->ev_used + 1)) {
+    if (h->ev_pool.ev.size() < 2 * (h->ev_used + 1)) {
       hipEvent_t e0, e1;
       SMX_HIP(hipEventCreate(&e0));
       SMX_HIP(hipEventCreate(&e1));
-      h->ev_pool.push_back(e0);
-      h->ev_pool.push_back(e1);
+      h->ev_pool.ev.push_back(e0);
+      h->ev_pool.ev.push_back(e1);
     }
-    SMX_HIP(hipEventRecord(h->ev_pool[2 * h->ev_used], stream));
+    SMX_HIP(hipEventRecord(h->ev_pool.ev[2 * h->ev_used], stream));
   }
   // phase timing (smx_set_timing level 2): one boundary event after every kernel of the tick
   hipEvent_t* ph = nullptr;
   if (p.phased) {
     const size_t need = (h->ph_used + 1) * (SMX_PHASE_COUNT + 1);
-    while (h->ph_pool.size() < need) {
+    while (h->ph_pool.ev.size() < need) {
       hipEvent_t e;
       SMX_HIP(hipEventCreate(&e));
-      h->ph_pool.push_back(e);
+      h->ph_pool.ev.push_back(e);
     }
-    ph = &h->ph_pool[h->ph_used * (SMX_PHASE_COUNT + 1)];
+    ph = &h->ph_pool.ev[h->ph_used * (SMX_PHASE_COUNT + 1)];
     SMX_HIP(hipEventRecord(ph[0], stream));
   }
   if (a.ogm_mask && !(h->ogm_known && h->ogm_rows == out->ogm)) {
     // the masks do not describe these rows (KernelArgs::ogm_mask): every piece may be non-zero, this pass stores whole tiles
-    SMX_HIP(hipMemsetAsync(h->ogm_mask, 0xff, h->ogm_mask_bytes, stream));
+    SMX_HIP(hipMemsetAsync(h->ogm_mask.get<unsigned long long>(), 0xff, h->ogm_mask_bytes, stream));
     h->ogm_rows = out->ogm;
     h->ogm_known = true;
   }
@@ -7041,7 +6495,7 @@ static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const
     h->ph_used += 1;
   }
   if (timed) {
-    SMX_HIP(hipEventRecord(h->ev_pool[2 * h->ev_used + 1], stream));
+    SMX_HIP(hipEventRecord(h->ev_pool.ev[2 * h->ev_used + 1], stream));
     h->ev_used += 1;
   }
   return SMX_OK;
@@ -7127,9 +6581,9 @@ extern "C" int smx_sync(smx_handle h, void* hip_stream) {
   SMX_HIP(hipStreamSynchronize((hipStream_t)hip_stream));
   if (h->status_dev) {  // what the kernels could not report themselves
     int32_t bits = 0;
-    SMX_HIP(hipMemcpy(&bits, h->status_dev, sizeof(bits), hipMemcpyDeviceToHost));
+    SMX_HIP(hipMemcpy(&bits, h->status_dev.get<int32_t>(), sizeof(bits), hipMemcpyDeviceToHost));
     if (bits) {
-      SMX_HIP(hipMemset(h->status_dev, 0, sizeof(int32_t)));
+      SMX_HIP(hipMemset(h->status_dev.get<int32_t>(), 0, sizeof(int32_t)));
       if (bits & SMX_DEVICE_BAD_LANE_ACTION)
         return fail(h, SMX_ERR_INVALID,
                     "a Lane action code outside -1..3 reached smx_step since the last smx_sync; the agents that sent one "
@@ -7156,7 +6610,7 @@ extern "C" int smx_debug_slow_counts(smx_handle h, int32_t* out4) {
   if (!h->slow_blob) return fail(h, SMX_ERR_STATE, "no slow lists (the map is not loaded)");
   SMX_HIP(hipDeviceSynchronize());
   const size_t total = (size_t)h->cfg.num_envs * h->cfg.num_vehicles;
-  SMX_HIP(hipMemcpy(out4, SlowLists{h->slow_blob, total}.counters(h->alive_parity ^ 1), 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  SMX_HIP(hipMemcpy(out4, SlowLists{h->slow_blob.get<int32_t>(), total}.counters(h->alive_parity ^ 1), 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
   return SMX_OK;
 }
 
@@ -7185,7 +6639,7 @@ extern "C" int smx_debug_knot_table_stats(smx_handle h, int64_t* out4) {
   if (!h->knot_table) return fail(h, SMX_ERR_STATE, "no knot table (no map loaded, or no waypoints sensor)");
   SMX_HIP(hipDeviceSynchronize());
   int32_t st[4];
-  SMX_HIP(hipMemcpy(st, h->knot_stats, sizeof(st), hipMemcpyDeviceToHost));
+  SMX_HIP(hipMemcpy(st, h->knot_stats.get<int32_t>(), sizeof(st), hipMemcpyDeviceToHost));
   unsigned long long served;
   std::memcpy(&served, st + 2, sizeof(served));
   out4[0] = h->map.n_lanepoints;
@@ -7221,7 +6675,7 @@ extern "C" int smx_read_phase_ms(smx_handle h, float* ms, int32_t max_steps, int
   if (!h || !ms || !n || max_steps < 0) return SMX_ERR_INVALID;
   int32_t count = 0;
   for (size_t i = 0; i < h->ph_used; ++i) {
-    hipEvent_t* ph = &h->ph_pool[i * (SMX_PHASE_COUNT + 1)];
+    hipEvent_t* ph = &h->ph_pool.ev[i * (SMX_PHASE_COUNT + 1)];
     SMX_HIP(hipEventSynchronize(ph[SMX_PHASE_COUNT]));
     if (count >= max_steps) continue;
     for (int p = 0; p < SMX_PHASE_COUNT; ++p) {
@@ -7240,9 +6694,9 @@ extern "C" int smx_read_step_ms(smx_handle h, float* ms, int32_t max, int32_t* n
   if (!h || !ms || !n || max < 0) return SMX_ERR_INVALID;
   int32_t count = 0;
   for (size_t i = 0; i < h->ev_used; ++i) {
-    SMX_HIP(hipEventSynchronize(h->ev_pool[2 * i + 1]));
+    SMX_HIP(hipEventSynchronize(h->ev_pool.ev[2 * i + 1]));
     float t = 0.f;
-    SMX_HIP(hipEventElapsedTime(&t, h->ev_pool[2 * i], h->ev_pool[2 * i + 1]));
+    SMX_HIP(hipEventElapsedTime(&t, h->ev_pool.ev[2 * i], h->ev_pool.ev[2 * i + 1]));
     if (count < max) ms[count++] = t;
   }
   h->ev_used = 0;
@@ -7254,43 +6708,11 @@ extern "C" int smx_last_step_ms(smx_handle h, float* ms) {
   if (!h || !ms) return SMX_ERR_INVALID;
   if (h->ev_used == 0) return fail(h, SMX_ERR_STATE, "no timed step recorded (smx_set_timing(1) then smx_step)");
   const size_t i = h->ev_used - 1;
-  SMX_HIP(hipEventSynchronize(h->ev_pool[2 * i + 1]));
-  SMX_HIP(hipEventElapsedTime(ms, h->ev_pool[2 * i], h->ev_pool[2 * i + 1]));
+  SMX_HIP(hipEventSynchronize(h->ev_pool.ev[2 * i + 1]));
+  SMX_HIP(hipEventElapsedTime(ms, h->ev_pool.ev[2 * i], h->ev_pool.ev[2 * i + 1]));
   return SMX_OK;
 }
 
 extern "C" const char* smx_last_error(smx_handle h) { return h ? h->err.c_str() : g_create_err.c_str(); }
 
-extern "C" void smx_destroy(smx_handle h) {
-  if (!h) return;
-  if (h->map_blob) (void)hipFree(h->map_blob);
-  if (h->knots_blob) (void)hipFree(h->knots_blob);
-  if (h->alive_blob) (void)hipFree(h->alive_blob);
-  if (h->scan_carry) (void)hipFree(h->scan_carry);
-  if (h->slow_blob) (void)hipFree(h->slow_blob);
-  if (h->pending_blob) (void)hipFree(h->pending_blob);
-  if (h->spill_blob) (void)hipFree(h->spill_blob);
-  if (h->knot_table) (void)hipFree(h->knot_table);
-  if (h->knot_stats) (void)hipFree(h->knot_stats);
-  if (h->ctrl_blob) (void)hipFree(h->ctrl_blob);
-  if (h->status_dev) (void)hipFree(h->status_dev);
-  if (h->side_ready) {
-    for (int i = 0; i < 3; ++i) {
-      (void)hipStreamSynchronize(h->side[i]);
-      (void)hipStreamDestroy(h->side[i]);
-      (void)hipEventDestroy(h->ev_join[i]);
-    }
-    (void)hipEventDestroy(h->ev_fork);
-    (void)hipEventDestroy(h->ev_fork_grid);
-  }
-  if (h->vias_dev) (void)hipFree(h->vias_dev);
-  if (h->via_off_dev) (void)hipFree(h->via_off_dev);
-  if (h->missions_blob) (void)hipFree(h->missions_blob);
-  if (h->goals_blob) (void)hipFree(h->goals_blob);
-  if (h->history_blob) (void)hipFree(h->history_blob);
-  if (h->dims_blob) (void)hipFree(h->dims_blob);
-  if (h->ogm_mask) (void)hipFree(h->ogm_mask);
-  for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
-  for (hipEvent_t e : h->ph_pool) (void)hipEventDestroy(e);
-  delete h;
-}
+extern "C" void smx_destroy(smx_handle h) { destroy_impl(h); }

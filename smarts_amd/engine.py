@@ -743,15 +743,7 @@ class BatchedSim:
         """One tick in which every agent follows its recorded vehicle (``smx_step_history_agents``; no actions)."""
         if not self._was_reset:
             raise RuntimeError("step() before reset()")
-        self._out.learner = self.next_learner_block.data_ptr()
-        rc = self.lib.smx_step_history_agents(self.handle, C.byref(self._st), C.byref(self._sp), C.byref(self._out),
-                                              self._stream_ptr())
-        if rc != 0:  # (no binding: refused before anything was launched, the learner block does not flip)
-            self._out.learner = self.out["learner"].data_ptr()
-        nat.check(self.lib, self.handle, rc, "smx_step_history_agents")
-        self._learner_k ^= 1
-        self.out["learner"] = self._learner[self._learner_k]
-        return self.out
+        return self._tick("smx_step_history_agents")
 
     def set_history_handover(self, ticks: Optional[torch.Tensor]):
         """Bind the handover table (``smx_set_history_handover``; needs bound history agents): int32 ``[R, E, A]`` on the
@@ -787,15 +779,7 @@ class BatchedSim:
             actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
         if tuple(actions.shape) != (self.E, self.N, 3):
             raise ValueError(f"actions must have shape {(self.E, self.N, 3)}, got {tuple(actions.shape)}")
-        self._out.learner = self.next_learner_block.data_ptr()
-        rc = self.lib.smx_step_history_handover(self.handle, actions.data_ptr(), C.byref(self._st), C.byref(self._sp),
-                                                C.byref(self._out), self._stream_ptr())
-        if rc != 0:  # (no binding: refused before anything was launched, the learner block does not flip)
-            self._out.learner = self.out["learner"].data_ptr()
-        nat.check(self.lib, self.handle, rc, "smx_step_history_handover")
-        self._learner_k ^= 1
-        self.out["learner"] = self._learner[self._learner_k]
-        return self.out
+        return self._tick("smx_step_history_handover", actions.data_ptr())
 
     history_agents = None
     history_handover = None
@@ -875,22 +859,24 @@ class BatchedSim:
             actions = actions.to(device=self.device, dtype=want_dtype).contiguous()
         if tuple(actions.shape) != want_shape:
             raise ValueError(f"{self.cfg.action_space} actions must have shape {want_shape}, got {tuple(actions.shape)}")
-        # only now that the call is known to go ahead does the learner block flip
+        # Lane: codes outside -1..3 cannot be seen from here without a device round trip: the kernel treats them as
+        # "no action" and smx_sync / BatchedSim.sync() reports them.  The float spaces: three floats per agent; NaN in
+        # the first one = no action this tick (Imitation: acceleration, angular velocity, -; a NaN angular velocity =
+        # the scalar form, the first float a speed to set)
+        return self._tick("smx_step" if lane else "smx_step_continuous", actions.data_ptr())
+
+    def _tick(self, entry: str, *args) -> Dict[str, torch.Tensor]:
+        """Issue one step entry point of the library (``args``: what it takes between the handle and the state block).
+        The call writes the next learner block (same extent and dtype as the other one); the blocks flip only when the
+        library took the call: a refusal raises and leaves ``out["learner"]`` and ``next_learner_block`` as they were."""
+        self._out.learner = self.next_learner_block.data_ptr()
+        rc = getattr(self.lib, entry)(self.handle, *args, C.byref(self._st), C.byref(self._sp), C.byref(self._out),
+                                      self._stream_ptr())
+        if rc != 0:
+            self._out.learner = self.out["learner"].data_ptr()
+            nat.check(self.lib, self.handle, rc, entry)
         self._learner_k ^= 1
         self.out["learner"] = self._learner[self._learner_k]
-        self._out.learner = self.out["learner"].data_ptr()  # same extent and dtype as the other block
-        if lane:
-            # (codes outside -1..3 cannot be seen from here without a device round trip: the kernel treats them
-            # as "no action" and smx_sync / BatchedSim.sync() reports them)
-            rc = self.lib.smx_step(self.handle, actions.data_ptr(), C.byref(self._st), C.byref(self._sp),
-                                   C.byref(self._out), self._stream_ptr())
-            nat.check(self.lib, self.handle, rc, "smx_step")
-        else:
-            # three floats per agent; NaN in the first one = no action this tick (Imitation: acceleration, angular
-            # velocity, -; a NaN angular velocity = the scalar form, the first float a speed to set)
-            rc = self.lib.smx_step_continuous(self.handle, actions.data_ptr(), C.byref(self._st), C.byref(self._sp),
-                                              C.byref(self._out), self._stream_ptr())
-            nat.check(self.lib, self.handle, rc, "smx_step_continuous")
         return self.out
 
     @property
@@ -945,13 +931,7 @@ class BatchedSim:
         trajectories = trajectories.to(device=self.device, dtype=torch.float64).contiguous()
         counts = counts.to(device=self.device, dtype=torch.int32).contiguous()
         assert trajectories.shape == (self.E, self.N, 4, nat.TRAJ_COLS) and counts.shape == (self.E, self.N)
-        self._learner_k ^= 1
-        self.out["learner"] = self._learner[self._learner_k]
-        self._out.learner = self.out["learner"].data_ptr()
-        rc = self.lib.smx_step_trajectory(self.handle, trajectories.data_ptr(), counts.data_ptr(), C.byref(self._st),
-                                          C.byref(self._sp), C.byref(self._out), self._stream_ptr())
-        nat.check(self.lib, self.handle, rc, "smx_step_trajectory")
-        return self.out
+        return self._tick("smx_step_trajectory", trajectories.data_ptr(), counts.data_ptr())
 
     def step_target_pose(self, targets: torch.Tensor, ego_centric: bool = False) -> Dict[str, torch.Tensor]:
         """One tick in ActionSpaceType.TargetPose: ``targets`` float64 [E, N, 4] = x, y, heading, seconds into the
@@ -966,13 +946,7 @@ class BatchedSim:
         targets = targets.to(device=self.device, dtype=torch.float64).contiguous()
         if tuple(targets.shape) != (self.E, self.N, 4):
             raise ValueError(f"TargetPose actions must have shape {(self.E, self.N, 4)}, got {tuple(targets.shape)}")
-        self._learner_k ^= 1
-        self.out["learner"] = self._learner[self._learner_k]
-        self._out.learner = self.out["learner"].data_ptr()
-        rc = self.lib.smx_step_target_pose(self.handle, targets.data_ptr(), C.byref(self._st), C.byref(self._sp),
-                                           C.byref(self._out), self._stream_ptr())
-        nat.check(self.lib, self.handle, rc, "smx_step_target_pose")
-        return self.out
+        return self._tick("smx_step_target_pose", targets.data_ptr())
 
     def step_trajectory_with_time(self, trajectories: torch.Tensor, counts: torch.Tensor,
                                   ego_centric: bool = False) -> Dict[str, torch.Tensor]:
@@ -992,14 +966,7 @@ class BatchedSim:
                 or tuple(counts.shape) != (self.E, self.N)):
             raise ValueError(f"TrajectoryWithTime actions must have shapes {(self.E, self.N, 5, 'T >= 2')} and "
                              f"{(self.E, self.N)}, got {tuple(trajectories.shape)} and {tuple(counts.shape)}")
-        self._learner_k ^= 1
-        self.out["learner"] = self._learner[self._learner_k]
-        self._out.learner = self.out["learner"].data_ptr()
-        rc = self.lib.smx_step_trajectory_with_time(self.handle, trajectories.data_ptr(), counts.data_ptr(),
-                                                    int(trajectories.shape[3]), C.byref(self._st), C.byref(self._sp),
-                                                    C.byref(self._out), self._stream_ptr())
-        nat.check(self.lib, self.handle, rc, "smx_step_trajectory_with_time")
-        return self.out
+        return self._tick("smx_step_trajectory_with_time", trajectories.data_ptr(), counts.data_ptr(), int(trajectories.shape[3]))
 
     def set_timing(self, level):
         """0/False = off, 1/True = one event pair per smx_step, 2 = per-kernel phases."""

@@ -244,3 +244,31 @@ def test_entry_errors(compiled_maps):
     torch.cuda.synchronize()
     assert out["rgb"] is other and bool((other[:, :AGENTS] != 0).any())
     sim.close()
+
+
+def test_a_refused_step_leaves_the_learner_blocks_as_they_were(compiled_maps):
+    """A step the library refuses (SMX_ERR_STATE: no image buffer bound) flips nothing: ``out["learner"]`` and
+    ``next_learner_block`` stay the tensors they were, and the next step that goes ahead writes the block that was
+    named before the refusal."""
+    import torch
+
+    sim = _sim(compiled_maps("loop"), 217, "small", **GRID)
+    images = sim.out["rgb"]
+    sim.reset()
+    torch.cuda.synchronize()
+    current, coming = sim.out["learner"], sim.next_learner_block
+    assert current is not coming and current.data_ptr() != coming.data_ptr()
+    sim.bind_rgb(None)
+    with pytest.raises(nat.SmxError, match=r"\(-3\).*smx_set_rgb_output"):  # SMX_ERR_STATE
+        _keep_lane(sim)
+    assert sim.out["learner"] is current and sim.next_learner_block is coming
+    sim.bind_rgb(images)
+    current.fill_(-7.0)
+    coming.fill_(-7.0)
+    torch.cuda.synchronize()
+    out = _keep_lane(sim)
+    torch.cuda.synchronize()
+    assert out["learner"] is coming and sim.next_learner_block is current
+    # the tick wrote the named block ([2, E, N]) and left the other one alone
+    assert bool((coming[..., :AGENTS] != -7.0).any()) and bool((current == -7.0).all())
+    sim.close()
