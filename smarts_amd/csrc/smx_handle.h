@@ -1,7 +1,8 @@
 // smx_handle.h — the handle of the C-ABI (include/smx.h) and everything it owns: device allocations, side streams,
 // event pools, and the bindings smx_load_map / smx_set_* make.  No kernel, no launch, no __device__: smx_kernels.hip
-// includes it and forwards its extern "C" entry points here, and tests/native/host_handle.cpp compiles it with g++ over a
-// host stand-in of the HIP memory calls, under AddressSanitizer and UBSan, with every HIP call failing in turn.
+// includes it (as does smx_tick.h, for CtrlHandoff and SMX_SEG_STRIDE) and forwards its extern "C" entry points here,
+// and tests/native/host_handle.cpp compiles it with g++ over a host stand-in of the HIP memory calls, under
+// AddressSanitizer and UBSan, with every HIP call failing in turn.
 //
 // Three rules hold throughout:
 //   One owner.  A device allocation is a DeviceBlob member of the handle and is freed by it alone; the side streams and

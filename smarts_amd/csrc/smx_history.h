@@ -11,6 +11,7 @@
 // plus an int32 tick count cannot overflow them) and compared against [0, n_frames) before it indexes anything, and a
 // replaced id is only ever compared.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/smx.h"

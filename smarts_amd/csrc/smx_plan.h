@@ -51,7 +51,7 @@ static constexpr size_t smx_ogm_mask_words(size_t tile_bytes) { return (tile_byt
 #ifndef SMX_FACTS_EARLY_MAX  // the facts half leaves with the grid kernels up to this many vehicles, else after the seeds half
 #define SMX_FACTS_EARLY_MAX 32768
 #endif
-// developer timing switches (SMX_SKIP in smx_kernels.hip) that change the plan: the small form / its split scan forced
+// developer timing switches (SMX_SKIP in smx_tick.h) that change the plan: the small form / its split scan forced
 #define SMX_SKIP_FORCE_SMALL 131072
 #define SMX_SKIP_FORCE_SCAN_SPLIT 65536
 

@@ -1,5 +1,5 @@
 """OGM delta stores on the device: a call stores only the pieces of a tile that are non-zero now or were after the last
-call (KernelArgs::ogm_mask in smarts_amd/csrc/smx_kernels.hip), and the rows read exactly as if whole tiles had been
+call (KernelArgs::ogm_mask in smarts_amd/csrc/smx_tick.h), and the rows read exactly as if whole tiles had been
 stored.  Every kernel form that writes tiles, at the shapes tests/test_gpu_large_form_features.py::test_ogm_kernel_forms
 draws them at:
 

@@ -53,5 +53,8 @@ def test_the_handle_header_launches_nothing():
     assert set(re.findall(r"\bhip[A-Z]\w+", code)) <= allowed, set(re.findall(r"\bhip[A-Z]\w+", code)) - allowed
     kernels = open(os.path.join(CSRC, "smx_kernels.hip")).read()
     assert '#include "smx_handle.h"' in kernels
-    # ownership is the header's alone: the kernels' file allocates and frees nothing
-    assert not re.search(r"\bhip(Malloc|Free)\s*\(", re.sub(r"//[^\n]*", "", kernels))
+    # ownership is the header's alone: the kernels' file and every other header allocate and free nothing
+    others = sorted(f for f in os.listdir(CSRC) if f != "smx_handle.h")
+    assert "smx_kernels.hip" in others and "smx_tick.h" in others
+    for name in others:
+        assert not re.search(r"\bhip(Malloc|Free)\s*\(", re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, name)).read())), name
