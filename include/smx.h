@@ -786,6 +786,48 @@ enum { SMX_HA_DRIVEN = 3 }; /* a history agent driven by its action in this tick
 int smx_set_history_handover(smx_handle h, const smx_history_handover* ho);
 int smx_check_history_handover(const smx_config* cfg, const smx_social_history* hist, const smx_history_handover* ho, char* err,
                                uint64_t err_len);
+/* Bubbles over a replayed history, evaluated on the device (the reference's BubbleManager.step, bubble_manager.py:393-463,
+ * for PositionalZone bubbles; DESIGN.md section 5.21 restates the rule).  While bound, every smx_step_history_handover tick
+ * starts with a bubble pass over the poses the previous pass left; it keeps one state byte and one cursor byte per agent:
+ *   state_dev    [E*N] SMX_BUBBLE_SOCIAL / _SHADOWED / _HIJACKED / _RELEASED, agents' bytes only, valid for the episode
+ *   cursor_dev   [E*N] bit b set: the agent's cursor at bubble b had a state (InBubble / InAirlock) in the last pass
+ * Both rows read 0 for an env after its reset pass (smx_reset, or under auto_reset inside the tick).
+ *   geometry     a bubble is the rectangle size_x x size_y (inner zone) and the same rectangle grown by `margin` on every
+ *                side (airlock); boundaries are outside.  follow_agent < 0: centred at (x, y), axis-aligned.
+ *                follow_agent = k: pinned to agent slot k of the same env, q = R(-heading_k) (p - p_k) - (offset_x,
+ *                offset_y), (x, y) unused; inactive (no cursors, its cursor bits clear, states stay) while k is not alive.
+ *   the pass     agents in ascending slot, bubbles in ascending index; only alive agents have cursors; limits count the
+ *                agents the previous pass left hijacked / shadowed at the bubble and the cursors made earlier in this pass
+ *                (0 = no limit).  SOCIAL -> SHADOWED in the airlock, SHADOWED -> HIJACKED inside, HIJACKED -> RELEASED and
+ *                SHADOWED -> SOCIAL once outside both.  An agent the handover table drives in the tick makes no transition.
+ *   the tick     an agent is DRIVEN iff the handover table says so (when one is bound) or its state is HIJACKED: status
+ *                SMX_HA_DRIVEN, as a table-driven agent in every word.  SOCIAL and SHADOWED agents follow as in every
+ *                mixed tick, status SMX_HA_FOLLOWING / SMX_HA_SHADOWED, expert action written for both.  A RELEASED agent
+ *                ends as a leaving follower ends: nothing stored, observed once more at the held pose with done = 1,
+ *                active = 0, counted as finished (SMX_F_LEFT), status SMX_HA_RELEASED; its recorded twin stays hidden.
+ * smx_step_history_agents and smx_step_continuous ignore the bubbles and do not touch the two rows.
+ * smx_set_history_bubbles needs bound history agents (SMX_ERR_STATE otherwise); refused (SMX_ERR_INVALID): n_bubbles
+ * outside 1..SMX_MAX_BUBBLES, a field that is not finite, a size or margin <= 0, follow_agent >= A, a negative limit,
+ * shadow_limit != 0 and < hijack_limit, a NULL row or one of fewer than E * N bytes.  hb = NULL unbinds; whatever drops
+ * the history agents drops the bubbles.  With bubbles bound smx_step_history_handover needs no handover table.  Waits for
+ * the device.  smx_check_history_bubbles is the validation alone, without a device or a handle. */
+#define SMX_MAX_BUBBLES 8
+typedef struct smx_bubble {
+  double x, y, size_x, size_y, margin, offset_x, offset_y;
+  int32_t follow_agent; /* agent slot of the same env the bubble travels with, -1 = fixed at (x, y) */
+  int32_t hijack_limit, shadow_limit; /* 0 = none */
+} smx_bubble;
+typedef struct smx_history_bubbles {
+  const smx_bubble* bubbles_host; /* host, [n_bubbles]; copied by the call */
+  int32_t n_bubbles;
+  uint8_t* state_dev;  /* device, caller-owned, [E*N] SMX_BUBBLE_* */
+  uint8_t* cursor_dev; /* device, caller-owned, [E*N] one bit per bubble */
+  uint64_t state_count, cursor_count;
+} smx_history_bubbles;
+enum { SMX_BUBBLE_SOCIAL = 0, SMX_BUBBLE_SHADOWED = 1, SMX_BUBBLE_HIJACKED = 2, SMX_BUBBLE_RELEASED = 3 };
+enum { SMX_HA_SHADOWED = 4, SMX_HA_RELEASED = 5 }; /* following while shadowed by a bubble; released by one in this tick */
+int smx_set_history_bubbles(smx_handle h, const smx_history_bubbles* hb);
+int smx_check_history_bubbles(const smx_config* cfg, const smx_history_bubbles* hb, char* err, uint64_t err_len);
 /* Frame stacking (smx_config.frame_stack = k): for every agent the device keeps the last k frames of each bound row,
  * newest first (frame 0 is this pass's row), in a caller-owned device buffer.  At the end of every smx_reset / smx_step*
  * pass, on the caller's stream, once every row of the pass is complete (under auto_reset: after the reset pass has

@@ -150,6 +150,22 @@ class SmxHistoryHandover(C.Structure):  # smx_history_handover (smx_set_history_
     _fields_ = [("tick_dev", _p), ("tick_count", C.c_uint64)]
 
 
+class SmxBubble(C.Structure):  # smx_bubble (smx_set_history_bubbles)
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("size_x", C.c_double), ("size_y", C.c_double), ("margin", C.c_double),
+                ("offset_x", C.c_double), ("offset_y", C.c_double), ("follow_agent", _i32), ("hijack_limit", _i32),
+                ("shadow_limit", _i32)]
+
+
+class SmxHistoryBubbles(C.Structure):  # smx_history_bubbles (smx_set_history_bubbles)
+    _fields_ = [("bubbles_host", C.POINTER(SmxBubble)), ("n_bubbles", _i32), ("state_dev", _p), ("cursor_dev", _p),
+                ("state_count", C.c_uint64), ("cursor_count", C.c_uint64)]
+
+
+MAX_BUBBLES = 8  # SMX_MAX_BUBBLES
+BUBBLE_SOCIAL, BUBBLE_SHADOWED, BUBBLE_HIJACKED, BUBBLE_RELEASED = 0, 1, 2, 3  # SMX_BUBBLE_*
+HA_SHADOWED, HA_RELEASED = 4, 5  # SMX_HA_*: following while shadowed by a bubble; released by one in this tick
+
+
 class SmxSpawns(C.Structure):
     _fields_ = [("episodes", _i32), ("pose", _p), ("social", _p), ("pose_count", C.c_uint64), ("social_count", C.c_uint64)]
 
@@ -215,6 +231,7 @@ EXPORTS = [
     "smx_set_history_agents", "smx_check_history_agents", "smx_step_history_agents",
     "smx_set_history_handover", "smx_check_history_handover", "smx_step_history_handover",
     "smx_invalidate_outputs", "smx_set_ogm_delta",
+    "smx_set_history_bubbles", "smx_check_history_bubbles",
 ]
 LAUNCH_FORMS = {0: "small", 1: "large_teams", 2: "large_one_lane"}
 LAUNCH_STRATEGIES = {"auto": 0, "small": 1, "large": 2, "large_one_lane": 3, "large_teams": 4}
@@ -322,6 +339,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.smx_check_history_handover.restype = C.c_int
     lib.smx_step_history_handover.argtypes = [h, _p, C.POINTER(SmxState), C.POINTER(SmxSpawns), C.POINTER(SmxOutputs), _p]
     lib.smx_step_history_handover.restype = C.c_int
+    lib.smx_set_history_bubbles.argtypes = [h, C.POINTER(SmxHistoryBubbles)]
+    lib.smx_set_history_bubbles.restype = C.c_int
+    lib.smx_check_history_bubbles.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxHistoryBubbles), C.c_char_p, C.c_uint64]
+    lib.smx_check_history_bubbles.restype = C.c_int
     lib.smx_read_phase_ms.argtypes = [h, C.POINTER(C.c_float), _i32, C.POINTER(_i32)]
     lib.smx_read_phase_ms.restype = C.c_int
     lib.smx_set_timing.argtypes = [h, C.c_int]

@@ -15,7 +15,7 @@
 //                       keeps vias, lidar rays, the image buffer and the frame stacks; re-checks the guard margin
 //       new missions    drop the goals and invalidate the knot keys
 //       a new history   (bind or unbind) drops dims, history agents and handover, and the carried alive list
-//       history agents  (bind or unbind) drop the handover table and the action / status rows
+//       history agents  (bind or unbind) drop the handover table, the bubbles and the action / status rows
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,6 +26,7 @@
 #include <utility>
 #include <vector>
 
+#include "smx_bubbles.h"
 #include "smx_guard.h"
 #include "smx_history.h"
 #include "smx_host.h"
@@ -195,6 +196,11 @@ struct smx_handle_s {
   float* ha_action;    // smx_set_history_agents: the caller's optional expert-action and status rows
   uint8_t* ha_status;
   int32_t history_max_id;  // the largest vehicle id of the bound table (-1: every cell empty)
+  // smx_set_history_bubbles: the bubbles (copied; k_bubbles gets them by value) and the caller's state and cursor rows
+  // (bubble_state null: none bound)
+  BubbleSet bubbles;
+  uint8_t* bubble_state;
+  uint8_t* bubble_cursor;
   // OGM delta stores (KernelArgs::ogm_mask): the tiles' piece mask, allocated with the handle when the OGM sensor is on.
   // The caller's out.ogm arrives with every call, so the masks describe the buffer of the last call only: `ogm_rows` is
   // that pointer, and a call that brings another one — or the first call, or the one after smx_invalidate_outputs /
@@ -295,10 +301,16 @@ static void unbind_missions(smx_handle h) {
   h->map.route_lane_ok = nullptr;
 }
 static void unbind_handover(smx_handle h) { h->history.handover = nullptr; }
+static void unbind_bubbles(smx_handle h) {
+  h->bubbles.n = 0;
+  h->bubble_state = nullptr;
+  h->bubble_cursor = nullptr;
+}
 static void unbind_history_agents(smx_handle h) {  // (every buffer is the caller's)
   h->history.follow = nullptr;
   h->history.n_agents = 0;
   unbind_handover(h);  // (the handover table is indexed as the follow table is)
+  unbind_bubbles(h);   // (the bubbles' rows and follow_agent are the followers')
   h->ha_action = nullptr;
   h->ha_status = nullptr;
 }
@@ -688,6 +700,27 @@ static int set_history_handover_impl(smx_handle h, const smx_history_handover* h
   SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
   unbind_handover(h);
   if (ho) h->history.handover = ho->tick_dev;
+  return SMX_OK;
+}
+
+static int set_history_bubbles_impl(smx_handle h, const smx_history_bubbles* hb) {
+  if (!h) return SMX_ERR_INVALID;
+  BubbleSet set{};  // filled here, committed after the wait
+  if (hb) {
+    if (h->history.follow == nullptr) return fail(h, SMX_ERR_STATE, "smx_set_history_bubbles needs bound history agents (smx_set_history_agents)");
+    std::string msg;
+    const int rc = check_history_bubbles_impl(h->cfg, *hb, msg);
+    if (rc != SMX_OK) return fail(h, rc, msg);
+    std::copy(hb->bubbles_host, hb->bubbles_host + hb->n_bubbles, set.b);
+    set.n = hb->n_bubbles;
+  }
+  SMX_HIP(hipSetDevice(h->device));
+  SMX_HIP(hipDeviceSynchronize());  // launches in flight still write the old rows
+  unbind_bubbles(h);
+  if (!hb) return SMX_OK;
+  h->bubbles = set;
+  h->bubble_state = hb->state_dev;
+  h->bubble_cursor = hb->cursor_dev;
   return SMX_OK;
 }
 

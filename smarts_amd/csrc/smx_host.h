@@ -458,6 +458,43 @@ inline int check_history_handover_impl(const smx_config& c, int32_t rows, const 
   return SMX_OK;
 }
 
+// ---- Bubbles (smx_set_history_bubbles / smx_check_history_bubbles) ----
+// k_bubbles indexes the two rows by vehicle and reads agent slot follow_agent of the env it works on: the counts and the
+// slot are checked against those shapes here; the limits' rule is BubbleLimits.__post_init__'s.
+inline int check_history_bubbles_impl(const smx_config& c, const smx_history_bubbles& hb, std::string& err) {
+  if (c.num_envs <= 0 || c.num_vehicles <= 0) return refuse(err, "history bubbles: num_envs and num_vehicles must be > 0");
+  if (c.num_social <= 0 || c.num_social >= c.num_vehicles)
+    return refuse(err, "history bubbles: the configuration needs social slots (the history's) and at least one agent slot");
+  if (c.num_vehicles - c.num_social > 64) return refuse(err, "history bubbles: an env's agent slots must fit one wavefront (64)");
+  if (hb.n_bubbles < 1 || hb.n_bubbles > SMX_MAX_BUBBLES)
+    return refuse(err, "history bubbles: n_bubbles is " + std::to_string(hb.n_bubbles) + ", 1 .. " + std::to_string(SMX_MAX_BUBBLES) + " are held");
+  if (!hb.bubbles_host) return refuse(err, "history bubbles: bubbles_host is NULL");
+  const int32_t agents = c.num_vehicles - c.num_social;
+  for (int32_t i = 0; i < hb.n_bubbles; ++i) {
+    const smx_bubble& b = hb.bubbles_host[i];
+    const std::string at = "history bubbles: bubble " + std::to_string(i);
+    const double fields[7] = {b.x, b.y, b.size_x, b.size_y, b.margin, b.offset_x, b.offset_y};
+    for (double f : fields)
+      if (!std::isfinite(f)) return refuse(err, at + " has a field that is not finite");
+    if (!(b.size_x > 0.0 && b.size_y > 0.0)) return refuse(err, at + ": size_x and size_y must be > 0");
+    if (!(b.margin > 0.0)) return refuse(err, at + ": margin must be > 0");
+    if (b.follow_agent >= agents)
+      return refuse(err, at + ": follow_agent is " + std::to_string(b.follow_agent) + ", an env has " + std::to_string(agents) + " agent slots");
+    if (b.hijack_limit < 0 || b.shadow_limit < 0) return refuse(err, at + ": a limit is negative (0 = none)");
+    if (b.shadow_limit != 0 && b.shadow_limit < b.hijack_limit)
+      return refuse(err, at + ": shadow_limit " + std::to_string(b.shadow_limit) + " is below hijack_limit " + std::to_string(b.hijack_limit));
+  }
+  const uint64_t total = (uint64_t)c.num_envs * (uint64_t)c.num_vehicles;
+  if (!hb.state_dev || !hb.cursor_dev) return refuse(err, "history bubbles: state_dev or cursor_dev is NULL");
+  if (hb.state_count < total)
+    return refuse(err, "history bubbles: state " + std::to_string(hb.state_count) + " elements declared, num_envs * num_vehicles is " +
+                           std::to_string(total) + " (a short row would be an out-of-bounds device write)");
+  if (hb.cursor_count < total)
+    return refuse(err, "history bubbles: cursor " + std::to_string(hb.cursor_count) + " elements declared, num_envs * num_vehicles is " +
+                           std::to_string(total) + " (a short row would be an out-of-bounds device write)");
+  return SMX_OK;
+}
+
 // ---- Frame stacking (smx_bind_frame_stack / smx_check_frame_stack) ----
 // bytes per agent of a stackable source, 0 with the reason in `err`: a row of smx_outputs by its SMX_OUT_* index — stackable,
 // its sensor on, its elements times the size of its dtype — or the image by SMX_STACK_SOURCE_RGB

@@ -34,6 +34,7 @@
 #include <string>
 #include <vector>
 
+#include "smx_bubbles.h"
 #include "smx_guard.h"
 #include "smx_handle.h"
 #include "smx_history.h"
@@ -738,9 +739,12 @@ __device__ __forceinline__ bool interpolate_trajectory(const double* tr, int n, 
 // has in the frame of the coming observation, Vehicle.update_state -> control(pose, speed, dt), smarts.py:919-921,
 // vehicle.py:573-579; no action is read.  HANDOVER, Imitation only, never with FOLLOW: the tick of
 // smx_step_history_handover — each lane decides from the handover table whether its agent follows, as above, or is driven
-// by its action as in the plain form, switch_control_to_agent's BoxChassis at the held pose and speed, smarts.py:505-561)
-template <int SPACE, bool GUARD = false, bool FOLLOW = false, bool HANDOVER = false>
-__global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic(const KernelArgs a) {
+// by its action as in the plain form, switch_control_to_agent's BoxChassis at the held pose and speed, smarts.py:505-561.
+// BUBBLES, with HANDOVER only: that tick with bubbles bound (smx_set_history_bubbles) — k_bubbles has left each agent's
+// state byte in `bubble_state`; a HIJACKED agent is driven as a table-driven one is, a RELEASED one ends as a leaving
+// follower does, a SHADOWED one follows under its own status; the table may be absent.)
+template <int SPACE, bool GUARD, bool FOLLOW, bool HANDOVER, bool BUBBLES>
+__device__ __forceinline__ void control_kinematic(const KernelArgs& a, const uint8_t* bubble_state) {
   const smx_config& c = a.cfg;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
   const size_t gid = (size_t)blockIdx.x * SMX_BLOCK + threadIdx.x;
@@ -765,10 +769,27 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic(const KernelArg
     const int env = (int)(gid / (size_t)c.num_vehicles);
     const int episode = a.st.env_episode[env];
     bool follows = true;
-    if constexpr (HANDOVER)
+    int follow_status = SMX_HA_FOLLOWING;
+    if constexpr (BUBBLES) {
+      const int bubble = bubble_state[gid];
+      if (a.history.handover != nullptr)
+        follows = !history_driven(history_handover(a.history, episode, env, (int)(gid - (size_t)env * c.num_vehicles)), a.st.env_ticks[env]);
+      if (bubble == SMX_BUBBLE_HIJACKED) follows = false;
+      if (follows && bubble == SMX_BUBBLE_RELEASED) {
+        // released by its bubble in this tick: the agent ends as a follower whose vehicle has left the recording ends
+        a.st.flags[gid] = flags | SMX_F_LEFT;
+        history_agent_report(a, gid, SMX_HA_RELEASED, 0, nullptr, -1);
+        return;
+      }
+      if (bubble == SMX_BUBBLE_SHADOWED) follow_status = SMX_HA_SHADOWED;
+    } else if constexpr (HANDOVER) {
       follows = !history_driven(history_handover(a.history, episode, env, (int)(gid - (size_t)env * c.num_vehicles)), a.st.env_ticks[env]);
+    }
     if (follows) {
-      history_agent_follow(a, gid, total, flags, env, episode, x, y);
+      if constexpr (BUBBLES)
+        history_agent_follow(a, gid, total, flags, env, episode, x, y, follow_status);
+      else
+        history_agent_follow(a, gid, total, flags, env, episode, x, y);
       return;
     }
     // a driven agent: the Imitation branch below from the state it holds — no expert label, and SMX_F_LEFT is never set
@@ -856,6 +877,99 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic(const KernelArg
   const double held_heading = SF(SMX_S_HEADING);
   SF(SMX_S_HEADING) = (SPACE == SMX_ACTION_SPACE_IMITATION && o.heading == held_heading) ? held_heading : wrap_heading(o.heading);
   SF(SMX_S_U) = o.speed;
+}
+template <int SPACE, bool GUARD = false, bool FOLLOW = false, bool HANDOVER = false>
+__global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic(const KernelArgs a) {
+  control_kinematic<SPACE, GUARD, FOLLOW, HANDOVER, false>(a, nullptr);
+}
+// (the BUBBLES form: the state row is the kernel's own second argument — KernelArgs does not grow for a rare binding)
+template <bool GUARD>
+__global__ void __launch_bounds__(SMX_BLOCK) k_control_kinematic_bubbles(const KernelArgs a, const uint8_t* bubble_state) {
+  control_kinematic<SMX_ACTION_SPACE_IMITATION, GUARD, false, true, true>(a, bubble_state);
+}
+
+// =================================================================================
+// k_bubbles (smx_set_history_bubbles; smx_bubbles.h holds the rule): the bubble pass ahead of the control kernel of a
+// mixed tick, one wavefront per env, one lane per agent slot, on the poses the previous pass left.  The zone tests run
+// per lane; ballots turn them and the state bytes into the per-bubble masks of bubble_recurrence, the serial loop over
+// the env's agent slots that the limits need, which every lane runs on the same words.  Each lane then applies its own
+// transitions in ascending bubble order and stores its two bytes.  An env in the first tick of an episode starts from
+// zero bytes whatever the rows hold (k_bubbles_clear zeroes them behind a reset pass of this entry point or of
+// smx_reset; a reset inside another entry point's tick leaves them alone).
+// =================================================================================
+struct BubbleArgs {
+  const int32_t* flags;        // [E*N]
+  const double* f64;           // [SMX_S_COUNT][E*N]
+  const int32_t* env_ticks;    // [E]
+  const int32_t* env_episode;  // [E]
+  HistoryDev history;          // (the handover table: who is an ego in this tick)
+  uint8_t* state;              // [E*N]
+  uint8_t* cursor;             // [E*N]
+  size_t total;
+  int num_envs, num_vehicles, n_agents, reset_elapsed_steps;
+};
+__global__ void __launch_bounds__(64) k_bubbles(const BubbleArgs g, const BubbleSet bs) {
+  const int env = (int)blockIdx.x, k = (int)threadIdx.x;
+  if (env >= g.num_envs) return;  // (uniform)
+  const bool lane = k < g.n_agents;
+  const size_t gid = (size_t)env * g.num_vehicles + (size_t)(lane ? k : 0);
+  const int ticks = g.env_ticks[env];
+  const bool fresh = ticks == g.reset_elapsed_steps;
+  const int flags = g.flags[gid];
+  const bool alive = lane && (flags & SMX_F_ALIVE) && !(flags & SMX_F_SOCIAL);
+  const double x = g.f64[(size_t)SMX_S_X * g.total + gid], y = g.f64[(size_t)SMX_S_Y * g.total + gid];
+  const double heading = g.f64[(size_t)SMX_S_HEADING * g.total + gid];
+  int state = fresh ? SMX_BUBBLE_SOCIAL : (int)g.state[gid];
+  const unsigned was = fresh ? 0u : (unsigned)g.cursor[gid];
+  const bool ego = lane && g.history.handover != nullptr && history_driven(history_handover(g.history, g.env_episode[env], env, lane ? k : 0), ticks);
+  const int seen = ego ? SMX_BUBBLE_EGO : state;
+  const uint64_t alive_m = __ballot(alive);
+  // (an agent that is not alive is in none of the three: for the reference's index a vehicle that is gone is neither
+  // hijacked nor shadowed, vehicle_index.py:189-201)
+  const uint64_t social_m = __ballot(alive && seen == SMX_BUBBLE_SOCIAL), shadowed_m = __ballot(alive && seen == SMX_BUBBLE_SHADOWED),
+                 hijacked_m = __ballot(alive && seen == SMX_BUBBLE_HIJACKED);
+  unsigned now = 0;
+  int applied = state;
+  for (int b = 0; b < bs.n && b < SMX_MAX_BUBBLES; ++b) {  // (uniform)
+    const smx_bubble& bb = bs.b[b];
+    const int f = bb.follow_agent < g.n_agents ? bb.follow_agent : -1;  // (held below the agent count at the bind)
+    double fx = 0.0, fy = 0.0, fh = 0.0;
+    bool active = true;
+    if (f >= 0) {
+      fx = __shfl(x, f);
+      fy = __shfl(y, f);
+      fh = __shfl(heading, f);
+      active = ((alive_m >> f) & 1) != 0;
+    }
+    if (!active) continue;  // no cursors: this bubble's bits clear, states stay
+    const BubbleZone z = bubble_zone(bb, x, y, fx, fy, fh);
+    BubbleMasks m;
+    m.alive = alive_m;
+    m.social = social_m;
+    m.shadowed = shadowed_m;
+    m.hijacked = hijacked_m;
+    m.was_in = __ballot(lane && ((was >> b) & 1u));
+    m.in_bubble = __ballot(alive && z.in_bubble);
+    m.in_airlock = __ballot(alive && z.in_airlock);
+    const BubbleResult r = bubble_recurrence(m, g.n_agents, bb.hijack_limit, bb.shadow_limit);
+    if (lane) {
+      if (((r.cur_bubble | r.cur_airlock) >> k) & 1) now |= 1u << b;
+      applied = bubble_apply(applied, bubble_transition_of(r, k));  // (an ego makes none)
+    }
+  }
+  if (lane) {
+    g.state[gid] = (uint8_t)applied;
+    g.cursor[gid] = (uint8_t)now;
+  }
+}
+// Behind a reset pass: the two bytes of every agent of an env that has just been reset read 0.
+__global__ void __launch_bounds__(SMX_BLOCK) k_bubbles_clear(const BubbleArgs g) {
+  const size_t gid = (size_t)blockIdx.x * SMX_BLOCK + threadIdx.x;
+  if (gid >= g.total) return;
+  const int env = (int)(gid / (size_t)g.num_vehicles);
+  if ((int)(gid - (size_t)env * g.num_vehicles) >= g.n_agents || g.env_ticks[env] != g.reset_elapsed_steps) return;
+  g.state[gid] = 0;
+  g.cursor[gid] = 0;
 }
 
 // The vehicles k_control_fast left on its slow list (large batches), a fixed grid striding the list, whose length is only
@@ -5186,6 +5300,7 @@ static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_sta
   in.follow_entry = follow;
   in.ogm_mask = h->ogm_mask && h->ogm_delta;
   in.handover_entry = handover;
+  in.bubbles_bound = h->bubble_state != nullptr;
   return in;
 }
 
@@ -5295,6 +5410,14 @@ extern "C" int smx_check_history_handover(const smx_config* cfg, const smx_socia
 }
 
 extern "C" int smx_set_history_handover(smx_handle h, const smx_history_handover* ho) { return set_history_handover_impl(h, ho); }
+
+extern "C" int smx_check_history_bubbles(const smx_config* cfg, const smx_history_bubbles* hb, char* err, uint64_t err_len) {
+  std::string msg;
+  const int rc = (cfg && hb) ? check_history_bubbles_impl(*cfg, *hb, msg) : refuse(msg, "null config / history bubbles");
+  return report(rc, msg, err, err_len);
+}
+
+extern "C" int smx_set_history_bubbles(smx_handle h, const smx_history_bubbles* hb) { return set_history_bubbles_impl(h, hb); }
 
 extern "C" int smx_bind_frame_stack(smx_handle h, int32_t source, int32_t layout, void* stack_dev, uint64_t bytes) {
   return bind_frame_stack_impl(h, source, layout, stack_dev, bytes);
@@ -5408,6 +5531,24 @@ static ControlKernels control_kernels(int action_space) {
   }
 }
 
+// what k_bubbles / k_bubbles_clear get of a call (only built with bubbles bound)
+static BubbleArgs bubble_args(const smx_handle_s* h, const KernelArgs& a) {
+  BubbleArgs g{};
+  g.flags = a.st.flags;
+  g.f64 = a.st.f64;
+  g.env_ticks = a.st.env_ticks;
+  g.env_episode = a.st.env_episode;
+  g.history = h->history;
+  g.state = h->bubble_state;
+  g.cursor = h->bubble_cursor;
+  g.total = (size_t)h->cfg.num_envs * h->cfg.num_vehicles;
+  g.num_envs = h->cfg.num_envs;
+  g.num_vehicles = h->cfg.num_vehicles;
+  g.n_agents = h->cfg.num_vehicles - h->cfg.num_social;
+  g.reset_elapsed_steps = h->cfg.reset_elapsed_steps;
+  return g;
+}
+
 static void launch_control(smx_handle h, const TickPlan& p, const KernelArgs& a, hipStream_t stream) {
   const ControlKernels k = p.guard ? control_kernels<true>(h->cfg.action_space) : control_kernels<false>(h->cfg.action_space);
   switch (p.control) {
@@ -5433,6 +5574,11 @@ static void launch_control(smx_handle h, const TickPlan& p, const KernelArgs& a,
     case Control::KINEMATIC_HANDOVER:  // (the binding again; smx_step_history_handover holds actions_f32 to non-null)
       launch(p.guard ? k_control_kinematic<SMX_ACTION_SPACE_IMITATION, true, false, true> : k_control_kinematic<SMX_ACTION_SPACE_IMITATION, false, false, true>,
              p.veh_blocks, 0, stream, a);
+      break;
+    case Control::KINEMATIC_BUBBLES:  // (the bubble pass, then the mixed tick that reads its state row; both on the caller's stream)
+      hipLaunchKernelGGL(k_bubbles, dim3((unsigned)h->cfg.num_envs), dim3(64), 0, stream, bubble_args(h, a), h->bubbles);
+      hipLaunchKernelGGL(p.guard ? k_control_kinematic_bubbles<true> : k_control_kinematic_bubbles<false>, dim3(p.veh_blocks), dim3(SMX_BLOCK), 0,
+                         stream, a, (const uint8_t*)h->bubble_state);
       break;
   }
 }
@@ -5704,7 +5850,7 @@ static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const
   if (follow) {  // (the binding holds cfg.action_space to Imitation; the tick reads no action)
     if (h->history.follow == nullptr) return fail(h, SMX_ERR_STATE, "smx_step_history_agents: no history agents are bound (smx_set_history_agents)");
   } else if (handover) {  // (the binding holds cfg.action_space to Imitation; the driven agents' rows are read)
-    if (h->history.follow == nullptr || h->history.handover == nullptr)
+    if (h->history.follow == nullptr || (h->history.handover == nullptr && h->bubble_state == nullptr))
       return fail(h, SMX_ERR_STATE, "smx_step_history_handover: no handover table is bound (smx_set_history_handover)");
     if (actions_f32 == nullptr) return fail(h, SMX_ERR_INVALID, "smx_step_history_handover: actions_dev is NULL");
   } else if (is_step) {
@@ -5764,6 +5910,9 @@ static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const
   }
   rc = tail_and_reset_pass(h, p, a, mask, st, stream, ph);
   if (rc != SMX_OK) return rc;
+  // bubbles: an env that this pass has reset (smx_reset, or auto_reset inside a mixed tick) starts from zero bytes
+  if (h->bubble_state != nullptr && (!is_step || (handover && p.reset_pass)))
+    hipLaunchKernelGGL(k_bubbles_clear, dim3(p.veh_blocks), dim3(SMX_BLOCK), 0, stream, bubble_args(h, a));
   if (p.frame_stack) {  // (after the reset pass: a restarted env's rows hold its first observation)
     rc = launch_frame_stacks(h, is_step, mask, st, out, stream);
     if (rc != SMX_OK) return rc;

@@ -94,6 +94,7 @@ struct PlanInputs {
   bool follow_entry;       // the call is smx_step_history_agents: the agents are placed on their recorded vehicles' rows
   bool ogm_mask;           // the handle holds the OGM tiles' piece mask and smx_set_ogm_delta has not switched it off
   bool handover_entry;     // the call is smx_step_history_handover: each agent follows or is driven, as its handover tick says
+  bool bubbles_bound;      // smx_set_history_bubbles holds bubbles: that call's tick starts with k_bubbles and reads its state row
 };
 
 enum class AliveList : uint8_t { NONE, CARRIED, BUILD };  // BUILD: k_alive_list ahead of the tick
@@ -102,8 +103,10 @@ enum class AliveList : uint8_t { NONE, CARRIED, BUILD };  // BUILD: k_alive_list
 // spaces and Trajectory the law alone (LAW); FAST_LISTED: one lane per vehicle, the rest through the slow list;
 // KINEMATIC: the kinematic spaces' k_control_kinematic, one lane per vehicle in either form (no candidate paths, no
 // control slow list); KINEMATIC_FOLLOW: its FOLLOW form, the tick of smx_step_history_agents — the same launch;
-// KINEMATIC_HANDOVER: its HANDOVER form, the tick of smx_step_history_handover — the same launch again
-enum class Control : uint8_t { NONE, ONE, ONE_LDS, PATHS_LAW, LAW, FAST_LISTED, KINEMATIC, KINEMATIC_FOLLOW, KINEMATIC_HANDOVER };
+// KINEMATIC_HANDOVER: its HANDOVER form, the tick of smx_step_history_handover — the same launch again;
+// KINEMATIC_BUBBLES: that tick with bubbles bound (smx_set_history_bubbles) — k_bubbles, then the BUBBLES form (it
+// stands first with its number: the older values keep theirs, and the line they end, which a test reads)
+enum class Control : uint8_t { KINEMATIC_BUBBLES = 9, NONE = 0, ONE, ONE_LDS, PATHS_LAW, LAW, FAST_LISTED, KINEMATIC, KINEMATIC_FOLLOW, KINEMATIC_HANDOVER };
 static constexpr bool smx_kinematic_space(int action_space) {
   // (one mask test; smx_create holds action_space to 0 .. SMX_ACTION_SPACE_IMITATION)
   constexpr unsigned kinematic = (1u << SMX_ACTION_SPACE_TARGET_POSE) | (1u << SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME) |
@@ -244,7 +247,9 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
   if (!in.is_step)
     p.control = Control::NONE;
   else if (smx_kinematic_space(c.action_space))
-    p.control = in.handover_entry ? Control::KINEMATIC_HANDOVER : in.follow_entry ? Control::KINEMATIC_FOLLOW : Control::KINEMATIC;
+    p.control = in.handover_entry ? (in.bubbles_bound ? Control::KINEMATIC_BUBBLES : Control::KINEMATIC_HANDOVER)
+                : in.follow_entry ? Control::KINEMATIC_FOLLOW
+                                  : Control::KINEMATIC;
   else if (!small && in.ctrl_blob)
     p.control = !lane_space ? Control::LAW : one_lane ? Control::FAST_LISTED : Control::PATHS_LAW;
   else

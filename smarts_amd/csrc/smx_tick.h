@@ -328,7 +328,7 @@ __device__ __forceinline__ void history_agent_report(const KernelArgs& a, size_t
   if (a.ha_status != nullptr) a.ha_status[gid] = (uint8_t)status;
   if (a.ha_action == nullptr) return;
   float acceleration = __builtin_nanf(""), angular_velocity = __builtin_nanf("");
-  if (status == SMX_HA_FOLLOWING) {
+  if (status == SMX_HA_FOLLOWING || status == SMX_HA_SHADOWED) {  // (a shadowed agent follows: its label is the follower's)
     const int next = history_find(a.history, frame + 1, v);
     if (next >= 0) {
       const double* to = history_row(a.history, frame + 1, next);
@@ -379,9 +379,10 @@ __device__ __forceinline__ int history_agents_absent(const KernelArgs& a, int en
 
 // A follower's tick (k_control_kinematic's FOLLOW form for every agent, its HANDOVER form for the agents the table does
 // not drive), on the flags word and position its caller has loaded: the agent is placed on the row its recorded vehicle
-// has in the frame of the coming observation, or leaves.
+// has in the frame of the coming observation, or leaves.  `status`: what a placed follower reports — SMX_HA_FOLLOWING, or
+// SMX_HA_SHADOWED from the BUBBLES form.
 __device__ __forceinline__ void history_agent_follow(const KernelArgs& a, size_t gid, size_t total, int flags, int env, int episode, double x,
-                                                     double y) {
+                                                     double y, int status = SMX_HA_FOLLOWING) {
   const smx_config& c = a.cfg;
   // (no placement test under the guard: every row of the table was checked against the grids when it was bound, and a
   // follower's byte reads 0 — also in a mixed tick, and for an agent that was driven a tick ago: it lands on a row too)
@@ -404,7 +405,7 @@ __device__ __forceinline__ void history_agent_follow(const KernelArgs& a, size_t
   SF(SMX_S_Y) = row[1];
   SF(SMX_S_HEADING) = row[2];  // (wrapped already, as Heading.__new__ wraps it: include/smx.h, frames_host)
   SF(SMX_S_U) = row[3];
-  history_agent_report(a, gid, SMX_HA_FOLLOWING, frame, row, v);
+  history_agent_report(a, gid, status, frame, row, v);
 }
 
 // Scripted social vehicle (lane follower: no controller, no dynamics), on state words its caller has loaded:

@@ -736,6 +736,7 @@ class BatchedSim:
     def _drop_history_agents(self):
         self.history_agents = None
         self.history_handover = None  # (the library drops the handover table with the follow table)
+        self._drop_history_bubbles()  # (... and the bubbles)
         self.out.pop("history_agent_status", None)
         self.out.pop("expert_action", None)
 
@@ -768,9 +769,40 @@ class BatchedSim:
         nat.check(self.lib, self.handle, self.lib.smx_set_history_handover(self.handle, C.byref(ho)), "smx_set_history_handover")
         self.history_handover = ticks  # (read by every mixed tick: lives as long as the binding)
 
+    def set_history_bubbles(self, bubbles):
+        """Bind bubbles (``smx_set_history_bubbles``; needs bound history agents): a sequence of 1 .. ``MAX_BUBBLES``
+        ``nat.SmxBubble`` — a rectangle ``size_x`` x ``size_y`` with an airlock ``margin`` around it, fixed at ``(x, y)``
+        or travelling with agent slot ``follow_agent`` at ``(offset_x, offset_y)`` in its frame, ``hijack_limit`` /
+        ``shadow_limit`` (0 = none).  Every ``step_history_handover(actions)`` tick then starts with the bubble pass
+        (``include/smx.h`` has the rule): ``out["bubble_state"]`` ``(E, N)`` uint8 holds ``BUBBLE_SOCIAL / SHADOWED /
+        HIJACKED / RELEASED`` per agent, ``out["bubble_cursor"]`` the per-bubble cursor bits.  A HIJACKED agent is driven
+        by its action, a RELEASED one ends; no handover table is needed.  ``step_history_agents()`` and ``step(actions)``
+        ignore the bubbles.  ``bubbles=None`` unbinds; so does everything that drops the history agents."""
+        if bubbles is None:
+            nat.check(self.lib, self.handle, self.lib.smx_set_history_bubbles(self.handle, None), "smx_set_history_bubbles")
+            self._drop_history_bubbles()
+            return
+        bubbles = list(bubbles)
+        state = torch.zeros((self.E, self.N), dtype=torch.uint8, device=self.device)
+        cursor = torch.zeros((self.E, self.N), dtype=torch.uint8, device=self.device)
+        hb = nat.SmxHistoryBubbles()
+        host = (nat.SmxBubble * max(len(bubbles), 1))(*bubbles)
+        hb.bubbles_host, hb.n_bubbles = host, len(bubbles)
+        hb.state_dev, hb.state_count = state.data_ptr(), int(state.numel())
+        hb.cursor_dev, hb.cursor_count = cursor.data_ptr(), int(cursor.numel())
+        nat.check(self.lib, self.handle, self.lib.smx_set_history_bubbles(self.handle, C.byref(hb)), "smx_set_history_bubbles")
+        self.history_bubbles = bubbles
+        self.out["bubble_state"] = state  # (written by every mixed tick: they live as long as the binding)
+        self.out["bubble_cursor"] = cursor
+
+    def _drop_history_bubbles(self):
+        self.history_bubbles = None
+        self.out.pop("bubble_state", None)
+        self.out.pop("bubble_cursor", None)
+
     def step_history_handover(self, actions: torch.Tensor) -> Dict[str, torch.Tensor]:
         """One tick in which every agent follows its recorded vehicle or is driven by its row of ``actions`` — float32
-        ``(E, N, 3)`` in ``step``'s Imitation layout — as the handover table says (``smx_step_history_handover``).
+        ``(E, N, 3)`` in ``step``'s Imitation layout — as the handover table and the bound bubbles say (``smx_step_history_handover``).
         Followers' and social rows of ``actions`` are ignored.  ``out["history_agent_status"]`` reads ``HA_DRIVEN`` for a
         driven agent and its ``out["expert_action"]`` row NaN, NaN, 0."""
         if not self._was_reset:
@@ -783,6 +815,7 @@ class BatchedSim:
 
     history_agents = None
     history_handover = None
+    history_bubbles = None
     history_dims = False
     traffic_history = None
     history_start_frames = None

@@ -5,6 +5,7 @@ from .agent_interface import (  # noqa: F401
     OGM, RGB, Accelerometer, ActionSpaceType, AgentInterface, AgentType, DoneCriteria, DrivableAreaGridMap,
     EventConfiguration, Lidar, NeighborhoodVehicles, RoadWaypoints, Waypoints,
 )
+from .bubbles import Bubble, BubbleLimits, MapZone, PositionalZone  # noqa: F401
 from .core import SMARTSDestroyedError, SMARTSNotSetupError  # noqa: F401
 from .ego_centric_adapters import ego_centric_observation_adapter, get_egocentric_adapters  # noqa: F401
 from .format_obs import FormatObs, StdObs  # noqa: F401

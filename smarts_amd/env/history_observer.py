@@ -11,6 +11,10 @@ recorded frame: a behaviour-cloning dataset is the two side by side.
 With ``handover`` the followers are handed over to actions one by one (``BatchedSim.set_history_handover``, the
 reference's ``SMARTS.switch_control_to_agent``): a log-replay warm-up, then ``step(actions)`` drives the agents whose
 handover tick has come while every other vehicle keeps replaying.
+
+With ``bubbles`` the device decides that itself, tick by tick (``BatchedSim.set_history_bubbles``, the reference's
+``BubbleManager.step``): a follower is shadowed in a bubble's airlock, driven inside, and released — it ends — once it is
+outside again; a bubble may travel with an agent that is itself driven.
 """
 from __future__ import annotations
 
@@ -65,11 +69,17 @@ class HistoryObserver:
     the interface's done criteria); nothing restarts.  ``handover`` (default ``None``: nobody is ever driven, every method
     behaves as without it): an int — the recorded ticks before every agent drives —, a mapping ``{vehicle id: ticks}``
     (vehicles it lacks are never driven), or a ready int32 table ``[1, E, A]`` (``TrafficHistoryTable.handover_ticks``
-    makes one from zone entry frames: a bubble)."""
+    makes one from zone entry frames: a bubble).  ``bubbles`` (default ``None``), alone or beside ``handover``: a sequence
+    of ``smarts_amd.env.Bubble`` with ``PositionalZone`` zones, evaluated on the device at the start of every tick;
+    ``follow_actor_id`` is an agent id of this observer (``agent_id``) and names the same agent slot in every env that has
+    it.  ``bubble_states()`` reads what they decided.  (``bubbles`` stands before ``handover`` in the signature: pass both
+    by keyword.)"""
+
+    bubbles = None
 
     def __init__(self, scenario: str, table_or_path, agent_interface: AgentInterface, vehicle_ids: Optional[Sequence[int]] = None,
                  num_envs: Optional[int] = None, dt: float = 0.1, num_agents: int = 1, device: str = "cuda:0",
-                 waypoint_window: Optional[Tuple[int, int]] = (4, 20), seed: int = 0, handover=None):
+                 waypoint_window: Optional[Tuple[int, int]] = (4, 20), seed: int = 0, bubbles=None, handover=None):
         import torch
 
         from ..engine import BatchedSim, make_spawns
@@ -102,6 +112,9 @@ class HistoryObserver:
         self.handover = None if handover is None else self._handover_table(handover)
         if self.handover is not None:
             self.sim.set_history_handover(torch.from_numpy(self.handover).to(self.sim.device))
+        self.bubbles = None if bubbles is None else list(bubbles)
+        if self.bubbles is not None:
+            self.sim.set_history_bubbles([b.to_native(self._slot_of) for b in self.bubbles])
         road_ids = [self.cm.road_ids[r] for r in self.cm.lane_road]
         names = [f"follower-{a}" for a in range(self.A)] + [f"social-{k}" for k in range(self.S)]
         self.builder = _FollowerNames(
@@ -116,6 +129,23 @@ class HistoryObserver:
         """``Agent-history-vehicle-<id>`` of the vehicle agent slot ``agent`` of env ``env`` follows, ``None`` for none."""
         v = int(self.followed[0, env, agent])
         return f"{AGENT_PREFIX}{HISTORY_VEHICLE_PREFIX}{v}" if v >= 0 else None
+
+    def _slot_of(self, agent_id: str) -> int:
+        """The agent slot that carries ``agent_id`` (a bubble's ``follow_actor_id``): one slot, in every env that has it."""
+        slots = {a for e in range(self.E) for a in range(self.A) if self.agent_id(e, a) == agent_id}
+        if len(slots) != 1:
+            raise ValueError(f"follow_actor_id {agent_id!r} names {'no agent' if not slots else 'different agent slots in different envs'}")
+        return slots.pop()
+
+    def bubble_states(self) -> List[Dict[str, int]]:
+        """Per env ``{agent id: BUBBLE_SOCIAL | BUBBLE_SHADOWED | BUBBLE_HIJACKED | BUBBLE_RELEASED}`` (``bubbles`` only)."""
+        if self.bubbles is None:
+            return [{} for _ in range(self.E)]
+        import torch
+
+        torch.cuda.synchronize(self.sim.device)
+        state = self.sim.out["bubble_state"].cpu().numpy()
+        return [{self.agent_id(e, a): int(state[e, a]) for a in range(self.A) if self.followed[0, e, a] >= 0} for e in range(self.E)]
 
     def _handover_table(self, handover) -> np.ndarray:
         """int32 ``[1, E, A]`` from an int, a mapping vehicle id -> ticks, or a ready table."""
@@ -134,16 +164,24 @@ class HistoryObserver:
         return table
 
     def driven(self) -> List[List[str]]:
-        """Per env, the ids of the agents the next ``step`` drives: alive, and their handover tick has come."""
-        if self.handover is None:
+        """Per env, the ids of the agents the last tick drove or whose handover tick has come: alive, and either the
+        handover table drives them in the next ``step`` or a bubble holds them (its state row reads HIJACKED; the bubble
+        pass of the next ``step`` may add to these, or release one)."""
+        if self.handover is None and self.bubbles is None:
             return [[] for _ in range(self.E)]
         import torch
 
         torch.cuda.synchronize(self.sim.device)
         ticks = self.sim.env_ticks.cpu().numpy()
         alive = (self.sim.flags[:, :self.A].cpu().numpy() & nat.F_ALIVE) != 0
+        by_table = np.zeros((self.E, self.A), dtype=bool)
+        if self.handover is not None:
+            by_table = (self.handover[0] >= 0) & (self.handover[0] <= ticks[:, None])
+        held = np.zeros((self.E, self.A), dtype=bool)
+        if self.bubbles is not None:
+            held = self.sim.out["bubble_state"][:, :self.A].cpu().numpy() == nat.BUBBLE_HIJACKED
         return [[self.agent_id(e, a) for a in range(self.A)
-                 if alive[e, a] and self.followed[0, e, a] >= 0 and 0 <= self.handover[0, e, a] <= ticks[e]] for e in range(self.E)]
+                 if alive[e, a] and self.followed[0, e, a] >= 0 and (by_table[e, a] or held[e, a])] for e in range(self.E)]
 
     def _action_rows(self, actions) -> np.ndarray:
         """float32 ``(E, N, 3)`` in ``BatchedSim.step``'s Imitation layout from ``{agent id: (acceleration,
@@ -172,14 +210,14 @@ class HistoryObserver:
         return self._collect(out)
 
     def step(self, actions=None):
-        """One tick.  ``actions`` (only with ``handover``): ``{agent id: (acceleration, angular_velocity) | speed}`` for
+        """One tick.  ``actions`` (only with ``handover`` or ``bubbles``): ``{agent id: (acceleration, angular_velocity) | speed}`` for
         the agents ``driven()`` names — one mapping for every env or a sequence of one per env; a missing id means no
         action, and what is given for a follower is ignored."""
         if not self._was_reset:
             raise RuntimeError("step() before reset()")
-        if self.handover is None:
+        if self.handover is None and self.bubbles is None:
             if actions is not None:
-                raise ValueError("actions need a handover: without one every agent follows its recorded vehicle")
+                raise ValueError("actions need a handover or bubbles: without either every agent follows its recorded vehicle")
             return self._collect(self.sim.step_history_agents())
         import torch
 
@@ -195,7 +233,7 @@ class HistoryObserver:
         act = self.sim.out["expert_action"].cpu().numpy()
         status = self.sim.out["history_agent_status"].cpu().numpy()
         return [{self.agent_id(e, a): act[e, a, :2].copy() for a in range(self.A)
-                 if self.followed[0, e, a] >= 0 and status[e, a] in (nat.HA_FOLLOWING, nat.HA_DRIVEN)} for e in range(self.E)]
+                 if self.followed[0, e, a] >= 0 and status[e, a] in (nat.HA_FOLLOWING, nat.HA_SHADOWED, nat.HA_DRIVEN)} for e in range(self.E)]
 
     def _collect(self, out):
         import torch
@@ -218,7 +256,8 @@ class HistoryObserver:
                 if name is None or not (active or ended):
                     continue
                 # (a vehicle that left the recording this tick is done without an observation, agent_manager.py:153-157)
-                left = rows["history_agent_status"][e, a] == nat.HA_LEFT
+                # (... and so is one its bubble released)
+                left = rows["history_agent_status"][e, a] in (nat.HA_LEFT, nat.HA_RELEASED)
                 if not left:
                     obs[name] = self.builder.build(er, a, t, round(t * self.dt, 6))
                     rew[name] = float(rows["reward"][e, a])
