@@ -687,8 +687,9 @@ int smx_check_social_history(const smx_config* cfg, const smx_map_tables* map, c
  * and the lidar (the mate's half length and half width; vertically the box keeps the sedan's underside,
  * SMX_BASE_HEIGHT + 0.1, and rises by the vehicle's height — the reference centres a BoxChassis box on z = 0, this path
  * stands every vehicle on the ground).  Not read by: the state rows of replayed slots (unchanged), the scripted models,
- * the ego's own box row, the off-route and path-seed radii, the neighbours' lane lookup (the EGO's length,
- * sensors.py:244-246).  Agents stay sedans, an agent that stands in for a recorded truck (`replaced`) included.
+ * and anything of an agent's own box: its ego box row, its off-route and path-seed radii, its neighbours' lane lookup (the
+ * EGO's length, sensors.py:244-246) are the agent's (smx_set_agent_dims below; without it agents are sedans, an agent
+ * that stands in for a recorded truck, `replaced`, included).
  * Needs a bound history (SMX_ERR_STATE without one); smx_set_social_history, with a table or NULL, and smx_load_map
  * drop the dimensions.  dims = NULL unbinds: the sedan's box again from the next tick.  Refused (SMX_ERR_INVALID, the
  * reason in smx_last_error): n_ids < 1; a non-empty cell of the bound vehicle_host whose id is >= n_ids; a value that is
@@ -702,6 +703,53 @@ typedef struct smx_social_dims {
 int smx_set_social_history_dims(smx_handle h, const smx_social_dims* dims);
 int smx_check_social_history_dims(const smx_config* cfg, const smx_social_history* hist, const smx_social_dims* dims, char* err,
                                   uint64_t err_len);
+/* Per-agent vehicle dimensions (Vehicle.agent_vehicle_dims -> BoxChassis, vehicle.py:339-357, 426-431; a recorded
+ * vehicle keeps its own when an agent takes it over, vehicle_index.py:439, 489).  Opt-in: with nothing bound every agent
+ * has the sedan's box, as before.
+ *   dims_host[rows][num_envs][num_agents][3]   length, width, height in metres (num_agents = num_vehicles - num_social);
+ *                                              three NaNs = the sedan's box
+ *   rows                                       an episode uses row (episode mod rows), as the spawn tables do
+ * A host pointer; the handle keeps a device copy and a triple per (env, vehicle) — the block smx_set_social_history_dims
+ * uses, which exists while either binding holds.  An agent's triple is written where its spawn pose is (a reset, the
+ * restart inside a launch under auto_reset, a history agent's placement) and nowhere else: a follower that is later
+ * shadowed, handed over, hijacked or released keeps it.  Read by everything that asks for a box: the agent's own
+ * collision test, the four corners behind on_shoulder / off_road, its ego box row, the lane lookups within its length
+ * (its neighbours' lane ids, the trip meter's first waypoint), its off_route radius (half diagonal + 5), and, as an
+ * env-mate, nb_box, the OGM, the RGB image and the lidar.  Not read by: motion (the kinematic spaces move a pose), the
+ * scripted models' gap, lane-TTC, road waypoints, bubbles and the state guard.
+ * The kinematic spaces only (SMX_ACTION_SPACE_TARGET_POSE, _TRAJECTORY_WITH_TIME, _IMITATION — and so every history
+ * agent): the dynamic spaces' model constants are the sedan's.  Deviation: the reference ignores the dimensions of an
+ * agent on a dynamic chassis with a warning (vehicle.py:410-415); here the call is refused.
+ * The cap.  Length <= 10 m, width <= 25 m, height <= 10 m (the reference's largest type, the trailer, is 10 x 2.5 x 4).
+ *   length  An observer reports a neighbour's lane as nearest_lane(neighbour, radius = the OBSERVER's length)
+ *           (sensors.py:245).  That lookup is answered from the neighbour's own road-facts search, which — for a social
+ *           slot and for an agent alike — runs at SMX_POSE_SCAN_RADIUS = 10 m (or two lane widths where that is more)
+ *           and keeps a lane only at a distance below that radius.  An observer longer than 10 m would be told "no lane"
+ *           for a neighbour whose lane is 10 m or more away where the reference finds one, so the length is capped at
+ *           that radius (SMX_AGENT_DIMS_MAX_LENGTH; the trailer's 10 m is exact: "dist < 10" is "dist < length").  A
+ *           recorded vehicle longer than 10 m can be replayed (smx_set_social_history_dims) but not followed at its
+ *           own length.
+ *   width   The agent's OWN lookups need a search that follows its box, and get one on this path: it runs at
+ *           radius = max(SMX_POSE_SCAN_RADIUS, half diagonal + max(5, widest road_with_point threshold)) — the
+ *           off_route radius is half diagonal + 5, 10.15 m for the trailer — and keeps every segment within threshold
+ *           + half diagonal of the centre, which covers the four corners (the sedan: the 10 m and 2 m of the path
+ *           without dimensions); the collision test's broad phase is boxes_within's own (half diagonal + the mate's +
+ *           the leeway).  Neither bounds the width; what does is what bounds a replayed vehicle's: the reaches and
+ *           pixel rectangles the mate-side consumers form from a triple, SMX_DIMS_MAX_PLANAR = 25 m.
+ *   height  SMX_DIMS_MAX_HEIGHT = 10 m, as for a replayed vehicle (the lidar's box).
+ * A box that outgrows the one-lane scan's candidate lists (SMX_FACTS_SPAN grid rows: a trailer's reach often does) is
+ * served by the team form through the slow list, as any vehicle those cannot serve.
+ * Refused (SMX_ERR_INVALID, the reason in smx_last_error): another action space; a null table; rows < 1; a component that
+ * is not finite, <= 0 or above its cap; a triple that is only partly NaN.  dims = NULL unbinds: every agent is a sedan
+ * again from its next (re)spawn (at once when no social dimensions are bound either).  smx_set_social_history, with a
+ * table or NULL, keeps the agents' dimensions (it drops the social ones); smx_load_map drops both.  Waits for the device.
+ * smx_check_agent_dims is the validation alone, without a device or a handle. */
+typedef struct smx_agent_dims {
+  const double* dims_host; /* [rows][num_envs][num_agents][3] length, width, height; NaN x 3 = the sedan's */
+  int32_t rows;
+} smx_agent_dims;
+int smx_set_agent_dims(smx_handle h, const smx_agent_dims* dims);
+int smx_check_agent_dims(const smx_config* cfg, const smx_agent_dims* dims, char* err, uint64_t err_len);
 /* History agents (the reference's SMARTS.attach_sensors_to_vehicles + observe_from over a traffic history, smarts.py:
  * 914-921: a recorded vehicle that carries sensors is a BoxChassis moved by Vehicle.control(pose, speed, dt)).  While
  * bound, agent slot `a` of env `e` follows recorded vehicle

@@ -137,6 +137,10 @@ class SmxSocialDims(C.Structure):  # smx_social_dims (smx_set_social_history_dim
     _fields_ = [("dims_host", _p), ("n_ids", _i32)]
 
 
+class SmxAgentDims(C.Structure):  # smx_agent_dims (smx_set_agent_dims)
+    _fields_ = [("dims_host", _p), ("rows", _i32)]
+
+
 class SmxHistoryAgents(C.Structure):  # smx_history_agents (smx_set_history_agents)
     _fields_ = [("vehicle_dev", _p), ("vehicle_count", C.c_uint64), ("action_dev", _p), ("status_dev", _p),
                 ("action_count", C.c_uint64), ("status_count", C.c_uint64)]
@@ -232,6 +236,7 @@ EXPORTS = [
     "smx_set_history_handover", "smx_check_history_handover", "smx_step_history_handover",
     "smx_invalidate_outputs", "smx_set_ogm_delta",
     "smx_set_history_bubbles", "smx_check_history_bubbles",
+    "smx_set_agent_dims", "smx_check_agent_dims",
 ]
 LAUNCH_FORMS = {0: "small", 1: "large_teams", 2: "large_one_lane"}
 LAUNCH_STRATEGIES = {"auto": 0, "small": 1, "large": 2, "large_one_lane": 3, "large_teams": 4}
@@ -325,6 +330,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.smx_check_social_history_dims.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxSocialHistory), C.POINTER(SmxSocialDims),
                                                   C.c_char_p, C.c_uint64]
     lib.smx_check_social_history_dims.restype = C.c_int
+    lib.smx_set_agent_dims.argtypes = [h, C.POINTER(SmxAgentDims)]
+    lib.smx_set_agent_dims.restype = C.c_int
+    lib.smx_check_agent_dims.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxAgentDims), C.c_char_p, C.c_uint64]
+    lib.smx_check_agent_dims.restype = C.c_int
     lib.smx_set_history_agents.argtypes = [h, C.POINTER(SmxHistoryAgents)]
     lib.smx_set_history_agents.restype = C.c_int
     lib.smx_check_history_agents.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxSocialHistory), C.POINTER(SmxHistoryAgents),

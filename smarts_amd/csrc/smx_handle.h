@@ -11,10 +11,12 @@
 //     moved into the handle and are the pointers the kernels get (map, knots, ctrl, missions, history, dims) set.  After
 //     a failed call every such pointer is null or points into an allocation the handle owns.
 //   The drop rule, once.  What a new binding drops is written in the unbind_* functions below and nowhere else:
-//       a new map       drops missions (-> goals) and the history (-> dims, history agents -> handover);
+//       a new map       drops missions (-> goals), the history (-> dims, history agents -> handover) and the agents' dimensions;
 //                       keeps vias, lidar rays, the image buffer and the frame stacks; re-checks the guard margin
 //       new missions    drop the goals and invalidate the knot keys
-//       a new history   (bind or unbind) drops dims, history agents and handover, and the carried alive list
+//       a new history   (bind or unbind) drops dims, history agents and handover, and the carried alive list; it keeps
+//                       the agents' dimensions (smx_set_agent_dims: they name no vehicle of the history), whose triples
+//                       move into a fresh triple block
 //       history agents  (bind or unbind) drop the handover table, the bubbles and the action / status rows
 #pragma once
 #include <hip/hip_runtime.h>
@@ -133,6 +135,9 @@ struct KernelSide {
   int side_prio;             // SMX_SIDE_PRIO
   // k_knot_table over h->map (the map just loaded) into `table`, counting into h->knot_stats, then a synchronisation
   int (*build_knot_table)(smx_handle_s* h, KnotRow* table);
+  // the agents' triples of triple block `from` into block `to` (both [num_envs * num_vehicles][3]), then a synchronisation:
+  // smx_set_agent_dims' triples outlive the block they were written into (build_dims_blob)
+  int (*copy_agent_dims)(smx_handle_s* h, const double* from, double* to);
 };
 
 // (created by `new smx_handle_s()`: every member without an initialiser starts as zero)
@@ -210,8 +215,11 @@ struct smx_handle_s {
   const uint8_t* ogm_rows;
   bool ogm_known;
   bool ogm_delta = true;  // smx_set_ogm_delta
-  DeviceBlob dims_blob;  // smx_set_social_history_dims: device copy of the table | the triple per vehicle (null: none bound)
-  HistoryDimsDev dims;   // ... and what the kernels get (table null: none bound)
+  // smx_set_social_history_dims / smx_set_agent_dims.  dims_blob: device copy of the social table (none: zero rows) | the
+  // triple per vehicle, which exists while either binding holds; agent_dims_blob: device copy of the agents' table.
+  DeviceBlob dims_blob;
+  DeviceBlob agent_dims_blob;
+  HistoryDimsDev dims;   // ... and what the kernels get (table / agent null: that one not bound; slot null: neither)
   struct StackBinding {  // smx_bind_frame_stack: one caller-owned stack per (source, layout)
     int32_t source, layout;
     uint8_t* dst;
@@ -314,9 +322,18 @@ static void unbind_history_agents(smx_handle h) {  // (every buffer is the calle
   h->ha_action = nullptr;
   h->ha_status = nullptr;
 }
+// (the social table and the triple block in its blob.  While the agents' dimensions stay bound the caller puts a block
+// back at once — install_dims, from a blob it built beforehand: build_dims_blob)
 static void unbind_dims(smx_handle h) {
   h->dims_blob.reset();
-  h->dims = HistoryDimsDev{};
+  h->dims.table = nullptr;
+  h->dims.slot = nullptr;
+  h->dims.n_ids = 0;
+}
+static void unbind_agent_dims(smx_handle h) {  // (the caller drops the triple block too when no social table is bound)
+  h->agent_dims_blob.reset();
+  h->dims.agent = nullptr;
+  h->dims.agent_rows = 0;
 }
 static void unbind_history(smx_handle h) {
   h->history_blob.reset();
@@ -399,6 +416,7 @@ static int load_map_impl(smx_handle h, const smx_map_tables* t) {
   h->host_lane_out_idx.assign(t->lane_out_idx, t->lane_out_idx + t->lane_out_off[nl]);
   unbind_missions(h);  // missions name roads of the map they were set for: a new map starts without any
   unbind_history(h);   // a bound traffic history was checked against the old map's grids: a new map starts without one
+  unbind_agent_dims(h);  // (the triple block went with the history's dimensions) a new map starts with sedans
   // the tick's alive list (large batches) + its counters, the env groups with new vehicles (alive_layout)
   if (!h->alive_blob) SMX_HIP(alloc_filled(h->alive_blob, alive_layout(h->cfg).size * sizeof(int32_t), 0));
   if (!h->slow_blob) SMX_HIP(alloc_filled(h->slow_blob, SlowLists::size(total) * sizeof(int32_t), 0));
@@ -600,6 +618,39 @@ static int set_guard_impl(smx_handle h, uint8_t* guard_dev, uint64_t count, doub
   return SMX_OK;
 }
 
+// The dims blob afresh, filled and not yet committed: `social`'s table (null: zero rows) | a triple per vehicle of the
+// batch — the sedan's until a replayed slot's pose or an agent's spawn pose is written, but for the agents' triples of the
+// block in place, which are carried over while their table is bound (an agent keeps its size until it is respawned).
+static int build_dims_blob(smx_handle h, const smx_social_dims* social, DeviceBlob& out) {
+  const size_t table_words = social ? (size_t)social->n_ids * 3 : 0;
+  const size_t total = (size_t)h->cfg.num_envs * (size_t)h->cfg.num_vehicles;
+  std::vector<double> host(table_words + total * 3);
+  if (social) std::copy(social->dims_host, social->dims_host + table_words, host.begin());
+  double* slot = host.data() + table_words;
+  for (size_t g = 0; g < total; ++g) {
+    slot[g * 3 + 0] = SMX_CHASSIS_LENGTH;
+    slot[g * 3 + 1] = SMX_CHASSIS_WIDTH;
+    slot[g * 3 + 2] = SMX_CHASSIS_HEIGHT;
+  }
+  DeviceBlob blob;
+  SMX_HIP(blob.alloc(host.size() * sizeof(double)));
+  SMX_HIP(hipMemcpy(blob.p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (h->dims.agent != nullptr && h->dims.slot != nullptr) {
+    const int rc = h->kernels.copy_agent_dims(h, h->dims.slot, blob.get<double>() + table_words);
+    if (rc != SMX_OK) return rc;
+  }
+  out = std::move(blob);
+  return SMX_OK;
+}
+// ... committed (after unbind_dims): the blob and the pointers into it
+static void install_dims(smx_handle h, DeviceBlob&& blob, const smx_social_dims* social) {
+  const size_t table_words = social ? (size_t)social->n_ids * 3 : 0;
+  h->dims_blob = std::move(blob);
+  h->dims.table = social ? h->dims_blob.get<double>() : nullptr;
+  h->dims.slot = h->dims_blob.get<double>() + table_words;
+  h->dims.n_ids = social ? social->n_ids : 0;
+}
+
 static int set_social_history_impl(smx_handle h, const smx_social_history* hist) {
   if (!h) return SMX_ERR_INVALID;
   if (hist) {
@@ -610,7 +661,13 @@ static int set_social_history_impl(smx_handle h, const smx_social_history* hist)
   }
   SMX_HIP(hipSetDevice(h->device));
   SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
+  DeviceBlob kept;  // the agents' dimensions outlive the history: their triples, in a block without a social table
+  if (h->dims.agent != nullptr) {
+    const int rc = build_dims_blob(h, nullptr, kept);
+    if (rc != SMX_OK) return rc;
+  }
   unbind_history(h);
+  if (kept) install_dims(h, std::move(kept), nullptr);
   // the alive list k_tail built for the next tick was built under the other rule (smx_plan.h: tail_builds_list)
   h->list_ready = false;
   if (!hist) return SMX_OK;
@@ -646,26 +703,45 @@ static int set_social_history_dims_impl(smx_handle h, const smx_social_dims* dim
   }
   SMX_HIP(hipSetDevice(h->device));
   SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
-  unbind_dims(h);
-  if (!dims) return SMX_OK;
-  // table | a triple per vehicle of the batch, the sedan's until a replayed slot's pose is written (agents: for good)
-  const size_t table_words = (size_t)dims->n_ids * 3, total = (size_t)h->cfg.num_envs * (size_t)h->cfg.num_vehicles;
-  std::vector<double> host(table_words + total * 3);
-  std::copy(dims->dims_host, dims->dims_host + table_words, host.begin());
-  for (size_t g = 0; g < total; ++g) {
-    host[table_words + g * 3 + 0] = SMX_CHASSIS_LENGTH;
-    host[table_words + g * 3 + 1] = SMX_CHASSIS_WIDTH;
-    host[table_words + g * 3 + 2] = SMX_CHASSIS_HEIGHT;
+  if (!dims && h->dims.agent == nullptr) {
+    unbind_dims(h);
+    return SMX_OK;
   }
-  DeviceBlob blob;
-  SMX_HIP(blob.alloc(host.size() * sizeof(double)));
-  SMX_HIP(hipMemcpy(blob.p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice));
-  HistoryDimsDev d;
-  d.table = blob.get<double>();
-  d.slot = blob.get<double>() + table_words;
-  d.n_ids = dims->n_ids;
-  h->dims_blob = std::move(blob);
-  h->dims = d;
+  DeviceBlob blob;  // (with the agents' dimensions bound an unbind leaves a block without a social table)
+  const int rc = build_dims_blob(h, dims, blob);
+  if (rc != SMX_OK) return rc;
+  unbind_dims(h);
+  install_dims(h, std::move(blob), dims);
+  return SMX_OK;
+}
+
+static int set_agent_dims_impl(smx_handle h, const smx_agent_dims* ad) {
+  if (!h) return SMX_ERR_INVALID;
+  if (ad) {
+    std::string msg;
+    const int rc = check_agent_dims_impl(h->cfg, *ad, msg);
+    if (rc != SMX_OK) return fail(h, rc, msg);
+  }
+  SMX_HIP(hipSetDevice(h->device));
+  SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
+  if (!ad) {  // every agent is a sedan again from its next (re)spawn: at once where no block is left to read
+    unbind_agent_dims(h);
+    if (h->dims.table == nullptr) unbind_dims(h);
+    return SMX_OK;
+  }
+  const size_t words = (size_t)ad->rows * (size_t)h->cfg.num_envs * (size_t)(h->cfg.num_vehicles - h->cfg.num_social) * 3;
+  DeviceBlob table, block;
+  SMX_HIP(table.alloc(words * sizeof(double)));
+  SMX_HIP(hipMemcpy(table.p, ad->dims_host, words * sizeof(double), hipMemcpyHostToDevice));
+  if (h->dims.slot == nullptr) {  // (a block in place stays: its agents keep their triples until they are respawned)
+    const int rc = build_dims_blob(h, nullptr, block);
+    if (rc != SMX_OK) return rc;
+  }
+  unbind_agent_dims(h);
+  h->agent_dims_blob = std::move(table);
+  h->dims.agent = h->agent_dims_blob.get<double>();
+  h->dims.agent_rows = ad->rows;
+  if (block) install_dims(h, std::move(block), nullptr);
   return SMX_OK;
 }
 

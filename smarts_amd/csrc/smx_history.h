@@ -98,11 +98,15 @@ SMX_HISTORY_FN int history_find(const HistoryDev& h, int64_t frame, int32_t id) 
 // ---- per-vehicle dimensions (smx_set_social_history_dims) ----
 // table: the handle's device copy of smx_social_dims (null: none bound, every vehicle has the sedan's box); slot: the
 // handle's triple per (env, vehicle), which the writers of a replayed slot's pose write beside it and every consumer
-// reads (agents' triples are the sedan's from the bind on and never written).
+// reads.  agent: the handle's device copy of smx_agent_dims (smx_set_agent_dims; null: none bound), which respawn_vehicle
+// writes an agent's triple from (an all-NaN triple: the sedan's).  slot exists when either binding holds — "sized" is
+// `slot != null` —; a vehicle whose binding is absent keeps the sedan's triple there.
 struct HistoryDimsDev {
   const double* table;  // [n_ids][3] length, width, height
   double* slot;         // [num_envs * num_vehicles][3]
   int32_t n_ids;
+  int32_t agent_rows;   // an episode uses row (episode mod agent_rows), as the spawn tables do
+  const double* agent;  // [agent_rows][num_envs][num_agents][3]
 };
 
 // The triple of the vehicle in `slot` of `frame` (only called when history_present said yes).  The bind-time check

@@ -417,6 +417,39 @@ inline int check_social_history_dims_impl(const smx_config& c, const smx_social_
   return check_social_dims_impl(d, social_history_max_id(hs), err);
 }
 
+// ---- Per-agent dimensions (smx_set_agent_dims / smx_check_agent_dims) ----
+// The kinematic spaces only; every triple whole: three values within the caps (include/smx.h has the derivation), or
+// three NaNs for the sedan's box.  The length's cap is the radius at which every vehicle's road-facts search runs
+// (SMX_POSE_SCAN_RADIUS, smx_tick.h, which asserts the two equal): an observer asks for its neighbours' lanes within its
+// own length (sensors.py:245) and is answered from the NEIGHBOUR's search, which finds no lane at that radius or beyond.
+#define SMX_AGENT_DIMS_MAX_LENGTH 10.0
+inline int check_agent_dims_impl(const smx_config& c, const smx_agent_dims& d, std::string& err) {
+  if (c.action_space != SMX_ACTION_SPACE_TARGET_POSE && c.action_space != SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME &&
+      c.action_space != SMX_ACTION_SPACE_IMITATION)
+    return refuse(err, "agent dimensions: only the kinematic action spaces (TargetPose, TrajectoryWithTime, Imitation) take them; "
+                       "a dynamic chassis is the sedan its model constants belong to");
+  if (c.num_envs <= 0 || c.num_vehicles <= 0 || c.num_social < 0 || c.num_social >= c.num_vehicles)
+    return refuse(err, "agent dimensions: the configuration has no agents");
+  if (!d.dims_host) return refuse(err, "agent dimensions: null table (dims_host)");
+  if (d.rows < 1) return refuse(err, "agent dimensions: rows must be >= 1");
+  const uint64_t triples = (uint64_t)d.rows * (uint64_t)c.num_envs * (uint64_t)(c.num_vehicles - c.num_social);
+  for (uint64_t i = 0; i < triples; ++i) {
+    const double* r = d.dims_host + i * 3;
+    const int nans = (r[0] != r[0]) + (r[1] != r[1]) + (r[2] != r[2]);
+    if (nans == 3) continue;
+    if (nans != 0)
+      return refuse(err, "agent dimensions: triple " + std::to_string(i) + " is partly NaN (three NaNs = the sedan's box, or three values)");
+    for (int q = 0; q < 3; ++q) {
+      const double cap = q == 0 ? SMX_AGENT_DIMS_MAX_LENGTH : (q == 1 ? SMX_DIMS_MAX_PLANAR : SMX_DIMS_MAX_HEIGHT);
+      if (!(std::isfinite(r[q]) && r[q] > 0.0 && r[q] <= cap))
+        return refuse(err, "agent dimensions: triple " + std::to_string(i) + (q == 0 ? ", length " : (q == 1 ? ", width " : ", height ")) +
+                               std::to_string(r[q]) + " must be finite, > 0 and <= " + std::to_string((int)cap) + " m" +
+                               (q == 0 ? " (the radius of the neighbours' lane search, which answers the lookup within the observer's length)" : ""));
+    }
+  }
+  return SMX_OK;
+}
+
 // ---- History agents (smx_set_history_agents / smx_check_history_agents) ----
 // The kernels index vehicle_dev by (episode mod rows, env, agent) and the two optional rows by vehicle: the counts are
 // checked against those shapes here; the ids the table holds are only ever compared.  `rows`: the bound history's.

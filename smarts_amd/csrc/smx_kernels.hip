@@ -1250,7 +1250,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_social(const KernelArgs a) {
 //          (sumo_road_network.py:815-882), used by the waypoints role now and by k_control next tick
 // =================================================================================
 // one half of k_scan for one vehicle team (see k_scan)
-template <int TEAM, bool ROUTED>
+template <int TEAM, bool ROUTED, int SIZED = -1>
 __device__ __forceinline__ void scan_role(const KernelArgs& a, const MapDev& m, const smx_config& c, size_t gid,
                                           size_t total, int rank, int flags, int role) {
   SMX_TSTAMP(ts0);
@@ -1264,14 +1264,17 @@ __device__ __forceinline__ void scan_role(const KernelArgs& a, const MapDev& m, 
     const double cys[4] = {0.5, 0.5, -0.5, -0.5};
     double cx[4], cy[4];
     const double ch = cos(s.heading), sh = sin(s.heading);
+    const bool social = (flags & SMX_F_SOCIAL) != 0;  // only its nearest lane is ever asked for (neighbour rows)
+    // the observer's own box (sensors.py:506): the sedan's, or with dimensions bound an agent's triple and its reaches
+    ObserverBox ob = {SMX_CHASSIS_LENGTH, SMX_CHASSIS_WIDTH, 2.0, SMX_POSE_SCAN_RADIUS};
+    if (own_box_sized<SIZED>(a) && !social) ob = observer_box(a, gid, a.dagm_reach + 0.1);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      double qx = s.x + cxs[q] * SMX_CHASSIS_WIDTH;
-      double qy = s.y + cys[q] * SMX_CHASSIS_LENGTH;
+      double qx = s.x + cxs[q] * ob.width;
+      double qy = s.y + cys[q] * ob.length;
       cx[q] = s.x + ch * (qx - s.x) + sh * (qy - s.y);
       cy[q] = s.y + -sh * (qx - s.x) + ch * (qy - s.y);
     }
-    const bool social = (flags & SMX_F_SOCIAL) != 0;  // only its nearest lane is ever asked for (neighbour rows)
     FactsCarry fc;
     fc.valid = false;
     if (a.facts_carry != nullptr && !(flags & SMX_F_FIRST)) {
@@ -1280,7 +1283,7 @@ __device__ __forceinline__ void scan_role(const KernelArgs& a, const MapDev& m, 
       fc.prev_dist = a.st.facts_f64[(size_t)SMX_FF_LANE_DIST * total + gid];
       fc.valid = fi[(size_t)SMX_FI_LANE * total + gid] >= 0;
     }
-    RoadFacts h = team_road_facts_seeded<TEAM>(m, s.x, s.y, SMX_POSE_SCAN_RADIUS, social ? 0 : 4, cx, cy, fc, a.dagm_reach + 0.1);
+    RoadFacts h = team_road_facts_seeded<TEAM>(m, s.x, s.y, ob.scan_radius, social ? 0 : 4, cx, cy, fc, a.dagm_reach + 0.1, ob.corner_reach);
     if (a.facts_carry != nullptr && rank == 0) {
       a.facts_carry[gid] = s.x;
       a.facts_carry[total + gid] = s.y;
@@ -1350,7 +1353,9 @@ __device__ __forceinline__ void scan_role(const KernelArgs& a, const MapDev& m, 
   // 349-351); TripMeterSensor.__init__ (sensors.py:885-898) asks the same on a new vehicle
   int obs_start = -1, trip_start = -1;
   if (!wp_on || (flags & SMX_F_FIRST)) {
-    const PathSeeds ts = team_compute_path_seeds<TEAM, false>(m, s.x, s.y, s.heading, SMX_CHASSIS_LENGTH, false, t, sc, a.missions, 0, &guess);
+    // (within_radius = the vehicle's length, sensors.py:895: with dimensions bound the agent's own)
+    const double own_length = own_box_sized<SIZED>(a) ? vehicle_box(a, gid, true).length : SMX_CHASSIS_LENGTH;
+    const PathSeeds ts = team_compute_path_seeds<TEAM, false>(m, s.x, s.y, s.heading, own_length, false, t, sc, a.missions, 0, &guess);
     trip_start = (ts.road >= 0) ? ts.start[0] : -1;
     obs_start = trip_start;
   }
@@ -1404,7 +1409,8 @@ __global__ void __attribute__((amdgpu_waves_per_eu(SPLIT ? 2 : SMX_SCAN_WAVES, 8
 // it needs (the facts half alone fits more wavefronts per SIMD than the pair).
 // (TEAM: four lanes a vehicle when the batch fills the chip, eight up to SMX_SCAN_WIDE_MAX_VEHICLES on maps whose lanes
 // split: a quarter-full chip is bound by one team's latency, and the wider team's is the shorter)
-template <int ROLE, bool ROUTED = false, int TEAM = SMX_TEAM_LARGE>
+// (SIZED: per-agent dimensions, TickPlan::sized — the agent's own box in the corners, the reaches and the trip meter's lookup)
+template <int ROLE, bool ROUTED = false, int TEAM = SMX_TEAM_LARGE, bool SIZED = false>
 __global__ void __attribute__((amdgpu_waves_per_eu(ROLE == 0 ? 4 : 3, 8))) __launch_bounds__(SMX_BLOCK) k_scan_half(const KernelArgs a) {
   const smx_config& c = a.cfg;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
@@ -1413,7 +1419,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(ROLE == 0 ? 4 : 3, 8))) __lau
   const int flags = a.st.flags[gid];
   if (!(flags & SMX_F_ALIVE)) return;
   if (a.first_only && !(flags & SMX_F_FIRST)) return;
-  scan_role<TEAM, ROUTED>(a, a.map, c, gid, total, team_rank<TEAM>(), flags, ROLE);
+  scan_role<TEAM, ROUTED, SIZED ? 1 : 0>(a, a.map, c, gid, total, team_rank<TEAM>(), flags, ROLE);
 }
 
 // k_scan_fast (large batches): one half of the scan with ONE lane per vehicle (smx_scan.h facts_one_lane /
@@ -1467,14 +1473,17 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_scan_fast(const KernelArgs a) {
       const double cys[4] = {0.5, 0.5, -0.5, -0.5};
       double cx[4], cy[4];
       const double ch = cos(sh_), sh = sin(sh_);
+      const bool social = (flags & SMX_F_SOCIAL) != 0;
+      // (the observer's own box: as in scan_role)
+      ObserverBox ob = {SMX_CHASSIS_LENGTH, SMX_CHASSIS_WIDTH, 2.0, SMX_POSE_SCAN_RADIUS};
+      if (dims_sized(a) && !social) ob = observer_box(a, gid, a.dagm_reach + 0.1);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        double qx = sx_ + cxs[q] * SMX_CHASSIS_WIDTH;
-        double qy = sy_ + cys[q] * SMX_CHASSIS_LENGTH;
+        double qx = sx_ + cxs[q] * ob.width;
+        double qy = sy_ + cys[q] * ob.length;
         cx[q] = sx_ + ch * (qx - sx_) + sh * (qy - sy_);
         cy[q] = sy_ + -sh * (qx - sx_) + ch * (qy - sy_);
       }
-      const bool social = (flags & SMX_F_SOCIAL) != 0;
       fc.valid = seeded && prev_lane >= 0;
       RoadFacts h;
       double lane_heading = 0.0;
@@ -1486,8 +1495,8 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_scan_fast(const KernelArgs a) {
         h.corner_mask = 15;
         served = true;
       } else {
-        served = facts_one_lane(m, sx_, sy_, SMX_POSE_SCAN_RADIUS, social ? 0 : 4, cx, cy, fc, a.dagm_reach + 0.1, cand, SMX_BLOCK,
-                                !social, h, lane_heading);
+        served = facts_one_lane(m, sx_, sy_, ob.scan_radius, social ? 0 : 4, cx, cy, fc, a.dagm_reach + 0.1, cand, SMX_BLOCK,
+                                !social, h, lane_heading, ob.corner_reach);
       }
       if (served) {
         a.facts_carry[gid] = sx_;
@@ -1536,7 +1545,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_scan_fast(const KernelArgs a) {
 // k_scan_half over a list whose length is only known on the device (the slow list): a fixed grid, teams striding it
 // (TEAM: four lanes a vehicle where the lists are long — maps whose lanes split —, eight where they hold a few
 // hundred vehicles and the kernel is one team's latency at the end of the slow chain: 70 against 55 us)
-template <int ROLE, bool ROUTED = false, int TEAM = SMX_TEAM_LARGE>
+template <int ROLE, bool ROUTED = false, int TEAM = SMX_TEAM_LARGE, bool SIZED = false>
 __global__ void __attribute__((amdgpu_waves_per_eu(ROLE == 0 ? 4 : 3, 8))) __launch_bounds__(SMX_BLOCK) k_scan_listed(const KernelArgs a) {
   const smx_config& c = a.cfg;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
@@ -1545,7 +1554,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(ROLE == 0 ? 4 : 3, 8))) __lau
   for (int i = (int)blockIdx.x * VPB + (int)threadIdx.x / TEAM; i < count; i += (int)gridDim.x * VPB) {
     const size_t gid = (size_t)a.slow_list[i];
     const int flags = a.st.flags[gid];
-    scan_role<TEAM, ROUTED>(a, a.map, c, gid, total, team_rank<TEAM>(), flags, ROLE);
+    scan_role<TEAM, ROUTED, SIZED ? 1 : 0>(a, a.map, c, gid, total, team_rank<TEAM>(), flags, ROLE);
   }
 }
 
@@ -2974,7 +2983,11 @@ __device__ inline void lap_goal_gate(const KernelArgs& a, size_t gid, size_t tot
   }
 }
 
-__device__ __forceinline__ void observe_role(const KernelArgs& a, const int block) {
+// (own_box: a triple block is bound, TickPlan::sized — the caller's literal; the copy without it keeps the observer's box
+// a constant.  A function argument and not a template argument: as a template the role's kernels without dimensions
+// took 27 registers more and spilled, profiles/r24_agent_dims_resources.txt)
+__device__ __forceinline__ void observe_role(const KernelArgs& a, const int block, const bool own_box) {
+  const bool OWN_BOX = own_box;
   __shared__ SharedPose pose[SMX_BLOCK];
   __shared__ ObsStage stage;
   __shared__ unsigned long long zero_mask;  // vehicles of the workgroup whose rows are to read as an absent agent's
@@ -3024,7 +3037,8 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
     p.lane_dist = my_lane_dist;
     p.alive = (valid && alive) ? 1 : 0;
     // what an observer reports as this vehicle's lane: nearest_lane(nv.pose.point, radius=vehicle.length)
-    // (sensors.py:244-246; every vehicle on this path has the sedan's length)
+    // (sensors.py:244-246: the OBSERVER's length — the sedan's here; with dimensions bound the readers of nl / nlidx
+    // take the lane and its distance and ask with their own length instead)
     const int nl = (my_lane >= 0 && my_lane_dist < SMX_CHASSIS_LENGTH) ? my_lane : -1;
     p.nl = (short)nl;
     p.nlidx = (short)(nl >= 0 ? m.lane_index[nl] : -1);
@@ -3087,12 +3101,18 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
         }
       }
       const double my_h = wrap_heading(s.heading);
-      const bool sized = __builtin_expect(a.dims.table != nullptr, 0);
+      const bool sized = dims_sized(a);
+      double my_len = SMX_CHASSIS_LENGTH, my_wid = SMX_CHASSIS_WIDTH;
       if (sized && want_col) {
-        // Dimensions bound (smx_set_social_history_dims): the candidates again, in a pass of its own so that the loop
-        // above stays what it is without them.  The reach is the sedan's half diagonal (the observer is an agent) plus
-        // the mate's plus the leeway — boxes_within's own broad phase; between two agents the one full diagonal.
-        const double my_half_diag = 0.5 * sqrt(SMX_CHASSIS_LENGTH * SMX_CHASSIS_LENGTH + SMX_CHASSIS_WIDTH * SMX_CHASSIS_WIDTH);
+        // Dimensions bound (smx_set_social_history_dims, smx_set_agent_dims): the candidates again, in a pass of its own
+        // so that the loop above stays what it is without them.  The reach is the observer's half diagonal plus the
+        // mate's plus the leeway — boxes_within's own broad phase; between two sedans the one full diagonal.
+        double my_half_diag = 0.5 * sqrt(SMX_CHASSIS_LENGTH * SMX_CHASSIS_LENGTH + SMX_CHASSIS_WIDTH * SMX_CHASSIS_WIDTH);
+        if (OWN_BOX) {
+          const VehBox my = vehicle_box(a, gid, true);
+          my_len = my.length, my_wid = my.width;
+          my_half_diag = 0.5 * sqrt(my_len * my_len + my_wid * my_wid);
+        }
         cand = 0ull;
         for (int j = 0; j < n_veh; ++j) {
           if (j == slot) continue;
@@ -3110,9 +3130,9 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
         const int j = __ffsll((long long)cand) - 1;
         cand &= cand - 1ull;
         const SharedPose& q = env_pose[j];
-        const VehBox mb = vehicle_box(a, gid - slot + j, sized);  // (the observer is an agent: a sedan)
-        if (boxes_within(px, py, my_h, q.x, q.y, q.heading, SMX_CHASSIS_LENGTH, SMX_CHASSIS_WIDTH, mb.length, mb.width,
-                         SMX_COLLISION_LEEWAY))
+        const VehBox mb = vehicle_box(a, gid - slot + j, sized);
+        if (boxes_within(px, py, my_h, q.x, q.y, q.heading, OWN_BOX ? my_len : SMX_CHASSIS_LENGTH, OWN_BOX ? my_wid : SMX_CHASSIS_WIDTH, mb.length,
+                         mb.width, SMX_COLLISION_LEEWAY))
           collidee_mask |= 1ull << j;
       }
       collided = collidee_mask != 0ull;
@@ -3159,6 +3179,12 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
     ef[SMX_EGO_BOX + 0] = (float)SMX_CHASSIS_LENGTH;
     ef[SMX_EGO_BOX + 1] = (float)SMX_CHASSIS_WIDTH;
     ef[SMX_EGO_BOX + 2] = (float)SMX_CHASSIS_HEIGHT;
+    if (OWN_BOX) {  // (sensors.py:317: the agent's own box)
+      const VehBox my = vehicle_box(a, gid, true);
+      ef[SMX_EGO_BOX + 0] = (float)my.length;
+      ef[SMX_EGO_BOX + 1] = (float)my.width;
+      ef[SMX_EGO_BOX + 2] = (float)my.height;
+    }
     stage.ego_lane[local][0] = (short)ego_lane;
     stage.ego_lane[local][1] = (short)(ego_lane >= 0 ? m.lane_index[ego_lane] : -1);
 
@@ -3220,7 +3246,7 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
           o.nb_heading[w] = (float)q.heading;
           o.nb_speed[w] = (float)q.speed;
           // nearest_lane(nv.pose.point, radius=vehicle.length) (sensors.py:244-246: the EGO's length)
-          int nl = (q.lane >= 0 && q.lane_dist < SMX_CHASSIS_LENGTH) ? q.lane : -1;
+          int nl = (q.lane >= 0 && q.lane_dist < vehicle_box(a, gid, OWN_BOX).length) ? q.lane : -1;
           o.nb_lane_id[w] = (int16_t)nl;
           o.nb_lane_index[w] = (int8_t)(nl >= 0 ? m.lane_index[nl] : -1);
           o.nb_slot[w] = (int8_t)j;
@@ -3326,7 +3352,7 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
     // (a lap goal's distance condition waits for this tick's trip meter, which the waypoints role is still writing:
     // the commit role applies it, lap_goal_gate)
     if (__builtin_expect(a.missions.goal_kind != nullptr, 0) && a.missions.goal_kind[slot].kind == SMX_GOAL_TRAVERSE)
-      reached_goal = drove_off_map(a.missions, m, n_veh, my_lane, my_lane_dist, s.x, s.y, wrap_heading(s.heading));
+      reached_goal = drove_off_map(a.missions, m, n_veh, OWN_BOX ? ego_lane : my_lane, my_lane_dist, s.x, s.y, wrap_heading(s.heading));
     const bool is_off_road = !(my_facts & SMX_FACT_ON_ROAD);           // sensors.py:498-500
     const bool is_on_shoulder = ((my_facts >> SMX_FACT_CORNER_SHIFT) & 15) != 15;  // sensors.py:502-509
     const bool reached_max = c.max_episode_steps > 0 && steps >= c.max_episode_steps;
@@ -3334,6 +3360,10 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
     {
       // sensors.py:527-594
       double radius = sqrt(SMX_CHASSIS_LENGTH * SMX_CHASSIS_LENGTH + SMX_CHASSIS_WIDTH * SMX_CHASSIS_WIDTH) * 0.5 + 5.0;
+      if (OWN_BOX) {  // (sensors.py:548: the agent's own half diagonal)
+        const VehBox my = vehicle_box(a, gid, true);
+        radius = sqrt(my.length * my.length + my.width * my.width) * 0.5 + 5.0;
+      }
       int nl = (my_lane >= 0 && my_lane_dist < radius) ? my_lane : -1;
       if (nl < 0) {
         is_off_route = true;
@@ -3443,7 +3473,7 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
         const SharedPose& P = pose[mate];
         o.nb_pos[g0 * K * 3 + e] = held ? (q == 0 ? P.x : (q == 1 ? P.y : SMX_BASE_HEIGHT)) : 0.0;
         float box = held ? (float)(q == 0 ? SMX_CHASSIS_LENGTH : (q == 1 ? SMX_CHASSIS_WIDTH : SMX_CHASSIS_HEIGHT)) : 0.0f;
-        if (__builtin_expect(a.dims.table != nullptr, 0) && held) box = (float)a.dims.slot[(g0 + mate) * 3 + q];
+        if (dims_sized(a) && held) box = (float)a.dims.slot[(g0 + mate) * 3 + q];
         o.nb_box[g0 * K * 3 + e] = box;
       }
       for (int e = local; e < wg_veh * K; e += nth) {         // the scalar neighbour rows
@@ -3455,8 +3485,13 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
         const size_t w = g0 * K + e;
         o.nb_heading[w] = held ? (float)P.heading : 0.0f;
         o.nb_speed[w] = held ? (float)P.speed : 0.0f;
-        o.nb_lane_id[w] = (int16_t)(held ? P.nl : -1);
-        o.nb_lane_index[w] = (int8_t)(held ? P.nlidx : 0);
+        int nl = held ? P.nl : -1, nlidx = held ? P.nlidx : 0;
+        if (OWN_BOX && held) {  // nearest_lane(nv.pose.point, radius = the observer's own length)
+          nl = (P.lane >= 0 && P.lane_dist < a.dims.slot[(g0 + v) * 3]) ? P.lane : -1;
+          nlidx = nl >= 0 ? m.lane_index[nl] : -1;
+        }
+        o.nb_lane_id[w] = (int16_t)nl;
+        o.nb_lane_index[w] = (int8_t)nlidx;
         o.nb_slot[w] = (int8_t)(held ? j : -1);
       }
     }
@@ -4053,7 +4088,7 @@ struct LidarPose {
 template <int SIZED>
 __device__ __forceinline__ void lidar_role(const KernelArgs& a, const int block) {
   __shared__ LidarPose mates[SMX_BLOCK];
-  const bool sized = SIZED < 0 ? __builtin_expect(a.dims.table != nullptr, 0) : SIZED != 0;
+  const bool sized = SIZED < 0 ? dims_sized(a) : SIZED != 0;
   const smx_config& c = a.cfg;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
   const size_t gid = (size_t)block;
@@ -4180,18 +4215,22 @@ __device__ __forceinline__ void lidar_role(const KernelArgs& a, const int block)
 // same pose / flags / facts and write disjoint outputs, so they overlap in time; the flags word
 // itself only changes in the commit role.
 // =================================================================================
-__global__ void __launch_bounds__(SMX_BLOCK) k_sensors(const KernelArgs a) {
+// (SIZED: a triple block is bound, TickPlan::sized — the observe role with the agent's own box)
+template <int SIZED>
+__device__ __forceinline__ void sensors_roles(const KernelArgs& a) {
   const int b = (int)blockIdx.x;
   if (b < a.wp_blocks) {
     waypoints_role(a, b);
   } else if (b < a.wp_blocks + a.obs_blocks) {
-    observe_role(a, b - a.wp_blocks);
+    observe_role(a, b - a.wp_blocks, SIZED != 0);
   } else if (b < a.wp_blocks + a.obs_blocks + a.lidar_blocks) {
     lidar_role<-1>(a, b - a.wp_blocks - a.obs_blocks);
   } else {
     ogm_role(a, b - a.wp_blocks - a.obs_blocks - a.lidar_blocks);
   }
 }
+__global__ void __launch_bounds__(SMX_BLOCK) k_sensors(const KernelArgs a) { sensors_roles<0>(a); }
+__global__ void __launch_bounds__(SMX_BLOCK) k_sensors_sized(const KernelArgs a) { sensors_roles<1>(a); }
 
 // =================================================================================
 // k_first: the reset pass (first observations of re-created vehicles) as ONE launch.  A workgroup
@@ -4205,6 +4244,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_sensors(const KernelArgs a) {
 // vehicle, fit the first 256 threads, whose knot scratch is all the LDS the workgroup may have)
 #define SMX_FIRST_BLOCK 512
 #define SMX_FIRST_WP_THREADS 256
+template <int SIZED>
 __device__ __forceinline__ void first_role(const KernelArgs& a, const int block) {
   __shared__ int knot_scratch[SMX_MAX_KNOTS * SMX_FIRST_WP_THREADS];
   const smx_config& c = a.cfg;
@@ -4250,7 +4290,7 @@ __device__ __forceinline__ void first_role(const KernelArgs& a, const int block)
           const size_t gid = g0 + (both ? (u >> 1) : u);
           const int half = both ? (int)(u & 1) : (turn == 0 ? 1 : 0);
           const int flags = a.st.flags[gid];
-          if ((flags & SMX_F_ALIVE) && (flags & SMX_F_FIRST)) scan_role<SMX_TEAM, true>(a, m, c, gid, total, team_rank<SMX_TEAM>(), flags, half);
+          if ((flags & SMX_F_ALIVE) && (flags & SMX_F_FIRST)) scan_role<SMX_TEAM, true, SIZED>(a, m, c, gid, total, team_rank<SMX_TEAM>(), flags, half);
         }
       }
     } else if (turn == 1 && threadIdx.x < SMX_FIRST_WP_THREADS) {  // (whole wavefronts; waypoints_for holds no barrier)
@@ -4265,7 +4305,7 @@ __device__ __forceinline__ void first_role(const KernelArgs& a, const int block)
     SMX_TACC_ALL(turn == 0 ? 57 : 58, tt0, tt1);
   }
   SMX_TSTAMP(tk2);
-  observe_role(a, block);
+  observe_role(a, block, SIZED != 0);
   SMX_TSTAMP(tk3);
   SMX_TACC_ALL(59, tk2, tk3);
   if ((c.sensors & SMX_SENSOR_LIDAR) && a.lidar_blocks != 0)  // (0: the reset pass launched k_lidar for the new vehicles)
@@ -4304,7 +4344,12 @@ __device__ __forceinline__ void first_role(const KernelArgs& a, const int block)
 // its 256: 436 bytes of scratch a lane.)
 __global__ void __launch_bounds__(SMX_FIRST_BLOCK) k_first(const KernelArgs a, const int32_t* groups, const int32_t* n_groups) {
   if ((int)blockIdx.x >= *n_groups) return;
-  first_role(a, groups[blockIdx.x]);
+  first_role<0>(a, groups[blockIdx.x]);
+}
+// (... with a triple block bound, TickPlan::sized: the scan and observe roles with the agent's own box)
+__global__ void __launch_bounds__(SMX_FIRST_BLOCK) k_first_sized(const KernelArgs a, const int32_t* groups, const int32_t* n_groups) {
+  if ((int)blockIdx.x >= *n_groups) return;
+  first_role<1>(a, groups[blockIdx.x]);
 }
 
 // single-role launches: large batches (each role then keeps its own register / LDS footprint and
@@ -5116,7 +5161,14 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_waypoints_walk_listed(const Kerne
 // (capped at 168 registers for a third wavefront per SIMD beside the waypoint kernels it spills 52 of them: 0.796 -> 0.806 ms)
 __global__ void __launch_bounds__(SMX_BLOCK) k_observe(const KernelArgs a) {
   SMX_TSTAMP(span0);
-  observe_role(a, (int)blockIdx.x);
+  observe_role(a, (int)blockIdx.x, false);
+  SMX_TSTAMP(span1);
+  SMX_TSPAN(5, span0, span1);
+}
+// (... with a triple block bound, TickPlan::sized)
+__global__ void __launch_bounds__(SMX_BLOCK) k_observe_sized(const KernelArgs a) {
+  SMX_TSTAMP(span0);
+  observe_role(a, (int)blockIdx.x, true);
   SMX_TSTAMP(span1);
   SMX_TSPAN(5, span0, span1);
 }
@@ -5149,7 +5201,8 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_lidar_first(const KernelArgs a) {
 // spawn poses (AckermannChassis._initialize_speed, chassis.py:668-671); the observation kernels
 // that follow produce their first observations.
 // =================================================================================
-template <bool GUARD = false>
+// (SIZED: a triple block is bound, TickPlan::sized — the agents' triples are written beside their spawn poses)
+template <bool GUARD = false, bool SIZED = false>
 __global__ void __launch_bounds__(SMX_BLOCK) k_reset(const KernelArgs a) {
   const smx_config& c = a.cfg;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
@@ -5168,7 +5221,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_reset(const KernelArgs a) {
     if constexpr (GUARD) a.guard[gid] = 0;  // (an agent absent from the pass)
     return;
   }
-  respawn_vehicle<GUARD>(a, gid, total, a.st.env_episode[env] + 1);  // every reset starts the next spawn row
+  respawn_vehicle<GUARD, SIZED ? 1 : 0>(a, gid, total, a.st.env_episode[env] + 1);  // every reset starts the next spawn row
   // per-env words are written by every thread of the env with the same values (no ordering needed
   // inside this kernel; the env's own threads never read them here)
   (void)slot;
@@ -5246,6 +5299,22 @@ static_assert(SMX_HOST_BLOCK == SMX_BLOCK && SMX_HOST_WP_LANES == SMX_WP_LANES &
               "smx_host.h mirrors these");
 
 // the map's knot table, for load_map_impl (smx_handle.h)
+// The agents' triples of one triple block into another (smx_handle.h build_dims_blob: the block moves when the social
+// table beside it is bound or dropped while smx_set_agent_dims' table stays), then a synchronisation.
+__global__ void __launch_bounds__(SMX_BLOCK) k_copy_agent_dims(const double* from, double* to, int n_veh, int n_agents, size_t total) {
+  const size_t g = (size_t)blockIdx.x * SMX_BLOCK + threadIdx.x;
+  if (g >= total || (int)(g % (size_t)n_veh) >= n_agents) return;
+  for (int q = 0; q < 3; ++q) to[g * 3 + q] = from[g * 3 + q];
+}
+static int copy_agent_dims(smx_handle h, const double* from, double* to) {
+  const size_t total = (size_t)h->cfg.num_envs * (size_t)h->cfg.num_vehicles;
+  hipLaunchKernelGGL(k_copy_agent_dims, dim3((unsigned)((total + SMX_BLOCK - 1) / SMX_BLOCK)), dim3(SMX_BLOCK), 0, 0, from, to,
+                     h->cfg.num_vehicles, h->cfg.num_vehicles - h->cfg.num_social, total);
+  SMX_HIP(hipGetLastError());
+  SMX_HIP(hipDeviceSynchronize());
+  return SMX_OK;
+}
+
 static int build_knot_table(smx_handle h, KnotRow* table) {
   hipLaunchKernelGGL(k_knot_table, dim3(smx_blocks((size_t)h->map.n_lanepoints)), dim3(SMX_BLOCK), 0, 0, h->map, (int)h->cfg.wp_lookahead,
                      table, h->knot_stats.get<int32_t>());
@@ -5255,7 +5324,7 @@ static int build_knot_table(smx_handle h, KnotRow* table) {
 }
 
 extern "C" int smx_create(const smx_config* cfg, int device, smx_handle* out) {
-  const int rc = create_impl(cfg, device, out, KernelSide{SMX_WPE_POOL, SMX_WPE_SPILL_GROUP_BYTES, SMX_SIDE_PRIO, build_knot_table});
+  const int rc = create_impl(cfg, device, out, KernelSide{SMX_WPE_POOL, SMX_WPE_SPILL_GROUP_BYTES, SMX_SIDE_PRIO, build_knot_table, copy_agent_dims});
 #ifdef SMX_DEBUG_TIMING
   if (const char* dbg = getenv("SMX_DEBUG_SKIP"))
     if (rc == SMX_OK) (*out)->debug_skip = atoi(dbg);
@@ -5296,6 +5365,7 @@ static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_sta
   in.frame_stack_bound = !h->stacks.empty();
   in.guard_bound = h->guard_out != nullptr;
   in.dims_bound = h->dims.table != nullptr;
+  in.agent_dims_bound = h->dims.agent != nullptr;
   in.history_bound = h->history.vehicle != nullptr;
   in.follow_entry = follow;
   in.ogm_mask = h->ogm_mask && h->ogm_delta;
@@ -5392,6 +5462,14 @@ extern "C" int smx_check_social_history_dims(const smx_config* cfg, const smx_so
 }
 
 extern "C" int smx_set_social_history_dims(smx_handle h, const smx_social_dims* dims) { return set_social_history_dims_impl(h, dims); }
+
+extern "C" int smx_check_agent_dims(const smx_config* cfg, const smx_agent_dims* dims, char* err, uint64_t err_len) {
+  std::string msg;
+  const int rc = (cfg && dims) ? check_agent_dims_impl(*cfg, *dims, msg) : refuse(msg, "null config / dims");
+  return report(rc, msg, err, err_len);
+}
+
+extern "C" int smx_set_agent_dims(smx_handle h, const smx_agent_dims* dims) { return set_agent_dims_impl(h, dims); }
 
 extern "C" int smx_check_history_agents(const smx_config* cfg, const smx_social_history* hist, const smx_history_agents* ha, char* err,
                                         uint64_t err_len) {
@@ -5619,10 +5697,10 @@ static void launch_grids(smx_handle h, const TickPlan& p, const KernelArgs& k, h
 // walks and rows by the serial emitter
 static void launch_slow_chain(const TickPlan& p, const KernelArgs& ks, hipStream_t s) {
   if (p.chain_fused) {
-    launch(k_scan_listed<1, false, SMX_TEAM>, p.slow_blocks, 0, s, ks);
+    launch(p.sized ? k_scan_listed<1, false, SMX_TEAM, true> : k_scan_listed<1, false, SMX_TEAM>, p.slow_blocks, 0, s, ks);
     launch(k_waypoints_walk_listed, p.slow_blocks, 0, s, ks);
   } else {
-    launch(k_scan_listed<1>, p.slow_blocks, 0, s, ks);
+    launch(p.sized ? k_scan_listed<1, false, SMX_TEAM_LARGE, true> : k_scan_listed<1>, p.slow_blocks, 0, s, ks);
     launch(k_waypoints_listed, p.slow_blocks, 0, s, ks);
     launch(k_wp_walk_listed, p.slow_blocks, 0, s, ks);
   }
@@ -5650,9 +5728,9 @@ static void observation_pass(smx_handle h, const TickPlan& p, const KernelArgs& 
       break;
     }
     case Seeds::ONE_LANE: launch(k_scan_fast<1>, p.seeds_blocks, 0, stream, ks); break;
-    case Seeds::ROUTED: launch(k_scan_half<1, true>, p.seeds_blocks, 0, stream, k); break;
-    case Seeds::WIDE: launch(k_scan_half<1, false, SMX_TEAM>, p.seeds_blocks, 0, stream, k); break;
-    case Seeds::FOUR: launch(k_scan_half<1>, p.seeds_blocks, 0, stream, k); break;
+    case Seeds::ROUTED: launch(p.sized ? k_scan_half<1, true, SMX_TEAM_LARGE, true> : k_scan_half<1, true>, p.seeds_blocks, 0, stream, k); break;
+    case Seeds::WIDE: launch(p.sized ? k_scan_half<1, false, SMX_TEAM, true> : k_scan_half<1, false, SMX_TEAM>, p.seeds_blocks, 0, stream, k); break;
+    case Seeds::FOUR: launch(p.sized ? k_scan_half<1, false, SMX_TEAM_LARGE, true> : k_scan_half<1>, p.seeds_blocks, 0, stream, k); break;
   }
   if (p.chain() == SlowChain::SIDE) {
     // the slow chain runs beside the main chain (k_wp_walk -> k_waypoints_emit pass over its vehicles)
@@ -5673,10 +5751,10 @@ static void observation_pass(smx_handle h, const TickPlan& p, const KernelArgs& 
     case Facts::SCAN: break;
     case Facts::ONE_LANE:
       launch(k_scan_fast<0>, p.facts_blocks, 0, s_obs, kf);
-      launch(k_scan_listed<0>, p.slow_blocks, 0, s_obs, kf);
+      launch(p.sized ? k_scan_listed<0, false, SMX_TEAM_LARGE, true> : k_scan_listed<0>, p.slow_blocks, 0, s_obs, kf);
       break;
-    case Facts::WIDE: launch(k_scan_half<0, false, SMX_TEAM>, p.facts_blocks, 0, s_obs, kf); break;
-    case Facts::FOUR: launch(k_scan_half<0>, p.facts_blocks, 0, s_obs, kf); break;  // (the facts half seeds no path)
+    case Facts::WIDE: launch(p.sized ? k_scan_half<0, false, SMX_TEAM, true> : k_scan_half<0, false, SMX_TEAM>, p.facts_blocks, 0, s_obs, kf); break;
+    case Facts::FOUR: launch(p.sized ? k_scan_half<0, false, SMX_TEAM_LARGE, true> : k_scan_half<0>, p.facts_blocks, 0, s_obs, kf); break;  // (the facts half seeds no path)
   }
   if (ph) (void)hipEventRecord(ph[SMX_PHASE_SCAN + 1], stream);
   if (!p.fork) launch_grids(h, p, k, stream);
@@ -5685,7 +5763,7 @@ static void observation_pass(smx_handle h, const TickPlan& p, const KernelArgs& 
   kw.seed_pending = p.seed_pending();
   const unsigned walk_blocks = smx_blocks(total * SMX_WP_LANES);
   switch (p.rows) {
-    case Rows::SENSORS: launch(k_sensors, p.sensor_blocks, p.sensor_lds, stream, k); break;
+    case Rows::SENSORS: launch(p.sized ? k_sensors_sized : k_sensors, p.sensor_blocks, p.sensor_lds, stream, k); break;
     case Rows::UNSTAGED: launch(k_waypoints, p.wp_blocks, 0, stream, k); break;
     case Rows::TABLES:
       launch(k_wp_walk, walk_blocks, 0, stream, kw);
@@ -5702,7 +5780,7 @@ static void observation_pass(smx_handle h, const TickPlan& p, const KernelArgs& 
       if (p.rows == Rows::EMIT_CHAIN_AFTER) launch_slow_chain(p, ks, stream);  // (one stream: after the main waypoint kernels)
       break;
   }
-  if (!p.small()) launch(k_observe, p.obs_blocks, 0, s_obs, k);
+  if (!p.small()) launch(p.sized ? k_observe_sized : k_observe, p.obs_blocks, 0, s_obs, k);
   if (p.lidar == Lidar::CALLER) launch(p.sized ? k_lidar<true> : k_lidar<false>, p.lidar_blocks, 0, stream, k);
   if (p.fork) {
     // (each side stream joins the caller's directly: chaining side 0 through side 1 puts one more hop behind the
@@ -5736,7 +5814,7 @@ static int tail_and_reset_pass(smx_handle h, const TickPlan& p, const KernelArgs
   r.reset_all = (!p.is_step && mask == nullptr) ? 1 : 0;
   r.env_mask = p.is_step ? nullptr : mask;
   if (!p.is_step) {
-    launch(p.guard ? k_reset<true> : k_reset<false>, p.veh_blocks, 0, stream, r);
+    launch(p.guard ? (p.sized ? k_reset<true, true> : k_reset<true>) : (p.sized ? k_reset<false, true> : k_reset<false>), p.veh_blocks, 0, stream, r);
     launch(k_reset_env, p.env_blocks, 0, stream, r);
   }
   TailArgs t{};
@@ -5768,7 +5846,7 @@ static int tail_and_reset_pass(smx_handle h, const TickPlan& p, const KernelArgs
       r.lidar_blocks = 0;
     }
     r.walk_new = p.first_walks_new ? 1 : 0;
-    hipLaunchKernelGGL(k_first, dim3(p.obs_blocks), dim3(SMX_FIRST_BLOCK), 0, stream, r, t.groups, t.n_groups);
+    hipLaunchKernelGGL((p.sized ? k_first_sized : k_first), dim3(p.obs_blocks), dim3(SMX_FIRST_BLOCK), 0, stream, r, t.groups, t.n_groups);
     if (p.lane_ttc)  // after k_first: it reads the first observations' rows, not SMX_F_FIRST
       hipLaunchKernelGGL(k_lane_ttc, dim3(p.ttc_first_blocks), dim3(SMX_BLOCK), p.ttc_lds, stream, r, (const int32_t*)t.groups, (const int32_t*)t.n_groups);
     if (p.ego_centric)

@@ -91,6 +91,7 @@ struct PlanInputs {
   bool guard_bound;        // smx_set_guard holds a buffer: the state guard is on
   bool history_bound;      // smx_set_social_history holds a table: the social slots replay it
   bool dims_bound;         // smx_set_social_history_dims holds a table: ... at each vehicle's own dimensions
+  bool agent_dims_bound;   // smx_set_agent_dims holds a table: the agents at their own (either one: a triple block is bound)
   bool follow_entry;       // the call is smx_step_history_agents: the agents are placed on their recorded vehicles' rows
   bool ogm_mask;           // the handle holds the OGM tiles' piece mask and smx_set_ogm_delta has not switched it off
   bool handover_entry;     // the call is smx_step_history_handover: each agent follows or is driven, as its handover tick says
@@ -176,7 +177,7 @@ struct TickPlan {
   // the state guard (smx_set_guard): the GUARD instantiations of the control kernels, k_reset and k_tail in the places of
   // the plain ones — the same launches on the same streams, no kernel and no edge more
   bool guard;
-  // per-vehicle dimensions (smx_set_social_history_dims): the SIZED instantiations of k_ogm_env, k_lidar and k_lidar_first
+  // per-vehicle dimensions (smx_set_social_history_dims or smx_set_agent_dims: a triple block is bound): the SIZED instantiations of k_ogm_env, k_lidar and k_lidar_first
   // in the places of the plain ones — the same launches on the same streams; every other reader branches on the pointer
   bool sized;
   bool tail_builds_list;  // k_tail builds the next tick's alive list
@@ -353,7 +354,7 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
   }
   p.frame_stack = c.frame_stack > 0 && in.frame_stack_bound;
   p.guard = in.guard_bound;
-  p.sized = in.dims_bound;
+  p.sized = in.dims_bound || in.agent_dims_bound;
   p.ego_centric = (c.sensors & SMX_SENSOR_EGO_CENTRIC) != 0;
   if (p.ego_centric) {
     const size_t apb = SMX_BLOCK / SMX_EC_TEAM;

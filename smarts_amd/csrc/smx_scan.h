@@ -43,7 +43,7 @@ __device__ __forceinline__ int team_or(int v) {
 template <int TEAM>
 __device__ inline RoadFacts team_road_facts(const MapDev& m, double px, double py, double radius, int n_corners,
                                             const double* cx, const double* cy, double dist_bound = SMX_INF,
-                                            double cell_radius = -1.0) {
+                                            double cell_radius = -1.0, double corner_reach = 2.0) {
   RoadFacts out;
   out.lane = -1;
   out.dist = SMX_INF;
@@ -73,7 +73,7 @@ __device__ inline RoadFacts team_road_facts(const MapDev& m, double px, double p
           const double gx = fmax(fmax(bx0 - px, px - bx1), 0.0), gy2 = fmax(fmax(by0 - py, py - by1), 0.0);
           const double lb2 = gx * gx + gy2 * gy2;
           const double keep_c = fmin(fmax(fmin(out.dist, dist_bound), s.thr), radius) + 1e-6;
-          const double keep_q = s.thr + 2.0 + 1e-6;
+          const double keep_q = s.thr + corner_reach + 1e-6;
           const double keep = n_corners > 0 ? fmax(keep_c, keep_q) : keep_c;
           if (lb2 > keep * keep) continue;
         }
@@ -134,17 +134,20 @@ struct FactsCarry {
 
 // team_road_facts with radius = max(pose_radius, 2 x default lane width), seeded from `c`: last tick's nearest lane
 // lies at most (its distance then + the way driven since) away, which bounds the nearest distance now; the corners
-// see segments up to the widest road_with_point threshold (`thr_max`) + half a vehicle diagonal (< 2 m) away.
+// see segments up to the widest road_with_point threshold (`thr_max`) + half a vehicle diagonal away (`corner_reach`:
+// < 2 m for the sedan; with per-agent dimensions the observer's own, and `pose_radius` >= thr_max + corner_reach then:
+// ObserverBox, smx_tick.h).
 template <int TEAM>
 __device__ inline RoadFacts team_road_facts_seeded(const MapDev& m, double px, double py, double pose_radius, int n_corners,
-                                                   const double* cx, const double* cy, const FactsCarry& c, double thr_max) {
+                                                   const double* cx, const double* cy, const FactsCarry& c, double thr_max,
+                                                   double corner_reach = 2.0) {
   const double radius = fmax(pose_radius, 2.0 * m.default_lane_width);
   double dist_bound = SMX_INF, cell_radius = -1.0;
   if (c.valid && c.qx == c.qx && c.qy == c.qy && c.prev_dist < radius) {
     dist_bound = (c.prev_dist + euclid(px, py, c.qx, c.qy)) * (1.0 + 1e-12) + 1e-9;
-    cell_radius = fmax(dist_bound, thr_max + (n_corners > 0 ? 2.0 : 0.0)) + 2e-6;
+    cell_radius = fmax(dist_bound, thr_max + (n_corners > 0 ? corner_reach : 0.0)) + 2e-6;
   }
-  return team_road_facts<TEAM>(m, px, py, radius, n_corners, cx, cy, dist_bound, cell_radius);
+  return team_road_facts<TEAM>(m, px, py, radius, n_corners, cx, cy, dist_bound, cell_radius, corner_reach);
 }
 
 // ---------------------------------------------------------------------------------
@@ -948,13 +951,14 @@ __device__ inline void lane_positions_at_offsets(const MapDev& m, int v0, int v1
 #define SMX_FACTS_SPAN 4  // grid rows the seeded visit handles (a reach of ~4 m over 8 m cells meets two, seldom three)
 __device__ inline bool facts_one_lane(const MapDev& m, double px, double py, double pose_radius, int n_corners,
                                       const double* cx, const double* cy, const FactsCarry& c, double thr_max, int* cand,
-                                      int stride, bool want_heading, RoadFacts& out, double& lane_heading) {
+                                      int stride, bool want_heading, RoadFacts& out, double& lane_heading,
+                                      double corner_reach = 2.0) {
   SMX_TSTAMP(tf0);
   const double radius = fmax(pose_radius, 2.0 * m.default_lane_width);
   if (!(c.valid && c.qx == c.qx && c.qy == c.qy && c.prev_dist < radius)) return false;
   const double dist_bound = (c.prev_dist + euclid(px, py, c.qx, c.qy)) * (1.0 + 1e-12) + 1e-9;
   if (!(dist_bound < radius)) return false;
-  const double reach = fmax(dist_bound, thr_max + (n_corners > 0 ? 2.0 : 0.0)) + 4e-6;
+  const double reach = fmax(dist_bound, thr_max + (n_corners > 0 ? corner_reach : 0.0)) + 4e-6;
   const double road_radius = fmax(5.0, 2.0 * m.default_lane_width);  // sumo_road_network.py:705
   int cx0 = (int)floor((px - reach - m.sg_x0) / m.sg_cell), cx1 = (int)floor((px + reach - m.sg_x0) / m.sg_cell);
   int cy0 = (int)floor((py - reach - m.sg_y0) / m.sg_cell), cy1 = (int)floor((py + reach - m.sg_y0) / m.sg_cell);
@@ -1005,7 +1009,7 @@ __device__ inline bool facts_one_lane(const MapDev& m, double px, double py, dou
         const double gx = fmax(fmax(fmin(x1[u], x2[u]) - px, px - fmax(x1[u], x2[u])), 0.0);
         const double gy2 = fmax(fmax(fmin(y1[u], y2[u]) - py, py - fmax(y1[u], y2[u])), 0.0);
         const double keep_c = fmin(fmax(dist_bound, thr[u]), radius) + 3e-6;
-        const double keep = n_corners > 0 ? fmax(keep_c, thr[u] + 2.0 + 1e-6) : keep_c;
+        const double keep = n_corners > 0 ? fmax(keep_c, thr[u] + corner_reach + 1e-6) : keep_c;
         if (!(gx * gx + gy2 * gy2 > keep * keep)) {
           if (n < SMX_FACTS_CAND)
             cand[n * stride] = kk[u];

@@ -70,8 +70,9 @@ struct KernelArgs {
   // traffic-history replay (smx_set_social_history; smx_history.h): history.vehicle null = none bound, the social slots are
   // the scripted lane followers.  Every branch on it is marked as the rare side.
   HistoryDev history;
-  // ... at each vehicle's own dimensions (smx_set_social_history_dims): dims.table null = none bound, every box is the
-  // sedan's.  dims.slot holds a triple per vehicle of the batch, written beside a replayed slot's pose.
+  // ... at each vehicle's own dimensions (smx_set_social_history_dims, smx_set_agent_dims): dims.slot null = neither bound,
+  // every box is the sedan's.  dims.slot holds a triple per vehicle of the batch, written beside a replayed slot's pose
+  // (dims.table) and beside an agent's spawn pose (dims.agent).
   HistoryDimsDev dims;
   // history agents (smx_set_history_agents; the table itself is history.follow): the caller's optional expert-action and
   // status rows, written where a follower's pose is (respawn_vehicle, k_control_kinematic's FOLLOW form); null: not wanted
@@ -292,8 +293,52 @@ __device__ __forceinline__ VehBox vehicle_box(const KernelArgs& a, size_t gid, b
   }
   return b;
 }
-__device__ __forceinline__ VehBox vehicle_box(const KernelArgs& a, size_t gid) {
-  return vehicle_box(a, gid, __builtin_expect(a.dims.table != nullptr, 0));
+__device__ __forceinline__ bool dims_sized(const KernelArgs& a) { return __builtin_expect(a.dims.slot != nullptr, 0); }
+__device__ __forceinline__ VehBox vehicle_box(const KernelArgs& a, size_t gid) { return vehicle_box(a, gid, dims_sized(a)); }
+// SIZED, an int template argument of the roles that read an agent's OWN box (scan, observe, respawn): 1 / 0 — the launch
+// plan chose the instantiation (TickPlan::sized), and the one without dimensions holds nothing of that work —, -1: the
+// role asks the argument block, the rare side of a branch.
+template <int SIZED>
+__device__ __forceinline__ bool own_box_sized(const KernelArgs& a) {
+  return SIZED < 0 ? dims_sized(a) : SIZED != 0;
+}
+// An agent's triple (smx_set_agent_dims), written by respawn_vehicle beside the spawn pose and by nobody else: row
+// (episode mod agent_rows) of the bound table, the sedan's for an all-NaN triple (the bind-time check lets NaN through
+// for whole triples only) and with no table bound (social dimensions alone: an unbind shows at the next respawn).
+// Only called with a triple block (dims.slot): with nothing bound nothing is written.
+__device__ __forceinline__ void agent_store_dims(const KernelArgs& a, size_t gid, int episode) {
+  VehBox b = {SMX_CHASSIS_LENGTH, SMX_CHASSIS_WIDTH, SMX_CHASSIS_HEIGHT};
+  if (a.dims.agent != nullptr) {
+    const int n_veh = a.cfg.num_vehicles, n_agents = n_veh - a.cfg.num_social, rows = a.dims.agent_rows;
+    const size_t env = gid / (size_t)n_veh, k = gid - env * (size_t)n_veh;
+    const size_t row = (size_t)(((episode % rows) + rows) % rows);
+    const double* d = a.dims.agent + ((row * (size_t)a.cfg.num_envs + env) * (size_t)n_agents + k) * 3;
+    if (d[0] == d[0]) b = VehBox{d[0], d[1], d[2]};
+  }
+  double* w = a.dims.slot + gid * 3;
+  w[0] = b.length;
+  w[1] = b.width;
+  w[2] = b.height;
+}
+// The observer's own box on the sized path, with the reaches the road-facts search takes from it (smx_scan.h): the
+// corners lie half a diagonal from the centre, and the search radius covers the lookups that are answered from its
+// own nearest lane — off_route's half diagonal + 5 (sensors.py:548); within_radius = length (sensors.py:274) is covered
+// by the length's cap, SMX_AGENT_DIMS_MAX_LENGTH = SMX_POSE_SCAN_RADIUS — and every segment a corner's road_with_point
+// can see (`thr_max`: the widest threshold of the map).  The sedan: 2 m and
+// SMX_POSE_SCAN_RADIUS, the constants of the path without dimensions.
+static_assert(SMX_AGENT_DIMS_MAX_LENGTH == SMX_POSE_SCAN_RADIUS, "an agent's length is capped at the radius of its mates' road-facts search");
+struct ObserverBox {
+  double length, width, corner_reach, scan_radius;
+};
+__device__ __forceinline__ ObserverBox observer_box(const KernelArgs& a, size_t gid, double thr_max) {
+  const VehBox b = vehicle_box(a, gid, true);
+  const double half_diag = 0.5 * sqrt(b.length * b.length + b.width * b.width);
+  ObserverBox o;
+  o.length = b.length;
+  o.width = b.width;
+  o.corner_reach = fmax(2.0, half_diag + 1e-6);
+  o.scan_radius = fmax(SMX_POSE_SCAN_RADIUS, half_diag + fmax(5.0, thr_max) + 1e-6);
+  return o;
 }
 // The replayed vehicle's step, in the scripted step's place in the tick (before collisions and sensors): the pose and
 // speed of the frame this tick's observation belongs to — env_ticks + 1, smarts.py:261-262 —, copied word for word.
@@ -538,7 +583,7 @@ __device__ __forceinline__ int history_respawn(const KernelArgs& a, size_t gid, 
   return SMX_F_SOCIAL | SMX_F_FIRST | (present ? SMX_F_ALIVE : 0);
 }
 
-template <bool GUARD>
+template <bool GUARD, int SIZED = -1>
 __device__ __forceinline__ void respawn_vehicle(const KernelArgs& a, size_t gid, size_t total, int episode) {
   const int row = a.sp.episodes > 0 ? (((episode % a.sp.episodes) + a.sp.episodes) % a.sp.episodes) : 0;
   const double* sp = a.sp.pose + ((size_t)row * total + gid) * 4;
@@ -580,10 +625,14 @@ __device__ __forceinline__ void respawn_vehicle(const KernelArgs& a, size_t gid,
       SF(SMX_S_MCL_Y) = so[1];  // arclength offset
       fl |= SMX_F_SOCIAL;
     }
-  } else if (__builtin_expect(a.history.follow != nullptr, 0)) {
-    // a history agent (smx_set_history_agents): the recording's row, not the spawn row (whose guard verdict goes with it)
-    fl = history_agent_respawn(a, gid, total, episode);
-    if constexpr (GUARD) a.guard[gid] = 0;
+  } else {
+    if (__builtin_expect(a.history.follow != nullptr, 0)) {
+      // a history agent (smx_set_history_agents): the recording's row, not the spawn row (whose guard verdict goes with it)
+      fl = history_agent_respawn(a, gid, total, episode);
+      if constexpr (GUARD) a.guard[gid] = 0;
+    }
+    // the agent's own dimensions (smx_set_agent_dims), beside its pose: a follower keeps them through whatever comes
+    if (own_box_sized<SIZED>(a)) agent_store_dims(a, gid, episode);
   }
   a.st.flags[gid] = fl;
   // the slot's knot lists belong to the vehicle that is gone (k_wp_walk only visits alive vehicles)

@@ -238,6 +238,31 @@ def check_guard(num_envs: int, num_vehicles: int, count: int, margin: float = na
         raise ValueError(err.value.decode())
 
 
+def check_agent_dims(action_space: str, num_envs: int, num_vehicles: int, num_social: int, dims: np.ndarray) -> None:
+    """``smx_check_agent_dims``: would ``smx_set_agent_dims`` take the float64 table ``dims`` ``(R, E, A, 3)`` for a shard
+    of this shape and action space?  Needs the built library, no device and no handle; raises ``ValueError`` with the
+    library's reason when not."""
+    lib = nat.load_library()
+    dims = _agent_dims_table(dims, int(num_envs), int(num_vehicles) - int(num_social))
+    c = nat.SmxConfig()
+    c.num_envs, c.num_vehicles, c.num_social = int(num_envs), int(num_vehicles), int(num_social)
+    if action_space not in nat.ACTION_SPACES:
+        raise ValueError(f"action space {action_space!r} is not on the accelerated path")
+    c.action_space = nat.ACTION_SPACES[action_space]
+    ad = nat.SmxAgentDims()
+    ad.dims_host, ad.rows = dims.ctypes.data, int(dims.shape[0])
+    err = C.create_string_buffer(512)
+    if lib.smx_check_agent_dims(C.byref(c), C.byref(ad), err, len(err)) != 0:
+        raise ValueError(err.value.decode())
+
+
+def _agent_dims_table(dims, num_envs: int, num_agents: int) -> np.ndarray:
+    dims = np.ascontiguousarray(dims, dtype=np.float64)
+    if dims.ndim != 4 or dims.shape[0] < 1 or tuple(dims.shape[1:]) != (num_envs, num_agents, 3):
+        raise ValueError(f"agent dims must be float64 of shape (R, {num_envs}, {num_agents}, 3), got {tuple(dims.shape)}")
+    return dims
+
+
 class BatchedSim:
     """One shard of environment instances resident on one GPU."""
 
@@ -694,6 +719,28 @@ class BatchedSim:
         nat.check(self.lib, self.handle, self.lib.smx_set_social_history_dims(self.handle, C.byref(sd)), "smx_set_social_history_dims")
         self.history_dims = True
 
+    def set_agent_dims(self, dims: Optional[np.ndarray]):
+        """Bind per-agent vehicle dimensions (``smx_set_agent_dims``; the kinematic action spaces TargetPose,
+        TrajectoryWithTime and Imitation only): host float64 ``(R, E, A, 3)`` — length, width, height of agent ``a`` of
+        env ``e`` in episode ``k`` (row ``k mod R``), three NaNs = the sedan's box; ``A = N - num_social``.  The library
+        copies the table.  An agent takes its triple where it is (re)spawned — the next ``reset``, a restart under
+        ``auto_reset``, a history agent's placement — and keeps it until the next one; from then on its collisions, its
+        ``on_shoulder`` / ``off_road`` corners, its ``off_route`` radius, its ego box row and its neighbours' lane ids are
+        its own box's, and its env-mates see it in ``nb_box``, OGM, RGB and lidar.  ``None`` unbinds: sedans again from
+        the next (re)spawn.  ``set_traffic_history`` keeps the binding.  Refused with the library's reason
+        (``SmxError``): a dynamic action space, a component that is not finite, <= 0 or above its cap (length 10 m —
+        the radius at which a neighbour's lane is searched, which answers the lookup within the observer's length —, width
+        25 m, height 10 m), a triple that is partly NaN."""
+        if dims is None:
+            nat.check(self.lib, self.handle, self.lib.smx_set_agent_dims(self.handle, None), "smx_set_agent_dims")
+            self.agent_dims = None
+            return
+        table = _agent_dims_table(dims, self.E, self.N - self.cfg.num_social)
+        ad = nat.SmxAgentDims()
+        ad.dims_host, ad.rows = table.ctypes.data, int(table.shape[0])
+        nat.check(self.lib, self.handle, self.lib.smx_set_agent_dims(self.handle, C.byref(ad)), "smx_set_agent_dims")
+        self.agent_dims = table.copy()
+
     def set_history_agents(self, vehicle: Optional[torch.Tensor], expert_actions: bool = True):
         """Bind the history agents (``smx_set_history_agents``; needs ``action_space="Imitation"`` and a bound traffic
         history): agent slot ``a`` of env ``e`` follows recorded vehicle ``vehicle[k mod R, e, a]`` in episode ``k`` —
@@ -817,6 +864,7 @@ class BatchedSim:
     history_handover = None
     history_bubbles = None
     history_dims = False
+    agent_dims = None  # the bound (R, E, A, 3) table of set_agent_dims (a host copy), or None
     traffic_history = None
     history_start_frames = None
     history_replaced = None

@@ -137,8 +137,14 @@ class BatchCore:
                  missions: Optional[Dict[str, Any]] = None, spawns: str = "reference", shuffle_scenarios: bool = True,
                  ego_centric: bool = False, state_guard: bool = False,
                  state_guard_margin: float = nat.GUARD_MARGIN_DEFAULT, traffic_history=None, history_start_frames=None,
-                 history_dims: bool = False):
-        """``traffic_history``: a ``smarts_amd.traffic_history.TrafficHistoryTable`` or the path of a converted dataset
+                 history_dims: bool = False, agent_dims: Optional[Dict[str, Sequence]] = None):
+        """``agent_dims``: ``{agent id: (length, width, height)}``, the agent's own vehicle dimensions
+        (``BatchedSim.set_agent_dims``; the reference's ``Vehicle.agent_vehicle_dims``): a component that is ``None``, 0
+        or -1 takes the passenger default (``Dimensions.copy_with_defaults``), agents it lacks stay sedans.  The agent's
+        start is placed from the front bumper with its own length, its events, ``ego_vehicle_state.bounding_box`` and
+        the box its env-mates see are its own.  ``ValueError`` for an action space that is not kinematic (TargetPose,
+        TrajectoryWithTime, Imitation): the dynamic chassis is the sedan.
+        ``traffic_history``: a ``smarts_amd.traffic_history.TrafficHistoryTable`` or the path of a converted dataset
         (SQLite): the ``num_social`` slots replay it (``BatchedSim.set_traffic_history``) and are named
         ``history-vehicle-<id>`` in the observations, the reference provider's prefix.  ``history_start_frames``: int
         ``[R, E]`` (or ``[E]``), the table frame at which episode ``k`` of env ``e`` starts (row ``k mod R``); ``None`` =
@@ -180,13 +186,27 @@ class BatchCore:
         if spawns not in ("reference", "synthetic"):
             raise ValueError('spawns must be "reference" or "synthetic"')
         spawn_mode = spawns
+        # the agents' own dimensions (resolved here: the start poses below are placed with the agent's own length)
+        self.agent_dims = None
+        own_length: List[Optional[float]] = [None] * self.N
+        if agent_dims:
+            from ..traffic_history import resolve_dimensions
+
+            unknown = set(agent_dims) - set(self.agent_ids)
+            if unknown:
+                raise ValueError(f"agent_dims for unknown agents: {sorted(unknown)}")
+            if self.cfg.action_space not in ("TargetPose", "TrajectoryWithTime", "Imitation"):
+                raise ValueError(f"agent_dims needs a kinematic action space (TargetPose, TrajectoryWithTime, Imitation): "
+                                 f"an agent of ActionSpaceType.{self.cfg.action_space} drives the sedan its dynamics model describes")
+            self.agent_dims = {a: resolve_dimensions(2, *agent_dims[a]) for a in agent_dims}  # 2: passenger
+            own_length = [self.agent_dims[a][0] if a in self.agent_dims else None for a in self.agent_ids]
         spawns, where = make_spawns(self.cm, num_envs, self.N + num_social, episodes=4, seed=seed, return_lanes=True)
         if spawn_mode == "reference":
             from ..missions import reference_spawn_table
             from ..sumo_map import load_net
 
             ref = reference_spawn_table(load_net(self.scenario_dir), num_envs, self.N, seed, episodes=spawns.shape[0],
-                                        shuffle_scenarios=shuffle_scenarios)
+                                        shuffle_scenarios=shuffle_scenarios, lengths=own_length if self.agent_dims else None)
             slots = self.N + num_social
             spawns.reshape(spawns.shape[0], num_envs, slots, 4)[:, :, :self.N] = ref.reshape(spawns.shape[0], num_envs, self.N, 4)
         # mission vias (sstudio Via per agent id) -> resolved lists per vehicle slot
@@ -216,10 +236,17 @@ class BatchCore:
             slots = self.N + num_social
             for i, m in enumerate(self.missions):
                 if m is not None:
-                    x, y, h = m.spawn_pose()
+                    own = own_length[i] if i < self.N else None
+                    x, y, h = m.spawn_pose() if own is None else m.spawn_pose(own)
                     spawns.reshape(spawns.shape[0], num_envs, slots, 4)[:, :, i] = (x, y, h, 0.0)
         self.sim = BatchedSim(self.cm, self.cfg, device=device, spawns=spawns, seed=seed, social_spawns=where,
                               vias=self.vias, missions=self.missions)
+        if self.agent_dims:
+            table = np.full((1, num_envs, self.N, 3), np.nan, dtype=np.float64)
+            for i, a in enumerate(self.agent_ids):
+                if a in self.agent_dims:
+                    table[0, :, i] = self.agent_dims[a]
+            self.sim.set_agent_dims(table)
         self.traffic_history = None
         if traffic_history is not None:
             import torch

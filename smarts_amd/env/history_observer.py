@@ -73,13 +73,18 @@ class HistoryObserver:
     of ``smarts_amd.env.Bubble`` with ``PositionalZone`` zones, evaluated on the device at the start of every tick;
     ``follow_actor_id`` is an agent id of this observer (``agent_id``) and names the same agent slot in every env that has
     it.  ``bubble_states()`` reads what they decided.  (``bubbles`` stands before ``handover`` in the signature: pass both
-    by keyword.)"""
+    by keyword.)  ``dims`` (by keyword too; default ``False``: every vehicle has the sedan's box): the replayed vehicles at their own
+    dimensions (``set_traffic_history(dims=True)``) and every follower at those of the vehicle it follows
+    (``BatchedSim.set_agent_dims`` over ``table.agent_dims``), through a handover and a bubble alike — the boxes, events
+    and lane ids beside every expert action are then the recorded vehicle's.  A followed vehicle longer than 10 m is refused
+    (``SmxError``: the cap of ``set_agent_dims``); it can be replayed at its size, not followed at it."""
 
     bubbles = None
 
     def __init__(self, scenario: str, table_or_path, agent_interface: AgentInterface, vehicle_ids: Optional[Sequence[int]] = None,
                  num_envs: Optional[int] = None, dt: float = 0.1, num_agents: int = 1, device: str = "cuda:0",
-                 waypoint_window: Optional[Tuple[int, int]] = (4, 20), seed: int = 0, bubbles=None, handover=None):
+                 waypoint_window: Optional[Tuple[int, int]] = (4, 20), seed: int = 0, bubbles=None, dims: bool = False,
+                 handover=None):
         import torch
 
         from ..engine import BatchedSim, make_spawns
@@ -107,8 +112,11 @@ class HistoryObserver:
         spawns, where = make_spawns(self.cm, self.E, self.A + self.S, episodes=1, seed=seed, return_lanes=True)  # (never read)
         self.sim = BatchedSim(self.cm, self.cfg, device=device, spawns=spawns, seed=seed, social_spawns=where)
         self.start_frames, self.followed = start, vehicle
-        self.sim.set_traffic_history(table, torch.from_numpy(start).to(self.sim.device))
+        self.dims = bool(dims)
+        self.sim.set_traffic_history(table, torch.from_numpy(start).to(self.sim.device), dims=self.dims)
         self.sim.set_history_agents(torch.from_numpy(vehicle).to(self.sim.device))
+        if self.dims:
+            self.sim.set_agent_dims(table.agent_dims(vehicle))
         self.handover = None if handover is None else self._handover_table(handover)
         if self.handover is not None:
             self.sim.set_history_handover(torch.from_numpy(self.handover).to(self.sim.device))

@@ -71,7 +71,7 @@ class ParallelEnv:
                                spawns=p._spawns, shuffle_scenarios=p._shuffle_scenarios,
                                state_guard=p._state_guard, state_guard_margin=p._state_guard_margin,
                                traffic_history=p._traffic_history, history_start_frames=self._history_start_frames,
-                               history_dims=self._history_dims)
+                               history_dims=self._history_dims, agent_dims=p._agent_dims)
         self._seed = seed
         return [seed + i for i in range(self._num_envs)]
 

@@ -373,14 +373,15 @@ def _center_pose_at_point(lane, point: Sequence[float]):
 
 
 def reference_spawn_table(net: SumoNet, num_envs: int, count: int, seed: int, episodes: int = 4,
-                          shuffle_scenarios: bool = True) -> np.ndarray:
+                          shuffle_scenarios: bool = True, lengths: Optional[Sequence[Optional[float]]] = None) -> np.ndarray:
     """Spawn poses ``[episodes, num_envs * count, 4]`` (x, y, heading, speed 0) of agents without missions, as
     ``hiway-v0`` starts them: env ``e`` of a ParallelEnv is seeded ``seed + e`` (parallel_env.py:190-202); every
     ``reset`` draws the scenario rolls again (scenario.py:211-214), then one ``Mission.random_endless_mission`` per
     agent; the agents' vehicles, created after all missions are drawn, take a ``gen_id()`` each
     (vehicle_index.py:602: ``random.getrandbits(128)``) from the same stream.  The vehicle's centre lies half a
     chassis length behind the mission's start (Pose.from_front_bumper, vehicle.py:379-387); it stands still
-    (TrapEntryTactic.default_entry_speed is None).  Episode 0 is pinned by tests/golden/default_missions.npz (the
+    (TrapEntryTactic.default_entry_speed is None); ``lengths``: per agent its own length where it has one (``agent_dims``
+    of the env layer; ``None``: the passenger's).  Episode 0 is pinned by tests/golden/default_missions.npz (the
     reference's own draw); the stream positions of later episodes follow from the calls named here (read, not run:
     hiway-v0 cannot run in this tree)."""
     import random as _random
@@ -391,7 +392,8 @@ def reference_spawn_table(net: SumoNet, num_envs: int, count: int, seed: int, ep
         for ep in range(episodes):
             ms = _draw_endless_missions(net, count, rng, 3 if shuffle_scenarios else 0)
             for i, m in enumerate(ms):
-                x, y, h = m.spawn_pose()
+                own = None if lengths is None else lengths[i]
+                x, y, h = m.spawn_pose() if own is None else m.spawn_pose(float(own))
                 out[ep, e * count + i] = (x, y, h, 0.0)
             for _ in range(count):
                 rng.getrandbits(128)

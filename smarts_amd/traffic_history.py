@@ -235,6 +235,18 @@ class TrafficHistoryTable:
             out[vid] = self.resolved_dimensions(vid)
         return out
 
+    def agent_dims(self, vehicle) -> np.ndarray:
+        """The table ``BatchedSim.set_agent_dims`` takes for agents that stand for recorded vehicles — followers
+        (``set_history_agents``' follow table) and ``replaced`` stand-ins alike: ``vehicle`` is an integer array of
+        vehicle ids, ``(R, E, A)`` for a follow table, and the result float64 ``vehicle.shape + (3,)`` holds each id's
+        ``resolved_dimensions`` (a recorded vehicle keeps its dimensions when an agent takes it over, vehicle_index.py:
+        439, 489).  An id < 0 (the slot follows nothing) gives three NaNs: the sedan's box."""
+        ids = np.asarray(vehicle.cpu() if hasattr(vehicle, "cpu") else vehicle, dtype=np.int64)
+        out = np.full(ids.shape + (3,), np.nan, dtype=np.float64)
+        for vid in np.unique(ids[ids >= 0]):
+            out[ids == vid] = self.resolved_dimensions(int(vid))
+        return out
+
     def vehicle_ids(self) -> List[int]:
         return sorted(int(v) for v in np.unique(self.vehicle) if v >= 0)
 
