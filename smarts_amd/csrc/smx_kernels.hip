@@ -23,6 +23,10 @@
 // sensors / commit restricted to the re-created vehicles.  Above 16384 vehicles every role is
 // launched on its own (k_waypoints, k_observe, k_lidar, k_ogm; see enqueue()).  Envs are independent
 // (reference: one process per env, parallel_env.py:96-122): no inter-workgroup communication.
+//
+// Three phases are in headers of their own so far, included below: smx_k_scan.h (k_scan and its listed forms),
+// smx_k_grids.h (OGM / DAGM / RGB roles, k_ogm, k_dagm, k_rgb) and smx_k_lidar.h (lidar role, k_lidar, k_lidar_first);
+// what the phases share is in smx_tick.h.  The other phases follow.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,6 +43,9 @@
 #include "smx_handle.h"
 #include "smx_history.h"
 #include "smx_host.h"
+#include "smx_k_grids.h"
+#include "smx_k_lidar.h"
+#include "smx_k_scan.h"
 #include "smx_plan.h"
 #include "smx_scan.h"
 #include "smx_tick.h"
@@ -1238,324 +1245,6 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_social(const KernelArgs a) {
     v_new = fmin(fmax(v + acc * c.dt, 0.0), v0);
   }
   SF(SMX_S_THROTTLE) = v_new;
-}
-
-// =================================================================================
-// k_scan: map sweeps at the vehicle's pose, SMX_TEAM lanes per vehicle.
-//   facts: nearest lane + distance (nearest_lane with any radius up to 10 m is "that lane if
-//          closer than r": ego lane sensors.py:277, neighbour lanes :244, off-route :552),
-//          road_with_point at the centre (:498-500) and at the four bounding-box corners
-//          (:502-509; Vehicle.bounding_box vehicle.py:315-332, rotate_around_point math.py:436-444)
-//   seeds: start road / route filter / start lanepoints of waypoint_paths(pose, route)
-//          (sumo_road_network.py:815-882), used by the waypoints role now and by k_control next tick
-// =================================================================================
-// one half of k_scan for one vehicle team (see k_scan)
-template <int TEAM, bool ROUTED, int SIZED = -1>
-__device__ __forceinline__ void scan_role(const KernelArgs& a, const MapDev& m, const smx_config& c, size_t gid,
-                                          size_t total, int rank, int flags, int role) {
-  SMX_TSTAMP(ts0);
-  const VehState s = load_vehicle(a, gid, total);
-  int32_t* fi = a.st.facts_i32;
-  if (SMX_SKIP(a, 512) && role == 1) return;
-  if (SMX_SKIP(a, 1024) && role == 0) return;
-  if (role == 0) {
-    // ---- road facts
-    const double cxs[4] = {-0.5, 0.5, 0.5, -0.5};
-    const double cys[4] = {0.5, 0.5, -0.5, -0.5};
-    double cx[4], cy[4];
-    const double ch = cos(s.heading), sh = sin(s.heading);
-    const bool social = (flags & SMX_F_SOCIAL) != 0;  // only its nearest lane is ever asked for (neighbour rows)
-    // the observer's own box (sensors.py:506): the sedan's, or with dimensions bound an agent's triple and its reaches
-    ObserverBox ob = {SMX_CHASSIS_LENGTH, SMX_CHASSIS_WIDTH, 2.0, SMX_POSE_SCAN_RADIUS};
-    if (own_box_sized<SIZED>(a) && !social) ob = observer_box(a, gid, a.dagm_reach + 0.1);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      double qx = s.x + cxs[q] * ob.width;
-      double qy = s.y + cys[q] * ob.length;
-      cx[q] = s.x + ch * (qx - s.x) + sh * (qy - s.y);
-      cy[q] = s.y + -sh * (qx - s.x) + ch * (qy - s.y);
-    }
-    FactsCarry fc;
-    fc.valid = false;
-    if (a.facts_carry != nullptr && !(flags & SMX_F_FIRST)) {
-      fc.qx = a.facts_carry[gid];
-      fc.qy = a.facts_carry[total + gid];
-      fc.prev_dist = a.st.facts_f64[(size_t)SMX_FF_LANE_DIST * total + gid];
-      fc.valid = fi[(size_t)SMX_FI_LANE * total + gid] >= 0;
-    }
-    RoadFacts h = team_road_facts_seeded<TEAM>(m, s.x, s.y, ob.scan_radius, social ? 0 : 4, cx, cy, fc, a.dagm_reach + 0.1, ob.corner_reach);
-    if (a.facts_carry != nullptr && rank == 0) {
-      a.facts_carry[gid] = s.x;
-      a.facts_carry[total + gid] = s.y;
-    }
-    SMX_TSTAMP(ts1);
-    SMX_TACC(10, ts0, ts1);
-    // wrong-way test input (sensors.py:556-562, 581-586): the lane heading at the point of the
-    // nearest lane closest to the vehicle; junction lanes are exempt (:548-551)
-    double lane_heading = 0.0;
-    if (SMX_SKIP(a, 2048)) return;
-    const bool want_heading = !social && h.lane >= 0 && !m.lane_in_junction[h.lane] && !SMX_SKIP(a, 64);  // uniform in the team
-    if (want_heading) lane_heading = team_lane_heading_at_point<TEAM>(m, h.lane, s.x, s.y, h.dist);
-    SMX_TSTAMP(ts2);
-    SMX_TACC(11, ts1, ts2);
-    if (rank == 0) {
-      fi[(size_t)SMX_FI_LANE * total + gid] = h.lane;
-      fi[(size_t)SMX_FI_FLAGS * total + gid] =
-          (h.on_road ? SMX_FACT_ON_ROAD : 0) | ((h.corner_mask & 15) << SMX_FACT_CORNER_SHIFT);
-      a.st.facts_f64[(size_t)SMX_FF_LANE_DIST * total + gid] = h.dist;
-      a.st.facts_f64[(size_t)SMX_FF_LANE_HEADING * total + gid] = lane_heading;
-    }
-    return;
-  }
-  // ---- path seeds
-  if (flags & SMX_F_SOCIAL) return;
-  SMX_TSTAMP(ts3);
-  Top10 t;
-  LaneGuess guess;
-  SeedsCarry scy;
-  scy.valid = false;
-  if (a.seeds_carry != nullptr && !(flags & SMX_F_FIRST)) {
-    const int32_t* sc_ = a.st.seed_cache;
-    scy.qx = a.seeds_carry[gid];
-    scy.qy = a.seeds_carry[total + gid];
-    scy.d10 = a.seeds_carry[2 * total + gid];
-    scy.d1 = a.seeds_carry[3 * total + gid];
-    scy.prev_road = sc_[0 * total + gid];
-    scy.prev_lanes = sc_[4 * total + gid];
-#pragma unroll
-    for (int q = 0; q < SMX_SEED_LANES; ++q) scy.prev_start[q] = sc_[(size_t)(5 + q) * total + gid];
-    scy.valid = true;
-  }
-  const bool wp_on = (c.sensors & SMX_SENSOR_WAYPOINTS) != 0;
-  team_nearest10_carried<TEAM>(m, s.x, s.y, scy, t, guess);
-  if (a.seeds_carry != nullptr && rank == 0) {
-    a.seeds_carry[gid] = s.x;
-    a.seeds_carry[total + gid] = s.y;
-    a.seeds_carry[2 * total + gid] = t.idx[9] >= 0 ? t.d2[9] : -1.0;
-    a.seeds_carry[3 * total + gid] = t.idx[0] >= 0 ? t.d2[0] : -1.0;
-  }
-  SMX_TSTAMP(ts4);
-  SMX_TACC(12, ts3, ts4);
-  // what the controller (and the waypoints sensor) ask: paths at this pose with the agent's route
-  if (SMX_SKIP(a, 4096)) return;
-  Top10Scores sc;
-  if (SMX_SKIP(a, 256)) {
-#pragma unroll
-    for (int k = 0; k < 10; ++k) sc.rel[k] = 0.0;
-  } else {
-    sc = team_top10_heading_terms<TEAM>(m, t, s.heading);
-  }
-  SMX_TSTAMP(ts4b);
-  SMX_TACC(9, ts4, ts4b);
-  const PathSeeds seed = team_compute_path_seeds<TEAM, ROUTED>(m, s.x, s.y, s.heading, 5.0, true, t, sc, a.missions, (int)(gid % (size_t)c.num_vehicles), &guess);
-  // without the waypoints sensor the observation still takes the first waypoint of
-  // waypoint_paths(pose, lookahead=1, within_radius=length) for the trip meter (sensors.py:270-275,
-  // 349-351); TripMeterSensor.__init__ (sensors.py:885-898) asks the same on a new vehicle
-  int obs_start = -1, trip_start = -1;
-  if (!wp_on || (flags & SMX_F_FIRST)) {
-    // (within_radius = the vehicle's length, sensors.py:895: with dimensions bound the agent's own)
-    const double own_length = own_box_sized<SIZED>(a) ? vehicle_box(a, gid, true).length : SMX_CHASSIS_LENGTH;
-    const PathSeeds ts = team_compute_path_seeds<TEAM, false>(m, s.x, s.y, s.heading, own_length, false, t, sc, a.missions, 0, &guess);
-    trip_start = (ts.road >= 0) ? ts.start[0] : -1;
-    obs_start = trip_start;
-  }
-  SMX_TSTAMP(ts5);
-  SMX_TACC(13, ts4, ts5);
-  if (rank == 0) {
-    store_seeds(a, gid, total, seed);
-    fi[(size_t)SMX_FI_TRIP_START * total + gid] = (flags & SMX_F_FIRST) ? trip_start : -1;
-    fi[(size_t)SMX_FI_OBS_START * total + gid] = obs_start;
-  }
-  SMX_TSTAMP(ts6);
-  SMX_TACC(14, ts0, ts6);
-}
-
-// Register budgets (amdgpu_waves_per_eu): the split form runs on small batches, where at most two or
-// three wavefronts per SIMD exist anyway, and takes the ~160 registers it wants — capped at 128 it
-// spilled 136 B per lane and cost 10 us of 48 at 8 k vehicles, plus 9 MB of scratch write-back per
-// tick.  The back-to-back form (large batches) is capped at 128 registers: four wavefronts per
-// SIMD; five (96 registers, 276 B of spills) was 1.5x slower at 131 k vehicles.
-#ifndef SMX_SCAN_WAVES
-#define SMX_SCAN_WAVES 3
-#endif
-// ROUTED: the instance that knows fixed routes (smx_set_missions); batches without missions run the other one
-template <bool SPLIT, bool ROUTED = false>
-__global__ void __attribute__((amdgpu_waves_per_eu(SPLIT ? 2 : SMX_SCAN_WAVES, 8))) __launch_bounds__(SMX_BLOCK) k_scan(const KernelArgs a) {
-  const smx_config& c = a.cfg;
-  const MapDev& m = a.map;
-  const size_t total = (size_t)c.num_envs * c.num_vehicles;
-  // the two halves of the scan are independent: on small batches they run as different workgroups
-  // of one launch (even: road facts + lane heading, odd: lanepoint search + path seeds) and
-  // overlap in time; on large ones every workgroup does both, one after the other
-  const size_t gid = ((size_t)(SPLIT ? (blockIdx.x >> 1) : blockIdx.x) * SMX_BLOCK + threadIdx.x) / SMX_TEAM;
-  const int rank = team_rank<SMX_TEAM>();
-  if (gid >= total) return;
-  const int flags = a.st.flags[gid];
-  if (!(flags & SMX_F_ALIVE)) return;
-  if (a.first_only && !(flags & SMX_F_FIRST)) return;
-  if (SPLIT) {
-    if (blockIdx.x & 1)
-      scan_role<SMX_TEAM, ROUTED>(a, m, c, gid, total, rank, flags, 1);
-    else
-      scan_role<SMX_TEAM, ROUTED>(a, m, c, gid, total, rank, flags, 0);
-  } else {
-    scan_role<SMX_TEAM, ROUTED>(a, m, c, gid, total, rank, flags, 0);
-    scan_role<SMX_TEAM, ROUTED>(a, m, c, gid, total, rank, flags, 1);
-  }
-}
-
-// One half of the scan as a launch of its own (large batches): the road facts feed the observe role only and
-// the path seeds the waypoint kernels only, so the two go to different streams and each keeps the registers
-// it needs (the facts half alone fits more wavefronts per SIMD than the pair).
-// (TEAM: four lanes a vehicle when the batch fills the chip, eight up to SMX_SCAN_WIDE_MAX_VEHICLES on maps whose lanes
-// split: a quarter-full chip is bound by one team's latency, and the wider team's is the shorter)
-// (SIZED: per-agent dimensions, TickPlan::sized — the agent's own box in the corners, the reaches and the trip meter's lookup)
-template <int ROLE, bool ROUTED = false, int TEAM = SMX_TEAM_LARGE, bool SIZED = false>
-__global__ void __attribute__((amdgpu_waves_per_eu(ROLE == 0 ? 4 : 3, 8))) __launch_bounds__(SMX_BLOCK) k_scan_half(const KernelArgs a) {
-  const smx_config& c = a.cfg;
-  const size_t total = (size_t)c.num_envs * c.num_vehicles;
-  const size_t gid = launch_vehicle(a, ((size_t)blockIdx.x * SMX_BLOCK + threadIdx.x) / TEAM, total);
-  if (gid >= total) return;
-  const int flags = a.st.flags[gid];
-  if (!(flags & SMX_F_ALIVE)) return;
-  if (a.first_only && !(flags & SMX_F_FIRST)) return;
-  scan_role<TEAM, ROUTED, SIZED ? 1 : 0>(a, a.map, c, gid, total, team_rank<TEAM>(), flags, ROLE);
-}
-
-// k_scan_fast (large batches): one half of the scan with ONE lane per vehicle (smx_scan.h facts_one_lane /
-// seeds_one_lane: searches seeded from last tick's answers, two passes over per-lane candidate lists).  A vehicle it
-// cannot serve — no usable carry, a list overflow, the in-junction rule, stacked lanes — is appended to the slow list
-// and served by k_scan_half's teams afterwards: one such vehicle would otherwise hold its whole wavefront for the
-// length of the searches from scratch.
-template <int ROLE>
-__global__ void __launch_bounds__(SMX_BLOCK) k_scan_fast(const KernelArgs a) {
-  SMX_TSTAMP(span0);
-  __shared__ int cand_lds[(ROLE == 0 ? SMX_FACTS_CAND : SMX_SEEDS_CAND) * SMX_BLOCK];
-  const smx_config& c = a.cfg;
-  const MapDev& m = a.map;
-  const size_t total = (size_t)c.num_envs * c.num_vehicles;
-  const size_t gid = launch_vehicle(a, (size_t)blockIdx.x * SMX_BLOCK + threadIdx.x, total);
-  bool slow = false;
-  // every word whose address only needs the vehicle is loaded here, together and whatever the flags say (one round
-  // trip instead of flags -> pose -> carry one behind the other: two wavefronts per SIMD hide nothing)
-  const bool in_range = gid < total;
-  const size_t g = in_range ? gid : 0;
-  const int flags = a.st.flags[g];
-  const double sx_ = a.st.f64[(size_t)SMX_S_X * total + g], sy_ = a.st.f64[(size_t)SMX_S_Y * total + g],
-               sh_ = a.st.f64[(size_t)SMX_S_HEADING * total + g];
-  int32_t* fi = a.st.facts_i32;
-  FactsCarry fc;
-  SeedsCarry scy;
-  fc.valid = false;
-  scy.valid = false;
-  int prev_lane = -1;
-  if (ROLE == 0) {
-    fc.qx = a.facts_carry[g];
-    fc.qy = a.facts_carry[total + g];
-    fc.prev_dist = a.st.facts_f64[(size_t)SMX_FF_LANE_DIST * total + g];
-    prev_lane = fi[(size_t)SMX_FI_LANE * total + g];
-  } else {
-    const int32_t* sc_ = a.st.seed_cache;
-    scy.qx = a.seeds_carry[g];
-    scy.qy = a.seeds_carry[total + g];
-    scy.d10 = a.seeds_carry[2 * total + g];
-    scy.d1 = a.seeds_carry[3 * total + g];
-    scy.prev_road = sc_[0 * total + g];
-    scy.prev_lanes = sc_[4 * total + g];
-#pragma unroll
-    for (int q = 0; q < SMX_SEED_LANES; ++q) scy.prev_start[q] = sc_[(size_t)(5 + q) * total + g];
-  }
-  if (in_range && (flags & SMX_F_ALIVE) && (!a.first_only || (flags & SMX_F_FIRST))) {
-    int* cand = cand_lds + threadIdx.x;
-    const bool seeded = !(flags & SMX_F_FIRST);
-    if (ROLE == 0) {
-      const double cxs[4] = {-0.5, 0.5, 0.5, -0.5};
-      const double cys[4] = {0.5, 0.5, -0.5, -0.5};
-      double cx[4], cy[4];
-      const double ch = cos(sh_), sh = sin(sh_);
-      const bool social = (flags & SMX_F_SOCIAL) != 0;
-      // (the observer's own box: as in scan_role)
-      ObserverBox ob = {SMX_CHASSIS_LENGTH, SMX_CHASSIS_WIDTH, 2.0, SMX_POSE_SCAN_RADIUS};
-      if (dims_sized(a) && !social) ob = observer_box(a, gid, a.dagm_reach + 0.1);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        double qx = sx_ + cxs[q] * ob.width;
-        double qy = sy_ + cys[q] * ob.length;
-        cx[q] = sx_ + ch * (qx - sx_) + sh * (qy - sy_);
-        cy[q] = sy_ + -sh * (qx - sx_) + ch * (qy - sy_);
-      }
-      fc.valid = seeded && prev_lane >= 0;
-      RoadFacts h;
-      double lane_heading = 0.0;
-      bool served;
-      if (SMX_SKIP(a, 1 << 23)) {  // (developer ablation: the prologue and the stores only)
-        h.lane = prev_lane;
-        h.dist = fc.prev_dist + cx[0] * 1e-30;
-        h.on_road = true;
-        h.corner_mask = 15;
-        served = true;
-      } else {
-        served = facts_one_lane(m, sx_, sy_, ob.scan_radius, social ? 0 : 4, cx, cy, fc, a.dagm_reach + 0.1, cand, SMX_BLOCK,
-                                !social, h, lane_heading, ob.corner_reach);
-      }
-      if (served) {
-        a.facts_carry[gid] = sx_;
-        a.facts_carry[total + gid] = sy_;
-        fi[(size_t)SMX_FI_LANE * total + gid] = h.lane;
-        fi[(size_t)SMX_FI_FLAGS * total + gid] =
-            (h.on_road ? SMX_FACT_ON_ROAD : 0) | ((h.corner_mask & 15) << SMX_FACT_CORNER_SHIFT);
-        a.st.facts_f64[(size_t)SMX_FF_LANE_DIST * total + gid] = h.dist;
-        a.st.facts_f64[(size_t)SMX_FF_LANE_HEADING * total + gid] = lane_heading;
-      } else {
-        slow = true;
-      }
-    } else if (!(flags & SMX_F_SOCIAL)) {
-      scy.valid = seeded;
-      PathSeeds one;
-      double d1sq = -1.0;
-      if (seeds_one_lane(m, sx_, sy_, sh_, 5.0, scy, cand, SMX_BLOCK, one, d1sq)) {
-        a.seeds_carry[gid] = sx_;
-        a.seeds_carry[total + gid] = sy_;
-        a.seeds_carry[2 * total + gid] = -1.0;  // (the tenth nearest was not looked for)
-        a.seeds_carry[3 * total + gid] = d1sq;
-        store_seeds(a, gid, total, one);
-        fi[(size_t)SMX_FI_TRIP_START * total + gid] = -1;  // (only a new vehicle or a batch without the waypoints
-        fi[(size_t)SMX_FI_OBS_START * total + gid] = -1;   //  sensor asks these: neither comes here)
-      } else {
-        // its seeds, walks and rows are the slow chain's (k_scan_listed -> k_waypoints_listed, beside the tick's main
-        // chain): k_wp_walk and k_waypoints_emit pass over the vehicle
-        slow = true;
-      }
-      if (a.seed_pending != nullptr) a.seed_pending[gid] = slow ? 1 : 0;
-    }
-  }
-  // the wavefront's slow vehicles, appended with one atomic
-  const unsigned long long mask = __ballot(slow);
-  if (mask != 0ull) {
-    const int lane = threadIdx.x & 63;
-    int base = 0;
-    if (lane == __ffsll((long long)mask) - 1) base = atomicAdd(a.slow_count, __popcll(mask));
-    base = __shfl(base, __ffsll((long long)mask) - 1);
-    if (slow) a.slow_list[base + __popcll(mask & ((1ull << lane) - 1ull))] = (int32_t)gid;
-  }
-  SMX_TSTAMP(span1);
-  SMX_TSPAN(ROLE == 1 ? 1 : 2, span0, span1);
-}
-
-// k_scan_half over a list whose length is only known on the device (the slow list): a fixed grid, teams striding it
-// (TEAM: four lanes a vehicle where the lists are long — maps whose lanes split —, eight where they hold a few
-// hundred vehicles and the kernel is one team's latency at the end of the slow chain: 70 against 55 us)
-template <int ROLE, bool ROUTED = false, int TEAM = SMX_TEAM_LARGE, bool SIZED = false>
-__global__ void __attribute__((amdgpu_waves_per_eu(ROLE == 0 ? 4 : 3, 8))) __launch_bounds__(SMX_BLOCK) k_scan_listed(const KernelArgs a) {
-  const smx_config& c = a.cfg;
-  const size_t total = (size_t)c.num_envs * c.num_vehicles;
-  const int count = *a.slow_count;
-  constexpr int VPB = SMX_BLOCK / TEAM;
-  for (int i = (int)blockIdx.x * VPB + (int)threadIdx.x / TEAM; i < count; i += (int)gridDim.x * VPB) {
-    const size_t gid = (size_t)a.slow_list[i];
-    const int flags = a.st.flags[gid];
-    scan_role<TEAM, ROUTED, SIZED ? 1 : 0>(a, a.map, c, gid, total, team_rank<TEAM>(), flags, ROLE);
-  }
 }
 
 // =================================================================================
@@ -3630,585 +3319,6 @@ __device__ __forceinline__ void commit_role(const KernelArgs& a, const int block
 
 
 // =================================================================================
-// OGM role: occupancy grid map sensor (OGMSensor, sensors.py:719-758): one wavefront per observing
-// vehicle.  The H x W byte tile is built in LDS (lane j rasterises env-mate j's footprint over the
-// few pixels its bounding rectangle touches) and leaves as full 16-byte pieces — the kernel is
-// bound by its own 4 KiB-per-agent output stream.  Pixel rule (substitution for the Panda3D
-// orthographic render, renderer.py:325-395): a pixel is 255 iff its centre lies inside a vehicle's
-// oriented chassis rectangle; view centred on the vehicle, +row = behind, row 0 = ahead
-// (np.flipud, sensors.py:748), extent width*res x height*res (renderer.py:384-385).
-// =================================================================================
-struct OgmMate {
-  double cx, cy, vfx, vfy, vrx, vry;  // centre and axes of the footprint in the ego frame
-  int c0, r0, bw, n_px;               // pixel rectangle: first column / row, width, pixel count
-};
-
-// Vehicle `og`'s footprint in the frame of the observer at (ex0, ey0) with right axis (rx, ry) and forward axis
-// (fx, fy), and the pixel rectangle of a W x H grid that can hold it; false (q untouched): the rectangle misses the view.
-__device__ __forceinline__ bool ogm_mate_footprint(const KernelArgs& a, const size_t og, const size_t total, const int W, const int H,
-                                                   const double res, const double ex0, const double ey0, const double rx, const double ry,
-                                                   const double fx, const double fy, OgmMate& q) {
-  const VehBox box = vehicle_box(a, og);
-  const double hl = 0.5 * box.length, hw = 0.5 * box.width;
-  const double vx = a.st.f64[(size_t)SMX_S_X * total + og], vy = a.st.f64[(size_t)SMX_S_Y * total + og];
-  const double vh = wrap_heading(a.st.f64[(size_t)SMX_S_HEADING * total + og]);
-  const double dx = vx - ex0, dy = vy - ey0;
-  const double cx = dx * rx + dy * ry, cy = dx * fx + dy * fy;  // centre in the ego frame
-  // the mate's axes in the ego frame from each vehicle's own cos / sin (the rule k_ogm_env shares)
-  const double cm = cos(vh), sm = sin(vh);
-  const double vfx = cm * ry - sm * rx, vfy = sm * ry + cm * rx, vrx = cm * rx + sm * ry, vry = sm * rx - cm * ry;
-  const double ext_x = fabs(vfx) * hl + fabs(vrx) * hw, ext_y = fabs(vfy) * hl + fabs(vry) * hw;
-  // pixel centre (r, col): x = (col + 0.5 - W/2) res, y = (H/2 - (r + 0.5)) res
-  int c0 = (int)floor((cx - ext_x) / res + 0.5 * W - 0.5) - 1, c1 = (int)ceil((cx + ext_x) / res + 0.5 * W - 0.5) + 1;
-  int r0 = (int)floor(0.5 * H - 0.5 - (cy + ext_y) / res) - 1, r1 = (int)ceil(0.5 * H - 0.5 - (cy - ext_y) / res) + 1;
-  c0 = max(c0, 0);
-  r0 = max(r0, 0);
-  c1 = min(c1, W - 1);
-  r1 = min(r1, H - 1);
-  if (c0 > c1 || r0 > r1) return false;
-  q.cx = cx;
-  q.cy = cy;
-  q.vfx = vfx;
-  q.vfy = vfy;
-  q.vrx = vrx;
-  q.vry = vry;
-  q.c0 = c0;
-  q.r0 = r0;
-  q.bw = c1 - c0 + 1;
-  q.n_px = (c1 - c0 + 1) * (r1 - r0 + 1);
-  return true;
-}
-
-// ... drawn by the workgroup's lanes over the rectangle's pixels: VALUE where the pixel centre lies inside the chassis
-// of vehicle `og` (the rectangle is clamped to the view and walked whole, whatever the vehicle's size)
-template <int VALUE>
-__device__ __forceinline__ void ogm_draw_mate(const KernelArgs& a, const size_t og, unsigned char* tile, const OgmMate& q, const int W,
-                                              const int H, const double res) {
-  const VehBox box = vehicle_box(a, og);
-  const double hl = 0.5 * box.length, hw = 0.5 * box.width;
-  for (int p = (int)threadIdx.x; p < q.n_px; p += SMX_BLOCK) {
-    const int r = q.r0 + p / q.bw, col = q.c0 + p % q.bw;
-    const double py = (0.5 * H - (r + 0.5)) * res - q.cy;
-    const double px = (col + 0.5 - 0.5 * W) * res - q.cx;
-    if (fabs(px * q.vfx + py * q.vfy) <= hl && fabs(px * q.vrx + py * q.vry) <= hw) tile[r * W + col] = VALUE;
-  }
-}
-
-__device__ __forceinline__ void ogm_role(const KernelArgs& a, const int block) {
-  extern __shared__ __align__(16) unsigned char tile[];
-  const smx_config& c = a.cfg;
-  const size_t total = (size_t)c.num_envs * c.num_vehicles;
-  const size_t gid = (size_t)block;
-  if (gid >= total) return;
-  const int flags = a.st.flags[gid];
-  const bool live = (flags & SMX_F_ALIVE) && !(flags & SMX_F_SOCIAL) && (!a.first_only || (flags & SMX_F_FIRST));
-  if (!live) return;  // uniform for the whole workgroup
-  const int W = c.ogm_width, H = c.ogm_height;
-  const int n_veh = c.num_vehicles;
-  const int env = (int)(gid / n_veh);
-  const int bytes = W * H;
-  for (int k = threadIdx.x; k < bytes / 4; k += SMX_BLOCK) reinterpret_cast<int*>(tile)[k] = 0;
-  __syncthreads();
-  const double res = c.ogm_resolution;
-  const double ex0 = SF(SMX_S_X), ey0 = SF(SMX_S_Y), eh = wrap_heading(SF(SMX_S_HEADING));
-  const double rx = cos(eh), ry = sin(eh);    // ego right axis
-  const double fx = -sin(eh), fy = cos(eh);   // ego forward axis
-  // Pass 1, lane j = env-mate j: its footprint in the ego frame and the pixel rectangle that can hold
-  // it.  Pass 2: the mates whose rectangle meets the view (a ballot; typically a handful of the env)
-  // are drawn one after the other with the wavefront's lanes over the rectangle's pixels — a lane per
-  // mate would make every lane wait for the mate with the most pixels while most lanes draw nothing.
-  __shared__ OgmMate mates[SMX_BLOCK];
-  for (int base = 0; base < n_veh; base += SMX_BLOCK) {
-    const int j = base + (int)threadIdx.x;
-    bool in_view = false;
-    if (j < n_veh) {
-      const size_t og = (size_t)env * n_veh + j;
-      if (a.st.flags[og] & SMX_F_ALIVE) in_view = ogm_mate_footprint(a, og, total, W, H, res, ex0, ey0, rx, ry, fx, fy, mates[threadIdx.x]);
-    }
-    unsigned long long todo = __ballot(in_view);
-    __syncthreads();
-    while (todo != 0ull) {  // uniform
-      const int idx = __ffsll((long long)todo) - 1;
-      const OgmMate q = mates[idx];
-      todo &= todo - 1ull;
-      ogm_draw_mate<255>(a, (size_t)env * n_veh + base + idx, tile, q, W, H, res);
-    }
-    __syncthreads();  // before the stage is reused (envs of more than 64 vehicles do not exist, but the loop is general)
-  }
-  __syncthreads();
-  static_assert(SMX_BLOCK == 64, "ogm_store_tile: the workgroup is one wavefront");
-  int4* dst = reinterpret_cast<int4*>(a.out.ogm + gid * (size_t)bytes);
-  ogm_store_tile(reinterpret_cast<const int4*>(tile), dst, a.ogm_mask ? a.ogm_mask + gid * smx_ogm_mask_words((size_t)bytes) : nullptr,
-                 bytes / 16, (int)threadIdx.x);
-}
-
-// k_ogm_env (large batches): the same tiles, one workgroup of four wavefronts per ENV.  The env's poses are
-// loaded once, with one cos / sin pair per vehicle (a workgroup per observer reloads all its mates and takes
-// a sine and a cosine per mate: n x n of each per env); every wavefront then builds the tiles of a quarter of
-// the observers, one after the other, in its own LDS tile.
-struct OgmPose {
-  double x, y, ch, sh;  // centre, cos / sin of the wrapped heading
-  int alive, observes;
-};
-#ifndef SMX_SIDE_PRIO  // developer: side streams that get the default priority instead of the lowest (bit i = side i)
-#define SMX_SIDE_PRIO 0
-#endif
-// orders a wavefront's own LDS traffic for the compiler (the hardware keeps a wavefront's LDS operations in order)
-#define SMX_WAVE_SYNC()                                   \
-  do {                                                    \
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
-    __builtin_amdgcn_wave_barrier();                      \
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
-  } while (0)
-// a double of another lane of the wavefront (lane index uniform): two v_readlane_b32
-__device__ __forceinline__ double readlane_f64(double v, int src) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), src);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-// OBS observers per wavefront at a time (two while the env has at most 32 vehicles and eight tiles fit the LDS a
-// workgroup may have): lane = (observer, env-mate) for the footprints' rectangles, so that a wavefront of 32-vehicle
-// envs is full; the footprints in view are then drawn two at a time, each by a half wavefront of 8 rows x 4 columns
-// (a car ahead is 3 x 6 pixels at 0.78 m per pixel: one step), its record fetched from the lane that holds it with
-// ds_bpermute.  390 -> 1xx vector instructions per tile (a third of the headline tick's were this kernel's).
-// (SIZED: per-vehicle dimensions are bound, smx_set_social_history_dims — a compile-time choice of the launch plan's: as a
-// branch on the bound pointer the extents cost the kernel without them ten registers and a wavefront per SIMD,
-// profiles/r17_vehicle_dims_resources.txt)
-template <int OBS, bool SIZED>
-__global__ void __attribute__((amdgpu_waves_per_eu(4, 8))) __launch_bounds__(SMX_OGM_WAVES * 64) k_ogm_env(const KernelArgs a) {
-  SMX_TSTAMP(span0);
-  extern __shared__ __align__(16) unsigned char tiles[];  // [SMX_OGM_WAVES][OBS][H * W]
-  __shared__ OgmPose pose[SMX_BLOCK];
-  __shared__ unsigned char observers[SMX_BLOCK];  // the env's observing slots, compacted: the wavefronts share them evenly
-  __shared__ int n_observers;                     // however many agents of the env are gone
-  const smx_config& c = a.cfg;
-  const int n_veh = c.num_vehicles;
-  const size_t total = (size_t)c.num_envs * n_veh;
-  const int env = (int)blockIdx.x;
-  const int W = c.ogm_width, H = c.ogm_height, bytes = W * H;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if ((int)threadIdx.x < n_veh) {
-    const size_t gid = (size_t)env * n_veh + threadIdx.x;
-    const int flags = a.st.flags[gid];
-    OgmPose p;
-    p.alive = (flags & SMX_F_ALIVE) ? 1 : 0;
-    p.observes = ((flags & SMX_F_ALIVE) && !(flags & SMX_F_SOCIAL) && (!a.first_only || (flags & SMX_F_FIRST))) ? 1 : 0;
-    p.x = SF(SMX_S_X);
-    p.y = SF(SMX_S_Y);
-    const double h = wrap_heading(SF(SMX_S_HEADING));
-    p.ch = cos(h);
-    p.sh = sin(h);
-    pose[threadIdx.x] = p;
-  }
-  if (wave == 0) {  // (n_veh <= 64: the first wavefront sees every slot)
-    const bool obs_here = lane < n_veh && pose[lane].observes;
-    const unsigned long long om = __ballot(obs_here);
-    if (obs_here) observers[__popcll(om & ((1ull << lane) - 1ull))] = (unsigned char)lane;
-    if (lane == 0) n_observers = __popcll(om);
-  }
-  __syncthreads();
-  unsigned char* tile = tiles + (size_t)wave * OBS * bytes;
-  const double res = c.ogm_resolution;
-  const double inv_res = 1.0 / res;  // for the pixel RECTANGLES only (an enumeration bound with a margin on every
-                                     // side); the pixel test itself keeps the oracle's arithmetic
-  const int half = lane >> 5, in_half = lane & 31;
-  const int mate = OBS == 2 ? in_half : lane;
-  const int mate_clamped = min(mate, n_veh - 1);  // (every lane computes; lanes past the env's vehicles are masked below)
-  // this lane's mate's half extents: the sedan's, or with dimensions bound (smx_set_social_history_dims) its own — a
-  // drawing step then fetches them from the lane that holds the footprint, as it fetches the rest of the record
-  const VehBox mate_box = vehicle_box(a, (size_t)env * n_veh + mate_clamped, SIZED);
-  const double hl = 0.5 * mate_box.length, hw = 0.5 * mate_box.width;
-  const int lr = in_half >> 2, lc = in_half & 3;  // this lane's pixel of a drawing step: 8 rows x 4 columns per half
-  // pixel centre (r, col): x = (col + 0.5 - W/2) res, y = (H/2 - (r + 0.5)) res; the sums in front of `res` are
-  // exact in any order (integers and halves), so the constants are folded
-  const double col_bias = 0.5 - 0.5 * W, row_bias = 0.5 * H - 0.5;
-  const int n_obs = n_observers;
-  const int per_round = SMX_OGM_WAVES * OBS;
-  const int rounds = (n_obs + per_round - 1) / per_round;
-  const size_t mask_words = smx_ogm_mask_words((size_t)bytes);
-  // Each wavefront owns its tiles: inside the loop only lanes of ONE wavefront exchange data through LDS, whose
-  // operations a wavefront issues in order — a scheduling fence is all that is needed (four workgroup barriers per
-  // round made the four wavefronts wait for the slowest one's rectangles)
-#pragma nounroll
-  for (int it = 0; it < rounds; ++it) {
-    const int turn0 = (it * SMX_OGM_WAVES + wave) * OBS;  // uniform in the wavefront
-    const int n_live = min(OBS, n_obs - turn0);
-    if (n_live <= 0) break;  // (turns grow with `it`)
-    for (int k = lane; k < n_live * (bytes / 16); k += 64) reinterpret_cast<int4*>(tile)[k] = make_int4(0, 0, 0, 0);
-    const int my_turn = turn0 + (OBS == 2 ? half : 0);
-    const bool live = my_turn < n_obs;
-    const int obs = (int)observers[live ? my_turn : turn0];
-    // the footprint of vehicle `mate` in this observer's frame stays in this lane's registers (no LDS copy of it)
-    const OgmPose e = pose[obs];
-    const OgmPose v = pose[mate_clamped];
-    const double rx = e.ch, ry = e.sh;   // ego right axis
-    const double fx = -e.sh, fy = e.ch;  // ego forward axis
-    const double dx = v.x - e.x, dy = v.y - e.y;
-    const double cx = dx * rx + dy * ry, cy = dx * fx + dy * fy;  // centre in the ego frame
-    const double cm = v.ch, sm = v.sh;
-    const double vfx = cm * ry - sm * rx, vfy = sm * ry + cm * rx, vrx = cm * rx + sm * ry, vry = sm * rx - cm * ry;
-    const double ext_x = fabs(vfx) * hl + fabs(vrx) * hw, ext_y = fabs(vfy) * hl + fabs(vry) * hw;
-    // (a pixel centre inside the footprint lies inside its bounding box: columns ceil(lo) .. floor(hi).  The bounds
-    // are rounded — a dozen operations on numbers below 1e3 pixels, errors of 1e-12 — and the pixel test accepts a
-    // centre its own rounding puts on the edge: a millionth of a pixel on every side covers both.  A whole pixel of
-    // margin made a car ahead, 3 x 6 pixels, a rectangle of 5 x 8.)
-    const double slack = 1e-6;
-    // (clamped as doubles first: a mate far away must not overflow the conversion)
-    const double c_lo = fmax((cx - ext_x) * inv_res + 0.5 * W - 0.5 - slack, -1.0), c_hi = fmin((cx + ext_x) * inv_res + 0.5 * W - 0.5 + slack, (double)W);
-    const double r_lo = fmax(0.5 * H - 0.5 - (cy + ext_y) * inv_res - slack, -1.0), r_hi = fmin(0.5 * H - 0.5 - (cy - ext_y) * inv_res + slack, (double)H);
-    const int c0 = max((int)ceil(c_lo), 0), c1 = min((int)floor(c_hi), W - 1);
-    const int r0 = max((int)ceil(r_lo), 0), r1 = min((int)floor(r_hi), H - 1);
-    const int bw = c1 - c0 + 1, bh = r1 - r0 + 1;
-    const bool in_view = live && mate < n_veh && v.alive != 0 && bw > 0 && bh > 0;
-    unsigned long long todo = __ballot(in_view);
-    SMX_WAVE_SYNC();
-    while (todo != 0ull) {  // uniform in the wavefront: two footprints per turn, one per half
-      const int s0 = __ffsll((long long)todo) - 1;
-      todo &= todo - 1ull;
-      const int s1 = todo != 0ull ? __ffsll((long long)todo) - 1 : s0;
-      const bool two = todo != 0ull;
-      todo &= todo - 1ull;  // (0 & anything = 0)
-      const int src = half ? s1 : s0;
-      const bool drawing = half == 0 || two;
-      const double qcx = __shfl(cx, src), qcy = __shfl(cy, src);
-      const double qvfx = __shfl(vfx, src), qvfy = __shfl(vfy, src), qvrx = __shfl(vrx, src), qvry = __shfl(vry, src);
-      const int qc0 = __shfl(c0, src), qr0 = __shfl(r0, src), qbw = __shfl(bw, src), qbh = __shfl(bh, src);
-      double qhl = 0.5 * SMX_CHASSIS_LENGTH, qhw = 0.5 * SMX_CHASSIS_WIDTH;
-      if constexpr (SIZED) qhl = __shfl(hl, src), qhw = __shfl(hw, src);
-      unsigned char* dst_tile = tile + (OBS == 2 ? (src >> 5) * bytes : 0);
-      const int bh_max = max(__builtin_amdgcn_readlane(bh, s0), __builtin_amdgcn_readlane(bh, s1));
-      const int bw_max = max(__builtin_amdgcn_readlane(bw, s0), __builtin_amdgcn_readlane(bw, s1));
-      // (one step nearly always: kept from the loop optimiser, which interleaved four column steps and paid two
-      // dozen register copies per footprint for it)
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-      for (int rr = 0; rr < bh_max; rr += 8) {
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-        for (int cc = 0; cc < bw_max; cc += 4) {
-          const int dr = rr + lr, dc = cc + lc;
-          const int r = qr0 + dr, col = qc0 + dc;
-          const double py = (row_bias - (double)r) * res - qcy;
-          const double px = ((double)col + col_bias) * res - qcx;
-          if (drawing && dr < qbh && dc < qbw && fabs(px * qvfx + py * qvfy) <= qhl && fabs(px * qvrx + py * qvry) <= qhw)
-            dst_tile[r * W + col] = 255;
-        }
-      }
-    }
-    SMX_WAVE_SYNC();
-    for (int t = 0; t < n_live; ++t) {
-      const int4* src_tile = reinterpret_cast<const int4*>(tile + (size_t)t * bytes);
-      const size_t gid = (size_t)env * n_veh + (int)observers[turn0 + t];
-      int4* dst = reinterpret_cast<int4*>(a.out.ogm + gid * (size_t)bytes);
-      ogm_store_tile(src_tile, dst, a.ogm_mask ? a.ogm_mask + gid * mask_words : nullptr, bytes / 16, lane);
-    }
-    SMX_WAVE_SYNC();  // the tiles are reused
-  }
-  SMX_TSTAMP(span1);
-  SMX_TSPAN(6, span0, span1);
-}
-
-// =================================================================================
-// DAGM role: drivable-area grid map (DrivableAreaGridMapSensor, sensors.py:675-716): one workgroup per
-// observing vehicle, the tile in LDS.  The reference renders the road mesh (lane centre lines
-// buffered by half the lane width) through the OGM's camera; here a pixel is 255 when its centre
-// lies within half a lane width of a segment of a lane centre line (DESIGN.md "Substitutions").
-// The segment grid only prunes: a segment that can reach the view lies within the view's
-// circumscribed circle grown by the widest half width, so its bounding box meets the visited cells.
-// Wavefronts take segments, lanes the pixels of a segment's bounding box; a segment listed in
-// several cells is drawn again (same value).
-// =================================================================================
-// The road layer of a W x H tile for the observer at (ex0, ey0): VALUE where the pixel centre lies within half a lane
-// width of a segment (wavefronts over the segments of the grid cells the view can reach, lanes over a segment's pixels).
-template <int VALUE>
-__device__ __forceinline__ void road_layer(const KernelArgs& a, unsigned char* tile, const int W, const int H, const double res,
-                                           const double ex0, const double ey0, const double rx, const double ry, const double fx,
-                                           const double fy) {
-  const MapDev& m = a.map;
-  const double vw = 0.5 * W * res, vh = 0.5 * H * res;
-  const double reach = sqrt(vw * vw + vh * vh) + a.dagm_reach + 1e-6;
-  int cx0 = (int)floor((ex0 - reach - m.sg_x0) / m.sg_cell), cx1 = (int)floor((ex0 + reach - m.sg_x0) / m.sg_cell);
-  int cy0 = (int)floor((ey0 - reach - m.sg_y0) / m.sg_cell), cy1 = (int)floor((ey0 + reach - m.sg_y0) / m.sg_cell);
-  cx0 = max(cx0, 0);
-  cy0 = max(cy0, 0);
-  cx1 = min(cx1, m.sg_nx - 1);
-  cy1 = min(cy1, m.sg_ny - 1);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, n_waves = SMX_BLOCK >> 6;
-  for (int gy = cy0; gy <= cy1; ++gy) {
-    if (cx0 > cx1) break;
-    const int row = gy * m.sg_nx;
-    // cells of one grid row are contiguous in the member array
-    const int m0 = m.sg_off[row + cx0], m1 = m.sg_off[row + cx1 + 1];
-    for (int k = m0 + wave; k < m1; k += n_waves) {
-      const smx_seg_rec s = m.sg_rec[k];
-      const double hw = 0.5 * m.lane_width[s.lane];
-      // end points in the ego frame (x to the right, y ahead)
-      const double d1x = s.x1 - ex0, d1y = s.y1 - ey0, d2x = s.x2 - ex0, d2y = s.y2 - ey0;
-      const double ax = d1x * rx + d1y * ry, ay = d1x * fx + d1y * fy;
-      const double bx = d2x * rx + d2y * ry, by = d2x * fx + d2y * fy;
-      // pixel centre (r, col): x = (col + 0.5 - W/2) res, y = (H/2 - (r + 0.5)) res
-      int c0 = (int)floor((fmin(ax, bx) - hw) / res + 0.5 * W - 0.5) - 1, c1 = (int)ceil((fmax(ax, bx) + hw) / res + 0.5 * W - 0.5) + 1;
-      int r0 = (int)floor(0.5 * H - 0.5 - (fmax(ay, by) + hw) / res) - 1, r1 = (int)ceil(0.5 * H - 0.5 - (fmin(ay, by) - hw) / res) + 1;
-      c0 = max(c0, 0);
-      r0 = max(r0, 0);
-      c1 = min(c1, W - 1);
-      r1 = min(r1, H - 1);
-      if (c0 > c1 || r0 > r1) continue;
-      const int bw = c1 - c0 + 1, n_px = bw * (r1 - r0 + 1);
-      for (int q = lane; q < n_px; q += 64) {
-        const int r = r0 + q / bw, col = c0 + q % bw;
-        const double px = (col + 0.5 - 0.5 * W) * res, py = (0.5 * H - (r + 0.5)) * res;
-        if (seg_point_dist2(px, py, ax, ay, bx, by) <= hw * hw) tile[r * W + col] = VALUE;
-      }
-    }
-  }
-}
-
-__device__ __forceinline__ void dagm_role(const KernelArgs& a, const int block) {
-  extern __shared__ __align__(16) unsigned char tile[];
-  const smx_config& c = a.cfg;
-  const size_t total = (size_t)c.num_envs * c.num_vehicles;
-  const size_t gid = (size_t)block;
-  if (gid >= total) return;
-  const int flags = a.st.flags[gid];
-  const bool live = (flags & SMX_F_ALIVE) && !(flags & SMX_F_SOCIAL) && (!a.first_only || (flags & SMX_F_FIRST));
-  if (!live) return;  // uniform for the whole workgroup
-  const int W = c.dagm_width, H = c.dagm_height;
-  const int bytes = W * H;
-  for (int k = threadIdx.x; k < bytes / 4; k += SMX_BLOCK) reinterpret_cast<int*>(tile)[k] = 0;
-  __syncthreads();
-  const double res = c.dagm_resolution;
-  const double ex0 = SF(SMX_S_X), ey0 = SF(SMX_S_Y), eh = wrap_heading(SF(SMX_S_HEADING));
-  const double rx = cos(eh), ry = sin(eh);    // ego right axis
-  const double fx = -sin(eh), fy = cos(eh);   // ego forward axis
-  road_layer<255>(a, tile, W, H, res, ex0, ey0, rx, ry, fx, fy);
-  __syncthreads();
-  int4* dst = reinterpret_cast<int4*>(a.out.dagm + gid * (size_t)bytes);
-  for (int k = threadIdx.x; k < bytes / 16; k += SMX_BLOCK) dst[k] = reinterpret_cast<const int4*>(tile)[k];
-}
-
-// =================================================================================
-// RGB role: the top-down RGB camera (RGBSensor, sensors.py:761-794; the image is defined in include/smx.h): one
-// workgroup per observing vehicle, a tile of one CLASS byte a pixel in LDS — 0 nothing, 1 road, 2 social vehicle,
-// 3 agent vehicle, the highest class that holds — built from the DAGM's road layer and the OGM's footprints, the very
-// functions those roles call.  The layers are drawn lowest class first with a workgroup barrier between them, so a
-// pixel is only ever raised and plain stores do (no read-modify-write, no race that could lose the larger class).
-// Copy-out: a thread turns 16 class bytes into the 48 bytes of their pixels and stores them as three 16-byte vectors;
-// thread k's 48 bytes follow thread k - 1's, so the workgroup's stores fill one contiguous span of the image, which is
-// written exactly once.
-// =================================================================================
-#define SMX_RGB_LUT_R 0xD2C05000u   // byte c = the red byte of class c:      0, 80, 192, 210 (colors.py:58-62)
-#define SMX_RGB_LUT_GB 0x1EC05000u  // ... its green and its blue byte:       0, 80, 192,  30
-__device__ __forceinline__ unsigned rgb_of_class(const unsigned cls) {  // R | G << 8 | B << 16
-  const unsigned r = (SMX_RGB_LUT_R >> (8u * cls)) & 0xffu, gb = (SMX_RGB_LUT_GB >> (8u * cls)) & 0xffu;
-  return r | (gb << 8) | (gb << 16);
-}
-
-__device__ __forceinline__ void rgb_role(const KernelArgs& a, const int block) {
-  extern __shared__ __align__(16) unsigned char tile[];
-  const smx_config& c = a.cfg;
-  const size_t total = (size_t)c.num_envs * c.num_vehicles;
-  const size_t gid = (size_t)block;
-  if (gid >= total) return;
-  const int flags = a.st.flags[gid];
-  const bool live = (flags & SMX_F_ALIVE) && !(flags & SMX_F_SOCIAL) && (!a.first_only || (flags & SMX_F_FIRST));
-  if (!live) return;  // uniform for the whole workgroup
-  const int W = c.rgb_width, H = c.rgb_height;
-  const int n_veh = c.num_vehicles;
-  const int env = (int)(gid / n_veh);
-  const int bytes = W * H;
-  for (int k = threadIdx.x; k < bytes / 4; k += SMX_BLOCK) reinterpret_cast<int*>(tile)[k] = 0;
-  __syncthreads();
-  const double res = c.rgb_resolution;
-  const double ex0 = SF(SMX_S_X), ey0 = SF(SMX_S_Y), eh = wrap_heading(SF(SMX_S_HEADING));
-  const double rx = cos(eh), ry = sin(eh);    // ego right axis
-  const double fx = -sin(eh), fy = cos(eh);   // ego forward axis
-  road_layer<1>(a, tile, W, H, res, ex0, ey0, rx, ry, fx, fy);
-  __syncthreads();
-  // the env's alive vehicles, the observer among them: the social ones (class 2), then the agents (class 3)
-  __shared__ OgmMate mates[SMX_BLOCK];
-  for (int cls = 2; cls <= 3; ++cls) {
-    for (int base = 0; base < n_veh; base += SMX_BLOCK) {
-      const int j = base + (int)threadIdx.x;
-      bool in_view = false;
-      if (j < n_veh) {
-        const size_t og = (size_t)env * n_veh + j;
-        const int f = a.st.flags[og];
-        if ((f & SMX_F_ALIVE) && ((f & SMX_F_SOCIAL) != 0) == (cls == 2))
-          in_view = ogm_mate_footprint(a, og, total, W, H, res, ex0, ey0, rx, ry, fx, fy, mates[threadIdx.x]);
-      }
-      unsigned long long todo = __ballot(in_view);
-      __syncthreads();
-      while (todo != 0ull) {  // uniform
-        const int idx = __ffsll((long long)todo) - 1;
-        const OgmMate q = mates[idx];
-        todo &= todo - 1ull;
-        const size_t og = (size_t)env * n_veh + base + idx;
-        if (cls == 2)
-          ogm_draw_mate<2>(a, og, tile, q, W, H, res);
-        else
-          ogm_draw_mate<3>(a, og, tile, q, W, H, res);
-      }
-      __syncthreads();  // the stage is reused, and the next class goes on top of this one
-    }
-  }
-  uint4* dst = reinterpret_cast<uint4*>(a.rgb + gid * (size_t)bytes * 3);
-  for (int k = threadIdx.x; k < bytes / 16; k += SMX_BLOCK) {
-    const uint4 cls4 = reinterpret_cast<const uint4*>(tile)[k];
-    const unsigned cw[4] = {cls4.x, cls4.y, cls4.z, cls4.w};
-    unsigned w[12];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {  // four pixels -> twelve bytes: R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
-      const unsigned p0 = rgb_of_class(cw[g] & 3u), p1 = rgb_of_class((cw[g] >> 8) & 3u);
-      const unsigned p2 = rgb_of_class((cw[g] >> 16) & 3u), p3 = rgb_of_class((cw[g] >> 24) & 3u);
-      w[3 * g] = p0 | (p1 << 24);
-      w[3 * g + 1] = (p1 >> 8) | (p2 << 16);
-      w[3 * g + 2] = (p2 >> 16) | (p3 << 8);
-    }
-    dst[3 * k] = make_uint4(w[0], w[1], w[2], w[3]);
-    dst[3 * k + 1] = make_uint4(w[4], w[5], w[6], w[7]);
-    dst[3 * k + 2] = make_uint4(w[8], w[9], w[10], w[11]);
-  }
-}
-
-// =================================================================================
-// lidar role: lidar sensor (LidarSensor sensors.py:797-827, Lidar lidar.py:58-134): one wavefront per
-// observing vehicle, lanes over rays.  Ray i = [origin, origin + base_ray[i]], origin = vehicle
-// position + (0, 0, 1); base rays come from the host (they do not rotate with the vehicle,
-// lidar.py:109-113).  pybullet rayTestBatch is substituted by exact ray / oriented-box and
-// ray / ground-plane intersection (DESIGN.md "Substitutions"); a miss reports (inf, inf, inf).
-// =================================================================================
-struct LidarPose {
-  double x, y, fx, fy;  // centre, forward axis
-  int slot;             // its slot in the env (the compacted list's order is not the env's)
-};
-
-// (SIZED: per-vehicle dimensions, smx_set_social_history_dims — 1 bound, 0 not: the launches of its own, for which the
-// launch plan picks the instantiation; -1: the role inside k_sensors / k_first, which asks the argument block)
-template <int SIZED>
-__device__ __forceinline__ void lidar_role(const KernelArgs& a, const int block) {
-  __shared__ LidarPose mates[SMX_BLOCK];
-  const bool sized = SIZED < 0 ? dims_sized(a) : SIZED != 0;
-  const smx_config& c = a.cfg;
-  const size_t total = (size_t)c.num_envs * c.num_vehicles;
-  const size_t gid = (size_t)block;
-  if (gid >= total) return;
-  const int flags = a.st.flags[gid];
-  const bool live = (flags & SMX_F_ALIVE) && !(flags & SMX_F_SOCIAL) && (!a.first_only || (flags & SMX_F_FIRST));
-  if (!live) return;
-  const int n_veh = c.num_vehicles;
-  const int env = (int)(gid / n_veh);
-  const int slot = (int)(gid - (size_t)env * n_veh);
-  // env-mates that a ray can reach at all (|ray| = max_distance; a chassis box lies within 2.1 m of
-  // its centre — with dimensions bound, smx_set_social_history_dims, within the mate's own half diagonal),
-  // compacted into LDS by ballot / prefix count — the order does not matter for a min
-  __shared__ int n_mates;
-  {
-    const double ex = SF(SMX_S_X), ey = SF(SMX_S_Y);
-    const double reach = c.lidar_max_distance + 2.1;
-    bool keep = false;
-    LidarPose p;
-    p.x = p.y = p.fx = p.fy = 0.0;
-    p.slot = (int)threadIdx.x;
-    if ((int)threadIdx.x < n_veh && (int)threadIdx.x != slot) {
-      const size_t og = (size_t)env * n_veh + threadIdx.x;
-      if (a.st.flags[og] & SMX_F_ALIVE) {
-        p.x = a.st.f64[(size_t)SMX_S_X * total + og];
-        p.y = a.st.f64[(size_t)SMX_S_Y * total + og];
-        const double dx = p.x - ex, dy = p.y - ey;
-        double mate_reach = reach;
-        if (sized) {
-          const VehBox mb = vehicle_box(a, og, true);
-          // (+ 0.12 m: the slack the sedan's 2.1 has over its 1.98 — a corner exactly at max_distance must not be lost to rounding)
-          mate_reach = c.lidar_max_distance + 0.5 * sqrt(mb.length * mb.length + mb.width * mb.width) + 0.12;
-        }
-        if (dx * dx + dy * dy <= mate_reach * mate_reach) {
-          const double h = wrap_heading(a.st.f64[(size_t)SMX_S_HEADING * total + og]);
-          p.fx = -sin(h);
-          p.fy = cos(h);
-          keep = true;
-        }
-      }
-    }
-    const unsigned long long mask = __ballot(keep);
-    if (keep) mates[__popcll(mask & ((1ull << threadIdx.x) - 1ull))] = p;
-    if (threadIdx.x == 0) n_mates = __popcll(mask);
-  }
-  __syncthreads();
-  const int mates_n = n_mates;
-  const double ox = SF(SMX_S_X), oy = SF(SMX_S_Y), oz = SMX_BASE_HEIGHT + 1.0;
-  const double hl = 0.5 * SMX_CHASSIS_LENGTH, hw = 0.5 * SMX_CHASSIS_WIDTH, hh = 0.5 * SMX_CHASSIS_HEIGHT;
-  const double bz = SMX_BASE_HEIGHT + 0.6;  // chassis box centre height (models/vehicle.urdf)
-  for (int i = threadIdx.x; i < c.lidar_rays; i += (int)blockDim.x) {
-    const double dx = a.lidar_rays[i * 3 + 0], dy = a.lidar_rays[i * 3 + 1], dz = a.lidar_rays[i * 3 + 2];
-    double best = SMX_INF;
-    if (dz < 0.0) {
-      const double t = -oz / dz;
-      if (t >= 0.0 && t <= 1.0) best = t;
-    }
-    for (int j = 0; j < mates_n; ++j) {
-      const LidarPose p = mates[j];
-      double mhl = hl, mhw = hw, mhh = hh, mbz = bz;
-      if (sized) {
-        // the mate's own half length and half width; vertically the box keeps the sedan's underside, SMX_BASE_HEIGHT
-        // + 0.1, and rises by the vehicle's height (a stated deviation: the reference centres a BoxChassis box on z = 0)
-        const VehBox mb = vehicle_box(a, (size_t)env * n_veh + p.slot, true);
-        mhl = 0.5 * mb.length, mhw = 0.5 * mb.width, mhh = 0.5 * mb.height;
-        mbz = bz + (mhh - hh);  // (a sedan-high mate: bz itself)
-      }
-      const double relx = ox - p.x, rely = oy - p.y, relz = oz - mbz;
-      // slabs along the box axes: forward f, right r = (f.y, -f.x), up
-      double tmin = 0.0, tmax = 1.0;
-      bool miss = false;
-#pragma unroll
-      for (int ax = 0; ax < 3; ++ax) {
-        double o, d, half;
-        if (ax == 0) {
-          o = relx * p.fx + rely * p.fy;
-          d = dx * p.fx + dy * p.fy;
-          half = mhl;
-        } else if (ax == 1) {
-          o = relx * p.fy + rely * (-p.fx);
-          d = dx * p.fy + dy * (-p.fx);
-          half = mhw;
-        } else {
-          o = relz;
-          d = dz;
-          half = mhh;
-        }
-        if (d == 0.0) {
-          if (fabs(o) > half) miss = true;
-        } else {
-          double t1 = (-half - o) / d, t2 = (half - o) / d;
-          if (t1 > t2) {
-            double tt = t1;
-            t1 = t2;
-            t2 = tt;
-          }
-          tmin = fmax(tmin, t1);
-          tmax = fmin(tmax, t2);
-          if (tmin > tmax) miss = true;
-        }
-      }
-      if (!miss && tmin < best) best = tmin;
-    }
-    const size_t q = gid * (size_t)c.lidar_rays + i;
-    if (best <= 1.0) {
-      a.out.lidar_hit[q] = 1;
-      a.out.lidar_point[q * 3 + 0] = ox + best * dx;
-      a.out.lidar_point[q * 3 + 1] = oy + best * dy;
-      a.out.lidar_point[q * 3 + 2] = oz + best * dz;
-    } else {
-      a.out.lidar_hit[q] = 0;
-      const double inf = __builtin_huge_val();
-      a.out.lidar_point[q * 3 + 0] = inf;
-      a.out.lidar_point[q * 3 + 1] = inf;
-      a.out.lidar_point[q * 3 + 2] = inf;
-    }
-  }
-}
-
-// =================================================================================
 // k_sensors: the observation of a pass as ONE launch whose workgroups take different roles —
 // waypoint paths + trip meter (4 lanes / vehicle), the rest of Sensors.observe (1 lane / vehicle,
 // whole envs per workgroup) and, if enabled, lidar and OGM (1 wavefront / vehicle each).  The roles read the
@@ -4352,12 +3462,6 @@ __global__ void __launch_bounds__(SMX_FIRST_BLOCK) k_first_sized(const KernelArg
   first_role<1>(a, groups[blockIdx.x]);
 }
 
-// single-role launches: large batches (each role then keeps its own register / LDS footprint and
-// occupancy; forcing more wavefronts per SIMD onto k_waypoints / k_observe by waves_per_eu cost more
-// in spills than it won: +20 % on loop 4096 x 32) and OGM tiles too large to ride along as dynamic LDS of every k_sensors workgroup
-__global__ void __launch_bounds__(SMX_BLOCK) k_ogm(const KernelArgs a) { ogm_role(a, (int)blockIdx.x); }
-__global__ void __launch_bounds__(SMX_BLOCK) k_dagm(const KernelArgs a) { dagm_role(a, (int)blockIdx.x); }
-__global__ void __launch_bounds__(SMX_BLOCK) k_rgb(const KernelArgs a) { rgb_role(a, (int)blockIdx.x); }
 // =================================================================================
 // k_road_waypoints: RoadWaypointsSensor (sensors.py:991-1040).  SMX_RW_LANE_CAP lanes of a wavefront share a
 // vehicle: every lane of the team builds the sensor's lane list for itself (the same serial steps, so the
@@ -5171,29 +4275,6 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_observe_sized(const KernelArgs a)
   observe_role(a, (int)blockIdx.x, true);
   SMX_TSTAMP(span1);
   SMX_TSPAN(5, span0, span1);
-}
-template <bool SIZED>
-__global__ void __launch_bounds__(SMX_BLOCK) k_lidar(const KernelArgs a) { lidar_role<SIZED ? 1 : 0>(a, (int)blockIdx.x); }
-// The lidar of the reset pass on large batches: almost no vehicle is new in a given tick, and when an env restarts
-// all its vehicles are — neighbours in memory.  Workgroup w looks at the vehicles v = w (mod gridDim.x), 64 flags per
-// load and ballot, and runs the lidar role for the new ones it finds: an env's 64 new vehicles land in 64 different
-// workgroups instead of one after the other in k_first's, and a tick without restarts pays a few microseconds.
-#define SMX_LIDAR_FIRST_BLOCKS 1024
-template <bool SIZED>
-__global__ void __launch_bounds__(SMX_BLOCK) k_lidar_first(const KernelArgs a) {
-  const size_t total = (size_t)a.cfg.num_envs * a.cfg.num_vehicles;
-  const size_t stride = (size_t)gridDim.x;
-  for (size_t base = blockIdx.x; base < total; base += stride * SMX_BLOCK) {
-    const size_t v = base + (size_t)threadIdx.x * stride;
-    const int f = v < total ? a.st.flags[v] : 0;
-    unsigned long long fresh = __ballot((f & SMX_F_ALIVE) && (f & SMX_F_FIRST) && !(f & SMX_F_SOCIAL));
-    while (fresh != 0ull) {  // uniform in the (one-wavefront) workgroup
-      const int l = __ffsll((long long)fresh) - 1;
-      fresh &= fresh - 1ull;
-      lidar_role<SIZED ? 1 : 0>(a, (int)(base + (size_t)l * stride));
-      __syncthreads();  // the role's LDS block is reused
-    }
-  }
 }
 
 // =================================================================================

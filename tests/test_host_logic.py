@@ -425,7 +425,7 @@ def test_release_library_has_no_debug_switches():
 
 
 # the headers cut out of the kernels' file: smx_tick.h first, the phase headers (smx_k_*.h) follow it
-CUT_HEADERS = ["smx_tick.h"]
+CUT_HEADERS = ["smx_tick.h", "smx_k_scan.h", "smx_k_grids.h", "smx_k_lidar.h"]
 # what smx_tick.h took out of smx_kernels.hip (more than one phase uses each)
 TICK_DEFINITIONS = ["KernelArgs", "seg_position", "launch_vehicle", "box_corners", "point_in_box", "seg_point_dist2", "boxes_within",
                     "store_seeds", "load_seeds", "trip_counts_waypoint", "load_vehicle", "history_slot_present",
@@ -452,8 +452,9 @@ def _includes_hip(csrc, name, seen=None):
 def test_every_header_compiles_on_its_own():
     """Each header under csrc/ has #pragma once and includes what it uses: the device headers pass hipcc's syntax check
     for gfx950 alone, the host-only ones g++'s.  No header cut out of the kernels' file is longer than smx_scan.h, the
-    longest header before the cutting began.  What smx_tick.h took is defined there alone, and it holds no kernel.
-    (The cut is staged, DESIGN.md §9: while smx_kernels.hip still holds the phases it holds __global__ and __device__;
+    longest header before the cutting began.  What smx_tick.h took is defined there and in no other file under csrc/,
+    and it holds no kernel: a __global__ lies in a phase header (smx_k_*.h) or, still, in smx_kernels.hip.
+    (The cut is staged, DESIGN.md §9: while smx_kernels.hip still holds phases it holds __global__ and __device__;
     the change that moves the last phase into its smx_k_*.h replaces the TICK_DEFINITIONS check by "smx_kernels.hip
     contains neither word outside comments".)"""
     import subprocess
@@ -483,11 +484,14 @@ def test_every_header_compiles_on_its_own():
         n = len(open(os.path.join(csrc, h)).read().splitlines())
         assert n <= LONGEST_HEADER, (h, n)
     code = lambda name: re.sub(r"//[^\n]*", "", open(os.path.join(csrc, name)).read())
-    kernels, tick = code("smx_kernels.hip"), code("smx_tick.h")
+    sources = {f: code(f) for f in sorted(os.listdir(csrc))}
+    tick = sources["smx_tick.h"]
     assert "__global__" not in tick
+    assert all(f == "smx_kernels.hip" or f.startswith("smx_k_") for f, text in sources.items() if "__global__" in text)
     for name in TICK_DEFINITIONS:
         head = r"^(struct (__align__\(\d+\) )?%s \{|__device__ [^;{]*\b%s\()" % (name, name)
-        assert re.search(head, tick, re.M) and not re.search(head, kernels, re.M), name
+        elsewhere = [f for f, text in sources.items() if f != "smx_tick.h" and re.search(head, text, re.M)]
+        assert re.search(head, tick, re.M) and not elsewhere, (name, elsewhere)
 
 
 def test_build_staleness_sees_every_header(tmp_path):

@@ -4,7 +4,8 @@
     python tools/dev_ablate_wp.py c4 0 1 1048576 2097152
 
 builds smarts_amd/libsmarts_mi355x_ab<mask>.so for every mask (here, on the CPU box, before gpurun) when called
-with --build, and times them on the GPU otherwise.  Bits: the SMX_SKIP(...) sites of smx_kernels.hip (the macro itself: smx_tick.h)."""
+with --build, and times them on the GPU otherwise.  Bits: the SMX_SKIP(...) sites of smx_kernels.hip
+and of the phase headers cut out of it (smx_k_scan.h so far; the macro itself: smx_tick.h)."""
 import os, sys, subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
