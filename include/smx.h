@@ -317,8 +317,10 @@ enum {
   SMX_F_HIST_SHIFT = 3, /* bits 3-4: accelerometer samples held (0..2) */
   SMX_F_FIRST = 1 << 5, /* vehicle was just (re)created: its next observation is a reset observation */
   SMX_F_SOCIAL = 1 << 6, /* scripted social vehicle (no controller, no observation) */
-  SMX_F_LEFT = 1 << 7 /* a history agent whose recorded vehicle has left the table (smx_set_history_agents): done at this
-                         tick's observation; cleared when the slot's vehicle is created again.  Never set without a binding. */
+  SMX_F_LEFT = 1 << 7, /* a history agent whose recorded vehicle has left the table (smx_set_history_agents): done at this
+                          tick's observation; cleared when the slot's vehicle is created again.  Never set without a binding. */
+  SMX_F_ENTERING = 1 << 8 /* beside SMX_F_FIRST: an agent entering inside a tick (smx_set_agent_entry), whose first
+                             observation runs its collision test; cleared with SMX_F_FIRST.  Never set without a binding. */
 };
 
 #define SMX_DRIVEN_PATH_LEN 500 /* DrivenPathSensor deque, sensors.py:838 */
@@ -876,6 +878,49 @@ enum { SMX_BUBBLE_SOCIAL = 0, SMX_BUBBLE_SHADOWED = 1, SMX_BUBBLE_HIJACKED = 2, 
 enum { SMX_HA_SHADOWED = 4, SMX_HA_RELEASED = 5 }; /* following while shadowed by a bubble; released by one in this tick */
 int smx_set_history_bubbles(smx_handle h, const smx_history_bubbles* hb);
 int smx_check_history_bubbles(const smx_config* cfg, const smx_history_bubbles* hb, char* err, uint64_t err_len);
+/* Delayed agent entry (the reference's Mission.start_time + TrapEntryTactic without a capture zone: trap_manager.py:53-65,
+ * 121-241; DESIGN.md section 5.23 has the rule and its deviations).  Opt-in: with nothing bound every agent enters at the
+ * reset observation, as before.  For agent `a` of env `e` in episode k (row = k mod rows):
+ *   ready_host[row][e][a]     the tick, counted from the reset observation (tick 0), from which the agent may enter; >= 0,
+ *                             and every (row, env) has an agent at 0 (the reset observation is the first that holds one)
+ *   check_host[row][e][a][3]  x, y of the mission's start point (the front bumper, not the spawn centre) and the new
+ *                             vehicle's largest plane dimension, in metres
+ *   reset     an agent at tick 0 is created as before, with no overlap check.  Any other agent is PENDING: not alive, its
+ *             rows an absent agent's (zeros, active = 0, done = 0), not counted in env_done_count — the env ends only
+ *             when every agent has entered and become done, as in the reference.
+ *   a tick    once the control phase has stepped every vehicle, a pending agent whose ready tick has come is BLOCKED in this
+ *             tick when an alive social slot s of its env has dx*dx + dy*dy <= (0.5 * (max(l_s, w_s) + dim))^2, dx, dy
+ *             the slot's position minus the check point (l_s, w_s: the slot's dimensions where smx_set_social_history_dims
+ *             binds them, else the sedan's); agents are not checked.  Otherwise it ENTERS: created from its spawn row
+ *             exactly as a reset creates it (pose, speed word, guard verdict, own dimensions), SMX_F_ALIVE | SMX_F_FIRST,
+ *             before the observation pass.  Its observation in that tick is a first observation (steps 1, distance 0,
+ *             no events carried) that runs its collision test (SMX_F_ENTERING); its action of that tick is not read; its env-mates see
+ *             it in the same tick (neighbours, collisions, OGM, RGB, lidar).  A blocked agent tries again next tick.
+ *   status_dev   [E*N] SMX_ENTRY_*, agents' bytes only: PENDING / BLOCKED until the agent enters, then ENTERED.
+ *   entered_dev  [E*N] -1 until the agent enters, then the tick of its entry observation (counted from the reset
+ *                observation: 0 for an agent that entered with it).
+ * Every launch form: the small form's tick observes the entrant in its own pass; the large forms' tick, whose kernels
+ * run over an alive list built a tick ahead, lets the mates see it (k_entry computes its road facts, so they report its
+ * lane as the small form does) and gives it its first observation in the reset pass
+ * after the commit (k_entry_first lists its env group), as a restart inside the tick does.
+ * A bind or unbind (or a new map that drops the table) holds smx_step* (SMX_ERR_STATE) until an smx_reset of every env
+ * (env_mask NULL): the status rows describe no episode before it, and a masked reset leaves envs that were not reset.
+ * Refused (SMX_ERR_INVALID, the reason in smx_last_error): a null table or row, rows < 1, a negative tick, a (row, env)
+ * with no agent at tick 0, a check row that is not finite or a dimension <= 0, status_count or entered_count < E * N;
+ * SMX_ERR_STATE while history agents (and so handover or bubbles) or a frame stack are bound — and those are refused
+ * while this is bound.  The tables are copied; the two rows are the caller's.  entry = NULL unbinds (every agent enters
+ * at its next reset).  Waits for the device.  smx_check_agent_entry is the validation alone, without a device or a handle. */
+typedef struct smx_agent_entry {
+  const int32_t* ready_host; /* host, [rows][num_envs][A] ready tick; copied by the call */
+  const double* check_host;  /* host, [rows][num_envs][A][3] x, y, largest plane dimension; copied by the call */
+  int32_t rows;
+  uint8_t* status_dev;  /* device, caller-owned, [E*N] SMX_ENTRY_* */
+  int32_t* entered_dev; /* device, caller-owned, [E*N] */
+  uint64_t status_count, entered_count;
+} smx_agent_entry;
+enum { SMX_ENTRY_PENDING = 0, SMX_ENTRY_BLOCKED = 1, SMX_ENTRY_ENTERED = 2 };
+int smx_set_agent_entry(smx_handle h, const smx_agent_entry* entry);
+int smx_check_agent_entry(const smx_config* cfg, const smx_agent_entry* entry, char* err, uint64_t err_len);
 /* Frame stacking (smx_config.frame_stack = k): for every agent the device keeps the last k frames of each bound row,
  * newest first (frame 0 is this pass's row), in a caller-owned device buffer.  At the end of every smx_reset / smx_step*
  * pass, on the caller's stream, once every row of the pass is complete (under auto_reset: after the reset pass has

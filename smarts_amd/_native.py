@@ -170,6 +170,14 @@ BUBBLE_SOCIAL, BUBBLE_SHADOWED, BUBBLE_HIJACKED, BUBBLE_RELEASED = 0, 1, 2, 3  #
 HA_SHADOWED, HA_RELEASED = 4, 5  # SMX_HA_*: following while shadowed by a bubble; released by one in this tick
 
 
+class SmxAgentEntry(C.Structure):  # smx_agent_entry (smx_set_agent_entry)
+    _fields_ = [("ready_host", _p), ("check_host", _p), ("rows", _i32), ("status_dev", _p), ("entered_dev", _p),
+                ("status_count", C.c_uint64), ("entered_count", C.c_uint64)]
+
+
+ENTRY_PENDING, ENTRY_BLOCKED, ENTRY_ENTERED = 0, 1, 2  # SMX_ENTRY_*
+
+
 class SmxSpawns(C.Structure):
     _fields_ = [("episodes", _i32), ("pose", _p), ("social", _p), ("pose_count", C.c_uint64), ("social_count", C.c_uint64)]
 
@@ -237,6 +245,7 @@ EXPORTS = [
     "smx_invalidate_outputs", "smx_set_ogm_delta",
     "smx_set_history_bubbles", "smx_check_history_bubbles",
     "smx_set_agent_dims", "smx_check_agent_dims",
+    "smx_set_agent_entry", "smx_check_agent_entry",
 ]
 LAUNCH_FORMS = {0: "small", 1: "large_teams", 2: "large_one_lane"}
 LAUNCH_STRATEGIES = {"auto": 0, "small": 1, "large": 2, "large_one_lane": 3, "large_teams": 4}
@@ -334,6 +343,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.smx_set_agent_dims.restype = C.c_int
     lib.smx_check_agent_dims.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxAgentDims), C.c_char_p, C.c_uint64]
     lib.smx_check_agent_dims.restype = C.c_int
+    lib.smx_set_agent_entry.argtypes = [h, C.POINTER(SmxAgentEntry)]
+    lib.smx_set_agent_entry.restype = C.c_int
+    lib.smx_check_agent_entry.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxAgentEntry), C.c_char_p, C.c_uint64]
+    lib.smx_check_agent_entry.restype = C.c_int
     lib.smx_set_history_agents.argtypes = [h, C.POINTER(SmxHistoryAgents)]
     lib.smx_set_history_agents.restype = C.c_int
     lib.smx_check_history_agents.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxSocialHistory), C.POINTER(SmxHistoryAgents),

@@ -18,6 +18,9 @@
 //                       the agents' dimensions (smx_set_agent_dims: they name no vehicle of the history), whose triples
 //                       move into a fresh triple block
 //       history agents  (bind or unbind) drop the handover table, the bubbles and the action / status rows
+//       a new map       also drops the agents' entry table (smx_set_agent_entry: its check points lie on the old map)
+//   What does not combine is refused, once, in entry_conflict below: the entry table beside history agents (and so their
+//   handover table and bubbles) or a frame stack — whichever is bound second is refused.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -39,6 +42,16 @@
 struct CtrlHandoff {
   double* path;  // [SMX_CTRL_WPS][3][E*N]: x, y, heading of the wanted path's waypoints
   int32_t* n;    // [E*N] waypoints held; 0 = no path found (the reference asserts; the last command is kept)
+};
+
+// What the kernels get of smx_set_agent_entry (ready null: none bound): the device copy of the two tables and the caller's
+// two rows.  ready [rows][E][A] ticks from the reset observation; check [rows][E][A][3] x, y, largest plane dimension.
+struct EntryDev {
+  const int32_t* ready;
+  const double* check;
+  int32_t rows;
+  uint8_t* status;   // [E*N] SMX_ENTRY_*
+  int32_t* entered;  // [E*N]
 };
 
 // One device allocation: allocates, frees in its destructor, reset() frees now, get<T>() reads the pointer.
@@ -220,6 +233,11 @@ struct smx_handle_s {
   DeviceBlob dims_blob;
   DeviceBlob agent_dims_blob;
   HistoryDimsDev dims;   // ... and what the kernels get (table / agent null: that one not bound; slot null: neither)
+  DeviceBlob entry_blob;  // smx_set_agent_entry: device copy of the tables, ready ticks | check rows (null: none bound)
+  EntryDev entry;         // ... and what the kernels get (ready null: none bound)
+  // a table was bound or unbound since the last smx_reset of every env: the status rows do not describe the episodes yet,
+  // so steps are refused until one (enqueue clears it)
+  bool entry_reset_needed;
   struct StackBinding {  // smx_bind_frame_stack: one caller-owned stack per (source, layout)
     int32_t source, layout;
     uint8_t* dst;
@@ -341,6 +359,27 @@ static void unbind_history(smx_handle h) {
   unbind_dims(h);  // the per-vehicle dimensions were checked against this history's ids
   unbind_history_agents(h);
 }
+static void unbind_agent_entry(smx_handle h) {  // (the two rows are the caller's)
+  h->entry_blob.reset();
+  h->entry = EntryDev{};
+}
+// The bindings that do not combine with delayed entry (include/smx.h smx_set_agent_entry), asked by whichever is bound
+// second: a history agent enters by its recording, not by a ready tick, and the reference hands an entrant a stack shorter
+// than the frame stacks here keep.  Empty: no conflict.
+enum class Binding { AGENT_ENTRY, HISTORY_AGENTS, FRAME_STACK };
+static const char* entry_conflict(const smx_handle_s* h, Binding b) {
+  switch (b) {
+    case Binding::AGENT_ENTRY:
+      if (h->history.follow != nullptr) return "agent entry: history agents are bound (smx_set_history_agents): they enter by their recording";
+      if (!h->stacks.empty()) return "agent entry: a frame stack is bound (smx_bind_frame_stack): an entrant's stack is not built";
+      return nullptr;
+    case Binding::HISTORY_AGENTS:
+      return h->entry.ready != nullptr ? "history agents: delayed agent entry is bound (smx_set_agent_entry)" : nullptr;
+    case Binding::FRAME_STACK:
+      return h->entry.ready != nullptr ? "frame stack: delayed agent entry is bound (smx_set_agent_entry)" : nullptr;
+  }
+  return nullptr;
+}
 
 static void destroy_impl(smx_handle h) {
   if (!h) return;
@@ -417,6 +456,8 @@ static int load_map_impl(smx_handle h, const smx_map_tables* t) {
   unbind_missions(h);  // missions name roads of the map they were set for: a new map starts without any
   unbind_history(h);   // a bound traffic history was checked against the old map's grids: a new map starts without one
   unbind_agent_dims(h);  // (the triple block went with the history's dimensions) a new map starts with sedans
+  if (h->entry.ready) h->entry_reset_needed = true;
+  unbind_agent_entry(h);  // the check points lie on the old map: a new map starts with every agent entering at its reset
   // the tick's alive list (large batches) + its counters, the env groups with new vehicles (alive_layout)
   if (!h->alive_blob) SMX_HIP(alloc_filled(h->alive_blob, alive_layout(h->cfg).size * sizeof(int32_t), 0));
   if (!h->slow_blob) SMX_HIP(alloc_filled(h->slow_blob, SlowLists::size(total) * sizeof(int32_t), 0));
@@ -749,6 +790,7 @@ static int set_history_agents_impl(smx_handle h, const smx_history_agents* ha) {
   if (!h) return SMX_ERR_INVALID;
   if (ha) {
     if (h->history.vehicle == nullptr) return fail(h, SMX_ERR_STATE, "smx_set_history_agents needs a bound history (smx_set_social_history)");
+    if (const char* why = entry_conflict(h, Binding::HISTORY_AGENTS)) return fail(h, SMX_ERR_STATE, why);
     std::string msg;
     const int rc = check_history_agents_impl(h->cfg, h->history.rows, *ha, msg);
     if (rc != SMX_OK) return fail(h, rc, msg);
@@ -800,6 +842,37 @@ static int set_history_bubbles_impl(smx_handle h, const smx_history_bubbles* hb)
   return SMX_OK;
 }
 
+static int set_agent_entry_impl(smx_handle h, const smx_agent_entry* en) {
+  if (!h) return SMX_ERR_INVALID;
+  DeviceBlob blob;  // ready ticks | check rows, filled here, committed after the wait
+  if (en) {
+    if (const char* why = entry_conflict(h, Binding::AGENT_ENTRY)) return fail(h, SMX_ERR_STATE, why);
+    std::string msg;
+    const int rc = check_agent_entry_impl(h->cfg, *en, msg);
+    if (rc != SMX_OK) return fail(h, rc, msg);
+    const size_t cells = (size_t)en->rows * (size_t)h->cfg.num_envs * (size_t)(h->cfg.num_vehicles - h->cfg.num_social);
+    const size_t ready_bytes = (cells * sizeof(int32_t) + 7) / 8 * 8;  // (the check rows start 8-byte aligned)
+    SMX_HIP(hipSetDevice(h->device));
+    SMX_HIP(blob.alloc(ready_bytes + cells * 3 * sizeof(double)));
+    SMX_HIP(hipMemcpy(blob.p, en->ready_host, cells * sizeof(int32_t), hipMemcpyHostToDevice));
+    SMX_HIP(hipMemcpy((char*)blob.p + ready_bytes, en->check_host, cells * 3 * sizeof(double), hipMemcpyHostToDevice));
+  }
+  SMX_HIP(hipSetDevice(h->device));
+  SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
+  if (en || h->entry.ready) h->entry_reset_needed = true;  // (an unbind of nothing changes no episode)
+  unbind_agent_entry(h);
+  if (!en) return SMX_OK;
+  const size_t cells = (size_t)en->rows * (size_t)h->cfg.num_envs * (size_t)(h->cfg.num_vehicles - h->cfg.num_social);
+  const size_t ready_bytes = (cells * sizeof(int32_t) + 7) / 8 * 8;
+  h->entry_blob = std::move(blob);
+  h->entry.ready = h->entry_blob.get<int32_t>();
+  h->entry.check = (const double*)((const char*)h->entry_blob.p + ready_bytes);
+  h->entry.rows = en->rows;
+  h->entry.status = en->status_dev;
+  h->entry.entered = en->entered_dev;
+  return SMX_OK;
+}
+
 static int bind_frame_stack_impl(smx_handle h, int32_t source, int32_t layout, void* stack_dev, uint64_t bytes) {
   if (!h) return SMX_ERR_INVALID;
   auto at = std::find_if(h->stacks.begin(), h->stacks.end(),
@@ -812,6 +885,7 @@ static int bind_frame_stack_impl(smx_handle h, int32_t source, int32_t layout, v
   uint64_t row;
   const int rc = check_frame_stack_impl(h->cfg, source, layout, bytes, row, msg);
   if (rc != SMX_OK) return fail(h, rc, msg);
+  if (const char* why = entry_conflict(h, Binding::FRAME_STACK)) return fail(h, SMX_ERR_STATE, why);
   if (layout == SMX_STACK_DSTACK && (reinterpret_cast<uintptr_t>(stack_dev) & 15) != 0)
     return fail(h, SMX_ERR_INVALID, "frame stack: an SMX_STACK_DSTACK buffer must be 16-byte aligned (it is moved with up to 16-byte accesses)");
   if (at != h->stacks.end()) {

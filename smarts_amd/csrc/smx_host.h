@@ -450,6 +450,47 @@ inline int check_agent_dims_impl(const smx_config& c, const smx_agent_dims& d, s
   return SMX_OK;
 }
 
+// ---- Delayed agent entry (smx_set_agent_entry / smx_check_agent_entry) ----
+// k_entry reads the two tables at (episode mod rows, env, agent) and writes the two rows by vehicle: their shapes are
+// checked here, and so is what the rule needs — a reset observation holds an agent (smarts.py:426-434 steps until one
+// exists), and the overlap radius is a positive length.
+inline int check_agent_entry_impl(const smx_config& c, const smx_agent_entry& d, std::string& err) {
+  if (c.num_envs <= 0 || c.num_vehicles <= 0 || c.num_social < 0 || c.num_social >= c.num_vehicles)
+    return refuse(err, "agent entry: the configuration has no agents");
+  if (!d.ready_host || !d.check_host) return refuse(err, "agent entry: null table (ready_host / check_host)");
+  if (d.rows < 1) return refuse(err, "agent entry: rows must be >= 1");
+  const uint64_t agents = (uint64_t)(c.num_vehicles - c.num_social), total = (uint64_t)c.num_envs * (uint64_t)c.num_vehicles;
+  if (!d.status_dev || d.status_count < total)
+    return refuse(err, "agent entry: status row missing or short (" + std::to_string(d.status_count) + " elements declared, num_envs * num_vehicles is " +
+                           std::to_string(total) + ": a short row would be an out-of-bounds device write)");
+  if (!d.entered_dev || d.entered_count < total)
+    return refuse(err, "agent entry: entered row missing or short (" + std::to_string(d.entered_count) + " elements declared, num_envs * num_vehicles is " +
+                           std::to_string(total) + ": a short row would be an out-of-bounds device write)");
+  for (int32_t r = 0; r < d.rows; ++r)
+    for (int32_t e = 0; e < c.num_envs; ++e) {
+      bool at_reset = false;
+      for (uint64_t a = 0; a < agents; ++a) {
+        const uint64_t i = ((uint64_t)r * (uint64_t)c.num_envs + (uint64_t)e) * agents + a;
+        const int32_t t = d.ready_host[i];
+        if (t < 0)
+          return refuse(err, "agent entry: row " + std::to_string(r) + ", env " + std::to_string(e) + ", agent " + std::to_string(a) +
+                                 ": ready tick " + std::to_string(t) + " is negative (ticks count from the reset observation)");
+        at_reset = at_reset || t == 0;
+        const double* q = d.check_host + i * 3;
+        if (!(std::isfinite(q[0]) && std::isfinite(q[1]) && std::isfinite(q[2])))
+          return refuse(err, "agent entry: row " + std::to_string(r) + ", env " + std::to_string(e) + ", agent " + std::to_string(a) +
+                                 ": check row is not finite");
+        if (!(q[2] > 0.0))
+          return refuse(err, "agent entry: row " + std::to_string(r) + ", env " + std::to_string(e) + ", agent " + std::to_string(a) +
+                                 ": dimension " + std::to_string(q[2]) + " must be > 0");
+      }
+      if (!at_reset)
+        return refuse(err, "agent entry: row " + std::to_string(r) + ", env " + std::to_string(e) +
+                               " has no agent at tick 0 (the reset observation is the first that holds an agent)");
+    }
+  return SMX_OK;
+}
+
 // ---- History agents (smx_set_history_agents / smx_check_history_agents) ----
 // The kernels index vehicle_dev by (episode mod rows, env, agent) and the two optional rows by vehicle: the counts are
 // checked against those shapes here; the ids the table holds are only ever compared.  `rows`: the bound history's.

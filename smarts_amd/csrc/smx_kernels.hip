@@ -46,6 +46,7 @@
 #include "smx_k_grids.h"
 #include "smx_k_lidar.h"
 #include "smx_k_scan.h"
+#include "smx_k_entry.h"  // (after smx_k_scan.h: its large-form instance runs the facts half for an entrant)
 #include "smx_plan.h"
 #include "smx_scan.h"
 #include "smx_tick.h"
@@ -2756,7 +2757,9 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
     stage.mode[local] = 1;
     const double px = s.x, py = s.y;
     int steps = a.st.steps[gid];
-    const int env_ticks = first ? a.st.env_ticks[env] : a.st.env_ticks[env] + 1;  // smarts.py:261-262
+    // (a reset pass runs after its commit: a new vehicle's tick is env_ticks; in a tick's own pass — a new vehicle there is
+    // an entrant of smx_set_agent_entry — the commit comes later)
+    const int env_ticks = (first && a.first_only) ? a.st.env_ticks[env] : a.st.env_ticks[env] + 1;  // smarts.py:261-262
     if (!first) ++steps;  // SensorState.step (agent_manager.py:250-258); a new vehicle starts at 1
 
     // ---- collisions (smarts.py:1270-1291): a new vehicle has not been through a physics step
@@ -2766,7 +2769,9 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
     // runs over the survivors only: a wavefront pays for max-over-lanes(candidates) box tests, not for n_veh) and
     // the neighbourhood (sensors.py:241-266, smarts.py:1191-1208: every other vehicle of the instance within
     // `radius`, in slot order, first nb_max kept) — both look at the same squared distance.
-    const bool want_col = !first && !SMX_SKIP(a, 4);
+    // (an entrant of smx_set_agent_entry, SMX_F_ENTERING, is tested: its mates see it in their collisions this tick, and
+    // so does it — include/smx.h)
+    const bool want_col = (!first || (flags & SMX_F_ENTERING)) && !SMX_SKIP(a, 4);
     const bool want_nb = (c.sensors & SMX_SENSOR_NEIGHBORS) && !SMX_SKIP(a, 8);
     const bool nb_in_pass = want_nb && nb_staged;  // (more rows than the staged form holds: the loop further down)
     int nb_cnt = 0;
@@ -3102,7 +3107,7 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
     if (first) done = false;  // sensors.py:465: `not sim.resetting and (...)`: reset observations never end an agent
 
     // ---- teardown (smarts.py:314, 329-363)
-    flags &= ~SMX_F_FIRST;
+    flags &= ~(SMX_F_FIRST | SMX_F_ENTERING);
     if (done) flags &= ~SMX_F_ALIVE;
     a.st.steps[gid] = steps;
     new_flags = flags;  // applied by k_tail's commit: the waypoints role of this launch still reads the old word
@@ -4282,8 +4287,9 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_observe_sized(const KernelArgs a)
 // spawn poses (AckermannChassis._initialize_speed, chassis.py:668-671); the observation kernels
 // that follow produce their first observations.
 // =================================================================================
-// (SIZED: a triple block is bound, TickPlan::sized — the agents' triples are written beside their spawn poses)
-template <bool GUARD = false, bool SIZED = false>
+// (SIZED: a triple block is bound, TickPlan::sized — the agents' triples are written beside their spawn poses; ENTRY: an
+// entry table is bound, TickPlan::entry — agents whose ready tick is not 0 are created pending)
+template <bool GUARD = false, bool SIZED = false, bool ENTRY = false>
 __global__ void __launch_bounds__(SMX_BLOCK) k_reset(const KernelArgs a) {
   const smx_config& c = a.cfg;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
@@ -4302,7 +4308,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_reset(const KernelArgs a) {
     if constexpr (GUARD) a.guard[gid] = 0;  // (an agent absent from the pass)
     return;
   }
-  respawn_vehicle<GUARD, SIZED ? 1 : 0>(a, gid, total, a.st.env_episode[env] + 1);  // every reset starts the next spawn row
+  respawn_vehicle<GUARD, SIZED ? 1 : 0, ENTRY ? 1 : 0>(a, gid, total, a.st.env_episode[env] + 1);  // every reset starts the next spawn row
   // per-env words are written by every thread of the env with the same values (no ordering needed
   // inside this kernel; the env's own threads never read them here)
   (void)slot;
@@ -4452,6 +4458,7 @@ static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_sta
   in.ogm_mask = h->ogm_mask && h->ogm_delta;
   in.handover_entry = handover;
   in.bubbles_bound = h->bubble_state != nullptr;
+  in.entry_bound = h->entry.ready != nullptr;
   return in;
 }
 
@@ -4551,6 +4558,14 @@ extern "C" int smx_check_agent_dims(const smx_config* cfg, const smx_agent_dims*
 }
 
 extern "C" int smx_set_agent_dims(smx_handle h, const smx_agent_dims* dims) { return set_agent_dims_impl(h, dims); }
+
+extern "C" int smx_check_agent_entry(const smx_config* cfg, const smx_agent_entry* entry, char* err, uint64_t err_len) {
+  std::string msg;
+  const int rc = (cfg && entry) ? check_agent_entry_impl(*cfg, *entry, msg) : refuse(msg, "null config / entry");
+  return report(rc, msg, err, err_len);
+}
+
+extern "C" int smx_set_agent_entry(smx_handle h, const smx_agent_entry* entry) { return set_agent_entry_impl(h, entry); }
 
 extern "C" int smx_check_history_agents(const smx_config* cfg, const smx_social_history* hist, const smx_history_agents* ha, char* err,
                                         uint64_t err_len) {
@@ -4895,7 +4910,11 @@ static int tail_and_reset_pass(smx_handle h, const TickPlan& p, const KernelArgs
   r.reset_all = (!p.is_step && mask == nullptr) ? 1 : 0;
   r.env_mask = p.is_step ? nullptr : mask;
   if (!p.is_step) {
-    launch(p.guard ? (p.sized ? k_reset<true, true> : k_reset<true>) : (p.sized ? k_reset<false, true> : k_reset<false>), p.veh_blocks, 0, stream, r);
+    if (p.entry)  // (the ENTRY instantiations: pending agents; the plain ones hold nothing of it)
+      launch(p.guard ? (p.sized ? k_reset<true, true, true> : k_reset<true, false, true>)
+                     : (p.sized ? k_reset<false, true, true> : k_reset<false, false, true>), p.veh_blocks, 0, stream, r);
+    else
+      launch(p.guard ? (p.sized ? k_reset<true, true> : k_reset<true>) : (p.sized ? k_reset<false, true> : k_reset<false>), p.veh_blocks, 0, stream, r);
     launch(k_reset_env, p.env_blocks, 0, stream, r);
   }
   TailArgs t{};
@@ -4912,6 +4931,8 @@ static int tail_and_reset_pass(smx_handle h, const TickPlan& p, const KernelArgs
     t.slow_next = SlowLists{h->slow_blob.get<int32_t>(), total}.counters(h->alive_parity);
   }
   hipLaunchKernelGGL(p.guard ? k_tail<true> : k_tail<false>, dim3(p.obs_blocks), dim3(SMX_BLOCK), p.tail_grids ? std::max({p.ogm_bytes, p.dagm_bytes, p.rgb_lds}) : 0, stream, r, t);
+  if (p.entry_first)  // (a large form's tick: this tick's entrants into the reset pass's groups, smx_k_entry.h)
+    hipLaunchKernelGGL(k_entry_first, dim3(p.obs_blocks), dim3(SMX_BLOCK), 0, stream, r, t.groups, t.n_groups);
   if (ph) SMX_HIP(hipEventRecord(ph[SMX_PHASE_COMMIT + 1], stream));
   h->group_parity ^= 1;
   h->list_ready = p.tail_builds_list;
@@ -4988,6 +5009,7 @@ static KernelArgs kernel_args(smx_handle h, const TickPlan& p, const int8_t* act
   a.ha_action = h->ha_action;
   a.ha_status = h->ha_status;
   a.ogm_mask = (p.ogm_delta && out->ogm) ? h->ogm_mask.get<unsigned long long>() : nullptr;
+  a.entry = h->entry;
   a.wp_blocks = (int)p.wp_blocks;
   a.obs_blocks = (int)p.obs_blocks;
   a.lidar_blocks = (int)p.lidar_blocks;
@@ -5029,6 +5051,10 @@ static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const
   }
   hipStream_t stream = (hipStream_t)stream_;
   const TickPlan p = tick_plan(plan_inputs(h, is_step, st, follow, handover));
+  if (is_step && h->entry_reset_needed)
+    return fail(h, SMX_ERR_STATE, "agent entry: smx_set_agent_entry bound or unbound a table since the last smx_reset of every "
+                                  "env (env_mask NULL); step after one");
+  if (!is_step && mask == nullptr) h->entry_reset_needed = false;
   KernelArgs a = kernel_args(h, p, actions, actions_f32, traj, traj_n, traj_max, mask, st, sp, out);
   const bool timed = h->timing && is_step && h->ev_used < 65536;
   if (timed) {
@@ -5064,6 +5090,10 @@ static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const
   alive_list(h, p, a, stream);
   if (is_step) {
     launch_control(h, p, a, stream);
+    if (p.entry)  // (after the control phase has moved the social slots, ahead of every sensor: smx_k_entry.h)
+      hipLaunchKernelGGL(p.small() ? (p.guard ? k_entry<true, false> : k_entry<false, false>)
+                                   : (p.guard ? k_entry<true, true> : k_entry<false, true>),
+                         dim3((unsigned)h->cfg.num_envs), dim3(64), 0, stream, a);
     if (ph) SMX_HIP(hipEventRecord(ph[SMX_PHASE_CONTROL + 1], stream));
     observation_pass(h, p, a, stream, ph);
   }

@@ -96,6 +96,7 @@ struct PlanInputs {
   bool ogm_mask;           // the handle holds the OGM tiles' piece mask and smx_set_ogm_delta has not switched it off
   bool handover_entry;     // the call is smx_step_history_handover: each agent follows or is driven, as its handover tick says
   bool bubbles_bound;      // smx_set_history_bubbles holds bubbles: that call's tick starts with k_bubbles and reads its state row
+  bool entry_bound;        // smx_set_agent_entry holds a table: pending agents enter inside a tick (k_entry)
 };
 
 enum class AliveList : uint8_t { NONE, CARRIED, BUILD };  // BUILD: k_alive_list ahead of the tick
@@ -180,6 +181,13 @@ struct TickPlan {
   // per-vehicle dimensions (smx_set_social_history_dims or smx_set_agent_dims: a triple block is bound): the SIZED instantiations of k_ogm_env, k_lidar and k_lidar_first
   // in the places of the plain ones — the same launches on the same streams; every other reader branches on the pointer
   bool sized;
+  // delayed agent entry (smx_set_agent_entry holds a table): the ENTRY instantiations of k_reset in a reset call (the
+  // tick's commit, which restarts envs under auto_reset, asks the argument block), and in a tick k_entry after the control
+  // phase, ahead of the observation pass, on the caller's stream.  The small form's tick kernels visit every vehicle, so
+  // the entrant's first observation is the tick's own; the large forms' tick lists its vehicles a tick ahead (entry_first)
+  bool entry;
+  // ... in a large form's tick: k_entry_first after k_tail, and the reset pass over the groups it lists (reset_pass)
+  bool entry_first;
   bool tail_builds_list;  // k_tail builds the next tick's alive list
   bool tail_grids;        // ... and the new vehicles' grid tiles
   bool reset_pass, lidar_first, first_walks_new;
@@ -317,7 +325,10 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
   // traffic history is bound: the reset pass's commit then still changes SMX_F_ALIVE of the new envs' social slots (a
   // slot shows the reset observation's frame in that pass and the next frame in the tick after it), behind k_tail
   p.tail_builds_list = !small && in.alive_blob && in.slow.base && !idm && !in.history_bound;
-  p.reset_pass = !in.is_step || c.auto_reset;  // (in a step, k_tail's commit respawns the envs that ended)
+  // (in a step, k_tail's commit respawns the envs that ended; with an entry table bound, a large form's tick also gives
+  // its entrants their first observation there)
+  p.entry_first = in.entry_bound && in.is_step && !small;
+  p.reset_pass = !in.is_step || c.auto_reset || p.entry_first;
   p.tail_grids = p.reset_pass && (p.ogm_bytes || p.dagm_bytes || p.rgb);
   // large batches: the new vehicles' lidar as a launch of its own instead of one after the other inside
   // k_first — at C5 an env restart brings 64 new vehicles, whose serial lidar roles made the reset pass 0.58 ms
@@ -355,6 +366,7 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
   p.frame_stack = c.frame_stack > 0 && in.frame_stack_bound;
   p.guard = in.guard_bound;
   p.sized = in.dims_bound || in.agent_dims_bound;
+  p.entry = in.entry_bound;
   p.ego_centric = (c.sensors & SMX_SENSOR_EGO_CENTRIC) != 0;
   if (p.ego_centric) {
     const size_t apb = SMX_BLOCK / SMX_EC_TEAM;

@@ -85,6 +85,9 @@ struct KernelArgs {
   // run beside each other touch the same agent's words: k_ogm_env / the OGM role draw for the agents alive at the tick's
   // start, zero_dense_rows runs for agents that were not, and k_tail's tiles of new vehicles come after both have joined.
   unsigned long long* ogm_mask;
+  // delayed agent entry (smx_set_agent_entry; smx_k_entry.h): entry.ready null = none bound, every agent enters at its
+  // reset.  Read by respawn_vehicle on the rare side of a branch, and by k_entry.
+  EntryDev entry;
 };
 enum {
   SMX_DEVICE_BAD_LANE_ACTION = 1,  // a Lane action code outside -1..3 was met (and treated as "no action")
@@ -583,7 +586,22 @@ __device__ __forceinline__ int history_respawn(const KernelArgs& a, size_t gid, 
   return SMX_F_SOCIAL | SMX_F_FIRST | (present ? SMX_F_ALIVE : 0);
 }
 
-template <bool GUARD, int SIZED = -1>
+// An agent of a freshly reset env under delayed entry (smx_set_agent_entry), on the flags word respawn_vehicle made: ready
+// tick 0 enters with the reset as before — status ENTERED at tick 0 —; any other is PENDING: not alive, SMX_F_FIRST all
+// the same so that the reset pass's observe role makes its rows an absent agent's, as for an empty replayed slot.
+__device__ __forceinline__ int entry_respawn(const KernelArgs& a, size_t gid, int episode, int fl) {
+  const int n_veh = a.cfg.num_vehicles, n_agents = n_veh - a.cfg.num_social, rows = a.entry.rows;
+  const size_t env = gid / (size_t)n_veh, k = gid - env * (size_t)n_veh;
+  const size_t row = (size_t)(((episode % rows) + rows) % rows);
+  const bool now = a.entry.ready[(row * (size_t)a.cfg.num_envs + env) * (size_t)n_agents + k] <= 0;
+  a.entry.status[gid] = (uint8_t)(now ? SMX_ENTRY_ENTERED : SMX_ENTRY_PENDING);
+  a.entry.entered[gid] = now ? 0 : -1;
+  return now ? fl : SMX_F_FIRST;
+}
+
+// (ENTRY, as SIZED: 1 / 0 — the plan chose the instantiation of k_reset (TickPlan::entry), and the one without a table
+// holds nothing of the entry branch —, -1: the caller asks the argument block, the rare side of a branch)
+template <bool GUARD, int SIZED = -1, int ENTRY = -1>
 __device__ __forceinline__ void respawn_vehicle(const KernelArgs& a, size_t gid, size_t total, int episode) {
   const int row = a.sp.episodes > 0 ? (((episode % a.sp.episodes) + a.sp.episodes) % a.sp.episodes) : 0;
   const double* sp = a.sp.pose + ((size_t)row * total + gid) * 4;
@@ -633,6 +651,13 @@ __device__ __forceinline__ void respawn_vehicle(const KernelArgs& a, size_t gid,
     }
     // the agent's own dimensions (smx_set_agent_dims), beside its pose: a follower keeps them through whatever comes
     if (own_box_sized<SIZED>(a)) agent_store_dims(a, gid, episode);
+    // delayed entry (smx_set_agent_entry): an agent whose ready tick is not the reset observation's waits for k_entry
+    if (ENTRY < 0 ? __builtin_expect(a.entry.ready != nullptr, 0) : ENTRY != 0) {
+      fl = entry_respawn(a, gid, episode, fl);
+      if constexpr (GUARD) {
+        if (!(fl & SMX_F_ALIVE)) a.guard[gid] = 0;  // (an absent agent's byte: its spawn row is tested when it enters)
+      }
+    }
   }
   a.st.flags[gid] = fl;
   // the slot's knot lists belong to the vehicle that is gone (k_wp_walk only visits alive vehicles)

@@ -108,6 +108,9 @@ class SimConfig:
     # out["guard"], [E, N] uint8, holds the reason (nat.GUARD_STEP / GUARD_STATE / GUARD_SPAWN)
     state_guard: bool = False
     state_guard_margin: float = nat.GUARD_MARGIN_DEFAULT
+    # delayed agent entry (smarts_amd.missions.entry_table): the steps reset() burns before the first agent enters,
+    # min over the agents of missions.entry_ticks; None = the 0.1 s default start time of every mission
+    entry_reset_steps: Optional[int] = None
 
     def __post_init__(self):
         checked_guard_margin(self.state_guard_margin)
@@ -151,6 +154,8 @@ class SimConfig:
         """Ticks the reference burns in ``reset()`` before the first ego observation exists:
         the trap fires once ``mission.start_time`` (0.1 s, plan.py:209) has *passed*
         (trap_manager.py:53-65), and ``reset`` spins ``step({})`` until then (smarts.py:426-434)."""
+        if self.entry_reset_steps is not None:
+            return int(self.entry_reset_steps)
         return int(math.floor(0.1 / self.dt + 1e-9)) + 1
 
 
@@ -254,6 +259,34 @@ def check_agent_dims(action_space: str, num_envs: int, num_vehicles: int, num_so
     err = C.create_string_buffer(512)
     if lib.smx_check_agent_dims(C.byref(c), C.byref(ad), err, len(err)) != 0:
         raise ValueError(err.value.decode())
+
+
+def check_agent_entry(num_envs: int, num_vehicles: int, num_social: int, ready_ticks: np.ndarray, check: np.ndarray) -> None:
+    """``smx_check_agent_entry``: would ``smx_set_agent_entry`` take the int32 table ``ready_ticks`` ``(R, E, A)`` and the
+    float64 table ``check`` ``(R, E, A, 3)`` for a shard of this shape?  Needs the built library, no device and no handle;
+    raises ``ValueError`` with the library's reason when not."""
+    lib = nat.load_library()
+    ready, chk = _agent_entry_tables(ready_ticks, check, int(num_envs), int(num_vehicles) - int(num_social))
+    c = nat.SmxConfig()
+    c.num_envs, c.num_vehicles, c.num_social = int(num_envs), int(num_vehicles), int(num_social)
+    en = nat.SmxAgentEntry()
+    en.ready_host, en.check_host, en.rows = ready.ctypes.data, chk.ctypes.data, int(ready.shape[0])
+    # (the rows' extents are what the check reads of them; no device buffer is touched)
+    en.status_dev, en.entered_dev = 1, 1
+    en.status_count = en.entered_count = int(num_envs) * int(num_vehicles)
+    err = C.create_string_buffer(512)
+    if lib.smx_check_agent_entry(C.byref(c), C.byref(en), err, len(err)) != 0:
+        raise ValueError(err.value.decode())
+
+
+def _agent_entry_tables(ready_ticks, check, num_envs: int, num_agents: int) -> Tuple[np.ndarray, np.ndarray]:
+    ready = np.ascontiguousarray(ready_ticks, dtype=np.int32)
+    chk = np.ascontiguousarray(check, dtype=np.float64)
+    if ready.ndim != 3 or ready.shape[0] < 1 or tuple(ready.shape[1:]) != (num_envs, num_agents):
+        raise ValueError(f"ready ticks must be int32 of shape (R, {num_envs}, {num_agents}), got {tuple(ready.shape)}")
+    if tuple(chk.shape) != tuple(ready.shape) + (3,):
+        raise ValueError(f"check must be float64 of shape {tuple(ready.shape) + (3,)}, got {tuple(chk.shape)}")
+    return ready, chk
 
 
 def _agent_dims_table(dims, num_envs: int, num_agents: int) -> np.ndarray:
@@ -741,6 +774,40 @@ class BatchedSim:
         nat.check(self.lib, self.handle, self.lib.smx_set_agent_dims(self.handle, C.byref(ad)), "smx_set_agent_dims")
         self.agent_dims = table.copy()
 
+    def set_agent_entry(self, ready_ticks: Optional[np.ndarray], check: Optional[np.ndarray] = None):
+        """Bind delayed agent entry (``smx_set_agent_entry``; ``smarts_amd.missions.entry_table`` builds both tables):
+        ``ready_ticks`` int32 ``(R, E, A)`` — the tick, counted from the reset observation, from which agent ``a`` of env
+        ``e`` may enter in episode ``k`` (row ``k mod R``), at least one 0 per (row, env) — and ``check`` float64
+        ``(R, E, A, 3)`` — the mission's start point (front bumper) and the new vehicle's largest plane dimension.  From
+        the next ``reset`` on an agent at tick 0 enters with the reset; any other is pending (its rows an absent agent's)
+        and enters in the first tick from its ready tick on in which no alive social vehicle overlaps its start point,
+        with a first observation its env-mates see in that tick.  ``out["entry_status"]`` ``(E, N)`` uint8 holds
+        ``ENTRY_PENDING / ENTRY_BLOCKED / ENTRY_ENTERED`` per agent and ``out["entered_tick"]`` ``(E, N)`` int32 the tick
+        of its entry observation (-1 before).  Every launch form.  After a bind or unbind ``step`` is refused until a
+        ``reset()`` of every env (no mask).  ``None`` unbinds (every agent enters at its
+        next reset); so does a new map.  Refused with the library's reason (``SmxError``): a negative tick, a (row, env)
+        without an agent at tick 0, a check row that is not finite or a dimension <= 0, history agents or a frame stack
+        bound."""
+        if ready_ticks is None:
+            nat.check(self.lib, self.handle, self.lib.smx_set_agent_entry(self.handle, None), "smx_set_agent_entry")
+            self.agent_entry = None
+            self.out.pop("entry_status", None)
+            self.out.pop("entered_tick", None)
+            return
+        if check is None:
+            raise ValueError("set_agent_entry needs the check table beside the ready ticks")
+        ready, chk = _agent_entry_tables(ready_ticks, check, self.E, self.N - self.cfg.num_social)
+        status = torch.full((self.E, self.N), nat.ENTRY_PENDING, dtype=torch.uint8, device=self.device)
+        entered = torch.full((self.E, self.N), -1, dtype=torch.int32, device=self.device)
+        en = nat.SmxAgentEntry()
+        en.ready_host, en.check_host, en.rows = ready.ctypes.data, chk.ctypes.data, int(ready.shape[0])
+        en.status_dev, en.status_count = status.data_ptr(), int(status.numel())
+        en.entered_dev, en.entered_count = entered.data_ptr(), int(entered.numel())
+        nat.check(self.lib, self.handle, self.lib.smx_set_agent_entry(self.handle, C.byref(en)), "smx_set_agent_entry")
+        self.agent_entry = (ready.copy(), chk.copy())
+        self.out["entry_status"] = status  # (written by every pass: they live as long as the binding)
+        self.out["entered_tick"] = entered
+
     def set_history_agents(self, vehicle: Optional[torch.Tensor], expert_actions: bool = True):
         """Bind the history agents (``smx_set_history_agents``; needs ``action_space="Imitation"`` and a bound traffic
         history): agent slot ``a`` of env ``e`` follows recorded vehicle ``vehicle[k mod R, e, a]`` in episode ``k`` —
@@ -865,6 +932,7 @@ class BatchedSim:
     history_bubbles = None
     history_dims = False
     agent_dims = None  # the bound (R, E, A, 3) table of set_agent_dims (a host copy), or None
+    agent_entry = None  # the bound (ready ticks, check) tables of set_agent_entry (host copies), or None
     traffic_history = None
     history_start_frames = None
     history_replaced = None

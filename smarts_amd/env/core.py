@@ -239,6 +239,26 @@ class BatchCore:
                     own = own_length[i] if i < self.N else None
                     x, y, h = m.spawn_pose() if own is None else m.spawn_pose(own)
                     spawns.reshape(spawns.shape[0], num_envs, slots, 4)[:, :, i] = (x, y, h, 0.0)
+        # delayed entry (Mission.start_time / entry_tactic, smarts_amd.missions.entry_table): bound only when the agents'
+        # fire steps differ; then the reset observation is the earliest agent's and the others enter inside a tick
+        self.entry = None
+        if missions:
+            from ..missions import entry_table
+
+            dims_rows = None
+            if self.agent_dims:
+                dims_rows = np.full((1, num_envs, self.N, 3), np.nan, dtype=np.float64)
+                for i, a in enumerate(self.agent_ids):
+                    if a in self.agent_dims:
+                        dims_rows[0, :, i] = self.agent_dims[a]
+            table = entry_table([missions.get(a) for a in self.agent_ids], self.missions[:self.N], num_envs, dt, dims_rows)
+            if table.differs:
+                self.entry = table
+                self.cfg.entry_reset_steps = table.reset_steps
+                slots = self.N + num_social
+                for i, speed in enumerate(table.entry_speed):
+                    if speed is not None:  # TrapEntryTactic.default_entry_speed: the new vehicle's speed
+                        spawns.reshape(spawns.shape[0], num_envs, slots, 4)[:, :, i, 3] = speed
         self.sim = BatchedSim(self.cm, self.cfg, device=device, spawns=spawns, seed=seed, social_spawns=where,
                               vias=self.vias, missions=self.missions)
         if self.agent_dims:
@@ -247,6 +267,8 @@ class BatchCore:
                 if a in self.agent_dims:
                     table[0, :, i] = self.agent_dims[a]
             self.sim.set_agent_dims(table)
+        if self.entry is not None:  # (the agent slots: the table's A is this core's N)
+            self.sim.set_agent_entry(self.entry.ready, self.entry.check)
         self.traffic_history = None
         if traffic_history is not None:
             import torch

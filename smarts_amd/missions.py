@@ -26,6 +26,27 @@ from .vias import _position_at_shape_offset
 
 Offset = Union[float, str]
 CHASSIS_LENGTH = 3.68  # vehicle.py:101 (passenger)
+CHASSIS_WIDTH = 1.47
+
+
+@dataclass(frozen=True)
+class TrapEntryTactic:
+    """sstudio/types.py ``TrapEntryTactic``: how a mission's agent enters.  The agent waits for its mission's
+    ``start_time``, then for ``wait_to_hijack_limit_s`` more, then is given a new vehicle at the mission's start at
+    ``default_entry_speed`` (``None``: the spawn table's speed word) once no social vehicle overlaps that point
+    (trap_manager.py:121-241).  Capturing a social vehicle inside ``zone`` is not built: a zone is refused."""
+
+    wait_to_hijack_limit_s: float
+    zone: Optional[object] = None
+    exclusion_prefixes: Tuple[str, ...] = ()
+    default_entry_speed: Optional[float] = None
+
+    def __post_init__(self):
+        if self.zone is not None:
+            raise ValueError("TrapEntryTactic(zone=...): capturing a social vehicle in a trap zone is not built; "
+                             "leave zone=None (the agent enters once its patience has expired)")
+        if not math.isfinite(float(self.wait_to_hijack_limit_s)) or float(self.wait_to_hijack_limit_s) < 0:
+            raise ValueError(f"wait_to_hijack_limit_s must be finite and >= 0, not {self.wait_to_hijack_limit_s!r}")
 
 
 @dataclass(frozen=True)
@@ -39,9 +60,12 @@ class Route:
 
 @dataclass(frozen=True)
 class Mission:
-    """sstudio/types.py ``Mission`` (the route is what this path reads)."""
+    """sstudio/types.py ``Mission`` (the route is what this path reads; ``start_time`` / ``entry_tactic``: delayed
+    entry, ``entry_ticks``)."""
 
     route: Route
+    start_time: float = 0.1
+    entry_tactic: Optional[TrapEntryTactic] = None
 
 
 @dataclass(frozen=True)
@@ -50,6 +74,8 @@ class EndlessMission:
 
     begin: Tuple[str, int, Offset]
     via: Tuple[str, ...] = ()
+    start_time: float = 0.1
+    entry_tactic: Optional[TrapEntryTactic] = None
 
 
 @dataclass(frozen=True)
@@ -59,6 +85,8 @@ class LapMission:
     route: Route
     num_laps: int
     via: Tuple[str, ...] = ()
+    start_time: float = 0.1
+    entry_tactic: Optional[TrapEntryTactic] = None
 
 
 @dataclass(frozen=True)
@@ -67,6 +95,8 @@ class TraverseMission:
     a dead-end lane, heading the lane's way (plan.py:147-166)."""
 
     begin: Tuple[str, int, Offset]
+    start_time: float = 0.1
+    entry_tactic: Optional[TrapEntryTactic] = None
 
 
 GOAL_POSITIONAL, GOAL_LAP, GOAL_TRAVERSE = 0, 1, 2  # SMX_GOAL_* (include/smx.h)
@@ -434,7 +464,9 @@ def load_missions(source: Union[str, dict]) -> Dict[str, object]:
     """Missions of a scenario as JSON (the ``missions.pkl`` of the reference's ``scenario build`` holds pickled
     sstudio objects): ``{agent id: {"begin": [road, lane index, offset], "end": [...], "via": [road, ...]}}``.
     An optional ``"type"`` names the kind: ``"mission"`` (the default: the format above), ``"lap"`` (the same keys
-    plus ``"num_laps"``), ``"endless"`` (``"begin"``, ``"via"``) or ``"traverse"`` (``"begin"``)."""
+    plus ``"num_laps"``), ``"endless"`` (``"begin"``, ``"via"``) or ``"traverse"`` (``"begin"``).  Every kind takes an
+    optional ``"start_time"`` (seconds, default 0.1) and ``"entry_tactic"``: ``{"wait_to_hijack_limit_s": s,
+    "default_entry_speed": v}`` (a ``TrapEntryTactic`` without a zone)."""
     if isinstance(source, str):
         with open(source) as f:
             source = json.load(f)
@@ -442,15 +474,114 @@ def load_missions(source: Union[str, dict]) -> Dict[str, object]:
     for agent_id, spec in source.items():
         kind = spec.get("type", "mission")
         via = tuple(spec.get("via", ()))
+        entry = {}
+        if "start_time" in spec:
+            entry["start_time"] = float(spec["start_time"])
+        if spec.get("entry_tactic") is not None:
+            entry["entry_tactic"] = TrapEntryTactic(**spec["entry_tactic"])
         if kind == "mission":
-            out[agent_id] = Mission(Route(begin=tuple(spec["begin"]), end=tuple(spec["end"]), via=via))
+            out[agent_id] = Mission(Route(begin=tuple(spec["begin"]), end=tuple(spec["end"]), via=via), **entry)
         elif kind == "lap":
             out[agent_id] = LapMission(Route(begin=tuple(spec["begin"]), end=tuple(spec["end"]), via=via),
-                                       num_laps=spec.get("num_laps"))
+                                       num_laps=spec.get("num_laps"), **entry)
         elif kind == "endless":
-            out[agent_id] = EndlessMission(begin=tuple(spec["begin"]), via=via)
+            out[agent_id] = EndlessMission(begin=tuple(spec["begin"]), via=via, **entry)
         elif kind == "traverse":
-            out[agent_id] = TraverseMission(begin=tuple(spec["begin"]))
+            out[agent_id] = TraverseMission(begin=tuple(spec["begin"]), **entry)
         else:
             raise ValueError(f"mission of {agent_id!r}: unknown type {kind!r}")
     return out
+
+
+# ---- delayed entry (Mission.start_time + TrapEntryTactic; trap_manager.py:53-65, 121-241, smarts.py:259-301, 426-434)
+def entry_ticks(start_time: float, patience: float, dt: float) -> int:
+    """The simulation step on which a pending agent's trap lets it enter, counted from the first step of ``reset()``
+    (step 1): the trap holds ``remaining = start_time``, every step does ``remaining -= dt`` first (``Trap.step_trigger``,
+    also in the steps ``reset()`` burns), and without a capture the agent enters once ``remaining < -patience``
+    (``patience_expired``, which implies ``ready``).  The repeated float64 subtraction, not ``start_time / dt``:
+    with ``dt = 0.1`` a start time of 0.3 s fires on step 3, where ``floor(t / dt + 1e-9) + 1`` says 4."""
+    remaining, patience, dt = float(start_time), float(patience), float(dt)
+    if not (dt > 0 and math.isfinite(dt)) or not math.isfinite(remaining) or not math.isfinite(patience):
+        raise ValueError(f"entry_ticks needs finite start_time and patience and dt > 0, not {start_time!r}, {patience!r}, {dt!r}")
+    step = 0
+    while True:
+        step += 1
+        remaining -= dt
+        if remaining < -patience:
+            return step
+
+
+def _entry_of(mission) -> Tuple[float, float, Optional[float]]:
+    """(start_time, patience, default_entry_speed) of a mission; ``None`` is the reference's default mission
+    (start_time 0.1, ``default_entry_tactic()``: patience 0, trap_manager.py:94-95)."""
+    if mission is None:
+        return 0.1, 0.0, None
+    tactic = getattr(mission, "entry_tactic", None)
+    if tactic is not None and not isinstance(tactic, TrapEntryTactic):
+        raise TypeError(f"entry_tactic must be a TrapEntryTactic, not {type(tactic).__name__}")  # trap_manager.py:97-101
+    start_time = float(getattr(mission, "start_time", 0.1))
+    if tactic is None:
+        return start_time, 0.0, None
+    speed = None if tactic.default_entry_speed is None else float(tactic.default_entry_speed)
+    return start_time, float(tactic.wait_to_hijack_limit_s), speed
+
+
+@dataclass(frozen=True)
+class EntryTable:
+    """What ``entry_table`` returns: the two tables ``BatchedSim.set_agent_entry`` takes, the steps the reset burns
+    (``SimConfig(entry_reset_steps=...)``) and each agent's entry speed (``None``: the spawn row's)."""
+
+    ready: np.ndarray          # int32 (R, E, A): ticks from the reset observation, k_a - min k
+    check: np.ndarray          # float64 (R, E, A, 3): start point x, y (front bumper), largest plane dimension
+    reset_steps: int           # min over the agents of entry_ticks: the steps reset() burns
+    steps: Tuple[int, ...]     # entry_ticks of every agent
+    entry_speed: Tuple[Optional[float], ...]
+
+    @property
+    def differs(self) -> bool:
+        """Whether the agents' fire steps differ (only then is a table worth binding)."""
+        return len(set(self.steps)) > 1
+
+
+def entry_table(missions: Sequence, planned: Sequence[Optional[PlannedMission]], num_envs: int, dt: float,
+                agent_dims: Optional[np.ndarray] = None) -> EntryTable:
+    """The delayed-entry tables of a batch whose agent slot ``a`` flies mission ``missions[a]`` in every env (``None``:
+    the default mission, start 0.1 s, no patience), planned as ``planned[a]`` (``plan_mission``).  An agent that enters
+    after the reset observation needs its planned mission (the start point it keeps clear); one that enters with it is
+    never checked, and ``None`` leaves its check row at (0, 0).  ``agent_dims``: float64 ``(R, E, A, 3)`` as
+    ``BatchedSim.set_agent_dims`` takes it (NaN x 3 = the sedan's); its rows give the table its rows.
+      ready[r, e, a]     entry_ticks(start_time, patience, dt) - min over the agents: the reset observation is the
+                         first step on which some agent enters (smarts.py:426-434), so every (row, env) has a 0
+      check[r, e, a]     PlannedMission.start_position (the front bumper, plan.py:39-45) and max(length, width) of the
+                         new vehicle (Vehicle.agent_vehicle_dims: the agent_dims row where it has one, else the sedan's
+                         3.68 x 1.47)"""
+    A = len(missions)
+    if len(planned) != A:
+        raise ValueError("entry_table: one planned mission (or None) per mission")
+    if A < 1:
+        raise ValueError("entry_table: no agents")
+    entries = [_entry_of(m) for m in missions]
+    steps = tuple(entry_ticks(t, p, dt) for t, p, _ in entries)
+    first = min(steps)
+    rows = 1
+    if agent_dims is not None:
+        agent_dims = np.asarray(agent_dims, dtype=np.float64)
+        if agent_dims.ndim != 4 or tuple(agent_dims.shape[1:]) != (num_envs, A, 3) or agent_dims.shape[0] < 1:
+            raise ValueError(f"agent_dims must have shape (R, {num_envs}, {A}, 3), got {tuple(agent_dims.shape)}")
+        rows = agent_dims.shape[0]
+    ready = np.zeros((rows, num_envs, A), dtype=np.int32)
+    check = np.zeros((rows, num_envs, A, 3), dtype=np.float64)
+    for a in range(A):
+        ready[:, :, a] = steps[a] - first
+        pm = planned[a]
+        if pm is None and steps[a] != first:
+            raise ValueError(f"entry_table: agent {a} enters {steps[a] - first} ticks after the reset observation and has "
+                             "no planned mission (no start point to keep clear)")
+        if pm is not None:
+            check[:, :, a, 0], check[:, :, a, 1] = pm.start_position
+        check[:, :, a, 2] = max(CHASSIS_LENGTH, CHASSIS_WIDTH)
+        if agent_dims is not None:
+            own = agent_dims[:, :, a, :]
+            has = ~np.isnan(own[..., 0])
+            check[:, :, a, 2] = np.where(has, np.maximum(own[..., 0], own[..., 1]), check[:, :, a, 2])
+    return EntryTable(ready, check, first, steps, tuple(speed for _, _, speed in entries))
