@@ -921,6 +921,32 @@ typedef struct smx_agent_entry {
 enum { SMX_ENTRY_PENDING = 0, SMX_ENTRY_BLOCKED = 1, SMX_ENTRY_ENTERED = 2 };
 int smx_set_agent_entry(smx_handle h, const smx_agent_entry* entry);
 int smx_check_agent_entry(const smx_config* cfg, const smx_agent_entry* entry, char* err, uint64_t err_len);
+/* Per-agent action spaces (every agent of the reference brings its own AgentInterface, agent_interface.py:300-330; the
+ * controller is chosen per agent, smarts.py:1233-1263 over controllers/__init__.py:61-152).  Opt-in: with nothing bound
+ * every agent has cfg.action_space, as before.  space_host[a] is the SMX_ACTION_SPACE_* of agent slot a — the same in
+ * every env, as missions and vias are — and the six spaces that drive the Ackermann chassis may be mixed freely: LANE,
+ * CONTINUOUS, ACTUATOR_DYNAMIC, LANE_WITH_CONTINUOUS_SPEED, TRAJECTORY, MPC.  They share the state layout, the reset and
+ * the observation pass; only the control phase of smx_step_mixed reads the table.  A table whose entries are all equal
+ * is legal.  While a table is bound
+ *   - smx_step_mixed is the tick; smx_step, smx_step_continuous, smx_step_trajectory, smx_step_target_pose,
+ *     smx_step_trajectory_with_time, smx_step_history_agents and smx_step_history_handover return SMX_ERR_STATE (the
+ *     message names smx_step_mixed), and so does smx_actions_to_world (ego-frame actions of a mixed fleet are not built);
+ *   - smx_set_history_agents, smx_set_history_handover, smx_set_history_bubbles and smx_set_agent_dims return
+ *     SMX_ERR_STATE (they need a kinematic cfg.action_space, which a table is refused beside);
+ *   - the LARGE launch form is the teams cut, whatever the map (smx_launch_form reports it).
+ * Binding and unbinding need no reset: the controller's state words are per agent.  Rebinding in the middle of an episode
+ * leaves a slot's controller words (SMX_S_LAT_INT .. SMX_S_SPD_ERR, SMX_S_MCL_X / _Y, SMX_F_MCL_SET) with the meaning
+ * its previous space gave them; an smx_reset after rebinding is recommended.
+ * Refused (SMX_ERR_INVALID, the reason names the slot): a null table, n_agents != num_vehicles - num_social, an entry that
+ * is no SMX_ACTION_SPACE_* or is kinematic (TARGET_POSE, TRAJECTORY_WITH_TIME, IMITATION), a cfg.action_space that is
+ * itself kinematic.  The table is copied; spaces = NULL unbinds.  Waits for the device.  smx_check_agent_spaces is the
+ * validation alone, without a device or a handle. */
+typedef struct smx_agent_spaces {
+  const int32_t* space_host;   /* [n_agents] SMX_ACTION_SPACE_* per agent slot; the same in every env */
+  int32_t n_agents;            /* must equal num_vehicles - num_social */
+} smx_agent_spaces;
+int smx_set_agent_spaces(smx_handle h, const smx_agent_spaces* spaces);
+int smx_check_agent_spaces(const smx_config* cfg, const smx_agent_spaces* spaces, char* err, uint64_t err_len);
 /* Frame stacking (smx_config.frame_stack = k): for every agent the device keeps the last k frames of each bound row,
  * newest first (frame 0 is this pass's row), in a caller-owned device buffer.  At the end of every smx_reset / smx_step*
  * pass, on the caller's stream, once every row of the pass is complete (under auto_reset: after the reset pass has
@@ -984,6 +1010,21 @@ int smx_step_target_pose(smx_handle h, const double* targets_dev, const smx_stat
 int smx_step_trajectory_with_time(smx_handle h, const double* trajectories_dev, const int32_t* counts_dev,
                                   int32_t max_points, const smx_state* st, const smx_spawns* sp, const smx_outputs* out,
                                   void* hip_stream);
+/* The tick of a mixed fleet (smx_set_agent_spaces, above): every agent slot is stepped by the controller of its own
+ * space, from the buffer of that space's kind, each laid out over all E*N vehicles as its uniform entry has it.  "No
+ * action" keeps each space's convention: code -1, a NaN first float, count 0.  A Lane code outside -1..3 is reported by
+ * smx_sync for Lane slots only (no other slot's byte is read).  The buffer of a space the table does not hold may be
+ * NULL and is never read; SMX_ERR_INVALID when the buffer of a space it holds is NULL, SMX_ERR_STATE when no table is
+ * bound.  One launch (small form) or pair of launches (large form, lane spaces) per space present, all on hip_stream;
+ * the social slots are stepped once, by the launch of the lowest-numbered space present. */
+typedef struct smx_mixed_actions {
+  const int8_t*  lane_dev;          /* [E*N], as smx_step: read for Lane slots                                   */
+  const float*   floats_dev;        /* [E*N][3], as smx_step_continuous: Continuous / ActuatorDynamic / LWCS slots */
+  const double*  trajectories_dev;  /* [E*N][4][SMX_TRAJ_COLS] and                                               */
+  const int32_t* counts_dev;        /* [E*N], as smx_step_trajectory: Trajectory / MPC slots                     */
+} smx_mixed_actions;
+int smx_step_mixed(smx_handle h, const smx_mixed_actions* acts, const smx_state* st, const smx_spawns* sp,
+                   const smx_outputs* out, void* hip_stream);
 /* The action half of the ego-centric adapters (ego_centric_adapters.py:195-266): rewrites an action buffer given in the
  * frame of each agent's last observation (out->ego_frame, out->ec_flags: the last smx_reset / smx_step* pass) into
  * out_dev, a second caller-owned device buffer of the same layout, which the matching smx_step_* then takes.  One

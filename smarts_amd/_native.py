@@ -178,6 +178,19 @@ class SmxAgentEntry(C.Structure):  # smx_agent_entry (smx_set_agent_entry)
 ENTRY_PENDING, ENTRY_BLOCKED, ENTRY_ENTERED = 0, 1, 2  # SMX_ENTRY_*
 
 
+class SmxAgentSpaces(C.Structure):  # smx_agent_spaces (smx_set_agent_spaces)
+    _fields_ = [("space_host", _p), ("n_agents", _i32)]
+
+
+class SmxMixedActions(C.Structure):  # smx_mixed_actions (smx_step_mixed)
+    _fields_ = [("lane_dev", _p), ("floats_dev", _p), ("trajectories_dev", _p), ("counts_dev", _p)]
+
+
+# the spaces that drive the Ackermann chassis and may be mixed inside one env (smx_set_agent_spaces)
+MIXABLE_SPACES = ("Lane", "Continuous", "ActuatorDynamic", "LaneWithContinuousSpeed", "Trajectory", "MPC")
+FLOAT_SPACES = ("Continuous", "ActuatorDynamic", "LaneWithContinuousSpeed")
+
+
 class SmxSpawns(C.Structure):
     _fields_ = [("episodes", _i32), ("pose", _p), ("social", _p), ("pose_count", C.c_uint64), ("social_count", C.c_uint64)]
 
@@ -246,6 +259,7 @@ EXPORTS = [
     "smx_set_history_bubbles", "smx_check_history_bubbles",
     "smx_set_agent_dims", "smx_check_agent_dims",
     "smx_set_agent_entry", "smx_check_agent_entry",
+    "smx_set_agent_spaces", "smx_check_agent_spaces", "smx_step_mixed",
 ]
 LAUNCH_FORMS = {0: "small", 1: "large_teams", 2: "large_one_lane"}
 LAUNCH_STRATEGIES = {"auto": 0, "small": 1, "large": 2, "large_one_lane": 3, "large_teams": 4}
@@ -347,6 +361,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.smx_set_agent_entry.restype = C.c_int
     lib.smx_check_agent_entry.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxAgentEntry), C.c_char_p, C.c_uint64]
     lib.smx_check_agent_entry.restype = C.c_int
+    lib.smx_set_agent_spaces.argtypes = [h, C.POINTER(SmxAgentSpaces)]
+    lib.smx_set_agent_spaces.restype = C.c_int
+    lib.smx_check_agent_spaces.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxAgentSpaces), C.c_char_p, C.c_uint64]
+    lib.smx_check_agent_spaces.restype = C.c_int
+    lib.smx_step_mixed.argtypes = [h, C.POINTER(SmxMixedActions), C.POINTER(SmxState), C.POINTER(SmxSpawns), C.POINTER(SmxOutputs), _p]
+    lib.smx_step_mixed.restype = C.c_int
     lib.smx_set_history_agents.argtypes = [h, C.POINTER(SmxHistoryAgents)]
     lib.smx_set_history_agents.restype = C.c_int
     lib.smx_check_history_agents.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxSocialHistory), C.POINTER(SmxHistoryAgents),

@@ -19,8 +19,11 @@
 //                       move into a fresh triple block
 //       history agents  (bind or unbind) drop the handover table, the bubbles and the action / status rows
 //       a new map       also drops the agents' entry table (smx_set_agent_entry: its check points lie on the old map)
+//       agent spaces    (smx_set_agent_spaces, bind or unbind) drop nothing, and a new map keeps the table: it names agent
+//                       slots, nothing of the map
 //   What does not combine is refused, once, in entry_conflict below: the entry table beside history agents (and so their
-//   handover table and bubbles) or a frame stack — whichever is bound second is refused.
+//   handover table and bubbles) or a frame stack — whichever is bound second is refused; and in spaces_conflict: the
+//   kinematic bindings (history agents, handover, bubbles, agent dimensions) beside a table of agent spaces.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,6 +55,19 @@ struct EntryDev {
   int32_t rows;
   uint8_t* status;   // [E*N] SMX_ENTRY_*
   int32_t* entered;  // [E*N]
+};
+
+// What the control kernels of smx_step_mixed get of smx_set_agent_spaces (space null: none bound), all in one blob:
+//   space [N]      SMX_ACTION_SPACE_* of every slot of an env.  The social slots carry `owner`, the lowest-numbered space
+//                  present: that space's launch steps them, so they are stepped once however many launches a tick has.
+//   slots [S][N]   per space s (S = SMX_ACTION_SPACE_IMITATION + 1) the slots whose entry in `space` is s, ascending —
+//                  the owner's list ends with the social slots — and count[s] how many (the small form's slot lists)
+struct AgentSpacesDev {
+  const int32_t* space;
+  const int32_t* slots;
+  int32_t count[SMX_ACTION_SPACE_IMITATION + 1];
+  unsigned mask;  // bit s: some AGENT slot has space s
+  int32_t owner;
 };
 
 // One device allocation: allocates, frees in its destructor, reset() frees now, get<T>() reads the pointer.
@@ -238,6 +254,8 @@ struct smx_handle_s {
   // a table was bound or unbound since the last smx_reset of every env: the status rows do not describe the episodes yet,
   // so steps are refused until one (enqueue clears it)
   bool entry_reset_needed;
+  DeviceBlob spaces_blob;  // smx_set_agent_spaces: device copy of the table and its slot lists (null: none bound)
+  AgentSpacesDev spaces;   // ... and what the control kernels of smx_step_mixed get (space null: none bound)
   struct StackBinding {  // smx_bind_frame_stack: one caller-owned stack per (source, layout)
     int32_t source, layout;
     uint8_t* dst;
@@ -379,6 +397,41 @@ static const char* entry_conflict(const smx_handle_s* h, Binding b) {
       return h->entry.ready != nullptr ? "frame stack: delayed agent entry is bound (smx_set_agent_entry)" : nullptr;
   }
   return nullptr;
+}
+
+static void unbind_agent_spaces(smx_handle h) {
+  h->spaces_blob.reset();
+  h->spaces = AgentSpacesDev{};
+}
+// The bindings a table of agent spaces is not taken beside (include/smx.h smx_set_agent_spaces): they make some agent a
+// kinematic one.  This is the one place the rule stands: the other order, a table bound beside one of them, does not
+// occur, since their checks ask for a kinematic cfg.action_space and the table's check refuses one.
+static int spaces_conflict(smx_handle h, const char* what) {  // SMX_OK: no conflict
+  if (h->spaces.space == nullptr) return SMX_OK;
+  return fail(h, SMX_ERR_STATE, std::string(what) + ": per-agent action spaces are bound (smx_set_agent_spaces): every slot of a mixed "
+                                                    "fleet drives the Ackermann chassis");
+}
+// Which tick entry a call may come through: smx_step_mixed with a table bound, the uniform entries without one.
+// `acts`: smx_step_mixed's argument (null: a uniform entry, `entry_name` says which).
+static int check_step_entry(smx_handle h, const char* entry_name, const smx_mixed_actions* acts, bool mixed_entry) {
+  if (!mixed_entry) {
+    if (h->spaces.space != nullptr)
+      return fail(h, SMX_ERR_STATE, std::string(entry_name) + ": per-agent action spaces are bound (smx_set_agent_spaces); the tick of a "
+                                    "mixed fleet is smx_step_mixed");
+    return SMX_OK;
+  }
+  if (h->spaces.space == nullptr) return fail(h, SMX_ERR_STATE, "smx_step_mixed: no table of agent spaces is bound (smx_set_agent_spaces)");
+  if (!acts) return fail(h, SMX_ERR_INVALID, "smx_step_mixed: acts is NULL");
+  const unsigned m = h->spaces.mask;
+  const unsigned floats = (1u << SMX_ACTION_SPACE_CONTINUOUS) | (1u << SMX_ACTION_SPACE_ACTUATOR_DYNAMIC) | (1u << SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED);
+  const unsigned tracking = (1u << SMX_ACTION_SPACE_TRAJECTORY) | (1u << SMX_ACTION_SPACE_MPC);
+  if ((m & (1u << SMX_ACTION_SPACE_LANE)) && !acts->lane_dev)
+    return fail(h, SMX_ERR_INVALID, "smx_step_mixed: the table holds Lane slots and lane_dev is NULL");
+  if ((m & floats) && !acts->floats_dev)
+    return fail(h, SMX_ERR_INVALID, "smx_step_mixed: the table holds Continuous / ActuatorDynamic / LaneWithContinuousSpeed slots and floats_dev is NULL");
+  if ((m & tracking) && (!acts->trajectories_dev || !acts->counts_dev))
+    return fail(h, SMX_ERR_INVALID, "smx_step_mixed: the table holds Trajectory / MPC slots and trajectories_dev or counts_dev is NULL");
+  return SMX_OK;
 }
 
 static void destroy_impl(smx_handle h) {
@@ -759,6 +812,7 @@ static int set_social_history_dims_impl(smx_handle h, const smx_social_dims* dim
 static int set_agent_dims_impl(smx_handle h, const smx_agent_dims* ad) {
   if (!h) return SMX_ERR_INVALID;
   if (ad) {
+    if (spaces_conflict(h, "agent dimensions") != SMX_OK) return SMX_ERR_STATE;
     std::string msg;
     const int rc = check_agent_dims_impl(h->cfg, *ad, msg);
     if (rc != SMX_OK) return fail(h, rc, msg);
@@ -789,6 +843,7 @@ static int set_agent_dims_impl(smx_handle h, const smx_agent_dims* ad) {
 static int set_history_agents_impl(smx_handle h, const smx_history_agents* ha) {
   if (!h) return SMX_ERR_INVALID;
   if (ha) {
+    if (spaces_conflict(h, "history agents") != SMX_OK) return SMX_ERR_STATE;
     if (h->history.vehicle == nullptr) return fail(h, SMX_ERR_STATE, "smx_set_history_agents needs a bound history (smx_set_social_history)");
     if (const char* why = entry_conflict(h, Binding::HISTORY_AGENTS)) return fail(h, SMX_ERR_STATE, why);
     std::string msg;
@@ -809,6 +864,7 @@ static int set_history_agents_impl(smx_handle h, const smx_history_agents* ha) {
 static int set_history_handover_impl(smx_handle h, const smx_history_handover* ho) {
   if (!h) return SMX_ERR_INVALID;
   if (ho) {
+    if (spaces_conflict(h, "history handover") != SMX_OK) return SMX_ERR_STATE;
     if (h->history.follow == nullptr) return fail(h, SMX_ERR_STATE, "smx_set_history_handover needs bound history agents (smx_set_history_agents)");
     std::string msg;
     const int rc = check_history_handover_impl(h->cfg, h->history.rows, *ho, msg);
@@ -825,6 +881,7 @@ static int set_history_bubbles_impl(smx_handle h, const smx_history_bubbles* hb)
   if (!h) return SMX_ERR_INVALID;
   BubbleSet set{};  // filled here, committed after the wait
   if (hb) {
+    if (spaces_conflict(h, "history bubbles") != SMX_OK) return SMX_ERR_STATE;
     if (h->history.follow == nullptr) return fail(h, SMX_ERR_STATE, "smx_set_history_bubbles needs bound history agents (smx_set_history_agents)");
     std::string msg;
     const int rc = check_history_bubbles_impl(h->cfg, *hb, msg);
@@ -870,6 +927,41 @@ static int set_agent_entry_impl(smx_handle h, const smx_agent_entry* en) {
   h->entry.rows = en->rows;
   h->entry.status = en->status_dev;
   h->entry.entered = en->entered_dev;
+  return SMX_OK;
+}
+
+// (a new map keeps the table: it names agent slots, nothing of the map.  No reset is needed either way: include/smx.h)
+static int set_agent_spaces_impl(smx_handle h, const smx_agent_spaces* as) {
+  if (!h) return SMX_ERR_INVALID;
+  constexpr int S = SMX_ACTION_SPACE_IMITATION + 1;
+  DeviceBlob blob;  // space [N] | slots [S][N], filled here, committed after the wait
+  AgentSpacesDev d{};
+  if (as) {
+    std::string msg;
+    const int rc = check_agent_spaces_impl(h->cfg, *as, msg);
+    if (rc != SMX_OK) return fail(h, rc, msg);
+  }
+  SMX_HIP(hipSetDevice(h->device));
+  if (as) {
+    const int32_t N = h->cfg.num_vehicles, agents = N - h->cfg.num_social;
+    d.mask = agent_spaces_mask(as->space_host, agents);
+    d.owner = __builtin_ctz(d.mask);
+    std::vector<int32_t> host((size_t)(1 + S) * N, -1);
+    for (int32_t slot = 0; slot < N; ++slot) {
+      const int32_t s = slot < agents ? as->space_host[slot] : d.owner;
+      host[slot] = s;
+      host[(size_t)(1 + s) * N + d.count[s]++] = slot;
+    }
+    SMX_HIP(blob.alloc(host.size() * sizeof(int32_t)));
+    SMX_HIP(hipMemcpy(blob.p, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old table
+  unbind_agent_spaces(h);
+  if (!as) return SMX_OK;
+  h->spaces_blob = std::move(blob);
+  d.space = h->spaces_blob.get<int32_t>();
+  d.slots = d.space + h->cfg.num_vehicles;
+  h->spaces = d;
   return SMX_OK;
 }
 

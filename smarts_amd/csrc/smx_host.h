@@ -491,6 +491,49 @@ inline int check_agent_entry_impl(const smx_config& c, const smx_agent_entry& d,
   return SMX_OK;
 }
 
+// ---- Per-agent action spaces (smx_set_agent_spaces / smx_check_agent_spaces) ----
+// The six spaces that drive the Ackermann chassis share the state layout, the reset and the observation pass, so only
+// the control phase reads the table; a kinematic agent's slot means something else to respawn_vehicle, the guard and the
+// observe role, which all read cfg.action_space: neither a kinematic entry nor a kinematic cfg.action_space is taken.
+static constexpr unsigned SMX_MIXABLE_SPACES =
+    (1u << SMX_ACTION_SPACE_LANE) | (1u << SMX_ACTION_SPACE_CONTINUOUS) | (1u << SMX_ACTION_SPACE_ACTUATOR_DYNAMIC) |
+    (1u << SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED) | (1u << SMX_ACTION_SPACE_TRAJECTORY) | (1u << SMX_ACTION_SPACE_MPC);
+inline const char* action_space_name(int32_t s) {
+  static const char* const names[] = {"Lane", "Continuous", "ActuatorDynamic", "LaneWithContinuousSpeed", "Trajectory",
+                                      "TargetPose", "TrajectoryWithTime", "MPC", "Imitation"};
+  return (s >= 0 && s <= SMX_ACTION_SPACE_IMITATION) ? names[s] : "unknown";
+}
+inline int check_agent_spaces_impl(const smx_config& c, const smx_agent_spaces& d, std::string& err) {
+  if (c.num_vehicles <= 0 || c.num_social < 0 || c.num_social >= c.num_vehicles)
+    return refuse(err, "agent spaces: the configuration has no agents");
+  if (c.action_space < 0 || c.action_space > SMX_ACTION_SPACE_IMITATION || !((SMX_MIXABLE_SPACES >> c.action_space) & 1u))
+    return refuse(err, std::string("agent spaces: cfg.action_space is ") + action_space_name(c.action_space) +
+                           ": a table is taken beside one of Lane, Continuous, ActuatorDynamic, LaneWithContinuousSpeed, "
+                           "Trajectory and MPC only (every slot of a kinematic configuration is a kinematic agent's)");
+  if (!d.space_host) return refuse(err, "agent spaces: null table (space_host)");
+  const int32_t agents = c.num_vehicles - c.num_social;
+  if (d.n_agents != agents)
+    return refuse(err, "agent spaces: n_agents is " + std::to_string(d.n_agents) + ", num_vehicles - num_social is " + std::to_string(agents) +
+                           " (slot " + std::to_string(d.n_agents < agents ? std::max(d.n_agents, 0) : agents) +
+                           (d.n_agents < agents ? " has no entry)" : " is no agent slot)"));
+  for (int32_t a = 0; a < agents; ++a) {
+    const int32_t s = d.space_host[a];
+    if (s < 0 || s > SMX_ACTION_SPACE_IMITATION)
+      return refuse(err, "agent spaces: slot " + std::to_string(a) + ": " + std::to_string(s) + " is no SMX_ACTION_SPACE_* value");
+    if (!((SMX_MIXABLE_SPACES >> s) & 1u))
+      return refuse(err, "agent spaces: slot " + std::to_string(a) + ": " + action_space_name(s) +
+                             " is a kinematic space; only Lane, Continuous, ActuatorDynamic, LaneWithContinuousSpeed, Trajectory and "
+                             "MPC may be mixed");
+  }
+  return SMX_OK;
+}
+// the spaces a table holds, bit s = SMX_ACTION_SPACE_* s (a checked table)
+inline unsigned agent_spaces_mask(const int32_t* space, int32_t n) {
+  unsigned m = 0;
+  for (int32_t a = 0; a < n; ++a) m |= 1u << space[a];
+  return m;
+}
+
 // ---- History agents (smx_set_history_agents / smx_check_history_agents) ----
 // The kernels index vehicle_dev by (episode mod rows, env, agent) and the two optional rows by vehicle: the counts are
 // checked against those shapes here; the ids the table holds are only ever compared.  `rows`: the bound history's.

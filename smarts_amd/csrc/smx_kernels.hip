@@ -359,11 +359,10 @@ __device__ __forceinline__ void ctrl_waypoints_from_knots(const KernelArgs& a, c
 // wavefronts per CU on large batches, so those keep the register form.
 // GUARD (every control kernel and k_reset / k_tail): the state guard as a compile-time choice — the plan launches the
 // GUARD instantiation while a guard buffer is bound, and the other one is the kernel without a guard, word for word.
-template <int SPACE, bool LDS_PATH = false, bool GUARD = false>
-__global__ void __attribute__((amdgpu_waves_per_eu(2, 8))) __launch_bounds__(SMX_BLOCK) k_control(const KernelArgs a) {
-  __shared__ int knot_scratch[SMX_MAX_KNOTS * SMX_BLOCK];
-  __shared__ double path_lds[LDS_PATH ? 3 * SMX_CTRL_WPS * SMX_BLOCK : 1];
-  int* knots = knot_scratch + threadIdx.x;
+// (the role: team lane threadIdx.x % SMX_WP_LANES of vehicle `gid`; k_control takes the vehicles in batch order,
+// k_control_slots — the tick of a mixed fleet — the slots of one action space)
+template <int SPACE, bool LDS_PATH, bool GUARD>
+__device__ __forceinline__ void control_one_for(const KernelArgs& a, const size_t gid, int* knots, double* path_lds) {
   // element (waypoint i, component q) of this lane's path: consecutive lanes, consecutive words
   auto path_put = [&](CtrlPath& p, int i, double x, double y, double h) {
     if (LDS_PATH) {
@@ -379,7 +378,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(2, 8))) __launch_bounds__(SMX
   const MapDev& m = a.map;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
   const int p0 = threadIdx.x % SMX_WP_LANES;
-  const size_t gid = ((size_t)blockIdx.x * SMX_BLOCK + threadIdx.x) / SMX_WP_LANES;
   if (gid >= total) return;  // whole teams leave together
   int flags = a.st.flags[gid];
   if (!(flags & SMX_F_ALIVE)) return;
@@ -497,6 +495,32 @@ __global__ void __attribute__((amdgpu_waves_per_eu(2, 8))) __launch_bounds__(SMX
   SMX_TACC(20, tc0, tc7);
 }
 
+template <int SPACE, bool LDS_PATH = false, bool GUARD = false>
+__global__ void __attribute__((amdgpu_waves_per_eu(2, 8))) __launch_bounds__(SMX_BLOCK) k_control(const KernelArgs a) {
+  __shared__ int knot_scratch[SMX_MAX_KNOTS * SMX_BLOCK];
+  __shared__ double path_lds[LDS_PATH ? 3 * SMX_CTRL_WPS * SMX_BLOCK : 1];
+  control_one_for<SPACE, LDS_PATH, GUARD>(a, ((size_t)blockIdx.x * SMX_BLOCK + threadIdx.x) / SMX_WP_LANES, knot_scratch + threadIdx.x, path_lds);
+}
+
+// The slots of ONE action space in a mixed fleet (smx_set_agent_spaces; the small form's tick of smx_step_mixed): team t
+// of the launch works on slot slots[t % n_slots] of env t / n_slots, so every wavefront is full of that space's agents
+// and an agent of another space costs the launch nothing.  The list of the space that owns the social slots ends with
+// them (smx_handle.h AgentSpacesDev): the role steps them as k_control does.
+struct SlotList {
+  const int32_t* slots;  // [n_slots] ascending slots of an env
+  int32_t n_slots;
+};
+template <int SPACE, bool GUARD = false>
+__global__ void __attribute__((amdgpu_waves_per_eu(2, 8))) __launch_bounds__(SMX_BLOCK) k_control_slots(const KernelArgs a, const SlotList sl) {
+  __shared__ int knot_scratch[SMX_MAX_KNOTS * SMX_BLOCK];
+  const size_t total = (size_t)a.cfg.num_envs * a.cfg.num_vehicles;
+  const size_t team = ((size_t)blockIdx.x * SMX_BLOCK + threadIdx.x) / SMX_WP_LANES;
+  const size_t env = team / (size_t)sl.n_slots;
+  // (past the last env: no vehicle — the role's own test; the slot is loaded from inside the list either way)
+  const size_t gid = env < (size_t)a.cfg.num_envs ? env * a.cfg.num_vehicles + (size_t)sl.slots[team % (size_t)sl.n_slots] : total;
+  control_one_for<SPACE, false, GUARD>(a, gid, knot_scratch + threadIdx.x, nullptr);
+}
+
 // =================================================================================
 // Large batches: the controller as two launches.  In k_control the control law and the 24 physics substeps
 // run on ONE lane of each vehicle's team of four (154 of its 223 us at 131 k vehicles, three quarters of the
@@ -598,6 +622,16 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_control_paths(const KernelArgs a,
   const size_t total = (size_t)a.cfg.num_envs * a.cfg.num_vehicles;
   control_paths_for<SPACE, GUARD>(a, ho, launch_vehicle(a, ((size_t)blockIdx.x * SMX_BLOCK + threadIdx.x) / SMX_WP_LANES, total), knot_scratch + threadIdx.x);
 }
+// ... of a mixed fleet (smx_step_mixed, large form): the same grid over the alive list, filtered by the table — a team
+// whose slot has another space leaves before the role loads anything of the vehicle.  `slot_space`: AgentSpacesDev::space.
+template <int SPACE, bool GUARD = false>
+__global__ void __launch_bounds__(SMX_BLOCK) k_control_paths_mixed(const KernelArgs a, const CtrlHandoff ho, const int32_t* slot_space) {
+  __shared__ int knot_scratch[SMX_MAX_KNOTS * SMX_BLOCK];
+  const size_t total = (size_t)a.cfg.num_envs * a.cfg.num_vehicles;
+  const size_t gid = launch_vehicle(a, ((size_t)blockIdx.x * SMX_BLOCK + threadIdx.x) / SMX_WP_LANES, total);
+  if (gid >= total || slot_space[gid % (size_t)a.cfg.num_vehicles] != SPACE) return;  // whole teams leave together
+  control_paths_for<SPACE, GUARD>(a, ho, gid, knot_scratch + threadIdx.x);
+}
 
 // Control law + vehicle dynamics, one lane per vehicle (see k_control_paths).  Every action space; the
 // lane-following ones read the wanted path from the hand-off.
@@ -665,6 +699,14 @@ __device__ __forceinline__ void control_law_for(const KernelArgs& a, const CtrlH
 template <int SPACE, bool GUARD = false>
 __global__ void __launch_bounds__(SMX_BLOCK) k_control_law(const KernelArgs a, const CtrlHandoff ho) {
   control_law_for<SPACE, GUARD>(a, ho, (size_t)blockIdx.x * SMX_BLOCK + threadIdx.x);
+}
+// ... of a mixed fleet (see k_control_paths_mixed): a lane whose slot has another space leaves before the role loads
+// anything of the vehicle.  The social slots carry the owner space in the table, so one launch of the tick steps them.
+template <int SPACE, bool GUARD = false>
+__global__ void __launch_bounds__(SMX_BLOCK) k_control_law_mixed(const KernelArgs a, const CtrlHandoff ho, const int32_t* slot_space) {
+  const size_t gid = (size_t)blockIdx.x * SMX_BLOCK + threadIdx.x;
+  if (slot_space[gid % (size_t)a.cfg.num_vehicles] != SPACE) return;
+  control_law_for<SPACE, GUARD>(a, ho, gid);
 }
 // =================================================================================
 // k_control_kinematic: the kinematic action spaces, one lane per vehicle, in the place of controller + vehicle_step.
@@ -4428,8 +4470,9 @@ extern "C" int smx_set_launch_strategy(smx_handle h, int strategy) {
 
 // What a call's plan (smx_plan.h) may depend on, read off the handle.  `st`: the caller's state block, for the carried
 // alive list (null: no tick is planned, only the form is asked for).
-// `follow`: the call is smx_step_history_agents; `handover`: smx_step_history_handover.
-static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_state* st, bool follow = false, bool handover = false) {
+// `follow`: the call is smx_step_history_agents; `handover`: smx_step_history_handover; `mixed`: smx_step_mixed.
+static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_state* st, bool follow = false, bool handover = false,
+                              bool mixed = false) {
   PlanInputs in{};
   in.cfg = &h->cfg;
   in.launch_strategy = h->launch_strategy;
@@ -4459,6 +4502,8 @@ static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_sta
   in.handover_entry = handover;
   in.bubbles_bound = h->bubble_state != nullptr;
   in.entry_bound = h->entry.ready != nullptr;
+  in.agent_spaces = h->spaces.space != nullptr ? h->spaces.mask : 0u;
+  in.mixed_entry = mixed;
   return in;
 }
 
@@ -4566,6 +4611,14 @@ extern "C" int smx_check_agent_entry(const smx_config* cfg, const smx_agent_entr
 }
 
 extern "C" int smx_set_agent_entry(smx_handle h, const smx_agent_entry* entry) { return set_agent_entry_impl(h, entry); }
+
+extern "C" int smx_check_agent_spaces(const smx_config* cfg, const smx_agent_spaces* spaces, char* err, uint64_t err_len) {
+  std::string msg;
+  const int rc = (cfg && spaces) ? check_agent_spaces_impl(*cfg, *spaces, msg) : refuse(msg, "agent spaces: null config / table");
+  return report(rc, msg, err, err_len);
+}
+
+extern "C" int smx_set_agent_spaces(smx_handle h, const smx_agent_spaces* spaces) { return set_agent_spaces_impl(h, spaces); }
 
 extern "C" int smx_check_history_agents(const smx_config* cfg, const smx_social_history* hist, const smx_history_agents* ha, char* err,
                                         uint64_t err_len) {
@@ -4705,6 +4758,55 @@ static ControlKernels control_kernels(int action_space) {
   }
 }
 
+// the controller kernels of one action space in a mixed fleet (smx_step_mixed; the six spaces of the Ackermann chassis)
+using SlotKernel = void (*)(KernelArgs, SlotList);
+using MixedKernel = void (*)(KernelArgs, CtrlHandoff, const int32_t*);
+struct MixedKernels {
+  SlotKernel one;
+  MixedKernel paths, law;  // (paths: the two lane spaces only)
+};
+template <int SPACE, bool GUARD>
+static MixedKernels mixed_kernels_of() {
+  MixedKernels k{k_control_slots<SPACE, GUARD>, nullptr, k_control_law_mixed<SPACE, GUARD>};
+  if constexpr (SPACE == SMX_ACTION_SPACE_LANE || SPACE == SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED)
+    k.paths = k_control_paths_mixed<SPACE, GUARD>;
+  return k;
+}
+template <bool GUARD>
+static MixedKernels mixed_kernels(int action_space) {
+  switch (action_space) {
+    case SMX_ACTION_SPACE_LANE: return mixed_kernels_of<SMX_ACTION_SPACE_LANE, GUARD>();
+    case SMX_ACTION_SPACE_CONTINUOUS: return mixed_kernels_of<SMX_ACTION_SPACE_CONTINUOUS, GUARD>();
+    case SMX_ACTION_SPACE_ACTUATOR_DYNAMIC: return mixed_kernels_of<SMX_ACTION_SPACE_ACTUATOR_DYNAMIC, GUARD>();
+    case SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED: return mixed_kernels_of<SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED, GUARD>();
+    case SMX_ACTION_SPACE_TRAJECTORY: return mixed_kernels_of<SMX_ACTION_SPACE_TRAJECTORY, GUARD>();
+    default: return mixed_kernels_of<SMX_ACTION_SPACE_MPC, GUARD>();
+  }
+}
+// One launch, or pair of launches, per space present, all on the caller's stream; they touch disjoint vehicles, so their
+// order is free (ascending space numbers here).
+static void launch_control_mixed(smx_handle h, const TickPlan& p, const KernelArgs& a, hipStream_t stream) {
+  const AgentSpacesDev& sd = h->spaces;
+  for (int s = 0; s <= SMX_ACTION_SPACE_IMITATION; ++s) {
+    if (!((p.mixed_spaces >> s) & 1u)) continue;
+    const MixedKernels k = p.guard ? mixed_kernels<true>(s) : mixed_kernels<false>(s);
+    switch (p.control_of[s]) {
+      case Control::ONE: {
+        const SlotList sl{sd.slots + (size_t)s * h->cfg.num_vehicles, sd.count[s]};
+        const unsigned blocks = smx_blocks((size_t)h->cfg.num_envs * sd.count[s], SMX_BLOCK / SMX_WP_LANES);
+        hipLaunchKernelGGL(k.one, dim3(blocks), dim3(SMX_BLOCK), 0, stream, a, sl);
+        break;
+      }
+      case Control::PATHS_LAW:
+        hipLaunchKernelGGL(k.paths, dim3(p.wp_blocks), dim3(SMX_BLOCK), 0, stream, a, h->ctrl, sd.space);
+        hipLaunchKernelGGL(k.law, dim3(p.veh_blocks), dim3(SMX_BLOCK), 0, stream, a, h->ctrl, sd.space);
+        break;
+      case Control::LAW: hipLaunchKernelGGL(k.law, dim3(p.veh_blocks), dim3(SMX_BLOCK), 0, stream, a, h->ctrl, sd.space); break;
+      default: break;
+    }
+  }
+}
+
 // what k_bubbles / k_bubbles_clear get of a call (only built with bubbles bound)
 static BubbleArgs bubble_args(const smx_handle_s* h, const KernelArgs& a) {
   BubbleArgs g{};
@@ -4727,6 +4829,7 @@ static void launch_control(smx_handle h, const TickPlan& p, const KernelArgs& a,
   const ControlKernels k = p.guard ? control_kernels<true>(h->cfg.action_space) : control_kernels<false>(h->cfg.action_space);
   switch (p.control) {
     case Control::NONE: break;
+    case Control::MIXED: launch_control_mixed(h, p, a, stream); break;
     case Control::ONE: launch(k.one, p.wp_blocks, 0, stream, a); break;
     case Control::ONE_LDS: launch(k.one_lds, p.wp_blocks, 0, stream, a); break;
     case Control::LAW: launch(k.law, p.veh_blocks, stream, a, h->ctrl); break;
@@ -5017,7 +5120,12 @@ static KernelArgs kernel_args(smx_handle h, const TickPlan& p, const int8_t* act
 }
 
 // which entry point a call came through (each hands over its own pointers and leaves the others null)
-enum class Entry { RESET, LANE, FLOATS, TRAJECTORY, TARGET_POSE, TRAJECTORY_WITH_TIME, HISTORY_AGENTS, HISTORY_HANDOVER };
+enum class Entry { RESET, LANE, FLOATS, TRAJECTORY, TARGET_POSE, TRAJECTORY_WITH_TIME, HISTORY_AGENTS, HISTORY_HANDOVER, MIXED };
+static const char* entry_name(Entry e) {
+  static const char* const names[] = {"smx_reset", "smx_step", "smx_step_continuous", "smx_step_trajectory", "smx_step_target_pose",
+                                      "smx_step_trajectory_with_time", "smx_step_history_agents", "smx_step_history_handover", "smx_step_mixed"};
+  return names[(int)e];
+}
 // (traj_max: columns per row of a TrajectoryWithTime action)
 static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const float* actions_f32, const double* traj,
                    const int32_t* traj_n, int32_t traj_max, const uint8_t* mask, const smx_state* st,
@@ -5027,14 +5135,19 @@ static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const
   int rc = check_buffers(h, st, sp, out);
   if (rc != SMX_OK) return rc;
   const bool is_step = entry != Entry::RESET;
-  const bool follow = entry == Entry::HISTORY_AGENTS, handover = entry == Entry::HISTORY_HANDOVER;
+  const bool follow = entry == Entry::HISTORY_AGENTS, handover = entry == Entry::HISTORY_HANDOVER, mixed = entry == Entry::MIXED;
+  if (is_step) {  // (smx_step_mixed with a table bound, the others without one; its buffers: smx_handle.h check_step_entry)
+    const smx_mixed_actions acts{actions, actions_f32, traj, traj_n};
+    rc = check_step_entry(h, entry_name(entry), mixed ? &acts : nullptr, mixed);
+    if (rc != SMX_OK) return rc;
+  }
   if (follow) {  // (the binding holds cfg.action_space to Imitation; the tick reads no action)
     if (h->history.follow == nullptr) return fail(h, SMX_ERR_STATE, "smx_step_history_agents: no history agents are bound (smx_set_history_agents)");
   } else if (handover) {  // (the binding holds cfg.action_space to Imitation; the driven agents' rows are read)
     if (h->history.follow == nullptr || (h->history.handover == nullptr && h->bubble_state == nullptr))
       return fail(h, SMX_ERR_STATE, "smx_step_history_handover: no handover table is bound (smx_set_history_handover)");
     if (actions_f32 == nullptr) return fail(h, SMX_ERR_INVALID, "smx_step_history_handover: actions_dev is NULL");
-  } else if (is_step) {
+  } else if (is_step && !mixed) {  // (smx_step_mixed's buffers were checked against the table above)
     const int sp_ = h->cfg.action_space;
     const bool ok = sp_ == SMX_ACTION_SPACE_LANE ? (entry == Entry::LANE && actions != nullptr)
                     : (sp_ == SMX_ACTION_SPACE_TRAJECTORY || sp_ == SMX_ACTION_SPACE_MPC)
@@ -5050,7 +5163,7 @@ static int enqueue(smx_handle h, const Entry entry, const int8_t* actions, const
                   "smx_step_trajectory_with_time: TrajectoryWithTime)");
   }
   hipStream_t stream = (hipStream_t)stream_;
-  const TickPlan p = tick_plan(plan_inputs(h, is_step, st, follow, handover));
+  const TickPlan p = tick_plan(plan_inputs(h, is_step, st, follow, handover, mixed));
   if (is_step && h->entry_reset_needed)
     return fail(h, SMX_ERR_STATE, "agent entry: smx_set_agent_entry bound or unbound a table since the last smx_reset of every "
                                   "env (env_mask NULL); step after one");
@@ -5159,10 +5272,20 @@ extern "C" int smx_step_trajectory_with_time(smx_handle h, const double* traject
   return enqueue(h, Entry::TRAJECTORY_WITH_TIME, nullptr, nullptr, trajectories_dev, counts_dev, max_points, nullptr, st, sp, out, hip_stream);
 }
 
+extern "C" int smx_step_mixed(smx_handle h, const smx_mixed_actions* acts, const smx_state* st, const smx_spawns* sp,
+                              const smx_outputs* out, void* hip_stream) {
+  if (!h) return SMX_ERR_INVALID;
+  if (!acts) return check_step_entry(h, "smx_step_mixed", nullptr, true);  // (no table: SMX_ERR_STATE; else the null argument)
+  return enqueue(h, Entry::MIXED, acts->lane_dev, acts->floats_dev, acts->trajectories_dev, acts->counts_dev, 0, nullptr, st, sp, out, hip_stream);
+}
+
 extern "C" int smx_actions_to_world(smx_handle h, int32_t action_space, const double* in_dev, const int32_t* counts_dev,
                                     int32_t max_points, double* out_dev, const smx_outputs* out, void* hip_stream) {
   if (!h) return SMX_ERR_INVALID;
   const smx_config& c = h->cfg;
+  if (h->spaces.space != nullptr)
+    return fail(h, SMX_ERR_STATE, "smx_actions_to_world: per-agent action spaces are bound (smx_set_agent_spaces); ego-frame actions of a "
+                                  "mixed fleet are not built");
   if (!(c.sensors & SMX_SENSOR_EGO_CENTRIC))
     return fail(h, SMX_ERR_STATE, "smx_actions_to_world: the configuration has no SMX_SENSOR_EGO_CENTRIC (no frame is kept)");
   const bool traj = action_space == SMX_ACTION_SPACE_TRAJECTORY || action_space == SMX_ACTION_SPACE_MPC;

@@ -97,6 +97,9 @@ struct PlanInputs {
   bool handover_entry;     // the call is smx_step_history_handover: each agent follows or is driven, as its handover tick says
   bool bubbles_bound;      // smx_set_history_bubbles holds bubbles: that call's tick starts with k_bubbles and reads its state row
   bool entry_bound;        // smx_set_agent_entry holds a table: pending agents enter inside a tick (k_entry)
+  // smx_set_agent_spaces holds a table: bit s = some agent slot has SMX_ACTION_SPACE_* s (0: none bound) ...
+  unsigned agent_spaces;
+  bool mixed_entry;        // ... and the call is smx_step_mixed, the only tick there is while one is bound
 };
 
 enum class AliveList : uint8_t { NONE, CARRIED, BUILD };  // BUILD: k_alive_list ahead of the tick
@@ -107,8 +110,10 @@ enum class AliveList : uint8_t { NONE, CARRIED, BUILD };  // BUILD: k_alive_list
 // control slow list); KINEMATIC_FOLLOW: its FOLLOW form, the tick of smx_step_history_agents — the same launch;
 // KINEMATIC_HANDOVER: its HANDOVER form, the tick of smx_step_history_handover — the same launch again;
 // KINEMATIC_BUBBLES: that tick with bubbles bound (smx_set_history_bubbles) — k_bubbles, then the BUBBLES form (it
-// stands first with its number: the older values keep theirs, and the line they end, which a test reads)
-enum class Control : uint8_t { KINEMATIC_BUBBLES = 9, NONE = 0, ONE, ONE_LDS, PATHS_LAW, LAW, FAST_LISTED, KINEMATIC, KINEMATIC_FOLLOW, KINEMATIC_HANDOVER };
+// stands first with its number: the older values keep theirs, and the line they end, which a test reads);
+// MIXED: the tick of smx_step_mixed over a table of several spaces (or one that is not cfg.action_space) — one launch or
+// pair of launches per space present, each in the form TickPlan::control_of names for it (it stands first as well)
+enum class Control : uint8_t { MIXED = 10, KINEMATIC_BUBBLES = 9, NONE = 0, ONE, ONE_LDS, PATHS_LAW, LAW, FAST_LISTED, KINEMATIC, KINEMATIC_FOLLOW, KINEMATIC_HANDOVER };
 static constexpr bool smx_kinematic_space(int action_space) {
   // (one mask test; smx_create holds action_space to 0 .. SMX_ACTION_SPACE_IMITATION)
   constexpr unsigned kinematic = (1u << SMX_ACTION_SPACE_TARGET_POSE) | (1u << SMX_ACTION_SPACE_TRAJECTORY_WITH_TIME) |
@@ -142,6 +147,13 @@ struct TickPlan {
   AliveList alive;
   int32_t* alive_zero;  // BUILD: the other parity's slow counters, zeroed by k_alive_list
   Control control;
+  // Control::MIXED: the spaces the table holds (PlanInputs::agent_spaces) and, per space present, the form its launches
+  // take — ONE in the small form (k_control_slots over the space's slot list), in the large form PATHS_LAW for the two
+  // lane spaces and LAW for the other four (the _mixed kernels, which filter by the table); NONE for a space not present.
+  // A table whose only space is cfg.action_space needs neither: the tick is the uniform one under the teams cut, `control`
+  // is its form and control_of names it too.
+  unsigned mixed_spaces;
+  Control control_of[SMX_ACTION_SPACE_IMITATION + 1];
   SlowRef control_slow;
   // Large batches, no per-kernel timing asked: the grid maps and the lidar (which read poses only) leave on
   // side stream 0 at once and overlap the scan — kernels bound by their own write stream beside one bound by
@@ -234,8 +246,10 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
   // of the vehicles would take the lists' serial forms (minicity, 262 144 vehicles: 1.40 ms a tick against 0.9x with
   // round 2's team kernels for everybody), so those maps keep the team kernels.  The strategies LARGE_ONE_LANE /
   // LARGE_TEAMS force a cut.
-  const bool one_lane_cut = in.launch_strategy == SMX_LAUNCH_LARGE_ONE_LANE ||
-                            (in.launch_strategy != SMX_LAUNCH_LARGE_TEAMS && (!in.map_junctions || SMX_ONE_LANE_ON_SPLIT_MAPS));
+  // A bound table of agent spaces acts like LARGE_TEAMS: k_control_fast / k_control_listed have no per-space forms.
+  const bool one_lane_cut = in.agent_spaces == 0 &&
+                            (in.launch_strategy == SMX_LAUNCH_LARGE_ONE_LANE ||
+                             (in.launch_strategy != SMX_LAUNCH_LARGE_TEAMS && (!in.map_junctions || SMX_ONE_LANE_ON_SPLIT_MAPS)));
   p.form = small ? SMX_FORM_SMALL : (in.alive_blob && in.slow.base && one_lane_cut) ? SMX_FORM_LARGE_ONE_LANE : SMX_FORM_LARGE_TEAMS;
   // the tick of the one-lane cut (not a reset call): one-lane kernels + teams over their slow lists
   const bool one_lane = in.is_step && p.form == SMX_FORM_LARGE_ONE_LANE;
@@ -263,6 +277,19 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
     p.control = !lane_space ? Control::LAW : one_lane ? Control::FAST_LISTED : Control::PATHS_LAW;
   else
     p.control = (lane_space && small && total * SMX_WP_LANES <= (size_t)1024 * 64) ? Control::ONE_LDS : Control::ONE;
+  if (in.is_step && in.mixed_entry && in.agent_spaces != 0) {
+    p.mixed_spaces = in.agent_spaces;
+    if (in.agent_spaces == (1u << c.action_space)) {
+      p.control_of[c.action_space] = p.control;
+    } else {
+      p.control = Control::MIXED;
+      for (int s = 0; s <= SMX_ACTION_SPACE_IMITATION; ++s) {
+        if (!((in.agent_spaces >> s) & 1u)) continue;
+        const bool lanes = s == SMX_ACTION_SPACE_LANE || s == SMX_ACTION_SPACE_LANE_WITH_CONTINUOUS_SPEED;
+        p.control_of[s] = (small || !in.ctrl_blob) ? Control::ONE : lanes ? Control::PATHS_LAW : Control::LAW;
+      }
+    }
+  }
 
   p.fork = in.is_step && !small && !p.phased && in.side_ready;
   p.scan_split = small || (in.debug_skip & SMX_SKIP_FORCE_SCAN_SPLIT);

@@ -261,6 +261,28 @@ def check_agent_dims(action_space: str, num_envs: int, num_vehicles: int, num_so
         raise ValueError(err.value.decode())
 
 
+def _agent_space_codes(spaces: Sequence[str]) -> np.ndarray:
+    unknown = [s for s in spaces if s not in nat.ACTION_SPACES]
+    if unknown:
+        raise ValueError(f"action space {unknown[0]!r} is not on the accelerated path (supported: {sorted(nat.ACTION_SPACES)})")
+    return np.ascontiguousarray([nat.ACTION_SPACES[s] for s in spaces], dtype=np.int32)
+
+
+def check_agent_spaces(action_space: str, num_vehicles: int, num_social: int, spaces: Sequence[str]) -> None:
+    """``smx_check_agent_spaces``: would ``smx_set_agent_spaces`` take ``spaces`` — one action space name per agent slot —
+    for a shard of this shape whose ``SimConfig.action_space`` is ``action_space``?  Needs the built library, no device
+    and no handle; raises ``ValueError`` with the library's reason when not."""
+    lib = nat.load_library()
+    codes = _agent_space_codes(list(spaces) + [action_space])
+    c = nat.SmxConfig()
+    c.num_envs, c.num_vehicles, c.num_social, c.action_space = 1, int(num_vehicles), int(num_social), int(codes[-1])
+    sp = nat.SmxAgentSpaces()
+    sp.space_host, sp.n_agents = codes.ctypes.data, len(codes) - 1
+    err = C.create_string_buffer(512)
+    if lib.smx_check_agent_spaces(C.byref(c), C.byref(sp), err, len(err)) != 0:
+        raise ValueError(err.value.decode())
+
+
 def check_agent_entry(num_envs: int, num_vehicles: int, num_social: int, ready_ticks: np.ndarray, check: np.ndarray) -> None:
     """``smx_check_agent_entry``: would ``smx_set_agent_entry`` take the int32 table ``ready_ticks`` ``(R, E, A)`` and the
     float64 table ``check`` ``(R, E, A, 3)`` for a shard of this shape?  Needs the built library, no device and no handle;
@@ -808,6 +830,60 @@ class BatchedSim:
         self.out["entry_status"] = status  # (written by every pass: they live as long as the binding)
         self.out["entered_tick"] = entered
 
+    def set_agent_spaces(self, spaces: Optional[Sequence[str]]):
+        """Bind per-agent action spaces (``smx_set_agent_spaces``): ``spaces[a]`` is the action space of agent slot ``a``
+        in every env — any of Lane, Continuous, ActuatorDynamic, LaneWithContinuousSpeed, Trajectory and MPC, mixed
+        freely.  While bound the tick is ``step_mixed``; ``step``, ``step_trajectory`` and the other uniform entries,
+        ``actions_to_world`` and the kinematic bindings (history agents, handover, bubbles, agent dimensions) raise, and a
+        large batch runs the teams cut.  No reset is needed; a slot that changes its space in the middle of an episode
+        keeps controller state of its previous space's meaning, so a ``reset()`` after rebinding is recommended.
+        ``None`` unbinds.  Refused with the library's reason (``SmxError``): a wrong length, a kinematic or unknown
+        entry, a kinematic ``SimConfig.action_space``."""
+        if spaces is None:
+            nat.check(self.lib, self.handle, self.lib.smx_set_agent_spaces(self.handle, None), "smx_set_agent_spaces")
+            self.agent_spaces = None
+            return
+        codes = _agent_space_codes(list(spaces))
+        sp = nat.SmxAgentSpaces()
+        sp.space_host, sp.n_agents = codes.ctypes.data, len(codes)
+        nat.check(self.lib, self.handle, self.lib.smx_set_agent_spaces(self.handle, C.byref(sp)), "smx_set_agent_spaces")
+        self.agent_spaces = tuple(spaces)
+
+    def step_mixed(self, lane: Optional[torch.Tensor] = None, floats: Optional[torch.Tensor] = None,
+                   trajectories: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """One tick of a mixed fleet (``smx_step_mixed``; ``set_agent_spaces`` first).  Each buffer is laid out over all
+        ``(E, N)`` vehicles as its uniform entry takes it, and a slot reads the buffer of its own space only: ``lane``
+        int8 ``(E, N)`` codes for Lane slots (-1 = no action), ``floats`` float32 ``(E, N, 3)`` for Continuous /
+        ActuatorDynamic / LaneWithContinuousSpeed slots (NaN first float = no action), ``trajectories`` float64
+        ``(E, N, 4, 11)`` with ``counts`` int32 ``(E, N)`` for Trajectory / MPC slots (count 0 = no action).  The buffer
+        of a space no slot has may be omitted; a missing buffer of a present space is a ``ValueError``."""
+        if not self._was_reset:
+            raise RuntimeError("step() before reset()")
+        if self.agent_spaces is None:
+            raise RuntimeError("step_mixed() without a table of agent spaces (set_agent_spaces)")
+        present = set(self.agent_spaces)
+        if "Lane" in present and lane is None:
+            raise ValueError("the fleet holds Lane agents: step_mixed needs lane")
+        if present & set(nat.FLOAT_SPACES) and floats is None:
+            raise ValueError(f"the fleet holds {sorted(present & set(nat.FLOAT_SPACES))} agents: step_mixed needs floats")
+        if present & {"Trajectory", "MPC"} and (trajectories is None or counts is None):
+            raise ValueError("the fleet holds Trajectory / MPC agents: step_mixed needs trajectories and counts")
+        acts = nat.SmxMixedActions()
+        keep = []  # (the converted tensors live until the call is issued)
+        for field, t, dtype, shape in (("lane_dev", lane, torch.int8, (self.E, self.N)),
+                                       ("floats_dev", floats, torch.float32, (self.E, self.N, 3)),
+                                       ("trajectories_dev", trajectories, torch.float64, (self.E, self.N, 4, nat.TRAJ_COLS)),
+                                       ("counts_dev", counts, torch.int32, (self.E, self.N))):
+            if t is None:
+                continue
+            if t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+                t = t.to(device=self.device, dtype=dtype).contiguous()
+            if tuple(t.shape) != shape:
+                raise ValueError(f"step_mixed: {field[:-4]} must have shape {shape}, got {tuple(t.shape)}")
+            keep.append(t)
+            setattr(acts, field, t.data_ptr())
+        return self._tick("smx_step_mixed", C.byref(acts))
+
     def set_history_agents(self, vehicle: Optional[torch.Tensor], expert_actions: bool = True):
         """Bind the history agents (``smx_set_history_agents``; needs ``action_space="Imitation"`` and a bound traffic
         history): agent slot ``a`` of env ``e`` follows recorded vehicle ``vehicle[k mod R, e, a]`` in episode ``k`` —
@@ -933,6 +1009,7 @@ class BatchedSim:
     history_dims = False
     agent_dims = None  # the bound (R, E, A, 3) table of set_agent_dims (a host copy), or None
     agent_entry = None  # the bound (ready ticks, check) tables of set_agent_entry (host copies), or None
+    agent_spaces = None  # the bound per-slot action space names of set_agent_spaces, or None
     traffic_history = None
     history_start_frames = None
     history_replaced = None

@@ -71,6 +71,45 @@ def encode_float_action(space: ActionSpaceType, action: Any):
     return vals
 
 
+# the action spaces whose agents may share one env (BatchedSim.set_agent_spaces; MPC is on the device too, but
+# AgentInterface.validate_for_device keeps it off the env layer)
+MIXED_ENV_SPACES = (ActionSpaceType.Lane, ActionSpaceType.Continuous, ActionSpaceType.ActuatorDynamic,
+                    ActionSpaceType.LaneWithContinuousSpeed, ActionSpaceType.Trajectory)
+
+
+def encode_mixed_actions(agent_ids: Sequence[str], agent_specs: Dict[str, AgentSpec], spaces: Sequence[ActionSpaceType],
+                         num_envs: int, slots: int, per_env_actions: Sequence[Dict[str, Any]]):
+    """Per-env ``{agent_id: action}`` dicts of a mixed fleet -> the buffers of ``BatchedSim.step_mixed``: every agent's
+    action goes through its own adapter and is encoded by its own space (``spaces[i]`` for ``agent_ids[i]``) into the
+    buffer of that space's kind.  Returns ``(lane, floats, trajectories, counts)`` over ``(num_envs, slots)``; an agent
+    without an action — absent from the dict, or adapted to ``None`` — keeps its space's "no action": code -1, NaN,
+    count 0.  Host code only."""
+    from ..engine import pack_trajectory
+
+    lane = np.full((num_envs, slots), NO_ACTION, dtype=np.int8)
+    floats = np.full((num_envs, slots, 3), np.nan, dtype=np.float32)
+    packed = np.zeros((num_envs, slots, 4, nat.TRAJ_COLS), dtype=np.float64)
+    counts = np.zeros((num_envs, slots), dtype=np.int32)
+    for e, agent_actions in enumerate(per_env_actions):
+        assert isinstance(agent_actions, dict) and all(isinstance(k, str) for k in agent_actions), \
+            "Expected Dict[str, any]"  # hiway_env.py:232-234
+        for agent_id, action in agent_actions.items():
+            adapted = agent_specs[agent_id].action_adapter(action)
+            i = agent_ids.index(agent_id)
+            if adapted is None:
+                continue
+            space = spaces[i]
+            if space is ActionSpaceType.Lane:
+                lane[e, i] = encode_lane_action(adapted)
+            elif space is ActionSpaceType.Trajectory or space is ActionSpaceType.MPC:
+                packed[e, i], counts[e, i] = pack_trajectory(adapted)
+            elif space in (ActionSpaceType.Continuous, ActionSpaceType.ActuatorDynamic, ActionSpaceType.LaneWithContinuousSpeed):
+                floats[e, i] = encode_float_action(space, adapted)
+            else:
+                raise ValueError(f"{space} agents cannot be part of a mixed fleet")
+    return lane, floats, packed, counts
+
+
 # paths kept per agent when the caller asks for the reference's full ``waypoint_paths`` (one path per
 # lane of the ego's road, plus junction branches; the shipped maps have at most 4 lanes per road)
 FULL_WINDOW_PATHS = 8
@@ -167,8 +206,22 @@ class BatchCore:
         if any(i is None for i in interfaces):
             raise ValueError("every AgentSpec needs an interface")
         first = interfaces[0]
-        if any(i != first for i in interfaces[1:]):
-            raise NotImplementedError("all agents of an accelerated env must share one AgentInterface")
+        # The agents may differ in their action space — a mixed fleet (BatchedSim.set_agent_spaces) — and in nothing else:
+        # sensors and done criteria are the shared part's.
+        if any(i.replace(action=first.action) != first for i in interfaces[1:]):
+            raise NotImplementedError("all agents of an accelerated env must share one AgentInterface (only the action "
+                                      "space may differ from agent to agent)")
+        self.agent_spaces: List[Optional[ActionSpaceType]] = [i.action for i in interfaces]
+        self.mixed = any(a is not first.action for a in self.agent_spaces[1:])
+        if self.mixed:
+            for agent_id, itf in zip(self.agent_ids, interfaces):
+                itf.validate_for_device()
+                if itf.action not in MIXED_ENV_SPACES:
+                    raise NotImplementedError(f"agent {agent_id!r}: {itf.action} cannot share an env with other action spaces "
+                                              f"(a mixed fleet takes {[a.name for a in MIXED_ENV_SPACES]})")
+            if ego_centric:
+                raise NotImplementedError("ego_centric=True with differing action spaces: ego-frame actions of a mixed fleet "
+                                          "are not built")
         self.interface: AgentInterface = first
         self.E, self.N, self.dt, self.seed = num_envs, len(self.agent_ids), dt, seed
         self.scenario_dir = resolve_scenario(scenario_dir)
@@ -267,6 +320,8 @@ class BatchCore:
                 if a in self.agent_dims:
                     table[0, :, i] = self.agent_dims[a]
             self.sim.set_agent_dims(table)
+        if self.mixed:
+            self.sim.set_agent_spaces([a.name for a in self.agent_spaces])
         if self.entry is not None:  # (the agent slots: the table's A is this core's N)
             self.sim.set_agent_entry(self.entry.ready, self.entry.check)
         self.traffic_history = None
@@ -331,6 +386,13 @@ class BatchCore:
 
         from ..engine import pack_trajectory
 
+        if self.mixed:
+            lane, floats, packed, counts = self.encode_mixed_actions(per_env_actions)
+            self._check_alive()
+            if not self._was_reset:
+                raise SMARTSNotSetupError("Must call reset() or setup() before stepping.")
+            return self.sim.step_mixed(torch.from_numpy(lane), torch.from_numpy(floats), torch.from_numpy(packed),
+                                       torch.from_numpy(counts))
         space = self.interface.action
         if space is ActionSpaceType.TargetPose or space is ActionSpaceType.TrajectoryWithTime:
             return self._step_kinematic(per_env_actions)
@@ -390,6 +452,11 @@ class BatchCore:
         for (e, i), a in adapted.items():
             trajs[e, i, :, :a.shape[1]], counts[e, i] = a, a.shape[1]
         return self.sim.step_trajectory_with_time(torch.from_numpy(trajs), torch.from_numpy(counts), ego_centric=self.ego_centric)
+
+    def encode_mixed_actions(self, per_env_actions: Sequence[Dict[str, Any]]):
+        """The buffers of ``BatchedSim.step_mixed`` for a mixed fleet's actions (``encode_mixed_actions`` above)."""
+        return encode_mixed_actions(self.agent_ids, self.agent_specs, self.agent_spaces, self.E, self.N + self.num_social,
+                                    per_env_actions)
 
     def encode_actions(self, per_env_actions: Sequence[Dict[str, Any]]) -> np.ndarray:
         space = self.interface.action

@@ -37,7 +37,9 @@ class ParallelEnv:
         sig = envs[0].signature()
         if any(e.signature() != sig for e in envs[1:]):
             # the reference raises ValueError when the spaces differ (parallel_env.py:160-188)
-            raise ValueError("environments of one accelerated batch must share scenario, agents, interface and timestep")
+            # (the signature holds one interface per agent: the agents of an env may differ in their action space —
+            # BatchCore — but agent i of every env must have the interface of agent i of the first)
+            raise ValueError("environments of one accelerated batch must share scenario, agents, each agent's interface and timestep")
         self._proto = envs[0]
         # every env replays its own window of the shared traffic history: column e holds env e's start frames
         starts = [e._history_start_frames for e in envs]
