@@ -805,3 +805,38 @@ __device__ __forceinline__ void zero_dense_rows(const KernelArgs& a, size_t gid,
     for (int k = t; k < c.lidar_rays * 3; k += nth) o.lidar_point[gid * (size_t)c.lidar_rays * 3 + k] = 0.0;
   }
 }
+
+// ---- team helpers: SMX_WP_LANES lanes per vehicle
+__device__ __forceinline__ int team_or(int v) {
+#pragma unroll
+  for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) v |= __shfl_xor(v, msk, SMX_WP_LANES);
+  return v;
+}
+
+// exclusive prefix of `cnt` over the team: the sum over the lanes below p0; `total`: the sum over the whole team
+__device__ __forceinline__ int team_exclusive_prefix(int cnt, int p0, int& total) {
+  int incl = cnt;
+  int t = __shfl_up(incl, 1, SMX_WP_LANES);
+  if (p0 >= 1) incl += t;
+  t = __shfl_up(incl, 2, SMX_WP_LANES);
+  if (p0 >= 2) incl += t;
+  total = __shfl(incl, SMX_WP_LANES - 1, SMX_WP_LANES);
+  return incl - cnt;
+}
+
+// nearest path over the team: smallest distance, then smallest number
+__device__ __forceinline__ void team_nearest(double& my_d, int& my_idx) {
+#pragma unroll
+  for (int msk = SMX_WP_LANES / 2; msk >= 1; msk >>= 1) {
+    const double od = __shfl_xor(my_d, msk, SMX_WP_LANES);
+    const int oi = __shfl_xor(my_idx, msk, SMX_WP_LANES);
+    if (od < my_d || (od == my_d && oi < my_idx)) {
+      my_d = od;
+      my_idx = oi;
+    }
+  }
+}
+
+// floor(e / d) for 0 <= e < 4096, 1 <= d <= 64, rcp = 1.0f / d: (e + 0.5) / d is at least 0.5 / d away from an integer,
+// the float32 product is off by less than 4096 / d * 2^-22
+__device__ __forceinline__ int small_quotient(int e, float rcp) { return (int)(((float)e + 0.5f) * rcp); }
