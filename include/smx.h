@@ -594,6 +594,49 @@ int smx_check_mission_goals(const smx_mission_goal* goals_host, int32_t n_slots,
                             int32_t map_lanes, char* err, uint64_t err_len);
 int smx_set_mission_goals(smx_handle h, const smx_mission_goal* goals_host, int32_t n_slots,
                           const double* lane_end_heading_host, const int32_t* lane_dead_end_host, int32_t n_lanes);
+/* A mission pool: missions per env and per episode, off unless bound (scenario.py:206-227, 292-294: a scenario's missions
+ * are handed out as variations, one after another, and every ParallelEnv worker runs its own cycle).  The pool is
+ * n_missions <= SMX_MISSION_POOL_MAX missions, each with what one slot has through the three calls above:
+ *   missions_host [n_missions] and route_roads_host [n_route_roads], as for smx_set_missions;
+ *   goals_host    [n_missions] as for smx_set_mission_goals, or NULL: every goal positional; the two lane tables and
+ *                 n_lanes as there (read only when some goal is SMX_GOAL_TRAVERSE);
+ *   vias_host     [n_vias] and via_off_host [n_missions + 1]: vias[via_off[m] .. via_off[m+1]) belong to mission m, at
+ *                 most 32 each; n_vias = 0: none (both may be NULL).  Needs cfg.via_max > 0 when n_vias > 0.
+ * Host pointers; the library keeps device copies.  The checks are those of the three calls, per pool entry.
+ *   rows_dev      int32 [rows][E][A] (A = num_vehicles - num_social), DEVICE memory owned by the caller, rows_count = the
+ *                 elements allocated (>= rows * E * A).  Agent a of env e has mission rows_dev[k mod rows][e][a] in
+ *                 episode k (the episode counter of smx_state::env_episode, as for smx_agent_dims).  -1 = an endless
+ *                 mission with an empty route and no vias, what a slot has before smx_set_missions.  Social slots have no
+ *                 entry and no mission.
+ * The library cannot check a device table, so the device is safe on its own: an entry outside -1 .. n_missions - 1 is
+ * read as -1, never indexes a table, and makes the next smx_sync return SMX_ERR_INVALID (once; the bit is cleared).
+ * The table is read by EVERY pass, wherever a mission is needed: rewriting the row of a running episode changes that
+ * agent's route, goal and vias in the middle of the episode (its via hits so far are kept by position in the list);
+ * rows of episodes not yet started may be rewritten freely — a curriculum sampled on the device.  The finishing tick of
+ * an episode reads the old episode's row; the reset pass, a restart inside the launch under auto_reset included, the
+ * new one's.
+ * The pool and the per-slot tables exclude each other: binding a pool drops what smx_set_missions /
+ * smx_set_mission_goals / smx_set_vias bound, and while a pool is bound those three return SMX_ERR_STATE.  pool = NULL
+ * unbinds: every mission is endless again, with no vias.  smx_load_map drops the pool as it drops the missions.  Waits
+ * for the device; not to be called between smx_step and the use of its outputs.
+ * smx_check_mission_pool is the validation alone, callable without a device or a handle (`map`: the tables of the map
+ * the pool is for; rows_dev is only tested for NULL): SMX_OK, or SMX_ERR_INVALID with the reason in err[err_len]. */
+#define SMX_MISSION_POOL_MAX 4096
+typedef struct smx_mission_pool {
+  const smx_mission* missions_host;
+  const int32_t* route_roads_host;
+  const smx_mission_goal* goals_host;
+  const double* lane_end_heading_host;
+  const int32_t* lane_dead_end_host;
+  const smx_via* vias_host;
+  const int32_t* via_off_host;
+  const int32_t* rows_dev;
+  uint64_t rows_count;
+  int32_t n_missions, n_route_roads, n_lanes, n_vias, rows, pad;
+} smx_mission_pool;
+int smx_set_mission_pool(smx_handle h, const smx_mission_pool* pool);
+int smx_check_mission_pool(const smx_config* cfg, const smx_map_tables* map, const smx_mission_pool* pool, char* err,
+                           uint64_t err_len);
 /* Base ray directions (device, [lidar_rays][3]); reference lidar.py:89-113 */
 int smx_set_lidar_rays(smx_handle h, const double* rays_dev, int32_t n_rays);
 /* The image buffer of SMX_SENSOR_RGB (device, caller-owned, [E*N][rgb_height][rgb_width][3] uint8; `count` = the bytes

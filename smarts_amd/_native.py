@@ -178,6 +178,15 @@ class SmxAgentEntry(C.Structure):  # smx_agent_entry (smx_set_agent_entry)
 ENTRY_PENDING, ENTRY_BLOCKED, ENTRY_ENTERED = 0, 1, 2  # SMX_ENTRY_*
 
 
+class SmxMissionPool(C.Structure):  # smx_mission_pool (smx_set_mission_pool)
+    _fields_ = [("missions_host", _p), ("route_roads_host", _p), ("goals_host", _p), ("lane_end_heading_host", _p),
+                ("lane_dead_end_host", _p), ("vias_host", _p), ("via_off_host", _p), ("rows_dev", _p), ("rows_count", C.c_uint64),
+                ("n_missions", _i32), ("n_route_roads", _i32), ("n_lanes", _i32), ("n_vias", _i32), ("rows", _i32), ("pad", _i32)]
+
+
+MISSION_POOL_MAX = 4096  # SMX_MISSION_POOL_MAX
+
+
 class SmxAgentSpaces(C.Structure):  # smx_agent_spaces (smx_set_agent_spaces)
     _fields_ = [("space_host", _p), ("n_agents", _i32)]
 
@@ -260,6 +269,7 @@ EXPORTS = [
     "smx_set_agent_dims", "smx_check_agent_dims",
     "smx_set_agent_entry", "smx_check_agent_entry",
     "smx_set_agent_spaces", "smx_check_agent_spaces", "smx_step_mixed",
+    "smx_set_mission_pool", "smx_check_mission_pool",
 ]
 LAUNCH_FORMS = {0: "small", 1: "large_teams", 2: "large_one_lane"}
 LAUNCH_STRATEGIES = {"auto": 0, "small": 1, "large": 2, "large_one_lane": 3, "large_teams": 4}
@@ -365,6 +375,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.smx_set_agent_spaces.restype = C.c_int
     lib.smx_check_agent_spaces.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxAgentSpaces), C.c_char_p, C.c_uint64]
     lib.smx_check_agent_spaces.restype = C.c_int
+    lib.smx_set_mission_pool.argtypes = [h, C.POINTER(SmxMissionPool)]
+    lib.smx_set_mission_pool.restype = C.c_int
+    lib.smx_check_mission_pool.argtypes = [C.POINTER(SmxConfig), C.POINTER(SmxMapTables), C.POINTER(SmxMissionPool), C.c_char_p, C.c_uint64]
+    lib.smx_check_mission_pool.restype = C.c_int
     lib.smx_step_mixed.argtypes = [h, C.POINTER(SmxMixedActions), C.POINTER(SmxState), C.POINTER(SmxSpawns), C.POINTER(SmxOutputs), _p]
     lib.smx_step_mixed.restype = C.c_int
     lib.smx_set_history_agents.argtypes = [h, C.POINTER(SmxHistoryAgents)]

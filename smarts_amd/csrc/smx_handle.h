@@ -14,6 +14,9 @@
 //       a new map       drops missions (-> goals), the history (-> dims, history agents -> handover) and the agents' dimensions;
 //                       keeps vias, lidar rays, the image buffer and the frame stacks; re-checks the guard margin
 //       new missions    drop the goals and invalidate the knot keys
+//       a mission pool  (smx_set_mission_pool, bind or unbind) drops the per-slot missions, goals and vias and invalidates
+//                       the knot keys; while it is bound the three per-slot calls are refused (SMX_ERR_STATE); a new map
+//                       drops it with its vias
 //       a new history   (bind or unbind) drops dims, history agents and handover, and the carried alive list; it keeps
 //                       the agents' dimensions (smx_set_agent_dims: they name no vehicle of the history), whose triples
 //                       move into a fresh triple block
@@ -336,7 +339,15 @@ static void unbind_goals(smx_handle h) {
   h->goals_blob.reset();
   h->missions.goal_kind = nullptr;
 }
+static void unbind_vias(smx_handle h) {
+  h->vias_dev.reset();
+  h->via_off_dev.reset();
+  h->n_vias = 0;
+}
+// (a mission pool — smx_set_mission_pool, missions.rows — lives in the blobs of the per-slot tables it excludes)
+static bool pool_bound(const smx_handle_s* h) { return h->missions.rows != nullptr; }
 static void unbind_missions(smx_handle h) {
+  if (pool_bound(h)) unbind_vias(h);  // a pool's vias are indexed by its missions: they go with it
   h->missions_blob.reset();
   unbind_goals(h);  // goal kinds go with the missions they refine
   h->host_route_last.clear();
@@ -569,6 +580,7 @@ static int load_map_impl(smx_handle h, const smx_map_tables* t) {
 
 static int set_vias_impl(smx_handle h, const smx_via* vias_host, int32_t n, const int32_t* slot_off_host) {
   if (!h) return SMX_ERR_INVALID;
+  if (pool_bound(h)) return fail(h, SMX_ERR_STATE, "smx_set_vias: a mission pool is bound (smx_set_mission_pool holds the vias; a NULL pool unbinds it)");
   if (n < 0 || (n > 0 && (!vias_host || !slot_off_host))) return fail(h, SMX_ERR_INVALID, "smx_set_vias: null table");
   if (n > 0 && h->cfg.via_max <= 0) return fail(h, SMX_ERR_INVALID, "smx_set_vias: cfg.via_max is 0");
   if (n > 0 && !h->map_loaded) return fail(h, SMX_ERR_STATE, "smx_set_vias needs the map (lane indices are checked)");
@@ -583,9 +595,7 @@ static int set_vias_impl(smx_handle h, const smx_via* vias_host, int32_t n, cons
         return fail(h, SMX_ERR_INVALID, "smx_set_vias: lane index out of range");
   }
   SMX_HIP(hipSetDevice(h->device));
-  h->vias_dev.reset();
-  h->via_off_dev.reset();
-  h->n_vias = 0;
+  unbind_vias(h);
   if (n == 0) return SMX_OK;
   DeviceBlob vias, offs;
   SMX_HIP(vias.alloc((size_t)n * sizeof(smx_via)));
@@ -601,6 +611,7 @@ static int set_vias_impl(smx_handle h, const smx_via* vias_host, int32_t n, cons
 static int set_missions_impl(smx_handle h, const smx_mission* missions_host, int32_t n_slots, const int32_t* route_roads_host,
                              int32_t n_route_roads) {
   if (!h) return SMX_ERR_INVALID;
+  if (pool_bound(h)) return fail(h, SMX_ERR_STATE, "smx_set_missions: a mission pool is bound (smx_set_mission_pool; a NULL pool unbinds it)");
   if (!h->map_loaded) return fail(h, SMX_ERR_STATE, "smx_set_missions needs the map (road indices are checked)");
   if (n_slots < 0 || n_route_roads < 0 || (n_slots > 0 && !missions_host) || (n_route_roads > 0 && !route_roads_host))
     return fail(h, SMX_ERR_INVALID, "smx_set_missions: null table");
@@ -641,6 +652,7 @@ static int set_missions_impl(smx_handle h, const smx_mission* missions_host, int
 static int set_mission_goals_impl(smx_handle h, const smx_mission_goal* goals_host, int32_t n_slots, const double* lane_end_heading_host,
                                   const int32_t* lane_dead_end_host, int32_t n_lanes) {
   if (!h) return SMX_ERR_INVALID;
+  if (pool_bound(h)) return fail(h, SMX_ERR_STATE, "smx_set_mission_goals: a mission pool is bound (smx_set_mission_pool holds the goal kinds; a NULL pool unbinds it)");
   if (!h->map_loaded) return fail(h, SMX_ERR_STATE, "smx_set_mission_goals needs the map (the lane tables are checked against it)");
   const int nv = h->cfg.num_vehicles, nl = h->map.n_lanes;
   const std::string msg = mission_goals_error(goals_host, n_slots, nv, lane_end_heading_host, lane_dead_end_host, n_lanes, nl);
@@ -663,6 +675,91 @@ static int set_mission_goals_impl(smx_handle h, const smx_mission_goal* goals_ho
   }
   h->goals_blob = std::move(blob);
   h->missions.goal_kind = (const smx_mission_goal*)base;
+  return SMX_OK;
+}
+
+// One table of a pool into a fresh allocation (`bytes` > 0)
+static hipError_t upload(DeviceBlob& dst, const void* src, size_t bytes) {
+  hipError_t e = dst.alloc(bytes);
+  if (e == hipSuccess) e = hipMemcpy(dst.p, src, bytes, hipMemcpyHostToDevice);
+  return e;
+}
+
+static int set_mission_pool_impl(smx_handle h, const smx_mission_pool* pool) {
+  if (!h) return SMX_ERR_INVALID;
+  const size_t key_bytes = 3 * (size_t)h->cfg.num_envs * h->cfg.num_vehicles * SMX_WP_LANES * sizeof(int32_t);
+  if (!pool) {  // unbind: every mission endless again, no vias
+    if (!pool_bound(h)) return SMX_OK;
+    SMX_HIP(hipSetDevice(h->device));
+    SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the tables
+    unbind_missions(h);
+    if (h->knots_blob && h->knots.key) SMX_HIP(hipMemset(h->knots.key, 0xff, key_bytes));
+    return SMX_OK;
+  }
+  if (!h->map_loaded) return fail(h, SMX_ERR_STATE, "smx_set_mission_pool needs the map (road and lane indices are checked)");
+  MissionPoolTables t;
+  const std::string msg = mission_pool_error(h->cfg, *pool, h->map.n_roads, h->map.n_lanes, h->host_lane_road, h->host_lane_out_off, h->host_lane_out_idx, t);
+  if (!msg.empty()) return fail(h, SMX_ERR_INVALID, msg);
+  SMX_HIP(hipSetDevice(h->device));
+  SMX_HIP(hipDeviceSynchronize());  // launches in flight still read the old tables
+  // the knot lists of the previous tick were walked under the old routes (harmless should a fill below fail: a list
+  // without a key is walked again)
+  if (h->knots_blob && h->knots.key) SMX_HIP(hipMemset(h->knots.key, 0xff, key_bytes));
+  const int M = pool->n_missions, nl = h->map.n_lanes;
+  // fill ...
+  DeviceBlob missions, goals, vias, offs;
+  size_t off_last = 0, off_pos = 0, off_lane = 0;
+  if (t.rt.any) {
+    const size_t goal_bytes = t.rt.goal.size() * sizeof(double), last_bytes = t.rt.last.size() * sizeof(int32_t),
+                 pos_bytes = t.rt.pos.size() * sizeof(int16_t);
+    off_last = goal_bytes, off_pos = (goal_bytes + last_bytes + 7) & ~(size_t)7;
+    off_lane = (off_pos + pos_bytes + 7) & ~(size_t)7;
+    SMX_HIP(missions.alloc(off_lane + t.rt.lane_ok.size()));
+    char* base = missions.get<char>();
+    SMX_HIP(hipMemcpy(base, t.rt.goal.data(), goal_bytes, hipMemcpyHostToDevice));
+    SMX_HIP(hipMemcpy(base + off_last, t.rt.last.data(), last_bytes, hipMemcpyHostToDevice));
+    SMX_HIP(hipMemcpy(base + off_pos, t.rt.pos.data(), pos_bytes, hipMemcpyHostToDevice));
+    SMX_HIP(hipMemcpy(base + off_lane, t.rt.lane_ok.data(), t.rt.lane_ok.size(), hipMemcpyHostToDevice));
+  }
+  if (!t.goals.empty()) {
+    const size_t kind_bytes = t.goals.size() * sizeof(smx_mission_goal);
+    const size_t head_bytes = t.traverse ? (size_t)nl * sizeof(double) : 0, dead_bytes = t.traverse ? (size_t)nl * sizeof(int32_t) : 0;
+    SMX_HIP(goals.alloc(kind_bytes + head_bytes + dead_bytes));
+    char* base = goals.get<char>();
+    SMX_HIP(hipMemcpy(base, t.goals.data(), kind_bytes, hipMemcpyHostToDevice));
+    if (t.traverse) {
+      SMX_HIP(hipMemcpy(base + kind_bytes, pool->lane_end_heading_host, head_bytes, hipMemcpyHostToDevice));
+      SMX_HIP(hipMemcpy(base + kind_bytes + head_bytes, pool->lane_dead_end_host, dead_bytes, hipMemcpyHostToDevice));
+    }
+  }
+  if (pool->n_vias > 0) {
+    SMX_HIP(upload(vias, pool->vias_host, (size_t)pool->n_vias * sizeof(smx_via)));
+    SMX_HIP(upload(offs, t.via_off.data(), t.via_off.size() * sizeof(int32_t)));
+  }
+  // ... then commit: the per-slot tables and vias go, the pool's take their places
+  unbind_missions(h);
+  unbind_vias(h);
+  h->host_route_last.clear();  // (smx_set_mission_goals is refused while the pool is bound)
+  if (missions) {
+    char* base = missions.get<char>();
+    h->missions_blob = std::move(missions);
+    h->missions.goal = (const double*)base;
+    h->missions.route_last = (const int32_t*)(base + off_last);
+    h->map.route_pos = (const int16_t*)(base + off_pos);
+    h->map.route_lane_ok = (const uint8_t*)(base + off_lane);
+  }
+  if (goals) {
+    h->missions.goal_kind = goals.get<smx_mission_goal>();
+    h->goals_blob = std::move(goals);
+  }
+  if (vias) {
+    h->vias_dev = std::move(vias);
+    h->via_off_dev = std::move(offs);
+    h->n_vias = pool->n_vias;
+  }
+  h->missions.rows = pool->rows_dev;
+  h->missions.n_rows = pool->rows;
+  h->missions.n = M;
   return SMX_OK;
 }
 

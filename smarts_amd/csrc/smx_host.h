@@ -867,3 +867,82 @@ inline const char* mission_goals_route_error(const smx_mission_goal* goals, int3
   }
   return nullptr;
 }
+
+// ---- Mission pool (smx_set_mission_pool) ----
+// What the handle copies to the device: every per-mission table with n_missions + 1 entries — the pool's missions and,
+// last, the endless mission that a table entry of -1 resolves to (MissionsDev, smx_roadmap.h).
+struct MissionPoolTables {
+  RouteTables rt;                       // [n_missions + 1] rows
+  std::vector<smx_mission_goal> goals;  // [n_missions + 1]; empty: every goal positional
+  std::vector<int32_t> via_off;         // [n_missions + 2]
+  bool traverse = false;                // some goal is a traverse goal: the two lane tables ride along
+};
+
+// The pool against the configuration and the map it is for (n_roads, n_lanes and the three lane tables of route_tables):
+// "" and the tables, or why the pool is refused.  The checks of smx_set_missions, smx_set_mission_goals and smx_set_vias
+// per pool entry; rows_dev, device memory, is tested for NULL and its declared size only.
+inline std::string mission_pool_error(const smx_config& c, const smx_mission_pool& p, int32_t n_roads, int32_t n_lanes,
+                                      const std::vector<int32_t>& lane_road, const std::vector<int32_t>& lane_out_off,
+                                      const std::vector<int32_t>& lane_out_idx, MissionPoolTables& out) {
+  const std::string at = "smx_set_mission_pool: ";
+  if (c.num_envs <= 0 || c.num_vehicles <= 0 || c.num_social < 0 || c.num_social >= c.num_vehicles)
+    return at + "the configuration has no agent slot";
+  const int M = p.n_missions;
+  if (M < 1 || M > SMX_MISSION_POOL_MAX) return at + "n_missions must be 1 .. SMX_MISSION_POOL_MAX (" SMX_STR(SMX_MISSION_POOL_MAX) ")";
+  if (!p.missions_host || p.n_route_roads < 0 || (p.n_route_roads > 0 && !p.route_roads_host)) return at + "null table (missions_host / route_roads_host)";
+  if (!p.rows_dev) return at + "null table (rows_dev)";
+  if (p.rows < 1) return at + "rows must be >= 1";
+  const uint64_t want = (uint64_t)p.rows * (uint64_t)c.num_envs * (uint64_t)(c.num_vehicles - c.num_social);
+  if (want > 0x7fffffffull) return at + "rows x num_envs x agents too large (the table is indexed with 32 bits)";
+  if (p.rows_count < want)
+    return at + "rows_dev holds " + std::to_string(p.rows_count) + " entries, rows x num_envs x agents needs " + std::to_string(want);
+  if (((size_t)M + 1) * (size_t)n_roads > 0x7fffffffull) return at + "missions x roads too large";
+  if (((size_t)M + 1) * (size_t)n_lanes > 0x7fffffffull) return at + "missions x lanes too large";  // (route_lane_ok's index)
+  std::vector<smx_mission> ms(p.missions_host, p.missions_host + M);
+  ms.push_back(smx_mission{});  // (route_len 0: the endless mission)
+  if (const char* why = route_tables(ms.data(), M + 1, p.route_roads_host, p.n_route_roads, n_roads, n_lanes, lane_road, lane_out_off, lane_out_idx, out.rt))
+    return at + why;
+  out.goals.clear();
+  out.traverse = false;
+  if (p.goals_host) {
+    const std::string msg = mission_goals_error(p.goals_host, M, M, p.lane_end_heading_host, p.lane_dead_end_host, p.n_lanes, n_lanes);
+    if (!msg.empty()) return at + msg;
+    bool any = false;
+    if (const char* why = mission_goals_route_error(p.goals_host, M, out.rt.last, any, out.traverse)) return at + why;
+    if (any) {
+      out.goals.assign(p.goals_host, p.goals_host + M);
+      out.goals.push_back(smx_mission_goal{SMX_GOAL_POSITIONAL, 0, 0.0});
+    }
+  }
+  if (p.n_vias < 0 || (p.n_vias > 0 && (!p.vias_host || !p.via_off_host))) return at + "null table (vias_host / via_off_host)";
+  if (p.n_vias > 0 && c.via_max <= 0) return at + "vias need cfg.via_max > 0";
+  out.via_off.assign((size_t)M + 2, p.n_vias);
+  if (p.n_vias > 0) {
+    if (p.via_off_host[0] != 0 || p.via_off_host[M] != p.n_vias) return at + "via offsets must run from 0 to n_vias";
+    for (int m = 0; m < M; ++m)
+      if (p.via_off_host[m + 1] < p.via_off_host[m] || p.via_off_host[m + 1] - p.via_off_host[m] > 32)
+        return at + "at most 32 vias per mission, offsets ascending (mission " + std::to_string(m) + ")";
+    for (int i = 0; i < p.n_vias; ++i)
+      if (p.vias_host[i].lane < 0 || p.vias_host[i].lane >= n_lanes) return at + "via lane index out of range";
+    std::copy(p.via_off_host, p.via_off_host + M + 1, out.via_off.begin());
+  }
+  return std::string();
+}
+
+// smx_check_mission_pool: the same against the host tables of the map
+inline int check_mission_pool_impl(const smx_config& c, const smx_map_tables& map, const smx_mission_pool& p, std::string& err) {
+  if (map.n_lanes <= 0 || map.n_roads <= 0 || !map.lane_road || !map.lane_out_off || !map.lane_out_idx)
+    return refuse(err, "smx_check_mission_pool: the map tables lack lane_road / lane_out_off / lane_out_idx");
+  const std::vector<int32_t> lane_road(map.lane_road, map.lane_road + map.n_lanes);
+  const std::vector<int32_t> lane_out_off(map.lane_out_off, map.lane_out_off + map.n_lanes + 1);
+  const std::vector<int32_t> lane_out_idx(map.lane_out_idx, map.lane_out_idx + lane_out_off[map.n_lanes]);
+  for (int32_t r : lane_road)
+    if (r < 0 || r >= map.n_roads) return refuse(err, "smx_check_mission_pool: lane_road out of range");
+  for (int l = 0; l < map.n_lanes; ++l)
+    if (lane_out_off[l] < 0 || lane_out_off[l + 1] < lane_out_off[l]) return refuse(err, "smx_check_mission_pool: lane_out_off not ascending");
+  for (int32_t l : lane_out_idx)
+    if (l < 0 || l >= map.n_lanes) return refuse(err, "smx_check_mission_pool: lane_out_idx out of range");
+  MissionPoolTables t;
+  const std::string msg = mission_pool_error(c, p, map.n_roads, map.n_lanes, lane_road, lane_out_off, lane_out_idx, t);
+  return msg.empty() ? SMX_OK : refuse(err, msg);
+}

@@ -19,7 +19,7 @@
 // one half of k_scan for one vehicle team (see k_scan)
 template <int TEAM, bool ROUTED, int SIZED = -1>
 __device__ __forceinline__ void scan_role(const KernelArgs& a, const MapDev& m, const smx_config& c, size_t gid,
-                                          size_t total, int rank, int flags, int role) {
+                                          size_t total, int rank, int flags, int role, const bool pooled = false) {
   SMX_TSTAMP(ts0);
   const VehState s = load_vehicle(a, gid, total);
   int32_t* fi = a.st.facts_i32;
@@ -114,7 +114,7 @@ __device__ __forceinline__ void scan_role(const KernelArgs& a, const MapDev& m, 
   }
   SMX_TSTAMP(ts4b);
   SMX_TACC(9, ts4, ts4b);
-  const PathSeeds seed = team_compute_path_seeds<TEAM, ROUTED>(m, s.x, s.y, s.heading, 5.0, true, t, sc, a.missions, (int)(gid % (size_t)c.num_vehicles), &guess);
+  const PathSeeds seed = team_compute_path_seeds<TEAM, ROUTED>(m, s.x, s.y, s.heading, 5.0, true, t, sc, a.missions, ROUTED ? mission_row(a, gid, pooled) : 0, &guess);
   // without the waypoints sensor the observation still takes the first waypoint of
   // waypoint_paths(pose, lookahead=1, within_radius=length) for the trip meter (sensors.py:270-275,
   // 349-351); TripMeterSensor.__init__ (sensors.py:885-898) asks the same on a new vehicle
@@ -171,6 +171,26 @@ __global__ void __attribute__((amdgpu_waves_per_eu(SPLIT ? 2 : SMX_SCAN_WAVES, 8
   }
 }
 
+// (... its pool instances, TickPlan::pool: the routed scan with the mission read through the pool's table)
+template <bool SPLIT>
+__global__ void __attribute__((amdgpu_waves_per_eu(SPLIT ? 2 : SMX_SCAN_WAVES, 8))) __launch_bounds__(SMX_BLOCK) k_scan_pool(const KernelArgs a) {
+  const smx_config& c = a.cfg;
+  const MapDev& m = a.map;
+  const size_t total = (size_t)c.num_envs * c.num_vehicles;
+  const size_t gid = ((size_t)(SPLIT ? (blockIdx.x >> 1) : blockIdx.x) * SMX_BLOCK + threadIdx.x) / SMX_TEAM;
+  const int rank = team_rank<SMX_TEAM>();
+  if (gid >= total) return;
+  const int flags = a.st.flags[gid];
+  if (!(flags & SMX_F_ALIVE)) return;
+  if (a.first_only && !(flags & SMX_F_FIRST)) return;
+  if (SPLIT) {
+    scan_role<SMX_TEAM, true>(a, m, c, gid, total, rank, flags, (blockIdx.x & 1) ? 1 : 0, true);
+  } else {
+    scan_role<SMX_TEAM, true>(a, m, c, gid, total, rank, flags, 0, true);
+    scan_role<SMX_TEAM, true>(a, m, c, gid, total, rank, flags, 1, true);
+  }
+}
+
 // One half of the scan as a launch of its own (large batches): the road facts feed the observe role only and
 // the path seeds the waypoint kernels only, so the two go to different streams and each keeps the registers
 // it needs (the facts half alone fits more wavefronts per SIMD than the pair).
@@ -187,6 +207,18 @@ __global__ void __attribute__((amdgpu_waves_per_eu(ROLE == 0 ? 4 : 3, 8))) __lau
   if (!(flags & SMX_F_ALIVE)) return;
   if (a.first_only && !(flags & SMX_F_FIRST)) return;
   scan_role<TEAM, ROUTED, SIZED ? 1 : 0>(a, a.map, c, gid, total, team_rank<TEAM>(), flags, ROLE);
+}
+// (... the seeds half's pool instance, TickPlan::pool)
+template <bool SIZED = false>
+__global__ void __attribute__((amdgpu_waves_per_eu(3, 8))) __launch_bounds__(SMX_BLOCK) k_scan_half_pool(const KernelArgs a) {
+  const smx_config& c = a.cfg;
+  const size_t total = (size_t)c.num_envs * c.num_vehicles;
+  const size_t gid = launch_vehicle(a, ((size_t)blockIdx.x * SMX_BLOCK + threadIdx.x) / SMX_TEAM_LARGE, total);
+  if (gid >= total) return;
+  const int flags = a.st.flags[gid];
+  if (!(flags & SMX_F_ALIVE)) return;
+  if (a.first_only && !(flags & SMX_F_FIRST)) return;
+  scan_role<SMX_TEAM_LARGE, true, SIZED ? 1 : 0>(a, a.map, c, gid, total, team_rank<SMX_TEAM_LARGE>(), flags, 1, true);
 }
 
 // k_scan_fast (large batches): one half of the scan with ONE lane per vehicle (smx_scan.h facts_one_lane /

@@ -276,14 +276,14 @@ __device__ __forceinline__ void trip_meter_store(const KernelArgs& a, size_t gid
 // the start, which may just have written it, and only when it is needed
 template <int KSTRIDE>
 __device__ __forceinline__ void trip_meter_update(const KernelArgs& a, size_t gid, size_t total, int flags, double px, double py,
-                                                  int* knots, const WpFirst& fw) {
+                                                  int* knots, const WpFirst& fw, const bool pooled) {
   double dist = SF(SMX_S_DIST);
   bool has_wp = a.st.facts_i32[(size_t)SMX_FI_TRIP_HAS_WP * total + gid] != 0;
   if (flags & SMX_F_FIRST) {
     has_wp = trip_meter_start<KSTRIDE>(a, gid, total, px, py, knots);
     dist = 0.0;
   }
-  const bool counts = fw.have && trip_counts_waypoint(a, a.map, gid, total);
+  const bool counts = fw.have && trip_counts_waypoint(a, a.map, gid, total, pooled);
   TripMeter t = trip_meter_of(dist, counts ? SF(SMX_S_TRIP_X) : 0.0, counts ? SF(SMX_S_TRIP_Y) : 0.0,
                               counts ? SF(SMX_S_TRIP_H) : 0.0, has_wp);
   if (counts) trip_meter_advance(a, gid, total, t, fw);
@@ -292,7 +292,7 @@ __device__ __forceinline__ void trip_meter_update(const KernelArgs& a, size_t gi
 
 // The serial emitter: every row of the vehicle and its trip meter, a team of SMX_WP_LANES lanes
 template <int KSTRIDE>
-__device__ __forceinline__ void waypoints_for(const KernelArgs& a, const size_t gid, int* knots) {
+__device__ __forceinline__ void waypoints_for(const KernelArgs& a, const size_t gid, int* knots, const bool pooled = false) {
   const smx_config& c = a.cfg;
   const MapDev& m = a.map;
   const size_t total = (size_t)c.num_envs * c.num_vehicles;
@@ -362,14 +362,14 @@ __device__ __forceinline__ void waypoints_for(const KernelArgs& a, const size_t 
   }
 
   if (p0 != 0) return;
-  trip_meter_update<KSTRIDE>(a, gid, total, flags, px, py, knots, fw);
+  trip_meter_update<KSTRIDE>(a, gid, total, flags, px, py, knots, fw, pooled);
   SMX_TSTAMP(tw3);
   SMX_TACC(3, tw0, tw3);
 }
 
-__device__ __forceinline__ void waypoints_role(const KernelArgs& a, const int block) {
+__device__ __forceinline__ void waypoints_role(const KernelArgs& a, const int block, const bool pooled = false) {
   __shared__ int knot_scratch[SMX_MAX_KNOTS * SMX_BLOCK];
-  waypoints_for<SMX_BLOCK>(a, ((size_t)block * SMX_BLOCK + threadIdx.x) / SMX_WP_LANES, knot_scratch + threadIdx.x);
+  waypoints_for<SMX_BLOCK>(a, ((size_t)block * SMX_BLOCK + threadIdx.x) / SMX_WP_LANES, knot_scratch + threadIdx.x, pooled);
 }
 
 // =================================================================================
@@ -568,7 +568,7 @@ struct __align__(16) WpStageCell {  // second pass: everything of a waypoint but
   signed char pad;
 };
 
-__device__ __forceinline__ void waypoints_tables_role(const KernelArgs& a, const int block) {
+__device__ __forceinline__ void waypoints_tables_role(const KernelArgs& a, const int block, const bool pooled = false) {
   extern __shared__ __align__(16) unsigned char stage_raw[];  // [wp_len][SMX_BLOCK] cells of 16 bytes
   __shared__ WpRowBook book;
   const smx_config& c = a.cfg;
@@ -757,7 +757,7 @@ __device__ __forceinline__ void waypoints_tables_role(const KernelArgs& a, const
   }
   SMX_TSTAMP(tw5);
   SMX_TACC(5, tw4, tw5);
-  if (live && p0 == 0) trip_meter_update<SMX_BLOCK>(a, gid, total, flags, px, py, knots, fw);
+  if (live && p0 == 0) trip_meter_update<SMX_BLOCK>(a, gid, total, flags, px, py, knots, fw, pooled);
   SMX_TSTAMP(tw6);
   SMX_TACC(3, tw0, tw6);
 }
@@ -799,7 +799,7 @@ struct WpKnotLanes {
 // the overflow area of one workgroup: per column SMX_WPE_KNOTS + 1 records, then as many lane pairs
 #define SMX_WPE_SPILL_GROUP_BYTES ((size_t)SMX_BLOCK * (SMX_WPE_KNOTS + 1) * (sizeof(WpKnot) + sizeof(WpKnotLanes)))
 
-__device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const int block) {
+__device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const int block, const bool pooled = false) {
   // 15.6 KB of LDS in all: ten workgroups per CU (its registers allow twelve: three wavefronts per SIMD)
   __shared__ WpKnot pool[SMX_WPE_POOL];
   __shared__ WpKnotLanes pool_lanes[SMX_WPE_POOL];
@@ -1316,7 +1316,7 @@ __device__ __forceinline__ void waypoints_emit_role(const KernelArgs& a, const i
   if (live && !slow_team && p0 == 0) {
     // the advance and the store, on the words loaded at the top (no new vehicle comes here: nothing to start)
     TripMeter t = trip_meter_of(trip_dist, trip_x, trip_y, trip_h, trip_has != 0);
-    if (tm.n_paths > 0 && trip_counts_waypoint(a, m, gid, total)) {
+    if (tm.n_paths > 0 && trip_counts_waypoint(a, m, gid, total, pooled)) {
       const WpFirst fw = {true, first_wp[v][0], first_wp[v][1], first_wp[v][2]};
       trip_meter_advance(a, gid, total, t, fw);
     }
@@ -1357,5 +1357,31 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_waypoints_walk_listed(const Kerne
       wp_walk_for(a, gid, (int)threadIdx.x % SMX_WP_LANES, false);
     else
       waypoints_for<SMX_BLOCK>(a, gid, knot_scratch + threadIdx.x);
+  }
+}
+
+// ---- the pool instances of the kernels above (TickPlan::pool; mission_row, smx_tick.h): the same roles with the trip
+// meter's on-route rule read through the pool's table
+__global__ void __launch_bounds__(SMX_BLOCK) k_waypoints_pool(const KernelArgs a) { waypoints_role(a, (int)blockIdx.x, true); }
+__global__ void __launch_bounds__(SMX_BLOCK) k_waypoints_tables_pool(const KernelArgs a) { waypoints_tables_role(a, (int)blockIdx.x, true); }
+__global__ void __launch_bounds__(SMX_BLOCK) k_waypoints_emit_pool(const KernelArgs a) { waypoints_emit_role(a, (int)blockIdx.x, true); }
+__global__ void __launch_bounds__(SMX_BLOCK) k_waypoints_listed_pool(const KernelArgs a) {
+  __shared__ int knot_scratch[SMX_MAX_KNOTS * SMX_BLOCK];
+  const int count = *a.slow_count;
+  constexpr int VPB = SMX_BLOCK / SMX_WP_LANES;
+  for (int i = (int)blockIdx.x * VPB + (int)threadIdx.x / SMX_WP_LANES; i < count; i += (int)gridDim.x * VPB)
+    waypoints_for<SMX_BLOCK>(a, (size_t)a.slow_list[i], knot_scratch + threadIdx.x, true);
+}
+__global__ void __launch_bounds__(SMX_BLOCK) k_waypoints_walk_listed_pool(const KernelArgs a) {
+  __shared__ int knot_scratch[SMX_MAX_KNOTS * SMX_BLOCK];
+  const int count = *a.slow_count;
+  constexpr int VPB = SMX_BLOCK / (2 * SMX_WP_LANES);
+  const bool walker = ((threadIdx.x / SMX_WP_LANES) & 1) != 0;
+  for (int i = (int)blockIdx.x * VPB + (int)threadIdx.x / (2 * SMX_WP_LANES); i < count; i += (int)gridDim.x * VPB) {
+    const size_t gid = (size_t)a.slow_list[i];
+    if (walker)
+      wp_walk_for(a, gid, (int)threadIdx.x % SMX_WP_LANES, false);
+    else
+      waypoints_for<SMX_BLOCK>(a, gid, knot_scratch + threadIdx.x, true);
   }
 }

@@ -131,8 +131,9 @@ __device__ inline bool drove_off_map(const MissionsDev& ms, const MapDev& m, int
 // row (sensors.py:465-476), and the flags / active / done / learner words the observe role derived from done.
 // (`tick`: the tick's commit, whose observe role saw every agent and wrote reward / done; k_tail's argument block is
 // the reset pass's, so first_only / keep_reward_done are read only for the reset pass's own commit)
-__device__ inline void lap_goal_gate(const KernelArgs& a, size_t gid, size_t total, int slot, bool tick) {
-  const smx_mission_goal g = a.missions.goal_kind[slot];
+// (`mission`: the slot's mission_row)
+__device__ inline void lap_goal_gate(const KernelArgs& a, size_t gid, size_t total, int mission, bool tick) {
+  const smx_mission_goal g = a.missions.goal_kind[mission];
   if (g.kind != SMX_GOAL_LAP) return;
   const smx_config& c = a.cfg;
   const smx_outputs& o = a.out;
@@ -160,7 +161,8 @@ __device__ inline void lap_goal_gate(const KernelArgs& a, size_t gid, size_t tot
 // (own_box: a triple block is bound, TickPlan::sized — the caller's literal; the copy without it keeps the observer's box
 // a constant.  A function argument and not a template argument: as a template the role's kernels without dimensions
 // took 27 registers more and spilled, profiles/r24_agent_dims_resources.txt)
-__device__ __forceinline__ void observe_role(const KernelArgs& a, const int block, const bool own_box) {
+// (pooled: the kernel is a pool instance, TickPlan::pool — a literal too; mission_row, smx_tick.h)
+__device__ __forceinline__ void observe_role(const KernelArgs& a, const int block, const bool own_box, const bool pooled = false) {
   const bool OWN_BOX = own_box;
   __shared__ SharedPose pose[SMX_BLOCK];
   __shared__ ObsStage stage;
@@ -472,8 +474,10 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
 
     // ---- via sensor (ViaSensor.__call__, sensors.py:1103-1146; acquisition range 40 m and speed
     //      tolerance 1.5 m/s from vehicle.py:553-557)
+    const int mission = mission_row(a, env, slot, pooled);
     if (c.via_max > 0 && a.vias != nullptr) {
-      const int v_a = a.via_slot_off[slot], v_b = a.via_slot_off[slot + 1];
+      const int via_row = mission;
+      const int v_a = a.via_slot_off[via_row], v_b = a.via_slot_off[via_row + 1];
       int32_t* consumed_p = a.st.facts_i32 + (size_t)SMX_FI_VIA_CONSUMED * total + gid;
       unsigned consumed = first ? 0u : (unsigned)*consumed_p;
       int hit = 0, cnt = 0;
@@ -520,17 +524,17 @@ __device__ __forceinline__ void observe_role(const KernelArgs& a, const int bloc
     // ---- events + done (sensors.py:443-489)
     // Mission.is_complete -> PositionalGoal.is_reached (plan.py:116-120, 220-222); EndlessGoal never (:76-84)
     RouteFilter route;
-    const bool fixed_route = route.fixed_route(a.missions, slot, m.n_roads);
+    const bool fixed_route = route.fixed_route(a.missions, mission, m.n_roads);
     bool reached_goal = false;
     if (fixed_route) {
-      const double gx = a.missions.goal[3 * slot], gy = a.missions.goal[3 * slot + 1], gr = a.missions.goal[3 * slot + 2];
+      const double gx = a.missions.goal[3 * mission], gy = a.missions.goal[3 * mission + 1], gr = a.missions.goal[3 * mission + 2];
       const double sqr_dist = (s.x - gx) * (s.x - gx) + (s.y - gy) * (s.y - gy);
       reached_goal = sqr_dist <= gr * gr;
     }
     // (a lap goal's distance condition waits for this tick's trip meter, which the waypoints role is still writing:
     // the commit role applies it, lap_goal_gate)
-    if (__builtin_expect(a.missions.goal_kind != nullptr, 0) && a.missions.goal_kind[slot].kind == SMX_GOAL_TRAVERSE)
-      reached_goal = drove_off_map(a.missions, m, n_veh, OWN_BOX ? ego_lane : my_lane, my_lane_dist, s.x, s.y, wrap_heading(s.heading));
+    if (__builtin_expect(a.missions.goal_kind != nullptr, 0) && a.missions.goal_kind[mission].kind == SMX_GOAL_TRAVERSE)
+      reached_goal = drove_off_map(a.missions, m, pooled ? a.missions.n + 1 : n_veh, OWN_BOX ? ego_lane : my_lane, my_lane_dist, s.x, s.y, wrap_heading(s.heading));
     const bool is_off_road = !(my_facts & SMX_FACT_ON_ROAD);           // sensors.py:498-500
     const bool is_on_shoulder = ((my_facts >> SMX_FACT_CORNER_SHIFT) & 15) != 15;  // sensors.py:502-509
     const bool reached_max = c.max_episode_steps > 0 && steps >= c.max_episode_steps;
@@ -710,7 +714,7 @@ __device__ __forceinline__ int history_commit(const KernelArgs& a, size_t gid, s
 }
 
 template <bool GUARD>
-__device__ __forceinline__ void commit_role(const KernelArgs& a, const int block, const bool tick) {
+__device__ __forceinline__ void commit_role(const KernelArgs& a, const int block, const bool tick, const bool pooled = false) {
   __shared__ int env_new_done[SMX_BLOCK];
   __shared__ int env_respawn[SMX_BLOCK];
   __shared__ int env_first_alive[SMX_BLOCK];
@@ -731,7 +735,7 @@ __device__ __forceinline__ void commit_role(const KernelArgs& a, const int block
   }
   __syncthreads();
   if (valid) {
-    if (__builtin_expect(a.missions.goal_kind != nullptr, 0)) lap_goal_gate(a, gid, total, slot, tick);
+    if (__builtin_expect(a.missions.goal_kind != nullptr, 0)) lap_goal_gate(a, gid, total, mission_row(a, env, slot, pooled), tick);
     const int old_flags = a.st.flags[gid];
     int new_flags = a.st.facts_i32[(size_t)SMX_FI_FLAGS_NEXT * total + gid];
     if constexpr (GUARD) {
@@ -816,12 +820,12 @@ __device__ __forceinline__ void commit_role(const KernelArgs& a, const int block
 // =================================================================================
 // (SIZED: a triple block is bound, TickPlan::sized — the observe role with the agent's own box)
 template <int SIZED>
-__device__ __forceinline__ void sensors_roles(const KernelArgs& a) {
+__device__ __forceinline__ void sensors_roles(const KernelArgs& a, const bool pooled = false) {
   const int b = (int)blockIdx.x;
   if (b < a.wp_blocks) {
-    waypoints_role(a, b);
+    waypoints_role(a, b, pooled);
   } else if (b < a.wp_blocks + a.obs_blocks) {
-    observe_role(a, b - a.wp_blocks, SIZED != 0);
+    observe_role(a, b - a.wp_blocks, SIZED != 0, pooled);
   } else if (b < a.wp_blocks + a.obs_blocks + a.lidar_blocks) {
     lidar_role<-1>(a, b - a.wp_blocks - a.obs_blocks);
   } else {
@@ -830,6 +834,9 @@ __device__ __forceinline__ void sensors_roles(const KernelArgs& a) {
 }
 __global__ void __launch_bounds__(SMX_BLOCK) k_sensors(const KernelArgs a) { sensors_roles<0>(a); }
 __global__ void __launch_bounds__(SMX_BLOCK) k_sensors_sized(const KernelArgs a) { sensors_roles<1>(a); }
+// (... their pool instances, TickPlan::pool)
+__global__ void __launch_bounds__(SMX_BLOCK) k_sensors_pool(const KernelArgs a) { sensors_roles<0>(a, true); }
+__global__ void __launch_bounds__(SMX_BLOCK) k_sensors_sized_pool(const KernelArgs a) { sensors_roles<1>(a, true); }
 
 // =================================================================================
 // k_first: the reset pass (first observations of re-created vehicles) as ONE launch.  A workgroup
@@ -844,7 +851,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_sensors_sized(const KernelArgs a)
 #define SMX_FIRST_BLOCK 512
 #define SMX_FIRST_WP_THREADS 256
 template <int SIZED>
-__device__ __forceinline__ void first_role(const KernelArgs& a, const int block) {
+__device__ __forceinline__ void first_role(const KernelArgs& a, const int block, const bool pooled = false) {
   __shared__ int knot_scratch[SMX_MAX_KNOTS * SMX_FIRST_WP_THREADS];
   const smx_config& c = a.cfg;
   const MapDev& m = a.map;
@@ -889,13 +896,13 @@ __device__ __forceinline__ void first_role(const KernelArgs& a, const int block)
           const size_t gid = g0 + (both ? (u >> 1) : u);
           const int half = both ? (int)(u & 1) : (turn == 0 ? 1 : 0);
           const int flags = a.st.flags[gid];
-          if ((flags & SMX_F_ALIVE) && (flags & SMX_F_FIRST)) scan_role<SMX_TEAM, true, SIZED>(a, m, c, gid, total, team_rank<SMX_TEAM>(), flags, half);
+          if ((flags & SMX_F_ALIVE) && (flags & SMX_F_FIRST)) scan_role<SMX_TEAM, true, SIZED>(a, m, c, gid, total, team_rank<SMX_TEAM>(), flags, half, pooled);
         }
       }
     } else if (turn == 1 && threadIdx.x < SMX_FIRST_WP_THREADS) {  // (whole wavefronts; waypoints_for holds no barrier)
       for (size_t base = g0; base < g1; base += SMX_FIRST_WP_THREADS / SMX_WP_LANES) {
         const size_t gid = base + threadIdx.x / SMX_WP_LANES;
-        if (gid < g1) waypoints_for<SMX_FIRST_WP_THREADS>(a, gid, knot_scratch + threadIdx.x);
+        if (gid < g1) waypoints_for<SMX_FIRST_WP_THREADS>(a, gid, knot_scratch + threadIdx.x, pooled);
       }
     }
     __threadfence();
@@ -904,7 +911,7 @@ __device__ __forceinline__ void first_role(const KernelArgs& a, const int block)
     SMX_TACC_ALL(turn == 0 ? 57 : 58, tt0, tt1);
   }
   SMX_TSTAMP(tk2);
-  observe_role(a, block, SIZED != 0);
+  observe_role(a, block, SIZED != 0, pooled);
   SMX_TSTAMP(tk3);
   SMX_TACC_ALL(59, tk2, tk3);
   if ((c.sensors & SMX_SENSOR_LIDAR) && a.lidar_blocks != 0)  // (0: the reset pass launched k_lidar for the new vehicles)
@@ -916,7 +923,7 @@ __device__ __forceinline__ void first_role(const KernelArgs& a, const int block)
   __syncthreads();
   // ---- commit
   SMX_TSTAMP(tk4);
-  commit_role<false>(a, block, false);  // (the reset pass's commit has no guard work: respawn_vehicle wrote the bytes)
+  commit_role<false>(a, block, false, pooled);  // (the reset pass's commit has no guard work: respawn_vehicle wrote the bytes)
   SMX_TSTAMP(tk5);
   SMX_TACC_ALL(60, tk4, tk5);
   SMX_TACC_ALL(61, tk0, tk5);
@@ -950,6 +957,15 @@ __global__ void __launch_bounds__(SMX_FIRST_BLOCK) k_first_sized(const KernelArg
   if ((int)blockIdx.x >= *n_groups) return;
   first_role<1>(a, groups[blockIdx.x]);
 }
+// (... their pool instances, TickPlan::pool)
+__global__ void __launch_bounds__(SMX_FIRST_BLOCK) k_first_pool(const KernelArgs a, const int32_t* groups, const int32_t* n_groups) {
+  if ((int)blockIdx.x >= *n_groups) return;
+  first_role<0>(a, groups[blockIdx.x], true);
+}
+__global__ void __launch_bounds__(SMX_FIRST_BLOCK) k_first_sized_pool(const KernelArgs a, const int32_t* groups, const int32_t* n_groups) {
+  if ((int)blockIdx.x >= *n_groups) return;
+  first_role<1>(a, groups[blockIdx.x], true);
+}
 
 // =================================================================================
 // k_road_waypoints: RoadWaypointsSensor (sensors.py:991-1040).  SMX_RW_LANE_CAP lanes of a wavefront share a
@@ -980,7 +996,7 @@ struct RwLanes {
   }
 };
 
-__global__ void __launch_bounds__(SMX_BLOCK) k_road_waypoints(const KernelArgs a) {
+__device__ __forceinline__ void road_waypoints_role(const KernelArgs& a, const bool pooled) {
   const smx_config& c = a.cfg;
   const MapDev& m = a.map;
   const smx_outputs& o = a.out;
@@ -1034,7 +1050,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_road_waypoints(const KernelArgs a
   int n_paths = 0;
   if (my_lane >= 0) {
     RouteFilter f;  // route = plan.route: a fixed route filters, the endless mission's empty route does not
-    f.fixed_route(a.missions, (int)(gid % (size_t)c.num_vehicles), m.n_roads);
+    f.fixed_route(a.missions, mission_row(a, gid, pooled), m.n_roads);
     // ---- paths_for_lane (sensors.py:1014-1040): depth first through the incoming lanes
     int st_lane[SMX_RW_STACK];
     double st_start[SMX_RW_STACK];
@@ -1093,6 +1109,9 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_road_waypoints(const KernelArgs a
   o.rw_path_count[lane_row] = (int16_t)n_paths;
   for (int p = min(n_paths, P); p < P; ++p) o.rw_count[lane_row * (size_t)P + p] = 0;
 }
+__global__ void __launch_bounds__(SMX_BLOCK) k_road_waypoints(const KernelArgs a) { road_waypoints_role(a, false); }
+// (... its pool instance, TickPlan::pool)
+__global__ void __launch_bounds__(SMX_BLOCK) k_road_waypoints_pool(const KernelArgs a) { road_waypoints_role(a, true); }
 
 // =================================================================================
 // k_lane_ttc: lane_ttc (custom_observations.py:148-280) of every agent with an observation, from the dense rows this
@@ -1655,8 +1674,8 @@ struct TailArgs {
   int32_t* slow_next;      // zeroed: the next tick's four slow-list counters
 };
 
-template <bool GUARD = false>
-__global__ void __launch_bounds__(SMX_BLOCK) k_tail(const KernelArgs a, const TailArgs t) {
+template <bool GUARD>
+__device__ __forceinline__ void tail_role(const KernelArgs& a, const TailArgs& t, const bool pooled) {
   const smx_config& c = a.cfg;
   const int block = (int)blockIdx.x;
   const int n_veh = c.num_vehicles;
@@ -1666,7 +1685,7 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_tail(const KernelArgs a, const Ta
   const size_t g1 = min(total, g0 + (size_t)epb * n_veh);
   const int lane = (int)threadIdx.x;
   const size_t gid = g0 + lane;
-  if (t.commit) commit_role<GUARD>(a, block, true);  // (lane l commits vehicle g0 + l: its flags word is read back below)
+  if (t.commit) commit_role<GUARD>(a, block, true, pooled);  // (lane l commits vehicle g0 + l: its flags word is read back below)
   if (block == 0 && lane == 0) {
     *t.n_groups_next = 0;
     if (t.list) {
@@ -1719,6 +1738,11 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_tail(const KernelArgs a, const Ta
     }
   }
 }
+template <bool GUARD = false>
+__global__ void __launch_bounds__(SMX_BLOCK) k_tail(const KernelArgs a, const TailArgs t) { tail_role<GUARD>(a, t, false); }
+// (... its pool instance, TickPlan::pool: the lap gate of the tick's commit reads the mission through the pool's table)
+template <bool GUARD = false>
+__global__ void __launch_bounds__(SMX_BLOCK) k_tail_pool(const KernelArgs a, const TailArgs t) { tail_role<GUARD>(a, t, true); }
 // (capped at 168 registers for a third wavefront per SIMD beside the waypoint kernels it spills 52 of them: 0.796 -> 0.806 ms)
 __global__ void __launch_bounds__(SMX_BLOCK) k_observe(const KernelArgs a) {
   SMX_TSTAMP(span0);
@@ -1733,6 +1757,9 @@ __global__ void __launch_bounds__(SMX_BLOCK) k_observe_sized(const KernelArgs a)
   SMX_TSTAMP(span1);
   SMX_TSPAN(5, span0, span1);
 }
+// (... their pool instances, TickPlan::pool)
+__global__ void __launch_bounds__(SMX_BLOCK) k_observe_pool(const KernelArgs a) { observe_role(a, (int)blockIdx.x, false, true); }
+__global__ void __launch_bounds__(SMX_BLOCK) k_observe_sized_pool(const KernelArgs a) { observe_role(a, (int)blockIdx.x, true, true); }
 
 // =================================================================================
 // k_reset: SMARTS.reset (smarts.py:365-460) for the selected envs — vehicles re-created at their
@@ -1888,7 +1915,8 @@ static PlanInputs plan_inputs(const smx_handle_s* h, bool is_step, const smx_sta
   in.launch_strategy = h->launch_strategy;
   in.map_junctions = h->map_junctions;
   in.slow_blocks = h->slow_blocks;
-  in.routed = h->missions.route_last != nullptr;
+  in.routed = h->missions.route_last != nullptr;  // (a mission pool: some pool entry has a fixed route)
+  in.pool_bound = h->missions.rows != nullptr;
   in.is_step = is_step;
   in.phase_timing = h->phase_timing && h->ph_used < 16384;
   in.side_ready = h->streams.ready;
@@ -1951,6 +1979,14 @@ extern "C" int smx_check_mission_goals(const smx_mission_goal* goals, int32_t n_
 extern "C" int smx_set_mission_goals(smx_handle h, const smx_mission_goal* goals_host, int32_t n_slots,
                                      const double* lane_end_heading_host, const int32_t* lane_dead_end_host, int32_t n_lanes) {
   return set_mission_goals_impl(h, goals_host, n_slots, lane_end_heading_host, lane_dead_end_host, n_lanes);
+}
+
+extern "C" int smx_set_mission_pool(smx_handle h, const smx_mission_pool* pool) { return set_mission_pool_impl(h, pool); }
+
+extern "C" int smx_check_mission_pool(const smx_config* cfg, const smx_map_tables* map, const smx_mission_pool* pool, char* err, uint64_t err_len) {
+  std::string msg;
+  const int rc = (cfg && map && pool) ? check_mission_pool_impl(*cfg, *map, *pool, msg) : refuse(msg, "null config, map or pool");
+  return report(rc, msg, err, err_len);
 }
 
 extern "C" int smx_set_lidar_rays(smx_handle h, const double* rays_dev, int32_t n_rays) { return set_lidar_rays_impl(h, rays_dev, n_rays); }
@@ -2119,8 +2155,23 @@ static int check_buffers(smx_handle h, const smx_state* st, const smx_spawns* sp
 // enqueue() issues a call's TickPlan (smx_plan.h) step by step; the steps launch what the plan names and decide nothing.
 using Kernel = void (*)(KernelArgs);
 using HandoffKernel = void (*)(KernelArgs, CtrlHandoff);
+// A kernel that reads a per-mission table has a pool instance (TickPlan::pool): the steps below name the kernel as they
+// always have, and while a pool is bound — a.missions.rows, which is what PlanInputs::pool_bound was read from — its
+// instance is launched in its place.  Kernels without such a site have none and are launched as they are.
+static Kernel pool_instance(Kernel k) {
+  static const struct { Kernel plain, pool; } twins[] = {
+      {k_scan<true, true>, k_scan_pool<true>}, {k_scan<false, true>, k_scan_pool<false>},
+      {k_scan_half<1, true>, k_scan_half_pool<false>}, {k_scan_half<1, true, SMX_TEAM_LARGE, true>, k_scan_half_pool<true>},
+      {k_sensors, k_sensors_pool}, {k_sensors_sized, k_sensors_sized_pool}, {k_observe, k_observe_pool}, {k_observe_sized, k_observe_sized_pool},
+      {k_waypoints, k_waypoints_pool}, {k_waypoints_tables, k_waypoints_tables_pool}, {k_waypoints_emit, k_waypoints_emit_pool},
+      {k_waypoints_listed, k_waypoints_listed_pool}, {k_waypoints_walk_listed, k_waypoints_walk_listed_pool},
+      {k_road_waypoints, k_road_waypoints_pool}};
+  for (const auto& t : twins)
+    if (t.plain == k) return t.pool;
+  return k;
+}
 static void launch(Kernel k, unsigned blocks, size_t lds, hipStream_t s, const KernelArgs& a) {
-  hipLaunchKernelGGL(k, dim3(blocks), dim3(SMX_BLOCK), lds, s, a);
+  hipLaunchKernelGGL(a.missions.rows != nullptr ? pool_instance(k) : k, dim3(blocks), dim3(SMX_BLOCK), lds, s, a);
 }
 static void launch(HandoffKernel k, unsigned blocks, hipStream_t s, const KernelArgs& a, const CtrlHandoff& ho) {
   hipLaunchKernelGGL(k, dim3(blocks), dim3(SMX_BLOCK), 0, s, a, ho);
@@ -2443,7 +2494,7 @@ static int tail_and_reset_pass(smx_handle h, const TickPlan& p, const KernelArgs
     t.flat_next = h->alive_blob.get<int32_t>() + al.flat + h->alive_parity;
     t.slow_next = SlowLists{h->slow_blob.get<int32_t>(), total}.counters(h->alive_parity);
   }
-  hipLaunchKernelGGL(p.guard ? k_tail<true> : k_tail<false>, dim3(p.obs_blocks), dim3(SMX_BLOCK), p.tail_grids ? std::max({p.ogm_bytes, p.dagm_bytes, p.rgb_lds}) : 0, stream, r, t);
+  hipLaunchKernelGGL(p.pool ? (p.guard ? k_tail_pool<true> : k_tail_pool<false>) : (p.guard ? k_tail<true> : k_tail<false>), dim3(p.obs_blocks), dim3(SMX_BLOCK), p.tail_grids ? std::max({p.ogm_bytes, p.dagm_bytes, p.rgb_lds}) : 0, stream, r, t);
   if (p.entry_first)  // (a large form's tick: this tick's entrants into the reset pass's groups, smx_k_entry.h)
     hipLaunchKernelGGL(k_entry_first, dim3(p.obs_blocks), dim3(SMX_BLOCK), 0, stream, r, t.groups, t.n_groups);
   if (ph) SMX_HIP(hipEventRecord(ph[SMX_PHASE_COMMIT + 1], stream));
@@ -2461,7 +2512,7 @@ static int tail_and_reset_pass(smx_handle h, const TickPlan& p, const KernelArgs
       r.lidar_blocks = 0;
     }
     r.walk_new = p.first_walks_new ? 1 : 0;
-    hipLaunchKernelGGL((p.sized ? k_first_sized : k_first), dim3(p.obs_blocks), dim3(SMX_FIRST_BLOCK), 0, stream, r, t.groups, t.n_groups);
+    hipLaunchKernelGGL(p.pool ? (p.sized ? k_first_sized_pool : k_first_pool) : (p.sized ? k_first_sized : k_first), dim3(p.obs_blocks), dim3(SMX_FIRST_BLOCK), 0, stream, r, t.groups, t.n_groups);
     if (p.lane_ttc)  // after k_first: it reads the first observations' rows, not SMX_F_FIRST
       hipLaunchKernelGGL(k_lane_ttc, dim3(p.ttc_first_blocks), dim3(SMX_BLOCK), p.ttc_lds, stream, r, (const int32_t*)t.groups, (const int32_t*)t.n_groups);
     if (p.ego_centric)
@@ -2748,6 +2799,10 @@ extern "C" int smx_sync(smx_handle h, void* hip_stream) {
                     "a TargetPose action whose pose is not finite reached smx_step_target_pose, or an Imitation action "
                     "with an infinite component or a pose or speed that is not finite reached smx_step_continuous, since the "
                     "last smx_sync; the agents that sent one were stepped as if they had sent no action");
+      if (bits & SMX_DEVICE_BAD_MISSION_ROW)
+        return fail(h, SMX_ERR_INVALID,
+                    "an entry outside -1 .. n_missions - 1 was read from the table of the mission pool (smx_set_mission_pool) "
+                    "since the last smx_sync; the agents it stood for had an endless mission, as for -1");
     }
   }
   return SMX_OK;

@@ -76,7 +76,8 @@ struct PlanInputs {
   int launch_strategy;  // SMX_LAUNCH_*
   bool map_junctions;   // lanes of the map split
   int slow_blocks;      // grid of the slow lists' kernels (smx_load_map)
-  bool routed;          // some slot has a fixed route: the scan instance that knows them
+  bool routed;          // some slot (with a mission pool: some pool entry) has a fixed route: the scan instance that knows them
+  bool pool_bound;      // smx_set_mission_pool holds a pool: the kernels' pool instances (mission_row, smx_tick.h)
   bool is_step;
   bool phase_timing;  // smx_set_timing level 2 (and room for this call's events): one boundary event after every kernel
   bool side_ready;
@@ -143,6 +144,7 @@ enum class Lidar : uint8_t { NONE, IN_SENSORS, SIDE, CALLER };
 struct TickPlan {
   int form;  // SMX_FORM_*
   bool is_step, phased, routed;
+  bool pool;  // the pool instances of the kernels that read a per-mission table (k_*_pool); without a pool the others, which hold no lookup
   bool social;  // k_social (IDM) ahead of the tick
   AliveList alive;
   int32_t* alive_zero;  // BUILD: the other parity's slow counters, zeroed by k_alive_list
@@ -234,6 +236,7 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
   p.is_step = in.is_step;
   p.phased = in.phase_timing && in.is_step;
   p.routed = in.routed;
+  p.pool = in.pool_bound;
   // Small batches are bound by one wavefront's latency, so independent work is spread over more
   // workgroups (k_scan halves as separate roles: 54 vs 70 us at 8 k vehicles; the OGM role inside
   // k_sensors); large batches are bound by throughput, where the same tricks cost occupancy
@@ -364,7 +367,7 @@ static inline TickPlan tick_plan(const PlanInputs& in) {
   // large batches: k_first also walks the new vehicles' knot lists, for the next tick's k_control_fast
   // (only k_control_fast reads them: not on the maps that keep the team kernels)
   // The table serves the lookaheads the controller's reuse is defined for (k_control_fast sends every vehicle to its slow
-  // list below that, with or without it), and batches without fixed routes: a route's filter names an agent slot, which
+  // list below that, with or without it), and batches without fixed routes: a route's filter names an agent slot (a pool row with a mission pool bound), which
   // no row is walked for, so with routes set the tick keeps the walked lists and every launch it had.
   const bool table = in.knot_table && !in.routed && staged && c.wp_lookahead >= 16;
   p.knot_table = table && one_lane;

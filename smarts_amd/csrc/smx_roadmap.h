@@ -290,6 +290,12 @@ struct MissionsDev {
   // smx_set_mission_goals, null: every goal positional.  One blob: [slots] kind / num_laps / route_length, then — the
   // lane facts of TraverseGoal — [n_lanes] end heading (double) and [n_lanes] dead end (int32)
   const smx_mission_goal* goal_kind;
+  // smx_set_mission_pool (rows null: no pool, the tables above are indexed by vehicle slot).  With a pool bound every
+  // table above — and the via offsets — has n + 1 entries: the pool's missions 0 .. n - 1 and, at n, the endless mission
+  // without a route, a goal or vias, which a table entry of -1 (or one outside -1 .. n - 1) and every social slot resolve
+  // to.  rows: the caller's device table [n_rows][E][A], read by every pass through mission_row (smx_tick.h) and nowhere else.
+  const int32_t* rows;
+  int32_t n_rows, n;
   __device__ __forceinline__ const double* lane_end_heading(int n_slots) const { return (const double*)(goal_kind + n_slots); }
   __device__ __forceinline__ const int32_t* lane_dead_end(int n_slots, int n_lanes) const {
     return (const int32_t*)(lane_end_heading(n_slots) + n_lanes);
@@ -300,8 +306,8 @@ struct MissionsDev {
 // road it leads to), the roads of a mission's fixed route, or none.
 #define SMX_ROUTE_FIXED 3
 struct RouteFilter {
-  int n;  // 0 = no filter; 1, 2 = the list road[]; SMX_ROUTE_FIXED = a fixed route: road[0] = the agent slot (row of
-          // MapDev::route_pos / route_lane_ok), road[1] = the route's last road
+  int n;  // 0 = no filter; 1, 2 = the list road[]; SMX_ROUTE_FIXED = a fixed route: road[0] = the agent slot — with a mission pool bound
+          // the pool row (mission_row, smx_tick.h) —, the row of MapDev::route_pos / route_lane_ok; road[1] = the route's last road
   int road[2];
   __device__ __forceinline__ bool has(const MapDev& m, int r) const {
     if (n == SMX_ROUTE_FIXED) return m.route_pos[road[0] * m.n_roads + r] >= 0;
@@ -312,7 +318,7 @@ struct RouteFilter {
     n = 0;
     road[0] = road[1] = -1;
   }
-  // the filter of agent slot `slot`'s mission; false (and no filter) if that mission is endless
+  // the filter of agent slot `slot`'s mission (`slot`: what mission_row gave); false (and no filter) if that mission is endless
   __device__ __forceinline__ bool fixed_route(const MissionsDev& ms, int slot, int n_roads) {
     none();
     if (ms.route_last == nullptr) return false;

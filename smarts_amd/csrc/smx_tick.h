@@ -29,8 +29,8 @@ struct KernelArgs {
   int traj_max;
   const uint8_t* env_mask;  // k_reset: explicit mask (NULL = use env_reset_pending / all)
   const double* lidar_rays;
-  const smx_via* vias;          // device copy of smx_set_vias
-  const int32_t* via_slot_off;  // [num_vehicles + 1]
+  const smx_via* vias;          // device copy of smx_set_vias, or of the vias of smx_set_mission_pool
+  const int32_t* via_slot_off;  // [num_vehicles + 1]; a pool: [missions + 2], read through mission_row
   int first_only;           // restrict to vehicles carrying SMX_F_FIRST (reset observations)
   int keep_reward_done;     // auto-reset: the terminal step's reward / done / env_done stay
   int reset_all;            // k_reset: every env (explicit reset with NULL mask)
@@ -48,7 +48,7 @@ struct KernelArgs {
   // and k_control_fast take their knot lists from it and k_wp_walk is not launched (null: the walked lists)
   const KnotRow* knot_table;
   unsigned long long* knot_served;  // developer (smx_debug_set_knot_table(h, 2)): path lanes k_waypoints_emit served from a row
-  MissionsDev missions;     // device copy of smx_set_missions (null pointers: every mission endless)
+  MissionsDev missions;     // device copy of smx_set_missions or smx_set_mission_pool (null pointers: every mission endless)
   // large batches: the tick's alive vehicles, compacted by k_alive_list at the start of the tick (null: launch
   // index = vehicle).  The per-vehicle team kernels then run over full wavefronts however many agents are gone.
   const int32_t* alive_list;
@@ -92,7 +92,8 @@ struct KernelArgs {
 enum {
   SMX_DEVICE_BAD_LANE_ACTION = 1,  // a Lane action code outside -1..3 was met (and treated as "no action")
   SMX_DEVICE_BAD_TRAJECTORY = 2,   // a TrajectoryWithTime action the reference raises on (it moved nothing)
-  SMX_DEVICE_BAD_TARGET_POSE = 4   // a TargetPose / Imitation action whose pose or speed came out not finite (it moved nothing)
+  SMX_DEVICE_BAD_TARGET_POSE = 4,  // a TargetPose / Imitation action whose pose or speed came out not finite (it moved nothing)
+  SMX_DEVICE_BAD_MISSION_ROW = 8   // an entry outside -1 .. M - 1 in the table of a mission pool was met (and read as -1)
 };
 
 #define SF(field) a.st.f64[(size_t)(field) * total + gid]
@@ -236,13 +237,44 @@ __device__ __forceinline__ PathSeeds load_seeds(const KernelArgs& a, size_t gid,
   return s;
 }
 
+// The mission of vehicle slot `slot` of env `env`, as the index every per-mission table is read with (MissionsDev's
+// tables, RouteFilter::road[0], the via offsets).  No pool bound: the slot itself.  A pool (smx_set_mission_pool): entry
+// [env_episode[env] mod n_rows][env][slot] of the caller's table when it lies in 0 .. n - 1, else n — the endless mission
+// the tables hold behind the pool's — for -1, for a social slot (it has no entry) and for any other value, which is
+// reported by the next smx_sync and never used as an index.  env_episode is read as it stands: every kernel of a tick
+// runs before the tick's commit advances it, every kernel of a reset pass after.  The table is the
+// caller's and may change under a running episode; each site takes what it reads.
+// `pooled` is a literal of the kernel that holds the site: the plan launches the kernels' pool instances (k_*_pool,
+// TickPlan::pool) while a pool is bound and the others otherwise, and in those `pooled` is false and the lookup is not
+// there — every kernel without a pool is the code it was before pools existed, as with ROUTED, SIZED, ENTRY and GUARD.
+// 32-bit index arithmetic: the bind-time check keeps n_rows x E x A below 2^31.  The row of the episode is taken as the
+// spawn, dimension and entry tables take theirs: ((k mod R) + R) mod R.
+__device__ __forceinline__ int mission_row(const KernelArgs& a, int env, int slot, const bool pooled) {
+  if (!pooled) return slot;
+  const MissionsDev& ms = a.missions;
+  const uint32_t n_agents = (uint32_t)(a.cfg.num_vehicles - a.cfg.num_social);
+  if ((uint32_t)slot >= n_agents) return ms.n;
+  const int rows = ms.n_rows;
+  const uint32_t row = (uint32_t)(((a.st.env_episode[env] % rows) + rows) % rows);
+  const int32_t entry = ms.rows[(row * (uint32_t)a.cfg.num_envs + (uint32_t)env) * n_agents + (uint32_t)slot];
+  if ((uint32_t)entry < (uint32_t)ms.n) return entry;
+  if (entry != -1) atomicOr(a.status, SMX_DEVICE_BAD_MISSION_ROW);
+  return ms.n;
+}
+__device__ __forceinline__ int mission_row(const KernelArgs& a, size_t gid, const bool pooled) {
+  const size_t n_veh = (size_t)a.cfg.num_vehicles;
+  if (!pooled) return (int)(gid % n_veh);
+  const uint32_t env = (uint32_t)gid / (uint32_t)n_veh;
+  return mission_row(a, (int)env, (int)((uint32_t)gid - env * (uint32_t)n_veh), true);
+}
+
 // TripMeterSensor.append_waypoint_if_new's should_count_wp (sensors.py:908-913): with a fixed route only waypoints
 // on the route's roads count.  The first waypoint of the first path lies on the seed road: with the waypoints
 // sensor that is one of the route's roads by construction (_waypoint_paths_along_route); without it the path
 // comes from the unrouted lookahead-1 query (sensors.py:271-275), whose start lanepoint is SMX_FI_OBS_START.
-__device__ __forceinline__ bool trip_counts_waypoint(const KernelArgs& a, const MapDev& m, size_t gid, size_t total) {
+__device__ __forceinline__ bool trip_counts_waypoint(const KernelArgs& a, const MapDev& m, size_t gid, size_t total, const bool pooled) {
   RouteFilter f;
-  if (!f.fixed_route(a.missions, (int)(gid % (size_t)a.cfg.num_vehicles), m.n_roads)) return true;
+  if (!f.fixed_route(a.missions, mission_row(a, gid, pooled), m.n_roads)) return true;
   if (a.cfg.sensors & SMX_SENSOR_WAYPOINTS) return true;
   const int os = a.st.facts_i32[(size_t)SMX_FI_OBS_START * total + gid];
   if (os < 0) return true;  // no waypoint this tick anyway

@@ -301,6 +301,76 @@ def check_agent_entry(num_envs: int, num_vehicles: int, num_social: int, ready_t
         raise ValueError(err.value.decode())
 
 
+def _mission_pool_struct(cm: CompiledMap, missions: Sequence, vias: Optional[Sequence[Sequence]]):
+    """``smx_mission_pool`` of a pool of ``PlannedMission | None`` and the via list of each (host side; the caller adds the
+    table of rows), with the arrays it points into."""
+    M = len(missions)
+    if vias is not None and len(vias) != M:
+        raise ValueError("mission pool: one via list per pool entry")
+    road_no = {rid: i for i, rid in enumerate(cm.road_ids)}
+    recs = (nat.SmxMission * max(M, 1))()
+    goals = (nat.SmxMissionGoal * max(M, 1))()
+    roads = []
+    for s, m in enumerate(missions):
+        if m is None:
+            continue
+        recs[s].goal_x, recs[s].goal_y, recs[s].goal_radius = m.goal
+        recs[s].route_off, recs[s].route_len = len(roads), len(m.route_roads)
+        roads += [road_no[r] for r in m.route_roads]
+        kind = getattr(m, "goal_kind", nat.GOAL_POSITIONAL)
+        goals[s].kind, goals[s].num_laps, goals[s].route_length = kind, int(m.num_laps), float(m.route_length)
+    road_arr = (C.c_int32 * max(len(roads), 1))(*roads)
+    keep = [recs, goals, road_arr]
+    mp = nat.SmxMissionPool()
+    mp.missions_host, mp.n_missions = C.addressof(recs), M
+    mp.route_roads_host, mp.n_route_roads = C.addressof(road_arr), len(roads)
+    if any(goals[s].kind != nat.GOAL_POSITIONAL for s in range(M)):
+        mp.goals_host = C.addressof(goals)
+        if any(goals[s].kind == nat.GOAL_TRAVERSE for s in range(M)):
+            from .missions import lane_end_tables
+
+            h, d = lane_end_tables(cm)  # the two lane facts of TraverseGoal: host libm
+            h, d = np.ascontiguousarray(h, dtype=np.float64), np.ascontiguousarray(d, dtype=np.int32)
+            mp.lane_end_heading_host, mp.lane_dead_end_host, mp.n_lanes = h.ctypes.data, d.ctypes.data, len(h)
+            keep += [h, d]
+    flat = [v for lst in (vias or []) for v in lst]
+    if flat:
+        vrecs = (nat.SmxVia * len(flat))()
+        for i, v in enumerate(flat):
+            vrecs[i].x, vrecs[i].y = v.position
+            vrecs[i].hit_distance, vrecs[i].required_speed, vrecs[i].lane = v.hit_distance, v.required_speed, v.lane
+        offs = (C.c_int32 * (M + 1))(*np.concatenate([[0], np.cumsum([len(lst) for lst in vias])]).astype(int).tolist())
+        mp.vias_host, mp.via_off_host, mp.n_vias = C.addressof(vrecs), C.addressof(offs), len(flat)
+        keep += [vrecs, offs]
+    return mp, keep
+
+
+def check_mission_pool(cm: CompiledMap, num_envs: int, num_vehicles: int, num_social: int, missions: Sequence,
+                       vias: Optional[Sequence[Sequence]] = None, rows: Optional[np.ndarray] = None, via_max: int = 0) -> None:
+    """``smx_check_mission_pool``: would ``smx_set_mission_pool`` take this pool — ``PlannedMission | None`` entries, a via
+    list per entry — and a table of rows of the shape of ``rows`` (host int32 ``(R, E, A)``; ``None``: one row) for a
+    shard of this shape on map ``cm``?  The host copy of the table is checked here as well: every entry in -1 .. M - 1
+    (on the device such an entry is read as -1 and reported by the next ``sync``).  Needs the built library, no device
+    and no handle; raises ``ValueError`` with the reason when not."""
+    lib = nat.load_library()
+    E, A = int(num_envs), int(num_vehicles) - int(num_social)
+    table = np.full((1, E, max(A, 0)), -1, dtype=np.int32) if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+    if table.ndim != 3 or table.shape[0] < 1 or tuple(table.shape[1:]) != (E, A):
+        raise ValueError(f"mission rows must be int32 of shape (R, {E}, {A}), got {tuple(table.shape)}")
+    c = nat.SmxConfig()
+    c.num_envs, c.num_vehicles, c.num_social, c.via_max = E, int(num_vehicles), int(num_social), int(via_max)
+    mp, keep = _mission_pool_struct(cm, missions, vias)
+    mp.rows_dev, mp.rows_count, mp.rows = table.ctypes.data, int(table.size), int(table.shape[0])  # (only tested for NULL)
+    tables, keep_map = map_tables_struct(cm)
+    err = C.create_string_buffer(512)
+    rc = lib.smx_check_mission_pool(C.byref(c), C.byref(tables), C.byref(mp), err, len(err))
+    del keep, keep_map
+    if rc != 0:
+        raise ValueError(err.value.decode())
+    if table.size and (table.min() < -1 or table.max() >= len(missions)):
+        raise ValueError(f"mission rows: entries must lie in -1 .. {len(missions) - 1}")
+
+
 def _agent_entry_tables(ready_ticks, check, num_envs: int, num_agents: int) -> Tuple[np.ndarray, np.ndarray]:
     ready = np.ascontiguousarray(ready_ticks, dtype=np.int32)
     chk = np.ascontiguousarray(check, dtype=np.float64)
@@ -405,6 +475,7 @@ class BatchedSim:
             offs = (C.c_int32 * (N + 1))(*np.concatenate([[0], np.cumsum([len(lst) for lst in self.vias])]).astype(int).tolist())
             nat.check(self.lib, self.handle, self.lib.smx_set_vias(self.handle, recs, len(flat), offs), "smx_set_vias")
         self.missions = None
+        self.mission_pool = self.mission_rows = None  # set_mission_pool
         if missions is not None:
             self.set_missions(missions)
         if cfg.lidar is not None:
@@ -661,6 +732,37 @@ class BatchedSim:
                 keep = (h, d)  # noqa: F841 (alive across the call)
             nat.check(self.lib, self.handle, self.lib.smx_set_mission_goals(self.handle, goals, N, heading, dead_end, n_lanes),
                       "smx_set_mission_goals")
+
+    def set_mission_pool(self, missions: Optional[Sequence], vias: Optional[Sequence[Sequence]] = None,
+                         rows: Optional[torch.Tensor] = None):
+        """Bind a mission pool (``smx_set_mission_pool``): missions per env and per episode.  ``missions``: a sequence of
+        ``PlannedMission | None`` (``None``: an endless mission), at most ``MISSION_POOL_MAX``; ``vias``: per pool entry a
+        list of ``vias.ResolvedVia`` (needs ``SimConfig(via_max > 0)``); ``rows``: int32 ``(R, E, A)`` on the sim's device,
+        ``A = N - num_social`` — agent ``a`` of env ``e`` has mission ``rows[k mod R, e, a]`` in episode ``k``, ``-1`` = an
+        endless mission without vias.  The tensor stays the caller's and is read by every pass wherever a mission is
+        needed: rewriting the row of a running episode changes that agent's mission in the middle of the episode; rows of
+        episodes that have not started may be rewritten freely (a curriculum sampled on the device).  An entry outside
+        ``-1 .. len(missions) - 1`` is read as ``-1`` and makes the next ``sync()`` raise.  The finishing tick of an
+        episode reads the old episode's row, the first observation of the next one — a restart under ``auto_reset``
+        included — the new one's.  Binding drops what ``set_missions`` and the constructor's ``vias`` bound, and while a
+        pool is bound ``set_missions`` raises; ``set_mission_pool(None)`` unbinds (every mission endless again).  A shard
+        of a larger batch binds its own slice ``rows[:, first_env:first_env + E]`` (contiguous), like every per-env
+        table."""
+        if missions is None:
+            nat.check(self.lib, self.handle, self.lib.smx_set_mission_pool(self.handle, None), "smx_set_mission_pool")
+            self.mission_pool = self.mission_rows = None
+            return
+        want = (self.E, self.N - self.cfg.num_social)
+        if (rows is None or rows.dtype != torch.int32 or rows.device != self.device or not rows.is_contiguous() or rows.ndim != 3
+                or rows.shape[0] < 1 or tuple(rows.shape[1:]) != want):
+            raise ValueError(f"rows must be a contiguous int32 tensor of shape [R, {want[0]}, {want[1]}] on {self.device}")
+        mp, keep = _mission_pool_struct(self.cm, missions, vias)
+        mp.rows_dev, mp.rows_count, mp.rows = rows.data_ptr(), int(rows.numel()), int(rows.shape[0])
+        nat.check(self.lib, self.handle, self.lib.smx_set_mission_pool(self.handle, C.byref(mp)), "smx_set_mission_pool")
+        del keep
+        # (the library reads the tensor in every pass: it lives as long as the binding)
+        self.mission_pool, self.mission_rows = (list(missions), [list(v) for v in vias] if vias is not None else None), rows
+        self.missions = self.vias = None
 
     def bind_rgb(self, images: Optional[torch.Tensor]):
         """Bind the image buffer of the RGB sensor (``smx_set_rgb_output``): uint8 [E, N, rgb_height, rgb_width, 3] on

@@ -176,8 +176,17 @@ class BatchCore:
                  missions: Optional[Dict[str, Any]] = None, spawns: str = "reference", shuffle_scenarios: bool = True,
                  ego_centric: bool = False, state_guard: bool = False,
                  state_guard_margin: float = nat.GUARD_MARGIN_DEFAULT, traffic_history=None, history_start_frames=None,
-                 history_dims: bool = False, agent_dims: Optional[Dict[str, Sequence]] = None):
-        """``agent_dims``: ``{agent id: (length, width, height)}``, the agent's own vehicle dimensions
+                 history_dims: bool = False, agent_dims: Optional[Dict[str, Sequence]] = None, mission_schedule=None):
+        """``missions``: ``{agent id: mission}`` — or ``{agent id: [mission, ...]}``: the scenario's variations
+        (scenario.py:206-227, 292-294).  All lists have one common length V, a single mission is repeated, and variation
+        ``j`` gives every agent of an env its ``j``-th mission.  ``mission_schedule``: int ``(R, E)`` (or ``(R,)``) of
+        variation numbers, episode ``k`` of env ``e`` runs ``schedule[k mod R, e]``; ``None``: every env cycles through
+        the variations, rolled per env when ``shuffle_scenarios`` is set (``missions.mission_schedule``).  With a list
+        anywhere the missions go to the device as a pool (``BatchedSim.set_mission_pool``): the agents' spawn rows,
+        routes, goals and the ``mission`` of their observations are the variation's, also across an auto-reset.
+        Variations of one agent that differ in ``start_time`` or ``entry_tactic`` are refused.  With no list nothing
+        changes and no pool is bound.
+        ``agent_dims``: ``{agent id: (length, width, height)}``, the agent's own vehicle dimensions
         (``BatchedSim.set_agent_dims``; the reference's ``Vehicle.agent_vehicle_dims``): a component that is ``None``, 0
         or -1 takes the passenger default (``Dimensions.copy_with_defaults``), agents it lacks stay sedans.  The agent's
         start is placed from the front bumper with its own length, its events, ``ego_vehicle_state.bounding_box`` and
@@ -253,7 +262,25 @@ class BatchCore:
                                  f"an agent of ActionSpaceType.{self.cfg.action_space} drives the sedan its dynamics model describes")
             self.agent_dims = {a: resolve_dimensions(2, *agent_dims[a]) for a in agent_dims}  # 2: passenger
             own_length = [self.agent_dims[a][0] if a in self.agent_dims else None for a in self.agent_ids]
-        spawns, where = make_spawns(self.cm, num_envs, self.N + num_social, episodes=4, seed=seed, return_lanes=True)
+        # mission variations (missions.mission_variations): the schedule first — spawn row (episode mod S) must be the
+        # start of the mission of table row (episode mod R), so the spawn table gets a multiple of R rows
+        self.mission_variations = self.mission_schedule = None
+        if missions and any(isinstance(m, (list, tuple)) for m in missions.values()):
+            from ..missions import _entry_of, mission_schedule as default_schedule, mission_variations
+
+            self.mission_variations = mission_variations(missions, self.agent_ids)
+            self.mission_schedule = default_schedule(len(self.mission_variations), num_envs, seed, shuffle_scenarios, mission_schedule)
+            for i, a in enumerate(self.agent_ids):
+                if len({_entry_of(v[i]) for v in self.mission_variations}) > 1:
+                    raise NotImplementedError(f"agent {a!r}: its mission variations differ in start_time / entry_tactic; the "
+                                              "delayed-entry table is built for one entry per agent")
+        elif mission_schedule is not None:
+            raise ValueError("mission_schedule needs missions with a list of variations")
+        spawn_rows = 4
+        if self.mission_schedule is not None:
+            R = self.mission_schedule.shape[0]
+            spawn_rows = R * -(-4 // R)
+        spawns, where = make_spawns(self.cm, num_envs, self.N + num_social, episodes=spawn_rows, seed=seed, return_lanes=True)
         if spawn_mode == "reference":
             from ..missions import reference_spawn_table
             from ..sumo_map import load_net
@@ -276,7 +303,21 @@ class BatchCore:
         # (Scenario._extract_mission + Plan.create_route), the agent's spawn rows become the mission's start in every
         # env and episode — for every kind, the ones with an empty route included
         self.missions = None
-        if missions:
+        self.planned_variations = None
+        if self.mission_variations is not None:
+            from ..missions import plan_mission
+            from ..sumo_map import load_net
+
+            net = load_net(self.scenario_dir)
+            self.planned_variations = [[plan_mission(net, m) if m is not None else None for m in v] for v in self.mission_variations]
+            from ..missions import mission_spawn_poses
+
+            slots = self.N + num_social
+            poses = mission_spawn_poses(self.planned_variations, self.mission_schedule, spawns.shape[0], own_length)
+            table = spawns.reshape(spawns.shape[0], num_envs, slots, 4)[:, :, :self.N]
+            given = ~np.isnan(poses[..., 0])
+            table[given, :3], table[given, 3] = poses[given], 0.0
+        elif missions:
             from ..missions import plan_mission
             from ..sumo_map import load_net
 
@@ -295,7 +336,29 @@ class BatchCore:
         # delayed entry (Mission.start_time / entry_tactic, smarts_amd.missions.entry_table): bound only when the agents'
         # fire steps differ; then the reset observation is the earliest agent's and the others enter inside a tick
         self.entry = None
-        if missions:
+        if self.mission_variations is not None:
+            # one entry per agent (checked above), the start point it keeps clear per row: the variation's
+            from ..missions import EntryTable, entry_table
+
+            dims_rows = None
+            if self.agent_dims:
+                dims_rows = np.full((1, num_envs, self.N, 3), np.nan, dtype=np.float64)
+                for i, a in enumerate(self.agent_ids):
+                    if a in self.agent_dims:
+                        dims_rows[0, :, i] = self.agent_dims[a]
+            per = [entry_table(v, p, num_envs, dt, dims_rows) for v, p in zip(self.mission_variations, self.planned_variations)]
+            if per[0].differs:
+                sched = self.mission_schedule
+                ready = np.repeat(per[0].ready, sched.shape[0], axis=0)
+                check = np.stack([np.stack([per[sched[k, e]].check[0, e] for e in range(num_envs)]) for k in range(sched.shape[0])])
+                self.entry = EntryTable(np.ascontiguousarray(ready), np.ascontiguousarray(check), per[0].reset_steps, per[0].steps,
+                                        per[0].entry_speed)
+                self.cfg.entry_reset_steps = per[0].reset_steps
+                slots = self.N + num_social
+                for i, speed in enumerate(per[0].entry_speed):
+                    if speed is not None:
+                        spawns.reshape(spawns.shape[0], num_envs, slots, 4)[:, :, i, 3] = speed
+        elif missions:
             from ..missions import entry_table
 
             dims_rows = None
@@ -312,8 +375,20 @@ class BatchCore:
                 for i, speed in enumerate(table.entry_speed):
                     if speed is not None:  # TrapEntryTactic.default_entry_speed: the new vehicle's speed
                         spawns.reshape(spawns.shape[0], num_envs, slots, 4)[:, :, i, 3] = speed
+        pooled = self.planned_variations is not None
         self.sim = BatchedSim(self.cm, self.cfg, device=device, spawns=spawns, seed=seed, social_spawns=where,
-                              vias=self.vias, missions=self.missions)
+                              vias=None if pooled else self.vias, missions=self.missions)
+        if pooled:
+            import torch
+
+            from ..missions import mission_pool_rows
+
+            # the pool variation by variation: entry j * N + a is agent a's mission in variation j, with the agent's vias
+            pool = [m for v in self.planned_variations for m in v]
+            pool_vias = [list(self.vias[i]) for _ in self.planned_variations for i in range(self.N)] if self.vias else None
+            rows = mission_pool_rows(self.planned_variations, self.mission_schedule,
+                                     [bool(self.vias[i]) for i in range(self.N)] if self.vias else None)
+            self.sim.set_mission_pool(pool, pool_vias, torch.from_numpy(rows).to(self.sim.device))
         if self.agent_dims:
             table = np.full((1, num_envs, self.N, 3), np.nan, dtype=np.float64)
             for i, a in enumerate(self.agent_ids):
@@ -355,6 +430,15 @@ class BatchCore:
             lidar_rays=base_rays(first.lidar.sensor_params) if first.lidar else None, dt=dt, vias=self.vias,
             road_waypoints=bool(first.road_waypoints), missions=self.missions, rgb=first.rgb or None,
             history=self.traffic_history)
+        # one name table per variation: the `mission` of an observation is the one its env flies in that episode
+        self.builders = None
+        if pooled:
+            self.builders = [ObservationBuilder(
+                self.cm.lane_ids, road_ids, vehicle_names, waypoints=self.cfg.waypoints, neighbors=self.cfg.neighbors,
+                accelerometer=self.cfg.accelerometer, ogm=first.ogm or None, dagm=first.drivable_area_grid_map or None,
+                lidar_rays=self.builder.lidar_rays, dt=dt, vias=self.vias, road_waypoints=bool(first.road_waypoints),
+                missions=list(v) + [None] * num_social, rgb=first.rgb or None, history=self.traffic_history)
+                for v in self.planned_variations]
         self._was_reset = False
         self._destroyed = False
 
@@ -494,9 +578,20 @@ class BatchCore:
             start = self.sim.history_start_frames.cpu().numpy().astype(np.int64)
             episode = self.sim.env_episode.cpu().numpy().astype(np.int64)
             rows["history_frame"] = start[episode % start.shape[0], np.arange(self.E)] + rows["env_ticks"]
+        if self.builders is not None:
+            # the variation every env flies now, and the one of the episode before (the finishing tick of a restart)
+            episode = self.sim.env_episode.cpu().numpy().astype(np.int64)
+            sched, envs = self.mission_schedule, np.arange(self.E)
+            rows["mission_variation"] = sched[episode % sched.shape[0], envs]
+            rows["mission_variation_before"] = sched[(episode - 1) % sched.shape[0], envs]
         return rows
 
-    PER_ENV_ROWS = ("env_done", "env_ticks", "history_frame")  # [E]; every other row is [E, N, ...]
+    PER_ENV_ROWS = ("env_done", "env_ticks", "history_frame", "mission_variation", "mission_variation_before")  # [E]; every other row is [E, N, ...]
+
+    def _builder(self, rows, env: int, before: bool = False):
+        if self.builders is None:
+            return self.builder
+        return self.builders[int(rows["mission_variation_before" if before else "mission_variation"][env])]
 
     def observations(self, rows: Dict[str, np.ndarray], env: int, present: np.ndarray) -> Dict[str, Observation]:
         er = {k: v[env] for k, v in rows.items() if k not in self.PER_ENV_ROWS}
@@ -504,7 +599,8 @@ class BatchCore:
             er["history_frame"] = int(rows["history_frame"][env])
         t = int(rows["env_ticks"][env])  # device clock: already that of the new episode after an auto-reset
         elapsed = round(t * self.dt, 6)
-        return {self.agent_ids[i]: self.builder.build(er, i, t, elapsed) for i in range(self.N) if present[i]}
+        builder = self._builder(rows, env)
+        return {self.agent_ids[i]: builder.build(er, i, t, elapsed) for i in range(self.N) if present[i]}
 
     def final_observations(self, rows: Dict[str, np.ndarray], env: int, present: np.ndarray, step_count: int) -> Dict[str, Observation]:
         """The finishing tick's observation of the agents of an env that restarted inside the launch
@@ -514,7 +610,8 @@ class BatchCore:
         for k in ("ego_pos", "ego_f32", "ego_lane", "events", "dist"):
             er[k] = rows["final_" + k][env]
         elapsed = round(step_count * self.dt, 6)
-        return {self.agent_ids[i]: self.builder.build(er, i, step_count, elapsed, low_dimensional=True)
+        builder = self._builder(rows, env, before=True)
+        return {self.agent_ids[i]: builder.build(er, i, step_count, elapsed, low_dimensional=True)
                 for i in range(self.N) if present[i]}
 
     def close(self):

@@ -54,6 +54,7 @@ class HiWayEnv:
         history_start_frames=None,
         history_dims: bool = False,
         agent_dims: Optional[Dict[str, Sequence]] = None,
+        mission_schedule: Optional[Sequence[int]] = None,
     ):
         self._log = logging.getLogger(self.__class__.__name__)
         if not headless or envision_record_data_replay_path or envision_endpoint:
@@ -111,6 +112,10 @@ class HiWayEnv:
             raise ValueError("history_start_frames needs traffic_history")
         self._history_start_frames = None if history_start_frames is None else \
             [int(v) for v in np.atleast_1d(np.asarray(history_start_frames)).reshape(-1)]
+        # mission variations (missions = {agent id: [mission, ...]}, BatchCore): the variation number of this env's episode
+        # k is mission_schedule[k mod R]; None = the variations one after another (rolled when shuffle_scenarios is set)
+        self._mission_schedule = None if mission_schedule is None else \
+            [int(v) for v in np.atleast_1d(np.asarray(mission_schedule)).reshape(-1)]
         # the agents' own vehicle dimensions, {agent id: (length, width, height)} (BatchCore; kinematic action spaces only)
         self._agent_dims = {a: tuple(v) for a, v in agent_dims.items()} if agent_dims else None
         self._dones_registered = 0
@@ -147,7 +152,7 @@ class HiWayEnv:
                 self._spawns, self._shuffle_scenarios, self._state_guard, self._state_guard_margin,
                 self._traffic_history if isinstance(self._traffic_history, (str, type(None))) else id(self._traffic_history),
                 None if self._history_start_frames is None else len(self._history_start_frames), self._history_dims,
-                repr(self._agent_dims))
+                repr(self._agent_dims), None if self._mission_schedule is None else len(self._mission_schedule))
 
     def seed(self, seed: int) -> int:
         """hiway_env.py:204-214.  Takes effect at the next ``reset`` that (re)builds the spawn table."""
@@ -171,6 +176,8 @@ class HiWayEnv:
                                    state_guard=self._state_guard, state_guard_margin=self._state_guard_margin,
                                    traffic_history=self._traffic_history, history_dims=self._history_dims,
                                    agent_dims=self._agent_dims,
+                                   mission_schedule=None if self._mission_schedule is None
+                                   else np.asarray(self._mission_schedule, dtype=np.int32).reshape(-1, 1),
                                    history_start_frames=None if self._history_start_frames is None
                                    else np.asarray(self._history_start_frames, dtype=np.int32).reshape(-1, 1))
         return self._core

@@ -45,6 +45,9 @@ class ParallelEnv:
         starts = [e._history_start_frames for e in envs]
         self._history_start_frames = None if starts[0] is None else np.asarray(starts, dtype=np.int32).T
         self._history_dims = self._proto._history_dims  # (part of the envs' signature: they agree on it)
+        # every env runs its own cycle of mission variations: column e holds env e's schedule (equal lengths: the signature)
+        schedules = [e._mission_schedule for e in envs]
+        self._mission_schedule = None if schedules[0] is None else np.asarray(schedules, dtype=np.int32).T
         self._num_envs = len(envs)
         self._auto_reset = auto_reset
         self._device = device
@@ -73,7 +76,8 @@ class ParallelEnv:
                                spawns=p._spawns, shuffle_scenarios=p._shuffle_scenarios,
                                state_guard=p._state_guard, state_guard_margin=p._state_guard_margin,
                                traffic_history=p._traffic_history, history_start_frames=self._history_start_frames,
-                               history_dims=self._history_dims, agent_dims=p._agent_dims)
+                               history_dims=self._history_dims, agent_dims=p._agent_dims,
+                               mission_schedule=self._mission_schedule)
         self._seed = seed
         return [seed + i for i in range(self._num_envs)]
 

@@ -585,3 +585,83 @@ def entry_table(missions: Sequence, planned: Sequence[Optional[PlannedMission]],
             has = ~np.isnan(own[..., 0])
             check[:, :, a, 2] = np.where(has, np.maximum(own[..., 0], own[..., 1]), check[:, :, a, 2])
     return EntryTable(ready, check, first, steps, tuple(speed for _, _, speed in entries))
+
+
+# ---- mission variations (scenario.py:206-227, 292-294: a scenario's missions are handed out as variations, one per
+# reset; BatchedSim.set_mission_pool holds them on the device)
+def mission_variations(missions: Dict[str, object], agent_ids: Sequence[str]) -> List[List[object]]:
+    """``missions``: ``{agent_id: mission | [mission, ...]}``.  A list is the agent's missions over the scenario's
+    variations; all lists have one common length V, and a single mission is repeated.  Returns V lists, one per
+    variation: the mission of every agent of ``agent_ids`` (``None``: the agent has none)."""
+    unknown = set(missions) - set(agent_ids)
+    if unknown:
+        raise ValueError(f"missions for unknown agents: {sorted(unknown)}")
+    lengths = {a: len(m) for a, m in missions.items() if isinstance(m, (list, tuple))}
+    if any(n < 1 for n in lengths.values()):
+        raise ValueError(f"missions: an empty list of variations ({sorted(a for a, n in lengths.items() if n < 1)})")
+    if len(set(lengths.values())) > 1:
+        raise ValueError(f"missions: the lists of variations must have one common length, got {dict(sorted(lengths.items()))}")
+    V = next(iter(lengths.values()), 1)
+    out = []
+    for j in range(V):
+        out.append([(missions[a][j] if a in lengths else missions[a]) if a in missions else None for a in agent_ids])
+    return out
+
+
+def mission_schedule(num_variations: int, num_envs: int, seed: Optional[int] = 0, shuffle_scenarios: bool = False,
+                     schedule=None) -> np.ndarray:
+    """int32 ``(R, E)``: the variation env ``e`` runs in episode ``k`` is ``schedule[k mod R, e]``.  Default: R = V and
+    every env cycles 0, 1, ..., V - 1 (``Scenario.scenario_variations`` + ``HiWayEnv.reset``); with ``shuffle_scenarios``
+    env ``e``'s cycle is rolled by an offset drawn from ``PCG64(seed + e)`` (the reference rolls by the unseeded global
+    ``random``, scenario.py:211-215).  An explicit ``schedule`` ``(R, E)`` or ``(R,)`` is checked and returned."""
+    V, E = int(num_variations), int(num_envs)
+    if V < 1 or E < 1:
+        raise ValueError("mission_schedule: at least one variation and one env")
+    if schedule is not None:
+        s = np.asarray(schedule)
+        if s.ndim == 1:
+            s = np.repeat(s[:, None], E, axis=1)
+        if s.ndim != 2 or s.shape[0] < 1 or s.shape[1] != E or not np.issubdtype(s.dtype, np.integer):
+            raise ValueError(f"mission_schedule must be an integer array of shape (R, {E}) or (R,), got {tuple(np.shape(schedule))}")
+        if s.min() < 0 or s.max() >= V:
+            raise ValueError(f"mission_schedule: variation numbers must lie in 0 .. {V - 1}")
+        return np.ascontiguousarray(s, dtype=np.int32)
+    offset = np.zeros(E, dtype=np.int64)
+    if shuffle_scenarios:
+        base = 0 if seed is None else int(seed)
+        offset = np.array([int(np.random.Generator(np.random.PCG64(base + e)).integers(V)) for e in range(E)], dtype=np.int64)
+    return ((np.arange(V)[:, None] + offset[None, :]) % V).astype(np.int32)
+
+
+def mission_pool_rows(planned: Sequence[Sequence[Optional[PlannedMission]]], schedule: np.ndarray,
+                      has_vias: Optional[Sequence[bool]] = None) -> np.ndarray:
+    """The table of rows of ``BatchedSim.set_mission_pool`` for a pool laid out variation by variation — entry
+    ``j * A + a`` is agent ``a``'s mission in variation ``j`` —: int32 ``(R, E, A)``, -1 where the agent has neither a
+    mission nor vias.  ``has_vias[a]``: agent ``a`` has via points; they ride with its pool entries, so an agent with
+    vias and no mission points at its (endless) entry — -1 names the entry behind the pool, which has no vias."""
+    A = len(planned[0])
+    has = np.array([[m is not None for m in row] for row in planned])            # (V, A)
+    if has_vias is not None:
+        has = has | np.asarray(has_vias, dtype=bool)[None, :]
+    index = np.arange(len(planned))[:, None] * A + np.arange(A)[None, :]           # (V, A)
+    return np.ascontiguousarray(np.where(has, index, -1)[schedule], dtype=np.int32)  # (R, E, A)
+
+
+def mission_spawn_poses(planned: Sequence[Sequence[Optional[PlannedMission]]], schedule: np.ndarray, spawn_rows: int,
+                        lengths: Optional[Sequence[Optional[float]]] = None) -> np.ndarray:
+    """float64 ``(spawn_rows, E, A, 3)``: x, y, heading of the vehicle centre at the start of the mission agent ``a`` of
+    env ``e`` flies in the episodes of spawn row ``s`` — variation ``schedule[s mod R, e]`` —, NaN where it has none.
+    ``spawn_rows`` is a multiple of R, so that spawn row (episode mod spawn_rows) and table row (episode mod R) name the
+    same variation.  ``lengths``: the agents' own lengths (``None``: the sedan's), ``PlannedMission.spawn_pose``."""
+    R, E = schedule.shape
+    if spawn_rows % R != 0:
+        raise ValueError(f"mission_spawn_poses: {spawn_rows} spawn rows are not a multiple of the schedule's {R}")
+    A = len(planned[0])
+    out = np.full((spawn_rows, E, A, 3), np.nan, dtype=np.float64)
+    for s in range(spawn_rows):
+        for e in range(E):
+            for a, m in enumerate(planned[int(schedule[s % R, e])]):
+                if m is not None:
+                    own = lengths[a] if lengths is not None else None
+                    out[s, e, a] = m.spawn_pose() if own is None else m.spawn_pose(own)
+    return out
