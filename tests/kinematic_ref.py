@@ -1,7 +1,7 @@
 """CPU restatement of the kinematic action spaces (TargetPose, TrajectoryWithTime) and of BoxChassis' read-back, in
-plain Python floats: what k_control_kinematic and the kinematic ego read-back of the observe role compute
-(smarts_amd/csrc/smx_kernels.hip), operation by operation.  Test infrastructure; held to the reference's own outputs
-(tests/golden/kinematic_*.npz) by tests/test_kinematic_cpu.py."""
+plain Python floats: what k_control_kinematic (smarts_amd/csrc/smx_k_control.h) and the kinematic ego read-back of the
+observe role (smarts_amd/csrc/smx_k_observe.h) compute, operation by operation.  Test infrastructure; held to the
+reference's own outputs (tests/golden/kinematic_*.npz) by tests/test_kinematic_cpu.py."""
 import math
 
 TWO_PI = 2 * math.pi

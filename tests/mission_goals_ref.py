@@ -1,6 +1,6 @@
-"""CPU restatement of the two goal tests beyond PositionalGoal, in plain Python floats: what ``lap_goal_gate`` and
-``drove_off_map`` compute (smarts_amd/csrc/smx_kernels.hip), operation by operation.  Test infrastructure; held to the
-reference's own outputs (tests/golden/mission_goals_*.npz) by tests/test_mission_goals.py."""
+"""CPU restatement of the two goal tests beyond PositionalGoal, in plain Python floats: what ``lap_goal_gate``
+(smarts_amd/csrc/smx_k_pass.h) and ``drove_off_map`` (smarts_amd/csrc/smx_k_observe.h) compute, operation by operation.
+Test infrastructure; held to the reference's own outputs (tests/golden/mission_goals_*.npz) by tests/test_mission_goals.py."""
 import math
 
 TWO_PI = 2 * math.pi

@@ -425,7 +425,8 @@ def test_release_library_has_no_debug_switches():
 
 
 # the headers cut out of the kernels' file: smx_tick.h first, the phase headers (smx_k_*.h) follow it
-CUT_HEADERS = ["smx_tick.h", "smx_k_scan.h", "smx_k_grids.h", "smx_k_lidar.h", "smx_k_control.h", "smx_k_waypoints.h"]
+CUT_HEADERS = ["smx_tick.h", "smx_k_scan.h", "smx_k_grids.h", "smx_k_lidar.h", "smx_k_control.h", "smx_k_waypoints.h",
+               "smx_k_rows.h", "smx_k_observe.h", "smx_k_pass.h"]
 # what smx_tick.h took out of smx_kernels.hip (more than one phase uses each)
 # (team_or(int) moved there too, with team_exclusive_prefix and team_nearest, but is not listed: the pattern below cannot
 # tell it from smx_scan.h's template <int TEAM> team_or, which stays where it is)
@@ -456,10 +457,10 @@ def test_every_header_compiles_on_its_own():
     """Each header under csrc/ has #pragma once and includes what it uses: the device headers pass hipcc's syntax check
     for gfx950 alone, the host-only ones g++'s.  No header cut out of the kernels' file is longer than smx_scan.h, the
     longest header before the cutting began.  What smx_tick.h took is defined there and in no other file under csrc/,
-    and it holds no kernel: a __global__ lies in a phase header (smx_k_*.h) or, still, in smx_kernels.hip.
-    (The cut is staged, DESIGN.md §9: while smx_kernels.hip still holds phases it holds __global__ and __device__;
-    the change that moves the last phase into its smx_k_*.h replaces the TICK_DEFINITIONS check by "smx_kernels.hip
-    contains neither word outside comments".)"""
+    and it holds no kernel: a __global__ lies in a phase header (smx_k_*.h) only.  The cut is finished:
+    smx_kernels.hip is the C-ABI and the launch code, and holds none of __global__, __device__, __shared__ and
+    __launch_bounds__ outside comments.  The includes point one way: smx_k_rows.h and smx_k_observe.h include no phase
+    header, and no phase header includes smx_k_pass.h, which strings the roles together."""
     import subprocess
     from concurrent.futures import ThreadPoolExecutor
 
@@ -490,7 +491,13 @@ def test_every_header_compiles_on_its_own():
     sources = {f: code(f) for f in sorted(os.listdir(csrc))}
     tick = sources["smx_tick.h"]
     assert "__global__" not in tick
-    assert all(f == "smx_kernels.hip" or f.startswith("smx_k_") for f, text in sources.items() if "__global__" in text)
+    assert all(f.startswith("smx_k_") and f.endswith(".h") for f, text in sources.items() if "__global__" in text)
+    for word in ("__global__", "__device__", "__shared__", "__launch_bounds__"):
+        assert word not in sources["smx_kernels.hip"], word
+    included = {f: set(re.findall(r'#include "(smx_\w+\.h)"', text)) for f, text in sources.items()}
+    for h in ("smx_k_rows.h", "smx_k_observe.h"):
+        assert not [inc for inc in included[h] if inc.startswith("smx_k_")], (h, included[h])
+    assert not [f for f, incs in included.items() if f.startswith("smx_k_") and "smx_k_pass.h" in incs]
     for name in TICK_DEFINITIONS:
         head = r"^(struct (__align__\(\d+\) )?%s \{|__device__ [^;{]*\b%s\()" % (name, name)
         elsewhere = [f for f, text in sources.items() if f != "smx_tick.h" and re.search(head, text, re.M)]

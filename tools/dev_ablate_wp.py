@@ -5,7 +5,7 @@
 
 builds smarts_amd/libsmarts_mi355x_ab<mask>.so for every mask (here, on the CPU box, before gpurun) when called
 with --build, and times them on the GPU otherwise.  Bits: the SMX_SKIP(...) sites of smx_kernels.hip
-and of the phase headers cut out of it (smx_k_control.h, smx_k_scan.h and smx_k_waypoints.h so far; the macro itself: smx_tick.h)."""
+and of the phase headers cut out of it (smx_k_control.h, smx_k_scan.h, smx_k_waypoints.h and smx_k_observe.h; the macro itself: smx_tick.h)."""
 import os, sys, subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
